@@ -10,8 +10,9 @@ calculate_ray_collions call (wgsl:353), counted exactly on the device; the
 segments whose hit is taken from the per-pixel primary-ray memo (no traversal)
 are counted too and `Mrays_traversed/s` is reported beside the headline.
 
-The window of K frames between two fences (barrier + synchronize) is timed `--repeats` times (default 5, each window
-continuing the accumulation): `ms_per_step` and `value` are the MEDIAN window's, `timing` carries min / max / every window.
+The timed region is EXACTLY K = `--steps` frames between two fences (barrier + synchronize).  `--repeats R` times R such
+windows instead (each continuing the accumulation): `ms_per_step` and `value` are then the MEDIAN window's, `timing` carries
+min / max / every window.
 A window renders its K frames with rt_render_frames: frames are sampled in
 batches (default 32 per launch) by ONE persistent launch over (frame, tile) work
 items and blended in frame order by a dense second kernel -- bit-identical to K
@@ -38,6 +39,12 @@ Launch: `python bench.py --gpus N` starts its own N ranks (one child process
 per GPU through torch.distributed.run, before this process touches the GPU);
 under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
 
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the accumulated frame a caller reads back
+(rt_read_image; N > 1: the assembled frame on rank 0) -- as DIR/image.npy, float32 (H, W, 4), right after the timed
+region.  The inputs are fixed (committed scene, frame index as seed), so equal arguments give equal inputs and two
+builds can be compared output for output.  A frame above 64 MB is written as a fixed, seeded sample of its pixels
+(image.npy, (n, 4)) with their row-major indices (pixel_index.npy, float64).
+
 Prints one JSON line on rank 0 (contract in the task statement), with
 `roofline` (compulsory HBM bytes per launch / measured launch time against the
 8 TB/s peak -- this path is VALU-bound, so the fraction is small by
@@ -54,12 +61,27 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# (before anything initialises the HIP runtime: the library's pipelined frames want a hardware queue per stream, see
-# ray_tracer_2_amd/__init__.py; a setting of the caller's wins)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# (the hardware queue count is the caller's environment: nothing here raises it, see ray_tracer_2_amd/__init__.py)
 
 WIDTH, HEIGHT, SPP, BOUNCES = 1920, 1080, 8, 4
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the frame as path/image.npy (float32, as computed); above DUMP_LIMIT_BYTES a fixed, seeded sample of
+    its pixels instead, with their row-major indices as path/pixel_index.npy (float64: exact for any pixel count)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    image = np.ascontiguousarray(image, np.float32)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(path, "image.npy"), image)
+        return
+    pixels = image.reshape(-1, image.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 4096) // (pixels.itemsize * pixels.shape[1] + 8)   # (sample + index + two .npy headers)
+    index = np.sort(np.random.default_rng(0).choice(pixels.shape[0], n, replace=False))
+    np.save(os.path.join(path, "image.npy"), pixels[index])
+    np.save(os.path.join(path, "pixel_index.npy"), index.astype(np.float64))
 
 
 def cpu_baseline(rt, arrays):
@@ -196,7 +218,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=32)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the window of --steps frames is timed (ms_per_step = the median window)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="how many windows of --steps frames are timed (default 1: exactly --steps timed steps; ms_per_step = the median window)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the un-overlapped / first-frame measurements")
     ap.add_argument("--no-per-frame-leg", action="store_true",
@@ -209,6 +232,8 @@ def main():
                     help="do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc); use the committed profile")
     ap.add_argument("--variant", type=int, default=None, help="kernel variant (tuning; default: library default)")
     ap.add_argument("--blocks", type=int, default=None, help="persistent grid size (tuning)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the timed path computed in its last step to DIR/image.npy (float32)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -331,9 +356,9 @@ def main():
 
     render(0, args.warmup)
     fence()
-    # The timed region: EXACTLY `steps` frames between two fences -- and that window `repeats` times over (default 5, each
-    # continuing the accumulation), because one window of 20 frames is 23 ms of wall time: one sample.  ms_per_step / value
-    # are the MEDIAN window's (N > 1: of the windows' max-over-ranks times); min / max go into the line beside it.
+    # The timed region: EXACTLY `steps` frames between two fences -- or, with --repeats R, R such windows (each continuing
+    # the accumulation: one window of 20 frames is 23 ms of wall time, one sample).  ms_per_step / value are the MEDIAN
+    # window's (N > 1: of the windows' max-over-ranks times); min / max go into the line beside it.
     windows = []
     for w_i in range(max(1, args.repeats)):
         tracer.reset_timing()
@@ -344,6 +369,9 @@ def main():
         st = tracer.stats()
         windows.append((dt, float(st.segments), float(st.segments_reused), st.kernel_ms / max(st.launches, 1), st.frames / max(st.launches, 1)))
     frames_done = args.warmup + max(1, args.repeats) * args.steps
+    if args.dump_outputs and rank == 0:
+        # (outside the timed region, before anything renders another frame into the image)
+        dump_outputs(args.dump_outputs, tracer.read_image(W, H) if world == 1 else frame.cpu().numpy().reshape(H, W, 4))
 
     if world > 1 and rank == 0 and os.environ.get("RT2_BENCH_VERIFY"):
         # the stitched frame must equal the single-GPU frame (same frames sequence)
@@ -635,7 +663,7 @@ def main():
             "value_definition": f"value = rays of {args.steps} frames / wall time with {frames_per_launch:g} frames per launch "
                                 "(intermediate frames of a batch are not observable); value_per_frame_launch = the same frames "
                                 "with one launch" + (" and one gather" if world > 1 else "") + " per frame, every frame observable, timed "
-                                "right after (N = 1: consecutive launches pipelined across internal streams, four frames in flight, option pipeline; "
+                                "right after (N = 1: consecutive launches pipelined across internal streams, option pipeline at its automatic depth; "
                                 "ms_per_frame_unoverlapped = the same with the pipeline off = a frame's latency; N >= 2: a call that continues "
                                 "the accumulation renders the next frames of the rank's small share with its own and the following calls blend "
                                 "theirs, option frame_ahead -- every call still leaves its frame in the image, and the gather is per frame)",

@@ -8,7 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE_ASSETS = "/root/reference/assets"  # absent on the GPU box
+# the upstream project's data files the tests load through the scene library (CornellBox-Original.obj/.mtl,
+# earthmap.png, and dragon.obj xz-compressed), stored verbatim as fixtures
+ASSETS = os.path.join(GOLDEN, "assets")
 
 
 def pytest_configure(config):
@@ -35,11 +37,6 @@ def oracle():
 def cornell(rt):
     """CornellBox-Original scene arrays from the committed fixture."""
     return rt.SceneArrays.load(os.path.join(GOLDEN, "cornell_scene.npz"))
-
-
-@pytest.fixture(scope="session")
-def have_reference_assets():
-    return os.path.isdir(REFERENCE_ASSETS)
 
 
 @pytest.fixture(scope="session")

@@ -87,7 +87,8 @@ def test_max_device_mb_bounds_the_optional_allocations(rt, cornell, cap_mb):
 
 def test_a_pipeline_deeper_than_the_hardware_queues_is_said_once(rt, cornell):
     import os
-    queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+    runtime_default = 4   # (what the HIP runtime takes when the variable is unset)
+    queues = int(os.environ.get("GPU_MAX_HW_QUEUES") or runtime_default)
     t = rt.RayTracer(device=0, max_width=256, max_height=144)
     try:
         t.load_scene(cornell)

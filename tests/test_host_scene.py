@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE_ASSETS, ROOT, bits
+from conftest import ASSETS, GOLDEN, ROOT, bits
 
 DATA = os.path.join(ROOT, "tests", "data")
 
@@ -47,9 +47,8 @@ def test_negative_indices_are_relative(rt):
     assert np.all(zs == 1.0)   # `f -3//1 -2//1 -1//1` addressed the three z = 1 vertices
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ASSETS), reason="reference assets not present")
 def test_cornell_from_assets_matches_fixture_and_survey(rt):
-    sc = rt.Scene.from_name("cornell_box", REFERENCE_ASSETS)
+    sc = rt.Scene.from_name("cornell_box", ASSETS)
     arr = rt.SceneArrays.from_scene(sc)
     fix = rt.SceneArrays.load(os.path.join(GOLDEN, "cornell_scene.npz"))
     assert arr.meshes.tobytes() == fix.meshes.tobytes()
@@ -79,10 +78,9 @@ def test_cornell_fixture_facts(cornell):
     assert np.all(cornell.meshes["model_to_world"] == np.eye(4, dtype=np.float32))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ASSETS), reason="reference assets not present")
 def test_loader_against_python_oracle(rt):
     from oracle import host_oracle as ho
-    models, mats, pos, tex, nrm = ho.load_obj(os.path.join(REFERENCE_ASSETS, "CornellBox-Original.obj"))
+    models, mats, pos, tex, nrm = ho.load_obj(os.path.join(ASSETS, "CornellBox-Original.obj"))
     assert [m["name"] for m in models] == ["floor", "ceiling", "backWall", "rightWall", "leftWall", "leftWall", "shortBox", "light"]
     fix = rt.SceneArrays.load(os.path.join(GOLDEN, "cornell_scene.npz"))
     for i, model in enumerate(models):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One launch per frame on rank 0's share of the config-2 frame for world = 1, 2, 4, 8 (measured on one GPU): wall time per
-frame against the frames in flight (option pipeline).   GPU_MAX_HW_QUEUES=16 python tools/strip_pipeline_depth.py"""
+frame against the frames in flight (option pipeline), on the hardware queues the environment allows."""
 import os
 import statistics
 import sys

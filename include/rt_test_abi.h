@@ -29,6 +29,23 @@ int rt_test_sweep(rt_handle* h, int which, uint64_t* out3);
 int rt_test_device_sample_texture(rt_handle* h, const rt_texture_desc* tex, const float* uv, float* rgba_out,
                                   uint64_t n);
 
+/* Test-only: the kernels' ray-scene intersection (intersect_scene) for n host-given rays on the uploaded scene, one lane
+ * per ray, with the arguments a render launches and the instantiation it would take -- unless `flags` force the general
+ * (RT_TEST_ISECT_GENERAL) or the SIMPLE one (RT_TEST_ISECT_SIMPLE: refused with RT_ERR_INVALID_ARGUMENT on a many-mesh scene
+ * or one with spheres, glass or textures); RT_TEST_ISECT_STATS takes the counter instantiation.  A ray whose `active`
+ * byte is 0 (active may be NULL: all rays) is not traced and its record stays zero.  Rays must be finite with a non-zero
+ * direction (else RT_ERR_INVALID_ARGUMENT), n <= RT_TEST_ISECT_MAX_RAYS.  Record per ray, RT_TEST_ISECT_WORDS u32 words:
+ * hit, dst, point xyz, normal xyz, u, v (floats as bits), backface, the winner (mesh index, or number of meshes + sphere
+ * index; 0xffffffff on a miss), node tests, triangle tests (counter instantiation only), the instantiation that ran (1
+ * many-mesh, 2 SIMPLE as in rt_last_launch out[3]; 32 counters, 64 scene in LDS), 0. */
+#define RT_TEST_ISECT_WORDS 16
+#define RT_TEST_ISECT_MAX_RAYS (1ull << 24)
+#define RT_TEST_ISECT_GENERAL 1
+#define RT_TEST_ISECT_STATS 2
+#define RT_TEST_ISECT_SIMPLE 4
+int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint8_t* active, uint64_t n, int flags,
+                      uint32_t* out);
+
 /* Test-only: raw copy of a buffer of the last wavefront sequence (which: 0 path state, 1 hit records, 2 the two slot
  * lists, 3 the per-round list counts; layouts in csrc/rt_device.h), or (which = 4) the pixels parked in front of each round
  * of the last deferred-walk sequence (72 u32), or (which = 5, 6) the park records of its even / odd rounds. */

@@ -162,6 +162,64 @@ def mat_point(m, v, w):   # (mat4 * vec4(v, w)).xyz, m[col][row]
     return v[:, 0:1] * m[0, :3] + v[:, 1:2] * m[1, :3] + v[:, 2:3] * m[2, :3] + w * m[3, :3]
 
 
+# Ray-triangle tests are evaluated for blocks of rays x triangles of at most this many pairs (memory stays bounded: the
+# dragon stand-in's 78 k triangles against 10^5 rays would be 10^10 doubles per array at once).
+PAIRS_PER_BLOCK = 1 << 21
+TRIS_PER_CHUNK = 256
+
+
+def _chunk_bounds(m):
+    """Bounding spheres of consecutive runs of TRIS_PER_CHUNK triangles (the leaf order keeps a run compact): centre, and
+    a radius enlarged by 1 % + 1e-6 of the mesh's scale so that no triangle a test below can count as (nearly) hit is
+    outside it."""
+    if "chunks" not in m:
+        nt = m["v1"].shape[0]
+        scale = max(float(np.abs(np.concatenate([m["v1"], m["v2"], m["v3"]])).max(initial=0.0)), 1e-30)
+        out = []
+        for a in range(0, nt, TRIS_PER_CHUNK):
+            b = min(nt, a + TRIS_PER_CHUNK)
+            pts = np.concatenate([m["v1"][a:b], m["v2"][a:b], m["v3"][a:b]])
+            c = 0.5 * (pts.min(0) + pts.max(0))
+            rad = np.sqrt(((pts - c) ** 2).sum(-1).max())
+            out.append((a, b, c, rad * 1.01 + 1e-6 * scale))
+        m["chunks"] = out
+    return m["chunks"]
+
+
+def _triangle_chunks(m, lo, ld):
+    """ray_triangle :258-290 of every (ray, triangle) pair that can matter, in blocks: yields (ray rows, triangle indices,
+    dict of (rows, triangles) arrays keep / det / dst / u / v / w / nrm_len / eab_len / eac_len).  A block holds the rays
+    whose half-line passes within a run's bounding sphere (all others miss every triangle of the run, with room to spare);
+    the triangles come in increasing index order."""
+    for a, b, c, rad in _chunk_bounds(m):
+        oc = c - lo
+        t = np.maximum(dot(oc, ld), 0.0)
+        near = np.sqrt(np.maximum(dot(oc, oc) - 2.0 * t * dot(oc, ld) + t * t, 0.0))
+        rows_all = np.flatnonzero(near <= rad)
+        if rows_all.size == 0:
+            continue
+        tris = np.arange(a, b)
+        step = max(1, PAIRS_PER_BLOCK // tris.size)
+        for s0 in range(0, rows_all.size, step):
+            rows = rows_all[s0:s0 + step]
+            v1 = m["v1"][a:b]
+            eab, eac = m["v2"][a:b] - v1, m["v3"][a:b] - v1        # :261-262
+            nrm = np.cross(eab, eac)                                # :263
+            l0, d0 = lo[rows], ld[rows]
+            ao = l0[:, None, :] - v1[None, :, :]                    # :264
+            dao = np.cross(ao, d0[:, None, :])                      # :265
+            det = -(d0[:, None, :] * nrm[None]).sum(-1)             # :266
+            keep = (np.abs(det) >= 1e-8) if m["glass"] else (det >= 1e-8)   # :268 (cull_backface = not glass, :375)
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                inv = 1.0 / det
+                dst = (ao * nrm[None]).sum(-1) * inv
+                u = (eac[None] * dao).sum(-1) * inv
+                v = -(eab[None] * dao).sum(-1) * inv
+            w = 1.0 - u - v
+            yield rows, tris, dict(keep=keep, det=det, dst=dst, u=u, v=v, w=w, nrm_len=np.sqrt(dot(nrm, nrm))[None, :],
+                                   eab_len=np.sqrt(dot(eab, eab))[None, :], eac_len=np.sqrt(dot(eac, eac))[None, :])
+
+
 def closest_hit(scene, ro, rd):
     """calculate_ray_collions :353-396: ray_sphere :223-256 over the spheres, then ray_triangle :258-290 over ALL triangles
     of every mesh.  Returns hit mask, world distance, world hit point, world normal, uv, material index, backface."""
@@ -202,27 +260,26 @@ def closest_hit(scene, ro, rd):
         uv = np.where(better[:, None], suv, uv)
         which = np.where(better, scene.n_meshes + si, which)
         backface = np.where(better, inside, backface)
+    r = np.arange(n)
     for mi, m in enumerate(scene.meshes):
         lo = mat_point(m["w2m"], ro, 1.0)                  # :371
         ld = normalize(mat_point(m["w2m"], rd, 0.0))       # :372
-        eab, eac = m["v2"] - m["v1"], m["v3"] - m["v1"]    # :261-262
-        nrm = np.cross(eab, eac)                           # :263
-        ao = lo[:, None, :] - m["v1"][None, :, :]          # :264
-        dao = np.cross(ao, ld[:, None, :])                 # :265
-        det = -(ld[:, None, :] * nrm[None]).sum(-1)        # :266
-        keep = (np.abs(det) >= 1e-8) if m["glass"] else (det >= 1e-8)   # :268 (cull_backface = not glass, :375)
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            inv = 1.0 / det
-            dst = (ao * nrm[None]).sum(-1) * inv
-            u = (eac[None] * dao).sum(-1) * inv
-            v = -(eab[None] * dao).sum(-1) * inv
-        w = 1.0 - u - v
-        ok = keep & (dst > EPSILON) & (u >= 0.0) & (v >= 0.0) & (w >= 0.0)   # :280
-        t = np.where(ok, dst, np.inf)
-        k = t.argmin(1)                                    # closest triangle of the mesh (ray_BVH keeps strictly closer hits)
-        r = np.arange(n)
-        mesh_hit = np.isfinite(t[r, k])
-        tk, uk, vk, wk, dk = t[r, k], u[r, k], v[r, k], w[r, k], det[r, k]
+        # the closest triangle of the mesh (ray_BVH keeps strictly closer hits): the first minimum in triangle order,
+        # gathered chunk by chunk (a later chunk wins only when strictly closer)
+        tk = np.full(n, np.inf)
+        k = np.zeros(n, np.int64)
+        uk, vk, wk, dk = np.zeros(n), np.zeros(n), np.zeros(n), np.ones(n)
+        for rows, tris, c in _triangle_chunks(m, lo, ld):
+            ok = c["keep"] & (c["dst"] > EPSILON) & (c["u"] >= 0.0) & (c["v"] >= 0.0) & (c["w"] >= 0.0)   # :280
+            t = np.where(ok, c["dst"], np.inf)
+            j = t.argmin(1)
+            rj = np.arange(rows.size)
+            closer = t[rj, j] < tk[rows]
+            sel = rows[closer]
+            tk[sel] = t[rj, j][closer]
+            k[sel] = tris[j[closer]]
+            uk[sel], vk[sel], wk[sel], dk[sel] = (c[q][rj, j][closer] for q in ("u", "v", "w", "det"))
+        mesh_hit = np.isfinite(tk)
         ln = normalize(m["n1"][k] * wk[:, None] + m["n2"][k] * uk[:, None] + m["n3"][k] * vk[:, None]) * np.sign(dk)[:, None]   # :282
         luv = m["uv1"][k] * wk[:, None] + m["uv2"][k] * uk[:, None] + m["uv3"][k] * vk[:, None]
         lhp = lo + ld * np.where(mesh_hit, tk, 0.0)[:, None]      # :379
@@ -238,6 +295,155 @@ def closest_hit(scene, ro, rd):
         which = np.where(better, mi, which)
         backface = np.where(better, dk < 0.0, backface)           # :283
     return hit, best, point, normal, uv, which, backface
+
+
+# ---- when may binary32 legitimately disagree with this file? ------------------------------------------------------------
+U32 = 2.0 ** -24     # binary32 unit roundoff
+C_LOCAL = 32.0       # local-space budget, in units of U32 * scale (see ambiguity)
+C_WORLD = 64.0       # world-distance budget, in units of U32 * (scale + distance) * condition of the transform
+
+
+def ambiguity(scene, ro, rd):
+    """Per ray, how far the float64 decisions of closest_hit are from flipping under binary32 arithmetic: each margin is
+    |quantity - threshold| / tolerance, so a margin below 1 means binary32 may legitimately decide the other way.
+    Returns a dict of per-ray arrays (+inf where nothing is in reach):
+
+      bary    min |smallest barycentric| of the winning triangle and of every triangle (nearly) hit within reach
+      det     min ||det| - 1e-8| of those triangles (the cull threshold, wgsl:268)
+      eps     min |dst - EPSILON| of those triangles (wgsl:280)
+      gap     relative gap between the best and the second-best world distance over every primitive (nearly) hit,
+              two triangles of one mesh included
+      disc    min |discriminant| of the spheres (nearly) hit within reach (wgsl:235)
+      far     min |far - 0.001| of those spheres (wgsl:239), and of dst_near against 0 (the inside test, wgsl:240)
+      ambiguous   any margin < 1
+      dst_tol, uv_tol, normal_tol   how far binary32's distance (and hit point), uv and world normal of the winner may
+              stray: for a triangle its distance's tolerance below and its barycentrics' tolerance times the change of
+              the attribute across the triangle (a small triangle far from the origin has barycentrics good to
+              ~ u |ao| / size, and an interpolated normal that turns fast across it carries that into the normal); for a
+              sphere its distance's tolerance, carried into the normal by 1 / radius and into uv by the derivatives of
+              acos / atan2 (1 at the seam of atan2, where u jumps from 0 to 1)
+
+    The tolerances are first-order bounds of binary32's error, with the scene's coordinate scale S (per mesh and ray: the
+    largest |component| of the local origin and of the mesh's vertices) and u = 2^-24:
+      * the local ray: lo = W ro + c carries <= 4u (|W| |ro| + |c|) <= 4u S per component, ld = normalize(W rd) <= 6u;
+        ao = lo - v1 adds u |ao|, cross(ao, ld) 2u |ao|, a 3-term dot 3u: every numerator of wgsl:266-278 (dot(ao, n),
+        dot(eac, dao), dot(eab, dao), all bounded by |e| |ao| or |n| |ao|, |ao| <= 2S) is good to <= 16u S |e| (|n| for the
+        distance), doubled for the neglected higher-order terms: C_LOCAL = 32;
+      * det = -dot(ld, n): n = cross(eab, eac) is exact up to 3u |n| (edges of binary32 vertices, rounded once), the dot 3u,
+        ld 6u: |det| good to 12u |n| (<= C_LOCAL u |n| used);
+      * u, v = numerator / det: absolute tolerance (C_LOCAL u S |e| + |u| C_LOCAL u |n|) / |det| -- grazing rays (small |det|)
+        get wide margins, as they should; w = (1 - u) - v the sum of both; dst likewise with |n| for |e|;
+      * world distances: M lhp + m and the norm add <= 8u (|M| (S + t) + |m|) relative to the condition of the transform:
+        tolerance C_WORLD u kappa (S_world + d), S_world = largest |component| of ro and of the world hit point;
+      * spheres: b^2 - 4ac is good to 8u (b^2 + |4ac|) (operands first rounded to 2u (|oc|^2 + r^2)), dst_far and dst_near
+        to C_LOCAL u (|oc| + r) (plus the square root's share of the discriminant's error, within the disc margin).
+    A triangle is "nearly hit" when every test of wgsl:268-280 passes within its tolerance, and it is "within reach" when its
+    world distance is at most the best one plus the world tolerance: exactly the triangles whose outcome binary32 may
+    decide differently and still compete for the closest hit."""
+    n = ro.shape[0]
+    inf = np.full(n, np.inf)
+    out = {k: inf.copy() for k in ("bary", "det", "eps", "gap", "disc", "far")}
+    out["dst_tol"], out["uv_tol"], out["normal_tol"] = np.zeros(n), np.zeros(n), np.zeros(n)
+    hit, best, _p, _n, _uv, which, _bf = closest_hit(scene, ro, rd)
+    sw = np.maximum(np.abs(ro).max(-1), np.where(hit, np.abs(_p).max(-1), 0.0))
+    # every primitive's world distance when (nearly) hit, to find the runner-up: (ray, distance, tolerance)
+    cand_r, cand_d, cand_t = [], [], []
+    for si in range(scene.sphere_pos.shape[0]):
+        oc = ro - scene.sphere_pos[si]
+        rr = scene.sphere_radius[si]
+        a = dot(rd, rd)
+        b = 2.0 * dot(oc, rd)
+        c = dot(oc, oc) - rr ** 2
+        disc = b * b - 4.0 * a * c
+        tol_disc = 8.0 * U32 * (b * b + np.abs(4.0 * a * c)) + 8.0 * U32 * (dot(oc, oc) + rr ** 2) * np.abs(b)
+        sq = np.sqrt(np.maximum(disc, 0.0))
+        near = (-b - sq) / (2.0 * a)
+        far = (-b + sq) / (2.0 * a)
+        tol_t = C_LOCAL * U32 * (np.sqrt(dot(oc, oc)) + rr) + np.sqrt(np.maximum(tol_disc, 0.0)) / (2.0 * a)
+        nearly = (disc >= -tol_disc) & (far >= 0.001 - tol_t)
+        dst = np.where(np.maximum(0.0, near) == 0.0, far, np.maximum(0.0, near))
+        tol_w = C_WORLD * U32 * (sw + np.abs(dst))
+        reach = nearly & (dst <= best + tol_w)
+        out["disc"] = np.where(reach, np.minimum(out["disc"], np.abs(disc) / np.maximum(tol_disc, 1e-300)), out["disc"])
+        m_far = np.minimum(np.abs(far - 0.001), np.abs(near)) / tol_t
+        out["far"] = np.where(reach, np.minimum(out["far"], m_far), out["far"])
+        won = hit & (which == scene.n_meshes + si) & (dst == best)
+        if won.any():
+            hp = ro[won] + rd[won] * dst[won][:, None]
+            nrm = normalize(hp - scene.sphere_pos[si])
+            t_n = 2.0 * (tol_t[won] + C_LOCAL * U32 * (np.abs(hp).max(-1) + np.abs(scene.sphere_pos[si]).max())) / rr
+            rho = np.sqrt(nrm[:, 0] ** 2 + nrm[:, 2] ** 2)
+            seam = (np.abs(nrm[:, 2]) <= t_n) & (nrm[:, 0] > 0.0)
+            out["dst_tol"][won] = tol_t[won]
+            out["normal_tol"][won] = t_n
+            out["uv_tol"][won] = np.where(seam, 1.0, t_n * (1.5 / PI) / np.maximum(rho, 1e-300))
+        cand_r.append(np.flatnonzero(reach))
+        cand_d.append(dst[reach])
+        cand_t.append(tol_w[reach])
+    for mi, m in enumerate(scene.meshes):
+        lo = mat_point(m["w2m"], ro, 1.0)
+        ld = normalize(mat_point(m["w2m"], rd, 0.0))
+        a3 = m["m2w"][:3, :3]
+        kappa = max(1.0, float(np.linalg.norm(a3, 2) * np.linalg.norm(np.linalg.inv(a3), 2)))
+        sv = float(np.abs(np.concatenate([m["v1"], m["v2"], m["v3"]])).max(initial=0.0))
+        smax = np.maximum(np.abs(lo).max(-1), sv)
+        for rows, _tris, c in _triangle_chunks(m, lo, ld):
+            S = smax[rows][:, None]
+            e = np.maximum(c["eab_len"], c["eac_len"])
+            adet = np.maximum(np.abs(c["det"]), 1e-300)
+            tol_det = np.broadcast_to(C_LOCAL * U32 * c["nrm_len"], c["det"].shape)
+            tol_b = (C_LOCAL * U32 * S * e + C_LOCAL * U32 * c["nrm_len"]) / adet
+            tol_d = (C_LOCAL * U32 * S * c["nrm_len"] + np.abs(c["dst"]) * C_LOCAL * U32 * c["nrm_len"]) / adet
+            det_ok = (np.abs(c["det"]) if m["glass"] else c["det"]) >= 1e-8 - tol_det
+            bmin = np.minimum(np.minimum(c["u"], c["v"]), c["w"])
+            with np.errstate(invalid="ignore"):
+                nearly = det_ok & (bmin >= -2.0 * tol_b) & (c["dst"] > EPSILON - tol_d) & np.isfinite(c["dst"])
+            if not nearly.any():
+                continue
+            ri, ti = np.nonzero(nearly)
+            rows_i = rows[ri]
+            t = c["dst"][ri, ti]
+            lhp = lo[rows_i] + ld[rows_i] * t[:, None]
+            whp = mat_point(m["m2w"], lhp, 1.0)
+            wd = np.sqrt(dot(ro[rows_i] - whp, ro[rows_i] - whp))
+            tol_w = C_WORLD * U32 * kappa * (sw[rows_i] + wd) + kappa * tol_d[ri, ti]
+            reach = wd <= best[rows_i] + tol_w
+            ri, ti, rows_i, wd, tol_w = ri[reach], ti[reach], rows_i[reach], wd[reach], tol_w[reach]
+            won = (which[rows_i] == mi) & (wd == best[rows_i])   # the winning triangle (closest_hit's arithmetic)
+            if won.any():
+                wr, wt, tb = rows_i[won], _tris[ti[won]], 2.0 * tol_b[ri[won], ti[won]]
+                du = np.abs(m["uv2"][wt] - m["uv1"][wt]).max(-1) + np.abs(m["uv3"][wt] - m["uv1"][wt]).max(-1)
+                n1, n2, n3 = m["n1"][wt], m["n2"][wt], m["n3"][wt]
+                uu, vv = c["u"][ri[won], ti[won]], c["v"][ri[won], ti[won]]
+                ni = np.sqrt(dot(*(2 * [n1 * (1.0 - uu - vv)[:, None] + n2 * uu[:, None] + n3 * vv[:, None]])))
+                dn = (np.sqrt(dot(n2 - n1, n2 - n1)) + np.sqrt(dot(n3 - n1, n3 - n1))) / np.maximum(ni, 1e-300)
+                out["dst_tol"][wr] = tol_w[won]
+                out["uv_tol"][wr] = tb * du
+                out["normal_tol"][wr] = tb * dn * kappa
+            mb = np.abs(bmin[ri, ti]) / (2.0 * tol_b[ri, ti])
+            ad = np.abs(np.abs(c["det"][ri, ti]) if m["glass"] else c["det"][ri, ti])
+            md = np.abs(ad - 1e-8) / tol_det[ri, ti]
+            me = np.abs(c["dst"][ri, ti] - EPSILON) / tol_d[ri, ti]
+            np.minimum.at(out["bary"], rows_i, mb)
+            np.minimum.at(out["det"], rows_i, md)
+            np.minimum.at(out["eps"], rows_i, me)
+            cand_r.append(rows_i)
+            cand_d.append(wd)
+            cand_t.append(tol_w)
+    if cand_r:
+        r = np.concatenate(cand_r)
+        d = np.concatenate(cand_d)
+        tw = np.concatenate(cand_t)
+        order = np.lexsort((d, r))
+        r, d, tw = r[order], d[order], tw[order]
+        first = np.r_[True, r[1:] != r[:-1]]
+        second = np.r_[False, ~first[1:]] & np.r_[False, first[:-1]]   # the runner-up of each ray
+        idx2 = np.flatnonzero(second)
+        out["gap"][r[idx2]] = (d[idx2] - d[idx2 - 1]) / (tw[idx2] + tw[idx2 - 1])
+    out["ambiguous"] = np.zeros(n, bool)
+    for k in ("bary", "det", "eps", "gap", "disc", "far"):
+        out["ambiguous"] |= out[k] < 1.0
+    return out
 
 
 def refract(I, N, eta):   # WGSL builtin

@@ -38,6 +38,7 @@ def load():
         L.oracle_rand.restype = C.c_float
         L.oracle_rand.argtypes = [C.POINTER(C.c_uint32)]
         L.oracle_hardware_threads.restype = C.c_int
+        L.oracle_intersect.restype = C.c_int
         _lib = L
     return _lib
 
@@ -95,6 +96,22 @@ def trace_pixel(params, arrays, x, y, cap=64):
     n = L.oracle_trace_pixel(C.byref(params), *_scene_args(arrays), C.c_uint32(x), C.c_uint32(y), rgba,
                              C.c_void_p(rec.ctypes.data), C.c_uint32(cap))
     return np.array(rgba, dtype=np.float32), rec[:n]
+
+
+def intersect(arrays, ro, rd):
+    """calculate_ray_collions (wgsl:353-396) per ray (ro[i], rd[i]), rd used as given: the (n, 16) u32 records of the
+    kernels' per-ray probe (include/rt_test_abi.h, rt_test_intersect), with the shader's BVH test counts."""
+    L = load()
+    ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+    rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
+    assert ro.shape == rd.shape
+    out = np.zeros((ro.shape[0], 16), np.uint32)
+    rc = L.oracle_intersect(C.byref(arrays.uniform), C.c_void_p(arrays.spheres.ctypes.data),
+                            C.c_void_p(arrays.meshes.ctypes.data), C.c_void_p(arrays.triangles.ctypes.data),
+                            C.c_void_p(arrays.nodes.ctypes.data), C.c_void_p(ro.ctypes.data), C.c_void_p(rd.ctypes.data),
+                            C.c_uint64(ro.shape[0]), C.c_void_p(out.ctypes.data))
+    assert rc == 0
+    return out
 
 
 def max_stack_index(reset=True):

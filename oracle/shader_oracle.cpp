@@ -676,6 +676,42 @@ int oracle_trace_pixel(const rt_params* params, const rt_scene_uniform* scene, c
     return (int)tb.n;
 }
 
+// calculate_ray_collions (wgsl:353-396) for n given rays, with its BVH test counts: the record of the kernels' per-ray
+// probe (include/rt_test_abi.h, rt_test_intersect; 16 u32 words per ray), instantiation word 0.
+int oracle_intersect(const rt_scene_uniform* scene, const rt_sphere* spheres, const rt_mesh_uniform* meshes,
+                     const rt_packed_triangle* triangles, const rt_node* nodes, const float* ro, const float* rd,
+                     uint64_t n, uint32_t* out) {
+    if (!scene || (n && (!ro || !rd || !out))) return -1;
+    orc::Ctx c{};
+    c.scene = *scene;
+    c.spheres = spheres;
+    c.meshes = meshes;
+    c.triangles = triangles;
+    c.nodes = nodes;
+    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
+    for (uint64_t i = 0; i < n; ++i) {
+        orc::Ray ray;
+        ray.origin = orc::vec3{ro[3 * i], ro[3 * i + 1], ro[3 * i + 2]};
+        ray.dir = orc::vec3{rd[3 * i], rd[3 * i + 1], rd[3 * i + 2]};
+        int32_t st[2] = {0, 0};
+        const orc::Hit h = orc::calculate_ray_collions(c, ray, st);
+        uint32_t* r = out + i * 16u;
+        r[0] = h.hit ? 1u : 0u;
+        r[1] = bits(h.dst);
+        r[2] = bits(h.hit_point.x); r[3] = bits(h.hit_point.y); r[4] = bits(h.hit_point.z);
+        r[5] = bits(h.normal.x); r[6] = bits(h.normal.y); r[7] = bits(h.normal.z);
+        r[8] = bits(h.uv.x);
+        r[9] = bits(h.uv.y);
+        r[10] = h.backface ? 1u : 0u;
+        r[11] = !h.hit ? 0xffffffffu : h.mesh >= 0 ? (uint32_t)h.mesh : scene->meshes + (uint32_t)(-2 - h.mesh);
+        r[12] = (uint32_t)st[0];
+        r[13] = (uint32_t)st[1];
+        r[14] = 0u;
+        r[15] = 0u;
+    }
+    return 0;
+}
+
 // Largest stack_index ray_BVH reached on the calling thread since the last reset (> 32 means
 // the shader's 32-entry stack overflowed and index clamping took effect).
 uint32_t oracle_max_stack_index(int reset) {

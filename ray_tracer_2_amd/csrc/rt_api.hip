@@ -43,6 +43,8 @@ size_t wf_walk_lds_bytes(const RenderArgs& a);
 #if RT_TEST_ENTRIES
 hipError_t launch_units(int fn, const float* x, const float* y, float* out, unsigned long long n, hipStream_t stream);
 hipError_t launch_sweep(int which, unsigned long long* out, hipStream_t stream);
+hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const float* rd, const uint8_t* active,
+                                 unsigned long long n, bool simple, bool stats, uint32_t* out, hipStream_t stream);
 hipError_t launch_units_texture(const uint8_t* rgba8, uint32_t width, uint32_t height, const float* srgb_lut, const float* uv,
                                 float* out, unsigned long long n, hipStream_t stream);
 #endif
@@ -1408,6 +1410,39 @@ static int wavefront_prepare(rt_handle*, const rt_params*, const RenderArgs&, ui
 static int wavefront_run(rt_handle*, const RenderArgs&, const WavefrontPlan&) { return RT_OK; }
 #endif
 
+// The scene- and option-dependent part of a launch's arguments: the scene, its item list and stack sizing, and which
+// instantiation the kernels take (scene in LDS, many-mesh, SIMPLE).  render_impl launches with these, and so does the
+// test library's per-ray probe (rt_test_intersect), which therefore walks exactly what a render walks.
+static void scene_args(const rt_handle* h, RenderArgs& a) {
+    a.blob = h->blob;
+    a.lay = h->lay;
+    // (an explicitly requested deferred-walk sequence -- option "sort_rounds" > 0, tests -- reads the scene in place: the
+    // parking instantiations exist for global-memory scenes only; the automatic setting never defers a mesh of a scene
+    // that fits the LDS)
+    a.lds_scene = (h->lds_scene && !h->force_global && !(h->sort_rounds > 0 && h->have_defer)) ? 1u : 0u;
+    a.cull_roots = (h->roots_are_unions && (h->cull_roots == 1 || (h->cull_roots < 0 && h->n_meshes >= 16))) ? 1u : 0u;
+    a.many_mesh = (h->has_tlas || (a.cull_roots && !h->has_forest)) ? 1u : 0u;
+    a.forest_cull = h->cull_roots != 0 ? 1u : 0u;
+    a.cross_prune = h->cross_prune != 0 ? 1u : 0u;
+    {
+        uint32_t ds, dv;
+        memcpy(&ds, &h->camera.defocus_strength, 4);
+        memcpy(&dv, &h->camera.diverge_strength, 4);
+        a.simple = (h->specialise && h->plain_materials && ds == 0u && dv == 0u) ? 1u : 0u;  // (both strengths +0)
+    }
+    a.textures = h->textures;
+    a.srgb_lut = h->srgb_lut;
+    a.n_meshes = h->n_meshes;
+    a.n_spheres = h->n_spheres;
+    a.n_textures = h->n_textures;
+    a.stack_entries = h->stack_entries;
+    a.tlas_entries = h->tlas_entries;
+    a.stack_wide = (h->stack_must_wide || (h->force_stack_wide < 0 ? h->stack_wide : h->force_stack_wide != 0)) ? 1u : 0u;
+    // (the global-memory kernels park a pending mesh hit of 5 dwords in the stack column, intersect_scene)
+    if (!a.lds_scene && a.stack_entries < (a.stack_wide ? 3u : 5u)) a.stack_entries = a.stack_wide ? 3u : 5u;
+    a.n_items = h->n_items;
+}
+
 static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uint32_t world, uint32_t n_batch = 0,
                        bool blend_later = false) {
     if (!h || !params) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
@@ -1477,36 +1512,10 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
         const int32_t n = params->rays_per_pixel;
         a.spp_reciprocal = (n > 0 && (n & (n - 1)) == 0) ? 1.0f / (float)n : 0.0f;
     }
-    a.blob = h->blob;
-    a.lay = h->lay;
-    // (an explicitly requested deferred-walk sequence -- option "sort_rounds" > 0, tests -- reads the scene in place: the
-    // parking instantiations exist for global-memory scenes only; the automatic setting never defers a mesh of a scene
-    // that fits the LDS)
-    a.lds_scene = (h->lds_scene && !h->force_global && !(h->sort_rounds > 0 && h->have_defer)) ? 1u : 0u;
-    a.cull_roots = (h->roots_are_unions && (h->cull_roots == 1 || (h->cull_roots < 0 && h->n_meshes >= 16))) ? 1u : 0u;
-    a.many_mesh = (h->has_tlas || (a.cull_roots && !h->has_forest)) ? 1u : 0u;
-    a.forest_cull = h->cull_roots != 0 ? 1u : 0u;
-    a.cross_prune = h->cross_prune != 0 ? 1u : 0u;
-    {
-        uint32_t ds, dv;
-        memcpy(&ds, &h->camera.defocus_strength, 4);
-        memcpy(&dv, &h->camera.diverge_strength, 4);
-        a.simple = (h->specialise && h->plain_materials && ds == 0u && dv == 0u) ? 1u : 0u;  // (both strengths +0)
-    }
+    scene_args(h, a);
     // the per-lane primary-ray cache is used when it still leaves room for 4 workgroups per CU
-    a.textures = h->textures;
-    a.srgb_lut = h->srgb_lut;
     a.image = n_batch ? h->batch_scratch : h->image;
     a.counters = h->counters;
-    a.n_meshes = h->n_meshes;
-    a.n_spheres = h->n_spheres;
-    a.n_textures = h->n_textures;
-    a.stack_entries = h->stack_entries;
-    a.tlas_entries = h->tlas_entries;
-    a.stack_wide = (h->stack_must_wide || (h->force_stack_wide < 0 ? h->stack_wide : h->force_stack_wide != 0)) ? 1u : 0u;
-    // (the global-memory kernels park a pending mesh hit of 5 dwords in the stack column, intersect_scene)
-    if (!a.lds_scene && a.stack_entries < (a.stack_wide ? 3u : 5u)) a.stack_entries = a.stack_wide ? 3u : 5u;
-    a.n_items = h->n_items;
     a.strip_rank = rank;
     a.strip_world = world;
     a.tiles_x = (params->width + 7) / 8;
@@ -2628,6 +2637,57 @@ int rt_test_device_units(rt_handle* h, int fn, const float* x, const float* y, f
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_dev(dx);
     free_dev(dy);
+    free_dev(dout);
+    return RT_OK;
+}
+
+// tests/test_gpu_intersect.py: intersect_scene for host-given rays, on the uploaded scene, with the arguments and the
+// instantiation a render launches (scene_args, launch_variant) unless `flags` force one.
+int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint8_t* active, uint64_t n, int flags,
+                      uint32_t* out) {
+    if (!h || (n && (!ro || !rd || !out))) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (flags & ~(RT_TEST_ISECT_GENERAL | RT_TEST_ISECT_STATS | RT_TEST_ISECT_SIMPLE))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    if ((flags & RT_TEST_ISECT_GENERAL) && (flags & RT_TEST_ISECT_SIMPLE))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "flags ask for both the general and the SIMPLE instantiation");
+    if (n > RT_TEST_ISECT_MAX_RAYS) return fail(h, RT_ERR_CAPACITY, "too many rays");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    // only rays a render can trace: finite origins, finite non-zero directions (the kernels' normalize gives these)
+    for (uint64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(ro[i]) || !std::isfinite(rd[i])) return fail(h, RT_ERR_INVALID_ARGUMENT, "non-finite ray");
+    for (uint64_t i = 0; i < n; ++i)
+        if (rd[3 * i] == 0.0f && rd[3 * i + 1] == 0.0f && rd[3 * i + 2] == 0.0f)
+            return fail(h, RT_ERR_INVALID_ARGUMENT, "zero direction");
+    RenderArgs a{};
+    scene_args(h, a);
+    const bool stats = (flags & RT_TEST_ISECT_STATS) != 0;
+    bool simple = !a.many_mesh && a.simple && !stats;  // launch_variant's choice
+    if (flags & RT_TEST_ISECT_GENERAL) simple = false;
+    if (flags & RT_TEST_ISECT_SIMPLE) {
+        if (a.many_mesh || !h->plain_materials)
+            return fail(h, RT_ERR_INVALID_ARGUMENT, "the SIMPLE instantiation needs a few-mesh scene without spheres, glass or textures");
+        simple = true;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+    float *dro = nullptr, *drd = nullptr;
+    uint8_t* dact = nullptr;
+    uint32_t* dout = nullptr;
+    const size_t m = (size_t)(n ? n : 1);
+    HIP_TRY(h, hipMalloc((void**)&dro, m * 3 * sizeof(float)));
+    HIP_TRY(h, hipMalloc((void**)&drd, m * 3 * sizeof(float)));
+    HIP_TRY(h, hipMalloc((void**)&dout, m * RT_TEST_ISECT_WORDS * sizeof(uint32_t)));
+    if (active) HIP_TRY(h, hipMalloc((void**)&dact, m));
+    HIP_TRY(h, hipMemcpyAsync(dro, ro, n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(drd, rd, n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (active) HIP_TRY(h, hipMemcpyAsync(dact, active, n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(dout, 0, m * RT_TEST_ISECT_WORDS * sizeof(uint32_t), h->stream));
+    HIP_TRY(h, launch_test_intersect(a, dro, drd, dact, n, simple, stats, dout, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, dout, n * RT_TEST_ISECT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    free_dev(dro);
+    free_dev(drd);
+    free_dev(dact);
     free_dev(dout);
     return RT_OK;
 }

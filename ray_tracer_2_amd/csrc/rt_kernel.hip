@@ -2928,6 +2928,61 @@ hipError_t launch_sweep(int which, unsigned long long* out, hipStream_t stream) 
     return hipGetLastError();
 }
 
+// Test-only: intersect_scene for rays the host chooses (rt_test_intersect, tests/test_gpu_intersect.py), one lane per ray,
+// with the prologue and stack of rt_debug_kernel and the instantiation launch_variant would take (or the one the caller
+// forces).  A lane whose `active` byte is 0 stays out of intersect_scene, as lanes do in the partial waves the vote and
+// the refill create.  Record per ray (16 words, RT_TEST_ISECT_WORDS): hit, dst, point xyz, normal xyz, u, v, backface,
+// winner (mesh index, or n_meshes + sphere index; ~0 on a miss), node tests, triangle tests, instantiation bits, 0.
+template <bool LDS, bool TLAS, bool SIMPLE, bool STATS>
+__global__ void __launch_bounds__(BLOCK_THREADS) rt_test_intersect_kernel(const RenderArgs a, const float* __restrict__ ro,
+                                                                          const float* __restrict__ rd,
+                                                                          const uint8_t* __restrict__ active,
+                                                                          unsigned long long n, uint32_t* __restrict__ out) {
+    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    if (i >= n || (active != nullptr && active[i] == 0u)) return;
+    const f3 o{ro[3 * i], ro[3 * i + 1], ro[3 * i + 2]}, d{rd[3 * i], rd[3 * i + 1], rd[3 * i + 2]};
+    int node_tests = 0, tri_tests = 0;
+    Isect unused;
+    const Hit h = intersect_scene<LDS, STATS, TLAS, false, SIMPLE>(a, o, d, stack, node_tests, tri_tests, unused);
+    uint32_t* r = out + i * 16u;
+    r[0] = h.hit ? 1u : 0u;
+    r[1] = __float_as_uint(h.dst);
+    r[2] = __float_as_uint(h.point.x); r[3] = __float_as_uint(h.point.y); r[4] = __float_as_uint(h.point.z);
+    r[5] = __float_as_uint(h.normal.x); r[6] = __float_as_uint(h.normal.y); r[7] = __float_as_uint(h.normal.z);
+    r[8] = __float_as_uint(h.u);
+    r[9] = __float_as_uint(h.v);
+    r[10] = h.backface ? 1u : 0u;
+    r[11] = h.hit ? (h.mat_off - a.lay.mat_off) / MATERIAL_BYTES : 0xffffffffu;
+    r[12] = (uint32_t)node_tests;
+    r[13] = (uint32_t)tri_tests;
+    r[14] = (TLAS ? 1u : 0u) | (SIMPLE ? 2u : 0u) | (STATS ? 32u : 0u) | (LDS ? 64u : 0u);
+    r[15] = 0u;
+}
+
+// simple: the SIMPLE instantiation (few-mesh scenes only: the host checks), stats: the counter instantiation
+hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const float* rd, const uint8_t* active,
+                                 unsigned long long n, bool simple, bool stats, uint32_t* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t lds = render_lds_bytes(a);
+    const uint32_t blocks = (uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
+    auto go = [&](auto kernel) {
+        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, ro, rd, active, n, out);
+    };
+    const bool lds_scene = a.lds_scene != 0u, tlas = a.many_mesh != 0u;
+    if (lds_scene) {
+        if (tlas) stats ? go(rt_test_intersect_kernel<true, true, false, true>) : go(rt_test_intersect_kernel<true, true, false, false>);
+        else if (simple) stats ? go(rt_test_intersect_kernel<true, false, true, true>) : go(rt_test_intersect_kernel<true, false, true, false>);
+        else stats ? go(rt_test_intersect_kernel<true, false, false, true>) : go(rt_test_intersect_kernel<true, false, false, false>);
+    } else {
+        if (tlas) stats ? go(rt_test_intersect_kernel<false, true, false, true>) : go(rt_test_intersect_kernel<false, true, false, false>);
+        else if (simple) stats ? go(rt_test_intersect_kernel<false, false, true, true>) : go(rt_test_intersect_kernel<false, false, true, false>);
+        else stats ? go(rt_test_intersect_kernel<false, false, false, true>) : go(rt_test_intersect_kernel<false, false, false, false>);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_units(int fn, const float* x, const float* y, float* out, unsigned long long n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_units_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, fn, x, y, out, n);

@@ -31,7 +31,7 @@ EXPORTS = [
 ]
 # every symbol include/rt_test_abi.h declares (the test library only)
 TEST_EXPORTS = ["rt_test_device_units", "rt_test_sweep", "rt_test_device_sample_texture", "rt_test_read_wavefront",
-                "rt_test_rccl_gather", "rt_test_frame_ahead_depth"]
+                "rt_test_rccl_gather", "rt_test_frame_ahead_depth", "rt_test_intersect"]
 
 _lib = None
 _test_lib = None
@@ -143,6 +143,7 @@ def _bind(L, with_test_entries):
             "rt_test_frame_ahead_depth": (i32, [i32, u64, i32, i32, i32]),
             "rt_test_read_wavefront": (i32, [vp, i32, vp, u64]),
             "rt_test_rccl_gather": (i32, [C.c_char_p, i32]),
+            "rt_test_intersect": (i32, [vp, vp, vp, vp, u64, i32, vp]),
         })
         assert set(sig) == set(EXPORTS) | set(TEST_EXPORTS)
     for name, (res, args) in sig.items():

@@ -159,6 +159,27 @@ class RayTracer:
         self._check(self._L.rt_test_device_sample_texture(self._h, C.byref(d), uv.ctypes.data, out.ctypes.data, uv.shape[0]))
         return out
 
+    # ---- test-only: the kernels' ray-scene intersection for chosen rays (tests/test_gpu_intersect.py) ----
+    def intersect(self, ro, rd, active=None, general=False, simple=False, stats=False):
+        """intersect_scene on the uploaded scene for rays (ro[i], normalize3(rd[i])), one lane per ray, in the instantiation
+        a render would take (general / simple force one; stats: the counter instantiation).  Returns the (n, 16) u32
+        records of include/rt_test_abi.h (rt_test_intersect); inactive rays (active[i] == 0) are not traced and stay zero."""
+        ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+        rd = normalize3_f32(rd)
+        if ro.shape != rd.shape or not (np.isfinite(ro).all() and np.isfinite(rd).all()):
+            raise ValueError("rays must be finite, with non-zero directions of finite length")
+        n = ro.shape[0]
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(active, np.uint8).ravel()
+            if act.size != n:
+                raise ValueError("one active flag per ray")
+        out = np.zeros((n, 16), np.uint32)
+        flags = (1 if general else 0) | (2 if stats else 0) | (4 if simple else 0)
+        self._check(self._L.rt_test_intersect(self._h, ro.ctypes.data, rd.ctypes.data, None if act is None else act.ctypes.data,
+                                              n, flags, out.ctypes.data))
+        return out
+
     def stats(self):
         s = A.Stats()
         self._check(self._L.rt_get_stats(self._h, C.byref(s)))
@@ -183,6 +204,16 @@ class RayTracer:
 
     def strip_texels(self, width, height, rank, world):
         return int(self._L.rt_strip_texels(width, height, rank, world))
+
+
+def normalize3_f32(v):
+    """The kernels' normalize3 in binary32: v * (1 / sqrt((x*x + y*y) + z*z)), every operation rounded.
+    The directions a render traces are outputs of it; a zero or non-finite vector gives non-finite components."""
+    v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        r = np.float32(1.0) / np.sqrt((x * x + y * y) + z * z)
+        return (v * r[:, None]).astype(np.float32)
 
 
 def render_multi(tracers, params, read_back=True, n_frames=1):

@@ -169,12 +169,18 @@ def test_primary_table_follows_camera_scene_and_strip_layout(rt, oracle, cornell
         t.close()
 
 
-@pytest.mark.parametrize("kw", [dict(lds_scene=0), dict(pixel_cache=0), dict(pixel_cache=2), dict(tile_feedback=0), dict(batch_tile_major=0)])
+@pytest.mark.parametrize("kw", [dict(lds_scene=0), dict(pixel_cache=0), dict(pixel_cache=2), dict(tile_feedback=0), dict(batch_tile_major=0),
+                                dict(memo_in_table=0), dict(persistent_blocks=3)])
 def test_render_frames_under_every_kernel_option(rt, tracer, cornell, kw):
     w, h = 160, 90
     tracer.load_scene(cornell)
     want = sequential(rt, tracer, w, h, 4, 8, 0, 12)
     (k, v), = kw.items()
+    # (the default of "persistent_blocks" depends on the device: a handle of its own takes that knob and is closed after)
+    own = k == "persistent_blocks"
+    if own:
+        tracer = rt.RayTracer(device=0, max_width=tracer.max_width, max_height=tracer.max_height)
+        tracer.load_scene(cornell)
     tracer.set_option(k, v)
     try:
         tracer.write_image(np.zeros((h, w, 4), np.float32))
@@ -183,8 +189,11 @@ def test_render_frames_under_every_kernel_option(rt, tracer, cornell, kw):
         tracer.render_frames(rt.make_params(w, h, 4, 8, skybox=1, frames=0), 12)
         got = tracer.read_image(w, h)
     finally:
-        tracer.set_option(k, {"lds_scene": 1, "pixel_cache": 1, "tile_feedback": 1, "batch_tile_major": 1}[k])
-        tracer.set_option("batch_frames", 32)
+        if own:
+            tracer.close()
+        else:
+            tracer.set_option(k, {"lds_scene": 1, "pixel_cache": 1, "tile_feedback": 1, "batch_tile_major": 1, "memo_in_table": 1}[k])
+            tracer.set_option("batch_frames", 32)
     assert np.array_equal(bits(got), bits(want))
 
 

@@ -428,18 +428,25 @@ def test_random_many_mesh_scenes(rt, oracle, tracer, seed):
                                    {"flat2": 0}, {"flat2": 0, "forest": 0},
                                    {"specialise": 0}, {"specialise": 0, "kernel_variant": 1}, {"specialise": 1, "kernel_variant": 1},
                                    {"fast_miss": 0}, {"fast_miss": 0, "kernel_variant": 1}, {"vote_eighths": 8, "vote_patience": 16},
-                                   {"vote_eighths": 0}, {"vote_eighths": 7, "vote_patience": 0}],
+                                   {"vote_eighths": 0}, {"vote_eighths": 7, "vote_patience": 0},
+                                   {"memo_in_table": 0}, {"memo_in_table": 0, "pixel_cache": 2}, {"persistent_blocks": 1},
+                                   {"persistent_blocks": 7}, {"tile_feedback_period": 1}],
                          ids=lambda k: ",".join(f"{a}={b}" for a, b in k.items()))
 def test_tuning_knobs_do_not_change_the_bits(rt, oracle, tracer, cornell, dragon_arrays, knobs):
     """rt_set_option's contract: results never depend on the knobs (forest items, stack entry
     width, memo placement, the LDS-staged BVH top) -- on the LDS-resident Cornell scene and the
     global-memory dragon scene."""
     defaults = {"forest": 1, "stack_wide": -1, "pixel_cache": 1, "primary_table": 1, "lds_top": 0, "flat2": 1, "specialise": 1,
-                "kernel_variant": -1, "fast_miss": 1, "vote_eighths": -1, "vote_patience": -1}
+                "kernel_variant": -1, "fast_miss": 1, "vote_eighths": -1, "vote_patience": -1, "memo_in_table": 1,
+                "tile_feedback_period": 8}
     if "lds_top" in knobs and not experiments_build():
         with pytest.raises(rt.RtError):   # the product library has no such code and says so
             tracer.set_option("lds_top", knobs["lds_top"])
         pytest.skip("option lds_top needs the -DRT_EXPERIMENTS=1 build")
+    # (the default of "persistent_blocks" depends on the device: a handle of its own takes the knob and is closed after)
+    own = "persistent_blocks" in knobs
+    if own:
+        tracer = rt.RayTracer(device=0, max_width=tracer.max_width, max_height=tracer.max_height)
     try:
         for name, value in knobs.items():
             tracer.set_option(name, value)
@@ -458,8 +465,11 @@ def test_tuning_knobs_do_not_change_the_bits(rt, oracle, tracer, cornell, dragon
             tracer.render(p)  # and the product kernels (no counters)
             assert same(tracer.read_image(w, h), ref), knobs
     finally:
-        for name, value in defaults.items():
-            tracer.set_option(name, value)
+        if own:
+            tracer.close()
+        else:
+            for name, value in defaults.items():
+                tracer.set_option(name, value)
 
 
 def test_config3_dragon_standin(rt, oracle, tracer, dragon_arrays):

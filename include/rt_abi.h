@@ -413,6 +413,56 @@ int rt_set_counters(rt_handle* h, int enabled);
 void* rt_device_image(rt_handle* h);
 void* rt_stream(rt_handle* h);
 
+/* Ray queries against the uploaded scene.  Each ray is intersected exactly as a render's walk
+ * does it (calculate_ray_collions, wgsl:353-396): the same instantiation, the same literal stack for BVH heights >= 32,
+ * the same tie-break by mesh index.  Queries leave the image, the primary table, a frame_ahead batch in flight, the
+ * pipeline slots, rt_get_stats and rt_last_launch as they are, and ignore rt_set_counters. */
+typedef struct rt_ray {            /* 32 bytes */
+    float origin[3];
+    float tmax;                    /* world distance; +INF = unbounded; must be > 0 */
+    float dir[3];                  /* any finite non-zero length; normalised by the library with the kernels' normalize3 */
+    uint32_t _p0;                  /* must be 0 */
+} rt_ray;
+
+typedef struct rt_hit {            /* 64 bytes */
+    float t;                       /* world distance (Hit.dst); +INF on a miss */
+    uint32_t object;               /* mesh index, or n_meshes + sphere index (the material numbering); 0xffffffff on a miss */
+    uint32_t primitive;            /* index into the triangle array given to rt_upload_scene; the sphere index for a sphere;
+                                    * 0xffffffff on a miss */
+    uint32_t flags;                /* RT_HIT_* */
+    float point[3];                /* world hit point */
+    float bary_u;                  /* barycentrics (u, v) of the triangle test (wgsl:258-290); w = (1 - u) - v; 0 for spheres */
+    float normal[3];               /* the shading normal the render uses */
+    float bary_v;
+    float tex_u, tex_v;            /* Hit.u / Hit.v: texture coordinates */
+    float _p1[2];
+} rt_hit;
+/* A miss record: t = +INF, object = primitive = 0xffffffff, everything else 0. */
+
+enum { RT_HIT_HIT = 1, RT_HIT_BACKFACE = 2 };
+enum { RT_QUERY_HOST_MEMORY = 1, RT_QUERY_PRUNE_TMAX = 2 };
+
+/* Closest hit of n rays.  A hit with t >= tmax is reported as a miss (a filter after the walk: exact).
+ * Without RT_QUERY_HOST_MEMORY `rays` and `hits` are device pointers on the handle's device (16-byte aligned) and the
+ * call is asynchronous, ordered on the handle's stream after every earlier call on the handle and before every later
+ * one.  With it they are host pointers: the rays are staged through temporary device buffers of at most 64 MB per
+ * chunk, counted against option "max_device_mb" while held (RT_ERR_OUT_OF_MEMORY when not even one ray fits), and the
+ * call returns when the hits are on the host.  A ray with a non-finite component, a direction whose normalisation is
+ * not finite and non-zero, tmax <= 0 or NaN, or _p0 != 0 gets a miss record on both paths (never an error).
+ * n = 0 is a no-op; n > 2^31 - 1 gives RT_ERR_CAPACITY.  Flags: RT_QUERY_HOST_MEMORY only. */
+int rt_intersect_rays(rt_handle* h, const rt_ray* rays, uint64_t n, rt_hit* hits, int flags);
+/* Occlusion: occluded[i] = 1 when the scene holds a hit closer than tmax, else 0 (invalid rays: 0).  The same walk in the
+ * same order that stops at the first candidate whose world distance is < tmax, so occluded == (closest hit && t < tmax)
+ * except for rays with some hit within a few ulps of tmax.  RT_QUERY_PRUNE_TMAX also skips boxes entered beyond a
+ * local-space bound for tmax: the fast path for short shadow rays, but not exact -- it
+ * rests on the same hypothesis as option "cross_prune".  Memory, ordering and limits as rt_intersect_rays
+ * (occluded: 4-byte aligned). */
+int rt_occluded_rays(rt_handle* h, const rt_ray* rays, uint64_t n, uint32_t* occluded, int flags);
+/* The closest hit of the ray the debug views trace for texel (x, y) of a params->width x params->height frame (row 0 is
+ * the bottom, no jitter, the camera currently set).  Synchronous; hit is host memory.  x or y out of range:
+ * RT_ERR_INVALID_ARGUMENT; no scene: RT_ERR_NO_SCENE. */
+int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hit* hit);
+
 /* The test-only entry points (rt_test_*: the kernels' arithmetic building blocks evaluated element-wise on the device, raw
  * copies of sequence buffers, the RCCL gather against a stub, the frame_ahead policy) are NOT exported by the product
  * library: include/rt_test_abi.h declares them and ray_tracer_2_amd/librt2_mi355x_test.so -- the same sources compiled

@@ -80,6 +80,15 @@ class Stats(C.Structure):
                 ("frames_speculative", u32), ("_reserved", u32)]
 
 
+class Ray(C.Structure):  # rt_ray: a ray query's input
+    _fields_ = [("origin", f32 * 3), ("tmax", f32), ("dir", f32 * 3), ("_p0", u32)]
+
+
+class Hit(C.Structure):  # rt_hit: a ray query's closest-hit record
+    _fields_ = [("t", f32), ("object", u32), ("primitive", u32), ("flags", u32), ("point", f32 * 3), ("bary_u", f32),
+                ("normal", f32 * 3), ("bary_v", f32), ("tex_u", f32), ("tex_v", f32), ("_p1", f32 * 2)]
+
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():
@@ -103,6 +112,14 @@ MESH_DTYPE = np.dtype([("world_to_model", "<f4", (4, 4)), ("model_to_world", "<f
 SPHERE_DTYPE = np.dtype([("pos", "<f4", 3), ("radius", "<f4"), ("material", MATERIAL_DTYPE)])
 assert NODE_DTYPE.itemsize == 48 and TRI_DTYPE.itemsize == 96
 assert MESH_DTYPE.itemsize == 240 and SPHERE_DTYPE.itemsize == 112
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("dir", "<f4", 3), ("_p0", "<u4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<u4"), ("primitive", "<u4"), ("flags", "<u4"), ("point", "<f4", 3),
+                      ("bary_u", "<f4"), ("normal", "<f4", 3), ("bary_v", "<f4"), ("tex_u", "<f4"), ("tex_v", "<f4"),
+                      ("_p1", "<f4", 2)])
+assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
+HIT_HIT, HIT_BACKFACE = 1, 2
+QUERY_HOST_MEMORY, QUERY_PRUNE_TMAX = 1, 2
+MISS = 0xFFFFFFFF
 
 RT_OK = 0
 MATERIAL_DEFAULT, MATERIAL_GLASS, MATERIAL_TEXTURE = 0, 1, 2

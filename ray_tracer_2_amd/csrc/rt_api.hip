@@ -37,6 +37,9 @@ hipError_t launch_tile_order(const uint32_t* cost, uint32_t n_tiles, uint32_t ma
 hipError_t launch_primary(const RenderArgs& a, void* table, bool with_hits, hipStream_t stream);
 hipError_t launch_blend_frames(const BlendArgs& b, hipStream_t stream);
 hipError_t launch_walk(const RenderArgs& a, uint32_t compute_units, hipStream_t stream);
+hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long long n, void* out, bool any, bool prune_tmax,
+                        uint32_t blocks, uint32_t compute_units, hipStream_t stream);
+hipError_t launch_pick_ray(const RenderArgs& a, uint32_t x, uint32_t y, float4* ray, hipStream_t stream);
 hipError_t launch_wf_shade(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_wf_walk(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
 size_t wf_walk_lds_bytes(const RenderArgs& a);
@@ -2443,6 +2446,105 @@ int rt_read_multi_frame(rt_handle* root, float* rgba32f_out, size_t bytes) {
     HIP_TRY(root, hipSetDevice(root->device));
     HIP_TRY(root, hipMemcpyAsync(rgba32f_out, root->multi_frame, bytes, hipMemcpyDeviceToHost, root->stream));
     HIP_TRY(root, hipStreamSynchronize(root->stream));
+    return RT_OK;
+}
+
+// ---- ray queries (include/rt_abi.h: rt_intersect_rays, rt_occluded_rays, rt_pick; rt_kernel.hip: rt_query_kernel) ----
+// A query launch takes the arguments a render of the scene takes (scene_args), no pixel memo, and the render's
+// persistent grid (workgroups that fit the CUs' LDS).  It reads nothing but the scene and writes nothing but its output:
+// the image, the tables, the pipeline slots and the counters are not touched.
+static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 64, "rt_ray / rt_hit layout");
+
+static uint32_t query_blocks(const rt_handle* h, const RenderArgs& a) {
+    const size_t lds = render_lds_bytes(a);
+    uint32_t per_cu = lds ? (uint32_t)((160u * 1024u) / lds) : BLOCKS_PER_CU;
+    if (per_cu > BLOCKS_PER_CU) per_cu = BLOCKS_PER_CU;
+    if (per_cu < 1u) per_cu = 1u;
+    const uint32_t fit = (h->persistent_blocks / BLOCKS_PER_CU) * per_cu;
+    return fit < h->persistent_blocks && fit > 0 ? fit : h->persistent_blocks;
+}
+
+// out_bytes: bytes of output per ray (sizeof(rt_hit) or 4)
+static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, size_t out_bytes, int flags, bool any) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    const int known = RT_QUERY_HOST_MEMORY | (any ? RT_QUERY_PRUNE_TMAX : 0);
+    if (flags & ~known) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (n == 0) return RT_OK;
+    if (!rays || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > 0x7fffffffull) return fail(h, RT_ERR_CAPACITY, "more than 2^31 - 1 rays");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    const bool host = (flags & RT_QUERY_HOST_MEMORY) != 0, prune = (flags & RT_QUERY_PRUNE_TMAX) != 0;
+    if (!host && (((uintptr_t)rays & 15u) != 0u || ((uintptr_t)out & (out_bytes == 4 ? 3u : 15u)) != 0u))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "device rays / results not aligned (16 bytes; 4 for occlusion flags)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    RenderArgs a{};
+    scene_args(h, a);
+    a.params = rt_params{};
+    a.camera = h->camera;
+    const uint32_t blocks = query_blocks(h, a);
+    if (!host) {
+        HIP_TRY(h, launch_query(a, rays, n, out, any, prune, blocks, h->compute_units, h->stream));
+        return RT_OK;
+    }
+    // host memory: chunks of at most 64 MB of device memory (rays and results), within option max_device_mb
+    const size_t per_ray = sizeof(rt_ray) + out_bytes;
+    size_t room = (size_t)64 << 20;
+    if (h->max_device_bytes != 0) {
+        const size_t held = optional_bytes(h);
+        const size_t left = h->max_device_bytes > held ? h->max_device_bytes - held : 0;
+        room = std::min(room, left);
+    }
+    const uint64_t chunk = std::min<uint64_t>(n, room / per_ray);
+    if (chunk == 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for a query's staging buffers");
+    void* d_rays = nullptr;
+    void* d_out = nullptr;
+    int rc = RT_OK;
+    auto hip_fail = [&](const char* what, hipError_t e) { return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
+    hipError_t e = hipMalloc(&d_rays, chunk * sizeof(rt_ray));
+    if (e == hipSuccess) e = hipMalloc(&d_out, chunk * out_bytes);
+    if (e != hipSuccess) {
+        rc = e == hipErrorOutOfMemory ? fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for a query's staging buffers")
+                                      : hip_fail("hipMalloc", e);
+    }
+    for (uint64_t i0 = 0; rc == RT_OK && i0 < n; i0 += chunk) {
+        const uint64_t m = std::min<uint64_t>(chunk, n - i0);
+        if ((e = hipMemcpyAsync(d_rays, rays + i0, m * sizeof(rt_ray), hipMemcpyHostToDevice, h->stream)) != hipSuccess) { rc = hip_fail("hipMemcpyAsync", e); break; }
+        if ((e = launch_query(a, d_rays, m, d_out, any, prune, blocks, h->compute_units, h->stream)) != hipSuccess) { rc = hip_fail("launch_query", e); break; }
+        if ((e = hipMemcpyAsync(static_cast<uint8_t*>(out) + i0 * out_bytes, d_out, m * out_bytes, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) { rc = hip_fail("hipMemcpyAsync", e); break; }
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) { rc = hip_fail("hipStreamSynchronize", e); break; }
+    }
+    if (rc != RT_OK) (void)hipStreamSynchronize(h->stream);  // (nothing may still use the buffers when they are freed)
+    free_dev(d_rays);
+    free_dev(d_out);
+    return rc;
+}
+
+int rt_intersect_rays(rt_handle* h, const rt_ray* rays, uint64_t n, rt_hit* hits, int flags) {
+    return query_impl(h, rays, n, hits, sizeof(rt_hit), flags, false);
+}
+
+int rt_occluded_rays(rt_handle* h, const rt_ray* rays, uint64_t n, uint32_t* occluded, int flags) {
+    return query_impl(h, rays, n, occluded, sizeof(uint32_t), flags, true);
+}
+
+int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hit* hit) {
+    if (!h || !params || !hit) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (x >= params->width || y >= params->height) return fail(h, RT_ERR_INVALID_ARGUMENT, "texel outside the frame");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    HIP_TRY(h, hipSetDevice(h->device));
+    RenderArgs a{};
+    scene_args(h, a);
+    a.params = *params;
+    a.camera = h->camera;
+    float4* d = nullptr;  // one rt_ray, then one rt_hit
+    HIP_TRY(h, hipMalloc((void**)&d, sizeof(rt_ray) + sizeof(rt_hit)));
+    hipError_t e = launch_pick_ray(a, x, y, d, h->stream);
+    if (e == hipSuccess) e = launch_query(a, d, 1, d + 2, false, false, 1, 1, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hit, d + 2, sizeof(rt_hit), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    free_dev(d);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(h, RT_ERR_DEVICE, std::string("rt_pick: ") + hipGetErrorString(e));
     return RT_OK;
 }
 

@@ -418,10 +418,16 @@ DEV uint32_t stack_dwords(const RenderArgs& a) {
 // registers instead of a push/pop pair), entries popped without re-testing.
 // "while-while": a lane first descends through internal nodes until it holds a
 // leaf, then the wave tests leaf triangles together.
-template <bool LDS, bool STATS>
+// ANY (the occlusion query kernels): after a leaf that improved `best`, probe(best) is asked whether that hit already
+// answers the query; if so the walk ends there.  The render kernels take ANY = false: no probe is compiled in.
+struct NoProbe {
+    template <class... T>
+    DEV bool operator()(const T&...) const { return false; }
+};
+template <bool LDS, bool STATS, bool ANY = false, class Probe = NoProbe>
 DEV void traverse_mesh(const RenderArgs& a, uint32_t root_idx, uint32_t root_count, bool cull, bool deep, f3 lo,
                        f3 ld, f3 inv, uint32_t* stack,
-                       MeshBest& best, int& node_tests, int& tri_tests) {
+                       MeshBest& best, int& node_tests, int& tri_tests, const Probe& probe = Probe{}) {
     const uint32_t tri0 = a.lay.tri_off;  // (indices are absolute)
     const LaneStack st{stack, a.stack_wide != 0u};
     if (root_count > 0) {
@@ -450,10 +456,12 @@ DEV void traverse_mesh(const RenderArgs& a, uint32_t root_idx, uint32_t root_cou
             stack_get(st, slot(stack_index), idx, cnt);
             if (cnt > 0) {
                 if (STATS) tri_tests += (int)cnt;
+                const float t_before = best.t;
                 for (uint32_t j = 0; j < cnt; ++j) {
                     const uint32_t t = tri0 + (idx + j) * TRI_ISECT_BYTES;
                     tri_test<8>(lo, ld, ld4<LDS>(a, t), ld4<LDS>(a, t + 16), ld4<LDS>(a, t + 32), cull, idx + j, best);
                 }
+                if constexpr (ANY) if (best.t < t_before && probe(best)) return;
             } else {
                 float4 q0, q1, q2, q3;
                 load_wide<LDS>(a, idx, q0, q1, q2, q3);
@@ -506,10 +514,12 @@ DEV void traverse_mesh(const RenderArgs& a, uint32_t root_idx, uint32_t root_cou
         }
         if (finished) break;
         if (STATS) tri_tests += (int)cur_count;
+        const float t_before = best.t;
         for (uint32_t j = 0; j < cur_count; ++j) {
             const uint32_t t = tri0 + (cur + j) * TRI_ISECT_BYTES;
             tri_test<8>(lo, ld, ld4<LDS>(a, t), ld4<LDS>(a, t + 16), ld4<LDS>(a, t + 32), cull, cur + j, best);
         }
+        if constexpr (ANY) if (best.t < t_before && probe(best)) break;
         if (sp == 0) break;
         --sp;
         stack_get(st, sp, cur, cur_count);
@@ -561,9 +571,10 @@ DEV void traverse_flat2(const RenderArgs& a, uint32_t root_rec, bool cull, f3 lo
 // wgsl:292-296) and the caller's closest-hit update is order-free, so the result is the same.
 // Skipping a member whose root box is missed is the monotonicity argument of intersect_scene
 // (FOREST_CULLABLE members only, finite ray only).
-template <bool LDS, bool STATS, bool SIMPLE, class Accept>
+// ANY: after a leaf that improved a member's best hit, probe(mesh, best) may end this lane's walk (traverse_mesh).
+template <bool LDS, bool STATS, bool SIMPLE, class Accept, bool ANY = false, class Probe = NoProbe>
 DEV void traverse_forest(const RenderArgs& a, uint32_t entry0, uint32_t n_members, f3 lo, f3 ld, f3 inv,
-                         uint32_t* stack, Accept&& accept, int& node_tests, int& tri_tests) {
+                         uint32_t* stack, Accept&& accept, int& node_tests, int& tri_tests, const Probe& probe = Probe{}) {
     const bool finite_ray = rtm::abs_(inv.x) < INF && rtm::abs_(inv.y) < INF && rtm::abs_(inv.z) < INF &&
                             rtm::abs_(lo.x) < INF && rtm::abs_(lo.y) < INF && rtm::abs_(lo.z) < INF;
     const uint32_t e0 = a.lay.forest_off + entry0 * FOREST_ENTRY_BYTES;
@@ -639,11 +650,17 @@ DEV void traverse_forest(const RenderArgs& a, uint32_t entry0, uint32_t n_member
         TIC(t7);
         if (have) {  // a leaf
             if (STATS) tri_tests += (int)cur_count;
+            const float t_before = b.t;
             for (uint32_t j = 0; j < cur_count; ++j) {
                 const uint32_t t = tri0 + (cur + j) * TRI_ISECT_BYTES;
                 tri_test<8>(lo, ld, ld4<LDS>(a, t), ld4<LDS>(a, t + 16), ld4<LDS>(a, t + 32), cull, cur + j, b);
             }
-            if (sp == 0) {
+            bool stop = false;
+            if constexpr (ANY) stop = b.t < t_before && probe(mesh, b);
+            if (stop) {
+                have = false;  // (the member's hit is offered above, at the next turn; no further member is walked)
+                todo = 0u;
+            } else if (sp == 0) {
                 have = false;
             } else {
                 --sp;
@@ -807,14 +824,24 @@ DEV Hit isect_finish(const RenderArgs& a, const Isect& I, f3 ro, f3 rd) {
 // jitter (RenderArgs::simple, decided by the host per launch) -- the instantiation BASELINE configs 2, 3 and 5 run.
 // The general code is the same code with those branches present; compiled out, they stop costing registers at the
 // kernels' 96-VGPR ceiling and instruction-cache space.
-template <bool LDS, bool STATS, bool TLAS, bool PARK = false, bool SIMPLE = false, bool HYB = false>
+// The query kernels (rt_query_kernel) add two parameters the render kernels leave off.  EXPORT: the closest-hit record
+// (Isect: winning triangle, barycentrics) is copied to I_parked before isect_finish.  ANY (occlusion): the walk is the
+// same walk in the same order, but a lane stops at the first candidate whose world distance (world_hit, as for the
+// winner) is < tmax -- checked for spheres, after every BVH leaf that improved the mesh's best hit and for every mesh
+// hit -- and only the Isect is returned (Hit::hit = that candidate exists); with prune_tmax, boxes entered at or beyond
+// the local-space bound of DESIGN.md section 2.4 for tmax are skipped as well (not exact: the step-2 hypothesis of
+// cross_prune).
+template <bool LDS, bool STATS, bool TLAS, bool PARK = false, bool SIMPLE = false, bool HYB = false, bool ANY = false,
+          bool EXPORT = false>
 DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int& node_tests,
-                        int& tri_tests, Isect& I_parked) {
+                        int& tri_tests, Isect& I_parked, float tmax = INF, bool prune_tmax = false) {
     // this lane's TLAS stack column sits behind the wave's BVH stack columns
     uint32_t* tstack = stack + stack_dwords(a);
     bool suspended = false;
     Isect I;
     if constexpr (!SIMPLE) isect_spheres<LDS>(a, ro, rd, I);
+    bool done = false;  // (ANY) a candidate closer than tmax has been found
+    if constexpr (ANY) done = I.any && I.closest < tmax;
     // meshes (wgsl:369-393), as items: single meshes and top-level trees over mesh root boxes
     f3 lo{0, 0, 0}, ld{0, 0, 0}, inv{0, 0, 0};
     bool cull_ok = false;
@@ -840,6 +867,20 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
         TOC(t19, 19);
     };
     auto accept_mesh_hit = [&](uint32_t i, const MeshBest& b) { accept_hit(i, compact(b)); };
+    // (ANY) the bound boxes are cut at: the closest hit so far, or tmax with prune_tmax
+    auto cut = [&]() { return t_cut_of(ANY && prune_tmax ? min_(I.closest, tmax) : I.closest); };
+    // (ANY) does mesh i's hit b end the walk?  If so it is offered (I.closest < tmax from then on)
+    auto any_probe = [&](uint32_t i, const MeshBest& b) {
+        f3 whp;
+        float wdst;
+        world_hit<LDS>(a, a.lay.mesh_off + i * MESH_REC_BYTES + 64u, lo, ld, ro, b.t, whp, wdst);
+        if (!(wdst < tmax)) return false;
+        isect_offer(I, i, compact(b), whp, wdst);
+        return true;
+    };
+    auto any_deliver = [&](uint32_t i, const MeshBest& b) {
+        if (any_probe(i, b)) done = true;
+    };
     // Deferred offers.  The meshes every lane visits together (root-leaf and two-leaf items) are hit by a few lanes
     // each, and mostly by different lanes: offering each hit at once costs a sparsely populated pass of world_hit
     // per mesh.  A lane therefore keeps ONE hit pending and offers it when it gets another one (rare: a ray seldom
@@ -887,15 +928,25 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
         b.tri = 0xffffffffu;
         b.u = b.v = 0.0f;
         if (!TLAS && fbits(hdr.z) == 0u) flush_pending();  // (a BVH walk uses the stack column / is where the register pressure peaks)
-        traverse_mesh<LDS, STATS>(a, fbits(hdr.y), fbits(hdr.z),
-                                  SIMPLE || (flags & DMESH_GLASS) == 0, (flags & DMESH_DEEP) != 0, lo, ld, inv, stack, b,
-                                  node_tests, tri_tests);
-        if (b.tri != 0xffffffffu) {
-            if (!TLAS && fbits(hdr.z) != 0u) offer_later(i, b);  // root leaf: the wave visits it in step
-            else accept_mesh_hit(i, b);
+        if constexpr (ANY) {
+            // (prune_tmax: meshes with an internal root walked with the ordinary stack, glass excluded -- ITEM_PRUNE's rules)
+            if (prune_tmax && fbits(hdr.z) == 0u && (flags & (DMESH_GLASS | DMESH_DEEP)) == 0u) b.t = cut();
+            traverse_mesh<LDS, STATS, true>(a, fbits(hdr.y), fbits(hdr.z), SIMPLE || (flags & DMESH_GLASS) == 0,
+                                            (flags & DMESH_DEEP) != 0, lo, ld, inv, stack, b, node_tests, tri_tests,
+                                            [&](const MeshBest& bb) { return any_probe(i, bb); });
+            if (b.tri != 0xffffffffu) any_deliver(i, b);
+        } else {
+            traverse_mesh<LDS, STATS>(a, fbits(hdr.y), fbits(hdr.z),
+                                      SIMPLE || (flags & DMESH_GLASS) == 0, (flags & DMESH_DEEP) != 0, lo, ld, inv, stack, b,
+                                      node_tests, tri_tests);
+            if (b.tri != 0xffffffffu) {
+                if (!TLAS && fbits(hdr.z) != 0u) offer_later(i, b);  // root leaf: the wave visits it in step
+                else accept_mesh_hit(i, b);
+            }
         }
     };
     for (uint32_t it = 0; it < a.n_items; ++it) {
+        if constexpr (ANY) if (done) break;
         const float4 item = ld4<LDS>(a, a.lay.item_off + it * ITEM_BYTES);
         // item words are the same in every lane: keep them scalar
         const uint32_t kind = __builtin_amdgcn_readfirstlane(fbits(item.x));
@@ -912,12 +963,12 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
             ld = normalize3<!LDS>(mat_cols_xyz(c0, c1, c2, c3, rd, 0.0f));
             inv = f3{rcp_(ld.x), rcp_(ld.y), rcp_(ld.z)};
             // the root-box arguments below are only proven for finite slab arithmetic
-            if constexpr (TLAS)
+            if constexpr (TLAS || ANY)
                 cull_ok = rtm::abs_(inv.x) < INF && rtm::abs_(inv.y) < INF && rtm::abs_(inv.z) < INF &&
                           rtm::abs_(lo.x) < INF && rtm::abs_(lo.y) < INF && rtm::abs_(lo.z) < INF;
-            if constexpr (PRUNE) {
+            if constexpr (PRUNE || ANY) {
                 pa = pb = INF;
-                if (a.cross_prune != 0u && cull_ok) {
+                if (((PRUNE && a.cross_prune != 0u) || (ANY && prune_tmax)) && cull_ok) {
                     // The world distance the shader computes for a hit at local parameter t (world_hit: wgsl:380-381) is
                     //   wdst_c(t) = fl|ro - fl(M (lo + ld t))|,  M = model_to_world = (A | c).
                     // In exact arithmetic M (lo + ld t) = p0 + t g with p0 = A lo + c, g = A ld, so
@@ -956,8 +1007,13 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
             // walk, where the register pressure peaks, was 7 more spilled dwords per lane: 95 MB of scratch write-back
             // per frame)
             flush_pending();
-            traverse_forest<LDS, STATS, SIMPLE>(a, ia, __builtin_amdgcn_readfirstlane(fbits(item.w)), lo, ld, inv, stack,
-                                                accept_mesh_hit, node_tests, tri_tests);
+            if constexpr (ANY)
+                traverse_forest<LDS, STATS, SIMPLE, decltype(any_deliver)&, true>(
+                    a, ia, __builtin_amdgcn_readfirstlane(fbits(item.w)), lo, ld, inv, stack, any_deliver, node_tests,
+                    tri_tests, any_probe);
+            else
+                traverse_forest<LDS, STATS, SIMPLE>(a, ia, __builtin_amdgcn_readfirstlane(fbits(item.w)), lo, ld, inv, stack,
+                                                    accept_mesh_hit, node_tests, tri_tests);
             continue;
         }
         if constexpr (!TLAS) {
@@ -1023,7 +1079,10 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                 traverse_flat2<LDS, STATS>(a, __builtin_amdgcn_readfirstlane(fbits(hdr.y)), SIMPLE || (fbits(hdr.x) & DMESH_GLASS) == 0, lo, ld, inv,
                                            b, node_tests, tri_tests);
                 TOC(t18, 18);
-                if (b.tri != 0xffffffffu) offer_later(ia, b);
+                if (b.tri != 0xffffffffu) {
+                    if constexpr (ANY) any_deliver(ia, b);
+                    else offer_later(ia, b);
+                }
             } else {
                 visit_mesh(ia, hdr);
             }
@@ -1043,7 +1102,7 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
             if ((kind & ITEM_TLAS) == 0u) {
                 bool may_hit = true;
                 const float4 hdr = ld4<LDS>(a, a.lay.item_off + it * ITEM_BYTES + 16);  // (flags, root, root count)
-                const float seed = prune_item && fbits(hdr.z) == 0u ? t_cut_of(I.closest) : INF;
+                const float seed = prune_item && fbits(hdr.z) == 0u ? cut() : INF;
                 if (a.cull_roots && fbits(hdr.z) == 0u) {
                     // Mesh-level culling that cannot change the result.  The shader
                     // never tests the root box, only its two children (wgsl:316-321) -- but the
@@ -1099,7 +1158,7 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                     TIC(t8);
                     if (!have) {
                         if (b.tri != 0xffffffffu) {  // the mesh just left had a hit
-                            accept_mesh_hit(mesh, b);
+                            if constexpr (!ANY) accept_mesh_hit(mesh, b);  // (ANY: probed leaf by leaf)
                             b.tri = 0xffffffffu;
                         }
                         while (tsp > 0 && !have) {
@@ -1112,7 +1171,7 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                                 cur = e & TLAS_REF_ROOT_MASK;
                                 cur_count = 0;
                                 cull = (e & TLAS_REF_GLASS) == 0u;
-                                b.t = prune_item ? t_cut_of(I.closest) : INF;
+                                b.t = prune_item ? cut() : INF;
                                 sp = 0;
                                 have = true;
                             } else {
@@ -1122,7 +1181,7 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                                 if constexpr (PRUNE) {
                                     // the nearer box is visited first (the order of the mesh loop is free: isect_offer
                                     // breaks ties by mesh index), so that what lies behind a hit meets a small t_cut
-                                    const float tc = prune_item ? t_cut_of(I.closest) : INF;
+                                    const float tc = prune_item ? cut() : INF;
                                     const float da = aabb_dist(lo, inv, q0, q1, tc), db = aabb_dist(lo, inv, q2, q3, tc);
                                     const bool hit_a = !cull_ok || da < INF, hit_b = !cull_ok || db < INF;
                                     const bool a_first = da <= db;
@@ -1184,11 +1243,18 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                     TIC(t7);
                     if (have) {  // a leaf
                         if (STATS) tri_tests += (int)cur_count;
+                        const float t_before = b.t;
                         for (uint32_t j = 0; j < cur_count; ++j) {
                             const uint32_t t = tri0 + (cur + j) * TRI_ISECT_BYTES;
                             tri_test<8>(lo, ld, ld4<LDS>(a, t), ld4<LDS>(a, t + 16), ld4<LDS>(a, t + 32), cull, cur + j, b);
                         }
-                        if (sp == 0) {
+                        bool stop = false;
+                        if constexpr (ANY) stop = b.t < t_before && any_probe(mesh, b);
+                        if (stop) {
+                            done = true;  // (no further mesh or tree entry)
+                            have = false;
+                            tsp = 0;
+                        } else if (sp == 0) {
                             have = false;
                         } else {
                             --sp;
@@ -1201,6 +1267,13 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
         }
     }
     if constexpr (!TLAS) flush_pending();
+    if constexpr (ANY || EXPORT) I_parked = I;
+    if constexpr (ANY) {
+        Hit h{};
+        h.hit = done;
+        h.dst = I.closest;
+        return h;
+    }
     if (PARK && suspended) {
         I_parked = I;
         Hit h;
@@ -2832,6 +2905,109 @@ hipError_t launch_wf_walk(const RenderArgs&, uint32_t, hipStream_t) { return hip
 hipError_t launch_blend_frames(const BlendArgs& b, hipStream_t stream) {
     if (b.texels == 0 || b.n == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_blend_frames_kernel, dim3((uint32_t)((b.texels + 255u) / 256u)), dim3(256), 0, stream, b);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick; include/rt_abi.h): intersect_scene for rays the host gives,
+// on the uploaded scene, in the instantiation a render of it takes (scene_args, launch_variant).  A persistent grid:
+// every workgroup stages an LDS scene once and then takes rays with a grid stride, one lane per ray, with the prologue
+// and stack layout of the render kernels.  rays: rt_ray records (32 B: origin, tmax, dir, _p0).  ANY = false writes one
+// rt_hit (64 B) per ray, ANY = true one u32 (occluded) per ray.  A ray with a non-finite component, a direction whose
+// normalize3 is not finite and non-zero, tmax <= 0 or NaN, or _p0 != 0 gets a miss record.
+// ---------------------------------------------------------------------------
+template <bool LDS, bool TLAS, bool SIMPLE, bool ANY>
+__global__ void __launch_bounds__(BLOCK_THREADS) rt_query_kernel(const RenderArgs a, const float4* __restrict__ rays,
+                                                                 unsigned long long n, void* __restrict__ out,
+                                                                 uint32_t prune_tmax) {
+    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
+    const unsigned long long stride = (unsigned long long)gridDim.x * BLOCK_THREADS;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK_THREADS + threadIdx.x; i < n; i += stride) {
+        const float4 r0 = rays[2 * i], r1 = rays[2 * i + 1];
+        const f3 ro{r0.x, r0.y, r0.z}, d{r1.x, r1.y, r1.z};
+        const float tmax = r0.w;
+        const f3 rd = normalize3(d);
+        auto finite3 = [](f3 v) { return rtm::abs_(v.x) < __builtin_inff() && rtm::abs_(v.y) < __builtin_inff() && rtm::abs_(v.z) < __builtin_inff(); };
+        const bool valid = finite3(ro) && finite3(d) && finite3(rd) && (rd.x != 0.0f || rd.y != 0.0f || rd.z != 0.0f) &&
+                           tmax > 0.0f && fbits(r1.w) == 0u;
+        int node_tests = 0, tri_tests = 0;
+        Isect I;
+        if constexpr (ANY) {
+            bool occluded = false;
+            if (valid) occluded = intersect_scene<LDS, false, TLAS, false, SIMPLE, false, true>(a, ro, rd, stack, node_tests, tri_tests, I, tmax, prune_tmax != 0u).hit;
+            static_cast<uint32_t*>(out)[i] = occluded ? 1u : 0u;
+        } else {
+            Hit h{};
+            if (valid) h = intersect_scene<LDS, false, TLAS, false, SIMPLE, false, false, true>(a, ro, rd, stack, node_tests, tri_tests, I);
+            float4* o = static_cast<float4*>(out) + 4 * i;
+            if (valid && h.hit && h.dst < tmax) {
+                const bool sphere = !SIMPLE && I.object < 0;
+                const uint32_t object = (h.mat_off - a.lay.mat_off) / MATERIAL_BYTES;
+                const uint32_t prim = sphere ? (uint32_t)(-I.object - 1) : (I.win_tri & 0x7fffffffu);
+                const float bu = sphere ? 0.0f : I.win_u, bv = sphere ? 0.0f : I.win_v;
+                o[0] = make_float4(h.dst, __uint_as_float(object), __uint_as_float(prim), __uint_as_float(1u | (h.backface ? 2u : 0u)));
+                o[1] = make_float4(h.point.x, h.point.y, h.point.z, bu);
+                o[2] = make_float4(h.normal.x, h.normal.y, h.normal.z, bv);
+                o[3] = make_float4(h.u, h.v, 0.0f, 0.0f);
+            } else {
+                o[0] = make_float4(__builtin_inff(), __uint_as_float(0xffffffffu), __uint_as_float(0xffffffffu), 0.0f);
+                o[1] = o[2] = o[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+    }
+}
+
+// rt_pick: the ray rt_debug_kernel traces for texel (x, y) -- the same operations -- as one rt_ray with tmax = +inf
+__global__ void rt_pick_ray_kernel(const RenderArgs a, uint32_t x, uint32_t y, float4* __restrict__ ray) {
+    const float sx = (float)a.params.width, sy = (float)a.params.height;
+    const float fx = (float)x, fy = (float)y;
+    const float* __restrict__ c2w = &a.camera.cam_to_world[0][0];
+    const f3 cam_origin{c2w[12], c2w[13], c2w[14]};
+    const float uvx = fx / (sx - 1.0f), uvy = fy / (sy - 1.0f);
+    const f3 local_focus = f3{uvx - 0.5f, uvy - 0.5f, 1.0f} *
+                           f3{a.camera.view_params[0], a.camera.view_params[1], a.camera.view_params[2]};
+    const f3 focus_point = mat_xyz(c2w, local_focus, 1.0f);
+    const f3 d = focus_point - cam_origin;  // (not normalised here: the query kernel's normalize3 is rt_debug_kernel's)
+    ray[0] = make_float4(cam_origin.x, cam_origin.y, cam_origin.z, __builtin_inff());
+    ray[1] = make_float4(d.x, d.y, d.z, 0.0f);
+}
+
+hipError_t launch_pick_ray(const RenderArgs& a, uint32_t x, uint32_t y, float4* ray, hipStream_t stream) {
+    hipLaunchKernelGGL(rt_pick_ray_kernel, dim3(1), dim3(1), 0, stream, a, x, y, ray);
+    return hipGetLastError();
+}
+
+// any: occlusion (out: u32 per ray), else closest hit (out: rt_hit per ray).  The persistent grid: at least `blocks`
+// workgroups (the render's persistent grid), raised to what the query kernel itself keeps resident on compute_units CUs
+// -- its registers allow more waves per SIMD than the render kernels' budget (measured: the render's grid of 4 waves
+// per SIMD was slower than one workgroup per 256 rays) -- and at most one workgroup per 256 rays.
+hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long long n, void* out, bool any, bool prune_tmax,
+                        uint32_t blocks, uint32_t compute_units, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t lds = render_lds_bytes(a);
+    const unsigned long long need = (n + BLOCK_THREADS - 1) / BLOCK_THREADS;
+    auto go = [&](auto kernel) {
+        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK_THREADS, lds) == hipSuccess && per_cu > 0 &&
+            (unsigned long long)per_cu * compute_units > blocks)
+            blocks = (uint32_t)per_cu * compute_units;
+        if (need < blocks) blocks = (uint32_t)need;
+        if (blocks == 0) blocks = 1;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, static_cast<const float4*>(rays), n, out,
+                           prune_tmax ? 1u : 0u);
+    };
+    // launch_variant's choice: the SIMPLE instantiation for the few-mesh product kernels of a plain scene
+    const bool tlas = a.many_mesh != 0u, simple = !tlas && a.simple != 0u;
+    if (a.lds_scene) {
+        if (tlas) any ? go(rt_query_kernel<true, true, false, true>) : go(rt_query_kernel<true, true, false, false>);
+        else if (simple) any ? go(rt_query_kernel<true, false, true, true>) : go(rt_query_kernel<true, false, true, false>);
+        else any ? go(rt_query_kernel<true, false, false, true>) : go(rt_query_kernel<true, false, false, false>);
+    } else {
+        if (tlas) any ? go(rt_query_kernel<false, true, false, true>) : go(rt_query_kernel<false, true, false, false>);
+        else if (simple) any ? go(rt_query_kernel<false, false, true, true>) : go(rt_query_kernel<false, false, true, false>);
+        else any ? go(rt_query_kernel<false, false, false, true>) : go(rt_query_kernel<false, false, false, false>);
+    }
     return hipGetLastError();
 }
 

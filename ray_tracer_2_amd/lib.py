@@ -28,6 +28,7 @@ EXPORTS = [
     "rt_scene_num_textures", "rt_scene_spheres", "rt_scene_meshes", "rt_scene_triangles",
     "rt_scene_nodes", "rt_scene_get_texture", "rt_scene_mesh_label", "rt_scene_mesh_data", "rt_scene_num_mesh_instances", "rt_scene_last_error",
     "rt_scene_destroy", "rt_upload_built_scene", "rt_scene_subdivide_meshes", "rt_export_rgba8",
+    "rt_intersect_rays", "rt_occluded_rays", "rt_pick",
 ]
 # every symbol include/rt_test_abi.h declares (the test library only)
 TEST_EXPORTS = ["rt_test_device_units", "rt_test_sweep", "rt_test_device_sample_texture", "rt_test_read_wavefront",
@@ -133,6 +134,9 @@ def _bind(L, with_test_entries):
         "rt_upload_built_scene": (i32, [vp, vp]),
         "rt_scene_subdivide_meshes": (i32, [vp, u32]),
         "rt_export_rgba8": (i32, [vp, u32, u32, vp]),
+        "rt_intersect_rays": (i32, [vp, vp, u64, vp, i32]),
+        "rt_occluded_rays": (i32, [vp, vp, u64, vp, i32]),
+        "rt_pick": (i32, [vp, P(A.Params), u32, u32, P(A.Hit)]),
     }
     assert set(sig) == set(EXPORTS)
     if with_test_entries:

@@ -31,6 +31,7 @@ class RayTracer:
                 self._h = None
             raise RtError(rc, msg)
         self.max_width, self.max_height = max_width, max_height
+        self.device = device
         # tuning knobs for experiments (results never depend on them): RT2_OPTIONS="forest=0,vote_eighths=5"
         for kv in os.environ.get("RT2_OPTIONS", "").split(","):
             if kv.strip():
@@ -179,6 +180,125 @@ class RayTracer:
         self._check(self._L.rt_test_intersect(self._h, ro.ctypes.data, rd.ctypes.data, None if act is None else act.ctypes.data,
                                               n, flags, out.ctypes.data))
         return out
+
+    # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick) ----
+    def trace_rays(self, origins, dirs, tmax=None):
+        """Closest hit of rays (origins[i], dirs[i]) on the uploaded scene, as a render's walk computes it; a hit at
+        t >= tmax[i] is reported as a miss (tmax None: unbounded).  numpy inputs: a synchronous call that returns a
+        numpy structured array of HIT_DTYPE (rt_hit).  Tensors on this handle's device (anything with data_ptr()):
+        an asynchronous call ordered after the current stream's work; returns an (n, 16) int32 tensor of rt_hit records
+        (hits_to_numpy converts it).  Invalid rays get miss records."""
+        rays, dev = self._query_rays(origins, dirs, tmax)
+        n = rays.shape[0]
+        if not dev:
+            hits = np.zeros(n, A.HIT_DTYPE)
+            if n:
+                self._check(self._L.rt_intersect_rays(self._h, rays.ctypes.data, n, hits.ctypes.data, A.QUERY_HOST_MEMORY))
+            return hits
+        import torch
+        hits = torch.empty((n, 16), dtype=torch.int32, device=rays.device)
+        self._device_query(self._L.rt_intersect_rays, rays, hits, 0)
+        return hits
+
+    def occluded(self, origins, dirs, tmax, prune=False):
+        """Is there a hit closer than tmax on each ray (shadow rays)?  numpy inputs: a numpy bool array; tensors on this
+        handle's device: a bool tensor (asynchronous).  prune: RT_QUERY_PRUNE_TMAX, the faster walk that is not exact
+        (include/rt_abi.h)."""
+        if tmax is None:
+            raise ValueError("occluded needs tmax")
+        rays, dev = self._query_rays(origins, dirs, tmax)
+        n = rays.shape[0]
+        flags = A.QUERY_PRUNE_TMAX if prune else 0
+        if not dev:
+            occ = np.zeros(n, np.uint32)
+            if n:
+                self._check(self._L.rt_occluded_rays(self._h, rays.ctypes.data, n, occ.ctypes.data, flags | A.QUERY_HOST_MEMORY))
+            return occ != 0
+        import torch
+        occ = torch.empty(n, dtype=torch.int32, device=rays.device)
+        self._device_query(self._L.rt_occluded_rays, rays, occ, flags)
+        return occ != 0
+
+    def pick(self, params, x, y):
+        """The closest hit under texel (x, y) of a params.width x params.height frame (row 0 = bottom), as the debug
+        views trace it: a dict of the rt_hit fields, or None for a miss."""
+        hit = A.Hit()
+        self._check(self._L.rt_pick(self._h, C.byref(params), int(x), int(y), C.byref(hit)))
+        if not hit.flags & A.HIT_HIT:
+            return None
+        return {"t": hit.t, "object": hit.object, "primitive": hit.primitive, "backface": bool(hit.flags & A.HIT_BACKFACE),
+                "point": tuple(hit.point), "normal": tuple(hit.normal), "bary": (hit.bary_u, hit.bary_v),
+                "uv": (hit.tex_u, hit.tex_v)}
+
+    @staticmethod
+    def hits_to_numpy(hits):
+        """rt_hit records of trace_rays' device path -> numpy structured array of HIT_DTYPE (synchronises)."""
+        return np.ascontiguousarray(hits.cpu().numpy()).view(A.HIT_DTYPE).reshape(-1)
+
+    def _query_rays(self, origins, dirs, tmax):
+        """Packs rt_ray records: (numpy (n, 8) f32 view, False) or (torch (n, 8) f32 tensor on this device, True)."""
+        dev = hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr") or hasattr(tmax, "data_ptr")
+        if dev:
+            import torch
+            ts = [t for t in (origins, dirs, tmax) if t is not None]
+            if not all(isinstance(t, torch.Tensor) for t in ts if not np.isscalar(t)) or any(isinstance(t, np.ndarray) for t in ts):
+                raise ValueError("mix of device tensors and host arrays")
+            for t in ts:
+                if isinstance(t, torch.Tensor):
+                    if t.dtype != torch.float32:
+                        raise ValueError(f"ray tensors must be float32, not {t.dtype}")
+                    if t.device.type != "cuda" or t.device.index != self.device:
+                        raise ValueError(f"ray tensors must be on cuda:{self.device}, not {t.device}")
+            if origins.dim() != 2 or origins.shape[1] != 3 or tuple(dirs.shape) != tuple(origins.shape):
+                raise ValueError("origins and dirs must both have shape (n, 3)")
+            n = origins.shape[0]
+            if tmax is None:
+                tm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=origins.device)
+            elif isinstance(tmax, torch.Tensor):
+                if tmax.dim() == 0:
+                    tm = tmax.reshape(1, 1).expand(n, 1)
+                elif tuple(tmax.shape) == (n,):
+                    tm = tmax.reshape(n, 1)
+                else:
+                    raise ValueError("tmax must be a scalar or have shape (n,)")
+            else:
+                tm = torch.full((n, 1), float(tmax), dtype=torch.float32, device=origins.device)
+            pad = torch.zeros((n, 1), dtype=torch.float32, device=origins.device)   # (_p0 = 0: +0.0 bits)
+            return torch.cat([origins, tm, dirs, pad], dim=1).contiguous(), True
+        o, d = np.asarray(origins), np.asarray(dirs)
+        for name, v in (("origins", o), ("dirs", d)):
+            if v.dtype.kind != "f":
+                raise ValueError(f"{name} must be a floating-point array, not {v.dtype}")
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("origins and dirs must both have shape (n, 3)")
+        n = o.shape[0]
+        rays = np.zeros(n, A.RAY_DTYPE)
+        rays["origin"] = o
+        rays["dir"] = d
+        if tmax is None:
+            rays["tmax"] = np.inf
+        else:
+            t = np.asarray(tmax)
+            if t.dtype.kind not in "fiu":
+                raise ValueError(f"tmax must be numeric, not {t.dtype}")
+            if t.ndim != 0 and t.shape != (n,):
+                raise ValueError("tmax must be a scalar or have shape (n,)")
+            rays["tmax"] = t
+        return rays, False
+
+    def _device_query(self, fn, rays, out, flags):
+        """Runs fn on the handle's stream, ordered after the current torch stream's work and before what follows on it."""
+        import torch
+        n = rays.shape[0]
+        if n == 0:
+            return
+        cur = torch.cuda.current_stream(rays.device)
+        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=rays.device)
+        ext.wait_stream(cur)
+        self._check(fn(self._h, rays.data_ptr(), n, out.data_ptr(), flags))
+        # (rays and out belong to the current stream, which now waits for the query: a later reuse of their memory is
+        # ordered after it -- no record_stream on the handle's stream, which rt_destroy may destroy before they are freed)
+        cur.wait_stream(ext)
 
     def stats(self):
         s = A.Stats()

@@ -207,6 +207,21 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
                     const rt_packed_triangle* triangles, uint32_t n_triangles,
                     const rt_node* nodes, uint32_t n_nodes);
 
+/* The per-instance part of update_buffers: new SceneUniform, spheres and mesh uniforms for the scene of the
+ * last successful rt_upload_scene / rt_upload_built_scene.  Triangles and BVH nodes stay those of that upload.
+ * n_meshes and, per mesh, node_offset / triangle_offset / triangles must equal the uploaded ones; transforms,
+ * materials, the camera and every sphere (count included, <= 500) may change.  The handle afterwards is exactly
+ * what rt_upload_scene with the same arrays and the uploaded triangles / nodes would leave: same blob bytes, same
+ * kernel choice, same images.  Only the blob's head (everything before the BVH / triangle records) is rebuilt and
+ * sent: in place when its size is unchanged, else into a new allocation with the old tail copied device to device.
+ * Like rt_upload_scene it waits for the launches already enqueued, drops frames rendered ahead and invalidates the
+ * primary tables.  Errors: RT_ERR_NO_SCENE (nothing uploaded), RT_ERR_INVALID_ARGUMENT (a changed mesh count or
+ * mesh offsets -- rt_last_error names the mesh --, counts that disagree with the SceneUniform, null arrays with
+ * non-zero counts), RT_ERR_CAPACITY (more than 500 spheres), RT_ERR_OUT_OF_MEMORY (no room for a resized blob).
+ * On any error nothing changes.  DESIGN.md section 2.8. */
+int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere* spheres, uint32_t n_spheres,
+                        const rt_mesh_uniform* meshes, uint32_t n_meshes);
+
 /* ≙ RayTracer::load_scene_gpu_resources (ray_tracer.rs:237-315). n <= 64. */
 int rt_upload_textures(rt_handle* h, const rt_texture_desc* descs, uint32_t n);
 
@@ -560,6 +575,17 @@ void rt_scene_destroy(rt_scene* s);
 /* Convenience: upload everything a built scene holds to a device handle
  * (≙ load_scene_gpu_resources + update_buffers). */
 int rt_upload_built_scene(rt_handle* h, const rt_scene* s);
+/* rt_update_instances from a built rt_scene whose geometry is the one uploaded (after the setters below). */
+int rt_update_built_scene(rt_handle* h, const rt_scene* s);
+
+/* Inspector edits of a scene (≙ the egui drag widgets, src/rendering/egui.rs:240-330).  i is a mesh instance
+ * (rt_scene_num_mesh_instances) / a sphere index.  On a built scene the instance's rt_mesh_uniform is rewritten the
+ * way rt_scene_build makes it (Transform::to_matrix and its inverse, the material); the BVH is not rebuilt and the
+ * scene stays built, so rt_update_built_scene sends the change.  A bad index or a null pointer gives
+ * RT_ERR_INVALID_ARGUMENT (rt_scene_last_error says which). */
+int rt_scene_set_mesh_transform(rt_scene* s, uint32_t i, const rt_transform* t);
+int rt_scene_set_mesh_material(rt_scene* s, uint32_t i, const rt_material* m);
+int rt_scene_set_sphere(rt_scene* s, uint32_t i, const float centre[3], float radius, const rt_material* m);
 
 /* Uniform n x n barycentric split of every triangle of every mesh added so
  * far (SURVEY 8d stand-in for the missing Dragon_80K / dragon_large assets). */

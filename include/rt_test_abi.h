@@ -46,6 +46,11 @@ int rt_test_device_sample_texture(rt_handle* h, const rt_texture_desc* tex, cons
 int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint8_t* active, uint64_t n, int flags,
                       uint32_t* out);
 
+/* Test-only: the uploaded scene's blob as the kernels read it (out may be NULL; else bytes >= its size, which
+ * layout_out[9] gives), its SceneLayout (csrc/rt_device.h, 12 words) and its device address.  Waits for the launches
+ * enqueued on the handle's streams. */
+int rt_test_scene_blob(rt_handle* h, void* out, uint64_t bytes, uint32_t layout_out[12], uint64_t* device_ptr);
+
 /* Test-only: raw copy of a buffer of the last wavefront sequence (which: 0 path state, 1 hit records, 2 the two slot
  * lists, 3 the per-round list counts; layouts in csrc/rt_device.h), or (which = 4) the pixels parked in front of each round
  * of the last deferred-walk sequence (72 u32), or (which = 5, 6) the park records of its even / odd rounds. */

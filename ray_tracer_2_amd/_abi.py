@@ -121,6 +121,10 @@ HIT_HIT, HIT_BACKFACE = 1, 2
 QUERY_HOST_MEMORY, QUERY_PRUNE_TMAX = 1, 2
 MISS = 0xFFFFFFFF
 
+# SceneLayout (csrc/rt_device.h): the 12 words rt_test_scene_blob returns; the head of the blob is [0, wide_off)
+SCENE_LAYOUT_FIELDS = ("mesh_off", "wide_off", "tri_off", "shade_off", "mat_off", "sphere_off", "item_off", "tlas_off",
+                       "forest_off", "bytes", "_pad0", "_pad1")
+
 RT_OK = 0
 MATERIAL_DEFAULT, MATERIAL_GLASS, MATERIAL_TEXTURE = 0, 1, 2
 

@@ -66,6 +66,12 @@ static int upload_arrays(rt_handle* h, const Scene& scene) {
                            scene.nodes.data(), (uint32_t)scene.nodes.size());
 }
 
+static int update_instance_arrays(rt_handle* h, const Scene& scene) {
+    rt_scene_uniform u = scene.to_uniform();
+    return rt_update_instances(h, &u, scene.spheres.data(), (uint32_t)scene.spheres.size(), scene.mesh_uniforms.data(),
+                               (uint32_t)scene.mesh_uniforms.size());
+}
+
 int RayTracer::load_scene_gpu_resources(const Scene& scene) {
     if (!h_) return RT_ERR_INVALID_ARGUMENT;
     return upload_textures(h_, scene);
@@ -75,6 +81,11 @@ int RayTracer::update_buffers(Scene& scene) {
     if (!h_) return RT_ERR_INVALID_ARGUMENT;
     if (!scene.built_bvh && !scene.meshes.empty()) scene.build_per_mesh(Quality::High);  // scene.rs:272-278
     return upload_arrays(h_, scene);
+}
+
+int RayTracer::update_instances(const Scene& scene) {
+    if (!h_ || !scene.built_bvh) return RT_ERR_INVALID_ARGUMENT;
+    return update_instance_arrays(h_, scene);
 }
 
 int RayTracer::render(const rt_params& params) { return h_ ? rt_render(h_, &params) : RT_ERR_INVALID_ARGUMENT; }
@@ -92,4 +103,11 @@ extern "C" int rt_upload_built_scene(rt_handle* h, const rt_scene* s) {
     int rc = rt2::upload_textures(h, scene);
     if (rc != RT_OK) return rc;
     return rt2::upload_arrays(h, scene);
+}
+
+extern "C" int rt_update_built_scene(rt_handle* h, const rt_scene* s) {
+    if (!h || !s) return RT_ERR_INVALID_ARGUMENT;
+    const rt2::Scene& scene = rt2::scene_of(s);
+    if (!scene.built_bvh && !scene.meshes.empty()) return RT_ERR_INVALID_ARGUMENT;  // (rt_scene_build, then rt_upload_built_scene)
+    return rt2::update_instance_arrays(h, scene);
 }

@@ -37,6 +37,9 @@ class RayTracer {
     // ≙ update_buffers (:397): scene arrays + SceneUniform.  Call on change;
     // rebuilds the BVH lazily like Scene::bvh_nodes (scene.rs:272-278).
     int update_buffers(Scene& scene);
+    // The per-instance part of update_buffers (rt_update_instances): transforms, materials, spheres and camera of a
+    // built scene whose geometry is the one last uploaded -- after the Scene's setters, without "Rebuild BVH".
+    int update_instances(const Scene& scene);
     // ≙ render (:420): one frame, asynchronous.
     int render(const rt_params& params);
     // ≙ the texture->buffer copy of save_render_to_file (app.rs:341-407).

@@ -282,6 +282,14 @@ bool AssetManager::load_model(const std::string& path, const Transform& transfor
     return true;
 }
 
+// MeshUniform's matrices (bvh.rs:186-190): model_to_world = Transform::to_matrix, world_to_model its inverse
+static void set_uniform_transform(rt_mesh_uniform& u, const Transform& t) {
+    Mat4 m2w = t.to_matrix();
+    Mat4 w2m = mat4_inverse(m2w);
+    memcpy(u.world_to_model, w2m.c, sizeof(w2m.c));
+    memcpy(u.model_to_world, m2w.c, sizeof(m2w.c));
+}
+
 void Scene::build_per_mesh(Quality q, int device, size_t device_min_tris) {  // bvh.rs:152-207
     triangles.clear();
     nodes.clear();
@@ -298,11 +306,8 @@ void Scene::build_per_mesh(Quality q, int device, size_t device_min_tris) {  // 
         } else {
             r = bvh_build(mi.data->vertices, mi.data->indices, q);
         }
-        Mat4 m2w = mi.transform.to_matrix();
-        Mat4 w2m = mat4_inverse(m2w);
         rt_mesh_uniform u{};
-        memcpy(u.world_to_model, w2m.c, sizeof(w2m.c));
-        memcpy(u.model_to_world, m2w.c, sizeof(m2w.c));
+        set_uniform_transform(u, mi.transform);
         u.node_offset = (uint32_t)node_offset;
         u.triangle_offset = (uint32_t)triangle_offset;
         u.triangles = (uint32_t)r.triangles.size();
@@ -314,6 +319,16 @@ void Scene::build_per_mesh(Quality q, int device, size_t device_min_tris) {  // 
         node_offset += r.nodes.size();
     }
     built_bvh = true;
+}
+
+void Scene::set_mesh_transform(size_t i, const Transform& t) {
+    meshes.at(i).transform = t;
+    if (built_bvh && i < mesh_uniforms.size()) set_uniform_transform(mesh_uniforms[i], t);
+}
+
+void Scene::set_mesh_material(size_t i, const rt_material& m) {
+    meshes.at(i).material = m;
+    if (built_bvh && i < mesh_uniforms.size()) mesh_uniforms[i].material = m;
 }
 
 rt_scene_uniform Scene::to_uniform() const {  // scene.rs:985-1001

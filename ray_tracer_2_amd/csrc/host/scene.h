@@ -83,6 +83,10 @@ class Scene {  // scene.rs:148-156
     // device >= 0: meshes of at least `device_min_tris` triangles have their SAH searches done on that
     // GPU (csrc/rt_bvh_search.hip); the result is the same, bit for bit
     void build_per_mesh(Quality q, int device = -2, size_t device_min_tris = 16384);  // -2: plain bvh_build
+    // Inspector edits (egui.rs:240-330) of mesh instance i: its Transform / material, and on a built scene its
+    // rt_mesh_uniform as build_per_mesh makes it -- the BVH stays (it does not depend on the transform), built_bvh too
+    void set_mesh_transform(size_t i, const Transform& t);
+    void set_mesh_material(size_t i, const rt_material& m);
     // ≙ Scene::to_uniform (scene.rs:985-1001)
     rt_scene_uniform to_uniform() const;
     // n x n barycentric split of every mesh triangle (stand-in geometry)

@@ -111,6 +111,39 @@ int rt_scene_add_sphere(rt_scene* s, const float centre[3], float radius, const 
     return RT_OK;
 }
 
+int rt_scene_set_mesh_transform(rt_scene* s, uint32_t i, const rt_transform* t) {
+    if (!s || !t) return RT_ERR_INVALID_ARGUMENT;
+    if (i >= s->scene.meshes.size()) {
+        s->err = "mesh instance " + std::to_string(i) + " out of range (" + std::to_string(s->scene.meshes.size()) + " instances)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    s->scene.set_mesh_transform(i, from_abi(t));
+    return RT_OK;
+}
+
+int rt_scene_set_mesh_material(rt_scene* s, uint32_t i, const rt_material* m) {
+    if (!s || !m) return RT_ERR_INVALID_ARGUMENT;
+    if (i >= s->scene.meshes.size()) {
+        s->err = "mesh instance " + std::to_string(i) + " out of range (" + std::to_string(s->scene.meshes.size()) + " instances)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    s->scene.set_mesh_material(i, *m);
+    return RT_OK;
+}
+
+int rt_scene_set_sphere(rt_scene* s, uint32_t i, const float centre[3], float radius, const rt_material* m) {
+    if (!s || !centre || !m) return RT_ERR_INVALID_ARGUMENT;
+    if (i >= s->scene.spheres.size()) {
+        s->err = "sphere " + std::to_string(i) + " out of range (" + std::to_string(s->scene.spheres.size()) + " spheres)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    rt_sphere& sp = s->scene.spheres[i];
+    memcpy(sp.pos, centre, 12);
+    sp.radius = radius;
+    sp.material = *m;
+    return RT_OK;
+}
+
 int rt_scene_add_obj(rt_scene* s, const char* assets_dir, const char* path, const rt_transform* t,
                      int use_mtl, const rt_material* m) {
     if (!s || !path) return RT_ERR_INVALID_ARGUMENT;

@@ -63,6 +63,31 @@ hipError_t diag_wave_times(unsigned long long* out);
 
 using namespace rtd;
 
+// Per-mesh facts of an uploaded scene that depend only on its triangles, nodes and offsets (rt_upload_scene's geometry
+// phase, rt_update_instances reuses them): O(meshes), no triangle or node array is kept on the host.
+struct MeshGeom {
+    uint32_t node_offset = 0, triangle_offset = 0, triangles = 0;  // as uploaded: an update must keep them
+    uint32_t wide_base = 0, internal = 0;                           // first wide record, internal nodes
+    uint32_t root_idx = 0, root_count = 0;                          // the root: record index, or triangle index + count (leaf)
+    uint32_t tri_lo = 0xffffffffu, tri_hi = 0u;                     // triangle range of the leaves
+    uint32_t need = 0;                                              // stack entries of its walk
+    float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};             // the root node's box
+    bool deep = false;          // height >= 32: the shader's literal stack (DMESH_DEEP)
+    bool contains = false;      // internal root whose box provably contains its children's (finite, proper)
+    bool flat2_shape = false;   // internal, not deep, two leaf children (ITEM_FLAT2 when the scene allows it)
+    bool hierarchy_ok = false;  // not deep, and a proper bounding hierarchy (cross-mesh pruning)
+};
+struct SceneGeom {
+    std::vector<MeshGeom> mesh;
+    uint32_t n_nodes = 0, n_triangles = 0, n_wide = 0;
+    uint32_t max_height = 0, max_leaf_ref = 0;  // (largest triangle count of a leaf that can go on a stack)
+    uint32_t top_mesh_records = 0, top_mesh_base = 0;
+    bool roots_are_unions = true, any_deep = false;
+    uint64_t tail_bytes() const {
+        return (uint64_t)n_wide * WIDE_REC_BYTES + (uint64_t)n_triangles * (TRI_ISECT_BYTES + TRI_SHADE_BYTES);
+    }
+};
+
 struct rt_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -263,6 +288,7 @@ struct rt_handle {
     // scene
     bool have_scene = false;
     float4* blob = nullptr;  // the scene, see rt_device.h
+    SceneGeom geom;          // the geometry phase's facts of the uploaded scene (rt_update_instances)
     SceneLayout lay{};
     bool lds_scene = false;
     bool roots_are_unions = false;  // every internal root's box is the exact union of its children's
@@ -578,6 +604,637 @@ void rt_destroy(rt_handle* h) {
     delete h;
 }
 
+}  // extern "C"
+
+// ---- rt_upload_scene / rt_update_instances: one upload in two phases ---------------------------------------------------
+// The blob (rt_device.h) is a head -- mesh records, materials, spheres, items, top-level trees, forest entries -- and a
+// tail from wide_off on: wide BVH records, triangle intersection records, shade records.  The tail holds record and
+// triangle indices, never byte offsets, so its bytes do not depend on where it starts.  The geometry phase builds the tail
+// and the per-mesh facts that depend only on triangles / nodes / offsets (kept on the handle: O(meshes)); the instance
+// phase builds the head from those facts and the transforms, materials and spheres.  rt_upload_scene runs both,
+// rt_update_instances only the second.
+namespace {
+
+struct WideRec { float4 q[4]; };
+
+int build_geometry(rt_handle* h, const rt_mesh_uniform* meshes, uint32_t n_meshes, const rt_packed_triangle* triangles,
+                   uint32_t n_triangles, const rt_node* nodes, uint32_t n_nodes, SceneGeom& g, std::vector<float4>& tail) {
+    // ---- validation + wide BVH records ---------------------------------
+    std::vector<WideRec> wide;
+    g.mesh.assign(n_meshes, MeshGeom{});
+    g.n_nodes = n_nodes;
+    g.n_triangles = n_triangles;
+    std::vector<uint32_t> wide_index(n_nodes, 0xffffffffu);  // per original node
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        const rt_mesh_uniform& m = meshes[i];
+        MeshGeom& mg = g.mesh[i];
+        mg.node_offset = m.node_offset;
+        mg.triangle_offset = m.triangle_offset;
+        mg.triangles = m.triangles;
+        uint32_t height = 0;
+        std::string why;
+        int rc = mesh_bvh_height(nodes, n_nodes, m.node_offset, m.triangle_offset, n_triangles, height, why);
+        if (rc != RT_OK) return fail(h, rc, "mesh " + std::to_string(i) + ": " + why);
+        // The shader's stack holds 32 entries (wgsl:297); with the near child kept in
+        // registers this kernel needs `height` entries and the shader height + 1.  A
+        // tree of height >= 32 can overflow the shader's stack; such a mesh is traversed
+        // with the shader's literal push/pop and clamped indices (DMESH_DEEP), which
+        // needs the full 32 entries.
+        mg.deep = height + 1 > RT_BVH_STACK;
+        const uint32_t need = mg.deep ? RT_BVH_STACK : height;
+        if (need > g.max_height) g.max_height = need;
+        mg.need = need;
+        // Wide records: internal nodes in DFS pre-order, indexed per mesh.
+        // (Meshes may alias node ranges; records are built per mesh.)
+        mg.wide_base = (uint32_t)wide.size();
+        const rt_node* mn = nodes + m.node_offset;
+        for (int k = 0; k < 3; ++k) { mg.box_lo[k] = mn[0].aabb_min[k]; mg.box_hi[k] = mn[0].aabb_max[k]; }
+        // (child and root indices are absolute: triangle index into the scene's triangle
+        // array, wide-record index into the scene's record array)
+        if (mn[0].count > 0) {
+            mg.root_idx = m.triangle_offset + mn[0].first;
+            mg.root_count = mn[0].count;
+            mg.tri_lo = mg.root_idx;
+            mg.tri_hi = mg.root_idx + mg.root_count;
+            continue;
+        }
+        mg.root_idx = mg.wide_base;
+        mg.root_count = 0;
+        // Record order: the first TOP_BFS internal nodes breadth-first from the root (any prefix of
+        // them is a "top of the tree": what the render kernels stage into LDS for a big mesh), the
+        // rest in depth-first pre-order below them.
+        std::vector<uint32_t> order;  // original mesh-local indices of internal nodes
+        std::vector<uint32_t> frontier{0u}, st;
+        constexpr size_t TOP_BFS = 2048;
+        for (size_t q = 0; q < frontier.size(); ++q) {
+            const uint32_t n = frontier[q];
+            if (order.size() >= TOP_BFS) { st.push_back(n); continue; }
+            wide_index[m.node_offset + n] = (uint32_t)order.size();
+            order.push_back(n);
+            if (mn[mn[n].left].count == 0) frontier.push_back(mn[n].left);
+            if (mn[mn[n].right].count == 0) frontier.push_back(mn[n].right);
+        }
+        std::reverse(st.begin(), st.end());  // (pop order = breadth-first order of the cut)
+        while (!st.empty()) {
+            uint32_t n = st.back();
+            st.pop_back();
+            wide_index[m.node_offset + n] = (uint32_t)order.size();
+            order.push_back(n);
+            if (mn[mn[n].right].count == 0) st.push_back(mn[n].right);
+            if (mn[mn[n].left].count == 0) st.push_back(mn[n].left);
+        }
+        if (order.size() > g.top_mesh_records) {  // the biggest BVH gets the LDS-staged top
+            g.top_mesh_records = (uint32_t)order.size();
+            g.top_mesh_base = mg.wide_base;
+        }
+        for (uint32_t n : order) {
+            const rt_node &ca = mn[mn[n].left], &cb = mn[mn[n].right];
+            auto kind = [&](const rt_node& c, uint32_t local, uint32_t& idx, uint32_t& cnt) {
+                if (c.count > 0) {
+                    idx = m.triangle_offset + c.first;
+                    cnt = c.count;
+                    if (cnt > g.max_leaf_ref) g.max_leaf_ref = cnt;
+                    mg.tri_lo = std::min(mg.tri_lo, idx);
+                    mg.tri_hi = std::max(mg.tri_hi, idx + cnt);
+                } else {
+                    idx = mg.wide_base + wide_index[m.node_offset + local];
+                    cnt = 0;
+                }
+            };
+            uint32_t ai, ac, bi, bc;
+            kind(ca, mn[n].left, ai, ac);
+            kind(cb, mn[n].right, bi, bc);
+            auto asf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+            WideRec w;
+            w.q[0] = make_float4(ca.aabb_min[0], ca.aabb_max[0], ca.aabb_min[1], ca.aabb_max[1]);
+            w.q[1] = make_float4(ca.aabb_min[2], ca.aabb_max[2], asf(ai), asf(ac));
+            w.q[2] = make_float4(cb.aabb_min[0], cb.aabb_max[0], cb.aabb_min[1], cb.aabb_max[1]);
+            w.q[3] = make_float4(cb.aabb_min[2], cb.aabb_max[2], asf(bi), asf(bc));
+            wide.push_back(w);
+        }
+    }
+    g.n_wide = (uint32_t)wide.size();
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        MeshGeom& mg = g.mesh[i];
+        mg.internal = (i + 1 < n_meshes ? g.mesh[i + 1].wide_base : g.n_wide) - mg.wide_base;
+        const rt_node* mn = nodes + meshes[i].node_offset;
+        g.any_deep = g.any_deep || mg.deep;
+        // (the root box provably contains its children's boxes -- root_box_ok below adds "walked with the ordinary
+        // stack"; the root-box shortcut, roots_are_unions, needs the same containment of proper child boxes)
+        if (mn[0].count == 0) {
+            const rt_node &ca = mn[mn[0].left], &cb = mn[mn[0].right];
+            bool contains = true, unions = true;
+            for (int k = 0; k < 3; ++k) {
+                const float lo_k = ca.aabb_min[k] < cb.aabb_min[k] ? ca.aabb_min[k] : cb.aabb_min[k];
+                const float hi_k = ca.aabb_max[k] > cb.aabb_max[k] ? ca.aabb_max[k] : cb.aabb_max[k];
+                // the root box may also be larger than the union (still conservative)
+                if (!(mn[0].aabb_min[k] <= lo_k && mn[0].aabb_max[k] >= hi_k)) contains = unions = false;
+                // (and the children must be proper boxes, or the interval argument does not hold)
+                if (!(ca.aabb_min[k] <= ca.aabb_max[k] && cb.aabb_min[k] <= cb.aabb_max[k])) contains = unions = false;
+                if (!(mn[0].aabb_min[k] - mn[0].aabb_min[k] == 0.0f && mn[0].aabb_max[k] - mn[0].aabb_max[k] == 0.0f)) contains = false;  // finite
+            }
+            mg.contains = contains;
+            if (!unions) g.roots_are_unions = false;
+            // (root with two leaf children: a straight-line item in the few-mesh kernels, ITEM_FLAT2)
+            mg.flat2_shape = !mg.deep && ca.count > 0 && cb.count > 0;
+        }
+        // A proper bounding hierarchy (cross-mesh pruning, build_instances): finite boxes, every child box inside its
+        // parent's, every leaf triangle inside its leaf's box (true of the reference's builder; verified, since BVHs may
+        // be foreign).  Only asked of meshes walked with the ordinary stack.
+        if (!mg.deep) {
+            auto finite_box = [](const rt_node& n) {
+                for (int k = 0; k < 3; ++k)
+                    if (!(n.aabb_min[k] <= n.aabb_max[k] && n.aabb_min[k] - n.aabb_min[k] == 0.0f && n.aabb_max[k] - n.aabb_max[k] == 0.0f)) return false;
+                return true;
+            };
+            auto hierarchy_ok = [&]() {
+                std::vector<uint32_t> st{0u};
+                while (!st.empty()) {
+                    const rt_node& n = mn[st.back()];
+                    st.pop_back();
+                    if (!finite_box(n)) return false;
+                    if (n.count > 0) {
+                        for (uint32_t t = 0; t < n.count; ++t) {
+                            const rt_packed_triangle& p = triangles[meshes[i].triangle_offset + n.first + t];
+                            for (const float* v : {p.v1, p.v2, p.v3})
+                                for (int k = 0; k < 3; ++k)
+                                    if (!(v[k] >= n.aabb_min[k] && v[k] <= n.aabb_max[k])) return false;
+                        }
+                    } else {
+                        for (uint32_t c : {n.left, n.right}) {
+                            const rt_node& ch = mn[c];
+                            for (int k = 0; k < 3; ++k)
+                                if (!(ch.aabb_min[k] >= n.aabb_min[k] && ch.aabb_max[k] <= n.aabb_max[k])) return false;
+                            st.push_back(c);
+                        }
+                    }
+                }
+                return true;
+            };
+            mg.hierarchy_ok = hierarchy_ok();
+        }
+    }
+    // ---- the tail: wide records, then the triangle re-layout (see rt_device.h) ----
+    const uint64_t tail_bytes = g.tail_bytes();
+    if (tail_bytes > 0xfffffff0ull) return fail(h, RT_ERR_CAPACITY, "scene larger than 4 GiB");
+    tail.assign(tail_bytes / 16, make_float4(0, 0, 0, 0));
+    if (!wide.empty()) memcpy(tail.data(), wide.data(), wide.size() * sizeof(WideRec));
+    const size_t tri_off = (size_t)g.n_wide * WIDE_REC_BYTES, shade_off = tri_off + (size_t)n_triangles * TRI_ISECT_BYTES;
+    // The subtractions and the cross product are wgsl:261-263, evaluated once here in binary32.
+    for (uint32_t t = 0; t < n_triangles; ++t) {
+        const rt_packed_triangle& p = triangles[t];
+        float abx = p.v2[0] - p.v1[0], aby = p.v2[1] - p.v1[1], abz = p.v2[2] - p.v1[2];
+        float acx = p.v3[0] - p.v1[0], acy = p.v3[1] - p.v1[1], acz = p.v3[2] - p.v1[2];
+        float nx = aby * acz - abz * acy;
+        float ny = abz * acx - abx * acz;
+        float nz = abx * acy - aby * acx;
+        float4* ti = tail.data() + (tri_off + (size_t)t * TRI_ISECT_BYTES) / 16;
+        ti[0] = make_float4(p.v1[0], p.v1[1], p.v1[2], nx);
+        ti[1] = make_float4(abx, aby, abz, ny);
+        ti[2] = make_float4(acx, acy, acz, nz);
+        float4* ts = tail.data() + (shade_off + (size_t)t * TRI_SHADE_BYTES) / 16;
+        ts[0] = make_float4(p.n1[0], p.n1[1], p.n1[2], p.uv10);
+        ts[1] = make_float4(p.n2[0], p.n2[1], p.n2[2], p.uv11);
+        ts[2] = make_float4(p.n3[0], p.n3[1], p.n3[2], p.uv20);
+        ts[3] = make_float4(p.uv21, p.uv30, p.uv31, 0.0f);
+    }
+    return RT_OK;
+}
+
+// What the instance phase decides: the head of the blob and the handle state that goes with it.
+struct SceneInstances {
+    SceneLayout lay{};
+    std::vector<float4> head;  // [0, lay.wide_off)
+    uint32_t n_items = 0, n_tlas_records = 0, n_forest_entries = 0, tlas_entries = 1;
+    bool has_tlas = false, has_forest = false, plain_materials = false;
+    bool have_defer = false;
+    uint32_t defer_mesh = 0, defer_xform = 0, defer_internal = 0;
+};
+
+int build_instances(rt_handle* h, const SceneGeom& g, const rt_sphere* spheres, uint32_t n_spheres,
+                    const rt_mesh_uniform* meshes, uint32_t n_meshes, SceneInstances& out) {
+    const std::vector<MeshGeom>& mg = g.mesh;
+    // ---- mesh-loop items and top-level trees -------------------------------------
+    // Runs of consecutive meshes with bit-identical world_to_model share a local space.
+    // Within a run, meshes with an internal, non-deep root whose box provably contains its
+    // children's go under a TLAS when there are enough of them; every other mesh is a
+    // single item.  (Visit order is free: rt_kernel.hip breaks distance ties by mesh index.)
+    struct Item { uint32_t kind, a, b, n; };
+    std::vector<Item> items;
+    std::vector<WideRec> tlas;
+    struct ForestEntry { float4 q[3]; };
+    std::vector<ForestEntry> forest_entries;
+    uint32_t tlas_depth = 0;
+    // (root_box_ok: the root box provably contains its children's boxes and the mesh is walked with the ordinary stack)
+    auto root_box_ok = [&](uint32_t i) { return !mg[i].deep && mg[i].contains; };
+    // (a tree's reference to a mesh has 9 bits for the mesh and 21 for its root record, rt_device.h)
+    auto tree_ok = [&](uint32_t i) { return root_box_ok(i) && i <= TLAS_REF_MESH_MASK && mg[i].root_idx <= TLAS_REF_ROOT_MASK; };
+    struct Box { float lo[3], hi[3]; };
+    auto asf2 = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+    // recursive split over the root boxes; returns the child reference (idx, count)
+    uint32_t tlas_max_depth = 0;  // set per tree: depth of the balanced tree + 6
+    auto ceil_log2 = [](size_t n) { uint32_t d = 0; while (((size_t)1 << d) < n) ++d; return d; };
+    std::function<void(std::vector<uint32_t>&, size_t, size_t, uint32_t, uint32_t&, uint32_t&, Box&)> build_tlas =
+        [&](std::vector<uint32_t>& ms, size_t b0, size_t e0, uint32_t depth, uint32_t& idx, uint32_t& cnt, Box& box) {
+            if (depth > tlas_depth) tlas_depth = depth;
+            if (e0 - b0 == 1) {
+                const MeshGeom& r = mg[ms[b0]];
+                for (int k = 0; k < 3; ++k) { box.lo[k] = r.box_lo[k]; box.hi[k] = r.box_hi[k]; }
+                idx = r.root_idx | (ms[b0] << TLAS_REF_MESH_SHIFT) |
+                      (meshes[ms[b0]].material.flag == RT_MATERIAL_GLASS ? TLAS_REF_GLASS : 0u);
+                cnt = 1;
+                return;
+            }
+            // Split: surface-area heuristic over the root boxes, swept along each axis in centroid order (the
+            // boxes are few -- one per mesh -- so the full sweep is affordable; a median split put the scene-wide
+            // floor and ceiling meshes of the many-mesh stand-in into the same subtrees as the columns next to
+            // their centroids).  Any split is a correct one: the tree only has to contain its root boxes.
+            auto centroid_less = [&](int axis) {
+                return [&, axis](uint32_t x, uint32_t y) {
+                    const MeshGeom &rx = mg[x], &ry = mg[y];
+                    const float cx = rx.box_lo[axis] + rx.box_hi[axis], cy = ry.box_lo[axis] + ry.box_hi[axis];
+                    return cx < cy || (cx == cy && x < y);
+                };
+            };
+            auto half_area = [](const double* lo3, const double* hi3) {
+                const double dx = hi3[0] - lo3[0], dy = hi3[1] - lo3[1], dz = hi3[2] - lo3[2];
+                return dx * dy + dy * dz + dz * dx;
+            };
+            const size_t cnt_here = e0 - b0;
+            int best_axis = 0;
+            size_t best_left = cnt_here / 2;
+            double best_cost = DBL_MAX;
+            std::vector<double> right_area(cnt_here);
+            for (int axis = 0; axis < 3; ++axis) {
+                std::sort(ms.begin() + b0, ms.begin() + e0, centroid_less(axis));
+                double lo3[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi3[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+                for (size_t q = cnt_here; q-- > 1;) {  // right_area[q]: boxes q .. end
+                    const MeshGeom& r = mg[ms[b0 + q]];
+                    for (int k = 0; k < 3; ++k) {
+                        if (r.box_lo[k] < lo3[k]) lo3[k] = r.box_lo[k];
+                        if (r.box_hi[k] > hi3[k]) hi3[k] = r.box_hi[k];
+                    }
+                    right_area[q] = half_area(lo3, hi3);
+                }
+                for (int k = 0; k < 3; ++k) { lo3[k] = DBL_MAX; hi3[k] = -DBL_MAX; }
+                for (size_t q = 1; q < cnt_here; ++q) {  // left = boxes 0 .. q-1
+                    const MeshGeom& r = mg[ms[b0 + q - 1]];
+                    for (int k = 0; k < 3; ++k) {
+                        if (r.box_lo[k] < lo3[k]) lo3[k] = r.box_lo[k];
+                        if (r.box_hi[k] > hi3[k]) hi3[k] = r.box_hi[k];
+                    }
+                    const double cost = half_area(lo3, hi3) * (double)q + right_area[q] * (double)(cnt_here - q);
+                    if (cost < best_cost) { best_cost = cost; best_axis = axis; best_left = q; }
+                }
+            }
+            // (every lane keeps a tree stack of depth + 2 entries in LDS: a subtree that would not fit below the
+            // depth limit any other way is split in the middle)
+            if (depth + ceil_log2(cnt_here) >= tlas_max_depth) best_left = cnt_here / 2;
+            std::sort(ms.begin() + b0, ms.begin() + e0, centroid_less(best_axis));
+            const size_t mid = b0 + best_left;
+            const uint32_t me = (uint32_t)tlas.size();
+            tlas.emplace_back();
+            uint32_t ai, ac, bi, bc;
+            Box ba, bb;
+            build_tlas(ms, b0, mid, depth + 1, ai, ac, ba);
+            build_tlas(ms, mid, e0, depth + 1, bi, bc, bb);
+            WideRec w;
+            w.q[0] = make_float4(ba.lo[0], ba.hi[0], ba.lo[1], ba.hi[1]);
+            w.q[1] = make_float4(ba.lo[2], ba.hi[2], asf2(ai), asf2(ac));
+            w.q[2] = make_float4(bb.lo[0], bb.hi[0], bb.lo[1], bb.hi[1]);
+            w.q[3] = make_float4(bb.lo[2], bb.hi[2], asf2(bi), asf2(bc));
+            tlas[me] = w;
+            for (int k = 0; k < 3; ++k) {  // exact union (min/max are exact)
+                box.lo[k] = ba.lo[k] < bb.lo[k] ? ba.lo[k] : bb.lo[k];
+                box.hi[k] = ba.hi[k] > bb.hi[k] ? ba.hi[k] : bb.hi[k];
+            }
+            idx = me;
+            cnt = 0;
+        };
+    // Forest items are walked by the few-mesh kernels only: none when the scene gets a top-level
+    // tree anywhere or has enough meshes for automatic root-box culling (many-mesh kernels).
+    bool any_tlas = false;
+    if (h->use_tlas)
+        for (uint32_t i0 = 0; i0 < n_meshes;) {
+            uint32_t i1 = i0 + 1, ok = 0;
+            while (i1 < n_meshes && memcmp(meshes[i1].world_to_model, meshes[i0].world_to_model, 64) == 0) ++i1;
+            for (uint32_t i = i0; i < i1; ++i) ok += tree_ok(i) ? 1u : 0u;
+            if (ok >= (uint32_t)h->tlas_min) any_tlas = true;
+            i0 = i1;
+        }
+    const bool allow_forest = h->use_forest && !any_tlas && n_meshes < 16;
+    // meshes whose root has two leaf children run as straight-line code in the few-mesh kernels (ITEM_FLAT2)
+    auto is_flat2 = [&](uint32_t i) { return h->use_flat2 && !any_tlas && n_meshes < 16 && mg[i].flat2_shape; };
+    for (uint32_t i0 = 0; i0 < n_meshes;) {
+        uint32_t i1 = i0 + 1;
+        while (i1 < n_meshes && memcmp(meshes[i1].world_to_model, meshes[i0].world_to_model, 64) == 0) ++i1;
+        std::vector<uint32_t> grouped;
+        if (h->use_tlas)
+            for (uint32_t i = i0; i < i1; ++i)
+                if (tree_ok(i)) grouped.push_back(i);
+        if (grouped.size() < (size_t)h->tlas_min) grouped.clear();
+        // the other meshes of the run with an internal, non-deep root (and the run's
+        // model_to_world as well) form a forest when there are at least two of them
+        std::vector<uint32_t> forest;
+        if (allow_forest) {
+            size_t g2 = 0;
+            for (uint32_t i = i0; i < i1; ++i) {
+                if (g2 < grouped.size() && grouped[g2] == i) { ++g2; continue; }
+                if (mg[i].root_count == 0 && !mg[i].deep && !is_flat2(i) && memcmp(meshes[i].model_to_world, meshes[i0].model_to_world, 64) == 0)
+                    forest.push_back(i);
+            }
+            if (forest.size() < 2) forest.clear();
+        }
+        bool first = true;
+        auto flag = [&]() { uint32_t f = first ? ITEM_NEW_XFORM : 0u; first = false; return f; };
+        size_t g2 = 0, fo = 0;
+        for (uint32_t i = i0; i < i1; ++i) {
+            if (g2 < grouped.size() && grouped[g2] == i) { ++g2; continue; }
+            if (fo < forest.size() && forest[fo] == i) { ++fo; continue; }
+            items.push_back(Item{flag() | (is_flat2(i) ? ITEM_FLAT2 : 0u), i, i0, 1});
+        }
+        for (size_t f0 = 0; f0 < forest.size(); f0 += FOREST_MAX_MEMBERS) {
+            const size_t f1 = std::min(forest.size(), f0 + (size_t)FOREST_MAX_MEMBERS);
+            items.push_back(Item{ITEM_FOREST | flag(), (uint32_t)forest_entries.size(), i0, (uint32_t)(f1 - f0)});
+            for (size_t f = f0; f < f1; ++f) {
+                const uint32_t i = forest[f];
+                const MeshGeom& r = mg[i];
+                ForestEntry e;
+                uint32_t fl = (meshes[i].material.flag == RT_MATERIAL_GLASS ? DMESH_GLASS : 0u) |
+                              (root_box_ok(i) ? FOREST_CULLABLE : 0u);
+                e.q[0] = make_float4(asf2(r.root_idx), asf2(i), asf2(fl), 0.0f);
+                e.q[1] = make_float4(r.box_lo[0], r.box_hi[0], r.box_lo[1], r.box_hi[1]);
+                e.q[2] = make_float4(r.box_lo[2], r.box_hi[2], 0.0f, 0.0f);
+                forest_entries.push_back(e);
+            }
+        }
+        if (!grouped.empty()) {
+            std::vector<uint32_t> ms = grouped;
+            uint32_t ridx, rcnt;
+            Box rb;
+            tlas_max_depth = 1 + ceil_log2(ms.size()) + 6;
+            build_tlas(ms, 0, ms.size(), 1, ridx, rcnt, rb);
+            items.push_back(Item{ITEM_TLAS | flag(), ridx, i0, (uint32_t)grouped.size()});
+        }
+        i0 = i1;
+    }
+    // Number the tree records breadth-first from the roots (all trees together): any prefix of the array is then
+    // "the top levels", which is what option "lds_tlas" stages into LDS when the whole tree does not fit.
+    if (!tlas.empty()) {
+        std::vector<uint32_t> order, new_of(tlas.size(), 0xffffffffu);
+        auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+        for (const Item& it : items)
+            if (it.kind & ITEM_TLAS) order.push_back(it.a);
+        for (size_t q = 0; q < order.size(); ++q) {
+            const WideRec& w = tlas[order[q]];
+            if (bits(w.q[1].w) == 0u) order.push_back(bits(w.q[1].z));  // child a is a tree node
+            if (bits(w.q[3].w) == 0u) order.push_back(bits(w.q[3].z));
+        }
+        if (order.size() == tlas.size()) {
+            for (size_t q = 0; q < order.size(); ++q) new_of[order[q]] = (uint32_t)q;
+            std::vector<WideRec> re(tlas.size());
+            for (size_t q = 0; q < order.size(); ++q) {
+                WideRec w = tlas[order[q]];
+                if (bits(w.q[1].w) == 0u) w.q[1].z = asf2(new_of[bits(w.q[1].z)]);
+                if (bits(w.q[3].w) == 0u) w.q[3].z = asf2(new_of[bits(w.q[3].z)]);
+                re[q] = w;
+            }
+            tlas.swap(re);
+            for (Item& it : items)
+                if (it.kind & ITEM_TLAS) it.a = new_of[it.a];
+        }
+    }
+    // ---- cross-mesh pruning (RenderArgs::cross_prune): which items may be cut, and the order of the loop ----
+    // An item gets ITEM_PRUNE when every mesh of it (a) has the model_to_world of the mesh that gives the item's
+    // local ray, bit for bit -- the kernel's bound on the world distance is derived from that matrix --, (b) is
+    // not glass (no backface culling: a ray leaving a surface is not culled against the coplanar triangles next
+    // to it, the one place where the triangle test's parameter is noise), (c) is walked with
+    // the ordinary stack, and (d) has a BVH that is a proper bounding hierarchy (MeshGeom::hierarchy_ok).
+    auto mesh_prune_ok = [&](uint32_t i, uint32_t xform_mesh) {
+        return !mg[i].deep && meshes[i].material.flag != RT_MATERIAL_GLASS && mg[i].hierarchy_ok &&
+               memcmp(meshes[i].model_to_world, meshes[xform_mesh].model_to_world, 64) == 0;
+    };
+    if (any_tlas || n_meshes >= 16) {  // (the scenes the many-mesh kernels render)
+        // members of a tree, per tree item (the trees are not renumbered again below)
+        auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+        for (Item& it : items) {
+            bool ok = true;
+            if (it.kind & ITEM_TLAS) {
+                std::vector<uint32_t> st{it.a};
+                while (!st.empty() && ok) {
+                    const WideRec w = tlas[st.back()];
+                    st.pop_back();
+                    for (int c = 0; c < 2 && ok; ++c) {
+                        const uint32_t idx = bits(w.q[2 * c + 1].z), cnt = bits(w.q[2 * c + 1].w);
+                        if (cnt == 0u) st.push_back(idx);
+                        else ok = mesh_prune_ok((idx >> TLAS_REF_MESH_SHIFT) & TLAS_REF_MESH_MASK, it.b);
+                    }
+                }
+            } else if (it.kind & ITEM_FOREST) {
+                ok = false;  // (few-mesh kernels only)
+            } else {
+                ok = mg[it.a].root_count == 0u && mesh_prune_ok(it.a, it.b);
+            }
+            if (ok) it.kind |= ITEM_PRUNE;
+        }
+        // The loop's order is free (ties between equal world distances go to the lower mesh index, rt_kernel.hip):
+        // first the meshes whose root is a leaf (the whole wave tests their triangles in step), then the other
+        // single meshes, then the trees, so that the long walks start with a closest hit to prune against.  Inside
+        // a class the order stays; an item opens its local space when its class's previous item had another one.
+        std::vector<Item> ordered;
+        for (int cls = 0; cls < 3; ++cls) {
+            bool first = true;
+            uint32_t prev_b = 0;
+            for (const Item& it0 : items) {
+                const int c = (it0.kind & ITEM_TLAS) ? 2 : ((it0.kind & ITEM_FOREST) || mg[it0.a].root_count == 0u) ? 1 : 0;
+                if (c != cls) continue;
+                Item it = it0;
+                it.kind &= ~(uint32_t)ITEM_NEW_XFORM;
+                if (first || it.b != prev_b) it.kind |= ITEM_NEW_XFORM;
+                first = false;
+                prev_b = it.b;
+                ordered.push_back(it);
+            }
+        }
+        // (classes follow each other: the first item of a class whose local space is the previous class's last one
+        // need not open it again)
+        for (size_t k = 1; k < ordered.size(); ++k)
+            if (ordered[k].b == ordered[k - 1].b) ordered[k].kind &= ~(uint32_t)ITEM_NEW_XFORM;
+        items.swap(ordered);
+    }
+    // (one entry is always there: the many-mesh kernels, which the debug views use too,
+    // run single meshes through the same stack)
+    out.tlas_entries = tlas.empty() ? 1u : tlas_depth + 2u;
+    out.has_tlas = !tlas.empty();
+
+    // ---- the deferred mesh (RenderArgs::park) ----------------------------------------------
+    // The biggest single-mesh item of a few-mesh scene with a real BVH:
+    // its item goes to the end of the mesh loop (the loop's order is free), where a launch can stop in front
+    // of it.
+    out.have_defer = false;
+    if (!any_tlas && n_meshes < 16) {
+        size_t best_k = items.size();
+        uint32_t best_big = 0;
+        for (size_t k = 0; k < items.size(); ++k) {
+            const Item& it = items[k];
+            if (it.kind & (ITEM_TLAS | ITEM_FOREST | ITEM_FLAT2)) continue;
+            const uint32_t mi = it.a;
+            if (mg[mi].root_count != 0) continue;
+            const uint32_t internal = mg[mi].internal;
+            if (internal >= (uint32_t)h->defer_min_nodes && internal > best_big) { best_big = internal; best_k = k; }
+        }
+        if (best_k < items.size()) {
+            Item d = items[best_k];
+            items.erase(items.begin() + (std::ptrdiff_t)best_k);
+            // (the item that followed it in the same local space now opens that space)
+            if ((d.kind & ITEM_NEW_XFORM) && best_k < items.size() && !(items[best_k].kind & ITEM_NEW_XFORM)) items[best_k].kind |= ITEM_NEW_XFORM;
+            d.kind |= ITEM_NEW_XFORM | ITEM_DEFER | (mg[d.a].contains ? ITEM_DEFER_CULL : 0u);
+            items.push_back(d);
+            out.have_defer = true;
+            out.defer_mesh = d.a;
+            out.defer_xform = d.b;
+            out.defer_internal = best_big;
+        }
+    }
+
+    // ---- blob layout ------------------------------------------------------
+    SceneLayout lay{};
+    uint64_t off = 0;
+    // (the per-scene sections first, the per-node / per-triangle arrays last: the small blob of the hybrid launches has
+    // the same sections with shorter arrays, so every offset up to wide_off is the same in both -- the primary-ray memo
+    // keeps a material's byte offset across launches that read different blobs)
+    lay.mesh_off = (uint32_t)off;   off += (uint64_t)n_meshes * MESH_REC_BYTES;
+    lay.mat_off = (uint32_t)off;    off += (uint64_t)(n_meshes + n_spheres) * MATERIAL_BYTES;
+    lay.sphere_off = (uint32_t)off; off += (uint64_t)n_spheres * SPHERE_BYTES;
+    lay.item_off = (uint32_t)off;   off += (uint64_t)items.size() * ITEM_BYTES;
+    lay.tlas_off = (uint32_t)off;   off += (uint64_t)tlas.size() * WIDE_REC_BYTES;
+    lay.forest_off = (uint32_t)off; off += (uint64_t)forest_entries.size() * FOREST_ENTRY_BYTES;
+    lay.wide_off = (uint32_t)off;   off += (uint64_t)g.n_wide * WIDE_REC_BYTES;
+    lay.tri_off = (uint32_t)off;    off += (uint64_t)g.n_triangles * TRI_ISECT_BYTES;
+    lay.shade_off = (uint32_t)off;  off += (uint64_t)g.n_triangles * TRI_SHADE_BYTES;
+    if (off == 0) off = 16;
+    if (off > 0xfffffff0ull) return fail(h, RT_ERR_CAPACITY, "scene larger than 4 GiB");
+    lay.bytes = (uint32_t)off;
+    std::vector<float4>& head = out.head;
+    head.assign(lay.wide_off / 16, make_float4(0, 0, 0, 0));
+    auto asf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        const rt_mesh_uniform& m = meshes[i];
+        float4* r = head.data() + (lay.mesh_off + (size_t)i * MESH_REC_BYTES) / 16;
+        memcpy(r, m.world_to_model, 64);
+        memcpy(r + 4, m.model_to_world, 64);
+        uint32_t flags = 0;
+        if (m.material.flag == RT_MATERIAL_GLASS) flags |= DMESH_GLASS;
+        if (mg[i].deep) flags |= DMESH_DEEP;
+        r[8] = make_float4(asf(flags), asf(mg[i].root_idx), asf(mg[i].root_count), asf(m.triangle_offset));
+        {
+            // S >= the largest absolute row sum of model_to_world's 3 x 3 part ([col][row]), C >= the largest
+            // absolute translation component: in double, then rounded up (cross-mesh pruning's error terms)
+            double S = 0.0, C = 0.0;
+            for (int row = 0; row < 3; ++row) {
+                const double rs = std::fabs((double)m.model_to_world[0][row]) + std::fabs((double)m.model_to_world[1][row]) +
+                                  std::fabs((double)m.model_to_world[2][row]);
+                if (!(rs <= S)) S = rs;  // (NaN sticks)
+                const double tc = std::fabs((double)m.model_to_world[3][row]);
+                if (!(tc <= C)) C = tc;
+            }
+            auto up = [](double d) { float f = (float)d; if ((double)f < d) f = std::nextafter(f, INFINITY); return f; };
+            r[9] = make_float4(asf(mg[i].wide_base), up(S), up(C), 0.0f);
+        }
+        r[10] = make_float4(mg[i].box_lo[0], mg[i].box_hi[0], mg[i].box_lo[1], mg[i].box_hi[1]);
+        r[11] = make_float4(mg[i].box_lo[2], mg[i].box_hi[2], 0.0f, 0.0f);
+        memcpy(head.data() + (lay.mat_off + (size_t)i * MATERIAL_BYTES) / 16, &m.material, MATERIAL_BYTES);
+    }
+    if (!tlas.empty()) memcpy(head.data() + lay.tlas_off / 16, tlas.data(), tlas.size() * sizeof(WideRec));
+    if (!forest_entries.empty())
+        memcpy(head.data() + lay.forest_off / 16, forest_entries.data(), forest_entries.size() * sizeof(ForestEntry));
+    for (size_t k = 0; k < items.size(); ++k) {
+        const Item& it = items[k];
+        const bool single = (it.kind & (ITEM_TLAS | ITEM_FOREST)) == 0;
+        head[lay.item_off / 16 + 2 * k] = make_float4(asf(it.kind), asf(it.a), asf(it.b), asf(single ? mg[it.a].wide_base : it.n));
+        if (single) head[lay.item_off / 16 + 2 * k + 1] = head[(lay.mesh_off + (size_t)it.a * MESH_REC_BYTES) / 16 + 8];
+    }
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        head[(lay.sphere_off + (size_t)i * SPHERE_BYTES) / 16] =
+            make_float4(spheres[i].pos[0], spheres[i].pos[1], spheres[i].pos[2], spheres[i].radius);
+        memcpy(head.data() + (lay.mat_off + (size_t)(n_meshes + i) * MATERIAL_BYTES) / 16,
+               &spheres[i].material, MATERIAL_BYTES);
+    }
+    out.lay = lay;
+    out.n_items = (uint32_t)items.size();
+    out.n_tlas_records = (uint32_t)tlas.size();
+    out.n_forest_entries = (uint32_t)forest_entries.size();
+    out.has_forest = !forest_entries.empty();
+    {
+        bool plain = n_spheres == 0;
+        for (uint32_t i = 0; i < n_meshes && plain; ++i) {
+            const rt_material& m = meshes[i].material;
+            if (m.flag == RT_MATERIAL_GLASS || (m.flag == RT_MATERIAL_TEXTURE && m.diffuse_index != -1)) plain = false;
+        }
+        out.plain_materials = plain;
+    }
+    return RT_OK;
+}
+
+// The handle state of an uploaded scene (after its blob is on the device): the geometry facts and the instance phase's
+// decisions, then the kernel shape that follows from the layout.
+void commit_scene(rt_handle* h, const SceneGeom& g, const SceneInstances& s, uint32_t n_spheres, const rt_camera_uniform& camera) {
+    const SceneLayout& lay = s.lay;
+    h->roots_are_unions = g.roots_are_unions;
+    h->lay = lay;
+    h->n_meshes = (uint32_t)g.mesh.size();
+    h->n_spheres = n_spheres;
+    h->n_nodes = g.n_nodes;
+    h->n_triangles = g.n_triangles;
+    h->stack_entries = g.max_height ? g.max_height : 1;
+    // One-dword stack entries hold 7 bits of leaf count and 24 bits of triangle index; they cost
+    // a few instructions per push/pop, so they are used when they buy occupancy: when two-dword
+    // entries would not leave room for the scene blob and the primary-ray memo in LDS.
+    {
+        const uint64_t fixed = 8u * 3u * 4u * WAVES_PER_BLOCK + (uint64_t)(LANE_STATE_DWORDS + PIXEL_MEMO_DWORDS) * 64u * 4u * WAVES_PER_BLOCK +
+                               (uint64_t)s.tlas_entries * 64u * 4u * WAVES_PER_BLOCK;
+        const uint64_t wide_stacks = (uint64_t)h->stack_entries * 128u * 4u * WAVES_PER_BLOCK;
+        const bool wide_fits = lay.bytes + fixed + wide_stacks <= LDS_BUDGET_BYTES;
+        h->stack_must_wide = g.max_leaf_ref > 127u || g.n_triangles > (1u << 24);
+        h->stack_wide = h->stack_must_wide || wide_fits;
+    }
+    h->tlas_entries = s.tlas_entries;
+    h->has_tlas = s.has_tlas;
+    h->n_tlas_records = s.n_tlas_records;
+    h->any_deep = g.any_deep;
+    h->has_forest = s.has_forest;
+    h->plain_materials = s.plain_materials;
+    h->n_items = s.n_items;
+    h->top_base = g.top_mesh_base;
+    h->top_available = g.top_mesh_records >= 64 ? std::min<uint32_t>(g.top_mesh_records, 2048u) : 0u;
+    h->have_defer = s.have_defer;
+    h->defer_mesh = s.defer_mesh;
+    h->defer_xform = s.defer_xform;
+    h->defer_internal = s.defer_internal;
+    // LDS residency: blob + the four waves' stacks, cost tables and lane state within the
+    // per-workgroup budget (the primary-ray memo goes to LDS only if it still fits, see render_impl)
+    uint64_t stacks = ((uint64_t)h->stack_entries * (h->stack_wide ? 128u : 64u) + (uint64_t)h->tlas_entries * 64u) * sizeof(uint32_t) * WAVES_PER_BLOCK +
+                      8u * 3u * 4u * WAVES_PER_BLOCK + (uint64_t)LANE_STATE_DWORDS * 64u * 4u * WAVES_PER_BLOCK;
+    h->lds_scene = (uint64_t)lay.bytes + stacks <= LDS_BUDGET_BYTES;
+    h->camera = camera;
+    h->have_scene = true;
+    h->history_valid = false;
+    h->primary_valid = false;  // (the table holds hits: a function of the scene)
+    for (auto& st : h->slot_primary) st.valid = false;
+}
+
+// Every launch enqueued so far on any of the handle's streams is complete (they all may read the blob).
+int drain_streams(rt_handle* h) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < rt_handle::PIPE_MAX; ++k)
+        if (h->pipe_stream[k]) HIP_TRY(h, hipStreamSynchronize(h->pipe_stream[k]));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere* spheres,
                     uint32_t n_spheres, const rt_mesh_uniform* meshes, uint32_t n_meshes,
                     const rt_packed_triangle* triangles, uint32_t n_triangles, const rt_node* nodes,
@@ -596,443 +1253,22 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
     HIP_TRY(h, hipSetDevice(h->device));
 
     try {
-        // ---- validation + wide BVH records ---------------------------------
-        struct WideRec { float4 q[4]; };
-        std::vector<WideRec> wide;
-        std::vector<uint32_t> wide_base(n_meshes), root_idx(n_meshes), root_count(n_meshes);
-        std::vector<char> deep(n_meshes, 0);
-        std::vector<uint32_t> tri_lo(n_meshes, 0xffffffffu), tri_hi(n_meshes, 0u), mesh_need(n_meshes, 0u);  // triangle range, stack entries
-        std::vector<uint32_t> wide_index(n_nodes, 0xffffffffu);  // per original node
-        uint32_t max_height = 0, max_leaf_ref = 0;  // (largest triangle count of a leaf that can go on a stack)
-        uint32_t top_mesh_records = 0, top_mesh_base = 0;
-        for (uint32_t i = 0; i < n_meshes; ++i) {
-            const rt_mesh_uniform& m = meshes[i];
-            uint32_t height = 0;
-            std::string why;
-            int rc = mesh_bvh_height(nodes, n_nodes, m.node_offset, m.triangle_offset, n_triangles, height, why);
-            if (rc != RT_OK) return fail(h, rc, "mesh " + std::to_string(i) + ": " + why);
-            // The shader's stack holds 32 entries (wgsl:297); with the near child kept in
-            // registers this kernel needs `height` entries and the shader height + 1.  A
-            // tree of height >= 32 can overflow the shader's stack; such a mesh is traversed
-            // with the shader's literal push/pop and clamped indices (DMESH_DEEP), which
-            // needs the full 32 entries.
-            deep[i] = height + 1 > RT_BVH_STACK;
-            const uint32_t need = deep[i] ? RT_BVH_STACK : height;
-            if (need > max_height) max_height = need;
-            mesh_need[i] = need;
-            // Wide records: internal nodes in DFS pre-order, indexed per mesh.
-            // (Meshes may alias node ranges; records are built per mesh.)
-            wide_base[i] = (uint32_t)wide.size();
-            const rt_node* mn = nodes + m.node_offset;
-            // (child and root indices are absolute: triangle index into the scene's triangle
-            // array, wide-record index into the scene's record array)
-            if (mn[0].count > 0) {
-                root_idx[i] = m.triangle_offset + mn[0].first;
-                root_count[i] = mn[0].count;
-                tri_lo[i] = root_idx[i];
-                tri_hi[i] = root_idx[i] + root_count[i];
-                continue;
-            }
-            root_idx[i] = wide_base[i];
-            root_count[i] = 0;
-            // Record order: the first TOP_BFS internal nodes breadth-first from the root (any prefix of
-            // them is a "top of the tree": what the render kernels stage into LDS for a big mesh), the
-            // rest in depth-first pre-order below them.
-            std::vector<uint32_t> order;  // original mesh-local indices of internal nodes
-            std::vector<uint32_t> frontier{0u}, st;
-            constexpr size_t TOP_BFS = 2048;
-            for (size_t q = 0; q < frontier.size(); ++q) {
-                const uint32_t n = frontier[q];
-                if (order.size() >= TOP_BFS) { st.push_back(n); continue; }
-                wide_index[m.node_offset + n] = (uint32_t)order.size();
-                order.push_back(n);
-                if (mn[mn[n].left].count == 0) frontier.push_back(mn[n].left);
-                if (mn[mn[n].right].count == 0) frontier.push_back(mn[n].right);
-            }
-            std::reverse(st.begin(), st.end());  // (pop order = breadth-first order of the cut)
-            while (!st.empty()) {
-                uint32_t n = st.back();
-                st.pop_back();
-                wide_index[m.node_offset + n] = (uint32_t)order.size();
-                order.push_back(n);
-                if (mn[mn[n].right].count == 0) st.push_back(mn[n].right);
-                if (mn[mn[n].left].count == 0) st.push_back(mn[n].left);
-            }
-            if (order.size() > top_mesh_records) {  // the biggest BVH gets the LDS-staged top
-                top_mesh_records = (uint32_t)order.size();
-                top_mesh_base = wide_base[i];
-            }
-            for (uint32_t n : order) {
-                const rt_node &ca = mn[mn[n].left], &cb = mn[mn[n].right];
-                auto kind = [&](const rt_node& c, uint32_t local, uint32_t& idx, uint32_t& cnt) {
-                    if (c.count > 0) {
-                        idx = m.triangle_offset + c.first;
-                        cnt = c.count;
-                        if (cnt > max_leaf_ref) max_leaf_ref = cnt;
-                        tri_lo[i] = std::min(tri_lo[i], idx);
-                        tri_hi[i] = std::max(tri_hi[i], idx + cnt);
-                    } else {
-                        idx = wide_base[i] + wide_index[m.node_offset + local];
-                        cnt = 0;
-                    }
-                };
-                uint32_t ai, ac, bi, bc;
-                kind(ca, mn[n].left, ai, ac);
-                kind(cb, mn[n].right, bi, bc);
-                auto asf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-                WideRec w;
-                w.q[0] = make_float4(ca.aabb_min[0], ca.aabb_max[0], ca.aabb_min[1], ca.aabb_max[1]);
-                w.q[1] = make_float4(ca.aabb_min[2], ca.aabb_max[2], asf(ai), asf(ac));
-                w.q[2] = make_float4(cb.aabb_min[0], cb.aabb_max[0], cb.aabb_min[1], cb.aabb_max[1]);
-                w.q[3] = make_float4(cb.aabb_min[2], cb.aabb_max[2], asf(bi), asf(bc));
-                wide.push_back(w);
-            }
-        }
-        // ---- mesh-loop items and top-level trees -------------------------------------
-        // Runs of consecutive meshes with bit-identical world_to_model share a local space.
-        // Within a run, meshes with an internal, non-deep root whose box provably contains its
-        // children's go under a TLAS when there are enough of them; every other mesh is a
-        // single item.  (Visit order is free: rt_kernel.hip breaks distance ties by mesh index.)
-        struct Item { uint32_t kind, a, b, n; };
-        std::vector<Item> items;
-        std::vector<WideRec> tlas;
-        struct ForestEntry { float4 q[3]; };
-        std::vector<ForestEntry> forest_entries;
-        uint32_t tlas_depth = 0;
-        // (root_box_contains: the root box provably contains its children's boxes; root_box_ok: ... and the mesh is
-        // walked with the ordinary stack)
-        auto root_box_contains = [&](uint32_t i) {
-            const rt_node* mn = nodes + meshes[i].node_offset;
-            if (mn[0].count > 0) return false;
-            const rt_node &ca = mn[mn[0].left], &cb = mn[mn[0].right];
-            for (int k = 0; k < 3; ++k) {
-                const float lo_k = ca.aabb_min[k] < cb.aabb_min[k] ? ca.aabb_min[k] : cb.aabb_min[k];
-                const float hi_k = ca.aabb_max[k] > cb.aabb_max[k] ? ca.aabb_max[k] : cb.aabb_max[k];
-                if (!(mn[0].aabb_min[k] <= lo_k && mn[0].aabb_max[k] >= hi_k)) return false;
-                if (!(ca.aabb_min[k] <= ca.aabb_max[k] && cb.aabb_min[k] <= cb.aabb_max[k])) return false;
-                if (!(mn[0].aabb_min[k] - mn[0].aabb_min[k] == 0.0f && mn[0].aabb_max[k] - mn[0].aabb_max[k] == 0.0f)) return false;  // finite
-            }
-            return true;
-        };
-        auto root_box_ok = [&](uint32_t i) { return !deep[i] && root_box_contains(i); };
-        // (a tree's reference to a mesh has 9 bits for the mesh and 21 for its root record, rt_device.h)
-        auto tree_ok = [&](uint32_t i) { return root_box_ok(i) && i <= TLAS_REF_MESH_MASK && root_idx[i] <= TLAS_REF_ROOT_MASK; };
-        struct Box { float lo[3], hi[3]; };
-        auto asf2 = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-        // recursive split over the root boxes; returns the child reference (idx, count)
-        uint32_t tlas_max_depth = 0;  // set per tree: depth of the balanced tree + 6
-        auto ceil_log2 = [](size_t n) { uint32_t d = 0; while (((size_t)1 << d) < n) ++d; return d; };
-        std::function<void(std::vector<uint32_t>&, size_t, size_t, uint32_t, uint32_t&, uint32_t&, Box&)> build_tlas =
-            [&](std::vector<uint32_t>& ms, size_t b0, size_t e0, uint32_t depth, uint32_t& idx, uint32_t& cnt, Box& box) {
-                if (depth > tlas_depth) tlas_depth = depth;
-                if (e0 - b0 == 1) {
-                    const rt_node& r = nodes[meshes[ms[b0]].node_offset];
-                    for (int k = 0; k < 3; ++k) { box.lo[k] = r.aabb_min[k]; box.hi[k] = r.aabb_max[k]; }
-                    idx = root_idx[ms[b0]] | (ms[b0] << TLAS_REF_MESH_SHIFT) |
-                          (meshes[ms[b0]].material.flag == RT_MATERIAL_GLASS ? TLAS_REF_GLASS : 0u);
-                    cnt = 1;
-                    return;
-                }
-                // Split: surface-area heuristic over the root boxes, swept along each axis in centroid order (the
-                // boxes are few -- one per mesh -- so the full sweep is affordable; a median split put the scene-wide
-                // floor and ceiling meshes of the many-mesh stand-in into the same subtrees as the columns next to
-                // their centroids).  Any split is a correct one: the tree only has to contain its root boxes.
-                auto centroid_less = [&](int axis) {
-                    return [&, axis](uint32_t x, uint32_t y) {
-                        const rt_node &rx = nodes[meshes[x].node_offset], &ry = nodes[meshes[y].node_offset];
-                        const float cx = rx.aabb_min[axis] + rx.aabb_max[axis], cy = ry.aabb_min[axis] + ry.aabb_max[axis];
-                        return cx < cy || (cx == cy && x < y);
-                    };
-                };
-                auto half_area = [](const double* lo3, const double* hi3) {
-                    const double dx = hi3[0] - lo3[0], dy = hi3[1] - lo3[1], dz = hi3[2] - lo3[2];
-                    return dx * dy + dy * dz + dz * dx;
-                };
-                const size_t cnt_here = e0 - b0;
-                int best_axis = 0;
-                size_t best_left = cnt_here / 2;
-                double best_cost = DBL_MAX;
-                std::vector<double> right_area(cnt_here);
-                for (int axis = 0; axis < 3; ++axis) {
-                    std::sort(ms.begin() + b0, ms.begin() + e0, centroid_less(axis));
-                    double lo3[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi3[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-                    for (size_t q = cnt_here; q-- > 1;) {  // right_area[q]: boxes q .. end
-                        const rt_node& r = nodes[meshes[ms[b0 + q]].node_offset];
-                        for (int k = 0; k < 3; ++k) {
-                            if (r.aabb_min[k] < lo3[k]) lo3[k] = r.aabb_min[k];
-                            if (r.aabb_max[k] > hi3[k]) hi3[k] = r.aabb_max[k];
-                        }
-                        right_area[q] = half_area(lo3, hi3);
-                    }
-                    for (int k = 0; k < 3; ++k) { lo3[k] = DBL_MAX; hi3[k] = -DBL_MAX; }
-                    for (size_t q = 1; q < cnt_here; ++q) {  // left = boxes 0 .. q-1
-                        const rt_node& r = nodes[meshes[ms[b0 + q - 1]].node_offset];
-                        for (int k = 0; k < 3; ++k) {
-                            if (r.aabb_min[k] < lo3[k]) lo3[k] = r.aabb_min[k];
-                            if (r.aabb_max[k] > hi3[k]) hi3[k] = r.aabb_max[k];
-                        }
-                        const double cost = half_area(lo3, hi3) * (double)q + right_area[q] * (double)(cnt_here - q);
-                        if (cost < best_cost) { best_cost = cost; best_axis = axis; best_left = q; }
-                    }
-                }
-                // (every lane keeps a tree stack of depth + 2 entries in LDS: a subtree that would not fit below the
-                // depth limit any other way is split in the middle)
-                if (depth + ceil_log2(cnt_here) >= tlas_max_depth) best_left = cnt_here / 2;
-                std::sort(ms.begin() + b0, ms.begin() + e0, centroid_less(best_axis));
-                const size_t mid = b0 + best_left;
-                const uint32_t me = (uint32_t)tlas.size();
-                tlas.emplace_back();
-                uint32_t ai, ac, bi, bc;
-                Box ba, bb;
-                build_tlas(ms, b0, mid, depth + 1, ai, ac, ba);
-                build_tlas(ms, mid, e0, depth + 1, bi, bc, bb);
-                WideRec w;
-                w.q[0] = make_float4(ba.lo[0], ba.hi[0], ba.lo[1], ba.hi[1]);
-                w.q[1] = make_float4(ba.lo[2], ba.hi[2], asf2(ai), asf2(ac));
-                w.q[2] = make_float4(bb.lo[0], bb.hi[0], bb.lo[1], bb.hi[1]);
-                w.q[3] = make_float4(bb.lo[2], bb.hi[2], asf2(bi), asf2(bc));
-                tlas[me] = w;
-                for (int k = 0; k < 3; ++k) {  // exact union (min/max are exact)
-                    box.lo[k] = ba.lo[k] < bb.lo[k] ? ba.lo[k] : bb.lo[k];
-                    box.hi[k] = ba.hi[k] > bb.hi[k] ? ba.hi[k] : bb.hi[k];
-                }
-                idx = me;
-                cnt = 0;
-            };
-        // Forest items are walked by the few-mesh kernels only: none when the scene gets a top-level
-        // tree anywhere or has enough meshes for automatic root-box culling (many-mesh kernels).
-        bool any_tlas = false;
-        if (h->use_tlas)
-            for (uint32_t i0 = 0; i0 < n_meshes;) {
-                uint32_t i1 = i0 + 1, ok = 0;
-                while (i1 < n_meshes && memcmp(meshes[i1].world_to_model, meshes[i0].world_to_model, 64) == 0) ++i1;
-                for (uint32_t i = i0; i < i1; ++i) ok += tree_ok(i) ? 1u : 0u;
-                if (ok >= (uint32_t)h->tlas_min) any_tlas = true;
-                i0 = i1;
-            }
-        const bool allow_forest = h->use_forest && !any_tlas && n_meshes < 16;
-        // meshes whose root has two leaf children run as straight-line code in the few-mesh kernels (ITEM_FLAT2)
-        auto is_flat2 = [&](uint32_t i) {
-            if (!h->use_flat2 || any_tlas || n_meshes >= 16 || root_count[i] != 0 || deep[i]) return false;
-            const rt_node* mn = nodes + meshes[i].node_offset;
-            return mn[mn[0].left].count > 0 && mn[mn[0].right].count > 0;
-        };
-        for (uint32_t i0 = 0; i0 < n_meshes;) {
-            uint32_t i1 = i0 + 1;
-            while (i1 < n_meshes && memcmp(meshes[i1].world_to_model, meshes[i0].world_to_model, 64) == 0) ++i1;
-            std::vector<uint32_t> grouped;
-            if (h->use_tlas)
-                for (uint32_t i = i0; i < i1; ++i)
-                    if (tree_ok(i)) grouped.push_back(i);
-            if (grouped.size() < (size_t)h->tlas_min) grouped.clear();
-            // the other meshes of the run with an internal, non-deep root (and the run's
-            // model_to_world as well) form a forest when there are at least two of them
-            std::vector<uint32_t> forest;
-            if (allow_forest) {
-                size_t g = 0;
-                for (uint32_t i = i0; i < i1; ++i) {
-                    if (g < grouped.size() && grouped[g] == i) { ++g; continue; }
-                    if (root_count[i] == 0 && !deep[i] && !is_flat2(i) && memcmp(meshes[i].model_to_world, meshes[i0].model_to_world, 64) == 0)
-                        forest.push_back(i);
-                }
-                if (forest.size() < 2) forest.clear();
-            }
-            bool first = true;
-            auto flag = [&]() { uint32_t f = first ? ITEM_NEW_XFORM : 0u; first = false; return f; };
-            size_t g = 0, fo = 0;
-            for (uint32_t i = i0; i < i1; ++i) {
-                if (g < grouped.size() && grouped[g] == i) { ++g; continue; }
-                if (fo < forest.size() && forest[fo] == i) { ++fo; continue; }
-                items.push_back(Item{flag() | (is_flat2(i) ? ITEM_FLAT2 : 0u), i, i0, 1});
-            }
-            for (size_t f0 = 0; f0 < forest.size(); f0 += FOREST_MAX_MEMBERS) {
-                const size_t f1 = std::min(forest.size(), f0 + (size_t)FOREST_MAX_MEMBERS);
-                items.push_back(Item{ITEM_FOREST | flag(), (uint32_t)forest_entries.size(), i0, (uint32_t)(f1 - f0)});
-                for (size_t f = f0; f < f1; ++f) {
-                    const uint32_t i = forest[f];
-                    const rt_node& r = nodes[meshes[i].node_offset];
-                    ForestEntry e;
-                    uint32_t fl = (meshes[i].material.flag == RT_MATERIAL_GLASS ? DMESH_GLASS : 0u) |
-                                  (root_box_ok(i) ? FOREST_CULLABLE : 0u);
-                    e.q[0] = make_float4(asf2(root_idx[i]), asf2(i), asf2(fl), 0.0f);
-                    e.q[1] = make_float4(r.aabb_min[0], r.aabb_max[0], r.aabb_min[1], r.aabb_max[1]);
-                    e.q[2] = make_float4(r.aabb_min[2], r.aabb_max[2], 0.0f, 0.0f);
-                    forest_entries.push_back(e);
-                }
-            }
-            if (!grouped.empty()) {
-                std::vector<uint32_t> ms = grouped;
-                uint32_t ridx, rcnt;
-                Box rb;
-                tlas_max_depth = 1 + ceil_log2(ms.size()) + 6;
-                build_tlas(ms, 0, ms.size(), 1, ridx, rcnt, rb);
-                items.push_back(Item{ITEM_TLAS | flag(), ridx, i0, (uint32_t)grouped.size()});
-            }
-            i0 = i1;
-        }
-        // Number the tree records breadth-first from the roots (all trees together): any prefix of the array is then
-        // "the top levels", which is what option "lds_tlas" stages into LDS when the whole tree does not fit.
-        if (!tlas.empty()) {
-            std::vector<uint32_t> order, new_of(tlas.size(), 0xffffffffu);
-            auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-            for (const Item& it : items)
-                if (it.kind & ITEM_TLAS) order.push_back(it.a);
-            for (size_t q = 0; q < order.size(); ++q) {
-                const WideRec& w = tlas[order[q]];
-                if (bits(w.q[1].w) == 0u) order.push_back(bits(w.q[1].z));  // child a is a tree node
-                if (bits(w.q[3].w) == 0u) order.push_back(bits(w.q[3].z));
-            }
-            if (order.size() == tlas.size()) {
-                for (size_t q = 0; q < order.size(); ++q) new_of[order[q]] = (uint32_t)q;
-                std::vector<WideRec> re(tlas.size());
-                for (size_t q = 0; q < order.size(); ++q) {
-                    WideRec w = tlas[order[q]];
-                    if (bits(w.q[1].w) == 0u) w.q[1].z = asf2(new_of[bits(w.q[1].z)]);
-                    if (bits(w.q[3].w) == 0u) w.q[3].z = asf2(new_of[bits(w.q[3].z)]);
-                    re[q] = w;
-                }
-                tlas.swap(re);
-                for (Item& it : items)
-                    if (it.kind & ITEM_TLAS) it.a = new_of[it.a];
-            }
-        }
-        // ---- cross-mesh pruning (RenderArgs::cross_prune): which items may be cut, and the order of the loop ----
-        // An item gets ITEM_PRUNE when every mesh of it (a) has the model_to_world of the mesh that gives the item's
-        // local ray, bit for bit -- the kernel's bound on the world distance is derived from that matrix --, (b) is
-        // not glass (no backface culling: a ray leaving a surface is not culled against the coplanar triangles next
-        // to it, the one place where the triangle test's parameter is noise), (c) is walked with
-        // the ordinary stack, and (d) has a BVH that is a proper bounding hierarchy: finite boxes, every child box inside
-        // its parent's, every leaf triangle inside its leaf's box (true of the reference's builder; verified, since
-        // BVHs may be foreign).
-        auto hierarchy_ok = [&](uint32_t i) {
-            const rt_mesh_uniform& m = meshes[i];
-            const rt_node* mn = nodes + m.node_offset;
-            auto finite_box = [](const rt_node& n) {
-                for (int k = 0; k < 3; ++k)
-                    if (!(n.aabb_min[k] <= n.aabb_max[k] && n.aabb_min[k] - n.aabb_min[k] == 0.0f && n.aabb_max[k] - n.aabb_max[k] == 0.0f)) return false;
-                return true;
-            };
-            std::vector<uint32_t> st{0u};
-            while (!st.empty()) {
-                const rt_node& n = mn[st.back()];
-                st.pop_back();
-                if (!finite_box(n)) return false;
-                if (n.count > 0) {
-                    for (uint32_t t = 0; t < n.count; ++t) {
-                        const rt_packed_triangle& p = triangles[m.triangle_offset + n.first + t];
-                        for (const float* v : {p.v1, p.v2, p.v3})
-                            for (int k = 0; k < 3; ++k)
-                                if (!(v[k] >= n.aabb_min[k] && v[k] <= n.aabb_max[k])) return false;
-                    }
-                } else {
-                    for (uint32_t c : {n.left, n.right}) {
-                        const rt_node& ch = mn[c];
-                        for (int k = 0; k < 3; ++k)
-                            if (!(ch.aabb_min[k] >= n.aabb_min[k] && ch.aabb_max[k] <= n.aabb_max[k])) return false;
-                        st.push_back(c);
-                    }
-                }
-            }
-            return true;
-        };
-        std::vector<signed char> prune_ok_memo(n_meshes, -1);
-        auto mesh_prune_ok = [&](uint32_t i, uint32_t xform_mesh) {
-            if (prune_ok_memo[i] < 0)
-                prune_ok_memo[i] = (!deep[i] && meshes[i].material.flag != RT_MATERIAL_GLASS && hierarchy_ok(i)) ? 1 : 0;
-            return prune_ok_memo[i] == 1 && memcmp(meshes[i].model_to_world, meshes[xform_mesh].model_to_world, 64) == 0;
-        };
-        if (any_tlas || n_meshes >= 16) {  // (the scenes the many-mesh kernels render)
-            // members of a tree, per tree item (the trees are not renumbered again below)
-            auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-            for (Item& it : items) {
-                bool ok = true;
-                if (it.kind & ITEM_TLAS) {
-                    std::vector<uint32_t> st{it.a};
-                    while (!st.empty() && ok) {
-                        const WideRec w = tlas[st.back()];
-                        st.pop_back();
-                        for (int c = 0; c < 2 && ok; ++c) {
-                            const uint32_t idx = bits(w.q[2 * c + 1].z), cnt = bits(w.q[2 * c + 1].w);
-                            if (cnt == 0u) st.push_back(idx);
-                            else ok = mesh_prune_ok((idx >> TLAS_REF_MESH_SHIFT) & TLAS_REF_MESH_MASK, it.b);
-                        }
-                    }
-                } else if (it.kind & ITEM_FOREST) {
-                    ok = false;  // (few-mesh kernels only)
-                } else {
-                    ok = root_count[it.a] == 0u && mesh_prune_ok(it.a, it.b);
-                }
-                if (ok) it.kind |= ITEM_PRUNE;
-            }
-            // The loop's order is free (ties between equal world distances go to the lower mesh index, rt_kernel.hip):
-            // first the meshes whose root is a leaf (the whole wave tests their triangles in step), then the other
-            // single meshes, then the trees, so that the long walks start with a closest hit to prune against.  Inside
-            // a class the order stays; an item opens its local space when its class's previous item had another one.
-            std::vector<Item> ordered;
-            for (int cls = 0; cls < 3; ++cls) {
-                bool first = true;
-                uint32_t prev_b = 0;
-                for (const Item& it0 : items) {
-                    const int c = (it0.kind & ITEM_TLAS) ? 2 : ((it0.kind & ITEM_FOREST) || root_count[it0.a] == 0u) ? 1 : 0;
-                    if (c != cls) continue;
-                    Item it = it0;
-                    it.kind &= ~(uint32_t)ITEM_NEW_XFORM;
-                    if (first || it.b != prev_b) it.kind |= ITEM_NEW_XFORM;
-                    first = false;
-                    prev_b = it.b;
-                    ordered.push_back(it);
-                }
-            }
-            // (classes follow each other: the first item of a class whose local space is the previous class's last one
-            // need not open it again)
-            for (size_t k = 1; k < ordered.size(); ++k)
-                if (ordered[k].b == ordered[k - 1].b) ordered[k].kind &= ~(uint32_t)ITEM_NEW_XFORM;
-            items.swap(ordered);
-        }
-        // (one entry is always there: the many-mesh kernels, which the debug views use too,
-        // run single meshes through the same stack)
-        const uint32_t tlas_entries = tlas.empty() ? 1u : tlas_depth + 2u;
-        const bool has_tlas = !tlas.empty();
-
-        // ---- the deferred mesh (RenderArgs::park) ----------------------------------------------
-        // The biggest single-mesh item of a few-mesh scene with a real BVH:
-        // its item goes to the end of the mesh loop (the loop's order is free), where a launch can stop in front
-        // of it.
-        bool have_defer = false;
-        uint32_t defer_mesh = 0, defer_xform = 0, defer_internal = 0;
-        if (!any_tlas && n_meshes < 16) {
-            size_t best_k = items.size();
-            uint32_t best_big = 0;
-            for (size_t k = 0; k < items.size(); ++k) {
-                const Item& it = items[k];
-                if (it.kind & (ITEM_TLAS | ITEM_FOREST | ITEM_FLAT2)) continue;
-                const uint32_t mi = it.a;
-                if (root_count[mi] != 0) continue;
-                const uint32_t internal = (mi + 1 < n_meshes ? wide_base[mi + 1] : (uint32_t)wide.size()) - wide_base[mi];
-                if (internal >= (uint32_t)h->defer_min_nodes && internal > best_big) { best_big = internal; best_k = k; }
-            }
-            if (best_k < items.size()) {
-                Item d = items[best_k];
-                items.erase(items.begin() + (std::ptrdiff_t)best_k);
-                // (the item that followed it in the same local space now opens that space)
-                if ((d.kind & ITEM_NEW_XFORM) && best_k < items.size() && !(items[best_k].kind & ITEM_NEW_XFORM)) items[best_k].kind |= ITEM_NEW_XFORM;
-                d.kind |= ITEM_NEW_XFORM | ITEM_DEFER | (root_box_contains(d.a) ? ITEM_DEFER_CULL : 0u);
-                items.push_back(d);
-                have_defer = true;
-                defer_mesh = d.a;
-                defer_xform = d.b;
-                defer_internal = best_big;
-            }
-        }
-
+        SceneGeom g;
+        std::vector<float4> tail;
+        int rc = build_geometry(h, meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, g, tail);
+        if (rc != RT_OK) return rc;
+        SceneInstances s;
+        if ((rc = build_instances(h, g, spheres, n_spheres, meshes, n_meshes, s)) != RT_OK) return rc;
+        const SceneLayout& lay = s.lay;
 #if RT_WALK2
         free_dev(h->walk2);
         h->walk2 = nullptr;
-        if (have_defer) {
-            const uint32_t base = wide_base[defer_mesh];
-            std::vector<float4> w2((size_t)defer_internal * 12u, make_float4(0, 0, 0, 0));
+        if (s.have_defer) {
+            const uint32_t base = g.mesh[s.defer_mesh].wide_base;
+            const WideRec* wide = reinterpret_cast<const WideRec*>(tail.data());  // (the tail starts with the wide records)
+            std::vector<float4> w2((size_t)s.defer_internal * 12u, make_float4(0, 0, 0, 0));
             auto bitsof = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-            for (uint32_t k = 0; k < defer_internal; ++k) {
+            for (uint32_t k = 0; k < s.defer_internal; ++k) {
                 const WideRec& w = wide[base + k];
                 for (int q = 0; q < 4; ++q) w2[(size_t)k * 12 + q] = w.q[q];
                 if (bitsof(w.q[1].w) == 0u) for (int q = 0; q < 4; ++q) w2[(size_t)k * 12 + 4 + q] = wide[bitsof(w.q[1].z)].q[q];
@@ -1043,171 +1279,114 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
             h->walk2_base = base;
         }
 #endif
-        // ---- blob layout ------------------------------------------------------
-        SceneLayout lay{};
-        uint64_t off = 0;
-        // (the per-scene sections first, the per-node / per-triangle arrays last: the small blob of the hybrid launches has
-        // the same sections with shorter arrays, so every offset up to wide_off is the same in both -- the primary-ray memo
-        // keeps a material's byte offset across launches that read different blobs)
-        lay.mesh_off = (uint32_t)off;   off += (uint64_t)n_meshes * MESH_REC_BYTES;
-        lay.mat_off = (uint32_t)off;    off += (uint64_t)(n_meshes + n_spheres) * MATERIAL_BYTES;
-        lay.sphere_off = (uint32_t)off; off += (uint64_t)n_spheres * SPHERE_BYTES;
-        lay.item_off = (uint32_t)off;   off += (uint64_t)items.size() * ITEM_BYTES;
-        lay.tlas_off = (uint32_t)off;   off += (uint64_t)tlas.size() * WIDE_REC_BYTES;
-        lay.forest_off = (uint32_t)off; off += (uint64_t)forest_entries.size() * FOREST_ENTRY_BYTES;
-        lay.wide_off = (uint32_t)off;   off += (uint64_t)wide.size() * WIDE_REC_BYTES;
-        lay.tri_off = (uint32_t)off;    off += (uint64_t)n_triangles * TRI_ISECT_BYTES;
-        lay.shade_off = (uint32_t)off;  off += (uint64_t)n_triangles * TRI_SHADE_BYTES;
-        if (off == 0) off = 16;
-        if (off > 0xfffffff0ull) return fail(h, RT_ERR_CAPACITY, "scene larger than 4 GiB");
-        lay.bytes = (uint32_t)off;
-        std::vector<float4> blob(off / 16, make_float4(0, 0, 0, 0));
-        auto asf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-        for (uint32_t i = 0; i < n_meshes; ++i) {
-            const rt_mesh_uniform& m = meshes[i];
-            float4* r = blob.data() + (lay.mesh_off + (size_t)i * MESH_REC_BYTES) / 16;
-            memcpy(r, m.world_to_model, 64);
-            memcpy(r + 4, m.model_to_world, 64);
-            uint32_t flags = 0;
-            if (m.material.flag == RT_MATERIAL_GLASS) flags |= DMESH_GLASS;
-            if (deep[i]) flags |= DMESH_DEEP;
-            r[8] = make_float4(asf(flags), asf(root_idx[i]), asf(root_count[i]), asf(m.triangle_offset));
-            {
-                // S >= the largest absolute row sum of model_to_world's 3 x 3 part ([col][row]), C >= the largest
-                // absolute translation component: in double, then rounded up (cross-mesh pruning's error terms)
-                double S = 0.0, C = 0.0;
-                for (int row = 0; row < 3; ++row) {
-                    const double rs = std::fabs((double)m.model_to_world[0][row]) + std::fabs((double)m.model_to_world[1][row]) +
-                                      std::fabs((double)m.model_to_world[2][row]);
-                    if (!(rs <= S)) S = rs;  // (NaN sticks)
-                    const double tc = std::fabs((double)m.model_to_world[3][row]);
-                    if (!(tc <= C)) C = tc;
-                }
-                auto up = [](double d) { float f = (float)d; if ((double)f < d) f = std::nextafter(f, INFINITY); return f; };
-                r[9] = make_float4(asf(wide_base[i]), up(S), up(C), 0.0f);
-            }
-            const rt_node& root = nodes[m.node_offset];
-            r[10] = make_float4(root.aabb_min[0], root.aabb_max[0], root.aabb_min[1], root.aabb_max[1]);
-            r[11] = make_float4(root.aabb_min[2], root.aabb_max[2], 0.0f, 0.0f);
-            memcpy(blob.data() + (lay.mat_off + (size_t)i * MATERIAL_BYTES) / 16, &m.material, MATERIAL_BYTES);
-        }
-        if (!wide.empty()) memcpy(blob.data() + lay.wide_off / 16, wide.data(), wide.size() * sizeof(WideRec));
-        if (!tlas.empty()) memcpy(blob.data() + lay.tlas_off / 16, tlas.data(), tlas.size() * sizeof(WideRec));
-        if (!forest_entries.empty())
-            memcpy(blob.data() + lay.forest_off / 16, forest_entries.data(), forest_entries.size() * sizeof(ForestEntry));
-        for (size_t k = 0; k < items.size(); ++k) {
-            const Item& it = items[k];
-            const bool single = (it.kind & (ITEM_TLAS | ITEM_FOREST)) == 0;
-            blob[lay.item_off / 16 + 2 * k] = make_float4(asf(it.kind), asf(it.a), asf(it.b), asf(single ? wide_base[it.a] : it.n));
-            if (single) blob[lay.item_off / 16 + 2 * k + 1] = blob[(lay.mesh_off + (size_t)it.a * MESH_REC_BYTES) / 16 + 8];
-        }
-        // Triangle re-layout (see rt_device.h).  The subtractions and the
-        // cross product are wgsl:261-263, evaluated once here in binary32.
-        for (uint32_t t = 0; t < n_triangles; ++t) {
-            const rt_packed_triangle& p = triangles[t];
-            float abx = p.v2[0] - p.v1[0], aby = p.v2[1] - p.v1[1], abz = p.v2[2] - p.v1[2];
-            float acx = p.v3[0] - p.v1[0], acy = p.v3[1] - p.v1[1], acz = p.v3[2] - p.v1[2];
-            float nx = aby * acz - abz * acy;
-            float ny = abz * acx - abx * acz;
-            float nz = abx * acy - aby * acx;
-            float4* ti = blob.data() + (lay.tri_off + (size_t)t * TRI_ISECT_BYTES) / 16;
-            ti[0] = make_float4(p.v1[0], p.v1[1], p.v1[2], nx);
-            ti[1] = make_float4(abx, aby, abz, ny);
-            ti[2] = make_float4(acx, acy, acz, nz);
-            float4* ts = blob.data() + (lay.shade_off + (size_t)t * TRI_SHADE_BYTES) / 16;
-            ts[0] = make_float4(p.n1[0], p.n1[1], p.n1[2], p.uv10);
-            ts[1] = make_float4(p.n2[0], p.n2[1], p.n2[2], p.uv11);
-            ts[2] = make_float4(p.n3[0], p.n3[1], p.n3[2], p.uv20);
-            ts[3] = make_float4(p.uv21, p.uv30, p.uv31, 0.0f);
-        }
-        for (uint32_t i = 0; i < n_spheres; ++i) {
-            blob[(lay.sphere_off + (size_t)i * SPHERE_BYTES) / 16] =
-                make_float4(spheres[i].pos[0], spheres[i].pos[1], spheres[i].pos[2], spheres[i].radius);
-            memcpy(blob.data() + (lay.mat_off + (size_t)(n_meshes + i) * MATERIAL_BYTES) / 16,
-                   &spheres[i].material, MATERIAL_BYTES);
-        }
-
         free_scene(h);
-        int rc;
-        if ((rc = upload(h, h->blob, blob.data(), blob.size())) != RT_OK) return rc;
+        HIP_TRY(h, hipMalloc((void**)&h->blob, lay.bytes));
+        if ((uint64_t)lay.wide_off + tail.size() * sizeof(float4) != lay.bytes)  // (an empty scene: 16 zero bytes)
+            HIP_TRY(h, hipMemsetAsync(h->blob, 0, lay.bytes, h->stream));
+        if (!s.head.empty())
+            HIP_TRY(h, hipMemcpyAsync(h->blob, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        if (!tail.empty())
+            HIP_TRY(h, hipMemcpyAsync((char*)h->blob + lay.wide_off, tail.data(), tail.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
         // ---- the small blob of the hybrid launches (experiments build only) ----
         std::vector<float4> small;
         SceneLayout sl{};
         uint32_t small_need = 1;
         bool small_ok = false;
 #if RT_EXPERIMENTS
+        {
+            // (the names the fragment reads: the whole blob and the per-mesh arrays of the geometry phase)
+            std::vector<float4> blob(s.head);
+            blob.insert(blob.end(), tail.begin(), tail.end());
+            blob.resize(lay.bytes / 16, make_float4(0, 0, 0, 0));
+            std::vector<uint32_t> wide_base(n_meshes), tri_lo(n_meshes), tri_hi(n_meshes), mesh_need(n_meshes);
+            for (uint32_t i = 0; i < n_meshes; ++i) {
+                wide_base[i] = g.mesh[i].wide_base;
+                tri_lo[i] = g.mesh[i].tri_lo;
+                tri_hi[i] = g.mesh[i].tri_hi;
+                mesh_need[i] = g.mesh[i].need;
+            }
+            const std::vector<char> wide(g.n_wide), items(s.n_items), tlas(s.n_tlas_records), forest_entries(s.n_forest_entries);
+            const bool have_defer = s.have_defer;
+            const uint32_t defer_mesh = s.defer_mesh, defer_internal = s.defer_internal;
 #include "experiments/rt_api_hybrid_blob.inl"   // (statement fragment: fills small / sl / small_need / small_ok)
+        }
 #endif
         if (small_ok && (rc = upload(h, h->small_blob, small.data(), small.size())) != RT_OK) return rc;
         h->small_ok = small_ok;
         h->small_lay = sl;
         h->small_stack_entries = small_need;
         HIP_TRY(h, hipStreamSynchronize(h->stream));  // host staging vectors die here
-        // The root-box shortcut needs root box == union of the two child boxes, bit for bit
-        // (true for the reference's builder; verified, not assumed, since BVHs may be foreign).
-        bool unions = true;
-        for (uint32_t i = 0; i < n_meshes && unions; ++i) {
-            const rt_node* mn = nodes + meshes[i].node_offset;
-            if (mn[0].count > 0) continue;
-            const rt_node &ca = mn[mn[0].left], &cb = mn[mn[0].right];
-            for (int k = 0; k < 3; ++k) {
-                const float lo_k = ca.aabb_min[k] < cb.aabb_min[k] ? ca.aabb_min[k] : cb.aabb_min[k];
-                const float hi_k = ca.aabb_max[k] > cb.aabb_max[k] ? ca.aabb_max[k] : cb.aabb_max[k];
-                // the root box may also be larger than the union (still conservative)
-                if (!(mn[0].aabb_min[k] <= lo_k && mn[0].aabb_max[k] >= hi_k)) unions = false;
-                // (and the children must be proper boxes, or the interval argument does not hold)
-                if (!(ca.aabb_min[k] <= ca.aabb_max[k] && cb.aabb_min[k] <= cb.aabb_max[k])) unions = false;
+        commit_scene(h, g, s, n_spheres, scene->camera);
+        h->geom = std::move(g);
+    } catch (const std::bad_alloc&) {
+        return fail(h, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+    }
+    return RT_OK;
+}
+
+int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere* spheres, uint32_t n_spheres,
+                        const rt_mesh_uniform* meshes, uint32_t n_meshes) {
+    if (!h || !scene) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle or scene");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if ((n_spheres && !spheres) || (n_meshes && !meshes))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "null array with non-zero count");
+    if (n_spheres > RT_MAX_SPHERES) return fail(h, RT_ERR_CAPACITY, "more than 500 spheres");
+    if (scene->spheres != n_spheres || scene->meshes != n_meshes)
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "SceneUniform counts disagree with the array lengths");
+    const SceneGeom& g = h->geom;
+    if (n_meshes != g.mesh.size())
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "mesh count " + std::to_string(n_meshes) + " differs from the uploaded " +
+                                                    std::to_string(g.mesh.size()) + " (new geometry needs rt_upload_scene)");
+    for (uint32_t i = 0; i < n_meshes; ++i)
+        if (meshes[i].node_offset != g.mesh[i].node_offset || meshes[i].triangle_offset != g.mesh[i].triangle_offset ||
+            meshes[i].triangles != g.mesh[i].triangles)
+            return fail(h, RT_ERR_INVALID_ARGUMENT, "mesh " + std::to_string(i) +
+                                                        ": node_offset / triangle_offset / triangles differ from the uploaded "
+                                                        "scene (new geometry needs rt_upload_scene)");
+#if RT_EXPERIMENTS || RT_WALK2
+    // (the hybrid small blob and walk2 are derived from the head and the deferred mesh, which an update may change)
+    return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_update_instances is not available in the experiments build (its hybrid small "
+                                            "blob and walk2 records derive from the head): use rt_upload_scene");
+#endif
+    HIP_TRY(h, hipSetDevice(h->device));
+    try {
+        SceneInstances s;
+        int rc = build_instances(h, g, spheres, n_spheres, meshes, n_meshes, s);
+        if (rc != RT_OK) return rc;
+        const SceneLayout& lay = s.lay;
+        const uint64_t tail_bytes = g.tail_bytes();
+        if (lay.wide_off == h->lay.wide_off) {
+            // the head in place: after every launch that may read it, and complete before the next one
+            if ((rc = drain_streams(h)) != RT_OK) return rc;
+            if (!s.head.empty())
+                HIP_TRY(h, hipMemcpyAsync(h->blob, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));  // (host staging vector dies here)
+        } else {
+            // a new blob: the new head from the host, the old tail device to device, the old blob freed after both
+            float4* fresh = nullptr;
+            if (hipMalloc((void**)&fresh, lay.bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(h, RT_ERR_OUT_OF_MEMORY, "rt_update_instances: no device memory for the resized scene");
             }
-        }
-        h->roots_are_unions = unions;
-        h->lay = lay;
-        h->n_meshes = n_meshes;
-        h->n_spheres = n_spheres;
-        h->n_nodes = n_nodes;
-        h->n_triangles = n_triangles;
-        h->stack_entries = max_height ? max_height : 1;
-        // One-dword stack entries hold 7 bits of leaf count and 24 bits of triangle index; they cost
-        // a few instructions per push/pop, so they are used when they buy occupancy: when two-dword
-        // entries would not leave room for the scene blob and the primary-ray memo in LDS.
-        {
-            const uint64_t fixed = 8u * 3u * 4u * WAVES_PER_BLOCK + (uint64_t)(LANE_STATE_DWORDS + PIXEL_MEMO_DWORDS) * 64u * 4u * WAVES_PER_BLOCK +
-                                   (uint64_t)tlas_entries * 64u * 4u * WAVES_PER_BLOCK;
-            const uint64_t wide_stacks = (uint64_t)h->stack_entries * 128u * 4u * WAVES_PER_BLOCK;
-            const bool wide_fits = lay.bytes + fixed + wide_stacks <= LDS_BUDGET_BYTES;
-            h->stack_must_wide = max_leaf_ref > 127u || n_triangles > (1u << 24);
-            h->stack_wide = h->stack_must_wide || wide_fits;
-        }
-        h->tlas_entries = tlas_entries;
-        h->has_tlas = has_tlas;
-        h->n_tlas_records = (uint32_t)tlas.size();
-        h->any_deep = false;
-        for (uint32_t i = 0; i < n_meshes; ++i) h->any_deep = h->any_deep || deep[i];
-        h->has_forest = !forest_entries.empty();
-        {
-            bool plain = n_spheres == 0;
-            for (uint32_t i = 0; i < n_meshes && plain; ++i) {
-                const rt_material& m = meshes[i].material;
-                if (m.flag == RT_MATERIAL_GLASS || (m.flag == RT_MATERIAL_TEXTURE && m.diffuse_index != -1)) plain = false;
+            rc = drain_streams(h);
+            hipError_t e = hipSuccess;
+            if (rc == RT_OK && (uint64_t)lay.wide_off + tail_bytes != lay.bytes)  // (an empty scene: 16 zero bytes)
+                e = hipMemsetAsync(fresh, 0, lay.bytes, h->stream);
+            if (rc == RT_OK && e == hipSuccess && !s.head.empty())
+                e = hipMemcpyAsync(fresh, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream);
+            if (rc == RT_OK && e == hipSuccess && tail_bytes)
+                e = hipMemcpyAsync((char*)fresh + lay.wide_off, (const char*)h->blob + h->lay.wide_off, tail_bytes,
+                                   hipMemcpyDeviceToDevice, h->stream);
+            if (rc == RT_OK && e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (rc != RT_OK || e != hipSuccess) {
+                (void)hipFree(fresh);
+                return rc != RT_OK ? rc : fail(h, RT_ERR_DEVICE, std::string("rt_update_instances: ") + hipGetErrorString(e));
             }
-            h->plain_materials = plain;
+            free_dev(h->blob);
+            h->blob = fresh;
         }
-        h->n_items = (uint32_t)items.size();
-        h->top_base = top_mesh_base;
-        h->top_available = top_mesh_records >= 64 ? std::min<uint32_t>(top_mesh_records, 2048u) : 0u;
-        h->have_defer = have_defer;
-        h->defer_mesh = defer_mesh;
-        h->defer_xform = defer_xform;
-        h->defer_internal = defer_internal;
-        // LDS residency: blob + the four waves' stacks, cost tables and lane state within the
-        // per-workgroup budget (the primary-ray memo goes to LDS only if it still fits, see render_impl)
-        uint64_t stacks = ((uint64_t)h->stack_entries * (h->stack_wide ? 128u : 64u) + (uint64_t)h->tlas_entries * 64u) * sizeof(uint32_t) * WAVES_PER_BLOCK +
-                          8u * 3u * 4u * WAVES_PER_BLOCK + (uint64_t)LANE_STATE_DWORDS * 64u * 4u * WAVES_PER_BLOCK;
-        h->lds_scene = (uint64_t)lay.bytes + stacks <= LDS_BUDGET_BYTES;
-        h->camera = scene->camera;
-        h->have_scene = true;
-        h->history_valid = false;
-        h->primary_valid = false;  // (the table holds hits: a function of the scene)
-        for (auto& st : h->slot_primary) st.valid = false;
+        commit_scene(h, g, s, n_spheres, scene->camera);
+        h->generation += 1;
     } catch (const std::bad_alloc&) {
         return fail(h, RT_ERR_OUT_OF_MEMORY, "out of host memory");
     }
@@ -2740,6 +2919,23 @@ int rt_test_device_units(rt_handle* h, int fn, const float* x, const float* y, f
     free_dev(dx);
     free_dev(dy);
     free_dev(dout);
+    return RT_OK;
+}
+
+// tests/test_gpu_scene_edits.py: the scene blob as the kernels read it, its SceneLayout and its device address -- to
+// compare an updated handle with a fresh upload, and to see that an in-place update kept its allocation.
+int rt_test_scene_blob(rt_handle* h, void* out, uint64_t bytes, uint32_t layout_out[12], uint64_t* device_ptr) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (out && bytes < h->lay.bytes) return fail(h, RT_ERR_INVALID_ARGUMENT, "output smaller than the blob");
+    static_assert(sizeof(SceneLayout) == 12 * sizeof(uint32_t), "SceneLayout is 12 words");
+    if (layout_out) memcpy(layout_out, &h->lay, sizeof(SceneLayout));
+    if (device_ptr) *device_ptr = (uint64_t)(uintptr_t)h->blob;
+    if (out) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = drain_streams(h); rc != RT_OK) return rc;
+        HIP_TRY(h, hipMemcpy(out, h->blob, h->lay.bytes, hipMemcpyDeviceToHost));
+    }
     return RT_OK;
 }
 

@@ -29,10 +29,12 @@ EXPORTS = [
     "rt_scene_nodes", "rt_scene_get_texture", "rt_scene_mesh_label", "rt_scene_mesh_data", "rt_scene_num_mesh_instances", "rt_scene_last_error",
     "rt_scene_destroy", "rt_upload_built_scene", "rt_scene_subdivide_meshes", "rt_export_rgba8",
     "rt_intersect_rays", "rt_occluded_rays", "rt_pick",
+    "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
+    "rt_scene_set_sphere",
 ]
 # every symbol include/rt_test_abi.h declares (the test library only)
 TEST_EXPORTS = ["rt_test_device_units", "rt_test_sweep", "rt_test_device_sample_texture", "rt_test_read_wavefront",
-                "rt_test_rccl_gather", "rt_test_frame_ahead_depth", "rt_test_intersect"]
+                "rt_test_rccl_gather", "rt_test_frame_ahead_depth", "rt_test_intersect", "rt_test_scene_blob"]
 
 _lib = None
 _test_lib = None
@@ -137,6 +139,11 @@ def _bind(L, with_test_entries):
         "rt_intersect_rays": (i32, [vp, vp, u64, vp, i32]),
         "rt_occluded_rays": (i32, [vp, vp, u64, vp, i32]),
         "rt_pick": (i32, [vp, P(A.Params), u32, u32, P(A.Hit)]),
+        "rt_update_instances": (i32, [vp, P(A.SceneUniform), vp, u32, vp, u32]),
+        "rt_update_built_scene": (i32, [vp, vp]),
+        "rt_scene_set_mesh_transform": (i32, [vp, u32, P(A.Transform)]),
+        "rt_scene_set_mesh_material": (i32, [vp, u32, P(A.Material)]),
+        "rt_scene_set_sphere": (i32, [vp, u32, P(C.c_float * 3), C.c_float, P(A.Material)]),
     }
     assert set(sig) == set(EXPORTS)
     if with_test_entries:
@@ -148,6 +155,7 @@ def _bind(L, with_test_entries):
             "rt_test_read_wavefront": (i32, [vp, i32, vp, u64]),
             "rt_test_rccl_gather": (i32, [C.c_char_p, i32]),
             "rt_test_intersect": (i32, [vp, vp, vp, vp, u64, i32, vp]),
+            "rt_test_scene_blob": (i32, [vp, vp, u64, P(u32 * 12), P(u64)]),
         })
         assert set(sig) == set(EXPORTS) | set(TEST_EXPORTS)
     for name, (res, args) in sig.items():

@@ -63,6 +63,18 @@ class RayTracer:
             a.meshes.shape[0], a.triangles.ctypes.data, a.triangles.shape[0], a.nodes.ctypes.data,
             a.nodes.shape[0]))
 
+    def update_instances(self, arrays):
+        """The per-instance part of update_buffers (rt_update_instances): the SceneUniform, spheres and mesh uniforms of
+        `arrays` over the triangles and nodes of the last update_buffers -- whose mesh count and per-mesh offsets `arrays`
+        must keep.  Only the blob's head is rebuilt and sent."""
+        a = arrays
+        self._check(self._L.rt_update_instances(self._h, C.byref(a.uniform), a.spheres.ctypes.data, a.spheres.shape[0],
+                                                a.meshes.ctypes.data, a.meshes.shape[0]))
+
+    def update_built_scene(self, scene):
+        """update_instances from a built Scene (C++ object) after its setters (rt_update_built_scene)."""
+        self._check(self._L.rt_update_built_scene(self._h, scene._p))
+
     def load_built_scene(self, scene):
         """A built Scene (C++ object) straight to the device: textures + arrays, without the round trip through numpy
         (rt_upload_built_scene: what the C++ mirror's load_scene_gpu_resources + update_buffers do)."""
@@ -180,6 +192,16 @@ class RayTracer:
         self._check(self._L.rt_test_intersect(self._h, ro.ctypes.data, rd.ctypes.data, None if act is None else act.ctypes.data,
                                               n, flags, out.ctypes.data))
         return out
+
+    # ---- test-only: the scene blob (tests/test_gpu_scene_edits.py) ----
+    def scene_blob(self):
+        """(blob bytes as uint8, SceneLayout as 12 uint32 -- A.SCENE_LAYOUT_FIELDS --, device address) of the uploaded scene
+        (rt_test_scene_blob; waits for the handle's streams)."""
+        lay, ptr = (C.c_uint32 * 12)(), C.c_uint64()
+        self._check(self._L.rt_test_scene_blob(self._h, None, 0, C.byref(lay), C.byref(ptr)))
+        out = np.empty(lay[9], np.uint8)
+        self._check(self._L.rt_test_scene_blob(self._h, out.ctypes.data, out.nbytes, C.byref(lay), C.byref(ptr)))
+        return out, np.array(lay, np.uint32), int(ptr.value)
 
     # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick) ----
     def trace_rays(self, origins, dirs, tmax=None):

@@ -97,6 +97,18 @@ class Scene:
         h, w, _ = rgba.shape
         return self._check(self._L.rt_scene_add_texture_rgba8(self._p, rgba.ctypes.data, w, h))
 
+    # ---- inspector edits (egui.rs:240-330): no BVH rebuild; RayTracer.update_built_scene sends them ----
+    def set_mesh_transform(self, i, xform):
+        """Position / Size / Rotation of mesh instance i (a Transform, see transform())."""
+        self._check(self._L.rt_scene_set_mesh_transform(self._p, int(i), C.byref(xform)))
+
+    def set_mesh_material(self, i, mat):
+        self._check(self._L.rt_scene_set_mesh_material(self._p, int(i), C.byref(mat)))
+
+    def set_sphere(self, i, centre, radius, mat):
+        self._check(self._L.rt_scene_set_sphere(self._p, int(i), C.byref((C.c_float * 3)(*centre)), float(radius),
+                                                C.byref(mat)))
+
     def subdivide_meshes(self, n):
         self._check(self._L.rt_scene_subdivide_meshes(self._p, n))
 

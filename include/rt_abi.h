@@ -222,6 +222,48 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
 int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere* spheres, uint32_t n_spheres,
                         const rt_mesh_uniform* meshes, uint32_t n_meshes);
 
+/* BVH refit: moved vertices, same topology.
+ *
+ * rt_refit_bvh (host only, no device needed) recomputes in place the node boxes of every mesh it selects: the meshes
+ * whose leaf range [tri_lo, tri_hi) -- the triangles their leaves reference -- meets [first, first + n).  Other meshes
+ * keep their nodes bit for bit (their boxes may be looser than a refit would make them, as in a foreign BVH), and the
+ * topology fields (left, right, first, count) never change.  The box rule, which the device reproduces bit for bit
+ * (csrc/rt_refit.h):
+ *   - min(a, b) / max(a, b) of two floats: the smaller / larger of two ordered values; of two equal ones -0 / +0 when
+ *     they are zeros of both signs; of a NaN and another value the other value (NaN only when both are NaN).  (Not libm
+ *     fmin: the sign of its zero results differs between compilers, so the builder's own boxes are only defined up to
+ *     the sign of zero, and a refit of unchanged vertices gives them back value for value, == on every float.)
+ *   - a leaf's box: a fold over its triangles in array order, from (+FLT_MAX, -FLT_MAX), each triangle contributing
+ *     min(v1, min(v2, v3)) and max(v1, max(v2, v3)) per axis (the builder's fit_bounds);
+ *   - an internal node's box: min(left, right) / max(left, right), element by element.
+ * No box holds a NaN; a leaf whose vertices are all NaN keeps the empty box (+FLT_MAX, -FLT_MAX).
+ * Refused with RT_ERR_INVALID_ARGUMENT, nothing changed, rt_last_error(NULL) naming the mesh: a selected mesh whose leaf
+ * range is not inside [first, first + n) (a mesh is refitted whole: its leaf boxes need every vertex), a selected mesh
+ * whose node interval [node_offset, highest node its root reaches] overlaps that of a mesh with another triangle_offset
+ * (no single node array could then describe the result), a range past n_triangles.  Invalid BVH indices give
+ * RT_ERR_INDEX_RANGE as rt_upload_scene does. */
+int rt_refit_bvh(const rt_mesh_uniform* meshes, uint32_t n_meshes, const rt_packed_triangle* triangles, uint32_t n_triangles,
+                 rt_node* nodes, uint32_t n_nodes, uint32_t first, uint32_t n);
+
+/* rt_refit_triangles replaces the uploaded triangles [first, first + n) and refits the uploaded BVH on the device.  The
+ * handle afterwards is exactly what rt_upload_scene would leave for the uniform, spheres and meshes of the last upload or
+ * update, the uploaded triangles with that range replaced, and the uploaded nodes passed through
+ * rt_refit_bvh(..., first, n): the same blob bytes, SceneLayout, kernel choice (rt_last_launch), images and ray-query
+ * results.  `triangles` holds n rt_packed_triangle records: device pointers on the handle's device (16-byte aligned),
+ * read in order on the handle's stream like rt_intersect_rays, unless flags has RT_REFIT_HOST_MEMORY (host pointers).
+ * The kernels rewrite the triangle records of the range and recompute the selected meshes' boxes bottom-up; the
+ * per-mesh root facts (root box, containment, proper hierarchy) are the only thing read back -- the call returns after
+ * that one small readback --, and the host then reruns the instance phase (top-level trees, forests, mesh records) and
+ * commits the head as rt_update_instances does: after the launches already enqueued, dropping frames rendered ahead and
+ * the primary tables; in place, or in a new allocation when the head's size changes.  Device scratch (about 72 bytes
+ * per BVH record of the selected meshes, and n x 96 bytes of staging for host input) is held only during the call and
+ * counts against option "max_device_mb".  Errors, all checked before anything is written, leaving the scene as it was:
+ * those of rt_refit_bvh, RT_ERR_NO_SCENE, RT_ERR_INVALID_ARGUMENT (null or misaligned triangles with n > 0, unknown
+ * flags, the experiments build), RT_ERR_OUT_OF_MEMORY (the cap or the device has no room for the scratch or a resized
+ * blob). */
+enum { RT_REFIT_HOST_MEMORY = 1 };
+int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32_t first, uint32_t n, int flags);
+
 /* ≙ RayTracer::load_scene_gpu_resources (ray_tracer.rs:237-315). n <= 64. */
 int rt_upload_textures(rt_handle* h, const rt_texture_desc* descs, uint32_t n);
 
@@ -577,6 +619,9 @@ void rt_scene_destroy(rt_scene* s);
 int rt_upload_built_scene(rt_handle* h, const rt_scene* s);
 /* rt_update_instances from a built rt_scene whose geometry is the one uploaded (after the setters below). */
 int rt_update_built_scene(rt_handle* h, const rt_scene* s);
+/* rt_refit_triangles with the packed triangles of mesh instances [first_mesh, first_mesh + n_meshes) of a built rt_scene
+ * whose topology is the one uploaded (after rt_scene_set_mesh_vertices), from host memory. */
+int rt_refit_built_scene(rt_handle* h, const rt_scene* s, uint32_t first_mesh, uint32_t n_meshes);
 
 /* Inspector edits of a scene (≙ the egui drag widgets, src/rendering/egui.rs:240-330).  i is a mesh instance
  * (rt_scene_num_mesh_instances) / a sphere index.  On a built scene the instance's rt_mesh_uniform is rewritten the
@@ -586,6 +631,17 @@ int rt_update_built_scene(rt_handle* h, const rt_scene* s);
 int rt_scene_set_mesh_transform(rt_scene* s, uint32_t i, const rt_transform* t);
 int rt_scene_set_mesh_material(rt_scene* s, uint32_t i, const rt_material* m);
 int rt_scene_set_sphere(rt_scene* s, uint32_t i, const float centre[3], float radius, const rt_material* m);
+/* Moved vertices of mesh instance i: n_vertices x (pos[3], normal[3], uv[2]) floats, as rt_scene_add_mesh_data takes
+ * them; n_vertices must equal the instance's count, and its index list stays.  Copy-on-write when the instance shares
+ * its mesh data with others (they keep the old vertices).  On a built scene the instance's packed triangles are repacked
+ * in BVH order and its nodes refitted (rt_refit_bvh): the scene stays built and rt_refit_built_scene sends the change.
+ * Refused (RT_ERR_INVALID_ARGUMENT, nothing changed) for another vertex count or a scene built with quality Disabled,
+ * which has no packed triangles. */
+int rt_scene_set_mesh_vertices(rt_scene* s, uint32_t i, const float* vertices8, uint32_t n_vertices);
+/* The BVH order of a built scene's mesh instance i: out[k] (rt_mesh_uniform.triangles entries) is the source triangle, in
+ * its index list, of packed triangle triangle_offset + k -- what a host needs to pack moved triangles itself, e.g. on the
+ * device.  RT_ERR_INVALID_ARGUMENT on an unbuilt scene. */
+int rt_scene_triangle_order(rt_scene* s, uint32_t i, uint32_t* out);
 
 /* Uniform n x n barycentric split of every triangle of every mesh added so
  * far (SURVEY 8d stand-in for the missing Dragon_80K / dragon_large assets). */

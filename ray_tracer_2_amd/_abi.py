@@ -119,6 +119,7 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<u4"), ("primitive", "<u4"), ("f
 assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
 HIT_HIT, HIT_BACKFACE = 1, 2
 QUERY_HOST_MEMORY, QUERY_PRUNE_TMAX = 1, 2
+REFIT_HOST_MEMORY = 1
 MISS = 0xFFFFFFFF
 
 # SceneLayout (csrc/rt_device.h): the 12 words rt_test_scene_blob returns; the head of the blob is [0, wide_off)

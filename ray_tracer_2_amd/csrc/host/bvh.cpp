@@ -1,9 +1,12 @@
 // bvh.cpp -- see bvh.h.  Line references are to src/core/bvh.rs.
 #include "bvh.h"
 
+#include "../rt_refit.h"
+
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <limits>
 #include <utility>
 
@@ -197,8 +200,10 @@ BvhResult bvh_build(const std::vector<Vertex>& vertices, const std::vector<uint3
     }
     b.subdivide(0, 0, n_tris, 0);
     out.triangles.resize(n_tris);
+    out.order.resize(n_tris);
     for (size_t k = 0; k < n_tris; ++k) {  // :278-287, PackedTriangle::new :37-52
         const BuildTri& t = b.tris[k];
+        out.order[k] = (uint32_t)(t.i / 3);
         const Vertex& a = vertices[indices[t.i]];
         const Vertex& bb = vertices[indices[t.i + 1]];
         const Vertex& c = vertices[indices[t.i + 2]];
@@ -387,8 +392,10 @@ BvhResult bvh_build_levels(const std::vector<Vertex>& vertices, const std::vecto
         out.nodes[renum[n]] = v;
     }
     out.triangles.resize(n_tris);
+    out.order.resize(n_tris);
     for (size_t k = 0; k < n_tris; ++k) {  // bvh.rs:278-287
         const BuildTri& t = b.tris[k];
+        out.order[k] = (uint32_t)(t.i / 3);
         const Vertex& a = vertices[indices[t.i]];
         const Vertex& bb = vertices[indices[t.i + 1]];
         const Vertex& c = vertices[indices[t.i + 2]];
@@ -401,6 +408,131 @@ BvhResult bvh_build_levels(const std::vector<Vertex>& vertices, const std::vecto
         out.triangles[k] = p;
     }
     return out;
+}
+
+// ---------------------------------------------------------------------------------------------
+// refit (rt_refit_bvh)
+// ---------------------------------------------------------------------------------------------
+int refit_span(const rt_mesh_uniform& m, const rt_node* nodes, uint32_t n_nodes, uint32_t n_triangles, RefitSpan& out,
+               std::string& why) {
+    out = RefitSpan{0xffffffffu, 0u, m.node_offset, m.node_offset, m.triangle_offset};
+    if (m.node_offset >= n_nodes) {
+        why = "mesh node_offset out of range";
+        return RT_ERR_INDEX_RANGE;
+    }
+    std::vector<uint32_t> st{m.node_offset};
+    uint64_t visits = 0;
+    while (!st.empty()) {
+        const uint32_t idx = st.back();
+        st.pop_back();
+        if (++visits > (uint64_t)n_nodes + 1) {
+            why = "BVH has a cycle";
+            return RT_ERR_INDEX_RANGE;
+        }
+        if (idx > out.node_hi) out.node_hi = idx;
+        const rt_node& nd = nodes[idx];
+        if (nd.count > 0) {
+            const uint64_t lo = (uint64_t)m.triangle_offset + nd.first, hi = lo + nd.count;
+            if (hi > n_triangles) {
+                why = "leaf triangle range out of bounds";
+                return RT_ERR_INDEX_RANGE;
+            }
+            if (lo < out.tri_lo) out.tri_lo = (uint32_t)lo;
+            if (hi > out.tri_hi) out.tri_hi = (uint32_t)hi;
+        } else {
+            const uint64_t a = (uint64_t)m.node_offset + nd.left, b = (uint64_t)m.node_offset + nd.right;
+            if (a >= n_nodes || b >= n_nodes) {
+                why = "BVH child index out of range";
+                return RT_ERR_INDEX_RANGE;
+            }
+            st.push_back((uint32_t)a);
+            st.push_back((uint32_t)b);
+        }
+    }
+    return RT_OK;
+}
+
+int refit_select(const std::vector<RefitSpan>& spans, uint32_t first, uint32_t n, std::vector<uint32_t>& selected,
+                 std::string& err) {
+    selected.clear();
+    const uint64_t end = (uint64_t)first + n;
+    for (uint32_t i = 0; i < spans.size(); ++i) {
+        const RefitSpan& s = spans[i];
+        if (s.tri_lo >= s.tri_hi || s.tri_hi <= first || s.tri_lo >= end) continue;
+        if (s.tri_lo < first || s.tri_hi > end) {
+            err = "mesh " + std::to_string(i) + ": its leaves reference triangles [" + std::to_string(s.tri_lo) + ", " +
+                  std::to_string(s.tri_hi) + "), not all inside the refitted range [" + std::to_string(first) + ", " +
+                  std::to_string(end) + "): a mesh is refitted whole";
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        for (uint32_t j = 0; j < spans.size(); ++j) {
+            const RefitSpan& o = spans[j];
+            if (o.triangle_offset != s.triangle_offset && o.node_lo <= s.node_hi && s.node_lo <= o.node_hi) {
+                err = "mesh " + std::to_string(i) + ": its BVH nodes [" + std::to_string(s.node_lo) + ", " + std::to_string(s.node_hi) +
+                      "] overlap those of mesh " + std::to_string(j) + ", whose triangle_offset differs";
+                return RT_ERR_INVALID_ARGUMENT;
+            }
+        }
+        selected.push_back(i);
+    }
+    return RT_OK;
+}
+
+int refit_bvh(const rt_mesh_uniform* meshes, uint32_t n_meshes, const rt_packed_triangle* triangles, uint32_t n_triangles,
+              rt_node* nodes, uint32_t n_nodes, uint32_t first, uint32_t n, std::string& err) {
+    if ((n_meshes && !meshes) || (n_nodes && !nodes) || (n_triangles && !triangles)) {
+        err = "null array with non-zero count";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if ((uint64_t)first + n > n_triangles) {
+        err = "triangle range [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) + ") exceeds the " +
+              std::to_string(n_triangles) + " triangles";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<RefitSpan> spans(n_meshes);
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        std::string why;
+        if (int rc = refit_span(meshes[i], nodes, n_nodes, n_triangles, spans[i], why); rc != RT_OK) {
+            err = "mesh " + std::to_string(i) + ": " + why;
+            return rc;
+        }
+    }
+    std::vector<uint32_t> selected;
+    if (int rc = refit_select(spans, first, n, selected, err); rc != RT_OK) return rc;
+    // every node after its children: reverse pre-order (a node shared by two paths is refitted twice, to the same box)
+    std::vector<uint32_t> pre, st;
+    for (uint32_t i : selected) {
+        const uint32_t base = meshes[i].node_offset;
+        pre.clear();
+        st.assign(1, base);
+        while (!st.empty()) {
+            const uint32_t idx = st.back();
+            st.pop_back();
+            pre.push_back(idx);
+            if (nodes[idx].count == 0) {
+                st.push_back(base + nodes[idx].left);
+                st.push_back(base + nodes[idx].right);
+            }
+        }
+        for (size_t k = pre.size(); k-- > 0;) {
+            rt_node& nd = nodes[pre[k]];
+            float lo[3], hi[3];
+            if (nd.count > 0) {
+                rt_box_empty(lo, hi);
+                const rt_packed_triangle* t = triangles + meshes[i].triangle_offset + nd.first;
+                for (uint32_t j = 0; j < nd.count; ++j) rt_box_fold(lo, hi, t[j].v1, t[j].v2, t[j].v3);
+            } else {
+                const rt_node &a = nodes[base + nd.left], &b = nodes[base + nd.right];
+                for (int c = 0; c < 3; ++c) {
+                    lo[c] = rt_box_min(a.aabb_min[c], b.aabb_min[c]);
+                    hi[c] = rt_box_max(a.aabb_max[c], b.aabb_max[c]);
+                }
+            }
+            memcpy(nd.aabb_min, lo, 12);
+            memcpy(nd.aabb_max, hi, 12);
+        }
+    }
+    return RT_OK;
 }
 
 }  // namespace rt2

@@ -88,6 +88,22 @@ int RayTracer::update_instances(const Scene& scene) {
     return update_instance_arrays(h_, scene);
 }
 
+int RayTracer::refit_triangles(const rt_packed_triangle* triangles, uint32_t first, uint32_t n, int flags) {
+    return h_ ? rt_refit_triangles(h_, triangles, first, n, flags) : RT_ERR_INVALID_ARGUMENT;
+}
+
+static int refit_scene_meshes(rt_handle* h, const Scene& scene, uint32_t first_mesh, uint32_t n_meshes) {
+    if (!scene.built_bvh || (uint64_t)first_mesh + n_meshes > scene.mesh_uniforms.size()) return RT_ERR_INVALID_ARGUMENT;
+    if (n_meshes == 0) return rt_refit_triangles(h, nullptr, 0, 0, RT_REFIT_HOST_MEMORY);
+    const rt_mesh_uniform &a = scene.mesh_uniforms[first_mesh], &b = scene.mesh_uniforms[first_mesh + n_meshes - 1];
+    const uint32_t first = a.triangle_offset, end = b.triangle_offset + b.triangles;
+    return rt_refit_triangles(h, scene.triangles.data() + first, first, end - first, RT_REFIT_HOST_MEMORY);
+}
+
+int RayTracer::refit_meshes(const Scene& scene, uint32_t first_mesh, uint32_t n_meshes) {
+    return h_ ? refit_scene_meshes(h_, scene, first_mesh, n_meshes) : RT_ERR_INVALID_ARGUMENT;
+}
+
 int RayTracer::render(const rt_params& params) { return h_ ? rt_render(h_, &params) : RT_ERR_INVALID_ARGUMENT; }
 int RayTracer::read_image(float* rgba, size_t bytes) { return h_ ? rt_read_image(h_, rgba, bytes) : RT_ERR_INVALID_ARGUMENT; }
 int RayTracer::snapshot_image(size_t bytes) { return h_ ? rt_snapshot_image(h_, bytes) : RT_ERR_INVALID_ARGUMENT; }
@@ -110,4 +126,9 @@ extern "C" int rt_update_built_scene(rt_handle* h, const rt_scene* s) {
     const rt2::Scene& scene = rt2::scene_of(s);
     if (!scene.built_bvh && !scene.meshes.empty()) return RT_ERR_INVALID_ARGUMENT;  // (rt_scene_build, then rt_upload_built_scene)
     return rt2::update_instance_arrays(h, scene);
+}
+
+extern "C" int rt_refit_built_scene(rt_handle* h, const rt_scene* s, uint32_t first_mesh, uint32_t n_meshes) {
+    if (!h || !s) return RT_ERR_INVALID_ARGUMENT;
+    return rt2::refit_scene_meshes(h, rt2::scene_of(s), first_mesh, n_meshes);
 }

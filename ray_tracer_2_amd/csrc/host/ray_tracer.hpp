@@ -40,6 +40,11 @@ class RayTracer {
     // The per-instance part of update_buffers (rt_update_instances): transforms, materials, spheres and camera of a
     // built scene whose geometry is the one last uploaded -- after the Scene's setters, without "Rebuild BVH".
     int update_instances(const Scene& scene);
+    // Moved vertices, same topology (rt_refit_triangles / rt_refit_built_scene): packed triangles [first, first + n) of
+    // the uploaded scene -- device pointers unless flags has RT_REFIT_HOST_MEMORY --, or mesh instances
+    // [first_mesh, first_mesh + n_meshes) of a built scene after Scene::set_mesh_vertices; the BVH is refitted, not rebuilt.
+    int refit_triangles(const rt_packed_triangle* triangles, uint32_t first, uint32_t n, int flags);
+    int refit_meshes(const Scene& scene, uint32_t first_mesh, uint32_t n_meshes);
     // ≙ render (:420): one frame, asynchronous.
     int render(const rt_params& params);
     // ≙ the texture->buffer copy of save_render_to_file (app.rs:341-407).

@@ -294,6 +294,7 @@ void Scene::build_per_mesh(Quality q, int device, size_t device_min_tris) {  // 
     triangles.clear();
     nodes.clear();
     mesh_uniforms.clear();
+    triangle_order.clear();
     size_t triangle_offset = 0, node_offset = 0;
     for (const MeshInstance& mi : meshes) {
         BvhResult r;
@@ -315,10 +316,12 @@ void Scene::build_per_mesh(Quality q, int device, size_t device_min_tris) {  // 
         mesh_uniforms.push_back(u);
         triangles.insert(triangles.end(), r.triangles.begin(), r.triangles.end());
         nodes.insert(nodes.end(), r.nodes.begin(), r.nodes.end());
+        triangle_order.insert(triangle_order.end(), r.order.begin(), r.order.end());
         triangle_offset += r.triangles.size();
         node_offset += r.nodes.size();
     }
     built_bvh = true;
+    built_quality = q;
 }
 
 void Scene::set_mesh_transform(size_t i, const Transform& t) {
@@ -329,6 +332,42 @@ void Scene::set_mesh_transform(size_t i, const Transform& t) {
 void Scene::set_mesh_material(size_t i, const rt_material& m) {
     meshes.at(i).material = m;
     if (built_bvh && i < mesh_uniforms.size()) mesh_uniforms[i].material = m;
+}
+
+int Scene::set_mesh_vertices(size_t i, const std::vector<Vertex>& vertices, std::string& err) {
+    if (i >= meshes.size()) {
+        err = "mesh instance " + std::to_string(i) + " out of range (" + std::to_string(meshes.size()) + " instances)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    MeshInstance& mi = meshes[i];
+    if (vertices.size() != mi.data->vertices.size()) {
+        err = "mesh instance " + std::to_string(i) + " has " + std::to_string(mi.data->vertices.size()) + " vertices, not " +
+              std::to_string(vertices.size()) + " (a refit keeps the vertex count and the index list)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const bool built = built_bvh && i < mesh_uniforms.size();
+    if (built && built_quality == Quality::Disabled) {
+        err = "the scene was built with quality Disabled, which has no packed triangles to refit";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (mi.data.use_count() > 1) mi.data = std::make_shared<MeshData>(*mi.data);  // (the other instances keep theirs)
+    mi.data->vertices = vertices;
+    if (!built) return RT_OK;
+    const rt_mesh_uniform& u = mesh_uniforms[i];
+    const std::vector<uint32_t>& idx = mi.data->indices;
+    auto put3 = [](float dst[3], Vec3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
+    for (uint32_t k = 0; k < u.triangles; ++k) {  // (as bvh_build packs them)
+        const size_t t = (size_t)triangle_order[u.triangle_offset + k] * 3;
+        const Vertex &a = vertices[idx[t]], &b = vertices[idx[t + 1]], &c = vertices[idx[t + 2]];
+        rt_packed_triangle& p = triangles[u.triangle_offset + k];
+        put3(p.v1, a.pos); put3(p.v2, b.pos); put3(p.v3, c.pos);
+        put3(p.n1, a.normal); put3(p.n2, b.normal); put3(p.n3, c.normal);
+        p.uv10 = a.uv[0]; p.uv11 = a.uv[1];
+        p.uv20 = b.uv[0]; p.uv21 = b.uv[1];
+        p.uv30 = c.uv[0]; p.uv31 = c.uv[1];
+    }
+    return refit_bvh(mesh_uniforms.data(), (uint32_t)mesh_uniforms.size(), triangles.data(), (uint32_t)triangles.size(),
+                     nodes.data(), (uint32_t)nodes.size(), u.triangle_offset, u.triangles, err);
 }
 
 rt_scene_uniform Scene::to_uniform() const {  // scene.rs:985-1001

@@ -76,8 +76,10 @@ class Scene {  // scene.rs:148-156
     std::vector<rt_packed_triangle> triangles;
     std::vector<rt_node> nodes;
     std::vector<rt_mesh_uniform> mesh_uniforms;
+    std::vector<uint32_t> triangle_order;  // per packed triangle: its source triangle in its mesh's index list (BvhResult::order)
     std::vector<Image> textures;
     bool built_bvh = false;
+    Quality built_quality = Quality::High;  // (of the last build_per_mesh)
 
     // ≙ BVH::build_per_mesh (bvh.rs:152-207)
     // device >= 0: meshes of at least `device_min_tris` triangles have their SAH searches done on that
@@ -87,6 +89,10 @@ class Scene {  // scene.rs:148-156
     // rt_mesh_uniform as build_per_mesh makes it -- the BVH stays (it does not depend on the transform), built_bvh too
     void set_mesh_transform(size_t i, const Transform& t);
     void set_mesh_material(size_t i, const rt_material& m);
+    // Moved vertices of mesh instance i (same count, same index list; copy-on-write when its MeshData is shared).  On a
+    // built scene the instance's packed triangles are repacked in BVH order and its nodes refitted (refit_bvh): the
+    // topology stays and the scene stays built.  Returns RT_OK, or an error code with `err` (nothing changed).
+    int set_mesh_vertices(size_t i, const std::vector<Vertex>& vertices, std::string& err);
     // ≙ Scene::to_uniform (scene.rs:985-1001)
     rt_scene_uniform to_uniform() const;
     // n x n barycentric split of every mesh triangle (stand-in geometry)

@@ -144,6 +144,39 @@ int rt_scene_set_sphere(rt_scene* s, uint32_t i, const float centre[3], float ra
     return RT_OK;
 }
 
+int rt_scene_set_mesh_vertices(rt_scene* s, uint32_t i, const float* vertices8, uint32_t n_vertices) {
+    if (!s || (n_vertices && !vertices8)) return RT_ERR_INVALID_ARGUMENT;
+    try {
+        std::vector<Vertex> v(n_vertices);
+        for (uint32_t k = 0; k < n_vertices; ++k) {
+            const float* p = vertices8 + (size_t)k * 8;
+            v[k].pos = {p[0], p[1], p[2]};
+            v[k].normal = {p[3], p[4], p[5]};
+            v[k].uv[0] = p[6];
+            v[k].uv[1] = p[7];
+        }
+        return s->scene.set_mesh_vertices(i, v, s->err);
+    } catch (const std::exception& e) {
+        s->err = e.what();
+        return RT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+int rt_scene_triangle_order(rt_scene* s, uint32_t i, uint32_t* out) {
+    if (!s || !out) return RT_ERR_INVALID_ARGUMENT;
+    if (!s->scene.built_bvh) {
+        s->err = "the scene is not built (rt_scene_build)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (i >= s->scene.mesh_uniforms.size()) {
+        s->err = "mesh instance " + std::to_string(i) + " out of range (" + std::to_string(s->scene.mesh_uniforms.size()) + " instances)";
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const rt_mesh_uniform& u = s->scene.mesh_uniforms[i];
+    if (u.triangles) memcpy(out, s->scene.triangle_order.data() + u.triangle_offset, (size_t)u.triangles * sizeof(uint32_t));
+    return RT_OK;
+}
+
 int rt_scene_add_obj(rt_scene* s, const char* assets_dir, const char* path, const rt_transform* t,
                      int use_mtl, const rt_material* m) {
     if (!s || !path) return RT_ERR_INVALID_ARGUMENT;

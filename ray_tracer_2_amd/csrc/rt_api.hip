@@ -19,7 +19,9 @@
 #include <string>
 #include <vector>
 
+#include "host/bvh.h"  // (rt2::refit_select / refit_bvh: the selection rule shared with the host refit)
 #include "rt_device.h"
+#include "rt_refit.h"
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0
@@ -51,6 +53,8 @@ hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const flo
 hipError_t launch_units_texture(const uint8_t* rgba8, uint32_t width, uint32_t height, const float* srgb_lut, const float* uv,
                                 float* out, unsigned long long n, hipStream_t stream);
 #endif
+hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
+hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -70,10 +74,12 @@ struct MeshGeom {
     uint32_t wide_base = 0, internal = 0;                           // first wide record, internal nodes
     uint32_t root_idx = 0, root_count = 0;                          // the root: record index, or triangle index + count (leaf)
     uint32_t tri_lo = 0xffffffffu, tri_hi = 0u;                     // triangle range of the leaves
+    uint32_t node_lo = 0, node_hi = 0;                              // interval of the nodes the root reaches (a refit's selection)
     uint32_t need = 0;                                              // stack entries of its walk
     float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};             // the root node's box
     bool deep = false;          // height >= 32: the shader's literal stack (DMESH_DEEP)
     bool contains = false;      // internal root whose box provably contains its children's (finite, proper)
+    bool unions = true;         // (internal root) the root box contains the union of two proper child boxes: roots_are_unions
     bool flat2_shape = false;   // internal, not deep, two leaf children (ITEM_FLAT2 when the scene allows it)
     bool hierarchy_ok = false;  // not deep, and a proper bounding hierarchy (cross-mesh pruning)
 };
@@ -289,6 +295,8 @@ struct rt_handle {
     bool have_scene = false;
     float4* blob = nullptr;  // the scene, see rt_device.h
     SceneGeom geom;          // the geometry phase's facts of the uploaded scene (rt_update_instances)
+    std::vector<rt_mesh_uniform> inst_meshes;  // the instance phase's inputs of the last upload / update (rt_refit_triangles
+    std::vector<rt_sphere> inst_spheres;       // reruns it)
     SceneLayout lay{};
     bool lds_scene = false;
     bool roots_are_unions = false;  // every internal root's box is the exact union of its children's
@@ -647,6 +655,7 @@ int build_geometry(rt_handle* h, const rt_mesh_uniform* meshes, uint32_t n_meshe
         // Wide records: internal nodes in DFS pre-order, indexed per mesh.
         // (Meshes may alias node ranges; records are built per mesh.)
         mg.wide_base = (uint32_t)wide.size();
+        mg.node_lo = mg.node_hi = m.node_offset;
         const rt_node* mn = nodes + m.node_offset;
         for (int k = 0; k < 3; ++k) { mg.box_lo[k] = mn[0].aabb_min[k]; mg.box_hi[k] = mn[0].aabb_max[k]; }
         // (child and root indices are absolute: triangle index into the scene's triangle
@@ -688,6 +697,7 @@ int build_geometry(rt_handle* h, const rt_mesh_uniform* meshes, uint32_t n_meshe
             g.top_mesh_base = mg.wide_base;
         }
         for (uint32_t n : order) {
+            mg.node_hi = std::max({mg.node_hi, m.node_offset + mn[n].left, m.node_offset + mn[n].right});
             const rt_node &ca = mn[mn[n].left], &cb = mn[mn[n].right];
             auto kind = [&](const rt_node& c, uint32_t local, uint32_t& idx, uint32_t& cnt) {
                 if (c.count > 0) {
@@ -734,6 +744,7 @@ int build_geometry(rt_handle* h, const rt_mesh_uniform* meshes, uint32_t n_meshe
                 if (!(mn[0].aabb_min[k] - mn[0].aabb_min[k] == 0.0f && mn[0].aabb_max[k] - mn[0].aabb_max[k] == 0.0f)) contains = false;  // finite
             }
             mg.contains = contains;
+            mg.unions = unions;
             if (!unions) g.roots_are_unions = false;
             // (root with two leaf children: a straight-line item in the few-mesh kernels, ITEM_FLAT2)
             mg.flat2_shape = !mg.deep && ca.count > 0 && cb.count > 0;
@@ -1260,6 +1271,8 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
         SceneInstances s;
         if ((rc = build_instances(h, g, spheres, n_spheres, meshes, n_meshes, s)) != RT_OK) return rc;
         const SceneLayout& lay = s.lay;
+        std::vector<rt_mesh_uniform> inst_meshes(meshes, meshes + n_meshes);
+        std::vector<rt_sphere> inst_spheres(spheres, spheres + n_spheres);
 #if RT_WALK2
         free_dev(h->walk2);
         h->walk2 = nullptr;
@@ -1318,6 +1331,8 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
         HIP_TRY(h, hipStreamSynchronize(h->stream));  // host staging vectors die here
         commit_scene(h, g, s, n_spheres, scene->camera);
         h->geom = std::move(g);
+        h->inst_meshes.swap(inst_meshes);
+        h->inst_spheres.swap(inst_spheres);
     } catch (const std::bad_alloc&) {
         return fail(h, RT_ERR_OUT_OF_MEMORY, "out of host memory");
     }
@@ -1353,6 +1368,8 @@ int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sp
         SceneInstances s;
         int rc = build_instances(h, g, spheres, n_spheres, meshes, n_meshes, s);
         if (rc != RT_OK) return rc;
+        std::vector<rt_mesh_uniform> inst_meshes(meshes, meshes + n_meshes);
+        std::vector<rt_sphere> inst_spheres(spheres, spheres + n_spheres);
         const SceneLayout& lay = s.lay;
         const uint64_t tail_bytes = g.tail_bytes();
         if (lay.wide_off == h->lay.wide_off) {
@@ -1386,11 +1403,193 @@ int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sp
             h->blob = fresh;
         }
         commit_scene(h, g, s, n_spheres, scene->camera);
+        h->inst_meshes.swap(inst_meshes);
+        h->inst_spheres.swap(inst_spheres);
         h->generation += 1;
     } catch (const std::bad_alloc&) {
         return fail(h, RT_ERR_OUT_OF_MEMORY, "out of host memory");
     }
     return RT_OK;
+}
+
+int rt_refit_bvh(const rt_mesh_uniform* meshes, uint32_t n_meshes, const rt_packed_triangle* triangles, uint32_t n_triangles,
+                 rt_node* nodes, uint32_t n_nodes, uint32_t first, uint32_t n) {
+    try {
+        std::string err;
+        const int rc = rt2::refit_bvh(meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, first, n, err);
+        return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+    } catch (const std::bad_alloc&) {
+        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+    }
+}
+
+// The device refit: validation and the scratch first, then the fit kernels, which write only the
+// scratch; their per-mesh results (one small readback) feed the instance phase; only then, once nothing can be refused,
+// the boxes and triangle records go into the blob -- the current one, or a resized one -- and the head is committed as
+// rt_update_instances commits it.
+int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32_t first, uint32_t n, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_REFIT_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    const bool host = (flags & RT_REFIT_HOST_MEMORY) != 0;
+    if (n && !triangles) return fail(h, RT_ERR_INVALID_ARGUMENT, "null triangles");
+    if (n && !host && ((uintptr_t)triangles & 15u) != 0u)
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "device triangles not aligned (16 bytes)");
+    const SceneGeom& g = h->geom;
+    if ((uint64_t)first + n > g.n_triangles)
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "triangle range [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) +
+                                                    ") exceeds the " + std::to_string(g.n_triangles) + " uploaded triangles");
+#if RT_EXPERIMENTS || RT_WALK2
+    // (as rt_update_instances: the hybrid small blob and walk2 records derive from the head and the deferred mesh's records)
+    return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_refit_triangles is not available in the experiments build (its hybrid small "
+                                            "blob and walk2 records derive from the scene): use rt_upload_scene");
+#endif
+    char* scratch = nullptr;
+    auto done = [&](int rc) {  // (every exit once the scratch exists: nothing may still use it when it is freed)
+        if (scratch) {
+            (void)hipStreamSynchronize(h->stream);
+            (void)hipFree(scratch);
+            scratch = nullptr;
+        }
+        return rc;
+    };
+    try {
+        // ---- the selection (rt_refit_bvh's rule, on the uploaded meshes' facts) and the slots ----
+        std::vector<rt2::RefitSpan> spans(g.mesh.size());
+        for (size_t i = 0; i < g.mesh.size(); ++i) {
+            const MeshGeom& mg = g.mesh[i];
+            spans[i] = rt2::RefitSpan{mg.tri_lo, mg.tri_hi, mg.node_lo, mg.node_hi, mg.triangle_offset};
+        }
+        std::vector<uint32_t> sel;
+        std::string why;
+        if (int rc = rt2::refit_select(spans, first, n, sel, why); rc != RT_OK) return fail(h, rc, why);
+        std::vector<RefitMesh> table(sel.size());
+        uint64_t slots = 0;
+        for (size_t q = 0; q < sel.size(); ++q) {
+            const MeshGeom& mg = g.mesh[sel[q]];
+            RefitMesh& r = table[q];
+            r.slot0 = (uint32_t)slots;
+            r.wide_base = mg.wide_base;
+            r.internal = mg.root_count ? 0u : mg.internal;
+            r.root_idx = mg.root_idx;
+            r.root_count = mg.root_count;
+            slots += r.internal ? r.internal : 1u;
+        }
+        // ---- scratch: mesh table, results, parent links, arrival counters, boxes, staging of host triangles ----
+        auto up = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
+        const uint64_t tab_b = up(table.size() * sizeof(RefitMesh)), res_b = up(table.size() * sizeof(RefitResult));
+        const uint64_t par_b = up(slots * 4u), arr_b = up(slots * 4u), box_b = up(slots * 64u);
+        const uint64_t stage_b = host ? up((uint64_t)n * sizeof(rt_packed_triangle)) : 0u;
+        const uint64_t scratch_b = tab_b + res_b + par_b + arr_b + box_b + stage_b;
+        if (!fits_cap(h, scratch_b))
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the refit's " +
+                                                     std::to_string((scratch_b + (1u << 20) - 1) >> 20) + " MB of scratch");
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (scratch_b && hipMalloc((void**)&scratch, scratch_b) != hipSuccess) {
+            scratch = nullptr;
+            (void)hipGetLastError();
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "rt_refit_triangles: no device memory for the scratch");
+        }
+        auto hip_fail = [&](const char* what, hipError_t e) {
+            return done(fail(h, RT_ERR_DEVICE, std::string("rt_refit_triangles: ") + what + ": " + hipGetErrorString(e)));
+        };
+        RefitArgs a{};
+        a.first = first;
+        a.n = n;
+        a.n_meshes = (uint32_t)table.size();
+        a.slots = (uint32_t)slots;
+        if (scratch) {
+            a.meshes = reinterpret_cast<const RefitMesh*>(scratch);
+            a.results = reinterpret_cast<RefitResult*>(scratch + tab_b);
+            a.parent = reinterpret_cast<uint32_t*>(scratch + tab_b + res_b);
+            a.arrivals = reinterpret_cast<uint32_t*>(scratch + tab_b + res_b + par_b);
+            a.boxes = reinterpret_cast<unsigned long long*>(scratch + tab_b + res_b + par_b + arr_b);
+        }
+        a.tris = host ? (const void*)(scratch + tab_b + res_b + par_b + arr_b + box_b) : (const void*)triangles;
+        hipError_t e = hipSuccess;
+        std::vector<RefitResult> results(table.size());
+        if (!table.empty()) {
+            if ((e = hipMemcpyAsync((void*)a.meshes, table.data(), table.size() * sizeof(RefitMesh), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return hip_fail("hipMemcpyAsync", e);
+            if ((e = hipMemsetAsync(a.results, 0, res_b, h->stream)) != hipSuccess) return hip_fail("hipMemsetAsync", e);
+            if ((e = hipMemsetAsync(a.parent, 0xff, par_b, h->stream)) != hipSuccess) return hip_fail("hipMemsetAsync", e);
+            if ((e = hipMemsetAsync(a.arrivals, 0, arr_b, h->stream)) != hipSuccess) return hip_fail("hipMemsetAsync", e);
+        }
+        if (host && n && (e = hipMemcpyAsync((void*)a.tris, triangles, (size_t)n * sizeof(rt_packed_triangle), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+            return hip_fail("hipMemcpyAsync", e);
+        // ---- fit: the scratch only (the blob's wide records are read for their references, which a refit keeps) ----
+        a.blob = h->blob;
+        a.wide_off = h->lay.wide_off;
+        a.tri_off = h->lay.tri_off;
+        a.shade_off = h->lay.shade_off;
+        if ((e = launch_refit_fit(a, h->stream)) != hipSuccess) return hip_fail("launch_refit_fit", e);
+        if (!table.empty() && (e = hipMemcpyAsync(results.data(), a.results, table.size() * sizeof(RefitResult), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
+            return hip_fail("hipMemcpyAsync", e);
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return hip_fail("hipStreamSynchronize", e);
+        // ---- the geometry facts of the refitted meshes, then the instance phase ----
+        SceneGeom g2 = g;
+        for (size_t q = 0; q < sel.size(); ++q) {
+            const RefitResult& r = results[q];
+            if ((r.flags & REFIT_DONE) == 0u || (r.flags & REFIT_BAD) != 0u)
+                return done(fail(h, RT_ERR_DEVICE, "rt_refit_triangles: mesh " + std::to_string(sel[q]) +
+                                                       ": the device refit did not reach its root (inconsistent BVH records)"));
+            MeshGeom& mg = g2.mesh[sel[q]];
+            for (int k = 0; k < 3; ++k) { mg.box_lo[k] = r.lo[k]; mg.box_hi[k] = r.hi[k]; }
+            if (mg.root_count == 0) {
+                mg.contains = (r.flags & REFIT_CONTAINS) != 0u;
+                mg.unions = (r.flags & REFIT_UNIONS) != 0u;
+            }
+            mg.hierarchy_ok = !mg.deep && (r.flags & REFIT_IMPROPER) == 0u;
+        }
+        g2.roots_are_unions = true;
+        for (const MeshGeom& mg : g2.mesh)
+            if (mg.root_count == 0 && !mg.unions) g2.roots_are_unions = false;
+        SceneInstances s;
+        if (int rc = build_instances(h, g2, h->inst_spheres.data(), (uint32_t)h->inst_spheres.size(), h->inst_meshes.data(),
+                                     (uint32_t)h->inst_meshes.size(), s); rc != RT_OK)
+            return done(rc);
+        // ---- write: from here on nothing is refused ----
+        const SceneLayout& lay = s.lay;
+        float4* target = h->blob;
+        if (lay.wide_off != h->lay.wide_off) {  // a resized head: a new blob, the old tail copied, then refitted there
+            if (hipMalloc((void**)&target, lay.bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return done(fail(h, RT_ERR_OUT_OF_MEMORY, "rt_refit_triangles: no device memory for the resized scene"));
+            }
+        }
+        auto drop_target = [&](int rc) {
+            if (target != h->blob) { (void)hipStreamSynchronize(h->stream); (void)hipFree(target); }
+            return rc;
+        };
+        if (int rc = drain_streams(h); rc != RT_OK) return done(drop_target(rc));  // (every launch that may read the blob)
+        const uint64_t tail_bytes = g2.tail_bytes();
+        if (target != h->blob) {
+            if ((uint64_t)lay.wide_off + tail_bytes != lay.bytes && (e = hipMemsetAsync(target, 0, lay.bytes, h->stream)) != hipSuccess)
+                return drop_target(hip_fail("hipMemsetAsync", e));
+            if (tail_bytes && (e = hipMemcpyAsync((char*)target + lay.wide_off, (const char*)h->blob + h->lay.wide_off, tail_bytes,
+                                                  hipMemcpyDeviceToDevice, h->stream)) != hipSuccess)
+                return drop_target(hip_fail("hipMemcpyAsync", e));
+        }
+        a.blob = target;
+        a.wide_off = lay.wide_off;
+        a.tri_off = lay.tri_off;
+        a.shade_off = lay.shade_off;
+        if ((e = launch_refit_write(a, h->stream)) != hipSuccess) return drop_target(hip_fail("launch_refit_write", e));
+        if (!s.head.empty() &&
+            (e = hipMemcpyAsync(target, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+            return drop_target(hip_fail("hipMemcpyAsync", e));
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return drop_target(hip_fail("hipStreamSynchronize", e));
+        if (target != h->blob) {
+            free_dev(h->blob);
+            h->blob = target;
+        }
+        const rt_camera_uniform camera = h->camera;
+        commit_scene(h, g2, s, (uint32_t)h->inst_spheres.size(), camera);
+        h->geom = std::move(g2);
+        h->generation += 1;
+        return done(RT_OK);
+    } catch (const std::bad_alloc&) {
+        return done(fail(h, RT_ERR_OUT_OF_MEMORY, "out of host memory"));
+    }
 }
 
 // rt_render_multi (device-to-device transport): the root may still be copying this handle's previous frame out of

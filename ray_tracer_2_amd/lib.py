@@ -31,6 +31,7 @@ EXPORTS = [
     "rt_intersect_rays", "rt_occluded_rays", "rt_pick",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
     "rt_scene_set_sphere",
+    "rt_refit_bvh", "rt_refit_triangles", "rt_refit_built_scene", "rt_scene_set_mesh_vertices", "rt_scene_triangle_order",
 ]
 # every symbol include/rt_test_abi.h declares (the test library only)
 TEST_EXPORTS = ["rt_test_device_units", "rt_test_sweep", "rt_test_device_sample_texture", "rt_test_read_wavefront",
@@ -144,6 +145,11 @@ def _bind(L, with_test_entries):
         "rt_scene_set_mesh_transform": (i32, [vp, u32, P(A.Transform)]),
         "rt_scene_set_mesh_material": (i32, [vp, u32, P(A.Material)]),
         "rt_scene_set_sphere": (i32, [vp, u32, P(C.c_float * 3), C.c_float, P(A.Material)]),
+        "rt_refit_bvh": (i32, [vp, u32, vp, u32, vp, u32, u32, u32]),
+        "rt_refit_triangles": (i32, [vp, vp, u32, u32, i32]),
+        "rt_refit_built_scene": (i32, [vp, vp, u32, u32]),
+        "rt_scene_set_mesh_vertices": (i32, [vp, u32, vp, u32]),
+        "rt_scene_triangle_order": (i32, [vp, u32, vp]),
     }
     assert set(sig) == set(EXPORTS)
     if with_test_entries:

@@ -75,6 +75,39 @@ class RayTracer:
         """update_instances from a built Scene (C++ object) after its setters (rt_update_built_scene)."""
         self._check(self._L.rt_update_built_scene(self._h, scene._p))
 
+    def refit_triangles(self, triangles, first):
+        """Moved vertices, same topology (rt_refit_triangles): uploaded triangles [first, first + n) become `triangles` and
+        the BVH is refitted on the device; the handle then equals a fresh update_buffers of the arrays with those triangles
+        and SceneArrays.refit_bvh(first, n)'s nodes.  `triangles`: n TRI_DTYPE records (numpy), or a float32 tensor of
+        shape (n, 24) on this handle's device -- read in order after the current torch stream's work, as trace_rays is."""
+        if hasattr(triangles, "data_ptr"):
+            import torch
+            t = triangles
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise ValueError("device triangles must be a float32 tensor")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"device triangles must be on cuda:{self.device}, not {t.device}")
+            if t.dim() != 2 or t.shape[1] != 24:
+                raise ValueError("device triangles must have shape (n, 24)")
+            t = t.contiguous()
+            n = t.shape[0]
+            cur = torch.cuda.current_stream(t.device)
+            ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=t.device)
+            ext.wait_stream(cur)
+            self._check(self._L.rt_refit_triangles(self._h, t.data_ptr() if n else None, int(first), n, 0))
+            cur.wait_stream(ext)   # (the call has read t when it returns; later work on the stream follows the refit)
+            return
+        t = np.ascontiguousarray(triangles).view(A.TRI_DTYPE).reshape(-1)
+        self._check(self._L.rt_refit_triangles(self._h, t.ctypes.data if t.shape[0] else None, int(first), t.shape[0],
+                                               A.REFIT_HOST_MEMORY))
+
+    def refit_built_scene(self, scene, first_mesh=0, n_meshes=None):
+        """refit_triangles with the packed triangles of mesh instances [first_mesh, first_mesh + n_meshes) of a built Scene
+        (C++ object) after its set_mesh_vertices (rt_refit_built_scene); n_meshes None: the rest of them."""
+        if n_meshes is None:
+            n_meshes = self._L.rt_scene_num_meshes(scene._p) - int(first_mesh)
+        self._check(self._L.rt_refit_built_scene(self._h, scene._p, int(first_mesh), int(n_meshes)))
+
     def load_built_scene(self, scene):
         """A built Scene (C++ object) straight to the device: textures + arrays, without the round trip through numpy
         (rt_upload_built_scene: what the C++ mirror's load_scene_gpu_resources + update_buffers do)."""

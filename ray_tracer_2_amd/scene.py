@@ -109,6 +109,25 @@ class Scene:
         self._check(self._L.rt_scene_set_sphere(self._p, int(i), C.byref((C.c_float * 3)(*centre)), float(radius),
                                                 C.byref(mat)))
 
+    # ---- moved vertices, same topology: a BVH refit instead of a rebuild ----
+    def set_mesh_vertices(self, i, vertices8):
+        """New (n, 8) float32 vertices (pos, normal, uv) of mesh instance i: the same count, the index list stays.  On a built
+        scene its packed triangles are repacked and its BVH refitted; RayTracer.refit_built_scene sends them."""
+        v = np.ascontiguousarray(vertices8, dtype=np.float32)
+        if v.ndim != 2 or v.shape[1] != 8:
+            raise ValueError("vertices8 must have shape (n, 8)")
+        self._check(self._L.rt_scene_set_mesh_vertices(self._p, int(i), v.ctypes.data, v.shape[0]))
+
+    def triangle_order(self, i):
+        """uint32 array: entry k is the source triangle (in mesh instance i's index list) of its packed triangle k, in BVH
+        order -- how to pack moved triangles (e.g. on the device) for RayTracer.refit_triangles."""
+        meshes = self.meshes()
+        if not 0 <= int(i) < len(meshes):
+            self._check(self._L.rt_scene_triangle_order(self._p, int(i), C.byref(C.c_uint32())))   # (its error)
+        out = np.empty(int(meshes[int(i)]["triangles"]), np.uint32)
+        self._check(self._L.rt_scene_triangle_order(self._p, int(i), out.ctypes.data if out.size else C.byref(C.c_uint32())))
+        return out
+
     def subdivide_meshes(self, n):
         self._check(self._L.rt_scene_subdivide_meshes(self._p, n))
 
@@ -205,6 +224,25 @@ class SceneArrays:
             tex.append(z[f"texture_{len(tex)}"])
         return cls(u, z["spheres"].astype(A.SPHERE_DTYPE), z["meshes"].astype(A.MESH_DTYPE),
                    z["triangles"].astype(A.TRI_DTYPE), z["nodes"].astype(A.NODE_DTYPE), tex)
+
+    def refit_bvh(self, first, n, triangles=None):
+        """rt_refit_bvh in place: optionally triangles[first:first + n] = `triangles` (n TRI_DTYPE records), then the node
+        boxes of every mesh whose leaves reference a triangle of [first, first + n) are recomputed from the triangles (the
+        box rule of include/rt_abi.h); the topology and the other meshes' nodes stay.  Returns self."""
+        first, n = int(first), int(n)
+        if triangles is not None:
+            t = np.ascontiguousarray(triangles).view(A.TRI_DTYPE).reshape(-1)
+            if t.shape[0] != n:
+                raise ValueError(f"{t.shape[0]} triangles for a range of {n}")
+            if first + n > self.triangles.shape[0]:
+                raise ValueError("triangle range past the end of the scene's triangles")
+            self.triangles[first:first + n] = t
+        L = load()
+        rc = L.rt_refit_bvh(self.meshes.ctypes.data, self.meshes.shape[0], self.triangles.ctypes.data, self.triangles.shape[0],
+                            self.nodes.ctypes.data, self.nodes.shape[0], first, n)
+        if rc < 0:
+            raise RtError(rc, L.rt_last_error(None).decode())
+        return self
 
     def texture_descs(self):
         n = len(self.textures)

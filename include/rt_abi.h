@@ -520,6 +520,47 @@ int rt_occluded_rays(rt_handle* h, const rt_ray* rays, uint64_t n, uint32_t* occ
  * RT_ERR_INVALID_ARGUMENT; no scene: RT_ERR_NO_SCENE. */
 int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hit* hit);
 
+/* First-hit buffers of a whole frame (the G-buffer a denoiser is guided by, an id mask, depth and normal maps; DESIGN.md
+ * section 2.10): for every texel of a params->width x params->height frame and the camera currently set, the closest hit
+ * of the ray the debug views and rt_pick trace for it (wgsl:502-515: no jitter), in ONE launch, into planes the caller
+ * owns.  Planes are row-major, tightly packed, row 0 = bottom of the view (as the image).  A NULL plane is not produced
+ * and costs nothing.  For every channel rt_hit also has, a texel holds the bits rt_pick(h, params, x, y, &hit) returns
+ * for it; a miss (and a texel whose ray rt_intersect_rays would call invalid, e.g. width == 1: x / (width - 1)) gets
+ * +INF, 0xffffffff and zeros -- `dir` is written all the same.
+ * Only width and height of `params` matter; the frame need not fit the handle's max_width x max_height (the image is
+ * not touched); width * height <= 2^31 - 1 (else RT_ERR_CAPACITY).
+ * Memory and ordering as rt_intersect_rays.  Without RT_GBUFFER_HOST_MEMORY the planes are device pointers on the
+ * handle's device (4-byte aligned; 16 for albedo / emission; 1 for flags) and the call is asynchronous on the handle's
+ * stream, after every earlier call on the handle and before every later one.  With it they are host pointers: the frame
+ * is produced in bands of whole rows through temporary device buffers of at most 64 MB, counted against option
+ * "max_device_mb" while held (RT_ERR_OUT_OF_MEMORY when not even one row fits), and the call returns when the data is
+ * on the host.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle / params / out, struct_bytes != sizeof(rt_gbuffer),
+ * _p0 != 0, unknown flags, zero width or height, misaligned device planes), RT_ERR_CAPACITY, RT_ERR_NO_SCENE.  All
+ * planes NULL: a no-op.
+ * Like the ray queries the call leaves the image, the primary tables, a frame_ahead batch in flight, the pipeline slots,
+ * rt_get_stats and rt_last_launch as they are, and ignores rt_set_counters. */
+typedef struct rt_gbuffer {
+    uint32_t  struct_bytes; /* = sizeof(rt_gbuffer): channels can be appended without writing past an older caller's struct */
+    uint32_t  _p0;          /* must be 0 */
+    float*    depth;        /* [h][w]     rt_hit.t: Hit.dst, world distance; +INF on a miss                        */
+    float*    dir;          /* [h][w][3]  the normalised ray direction (the origin is cam_to_world[3])             */
+    float*    point;        /* [h][w][3]  rt_hit.point                                                             */
+    float*    normal;       /* [h][w][3]  rt_hit.normal (the shading normal the render uses)                       */
+    float*    bary;         /* [h][w][2]  rt_hit.bary_u, bary_v                                                    */
+    float*    texcoord;     /* [h][w][2]  rt_hit.tex_u, tex_v                                                      */
+    float*    albedo;       /* [h][w][4]  `color` of wgsl:453-458: the diffuse texture's sample at Hit.uv when flag ==
+                             *            RT_MATERIAL_TEXTURE and diffuse_index != -1, else material.color (glass too);
+                             *            zeros on a miss                                                          */
+    float*    emission;     /* [h][w][4]  emission_color * emission_strength (wgsl:450), one multiply per component;
+                             *            zeros on a miss                                                          */
+    uint32_t* object;       /* [h][w]     rt_hit.object; 0xffffffff on a miss                                      */
+    uint32_t* primitive;    /* [h][w]     rt_hit.primitive; 0xffffffff on a miss                                   */
+    uint8_t*  flags;        /* [h][w]     RT_HIT_HIT | RT_HIT_BACKFACE                                             */
+} rt_gbuffer;
+enum { RT_GBUFFER_HOST_MEMORY = 1 };
+int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* out, int flags);
+
 /* The test-only entry points (rt_test_*: the kernels' arithmetic building blocks evaluated element-wise on the device, raw
  * copies of sequence buffers, the RCCL gather against a stub, the frame_ahead policy) are NOT exported by the product
  * library: include/rt_test_abi.h declares them and ray_tracer_2_amd/librt2_mi355x_test.so -- the same sources compiled

@@ -89,6 +89,18 @@ class Hit(C.Structure):  # rt_hit: a ray query's closest-hit record
                 ("normal", f32 * 3), ("bary_v", f32), ("tex_u", f32), ("tex_v", f32), ("_p1", f32 * 2)]
 
 
+class GBuffer(C.Structure):  # rt_gbuffer: the planes rt_render_gbuffer writes (a NULL plane is not produced)
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("depth", C.c_void_p), ("dir", C.c_void_p), ("point", C.c_void_p),
+                ("normal", C.c_void_p), ("bary", C.c_void_p), ("texcoord", C.c_void_p), ("albedo", C.c_void_p),
+                ("emission", C.c_void_p), ("object", C.c_void_p), ("primitive", C.c_void_p), ("flags", C.c_void_p)]
+
+
+# channel of rt_gbuffer -> (numpy dtype, components per texel; 0: a plane of shape (H, W))
+GBUFFER_CHANNELS = {"depth": ("<f4", 0), "dir": ("<f4", 3), "point": ("<f4", 3), "normal": ("<f4", 3), "bary": ("<f4", 2),
+                    "texcoord": ("<f4", 2), "albedo": ("<f4", 4), "emission": ("<f4", 4), "object": ("<u4", 0),
+                    "primitive": ("<u4", 0), "flags": ("u1", 0)}
+GBUFFER_HOST_MEMORY = 1
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():

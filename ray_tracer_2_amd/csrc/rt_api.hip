@@ -42,6 +42,7 @@ hipError_t launch_walk(const RenderArgs& a, uint32_t compute_units, hipStream_t 
 hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long long n, void* out, bool any, bool prune_tmax,
                         uint32_t blocks, uint32_t compute_units, hipStream_t stream);
 hipError_t launch_pick_ray(const RenderArgs& a, uint32_t x, uint32_t y, float4* ray, hipStream_t stream);
+hipError_t launch_gbuffer(const RenderArgs& a, const GBufferArgs& g, hipStream_t stream);
 hipError_t launch_wf_shade(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_wf_walk(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
 size_t wf_walk_lds_bytes(const RenderArgs& a);
@@ -2924,6 +2925,100 @@ int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hi
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail(h, RT_ERR_DEVICE, std::string("rt_pick: ") + hipGetErrorString(e));
     return RT_OK;
+}
+
+// ---- first-hit buffers of a frame (include/rt_abi.h: rt_render_gbuffer; rt_kernel.hip: rt_gbuffer_kernel) ----
+// Launched like a query: the arguments a render of the scene takes, nothing read but the scene and nothing written but
+// the caller's planes.
+int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* out, int flags) {
+    if (!h || !params || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (out->struct_bytes != sizeof(rt_gbuffer)) return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_gbuffer.struct_bytes is not sizeof(rt_gbuffer)");
+    if (out->_p0 != 0u) return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_gbuffer._p0 must be 0");
+    if (flags & ~RT_GBUFFER_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const uint32_t W = params->width, H = params->height;
+    if (W == 0u || H == 0u) return fail(h, RT_ERR_INVALID_ARGUMENT, "zero width or height");
+    if ((uint64_t)W * H > 0x7fffffffull) return fail(h, RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
+    // the planes in struct order: pointer, bytes per texel, alignment of a device pointer
+    void* const ptr[11] = {out->depth, out->dir, out->point, out->normal, out->bary, out->texcoord, out->albedo, out->emission,
+                           out->object, out->primitive, out->flags};
+    static const uint32_t bytes[11] = {4, 12, 12, 12, 8, 8, 16, 16, 4, 4, 1}, align[11] = {4, 4, 4, 4, 4, 4, 16, 16, 4, 4, 1};
+    static const char* const names[11] = {"depth", "dir", "point", "normal", "bary", "texcoord", "albedo", "emission", "object",
+                                          "primitive", "flags"};
+    size_t per_texel = 0;
+    for (int c = 0; c < 11; ++c) per_texel += ptr[c] ? bytes[c] : 0u;
+    if (per_texel == 0) return RT_OK;   // no plane asked for
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    const bool host = (flags & RT_GBUFFER_HOST_MEMORY) != 0;
+    if (!host)
+        for (int c = 0; c < 11; ++c)
+            if (ptr[c] && ((uintptr_t)ptr[c] & (align[c] - 1u)) != 0u)
+                return fail(h, RT_ERR_INVALID_ARGUMENT, std::string("device plane ") + names[c] + " is not aligned to " + std::to_string(align[c]) + " bytes");
+    HIP_TRY(h, hipSetDevice(h->device));
+    RenderArgs a{};
+    scene_args(h, a);
+    a.params = rt_params{};
+    a.params.width = W;
+    a.params.height = H;
+    a.camera = h->camera;
+    GBufferArgs g{};
+    g.width = W;
+    g.height = H;
+    auto bind = [&](void* const p[11]) {
+        g.depth = (float*)p[0]; g.dir = (float*)p[1]; g.point = (float*)p[2]; g.normal = (float*)p[3]; g.bary = (float*)p[4];
+        g.texcoord = (float*)p[5]; g.albedo = (float4*)p[6]; g.emission = (float4*)p[7]; g.object = (uint32_t*)p[8];
+        g.primitive = (uint32_t*)p[9]; g.flags = (uint8_t*)p[10];
+    };
+    if (!host) {
+        g.row0 = 0;
+        g.rows = H;
+        bind(ptr);
+        HIP_TRY(h, launch_gbuffer(a, g, h->stream));
+        return RT_OK;
+    }
+    // host memory: bands of whole rows through one temporary device buffer of at most 64 MB, within option max_device_mb;
+    // each plane's part of it starts at a multiple of 256 bytes (11 x 256 bytes of slack at most)
+    const size_t slack = 11u * 256u;
+    size_t room = (size_t)64 << 20;
+    if (h->max_device_bytes != 0) {
+        const size_t held = optional_bytes(h);
+        const size_t left = h->max_device_bytes > held ? h->max_device_bytes - held : 0;
+        room = std::min(room, left);
+    }
+    const size_t row_bytes = (size_t)W * per_texel;
+    const uint32_t band = room > slack ? (uint32_t)std::min<uint64_t>(H, (room - slack) / row_bytes) : 0u;
+    if (band == 0u) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for one row of the G-buffer's staging planes");
+    auto hip_fail = [&](const char* what, hipError_t e) { return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
+    uint8_t* d_buf = nullptr;
+    void* d_ptr[11] = {};
+    size_t off = 0;
+    for (int c = 0; c < 11; ++c) {
+        if (!ptr[c]) continue;
+        d_ptr[c] = (void*)off;   // (offset for now)
+        off = (off + (size_t)band * W * bytes[c] + 255u) & ~(size_t)255u;
+    }
+    hipError_t e = hipMalloc((void**)&d_buf, off);
+    if (e != hipSuccess)
+        return e == hipErrorOutOfMemory ? fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the G-buffer's staging planes") : hip_fail("hipMalloc", e);
+    for (int c = 0; c < 11; ++c)
+        if (ptr[c]) d_ptr[c] = d_buf + (size_t)d_ptr[c];
+    bind(d_ptr);
+    int rc = RT_OK;
+    for (uint32_t r0 = 0; rc == RT_OK && r0 < H; r0 += band) {
+        g.row0 = r0;
+        g.rows = std::min(band, H - r0);
+        if ((e = launch_gbuffer(a, g, h->stream)) != hipSuccess) { rc = hip_fail("launch_gbuffer", e); break; }
+        for (int c = 0; c < 11 && rc == RT_OK; ++c) {
+            if (!ptr[c]) continue;
+            const size_t row = (size_t)W * bytes[c];
+            if ((e = hipMemcpyAsync(static_cast<uint8_t*>(ptr[c]) + r0 * row, d_ptr[c], g.rows * row, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
+                rc = hip_fail("hipMemcpyAsync", e);
+        }
+        if (rc != RT_OK) break;
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) { rc = hip_fail("hipStreamSynchronize", e); break; }
+    }
+    if (rc != RT_OK) (void)hipStreamSynchronize(h->stream);  // (nothing may still use the buffer when it is freed)
+    free_dev(d_buf);
+    return rc;
 }
 
 int rt_synchronize(rt_handle* h) {

@@ -297,6 +297,22 @@ struct BlendArgs {
     float weight[RT_MAX_BATCH_FRAMES], rest[RT_MAX_BATCH_FRAMES];  // wgsl:157-158 per frame, from the host
 };
 
+// rt_gbuffer_kernel (rt_render_gbuffer): rows [row0, row0 + rows) of the width x height frame; every plane pointer
+// addresses the first texel of row row0 (a NULL plane is not produced).
+struct GBufferArgs {
+    uint32_t width, height, row0, rows;
+    float *depth, *dir, *point, *normal, *bary, *texcoord;
+    float4 *albedo, *emission;
+    uint32_t *object, *primitive;
+    uint8_t* flags;
+};
+// 64-texel work items of the band: runs of 64 consecutive texels, or (tiles: the many-mesh kernels) tiles of 8x8, partial
+// ones at the right and top edges included
+__host__ __device__ inline uint32_t gbuffer_chunks(const GBufferArgs& g, bool tiles) {
+    if (!tiles) return (uint32_t)(((unsigned long long)g.rows * g.width + 63u) / 64u);
+    return ((g.width + 7u) / 8u) * ((g.rows + 7u) / 8u);
+}
+
 }  // namespace rtd
 
 #endif

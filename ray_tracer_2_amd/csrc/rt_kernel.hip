@@ -3011,6 +3011,153 @@ hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long lon
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// First-hit buffers of a frame (rt_render_gbuffer; include/rt_abi.h): for every texel of rows
+// [row0, row0 + rows) the ray rt_debug_kernel / rt_pick_ray_kernel generate for it -- the same operations --, validated
+// and intersected as rt_query_kernel does it for rt_pick (same instantiation, EXPORT), and the hit written channel by
+// channel into the planes that are not NULL (wave-uniform branches: a channel that is off costs nothing, the texture
+// filter included).  One wave per chunk of 64 texels (the queries' persistent grid was measured a sixth slower here) -- for
+// the few-mesh kernels 64 consecutive texels of the band in row-major order (the planes are tightly packed, so the band is ONE array:
+// every store of a wave is one contiguous run for any width), for the many-mesh kernels (TLAS), whose walk gains a fifth
+// from coherent rays, a tile of 8x8 texels (runs of 8 texels per row); measured, DESIGN.md section 2.10.
+// Every channel is ONE store per lane of the texel's 1, 4, 8, 12 or 16 contiguous bytes (the planes of 2 and 3 floats
+// are only 4-byte aligned: global memory takes such a store): lane after lane a run's bytes are contiguous, so one
+// instruction fills every 32-byte sector it touches but the run's two ends.
+// The wave index is read from the first lane, so the chunk's place in the frame is wave-uniform; a plane is addressed from
+// the chunk's first texel in it -- a scalar base, passed through scalar_base so that the compiler keeps it apart from the
+// lane's part instead of holding eleven per-lane 64-bit addresses across the walk -- plus the lane's texel within the
+// chunk, a 32-bit element index.
+// ---------------------------------------------------------------------------
+template <class T>
+DEV T* scalar_base(T* p) {
+    unsigned long long b = reinterpret_cast<unsigned long long>(p);
+    asm("" : "+s"(b));  // (no instruction: the value is wave-uniform and lives in a scalar register pair from here on)
+    return reinterpret_cast<T*>(b);
+}
+// The planes are written once and read by nobody in the launch: streaming stores keep them from displacing the scene in L2.
+// base: the chunk's first texel in the plane; e: this lane's texel from there.  (global-address-space pointers:
+// global_store, not flat_store -- the integer round trip of scalar_base forgets the address space)
+#define RT_GLOBAL(T, p) ((__attribute__((address_space(1))) T*)(void*)(p))
+template <class T>
+DEV void store_plane(T* base, uint32_t e, T v) { __builtin_nontemporal_store(v, RT_GLOBAL(T, base + e)); }
+DEV void store_plane(float4* base, uint32_t e, float4 v) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, RT_GLOBAL(v4f, base + e));
+}
+DEV void store_plane2(float* base, uint32_t e, float x, float y) {
+    typedef float v2f __attribute__((ext_vector_type(2), aligned(4)));
+    __builtin_nontemporal_store(v2f{x, y}, RT_GLOBAL(v2f, base + 2u * (size_t)e));
+}
+DEV void store_plane3(float* base, uint32_t e, float x, float y, float z) {
+    typedef float v3f __attribute__((ext_vector_type(3), aligned(4)));
+    __builtin_nontemporal_store(v3f{x, y, z}, RT_GLOBAL(v3f, base + 3u * (size_t)e));
+}
+
+template <bool LDS, bool TLAS, bool SIMPLE>
+__global__ void __launch_bounds__(BLOCK_THREADS) rt_gbuffer_kernel(const RenderArgs a, const GBufferArgs g) {
+    constexpr bool TILES = TLAS;
+    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6)));
+    const uint32_t chunk = wave;
+    const uint32_t n = g.rows * g.width;  // (<= 2^31 - 1: the host checks)
+    const uint32_t tiles_x = (g.width + 7u) >> 3;
+    // this lane's texel from the chunk's first one, in the planes (a tile's rows beyond the band wrap: never stored)
+    const uint32_t e = TILES ? (lane >> 3) * g.width + (lane & 7u) : lane;
+    const float sx = (float)g.width, sy = (float)g.height;
+    const float* __restrict__ c2w = &a.camera.cam_to_world[0][0];
+    const f3 cam_origin{c2w[12], c2w[13], c2w[14]};
+    auto finite3 = [](f3 v) { return rtm::abs_(v.x) < __builtin_inff() && rtm::abs_(v.y) < __builtin_inff() && rtm::abs_(v.z) < __builtin_inff(); };
+    {
+        uint32_t x, yl, first;  // this lane's texel in the band; the chunk's first texel in the planes
+        bool inside;
+        if constexpr (!TILES) {
+            first = chunk * 64u;
+            const uint32_t i = first + lane;
+            inside = i < n;
+            yl = i / g.width;
+            x = i - yl * g.width;
+        } else {
+            const uint32_t ty = chunk / tiles_x, x0 = (chunk - ty * tiles_x) << 3;
+            x = x0 + (lane & 7u);
+            yl = ty * 8u + (lane >> 3);
+            inside = yl < g.rows && x < g.width;
+            first = ty * 8u * g.width + x0;
+        }
+        // wgsl:502-515, as rt_debug_kernel
+        const float fx = (float)x, fy = (float)(g.row0 + yl);
+        const float uvx = fx / (sx - 1.0f), uvy = fy / (sy - 1.0f);
+        const f3 local_focus = f3{uvx - 0.5f, uvy - 0.5f, 1.0f} *
+                               f3{a.camera.view_params[0], a.camera.view_params[1], a.camera.view_params[2]};
+        const f3 focus_point = mat_xyz(c2w, local_focus, 1.0f);
+        const f3 d = focus_point - cam_origin;
+        const f3 rd = normalize3(d);
+        // rt_query_kernel's validity of the rt_ray (cam_origin, +inf, d, 0) and its closest hit
+        const bool valid = inside && finite3(cam_origin) && finite3(d) && finite3(rd) && (rd.x != 0.0f || rd.y != 0.0f || rd.z != 0.0f);
+        if (g.dir && inside) store_plane3(scalar_base(g.dir + 3u * (size_t)first), e, rd.x, rd.y, rd.z);  // (before the walk: nothing of the ray outlives it)
+        int node_tests = 0, tri_tests = 0;
+        Isect I;
+        Hit h{};
+        if (valid) h = intersect_scene<LDS, false, TLAS, false, SIMPLE, false, false, true>(a, cam_origin, rd, stack, node_tests, tri_tests, I);
+        const bool hit = valid && h.hit && h.dst < __builtin_inff();
+        const bool sphere = !SIMPLE && I.object < 0;
+        if (g.depth && inside) store_plane(scalar_base(g.depth + first), e, hit ? h.dst : __builtin_inff());
+        if (g.object && inside) store_plane(scalar_base(g.object + first), e, hit ? (h.mat_off - a.lay.mat_off) / MATERIAL_BYTES : 0xffffffffu);
+        if (g.primitive && inside) store_plane(scalar_base(g.primitive + first), e, hit ? (sphere ? (uint32_t)(-I.object - 1) : (I.win_tri & 0x7fffffffu)) : 0xffffffffu);
+        if (g.flags && inside) store_plane(scalar_base(g.flags + first), e, hit ? (uint8_t)(1u | (h.backface ? 2u : 0u)) : (uint8_t)0u);
+        if (g.point && inside) store_plane3(scalar_base(g.point + 3u * (size_t)first), e, hit ? h.point.x : 0.0f, hit ? h.point.y : 0.0f, hit ? h.point.z : 0.0f);
+        if (g.normal && inside) store_plane3(scalar_base(g.normal + 3u * (size_t)first), e, hit ? h.normal.x : 0.0f, hit ? h.normal.y : 0.0f, hit ? h.normal.z : 0.0f);
+        if (g.bary && inside) store_plane2(scalar_base(g.bary + 2u * (size_t)first), e, hit && !sphere ? I.win_u : 0.0f, hit && !sphere ? I.win_v : 0.0f);
+        if (g.texcoord && inside) store_plane2(scalar_base(g.texcoord + 2u * (size_t)first), e, hit ? h.u : 0.0f, hit ? h.v : 0.0f);
+        if (g.albedo) {  // `color` of wgsl:453-458
+            float4 color = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (hit) {
+                const int flag = ldi<LDS>(a, h.mat_off + M_FLAG), diffuse_index = ldi<LDS>(a, h.mat_off + M_DIFFUSE_IDX);
+                if (!SIMPLE && flag == RT_MATERIAL_TEXTURE && diffuse_index != -1) {
+                    const f4 s = sample_texture(a, diffuse_index, h.u, h.v);
+                    color = make_float4(s.x, s.y, s.z, s.w);
+                } else {
+                    color = ld4<LDS>(a, h.mat_off + M_COLOR);
+                }
+            }
+            if (inside) store_plane(scalar_base(g.albedo + first), e, color);
+        }
+        if (g.emission) {  // wgsl:450
+            float4 em = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (hit) {
+                const float4 ec = ld4<LDS>(a, h.mat_off + M_EMISSION);
+                const float es = ldf<LDS>(a, h.mat_off + M_EMISSION_S);
+                em = make_float4(ec.x * es, ec.y * es, ec.z * es, ec.w * es);
+            }
+            if (inside) store_plane(scalar_base(g.emission + first), e, em);
+        }
+    }
+}
+
+// grid: one wave per chunk (the workgroups of the last partial one have waves without a chunk: they stage and leave).
+// Measured against the queries' persistent grid, which restages an LDS scene less often: DESIGN.md section 2.10.
+hipError_t launch_gbuffer(const RenderArgs& a, const GBufferArgs& g, hipStream_t stream) {
+    const bool tlas = a.many_mesh != 0u, simple = !tlas && a.simple != 0u;  // launch_variant's choice
+    const uint32_t chunks = gbuffer_chunks(g, tlas);
+    if (chunks == 0) return hipSuccess;
+    const size_t lds = render_lds_bytes(a);
+    const uint32_t blocks = (chunks + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    auto go = [&](auto kernel) {
+        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, g);
+    };
+    if (a.lds_scene) {
+        if (tlas) go(rt_gbuffer_kernel<true, true, false>);
+        else if (simple) go(rt_gbuffer_kernel<true, false, true>);
+        else go(rt_gbuffer_kernel<true, false, false>);
+    } else {
+        if (tlas) go(rt_gbuffer_kernel<false, true, false>);
+        else if (simple) go(rt_gbuffer_kernel<false, false, true>);
+        else go(rt_gbuffer_kernel<false, false, false>);
+    }
+    return hipGetLastError();
+}
+
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0
 #endif

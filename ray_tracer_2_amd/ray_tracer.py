@@ -236,7 +236,7 @@ class RayTracer:
         self._check(self._L.rt_test_scene_blob(self._h, out.ctypes.data, out.nbytes, C.byref(lay), C.byref(ptr)))
         return out, np.array(lay, np.uint32), int(ptr.value)
 
-    # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick) ----
+    # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick) and frame-wide first hits (rt_render_gbuffer) ----
     def trace_rays(self, origins, dirs, tmax=None):
         """Closest hit of rays (origins[i], dirs[i]) on the uploaded scene, as a render's walk computes it; a hit at
         t >= tmax[i] is reported as a miss (tmax None: unbounded).  numpy inputs: a synchronous call that returns a
@@ -284,6 +284,44 @@ class RayTracer:
         return {"t": hit.t, "object": hit.object, "primitive": hit.primitive, "backface": bool(hit.flags & A.HIT_BACKFACE),
                 "point": tuple(hit.point), "normal": tuple(hit.normal), "bary": (hit.bary_u, hit.bary_v),
                 "uv": (hit.tex_u, hit.tex_v)}
+
+    def render_gbuffer(self, params, channels=("depth", "normal", "albedo", "object"), device=False):
+        """First-hit buffers of the params.width x params.height frame for the camera currently set (rt_render_gbuffer): per
+        texel the closest hit of the ray the debug views and pick trace for it, row 0 = bottom.  `channels`: names of
+        rt_gbuffer's planes (_abi.GBUFFER_CHANNELS); a channel that is not asked for costs nothing.  Returns a dict of
+        numpy arrays of shape (H, W) or (H, W, C) (synchronous), or with device=True of torch tensors on this handle's
+        device, produced asynchronously after the current torch stream's work, as trace_rays orders itself."""
+        if not isinstance(params, A.Params):
+            raise ValueError("params must be a Params (make_params)")
+        channels = tuple(channels)
+        for c in channels:
+            if c not in A.GBUFFER_CHANNELS:
+                raise ValueError(f"unknown G-buffer channel {c!r}: one of {', '.join(A.GBUFFER_CHANNELS)}")
+        if len(set(channels)) != len(channels):
+            raise ValueError("a G-buffer channel is named twice")
+        H, W = int(params.height), int(params.width)
+        g = A.GBuffer(struct_bytes=C.sizeof(A.GBuffer))
+        out = {}
+        if not device:
+            for c in channels:
+                dt, k = A.GBUFFER_CHANNELS[c]
+                out[c] = np.zeros((H, W, k) if k else (H, W), np.dtype(dt))
+                setattr(g, c, out[c].ctypes.data)
+            self._check(self._L.rt_render_gbuffer(self._h, C.byref(params), C.byref(g), A.GBUFFER_HOST_MEMORY))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        kinds = {"<f4": torch.float32, "<u4": torch.int32, "u1": torch.uint8}   # (object / primitive: the u32 bits as int32)
+        for c in channels:
+            dt, k = A.GBUFFER_CHANNELS[c]
+            out[c] = torch.empty((H, W, k) if k else (H, W), dtype=kinds[dt], device=dev)
+            setattr(g, c, out[c].data_ptr() if out[c].numel() else None)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
+        ext.wait_stream(cur)
+        self._check(self._L.rt_render_gbuffer(self._h, C.byref(params), C.byref(g), 0))
+        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launch: _device_query)
+        return out
 
     @staticmethod
     def hits_to_numpy(hits):

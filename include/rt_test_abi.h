@@ -64,6 +64,27 @@ int rt_test_rccl_gather(const char* lib_path, int n_ranks);
  * and whether the host counts as one that waits for every frame.  0 = the call renders its own frame only. */
 int rt_test_frame_ahead_depth(int lds_scene, uint64_t texels, int rays_per_pixel, int number_of_bounces, int host_waits);
 
+/* Test-only: the BVH builder's SAH plane search (find_best_split, bvh.rs:299-351) for host-given nodes, without a build
+ * around it: device -1 runs the host search (csrc/host/bvh.cpp: make_host_level_search, no GPU needed), device >= 0 the
+ * kernels of csrc/rt_bvh_search.hip (make_device_level_search).  tri9: nine floats per triangle (centroid, min, max; any
+ * values, non-finite ones included); order: the n triangle ids in their current order; a query is a node -- positions
+ * [start, start + count) of `order` and the node's box.  The queries are given level by level: level l has
+ * level_counts[l] of them (0 allowed), consecutive in `queries`; all n_levels levels go, in turn, through ONE search
+ * object (the device buffers a level outgrows are reallocated, as in a build).  out: one result per query.
+ * RT_ERR_INVALID_ARGUMENT, before anything reaches the device, for a null array, an order entry >= n, count < 2 (the
+ * builder never asks, and host and device answer differently) or start + count > n; a HIP error is RT_ERR_DEVICE.
+ * Error text: rt_last_error(NULL). */
+typedef struct rt_test_sah_query {
+    uint32_t start, count;
+    float aabb_min[3], aabb_max[3];
+} rt_test_sah_query;
+typedef struct rt_test_sah_result {
+    int32_t axis;
+    float pos, cost;
+} rt_test_sah_result;
+int rt_test_sah_search(int device, const float* tri9, uint64_t n, const uint32_t* order, const rt_test_sah_query* queries,
+                       const uint32_t* level_counts, uint32_t n_levels, rt_test_sah_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3389,6 +3389,50 @@ int rt_test_rccl_gather(const char* lib_path, int n_ranks) {
     api.unload();
     return ok ? RT_OK : fail(nullptr, RT_ERR_DEVICE, "rt_render_multi gather: " + gerr);
 }
+
+// Test-only: find_best_split for host-given nodes through a LevelSearch -- the host one (device -1, no GPU needed) or
+// the kernels of rt_bvh_search.hip --, the levels in turn through one search object, as bvh_build_levels drives it.
+// tests/test_bvh_search_host.py, tests/test_gpu_bvh_search.py.
+int rt_test_sah_search(int device, const float* tri9, uint64_t n, const uint32_t* order, const rt_test_sah_query* queries,
+                       const uint32_t* level_counts, uint32_t n_levels, rt_test_sah_result* out) {
+    if (device < -1) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "device must be -1 (host search) or a device ordinal");
+    if (n == 0 || n > RT_MAX_TRIANGLES || !tri9 || !order) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "no triangles, or too many");
+    if (n_levels && !level_counts) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null level_counts");
+    uint64_t total = 0;
+    for (uint32_t l = 0; l < n_levels; ++l) total += level_counts[l];
+    if (total && (!queries || !out)) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null queries or results");
+    for (uint64_t p = 0; p < n; ++p)
+        if (order[p] >= n) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "order[" + std::to_string(p) + "] is not a triangle id");
+    for (uint64_t k = 0; k < total; ++k) {
+        if (queries[k].count < 2)
+            return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "query " + std::to_string(k) + ": count < 2 (the builder never searches such a node)");
+        if ((uint64_t)queries[k].start + queries[k].count > n)
+            return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "query " + std::to_string(k) + ": start + count exceeds the " + std::to_string(n) + " triangles");
+    }
+    try {
+        const rt2::LevelSearch search = device >= 0 ? rt2::make_device_level_search(device, tri9, (size_t)n)
+                                                    : rt2::make_host_level_search(tri9, (size_t)n);
+        std::vector<rt2::SplitQuery> qs;
+        std::vector<rt2::SplitResult> rs;
+        uint64_t base = 0;
+        for (uint32_t l = 0; l < n_levels; ++l) {
+            qs.resize(level_counts[l]);
+            for (uint32_t k = 0; k < level_counts[l]; ++k) {
+                const rt_test_sah_query& q = queries[base + k];
+                qs[k].start = q.start;
+                qs[k].count = q.count;
+                memcpy(qs[k].aabb_min, q.aabb_min, 12);
+                memcpy(qs[k].aabb_max, q.aabb_max, 12);
+            }
+            search(order, (size_t)n, qs, rs);
+            for (uint32_t k = 0; k < level_counts[l]; ++k) out[base + k] = rt_test_sah_result{rs[k].axis, rs[k].pos, rs[k].cost};
+            base += level_counts[l];
+        }
+    } catch (const std::exception& e) {   // (as rt_scene_build_device sorts them)
+        return fail(nullptr, strncmp(e.what(), "HIP", 3) == 0 ? RT_ERR_DEVICE : RT_ERR_OUT_OF_MEMORY, e.what());
+    }
+    return RT_OK;
+}
 #endif  // RT_TEST_ENTRIES
 
 void* rt_device_image(rt_handle* h) { return h ? (void*)h->image : nullptr; }

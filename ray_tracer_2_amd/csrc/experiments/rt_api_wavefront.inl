@@ -49,21 +49,10 @@ static int wavefront_prepare(rt_handle* h, const rt_params* params, const Render
     }
     if (wavefront) {
         const size_t need_counts = (size_t)wf_rounds64 + 2;
-        if (h->wf_counts_capacity < need_counts) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            free_dev(h->wf_counts);
-            HIP_TRY(h, hipMalloc((void**)&h->wf_counts, need_counts * sizeof(uint32_t)));
-            h->wf_counts_capacity = need_counts;
-        }
+        if (int rc = regrow(h, h->wf_counts, h->wf_counts_capacity, need_counts, h->stream); rc != RT_OK) return rc;
         // the slots' primary-ray memos: 13 dwords each, in blocks of 64 slots
         const size_t need = (((size_t)wf_slots64 + 63) / 64) * 64 * PIXEL_MEMO_DWORDS;
-        if (h->pixel_cache_words < need) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            free_dev(h->pixel_cache_mem);
-            h->pixel_cache_words = 0;
-            HIP_TRY(h, hipMalloc((void**)&h->pixel_cache_mem, need * sizeof(uint32_t)));
-            h->pixel_cache_words = need;
-        }
+        if (int rc = regrow(h, h->pixel_cache_mem, h->pixel_cache_words, need, h->stream); rc != RT_OK) return rc;
         rounds = false;
     }
     wf.on = wavefront;
@@ -99,10 +88,7 @@ static int wavefront_run(rt_handle* h, const RenderArgs& a, const WavefrontPlan&
     uint32_t* lists[2] = {h->wf_lists, h->wf_lists + h->wf_capacity};
     const uint32_t shade_blocks = h->compute_units * 4u;  // (the shade kernel is compiled for 4 waves per SIMD: 128 VGPRs)
     const size_t wlds = wf_walk_lds_bytes(w);
-    uint32_t walk_per_cu = wlds ? (uint32_t)((160u * 1024u) / wlds) : BLOCKS_PER_CU;
-    if (walk_per_cu > BLOCKS_PER_CU) walk_per_cu = BLOCKS_PER_CU;
-    if (walk_per_cu < 1u) walk_per_cu = 1u;
-    const uint32_t walk_blocks = h->compute_units * walk_per_cu;
+    const uint32_t walk_blocks = h->compute_units * blocks_per_cu_for(wlds);
     w.wf_round0 = 1;
     w.wf_list_in = nullptr;
     w.wf_count_in = nullptr;
@@ -113,9 +99,7 @@ static int wavefront_run(rt_handle* h, const RenderArgs& a, const WavefrontPlan&
     for (uint32_t r = 0; r < R; ++r) {
         w.wf_list_in = lists[r & 1u];
         w.wf_count_in = h->wf_counts + r;
-        h->work_slot = (h->work_slot + 1) & 63u;
-        if (h->work_slot == 0u) HIP_TRY(h, hipMemsetAsync(h->work_counters, 0, 64 * sizeof(uint32_t), h->stream));
-        w.work_counter = h->work_counters + h->work_slot;
+        HIP_TRY(h, h->work.next(h->stream, w.work_counter));
         HIP_TRY(h, launch_wf_walk(w, walk_blocks, h->stream));
         w.wf_list_out = lists[(r + 1) & 1u];
         w.wf_count_out = h->wf_counts + r + 1;

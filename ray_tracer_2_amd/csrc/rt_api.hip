@@ -95,6 +95,60 @@ struct SceneGeom {
     }
 };
 
+// The frame layout a buffer, a table or a history was made for: the image size and the strip split.  The default (zero)
+// shape is "nothing made yet": it equals no shape a launch can have (render_impl refuses world == 0).
+struct FrameShape {
+    uint32_t width = 0, height = 0, rank = 0, world = 0;
+    bool operator==(const FrameShape& o) const { return width == o.width && height == o.height && rank == o.rank && world == o.world; }
+    bool operator!=(const FrameShape& o) const { return !(*this == o); }
+    // texels of this rank's share (world == 1: the frame itself, without the padding of a ragged last strip)
+    uint64_t texels() const { return world == 1 ? (uint64_t)width * height : rt_strip_texels(width, height, rank, world); }
+};
+
+// primary table (rt_primary_kernel): every pixel's memo -- its constant primary ray and (option "primary_hits") that
+// ray's hit -- valid for (camera, width, height, strip layout, scene, with / without hits); 64 B per pixel
+struct PrimaryTable {
+    void* table = nullptr;
+    size_t texels = 0;
+    bool valid = false, with_hits = false;  // (valid: cleared by whatever changes the scene or the walk that found the hits)
+    rt_camera_uniform camera{};
+    FrameShape shape;
+};
+
+// a fresh tile counter per launch: a ring of 64, zeroed in one go each time it wraps (launches on
+// one stream are ordered, so every earlier user of the ring is done by then)
+struct CounterRing {
+    uint32_t* mem = nullptr;
+    uint32_t slot = 0;
+    hipError_t create(hipStream_t stream) {
+        const hipError_t e = hipMalloc((void**)&mem, 64 * sizeof(uint32_t));
+        slot = 0;
+        return e != hipSuccess ? e : hipMemsetAsync(mem, 0, 64 * sizeof(uint32_t), stream);
+    }
+    hipError_t next(hipStream_t stream, uint32_t*& counter) {
+        slot = (slot + 1) & 63u;
+        counter = mem + slot;
+        return slot == 0u ? hipMemsetAsync(mem, 0, 64 * sizeof(uint32_t), stream) : hipSuccess;
+    }
+};
+
+// One frame in flight of the pipelined single frames (rt_handle::pipeline): what is per slot.
+struct PipeSlot {
+    hipStream_t stream = nullptr;
+    hipEvent_t sampled = nullptr;     // frame sampled into `scratch` (recorded on `stream`)
+    hipEvent_t blended = nullptr;     // ... and blended out of it (recorded on the handle's stream)
+    bool sampled_set = false, blended_set = false;
+    float4* scratch = nullptr;        // (rt_handle::pipe_scratch_texels texels)
+    FrameShape zeroed;                // the frame layout the scratch image's padding rows were zeroed for
+    CounterRing work;                 // a ring of launch counters per pipe stream
+    uint32_t* memo = nullptr;         // further global-memory primary-ray memos (pixel_cache == 2)
+    size_t memo_words = 0;
+    // A pipelined frame whose camera (or shape) is not the shared table's builds a table of its OWN pipeline slot on its own
+    // stream -- ordered behind that slot's previous frame and read by nobody else, so no frame in flight has to finish
+    // first: the frames of a moving camera overlap like those of a standing one (option "primary_per_slot", default 1).
+    PrimaryTable primary;
+};
+
 struct rt_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -183,20 +237,12 @@ struct rt_handle {
     hipStream_t copy_stream = nullptr;
     hipEvent_t snapshot_taken = nullptr, snapshot_read = nullptr;
     bool snapshot_read_pending = false;                // a read of the staging buffer was queued since the last snapshot
-    uint32_t pipe_layout[PIPE_MAX][5] = {};            // (w, h, rank, world, texels) each scratch image's padding rows were zeroed for
-    hipStream_t pipe_stream[PIPE_MAX] = {};
-    hipEvent_t pipe_sampled[PIPE_MAX] = {};            // frame sampled into scratch[i] (recorded on pipe_stream[i])
-    hipEvent_t pipe_blended[PIPE_MAX] = {};            // ... and blended out of it (recorded on the handle's stream)
+    PipeSlot pipe[PIPE_MAX];
     hipEvent_t pipe_book = nullptr;                    // the last tile-order / primary-table rebuild (recorded on a pipe stream)
     hipEvent_t pipe_main = nullptr;                    // the last launch that was not pipelined (recorded on the handle's stream)
-    bool pipe_sampled_set[PIPE_MAX] = {}, pipe_blended_set[PIPE_MAX] = {}, pipe_book_set = false, pipe_main_set = false;
+    bool pipe_book_set = false, pipe_main_set = false;
     bool pipe_main_need = true;                        // pipelined frames have to wait for pipe_main before they sample (render_impl)
-    float4* pipe_scratch[PIPE_MAX] = {};
-    size_t pipe_scratch_texels = 0;
-    uint32_t* pipe_work[PIPE_MAX] = {};                // a ring of launch counters per pipe stream
-    uint32_t pipe_work_slot[PIPE_MAX] = {};
-    uint32_t* pipe_memo[PIPE_MAX] = {};                // further global-memory primary-ray memos (pixel_cache == 2)
-    size_t pipe_memo_words[PIPE_MAX] = {};
+    size_t pipe_scratch_texels = 0;                    // texels of every slot's scratch image
     uint32_t pipe_seq = 0;
     float4* small_blob = nullptr;
     SceneLayout small_lay{};
@@ -215,7 +261,7 @@ struct rt_handle {
     int multi_copied_device = -1;
     bool multi_copy_pending = false;
     // batch scratch: the frame layout its padding rows were zeroed for
-    uint32_t scratch_w = 0, scratch_h = 0, scratch_rank = 0, scratch_world = 0, scratch_n = 0;
+    FrameShape batch_zeroed;
     // root side of rt_render_multi
     std::vector<void*> multi_comms;       // ncclComm_t per rank
     std::vector<int> multi_comm_devices;  // the device list the communicators were made for
@@ -244,36 +290,17 @@ struct rt_handle {
     uint32_t max_width = 0, max_height = 0;
     float4* image = nullptr;
     Counters* counters = nullptr;
-    uint32_t* work_counters = nullptr;  // ring of per-launch tile counters
+    CounterRing work;  // ring of per-launch tile counters (launches on the handle's stream)
     uint32_t* pixel_cache_mem = nullptr;  // primary-ray cache when LDS has no room (persistent kernel)
     size_t pixel_cache_words = 0;
-    uint32_t work_slot = 0;
     int kernel_variant = -1;  // -1 auto, 0 persistent + lane refill, 1 one wave per tile
     // tile-cost feedback: rays per tile of the previous frame order the next frame's tiles
     uint32_t* tile_cost[2] = {nullptr, nullptr};
     uint32_t* tile_order = nullptr;
     uint32_t tile_capacity = 0;
     int cost_slot = 0;
-    bool history_valid = false;
-    uint32_t hist_w = 0, hist_h = 0, hist_rank = 0, hist_world = 0;
-    // primary table (rt_primary_kernel): every pixel's memo -- its constant primary ray and (option "primary_hits") that
-    // ray's hit -- valid for (camera, width, height, strip layout, scene, with / without hits); 64 B per pixel
-    void* primary = nullptr;
-    size_t primary_texels = 0;
-    bool primary_valid = false;
-    rt_camera_uniform primary_camera{};
-    uint32_t primary_w = 0, primary_h = 0, primary_rank = 0, primary_world = 0;
-    bool primary_with_hits = false;
-    // A pipelined frame whose camera (or shape) is not the shared table's builds a table of its OWN pipeline slot on its own
-    // stream -- ordered behind that slot's previous frame and read by nobody else, so no frame in flight has to finish
-    // first: the frames of a moving camera overlap like those of a standing one (option "primary_per_slot", default 1).
-    struct SlotTable {
-        void* table = nullptr;
-        size_t texels = 0;
-        bool valid = false, with_hits = false;
-        rt_camera_uniform camera{};
-        uint32_t w = 0, h = 0, rank = 0, world = 0;
-    } slot_primary[PIPE_MAX];
+    FrameShape history;  // the frame layout the tile costs and the tile order were recorded for
+    PrimaryTable primary;  // the shared table (every stream's frames read it); the slots' own: PipeSlot::primary
     int primary_per_slot = 1;
     // A frame whose camera is not the previous frame's (the camera is MOVING) renders without a table: every pixel computes its
     // own memo (its primary ray is traversed once, by its first sample) -- building a table that the next frame throws away
@@ -377,11 +404,11 @@ int fail(rt_handle* h, int code, const std::string& msg) {
 
 // bytes of device memory the handle holds on its own initiative (see rt_handle::max_device_bytes)
 size_t optional_bytes(const rt_handle* h) {
-    size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary_texels * 64u +
+    size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary.texels * 64u +
                2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity;
-    for (int k = 0; k < rt_handle::PIPE_MAX; ++k) {
-        if (h->pipe_scratch[k]) b += h->pipe_scratch_texels * sizeof(float4);
-        b += h->pipe_memo_words[k] * sizeof(uint32_t) + h->slot_primary[k].texels * 64u;
+    for (const PipeSlot& ps : h->pipe) {
+        if (ps.scratch) b += h->pipe_scratch_texels * sizeof(float4);
+        b += ps.memo_words * sizeof(uint32_t) + ps.primary.texels * 64u;
     }
     return b;
 }
@@ -405,6 +432,72 @@ void free_dev(T*& p) {
         (void)hipFree(p);
         p = nullptr;
     }
+}
+
+// A device buffer of `have` elements of `each` bytes is replaced by one of `need`: free, hipMalloc, record the size (0
+// while there is no buffer).  Whoever may still read the old buffer has been synchronised by the caller.
+int replace_dev(rt_handle* h, void** p, size_t& have, size_t need, size_t each) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    have = 0;
+    HIP_TRY(h, hipMalloc(p, need * each));
+    have = need;
+    return RT_OK;
+}
+// Grow a device buffer that only the launches on `reader` read: synchronise them, then replace it.
+template <typename T>
+int regrow(rt_handle* h, T*& p, size_t& have, size_t need, hipStream_t reader) {
+    if (have >= need) return RT_OK;
+    HIP_TRY(h, hipStreamSynchronize(reader));
+    return replace_dev(h, (void**)&p, have, need, sizeof(T));
+}
+
+// workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
+constexpr size_t CU_LDS_BYTES = (160u * 1024u);
+uint32_t blocks_per_cu_for(size_t lds_bytes) {
+    const uint32_t per_cu = lds_bytes ? (uint32_t)(CU_LDS_BYTES / lds_bytes) : BLOCKS_PER_CU;
+    return per_cu > BLOCKS_PER_CU ? BLOCKS_PER_CU : per_cu < 1u ? 1u : per_cu;
+}
+// ... and the persistent grid of the handle at that occupancy (option "persistent_blocks" counts BLOCKS_PER_CU per CU)
+uint32_t persistent_blocks_for(const rt_handle* h, size_t lds_bytes) {
+    const uint32_t fit = (h->persistent_blocks / BLOCKS_PER_CU) * blocks_per_cu_for(lds_bytes);
+    return fit < h->persistent_blocks && fit > 0 ? fit : h->persistent_blocks;
+}
+
+// The blend weight pair of frame `frames` (wgsl:157-158): two separate IEEE operations, as the shader rounds them
+// (i32 arithmetic wraps in the shader; frames = -1 gives +inf there too)
+void blend_weights(int32_t frames, float& weight, float& rest) {
+    volatile float w = 1.0f / (float)(int32_t)((uint32_t)frames + 1u);
+    volatile float r = 1.0f - w;
+    weight = w;
+    rest = r;
+}
+
+// whatever the tables hold (the primary hits: a function of the scene and of the walk that found them) is stale
+void invalidate_primary_tables(rt_handle* h) {
+    h->primary.valid = false;
+    for (PipeSlot& ps : h->pipe) ps.primary.valid = false;
+}
+
+// A pipeline slot's stream, events and counter ring (its scratch image, memo and table are made when a frame needs them)
+int pipe_slot_create(rt_handle* h, PipeSlot& ps) {
+    if (!ps.stream) HIP_TRY(h, hipStreamCreateWithFlags(&ps.stream, hipStreamNonBlocking));
+    if (!ps.sampled) HIP_TRY(h, hipEventCreateWithFlags(&ps.sampled, hipEventDisableTiming));
+    if (!ps.blended) HIP_TRY(h, hipEventCreateWithFlags(&ps.blended, hipEventDisableTiming));
+    if (!ps.work.mem) HIP_TRY(h, ps.work.create(ps.stream));
+    return RT_OK;
+}
+void pipe_slot_destroy(PipeSlot& ps) {
+    if (ps.stream) {
+        (void)hipStreamSynchronize(ps.stream);
+        (void)hipStreamDestroy(ps.stream);
+    }
+    if (ps.sampled) (void)hipEventDestroy(ps.sampled);
+    if (ps.blended) (void)hipEventDestroy(ps.blended);
+    free_dev(ps.scratch);
+    free_dev(ps.work.mem);
+    free_dev(ps.memo);
+    free_dev(ps.primary.table);
 }
 
 void free_scene(rt_handle* h) {
@@ -532,8 +625,7 @@ int rt_create(int device_ordinal, uint32_t max_width, uint32_t max_height, rt_ha
     HIP_TRY(h, hipMemsetAsync(h->image, 0, texels * sizeof(float4), h->stream));
     HIP_TRY(h, hipMalloc((void**)&h->counters, sizeof(Counters)));
     HIP_TRY(h, hipMemsetAsync(h->counters, 0, sizeof(Counters), h->stream));
-    HIP_TRY(h, hipMalloc((void**)&h->work_counters, 64 * sizeof(uint32_t)));
-    HIP_TRY(h, hipMemsetAsync(h->work_counters, 0, 64 * sizeof(uint32_t), h->stream));
+    HIP_TRY(h, h->work.create(h->stream));
     h->tile_capacity = ((max_width + 7) / 8) * ((max_height + 7) / 8 + 1);
     for (int k = 0; k < 2; ++k) HIP_TRY(h, hipMalloc((void**)&h->tile_cost[k], (size_t)h->tile_capacity * sizeof(uint32_t)));
     HIP_TRY(h, hipMalloc((void**)&h->tile_order, (size_t)h->tile_capacity * sizeof(uint32_t)));
@@ -565,17 +657,7 @@ void rt_destroy(rt_handle* h) {
     free_dev(h->park_queue[0]);
     free_dev(h->park_queue[1]);
     free_dev(h->park_counts);
-    for (int k = 0; k < rt_handle::PIPE_MAX; ++k) {
-        free_dev(h->pipe_memo[k]);
-        if (h->pipe_stream[k]) {
-            (void)hipStreamSynchronize(h->pipe_stream[k]);
-            (void)hipStreamDestroy(h->pipe_stream[k]);
-        }
-        if (h->pipe_sampled[k]) (void)hipEventDestroy(h->pipe_sampled[k]);
-        if (h->pipe_blended[k]) (void)hipEventDestroy(h->pipe_blended[k]);
-        free_dev(h->pipe_scratch[k]);
-        free_dev(h->pipe_work[k]);
-    }
+    for (PipeSlot& ps : h->pipe) pipe_slot_destroy(ps);
     if (h->pipe_book) (void)hipEventDestroy(h->pipe_book);
     if (h->pipe_main) (void)hipEventDestroy(h->pipe_main);
     if (h->copy_stream) {
@@ -594,9 +676,8 @@ void rt_destroy(rt_handle* h) {
     if (g_rccl.lib)
         for (void* c : h->multi_comms) (void)g_rccl.CommDestroy((ncclComm_t)c);
     free_dev(h->counters);
-    free_dev(h->work_counters);
-    free_dev(h->primary);
-    for (auto& st : h->slot_primary) free_dev(st.table);
+    free_dev(h->work.mem);
+    free_dev(h->primary.table);
     free_dev(h->pixel_cache_mem);
 #if RT_WALK2
     free_dev(h->walk2);
@@ -1230,16 +1311,15 @@ void commit_scene(rt_handle* h, const SceneGeom& g, const SceneInstances& s, uin
     h->lds_scene = (uint64_t)lay.bytes + stacks <= LDS_BUDGET_BYTES;
     h->camera = camera;
     h->have_scene = true;
-    h->history_valid = false;
-    h->primary_valid = false;  // (the table holds hits: a function of the scene)
-    for (auto& st : h->slot_primary) st.valid = false;
+    h->history = FrameShape{};
+    invalidate_primary_tables(h);  // (the tables hold hits: a function of the scene)
 }
 
 // Every launch enqueued so far on any of the handle's streams is complete (they all may read the blob).
 int drain_streams(rt_handle* h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < rt_handle::PIPE_MAX; ++k)
-        if (h->pipe_stream[k]) HIP_TRY(h, hipStreamSynchronize(h->pipe_stream[k]));
+    for (PipeSlot& ps : h->pipe)
+        if (ps.stream) HIP_TRY(h, hipStreamSynchronize(ps.stream));
     return RT_OK;
 }
 
@@ -1649,13 +1729,12 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
         h->persistent_blocks = (uint32_t)value;
     } else if (n == "tile_feedback") {
         h->tile_feedback = value ? 1 : 0;
-        h->history_valid = false;
+        h->history = FrameShape{};
     } else if (n == "primary_table") {
         h->use_primary = value ? 1 : 0;
     } else if (n == "primary_hits") {
         h->primary_hits = value ? 1 : 0;
-        h->primary_valid = false;
-        for (auto& st : h->slot_primary) st.valid = false;
+        invalidate_primary_tables(h);
     } else if (n == "max_device_mb") {
         if (value < 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "max_device_mb must be >= 0 (0 = no cap)");
         h->max_device_bytes = (size_t)value << 20;
@@ -1666,7 +1745,7 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
     } else if (n == "tile_feedback_period") {
         if (value < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "tile_feedback_period must be >= 1");
         h->tile_feedback_period = value;
-        h->history_valid = false;
+        h->history = FrameShape{};
     } else if (n == "vote_eighths") {
         if (value < -1 || value > 8) return fail(h, RT_ERR_INVALID_ARGUMENT, "vote_eighths must be -1 (automatic) or 0..8");
         h->vote_eighths = value;
@@ -1693,8 +1772,7 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
         h->cull_roots = value;
     } else if (n == "cross_prune") {
         h->cross_prune = value ? 1 : 0;
-        h->primary_valid = false;   // (the primary hits in the tables were found by the other walk)
-        for (auto& st : h->slot_primary) st.valid = false;
+        invalidate_primary_tables(h);   // (the primary hits in the tables were found by the other walk)
     } else if (n == "lds_scene") {
         h->force_global = value ? 0 : 1;
     } else if (n == "defer_min_nodes") {
@@ -1762,9 +1840,6 @@ uint64_t rt_strip_texels(uint32_t width, uint32_t height, uint32_t rank, uint32_
     return (uint64_t)local * 8u * width;
 }
 
-// One launch of the hot path: a single frame (n_batch == 0: wgsl `main`, blending in place), or a batch
-// of n_batch >= 2 consecutive frames (Params.frames advancing by one each, app.rs:44-53) sampled in one
-// persistent launch over (frame, tile) work items and blended in frame order by a dense second kernel.
 // Sum of the recorded launch times (HIP events around every launch since rt_reset_timing).  The pairs are recorded on
 // whichever stream the launch ran on -- the pipelined frames' internal streams too -- and synchronising the handle's
 // stream only proves that the KERNELS before a pair's second event are done (the blends wait for them), not that the
@@ -1825,75 +1900,96 @@ static void scene_args(const rt_handle* h, RenderArgs& a) {
     a.n_items = h->n_items;
 }
 
-static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uint32_t world, uint32_t n_batch = 0,
-                       bool blend_later = false) {
-    if (!h || !params) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    h->ahead.valid = false;  // (whatever launches here breaks a sequence of frames rendered ahead: render_single)
+// What the steps of one render_impl call decide and share.
+struct LaunchPlan {
+    FrameShape shape;
+    uint32_t n_batch = 0;        // frames of the batch (0: a single frame)
+    bool blend_later = false;    // (frames rendered ahead: the calls that ask for them blend them, render_single)
+    uint64_t need_texels = 0;    // texels of this rank's share
+    size_t park_records = 0, park_bytes = 0;  // deferred walks: records and bytes of ONE park queue
+    uint32_t n_rounds = 0;       // how many rounds of deferred walks this launch would run (0: none)
+    bool rounds = false;         // ... and whether it runs them
+    WavefrontPlan wf;
+    bool pipe = false;           // a pipelined single frame
+    uint32_t pslot = 0;          // its pipeline slot
+    hipStream_t S = nullptr;     // the stream this frame's sampling launch and its bookkeeping run on
+    bool pipe_barrier = false;   // this frame rewrites shared tables (tile order, primary rays): the other stream's frame has to be done
+    bool took_idle_path = false; // this frame would have been pipelined, found nothing in flight and takes the plain launch
+    bool wrote_tables = false;   // this launch rewrites a table later launches read (tile order, tile costs, primary table)
+    uint32_t n_tiles = 0;
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;  // the launch's (start, stop) events
+};
+
+static int validate_and_shape(rt_handle* h, LaunchPlan& pl) {
     if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    if (world == 0 || rank >= world) return fail(h, RT_ERR_INVALID_ARGUMENT, "bad rank/world");
-    if (params->width == 0 || params->height == 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "empty image");
-    const uint64_t need_texels = world == 1 ? (uint64_t)params->width * params->height
-                                            : rt_strip_texels(params->width, params->height, rank, world);
-    if (need_texels > h->image_texels)
+    if (pl.shape.world == 0 || pl.shape.rank >= pl.shape.world) return fail(h, RT_ERR_INVALID_ARGUMENT, "bad rank/world");
+    if (pl.shape.width == 0 || pl.shape.height == 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "empty image");
+    pl.need_texels = pl.shape.texels();
+    if (pl.need_texels > h->image_texels)
         return fail(h, RT_ERR_CAPACITY, "image larger than the bound image buffer");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-    RenderArgs a{};
+    return wait_pending_copy(h);
+}
+
+static int prepare_batch_scratch(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
+    const uint32_t n_batch = pl.n_batch;
+    if (!n_batch) return RT_OK;
+    if (n_batch > RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "batch too large");
+    const uint64_t scratch_stride = pl.need_texels;
+    if (h->batch_scratch_texels < scratch_stride * n_batch) {
+        // Room for the largest batch the options allow, not just this one: a later, larger batch of the same shape
+        // (a warm-up of 5 frames, then 20) must not re-allocate -- a hipMalloc of hundreds of megabytes costs tens of
+        // milliseconds -- in the middle of a host's frame sequence.
+        const uint64_t slots = std::max<uint64_t>(n_batch, std::min<uint64_t>((uint64_t)h->batch_frames_opt, RT_MAX_BATCH_FRAMES));
+        const size_t old_bytes = h->batch_scratch_texels * sizeof(float4);
+        if (!fits_cap(h, scratch_stride * n_batch * sizeof(float4), old_bytes))
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the scratch images of this batch");
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        free_dev(h->batch_scratch);
+        h->batch_scratch_texels = 0;
+        if (fits_cap(h, scratch_stride * slots * sizeof(float4)) &&
+            hipMalloc((void**)&h->batch_scratch, scratch_stride * slots * sizeof(float4)) == hipSuccess) {
+            h->batch_scratch_texels = scratch_stride * slots;
+        } else {   // (not that much memory: what this batch needs)
+            (void)hipGetLastError();
+            HIP_TRY(h, hipMalloc((void**)&h->batch_scratch, scratch_stride * n_batch * sizeof(float4)));
+            h->batch_scratch_texels = scratch_stride * n_batch;
+        }
+        h->batch_zeroed = FrameShape{};  // (new memory: zero it below)
+    }
+    // The padding rows of a ragged last strip are never rendered: they must blend as zeros, not as the samples an
+    // earlier batch of another shape left there.  Zero ALL of the scratch whenever the shape of its frames changes
+    // (slot k of any later batch of this shape starts at k strides: the number of frames does not matter).
+    if (h->batch_zeroed != pl.shape) {
+        HIP_TRY(h, hipMemsetAsync(h->batch_scratch, 0, h->batch_scratch_texels * sizeof(float4), h->stream));
+        h->batch_zeroed = pl.shape;
+    }
+    a.batch_frames = n_batch;
+    a.batch_stride = scratch_stride;
+    a.batch_tile_major = (uint32_t)h->batch_tile_major;
+    return RT_OK;
+}
+
+// the frame's constants: parameters, camera, the memo's ray origin, the blend weights, the reciprocal of the sample count
+static void frame_constants(const rt_handle* h, const rt_params* params, RenderArgs& a) {
     a.params = *params;
     a.camera = h->camera;
-    if (n_batch) {
-        if (n_batch > RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "batch too large");
-        const uint64_t scratch_stride = need_texels;
-        if (h->batch_scratch_texels < scratch_stride * n_batch) {
-            // Room for the largest batch the options allow, not just this one: a later, larger batch of the same shape
-            // (a warm-up of 5 frames, then 20) must not re-allocate -- a hipMalloc of hundreds of megabytes costs tens of
-            // milliseconds -- in the middle of a host's frame sequence.
-            const uint64_t slots = std::max<uint64_t>(n_batch, std::min<uint64_t>((uint64_t)h->batch_frames_opt, RT_MAX_BATCH_FRAMES));
-            const size_t old_bytes = h->batch_scratch_texels * sizeof(float4);
-            if (!fits_cap(h, scratch_stride * n_batch * sizeof(float4), old_bytes))
-                return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the scratch images of this batch");
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            free_dev(h->batch_scratch);
-            h->batch_scratch_texels = 0;
-            if (fits_cap(h, scratch_stride * slots * sizeof(float4)) &&
-                hipMalloc((void**)&h->batch_scratch, scratch_stride * slots * sizeof(float4)) == hipSuccess) {
-                h->batch_scratch_texels = scratch_stride * slots;
-            } else {   // (not that much memory: what this batch needs)
-                (void)hipGetLastError();
-                HIP_TRY(h, hipMalloc((void**)&h->batch_scratch, scratch_stride * n_batch * sizeof(float4)));
-                h->batch_scratch_texels = scratch_stride * n_batch;
-            }
-            h->scratch_w = 0;  // (new memory: zero it below)
-        }
-        // The padding rows of a ragged last strip are never rendered: they must blend as zeros, not as the samples an
-        // earlier batch of another shape left there.  Zero ALL of the scratch whenever the shape of its frames changes
-        // (slot k of any later batch of this shape starts at k strides: the number of frames does not matter).
-        if (h->scratch_w != params->width || h->scratch_h != params->height || h->scratch_rank != rank ||
-            h->scratch_world != world) {
-            HIP_TRY(h, hipMemsetAsync(h->batch_scratch, 0, h->batch_scratch_texels * sizeof(float4), h->stream));
-            h->scratch_w = params->width; h->scratch_h = params->height; h->scratch_rank = rank;
-            h->scratch_world = world; h->scratch_n = n_batch;
-        }
-        a.batch_frames = n_batch;
-        a.batch_stride = scratch_stride;
-        a.batch_tile_major = (uint32_t)h->batch_tile_major;
-    }
     for (int k = 0; k < 3; ++k) {  // see pixel_cache_begin: the same IEEE operations, unfused
         volatile float rz = h->camera.cam_to_world[0][k] * 0.0f, uz = h->camera.cam_to_world[1][k] * 0.0f;
         volatile float t = h->camera.cam_to_world[3][k] + rz;
         a.memo_ro[k] = t + uz;
     }
-    {
-        // (i32 arithmetic wraps in the shader; frames = -1 gives +inf there too)
-        volatile float w = 1.0f / (float)(int32_t)((uint32_t)params->frames + 1u);
-        volatile float r = 1.0f - w;
-        a.blend_weight = w;
-        a.blend_rest = r;
-    }
+    blend_weights(params->frames, a.blend_weight, a.blend_rest);
     {
         const int32_t n = params->rays_per_pixel;
         a.spp_reciprocal = (n > 0 && (n & (n - 1)) == 0) ? 1.0f / (float)n : 0.0f;
     }
+}
+
+// Which kernel runs and what its workgroups hold: the variant, the pixel memo's home, the LDS-staged tops of the
+// experiments build, the persistent grid.
+static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs& a, const LaunchPlan& pl) {
+    const uint32_t rank = pl.shape.rank, world = pl.shape.world, n_batch = pl.n_batch;
     scene_args(h, a);
     // the per-lane primary-ray cache is used when it still leaves room for 4 workgroups per CU
     a.image = n_batch ? h->batch_scratch : h->image;
@@ -1933,41 +2029,30 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
         // 1: as many of the breadth-first numbered records (the top levels first) as fit without costing a workgroup per
         // CU; 2: the whole tree if the LDS can hold it at all
         const size_t used = render_lds_bytes(a), need = (size_t)h->n_tlas_records * WIDE_REC_BYTES;
-        const uint32_t per_cu_now = std::min<uint32_t>(BLOCKS_PER_CU, (uint32_t)((160u * 1024u) / (used ? used : 1)));
-        const size_t room = (160u * 1024u) / per_cu_now > used ? (160u * 1024u) / per_cu_now - used : 0;
+        const uint32_t per_cu_now = blocks_per_cu_for(used);
+        const size_t room = CU_LDS_BYTES / per_cu_now > used ? CU_LDS_BYTES / per_cu_now - used : 0;
         if (h->lds_tlas == 2) {
             if (used + need <= 64u * 1024u) a.tlas_lds = h->n_tlas_records;
         } else {
             a.tlas_lds = std::min<uint32_t>(h->n_tlas_records, (uint32_t)(room / WIDE_REC_BYTES));
         }
     }
-    a.persistent_blocks = h->persistent_blocks;
-    {
-        // workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
-        const size_t lds = render_lds_bytes(a);
-        uint32_t per_cu = lds ? (uint32_t)((160u * 1024u) / lds) : BLOCKS_PER_CU;
-        if (per_cu > BLOCKS_PER_CU) per_cu = BLOCKS_PER_CU;
-        if (per_cu < 1u) per_cu = 1u;
-        const uint32_t fit = (h->persistent_blocks / BLOCKS_PER_CU) * per_cu;
-        if (fit < a.persistent_blocks && fit > 0) a.persistent_blocks = fit;
-    }
+    a.persistent_blocks = persistent_blocks_for(h, render_lds_bytes(a));
+    const size_t memo_words = (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
     if (h->pixel_cache_opt && a.pixel_cache == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
-        (h->pixel_cache_words >= (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u ||
-         fits_cap(h, (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u * sizeof(uint32_t), h->pixel_cache_words * sizeof(uint32_t)))) {
+        (h->pixel_cache_words >= memo_words || fits_cap(h, memo_words * sizeof(uint32_t), h->pixel_cache_words * sizeof(uint32_t)))) {
         // persistent kernel: a fixed number of waves, so the cache can live in global memory
-        const size_t need = (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
-        if (h->pixel_cache_words < need) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            free_dev(h->pixel_cache_mem);
-            HIP_TRY(h, hipMalloc((void**)&h->pixel_cache_mem, need * sizeof(uint32_t)));
-            h->pixel_cache_words = need;
-        }
+        if (int rc = regrow(h, h->pixel_cache_mem, h->pixel_cache_words, memo_words, h->stream); rc != RT_OK) return rc;
         a.pixel_cache = 2;
         a.pixel_cache_mem = h->pixel_cache_mem;
     }
     a.fast_miss = h->fast_miss != 0 && a.pixel_cache != 0u ? 1u : 0u;
-    // how many rounds of deferred walks this launch would run (0: none)
-    const size_t park_records = (size_t)need_texels * (n_batch ? n_batch : 1u);
+    return RT_OK;
+}
+
+// how many rounds of deferred walks this launch would run (0: none)
+static void plan_rounds(const rt_handle* h, const rt_params* params, const RenderArgs& a, LaunchPlan& pl) {
+    const size_t park_records = (size_t)pl.need_texels * (pl.n_batch ? pl.n_batch : 1u);
     const size_t park_bytes = ((park_records + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4);  // per queue
     uint32_t n_rounds = h->sort_rounds > 0 ? (uint32_t)h->sort_rounds : 0u;
     if (h->sort_rounds < 0 && h->have_defer) {
@@ -1988,23 +2073,31 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
             if (!fits_cap(h, 2 * park_bytes, 2 * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)))) n_rounds = 0;  // (option max_device_mb)
         }
     }
-    bool rounds = n_rounds > 0 && h->have_defer && a.many_mesh == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
-                  params->rays_per_pixel > 0 && a.lds_scene == 0u;
-    // The intersection vote (path_begin).  The more a traversal costs beside the rest of an iteration, the longer it pays
-    // to let the lanes on memoised primary segments catch up first: 6/8 of the lanes or 3 iterations when the scene is in
-    // LDS and walked by the few-mesh kernels (config 2: 1.221 ms per frame; 1.222 with 7/8 and 16, 1.366 with 8/8), 7/8 or
-    // 16 iterations otherwise (sponza-sized stand-in 10.69 -> 10.21 ms, 200-mesh stand-in 5.00 -> 4.85), every lane or 16
-    // iterations in a deferred-walk sequence, whose resumed pixels arrive in every phase (config 3 stand-in 5.86 -> 5.45,
-    // config 5 geometry 3.35 -> 3.22; profiles/r03_experiments/ab_*_vote*.txt).
-    {
-        const bool costly = a.lds_scene == 0u || a.many_mesh != 0u;
-        a.vote_eighths = h->vote_eighths >= 0 ? (uint32_t)h->vote_eighths : rounds ? 8u : costly ? 7u : 6u;
-        a.vote_patience = h->vote_patience >= 0 ? (uint32_t)h->vote_patience : (rounds || costly) ? 16u : 3u;
-    }
+    pl.park_records = park_records;
+    pl.park_bytes = park_bytes;
+    pl.n_rounds = n_rounds;
+    pl.rounds = n_rounds > 0 && h->have_defer && a.many_mesh == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
+                params->rays_per_pixel > 0 && a.lds_scene == 0u;
+}
+
+// The intersection vote (path_begin).  The more a traversal costs beside the rest of an iteration, the longer it pays
+// to let the lanes on memoised primary segments catch up first: 6/8 of the lanes or 3 iterations when the scene is in
+// LDS and walked by the few-mesh kernels (config 2: 1.221 ms per frame; 1.222 with 7/8 and 16, 1.366 with 8/8), 7/8 or
+// 16 iterations otherwise (sponza-sized stand-in 10.69 -> 10.21 ms, 200-mesh stand-in 5.00 -> 4.85), every lane or 16
+// iterations in a deferred-walk sequence, whose resumed pixels arrive in every phase (config 3 stand-in 5.86 -> 5.45,
+// config 5 geometry 3.35 -> 3.22; profiles/r03_experiments/ab_*_vote*.txt).
+static void vote_thresholds(const rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
+    const bool costly = a.lds_scene == 0u || a.many_mesh != 0u;
+    a.vote_eighths = h->vote_eighths >= 0 ? (uint32_t)h->vote_eighths : pl.rounds ? 8u : costly ? 7u : 6u;
+    a.vote_patience = h->vote_patience >= 0 ? (uint32_t)h->vote_patience : (pl.rounds || costly) ? 16u : 3u;
+}
+
+// Pipelined single frames: a plain one-frame launch (no batch, no sequence of launches).
+// S is the stream this frame's sampling launch and its bookkeeping run on.
+static int pipeline_acquire(rt_handle* h, const rt_params* params, const RenderArgs& a, LaunchPlan& pl) {
+    const uint64_t need_texels = pl.need_texels;
     const bool wavefront_wanted = RT_EXPERIMENTS && h->wavefront != 0 && a.many_mesh != 0 && !h->any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0;
-    // Pipelined single frames: a plain one-frame launch (no batch, no sequence of launches).
-    // S is the stream this frame's sampling launch and its bookkeeping run on.
-    const int pipeline_opt = h->pipeline < 0 ? automatic_pipeline_depth(world) : h->pipeline;
+    const int pipeline_opt = h->pipeline < 0 ? automatic_pipeline_depth(pl.shape.world) : h->pipeline;
     if (!h->queues_noted && pipeline_opt != 0 && (hw_queues_requested() < 5 || pipeline_opt + 1 > hw_queues_requested())) {
         // Not an error, said once (rt_last_error after a call that returned RT_OK): the pipeline is limited by, or
         // oversubscribes, the hardware queues the host asked the runtime for.
@@ -2015,95 +2108,113 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
                  "; export GPU_MAX_HW_QUEUES=8 (12 for strip shares of >= 4 ranks) before the HIP runtime initialises (INTEGRATION.md section 3)";
     }
     const uint32_t pipe_depth = pipeline_opt >= 2 ? (uint32_t)pipeline_opt : 2u;
-    bool pipe = pipeline_opt != 0 && n_batch == 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 &&
-                !rounds && !wavefront_wanted;   // (strips too: the gather reads the image behind the blend, on the handle's stream)
+    bool pipe = pipeline_opt != 0 && pl.n_batch == 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 &&
+                !pl.rounds && !wavefront_wanted;   // (strips too: the gather reads the image behind the blend, on the handle's stream)
     if (pipe && h->pipe_scratch_texels < need_texels) {   // (option max_device_mb: the pipeline's scratch images have to fit)
         size_t held = 0;
-        for (int k = 0; k < rt_handle::PIPE_MAX; ++k) if (h->pipe_scratch[k]) held += h->pipe_scratch_texels * sizeof(float4);
+        for (const PipeSlot& ps : h->pipe) if (ps.scratch) held += h->pipe_scratch_texels * sizeof(float4);
         if (!fits_cap(h, (size_t)pipe_depth * need_texels * sizeof(float4), held)) pipe = false;
     } else if (pipe) {
         uint32_t have = 0;
-        for (uint32_t k = 0; k < pipe_depth; ++k) have += h->pipe_scratch[k] ? 1u : 0u;
+        for (uint32_t k = 0; k < pipe_depth; ++k) have += h->pipe[k].scratch ? 1u : 0u;
         if (!fits_cap(h, (size_t)(pipe_depth - have) * h->pipe_scratch_texels * sizeof(float4))) pipe = false;
     }
-    bool took_idle_path = false;  // this frame would have been pipelined, found nothing in flight and takes the plain launch
-    bool wrote_tables = false;    // this launch rewrites a table later launches read (tile order, tile costs, primary table)
     if (pipe && h->pipeline_when_idle == 0) {
         // Every pipelined frame ends with its blend on the handle's stream: an idle stream means no frame is in flight,
         // i.e. this frame has nothing to overlap with (yet).  It takes the plain launch; the frames a host issues while
         // this one runs are pipelined behind it.
         const hipError_t q = hipStreamQuery(h->stream);
         (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure: do not leave it for the launchers' hipGetLastError)
-        if (q == hipSuccess) { pipe = false; took_idle_path = true; }
+        if (q == hipSuccess) { pipe = false; pl.took_idle_path = true; }
         else if (q != hipErrorNotReady) return fail(h, RT_ERR_DEVICE, std::string("hipStreamQuery: ") + hipGetErrorString(q));
     }
-    const uint32_t pslot = h->pipe_seq % pipe_depth;
-    hipStream_t S = h->stream;
-    bool pipe_barrier = false;  // this frame rewrites shared tables (tile order, primary rays): the other stream's frame has to be done
-    if (pipe) {
-        h->pipe_seq = (h->pipe_seq + 1) % 840u;   // (a multiple of every depth)
-        for (int k = 0; k < (int)pipe_depth; ++k) {   // (no more streams than frames in flight: they share the process's hardware queues)
-            if (!h->pipe_stream[k]) HIP_TRY(h, hipStreamCreateWithFlags(&h->pipe_stream[k], hipStreamNonBlocking));
-            if (!h->pipe_sampled[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->pipe_sampled[k], hipEventDisableTiming));
-            if (!h->pipe_blended[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->pipe_blended[k], hipEventDisableTiming));
-            if (!h->pipe_work[k]) {
-                HIP_TRY(h, hipMalloc((void**)&h->pipe_work[k], 64 * sizeof(uint32_t)));
-                HIP_TRY(h, hipMemsetAsync(h->pipe_work[k], 0, 64 * sizeof(uint32_t), h->pipe_stream[k]));
-                h->pipe_work_slot[k] = 0;
-            }
+    pl.pipe = pipe;
+    pl.pslot = h->pipe_seq % pipe_depth;
+    pl.S = h->stream;
+    if (!pipe) return RT_OK;
+    PipeSlot& slot = h->pipe[pl.pslot];
+    h->pipe_seq = (h->pipe_seq + 1) % 840u;   // (a multiple of every depth)
+    for (uint32_t k = 0; k < pipe_depth; ++k)   // (no more streams than frames in flight: they share the process's hardware queues)
+        if (int rc = pipe_slot_create(h, h->pipe[k]); rc != RT_OK) return rc;
+    if (!h->pipe_book) HIP_TRY(h, hipEventCreateWithFlags(&h->pipe_book, hipEventDisableTiming));
+    if (!h->pipe_main) HIP_TRY(h, hipEventCreateWithFlags(&h->pipe_main, hipEventDisableTiming));
+    if (h->pipe_scratch_texels < need_texels) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the blends on this stream wait for every sampling launch)
+        for (PipeSlot& ps : h->pipe) {
+            free_dev(ps.scratch);
+            ps.blended_set = false;
         }
-        if (!h->pipe_book) HIP_TRY(h, hipEventCreateWithFlags(&h->pipe_book, hipEventDisableTiming));
-        if (!h->pipe_main) HIP_TRY(h, hipEventCreateWithFlags(&h->pipe_main, hipEventDisableTiming));
-        if (h->pipe_scratch_texels < need_texels) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the blends on this stream wait for every sampling launch)
-            for (int k = 0; k < rt_handle::PIPE_MAX; ++k) {
-                free_dev(h->pipe_scratch[k]);
-                h->pipe_scratch[k] = nullptr;
-                h->pipe_blended_set[k] = false;
-            }
-            h->pipe_scratch_texels = need_texels;
-        }
-        if (!h->pipe_scratch[pslot]) {
-            HIP_TRY(h, hipMalloc((void**)&h->pipe_scratch[pslot], h->pipe_scratch_texels * sizeof(float4)));
-            h->pipe_layout[pslot][4] = 0u;  // (nothing zeroed yet)
-        }
-        S = h->pipe_stream[pslot];
-        // this frame's scratch image is free once the frame before last has been blended out of it; the tables the last
-        // bookkeeping frame rewrote are complete; whatever the handle's stream did outside the pipeline is complete
-        if (h->pipe_blended_set[pslot]) HIP_TRY(h, hipStreamWaitEvent(S, h->pipe_blended[pslot], 0));
-        {
-            // The blend covers all need_texels, the sampling launch writes the pixels of the frame only: the padding rows of
-            // a ragged last strip (world > 1, height % 8 != 0) must blend as zeros, as in the batch path -- a fresh
-            // allocation, or samples an earlier frame of another shape left there, would otherwise reach the strip
-            // buffer's padding rows (the assembled frame never reads them).
-            const uint32_t key[5] = {params->width, params->height, rank, world, (uint32_t)need_texels};
-            if (memcmp(h->pipe_layout[pslot], key, sizeof(key)) != 0) {
-                HIP_TRY(h, hipMemsetAsync(h->pipe_scratch[pslot], 0, need_texels * sizeof(float4), S));
-                memcpy(h->pipe_layout[pslot], key, sizeof(key));
-            }
-        }
-        if (h->pipe_book_set) HIP_TRY(h, hipStreamWaitEvent(S, h->pipe_book, 0));
-        // (not for a frame that took the plain launch because nothing was in flight and rewrote no table: the host SAW the
-        // stream idle before it, so everything older is complete; this frame's samples go to a scratch image, and its blend
-        // follows that launch in the handle's stream's order anyway -- so the second frame of a burst overlaps the first)
-        if (h->pipe_main_set && h->pipe_main_need) HIP_TRY(h, hipStreamWaitEvent(S, h->pipe_main, 0));
+        h->pipe_scratch_texels = need_texels;
     }
-    auto barrier_other = [&]() -> hipError_t {   // before rewriting a shared table: the other stream's sampling launch is done
-        wrote_tables = true;
-        if (!pipe || pipe_barrier) return hipSuccess;
-        pipe_barrier = true;
-        if (h->pipe_main_set) {   // (... and whatever the handle's stream last launched outside the pipeline)
-            const hipError_t e = hipStreamWaitEvent(S, h->pipe_main, 0);
+    if (!slot.scratch) {
+        HIP_TRY(h, hipMalloc((void**)&slot.scratch, h->pipe_scratch_texels * sizeof(float4)));
+        slot.zeroed = FrameShape{};  // (nothing zeroed yet)
+    }
+    const hipStream_t S = pl.S = slot.stream;
+    // this frame's scratch image is free once the frame before last has been blended out of it; the tables the last
+    // bookkeeping frame rewrote are complete; whatever the handle's stream did outside the pipeline is complete
+    if (slot.blended_set) HIP_TRY(h, hipStreamWaitEvent(S, slot.blended, 0));
+    // The blend covers all need_texels, the sampling launch writes the pixels of the frame only: the padding rows of
+    // a ragged last strip (world > 1, height % 8 != 0) must blend as zeros, as in the batch path -- a fresh
+    // allocation, or samples an earlier frame of another shape left there, would otherwise reach the strip
+    // buffer's padding rows (the assembled frame never reads them).
+    if (slot.zeroed != pl.shape) {
+        HIP_TRY(h, hipMemsetAsync(slot.scratch, 0, need_texels * sizeof(float4), S));
+        slot.zeroed = pl.shape;
+    }
+    if (h->pipe_book_set) HIP_TRY(h, hipStreamWaitEvent(S, h->pipe_book, 0));
+    // (not for a frame that took the plain launch because nothing was in flight and rewrote no table: the host SAW the
+    // stream idle before it, so everything older is complete; this frame's samples go to a scratch image, and its blend
+    // follows that launch in the handle's stream's order anyway -- so the second frame of a burst overlaps the first)
+    if (h->pipe_main_set && h->pipe_main_need) HIP_TRY(h, hipStreamWaitEvent(S, h->pipe_main, 0));
+    return RT_OK;
+}
+
+// before rewriting a shared table: the other stream's sampling launch is done
+static hipError_t barrier_other(rt_handle* h, LaunchPlan& pl) {
+    pl.wrote_tables = true;
+    if (!pl.pipe || pl.pipe_barrier) return hipSuccess;
+    pl.pipe_barrier = true;
+    if (h->pipe_main_set) {   // (... and whatever the handle's stream last launched outside the pipeline)
+        const hipError_t e = hipStreamWaitEvent(pl.S, h->pipe_main, 0);
+        if (e != hipSuccess) return e;
+    }
+    for (uint32_t k = 0; k < (uint32_t)rt_handle::PIPE_MAX; ++k)
+        if (k != pl.pslot && h->pipe[k].sampled_set) {
+            const hipError_t e = hipStreamWaitEvent(pl.S, h->pipe[k].sampled, 0);
             if (e != hipSuccess) return e;
         }
-        for (uint32_t k = 0; k < (uint32_t)rt_handle::PIPE_MAX; ++k)
-            if (k != pslot && h->pipe_sampled_set[k]) {
-                const hipError_t e = hipStreamWaitEvent(S, h->pipe_sampled[k], 0);
-                if (e != hipSuccess) return e;
-            }
-        return hipSuccess;
-    };
-    // Primary-ray table for the memo: recomputed when the camera or the frame size changed
+    return hipSuccess;
+}
+
+// does the table serve (camera, shape, with / without hits) as it stands?
+static bool primary_table_serves(const PrimaryTable& t, size_t texels, const rt_camera_uniform& camera, const FrameShape& shape,
+                                 bool want_hits) {
+    return t.table && t.texels >= texels && t.valid && t.shape == shape && (!want_hits || t.with_hits) &&
+           memcmp(&t.camera, &camera, sizeof(rt_camera_uniform)) == 0;
+}
+
+// Makes the table serve (the handle's camera, shape, with / without hits) on `stream`: grown if it is too small,
+// recomputed, marked.  The caller's business, because it is what differs between the shared table and a slot's own: whoever
+// may still read a table that has to grow has been synchronised, and barrier_other() before a table that other streams'
+// frames read is rewritten.
+static int primary_table_make(rt_handle* h, RenderArgs& a, PrimaryTable& t, size_t texels, const FrameShape& shape, bool want_hits,
+                              hipStream_t stream) {
+    if (t.texels < texels) {
+        t.valid = false;
+        if (int rc = replace_dev(h, &t.table, t.texels, texels, 64); rc != RT_OK) return rc;
+    }
+    a.primary = nullptr;
+    HIP_TRY(h, launch_primary(a, t.table, want_hits, stream));
+    t.valid = true;
+    t.shape = shape;
+    t.with_hits = want_hits;
+    t.camera = h->camera;
+    return RT_OK;
+}
+
+// Primary-ray table for the memo: recomputed when the camera or the frame size changed
+static int bind_primary_table(rt_handle* h, const rt_params* params, RenderArgs& a, LaunchPlan& pl) {
     a.primary = nullptr;
     a.primary_complete = 0u;
     const bool camera_moved = h->last_frame_camera_valid && memcmp(&h->last_frame_camera, &h->camera, sizeof(rt_camera_uniform)) != 0;
@@ -2112,70 +2223,34 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
         h->last_frame_camera_valid = true;
     }
     // (a batch keeps the table whatever the camera did: its frames share it)
-    const size_t table_texels = (size_t)((params->width + 7) / 8) * ((params->height + 7) / 8) * 64;  // whole 8x8 tiles
+    const size_t texels = (size_t)((params->width + 7) / 8) * ((params->height + 7) / 8) * 64;  // whole 8x8 tiles
     // (option max_device_mb: a table that would have to be allocated beyond the cap is done without -- every pixel then
     // computes its own memo; a slot table likewise falls back to the shared one)
-    const bool table_fits = h->primary_texels >= table_texels || fits_cap(h, table_texels * 64u, h->primary_texels * 64u);
-    if (h->use_primary && table_fits && a.pixel_cache != 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 && !(camera_moved && n_batch == 0)) {
-        const size_t texels = table_texels;
-        // (the counter kernels re-intersect every segment, so a launch with counters neither needs nor fills the hits)
-        const bool want_hits = h->primary_hits != 0 && a.count_tests == 0u;
-        const bool shared_fits = h->primary && h->primary_texels >= texels && h->primary_valid && h->primary_w == params->width &&
-                                 h->primary_h == params->height && h->primary_rank == rank && h->primary_world == world &&
-                                 (!want_hits || h->primary_with_hits) &&
-                                 memcmp(&h->primary_camera, &h->camera, sizeof(rt_camera_uniform)) == 0;
-        if (pipe && !shared_fits && h->primary_per_slot != 0 && pslot < (uint32_t)rt_handle::PIPE_MAX &&
-            (h->slot_primary[pslot].texels >= texels || fits_cap(h, texels * 64u, h->slot_primary[pslot].texels * 64u))) {
-            rt_handle::SlotTable& st = h->slot_primary[pslot];
-            if (st.texels < texels) {
-                HIP_TRY(h, hipStreamSynchronize(S));   // (the slot's previous frame read the old one)
-                free_dev(st.table);
-                st.texels = 0;
-                st.valid = false;
-                HIP_TRY(h, hipMalloc((void**)&st.table, texels * 64));
-                st.texels = texels;
-            }
-            if (!st.valid || st.w != params->width || st.h != params->height || st.rank != rank || st.world != world ||
-                (want_hits && !st.with_hits) || memcmp(&st.camera, &h->camera, sizeof(rt_camera_uniform)) != 0) {
-                a.primary = nullptr;
-                HIP_TRY(h, launch_primary(a, st.table, want_hits, S));
-                st.valid = true;
-                st.w = params->width; st.h = params->height; st.rank = rank; st.world = world;
-                st.with_hits = want_hits;
-                st.camera = h->camera;
-            }
-            a.primary = st.table;
-            a.primary_complete = st.with_hits ? 1u : 0u;
+    const bool table_fits = h->primary.texels >= texels || fits_cap(h, texels * 64u, h->primary.texels * 64u);
+    if (!(h->use_primary && table_fits && a.pixel_cache != 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 && !(camera_moved && pl.n_batch == 0)))
+        return RT_OK;
+    // (the counter kernels re-intersect every segment, so a launch with counters neither needs nor fills the hits)
+    const bool want_hits = h->primary_hits != 0 && a.count_tests == 0u;
+    PrimaryTable& own = h->pipe[pl.pslot].primary;
+    const bool use_own = pl.pipe && !primary_table_serves(h->primary, texels, h->camera, pl.shape, want_hits) && h->primary_per_slot != 0 &&
+                         (own.texels >= texels || fits_cap(h, texels * 64u, own.texels * 64u));
+    PrimaryTable& t = use_own ? own : h->primary;
+    if (!primary_table_serves(t, texels, h->camera, pl.shape, want_hits)) {
+        if (use_own) {
+            if (t.texels < texels) HIP_TRY(h, hipStreamSynchronize(pl.S));   // (the slot's previous frame read the old one)
         } else {
-        if (h->primary_texels < texels) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            for (int k = 0; k < rt_handle::PIPE_MAX; ++k)   // (pipelined frames read the table on their own streams)
-                if (h->pipe_stream[k]) HIP_TRY(h, hipStreamSynchronize(h->pipe_stream[k]));
-            free_dev(h->primary);
-            HIP_TRY(h, hipMalloc((void**)&h->primary, texels * 64));
-            h->primary_texels = texels;
-            h->primary_valid = false;
+            if (t.texels < texels)   // (pipelined frames read the table on their own streams)
+                if (int rc = drain_streams(h); rc != RT_OK) return rc;
+            HIP_TRY(h, barrier_other(h, pl));
         }
-        // (the counter kernels re-intersect every segment, so a launch with counters neither needs nor fills the hits)
-        const bool with_hits = h->primary_hits != 0 && a.count_tests == 0u;
-        if (!h->primary_valid || h->primary_w != params->width || h->primary_h != params->height ||
-            h->primary_rank != rank || h->primary_world != world || (with_hits && !h->primary_with_hits) ||
-            memcmp(&h->primary_camera, &h->camera, sizeof(rt_camera_uniform)) != 0) {
-            HIP_TRY(h, barrier_other());
-            a.primary = nullptr;
-            HIP_TRY(h, launch_primary(a, h->primary, with_hits, S));
-            h->primary_valid = true;
-            h->primary_w = params->width;
-            h->primary_h = params->height;
-            h->primary_rank = rank;
-            h->primary_world = world;
-            h->primary_with_hits = with_hits;
-            h->primary_camera = h->camera;
-        }
-        a.primary = h->primary;
-        a.primary_complete = h->primary_with_hits ? 1u : 0u;
-        }
+        if (int rc = primary_table_make(h, a, t, texels, pl.shape, want_hits, pl.S); rc != RT_OK) return rc;
     }
+    a.primary = t.table;
+    a.primary_complete = t.with_hits ? 1u : 0u;
+    return RT_OK;
+}
+
+static int bind_memo(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
     // With a complete table a lane's memo EQUALS its table entry for the pixel's whole life: the kernels whose memo has no
     // room in LDS read the entry in place (pixel_cache = 4) instead of copying it into a buffer in global memory --
     // that copy was most of what the global-memory kernels wrote and half of what they read.
@@ -2186,89 +2261,73 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
     // The global-memory memo is per resident wave and stateful across a pixel's samples: one per concurrent launch.
     // Slot 0 has its own too -- a plain launch on the handle's stream (pixel_cache_mem) may still be running beside
     // the pipelined frame of slot 0 when pipe_main_need is false (a frame that found the stream idle).
-    if (pipe && a.pixel_cache == 2u) {
+    if (pl.pipe && a.pixel_cache == 2u) {
+        PipeSlot& slot = h->pipe[pl.pslot];
         const size_t need = (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
-        if (h->pipe_memo_words[pslot] < need) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            free_dev(h->pipe_memo[pslot]);
-            HIP_TRY(h, hipMalloc((void**)&h->pipe_memo[pslot], need * sizeof(uint32_t)));
-            h->pipe_memo_words[pslot] = need;
-        }
-        a.pixel_cache_mem = h->pipe_memo[pslot];
+        if (int rc = regrow(h, slot.memo, slot.memo_words, need, h->stream); rc != RT_OK) return rc;
+        a.pixel_cache_mem = slot.memo;
     }
-    // a fresh tile counter per launch: a ring of 64, zeroed in one go each time it wraps (launches on
-    // one stream are ordered, so every earlier user of the ring is done by then)
-    if (pipe) {   // (a ring per pipe stream: its memset only touches launches of its own, in-order stream)
-        h->pipe_work_slot[pslot] = (h->pipe_work_slot[pslot] + 1) & 63u;
-        if (h->pipe_work_slot[pslot] == 0u) HIP_TRY(h, hipMemsetAsync(h->pipe_work[pslot], 0, 64 * sizeof(uint32_t), S));
-        a.work_counter = h->pipe_work[pslot] + h->pipe_work_slot[pslot];
-    } else {
-        h->work_slot = (h->work_slot + 1) & 63u;
-        if (h->work_slot == 0u) HIP_TRY(h, hipMemsetAsync(h->work_counters, 0, 64 * sizeof(uint32_t), h->stream));
-        a.work_counter = h->work_counters + h->work_slot;
-    }
-    // Tile-cost feedback (persistent kernel, path-trace frames only): the tiles are handed out in the
-    // order of the rays each took in an earlier frame of the same shape, heaviest first.  Progressive
-    // accumulation re-renders the same view, so an order stays good: it is refreshed every
-    // `tile_feedback_period` frames (costs are recorded in the frame before a refresh), not every frame.
-    const uint32_t n_tiles = a.tiles_x * a.tiles_y;
-    a.tile_order = nullptr;
-    a.tile_cost = nullptr;
-    // Wavefront sequence (option "wavefront", experiments build only: experiments/rt_api_wavefront.inl)
-    WavefrontPlan wf{};
-    if (int rc = wavefront_prepare(h, params, a, n_tiles, n_batch, wf, rounds); rc != RT_OK) return rc;
-    const bool wavefront = wf.on;
-    if (rounds && h->park_capacity < park_records) {
-        // the two park queues (an automatic sequence that cannot have them falls back to the plain launch)
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RT_OK;
+}
+
+// the two park queues (an automatic sequence that cannot have them falls back to the plain launch)
+static int prepare_park_queues(rt_handle* h, LaunchPlan& pl) {
+    if (!pl.rounds || h->park_capacity >= pl.park_records) return RT_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    free_dev(h->park_queue[0]);
+    free_dev(h->park_queue[1]);
+    h->park_capacity = 0;
+    const hipError_t e0 = hipMalloc((void**)&h->park_queue[0], pl.park_bytes);
+    const hipError_t e1 = e0 == hipSuccess ? hipMalloc((void**)&h->park_queue[1], pl.park_bytes) : e0;
+    if (e1 != hipSuccess) {
+        (void)hipGetLastError();
         free_dev(h->park_queue[0]);
         free_dev(h->park_queue[1]);
-        h->park_capacity = 0;
-        const hipError_t e0 = hipMalloc((void**)&h->park_queue[0], park_bytes);
-        const hipError_t e1 = e0 == hipSuccess ? hipMalloc((void**)&h->park_queue[1], park_bytes) : e0;
-        if (e1 != hipSuccess) {
-            (void)hipGetLastError();
-            free_dev(h->park_queue[0]);
-            free_dev(h->park_queue[1]);
-            if (h->sort_rounds > 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "sort_rounds: no device memory for the park queues");
-            rounds = false;
-        } else {
-            h->park_capacity = park_records;
-        }
+        if (h->sort_rounds > 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "sort_rounds: no device memory for the park queues");
+        pl.rounds = false;
+    } else {
+        h->park_capacity = pl.park_records;
     }
-    if (h->tile_feedback && params->debug_flag == 0 && n_tiles <= h->tile_capacity && n_tiles > 0 && a.kernel_variant == 0) {
-        const bool same_shape = h->history_valid && h->hist_w == params->width && h->hist_h == params->height &&
-                                h->hist_rank == rank && h->hist_world == world;
-        if (!same_shape) {
-            h->have_order = false;
-            h->costs_ready = false;
-        }
-        if (h->costs_ready && (!h->have_order || h->order_age >= (uint32_t)h->tile_feedback_period)) {
-            const long long per_tile = 64ll * (params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) *
-                                       (params->number_of_bounces >= 0 ? params->number_of_bounces + 1 : 0);
-            const uint32_t max_cost = per_tile > 0xffffffffll ? 0xffffffffu : (uint32_t)per_tile;
-            HIP_TRY(h, barrier_other());
-            HIP_TRY(h, launch_tile_order(h->tile_cost[h->cost_slot], n_tiles, max_cost, h->tile_order, S));
-            h->have_order = true;
-            h->order_age = 0;
-            h->costs_ready = false;
-        }
-        const uint32_t frames_now = n_batch ? n_batch : 1u;
-        if (h->have_order) a.tile_order = h->tile_order;
-        if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->tile_feedback_period) {
-            h->cost_slot ^= 1;
-            a.tile_cost = h->tile_cost[h->cost_slot];
-            wrote_tables = true;
-            HIP_TRY(h, hipMemsetAsync(a.tile_cost, 0, (size_t)n_tiles * sizeof(uint32_t), S));
-            h->costs_ready = true;
-        }
-        h->order_age += frames_now;
-        h->history_valid = true;
-        h->hist_w = params->width;
-        h->hist_h = params->height;
-        h->hist_rank = rank;
-        h->hist_world = world;
+    return RT_OK;
+}
+
+// Tile-cost feedback (persistent kernel, path-trace frames only): the tiles are handed out in the
+// order of the rays each took in an earlier frame of the same shape, heaviest first.  Progressive
+// accumulation re-renders the same view, so an order stays good: it is refreshed every
+// `tile_feedback_period` frames (costs are recorded in the frame before a refresh), not every frame.
+static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, LaunchPlan& pl) {
+    const uint32_t n_tiles = pl.n_tiles;
+    if (!(h->tile_feedback && params->debug_flag == 0 && n_tiles <= h->tile_capacity && n_tiles > 0 && a.kernel_variant == 0)) return RT_OK;
+    if (h->history != pl.shape) {
+        h->have_order = false;
+        h->costs_ready = false;
     }
+    if (h->costs_ready && (!h->have_order || h->order_age >= (uint32_t)h->tile_feedback_period)) {
+        const long long per_tile = 64ll * (params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) *
+                                   (params->number_of_bounces >= 0 ? params->number_of_bounces + 1 : 0);
+        const uint32_t max_cost = per_tile > 0xffffffffll ? 0xffffffffu : (uint32_t)per_tile;
+        HIP_TRY(h, barrier_other(h, pl));
+        HIP_TRY(h, launch_tile_order(h->tile_cost[h->cost_slot], n_tiles, max_cost, h->tile_order, pl.S));
+        h->have_order = true;
+        h->order_age = 0;
+        h->costs_ready = false;
+    }
+    const uint32_t frames_now = pl.n_batch ? pl.n_batch : 1u;
+    if (h->have_order) a.tile_order = h->tile_order;
+    if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->tile_feedback_period) {
+        h->cost_slot ^= 1;
+        a.tile_cost = h->tile_cost[h->cost_slot];
+        pl.wrote_tables = true;
+        HIP_TRY(h, hipMemsetAsync(a.tile_cost, 0, (size_t)n_tiles * sizeof(uint32_t), pl.S));
+        h->costs_ready = true;
+    }
+    h->order_age += frames_now;
+    h->history = pl.shape;
+    return RT_OK;
+}
+
+// the launch's pair of timing events, out of the pool
+static int timing_events(rt_handle* h, LaunchPlan& pl) {
     if (h->ev_used == h->ev_pool.size()) {
         if (h->ev_pool.size() >= 4096) {
             // the pool is full: add the recorded times to the running total, then reuse the events
@@ -2281,157 +2340,135 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
             h->ev_pool.emplace_back(s0, s1);
         }
     }
-    {
-        const uint32_t tile_blocks = (n_tiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        h->last_launch[0] = (uint32_t)render_lds_bytes(a);
-        h->last_launch[1] = a.kernel_variant == 1 || params->debug_flag != 0 ? tile_blocks : std::min(a.persistent_blocks, tile_blocks);
-        h->last_launch[2] = a.lds_scene;
-        h->last_launch[3] = (a.many_mesh ? 1u : 0u) | ((a.simple && !a.many_mesh && !a.count_tests) ? 2u : 0u) |
-                            (a.kernel_variant == 1 ? 4u : 0u) | (rounds ? 8u : 0u);
-    }
-    auto& ev = h->ev_pool[h->ev_used++];
-    if (pipe && pipe_barrier) {   // the tables this frame rewrote: later frames of the other stream wait for them
-        HIP_TRY(h, hipEventRecord(h->pipe_book, S));
-        h->pipe_book_set = true;
-    }
-    HIP_TRY(h, hipEventRecord(ev.first, S));
-    if (wavefront) {
-        if (int rc = wavefront_run(h, a, wf); rc != RT_OK) return rc;
-    } else if (pipe) {
-        // sample into this slot's scratch image on its stream; blend in frame order on the handle's stream
-        a.image = h->pipe_scratch[pslot];
-        a.batch_frames = 1;
-        a.batch_stride = need_texels;
-        a.batch_tile_major = 0;
-        HIP_TRY(h, launch_render(a, S));
-        HIP_TRY(h, hipEventRecord(h->pipe_sampled[pslot], S));
-        h->pipe_sampled_set[pslot] = true;
-        HIP_TRY(h, hipEventRecord(ev.second, S));
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->pipe_sampled[pslot], 0));
-        BlendArgs b{};
-        b.image = h->image;
-        b.scratch = h->pipe_scratch[pslot];
-        b.texels = need_texels;
-        b.stride = need_texels;
-        b.n = 1;
-        b.frames0 = params->frames;
-        b.weight[0] = a.blend_weight;   // (wgsl:157-158 with the host's two operations, as in a one-frame launch)
-        b.rest[0] = a.blend_rest;
-        HIP_TRY(h, launch_blend_frames(b, h->stream));
-        HIP_TRY(h, hipEventRecord(h->pipe_blended[pslot], h->stream));
-        h->pipe_blended_set[pslot] = true;
-    } else if (!rounds) {
-        HIP_TRY(h, launch_render(a, h->stream));
-    } else {
-        // launch 0 takes the tiles and parks every pixel in front of its first entry into the big mesh; then, round
-        // after round, rt_walk_kernel walks the mesh for the parked rays and a render launch resumes those pixels
-        // (parking them again at their next entry); the last render launch does not park: it walks what is left
-        // inline.  Everything is ordered on the stream; a launch whose queue is empty ends at once.
-        if (!h->park_counts) HIP_TRY(h, hipMalloc((void**)&h->park_counts, 72 * sizeof(uint32_t)));
-        HIP_TRY(h, hipMemsetAsync(h->park_counts, 0, 72 * sizeof(uint32_t), h->stream));
-        a.defer_mesh = h->defer_mesh;
-        a.defer_xform = h->defer_xform;
+    pl.ev = &h->ev_pool[h->ev_used++];
+    return RT_OK;
+}
+
+// what rt_last_launch reports
+static void note_launch(rt_handle* h, const rt_params* params, const RenderArgs& a, const LaunchPlan& pl) {
+    const uint32_t tile_blocks = (pl.n_tiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    h->last_launch[0] = (uint32_t)render_lds_bytes(a);
+    h->last_launch[1] = a.kernel_variant == 1 || params->debug_flag != 0 ? tile_blocks : std::min(a.persistent_blocks, tile_blocks);
+    h->last_launch[2] = a.lds_scene;
+    h->last_launch[3] = (a.many_mesh ? 1u : 0u) | ((a.simple && !a.many_mesh && !a.count_tests) ? 2u : 0u) |
+                        (a.kernel_variant == 1 ? 4u : 0u) | (pl.rounds ? 8u : 0u);
+}
+
+// Blend n frames of `texels` texels each out of `scratch` into the image, in frame order on the handle's stream:
+// wgsl:157-158 per frame, each with the weights of its own frame number (the host's two operations, as in a one-frame launch)
+static int blend_frames(rt_handle* h, const float4* scratch, uint64_t texels, uint32_t n, int32_t frames0) {
+    BlendArgs b{};
+    b.image = h->image;
+    b.scratch = scratch;
+    b.texels = texels;
+    b.stride = texels;
+    b.n = n;
+    b.frames0 = frames0;
+    for (uint32_t k = 0; k < n; ++k) blend_weights((int32_t)((uint32_t)frames0 + k), b.weight[k], b.rest[k]);
+    HIP_TRY(h, launch_blend_frames(b, h->stream));
+    return RT_OK;
+}
+
+// sample into this slot's scratch image on its stream; blend in frame order on the handle's stream
+static int launch_pipelined(rt_handle* h, const rt_params* params, RenderArgs& a, const LaunchPlan& pl) {
+    PipeSlot& slot = h->pipe[pl.pslot];
+    a.image = slot.scratch;
+    a.batch_frames = 1;
+    a.batch_stride = pl.need_texels;
+    a.batch_tile_major = 0;
+    HIP_TRY(h, launch_render(a, pl.S));
+    HIP_TRY(h, hipEventRecord(slot.sampled, pl.S));
+    slot.sampled_set = true;
+    HIP_TRY(h, hipEventRecord(pl.ev->second, pl.S));
+    HIP_TRY(h, hipStreamWaitEvent(h->stream, slot.sampled, 0));
+    if (int rc = blend_frames(h, slot.scratch, pl.need_texels, 1, params->frames); rc != RT_OK) return rc;
+    HIP_TRY(h, hipEventRecord(slot.blended, h->stream));
+    slot.blended_set = true;
+    return RT_OK;
+}
+
+// launch 0 takes the tiles and parks every pixel in front of its first entry into the big mesh; then, round
+// after round, rt_walk_kernel walks the mesh for the parked rays and a render launch resumes those pixels
+// (parking them again at their next entry); the last render launch does not park: it walks what is left
+// inline.  Everything is ordered on the stream; a launch whose queue is empty ends at once.
+static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
+    if (!h->park_counts) HIP_TRY(h, hipMalloc((void**)&h->park_counts, 72 * sizeof(uint32_t)));
+    HIP_TRY(h, hipMemsetAsync(h->park_counts, 0, 72 * sizeof(uint32_t), h->stream));
+    a.defer_mesh = h->defer_mesh;
+    a.defer_xform = h->defer_xform;
 #if RT_WALK2
-        a.walk2 = h->walk2;
-        a.walk2_base = h->walk2_base;
+    a.walk2 = h->walk2;
+    a.walk2_base = h->walk2_base;
 #endif
-        auto fresh_counter = [&]() -> hipError_t {
-            h->work_slot = (h->work_slot + 1) & 63u;
-            if (h->work_slot == 0u) {
-                hipError_t e = hipMemsetAsync(h->work_counters, 0, 64 * sizeof(uint32_t), h->stream);
-                if (e != hipSuccess) return e;
-            }
-            a.work_counter = h->work_counters + h->work_slot;
-            return hipSuccess;
-        };
-        const uint32_t R = n_rounds;
-        a.park = 1;
-        a.park_levels = (uint32_t)h->park_levels;
-        a.q_in = nullptr;
-        a.q_in_count = nullptr;
-        a.q_out = h->park_queue[0];
-        a.q_out_count = h->park_counts;
-        // Hybrid launches: the render launches that PARK never walk the big mesh, so they run the LDS-scene kernels on
-        // the small blob (everything but the big mesh's BVH and triangles) with the small meshes' stack depth; a winner on
-        // the big mesh reads its shading record from the full blob.  The last launch (park = 0) and rt_walk_kernel
-        // read the full blob as before.
-        RenderArgs ah = a;
-        bool hybrid = RT_EXPERIMENTS && h->hybrid != 0 && h->small_ok && !a.lds_scene && a.count_tests == 0 && a.kernel_variant == 0;
-        if (hybrid) {
-            ah.blob = h->small_blob;
-            ah.lay = h->small_lay;
-            ah.lds_scene = 1;
-            ah.hybrid = 1;
-            ah.big_blob = h->blob;
-            ah.big_shade_off = h->lay.shade_off;
-            ah.top_count = 0;
-            ah.stack_entries = h->small_stack_entries ? h->small_stack_entries : 1u;
-            ah.stack_wide = 0;
-            ah.pixel_cache = h->pixel_cache_opt ? 1u : 0u;
-            if (ah.pixel_cache && render_lds_bytes(ah) > LDS_BUDGET_BYTES) {
-                // (the global-memory memo buffer; the plain launches may read theirs in place from the table -- pixel_cache 4 --,
-                // which the LDS-scene kernels of the hybrid launches have not compiled in: a parked pixel's memo is rebuilt from
-                // the table on resume either way, RenderArgs::primary_complete)
-                ah.pixel_cache = (a.pixel_cache == 2u || a.pixel_cache == 4u) && h->pixel_cache_mem ? 2u : 0u;
-                ah.pixel_cache_mem = h->pixel_cache_mem;
-            }
-            if (!ah.pixel_cache) ah.primary = nullptr;
-            ah.fast_miss = h->fast_miss != 0 && ah.pixel_cache != 0u ? 1u : 0u;
-            if (render_lds_bytes(ah) > LDS_BUDGET_BYTES) hybrid = false;
-            ah.persistent_blocks = h->persistent_blocks;
-            ah.park_levels = 0;  // (the small blob has no record of the big mesh's BVH)
+    const uint32_t R = pl.n_rounds;
+    a.park = 1;
+    a.park_levels = (uint32_t)h->park_levels;
+    a.q_in = nullptr;
+    a.q_in_count = nullptr;
+    a.q_out = h->park_queue[0];
+    a.q_out_count = h->park_counts;
+    // Hybrid launches: the render launches that PARK never walk the big mesh, so they run the LDS-scene kernels on
+    // the small blob (everything but the big mesh's BVH and triangles) with the small meshes' stack depth; a winner on
+    // the big mesh reads its shading record from the full blob.  The last launch (park = 0) and rt_walk_kernel
+    // read the full blob as before.
+    RenderArgs ah = a;
+    bool hybrid = RT_EXPERIMENTS && h->hybrid != 0 && h->small_ok && !a.lds_scene && a.count_tests == 0 && a.kernel_variant == 0;
+    if (hybrid) {
+        ah.blob = h->small_blob;
+        ah.lay = h->small_lay;
+        ah.lds_scene = 1;
+        ah.hybrid = 1;
+        ah.big_blob = h->blob;
+        ah.big_shade_off = h->lay.shade_off;
+        ah.top_count = 0;
+        ah.stack_entries = h->small_stack_entries ? h->small_stack_entries : 1u;
+        ah.stack_wide = 0;
+        ah.pixel_cache = h->pixel_cache_opt ? 1u : 0u;
+        if (ah.pixel_cache && render_lds_bytes(ah) > LDS_BUDGET_BYTES) {
+            // (the global-memory memo buffer; the plain launches may read theirs in place from the table -- pixel_cache 4 --,
+            // which the LDS-scene kernels of the hybrid launches have not compiled in: a parked pixel's memo is rebuilt from
+            // the table on resume either way, RenderArgs::primary_complete)
+            ah.pixel_cache = (a.pixel_cache == 2u || a.pixel_cache == 4u) && h->pixel_cache_mem ? 2u : 0u;
+            ah.pixel_cache_mem = h->pixel_cache_mem;
         }
-        if (!hybrid) ah = a;
-        auto sync_queues = [&]() {  // (the queue fields move with the rounds: keep the hybrid copy's in step)
-            ah.park = a.park; ah.q_in = a.q_in; ah.q_in_count = a.q_in_count; ah.q_out = a.q_out; ah.q_out_count = a.q_out_count;
-            ah.work_counter = a.work_counter; ah.defer_mesh = a.defer_mesh; ah.defer_xform = a.defer_xform;
-        };
+        if (!ah.pixel_cache) ah.primary = nullptr;
+        ah.fast_miss = h->fast_miss != 0 && ah.pixel_cache != 0u ? 1u : 0u;
+        if (render_lds_bytes(ah) > LDS_BUDGET_BYTES) hybrid = false;
+        ah.persistent_blocks = h->persistent_blocks;
+        ah.park_levels = 0;  // (the small blob has no record of the big mesh's BVH)
+    }
+    if (!hybrid) ah = a;
+    auto sync_queues = [&]() {  // (the queue fields move with the rounds: keep the hybrid copy's in step)
+        ah.park = a.park; ah.q_in = a.q_in; ah.q_in_count = a.q_in_count; ah.q_out = a.q_out; ah.q_out_count = a.q_out_count;
+        ah.work_counter = a.work_counter; ah.defer_mesh = a.defer_mesh; ah.defer_xform = a.defer_xform;
+    };
+    sync_queues();
+    HIP_TRY(h, launch_render(ah, h->stream));
+    for (uint32_t r = 0; r < R; ++r) {
+        const bool last = r + 1 == R;
+        a.q_in = h->park_queue[r & 1u];
+        a.q_in_count = h->park_counts + r;
+        HIP_TRY(h, h->work.next(h->stream, a.work_counter));
+        {
+            RenderArgs w = a;
+            w.top_count = 0;  // (nothing is staged into the walk kernel's LDS)
+            HIP_TRY(h, launch_walk(w, h->compute_units, h->stream));
+        }
+        HIP_TRY(h, h->work.next(h->stream, a.work_counter));
+        a.park = last ? 0u : 1u;
+        a.q_out = last ? nullptr : h->park_queue[(r + 1) & 1u];
+        a.q_out_count = last ? nullptr : h->park_counts + r + 1;
         sync_queues();
-        HIP_TRY(h, launch_render(ah, h->stream));
-        for (uint32_t r = 0; r < R; ++r) {
-            const bool last = r + 1 == R;
-            a.q_in = h->park_queue[r & 1u];
-            a.q_in_count = h->park_counts + r;
-            HIP_TRY(h, fresh_counter());
-            {
-                RenderArgs w = a;
-                w.top_count = 0;  // (nothing is staged into the walk kernel's LDS)
-                HIP_TRY(h, launch_walk(w, h->compute_units, h->stream));
-            }
-            HIP_TRY(h, fresh_counter());
-            a.park = last ? 0u : 1u;
-            a.q_out = last ? nullptr : h->park_queue[(r + 1) & 1u];
-            a.q_out_count = last ? nullptr : h->park_counts + r + 1;
-            sync_queues();
-            HIP_TRY(h, launch_render(last ? a : ah, h->stream));
-        }
+        HIP_TRY(h, launch_render(last ? a : ah, h->stream));
     }
-    if (n_batch && !blend_later) {
-        BlendArgs b{};
-        b.image = h->image;
-        b.scratch = h->batch_scratch;
-        b.texels = need_texels;
-        b.stride = need_texels;
-        b.n = n_batch;
-        b.frames0 = params->frames;
-        for (uint32_t k = 0; k < n_batch; ++k) {  // wgsl:157-158 per frame: the same two IEEE operations
-            volatile float w = 1.0f / (float)(int32_t)((uint32_t)params->frames + k + 1u);
-            volatile float r = 1.0f - w;
-            b.weight[k] = w;
-            b.rest[k] = r;
-        }
-        HIP_TRY(h, launch_blend_frames(b, h->stream));
-    }
-    if (!pipe) {
-        HIP_TRY(h, hipEventRecord(ev.second, h->stream));
-        if (h->pipe_stream[0]) {   // (pipelined frames may follow: their streams wait for this launch)
-            HIP_TRY(h, hipEventRecord(h->pipe_main, h->stream));
-            h->pipe_main_set = true;
-            h->pipe_main_need = !(took_idle_path && !wrote_tables);
-        }
-    }
+    return RT_OK;
+}
+
+// what rt_get_stats reports
+static void account_launch(rt_handle* h, const rt_params* params, const LaunchPlan& pl) {
+    const uint32_t n_batch = pl.n_batch;
     h->launches_total += 1;
-    if (blend_later) {   // (frames rendered ahead: the call's own frame; the others count as asked for when their calls come)
+    if (pl.blend_later) {   // (frames rendered ahead: the call's own frame; the others count as asked for when their calls come)
         h->frames_total += 1u;
         h->frames_speculative += n_batch - 1u;
     } else {
@@ -2440,12 +2477,68 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
     if (params->debug_flag == 0 && params->rays_per_pixel > 0) {
         // pixels this call renders (strips are clipped to the image height)
         unsigned long long rows = 0;
-        for (uint32_t st = rank; st < strips; st += world) {
+        for (uint32_t st = pl.shape.rank; st < (params->height + 7) / 8; st += pl.shape.world) {
             uint32_t y0 = st * 8, y1 = y0 + 8 < params->height ? y0 + 8 : params->height;
             rows += y1 - y0;
         }
         h->paths_total += rows * params->width * (unsigned long long)params->rays_per_pixel * (n_batch ? n_batch : 1u);
     }
+}
+
+// One launch of the hot path: a single frame (n_batch == 0: wgsl `main`, blending in place), or a batch
+// of n_batch >= 2 consecutive frames (Params.frames advancing by one each, app.rs:44-53) sampled in one
+// persistent launch over (frame, tile) work items and blended in frame order by a dense second kernel.
+// The steps run in this order; each is the function of that name above.
+static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uint32_t world, uint32_t n_batch = 0,
+                       bool blend_later = false) {
+    if (!h || !params) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    h->ahead.valid = false;  // (whatever launches here breaks a sequence of frames rendered ahead: render_single)
+    LaunchPlan pl;
+    pl.shape = FrameShape{params->width, params->height, rank, world};
+    pl.n_batch = n_batch;
+    pl.blend_later = blend_later;
+    RenderArgs a{};
+    int rc;
+    if ((rc = validate_and_shape(h, pl)) != RT_OK) return rc;
+    if ((rc = prepare_batch_scratch(h, a, pl)) != RT_OK) return rc;
+    frame_constants(h, params, a);
+    if ((rc = choose_kernel_shape(h, params, a, pl)) != RT_OK) return rc;
+    plan_rounds(h, params, a, pl);
+    vote_thresholds(h, a, pl);
+    if ((rc = pipeline_acquire(h, params, a, pl)) != RT_OK) return rc;
+    if ((rc = bind_primary_table(h, params, a, pl)) != RT_OK) return rc;
+    if ((rc = bind_memo(h, a, pl)) != RT_OK) return rc;
+    // (a ring per pipe stream: its memset only touches launches of its own, in-order stream)
+    HIP_TRY(h, (pl.pipe ? h->pipe[pl.pslot].work : h->work).next(pl.S, a.work_counter));
+    pl.n_tiles = a.tiles_x * a.tiles_y;
+    a.tile_order = nullptr;
+    a.tile_cost = nullptr;
+    // Wavefront sequence (option "wavefront", experiments build only: experiments/rt_api_wavefront.inl)
+    if ((rc = wavefront_prepare(h, params, a, pl.n_tiles, n_batch, pl.wf, pl.rounds)) != RT_OK) return rc;
+    if ((rc = prepare_park_queues(h, pl)) != RT_OK) return rc;
+    if ((rc = tile_feedback(h, params, a, pl)) != RT_OK) return rc;
+    if ((rc = timing_events(h, pl)) != RT_OK) return rc;
+    note_launch(h, params, a, pl);
+    if (pl.pipe && pl.pipe_barrier) {   // the tables this frame rewrote: later frames of the other stream wait for them
+        HIP_TRY(h, hipEventRecord(h->pipe_book, pl.S));
+        h->pipe_book_set = true;
+    }
+    HIP_TRY(h, hipEventRecord(pl.ev->first, pl.S));
+    if (pl.wf.on) rc = wavefront_run(h, a, pl.wf);
+    else if (pl.pipe) rc = launch_pipelined(h, params, a, pl);
+    else if (pl.rounds) rc = launch_rounds(h, a, pl);
+    else HIP_TRY(h, launch_render(a, h->stream));
+    if (rc != RT_OK) return rc;
+    if (n_batch && !blend_later && (rc = blend_frames(h, h->batch_scratch, pl.need_texels, n_batch, params->frames)) != RT_OK) return rc;
+    if (!pl.pipe) {
+        HIP_TRY(h, hipEventRecord(pl.ev->second, h->stream));
+        if (h->pipe[0].stream) {   // (pipelined frames may follow: their streams wait for this launch)
+            HIP_TRY(h, hipEventRecord(h->pipe_main, h->stream));
+            h->pipe_main_set = true;
+            h->pipe_main_need = !(pl.took_idle_path && !pl.wrote_tables);
+        }
+    }
+    account_launch(h, params, pl);
     return RT_OK;
 }
 
@@ -2460,7 +2553,7 @@ static int render_frames_impl(rt_handle* h, const rt_params* params, uint32_t n_
     // batches of equal size (20 frames at 16 per launch: 10 + 10, not 16 + 4)
     uint32_t cap = (uint32_t)h->batch_frames_opt;
     if (h->max_device_bytes != 0 && world != 0 && rank < world) {   // (option max_device_mb: as many scratch frames as fit; 1 = plain launches)
-        const uint64_t texels = world == 1 ? (uint64_t)params->width * params->height : rt_strip_texels(params->width, params->height, rank, world);
+        const uint64_t texels = FrameShape{params->width, params->height, rank, world}.texels();
         const size_t other = optional_bytes(h) - h->batch_scratch_texels * sizeof(float4);
         const size_t room = h->max_device_bytes > other ? h->max_device_bytes - other : 0;
         const uint64_t fit = texels ? room / (texels * sizeof(float4)) : cap;
@@ -2515,21 +2608,8 @@ static uint32_t ahead_depth(const rt_handle* h, const rt_params* params, uint64_
 static int blend_ahead_slot(rt_handle* h, uint32_t slot, int32_t frames) {
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-    BlendArgs b{};
-    b.image = h->image;
-    b.scratch = h->batch_scratch + (size_t)slot * h->ahead.texels;
-    b.texels = h->ahead.texels;
-    b.stride = h->ahead.texels;
-    b.n = 1;
-    b.frames0 = frames;
-    {
-        volatile float w = 1.0f / (float)(int32_t)((uint32_t)frames + 1u);
-        volatile float r = 1.0f - w;
-        b.weight[0] = w;
-        b.rest[0] = r;
-    }
-    HIP_TRY(h, launch_blend_frames(b, h->stream));
-    if (h->pipe_stream[0]) {  // (pipelined frames may follow: their blends are ordered behind this one)
+    if (int rc = blend_frames(h, h->batch_scratch + (size_t)slot * h->ahead.texels, h->ahead.texels, 1, frames); rc != RT_OK) return rc;
+    if (h->pipe[0].stream) {  // (pipelined frames may follow: their blends are ordered behind this one)
         HIP_TRY(h, hipEventRecord(h->pipe_main, h->stream));
         h->pipe_main_set = true;
         h->pipe_main_need = true;
@@ -2569,8 +2649,7 @@ static int render_single(rt_handle* h, const rt_params* params, uint32_t rank, u
                            h->last_single.rank == rank && h->last_single.world == world &&
                            same_frame_params(*params, h->last_single.params, (int32_t)((uint32_t)h->last_single.params.frames + 1u));
     if (continues && h->have_scene && world != 0 && rank < world && params->width != 0 && params->height != 0) {
-        const uint64_t need_texels = world == 1 ? (uint64_t)params->width * params->height
-                                                : rt_strip_texels(params->width, params->height, rank, world);
+        const uint64_t need_texels = FrameShape{params->width, params->height, rank, world}.texels();
         // (a host that WAITS for its frames finds the stream idle; one that runs ahead of the device finds it busy)
         const bool host_waits = h->frame_ahead < 0 && !(hipSetDevice(h->device) == hipSuccess && hipStreamQuery(h->stream) == hipErrorNotReady);
         (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure: not for the launchers' hipGetLastError)
@@ -2585,7 +2664,7 @@ static int render_single(rt_handle* h, const rt_params* params, uint32_t rank, u
                     free_dev(h->batch_scratch);
                     h->batch_scratch = bigger;
                     h->batch_scratch_texels = need_texels * d;
-                    h->scratch_w = 0;  // (new memory: render_impl zeroes it)
+                    h->batch_zeroed = FrameShape{};  // (new memory: render_impl zeroes it)
                 } else {
                     (void)hipGetLastError();
                 }
@@ -2674,18 +2753,8 @@ static int render_multi_impl(rt_handle** per_gpu, int n_gpus, const rt_params* p
                                                    "hold two ranks of one device (multi_rccl = 1 uses device-to-device copies there)");
     // root-side staging, grown on demand
     HIP_TRY(root, hipSetDevice(root->device));
-    if (root->multi_gathered_texels < pad * world) {
-        HIP_TRY(root, hipStreamSynchronize(root->stream));
-        free_dev(root->multi_gathered);
-        HIP_TRY(root, hipMalloc((void**)&root->multi_gathered, pad * world * sizeof(float4)));
-        root->multi_gathered_texels = pad * world;
-    }
-    if (root->multi_frame_texels < frame_texels) {
-        HIP_TRY(root, hipStreamSynchronize(root->stream));
-        free_dev(root->multi_frame);
-        HIP_TRY(root, hipMalloc((void**)&root->multi_frame, frame_texels * sizeof(float4)));
-        root->multi_frame_texels = frame_texels;
-    }
+    if (int rc = regrow(root, root->multi_gathered, root->multi_gathered_texels, pad * world, root->stream); rc != RT_OK) return rc;
+    if (int rc = regrow(root, root->multi_frame, root->multi_frame_texels, frame_texels, root->stream); rc != RT_OK) return rc;
     for (int r = 0; r < n_gpus; ++r) {  // every rank's "the root has copied my strips" event: of the root's device
         rt_handle* h = per_gpu[r];
         if (h->multi_copied && h->multi_copied_device == root->device) continue;
@@ -2751,9 +2820,8 @@ static int render_multi_impl(rt_handle** per_gpu, int n_gpus, const rt_params* p
         }
     }
     // 2. gather: one transfer per rank into the root's [world][pad] buffer
-    auto rank_texels = [&](int r) {
-        // world == 1: the "strips" are the frame itself (no padding of a ragged last strip)
-        return world == 1 ? frame_texels : rt_strip_texels(params->width, params->height, (uint32_t)r, world);
+    auto rank_texels = [&](int r) {  // (world == 1: the "strips" are the frame itself, no padding of a ragged last strip)
+        return FrameShape{params->width, params->height, (uint32_t)r, world}.texels();
     };
     if (use_rccl) {
         std::vector<GatherLeg> legs;
@@ -2834,14 +2902,6 @@ int rt_read_multi_frame(rt_handle* root, float* rgba32f_out, size_t bytes) {
 // the image, the tables, the pipeline slots and the counters are not touched.
 static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 64, "rt_ray / rt_hit layout");
 
-static uint32_t query_blocks(const rt_handle* h, const RenderArgs& a) {
-    const size_t lds = render_lds_bytes(a);
-    uint32_t per_cu = lds ? (uint32_t)((160u * 1024u) / lds) : BLOCKS_PER_CU;
-    if (per_cu > BLOCKS_PER_CU) per_cu = BLOCKS_PER_CU;
-    if (per_cu < 1u) per_cu = 1u;
-    const uint32_t fit = (h->persistent_blocks / BLOCKS_PER_CU) * per_cu;
-    return fit < h->persistent_blocks && fit > 0 ? fit : h->persistent_blocks;
-}
 
 // out_bytes: bytes of output per ray (sizeof(rt_hit) or 4)
 static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, size_t out_bytes, int flags, bool any) {
@@ -2860,7 +2920,7 @@ static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, s
     scene_args(h, a);
     a.params = rt_params{};
     a.camera = h->camera;
-    const uint32_t blocks = query_blocks(h, a);
+    const uint32_t blocks = persistent_blocks_for(h, render_lds_bytes(a));
     if (!host) {
         HIP_TRY(h, launch_query(a, rays, n, out, any, prune, blocks, h->compute_units, h->stream));
         return RT_OK;

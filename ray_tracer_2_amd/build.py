@@ -18,7 +18,7 @@ PRODUCT_SOURCES = [
     "host/png_decode.cpp", "host/scene_capi.cpp", "host/ray_tracer.cpp",
 ]
 PRODUCT_HEADERS = [
-    "rt_transc.h", "rt_texture.h", "rt_srgb_lut.h", "rt_device.h", "rt_rccl.h", "rt_refit.h", "host/glam_math.h",
+    "rt_queries.inl", "rt_test_kernels.inl", "rt_transc.h", "rt_texture.h", "rt_srgb_lut.h", "rt_device.h", "rt_rccl.h", "rt_refit.h", "host/glam_math.h",
     "host/obj_loader.h", "host/bvh.h", "host/scene.h", "host/ray_tracer.hpp",
     "../../include/rt_abi.h", "../../include/rt_test_abi.h", "experiments/rt_wavefront.inl", "experiments/rt_wavefront_launch.inl", "experiments/rt_api_wavefront.inl", "experiments/rt_api_hybrid_blob.inl",
 ]
@@ -137,7 +137,7 @@ def source_hash():
     figures measured on the build it is running."""
     import hashlib
     hh = hashlib.sha1()
-    for f in ("rt_kernel.hip", "rt_api.hip", "rt_device.h", "rt_transc.h", "rt_texture.h"):
+    for f in ("rt_kernel.hip", "rt_queries.inl", "rt_test_kernels.inl", "rt_api.hip", "rt_device.h", "rt_transc.h", "rt_texture.h"):
         hh.update(open(os.path.join(CSRC, f), "rb").read())
     hh.update(open(os.path.abspath(__file__), "rb").read())
     return hh.hexdigest()[:16]

@@ -33,6 +33,7 @@
 
 namespace rtd {
 hipError_t launch_render(const RenderArgs& a, hipStream_t stream);
+bool render_takes_simple(const RenderArgs& a);
 size_t render_lds_bytes(const RenderArgs& a);
 hipError_t launch_tile_order(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t* order,
                              hipStream_t stream);
@@ -2350,7 +2351,7 @@ static void note_launch(rt_handle* h, const rt_params* params, const RenderArgs&
     h->last_launch[0] = (uint32_t)render_lds_bytes(a);
     h->last_launch[1] = a.kernel_variant == 1 || params->debug_flag != 0 ? tile_blocks : std::min(a.persistent_blocks, tile_blocks);
     h->last_launch[2] = a.lds_scene;
-    h->last_launch[3] = (a.many_mesh ? 1u : 0u) | ((a.simple && !a.many_mesh && !a.count_tests) ? 2u : 0u) |
+    h->last_launch[3] = (a.many_mesh ? 1u : 0u) | (render_takes_simple(a) ? 2u : 0u) |
                         (a.kernel_variant == 1 ? 4u : 0u) | (pl.rounds ? 8u : 0u);
 }
 
@@ -2896,12 +2897,31 @@ int rt_read_multi_frame(rt_handle* root, float* rgba32f_out, size_t bytes) {
     return RT_OK;
 }
 
-// ---- ray queries (include/rt_abi.h: rt_intersect_rays, rt_occluded_rays, rt_pick; rt_kernel.hip: rt_query_kernel) ----
+// ---- ray queries (include/rt_abi.h: rt_intersect_rays, rt_occluded_rays, rt_pick; rt_queries.inl: rt_query_kernel) ----
 // A query launch takes the arguments a render of the scene takes (scene_args), no pixel memo, and the render's
 // persistent grid (workgroups that fit the CUs' LDS).  It reads nothing but the scene and writes nothing but its output:
 // the image, the tables, the pipeline slots and the counters are not touched.
 static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 64, "rt_ray / rt_hit layout");
 
+// The arguments of a launch on the scene outside a render (queries, rt_pick, rt_render_gbuffer, the test probe): what a
+// render of the scene takes (scene_args), the handle's camera, and the caller's frame parameters or none.
+static RenderArgs query_args(const rt_handle* h, const rt_params* params) {
+    RenderArgs a{};
+    scene_args(h, a);
+    a.params = params ? *params : rt_params{};
+    a.camera = h->camera;
+    return a;
+}
+
+// Device memory a host-memory call may stage through: at most 64 MB, within what option max_device_mb leaves.
+static size_t staging_room(const rt_handle* h) {
+    size_t room = (size_t)64 << 20;
+    if (h->max_device_bytes != 0) {
+        const size_t held = optional_bytes(h);
+        room = std::min(room, h->max_device_bytes > held ? h->max_device_bytes - held : 0);
+    }
+    return room;
+}
 
 // out_bytes: bytes of output per ray (sizeof(rt_hit) or 4)
 static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, size_t out_bytes, int flags, bool any) {
@@ -2916,10 +2936,7 @@ static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, s
     if (!host && (((uintptr_t)rays & 15u) != 0u || ((uintptr_t)out & (out_bytes == 4 ? 3u : 15u)) != 0u))
         return fail(h, RT_ERR_INVALID_ARGUMENT, "device rays / results not aligned (16 bytes; 4 for occlusion flags)");
     HIP_TRY(h, hipSetDevice(h->device));
-    RenderArgs a{};
-    scene_args(h, a);
-    a.params = rt_params{};
-    a.camera = h->camera;
+    const RenderArgs a = query_args(h, nullptr);
     const uint32_t blocks = persistent_blocks_for(h, render_lds_bytes(a));
     if (!host) {
         HIP_TRY(h, launch_query(a, rays, n, out, any, prune, blocks, h->compute_units, h->stream));
@@ -2927,13 +2944,7 @@ static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, s
     }
     // host memory: chunks of at most 64 MB of device memory (rays and results), within option max_device_mb
     const size_t per_ray = sizeof(rt_ray) + out_bytes;
-    size_t room = (size_t)64 << 20;
-    if (h->max_device_bytes != 0) {
-        const size_t held = optional_bytes(h);
-        const size_t left = h->max_device_bytes > held ? h->max_device_bytes - held : 0;
-        room = std::min(room, left);
-    }
-    const uint64_t chunk = std::min<uint64_t>(n, room / per_ray);
+    const uint64_t chunk = std::min<uint64_t>(n, staging_room(h) / per_ray);
     if (chunk == 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for a query's staging buffers");
     void* d_rays = nullptr;
     void* d_out = nullptr;
@@ -2971,10 +2982,7 @@ int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hi
     if (x >= params->width || y >= params->height) return fail(h, RT_ERR_INVALID_ARGUMENT, "texel outside the frame");
     if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
     HIP_TRY(h, hipSetDevice(h->device));
-    RenderArgs a{};
-    scene_args(h, a);
-    a.params = *params;
-    a.camera = h->camera;
+    const RenderArgs a = query_args(h, params);
     float4* d = nullptr;  // one rt_ray, then one rt_hit
     HIP_TRY(h, hipMalloc((void**)&d, sizeof(rt_ray) + sizeof(rt_hit)));
     hipError_t e = launch_pick_ray(a, x, y, d, h->stream);
@@ -2987,7 +2995,7 @@ int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hi
     return RT_OK;
 }
 
-// ---- first-hit buffers of a frame (include/rt_abi.h: rt_render_gbuffer; rt_kernel.hip: rt_gbuffer_kernel) ----
+// ---- first-hit buffers of a frame (include/rt_abi.h: rt_render_gbuffer; rt_queries.inl: rt_gbuffer_kernel) ----
 // Launched like a query: the arguments a render of the scene takes, nothing read but the scene and nothing written but
 // the caller's planes.
 int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* out, int flags) {
@@ -3014,12 +3022,9 @@ int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* o
             if (ptr[c] && ((uintptr_t)ptr[c] & (align[c] - 1u)) != 0u)
                 return fail(h, RT_ERR_INVALID_ARGUMENT, std::string("device plane ") + names[c] + " is not aligned to " + std::to_string(align[c]) + " bytes");
     HIP_TRY(h, hipSetDevice(h->device));
-    RenderArgs a{};
-    scene_args(h, a);
-    a.params = rt_params{};
+    RenderArgs a = query_args(h, nullptr);
     a.params.width = W;
     a.params.height = H;
-    a.camera = h->camera;
     GBufferArgs g{};
     g.width = W;
     g.height = H;
@@ -3037,13 +3042,7 @@ int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* o
     }
     // host memory: bands of whole rows through one temporary device buffer of at most 64 MB, within option max_device_mb;
     // each plane's part of it starts at a multiple of 256 bytes (11 x 256 bytes of slack at most)
-    const size_t slack = 11u * 256u;
-    size_t room = (size_t)64 << 20;
-    if (h->max_device_bytes != 0) {
-        const size_t held = optional_bytes(h);
-        const size_t left = h->max_device_bytes > held ? h->max_device_bytes - held : 0;
-        room = std::min(room, left);
-    }
+    const size_t slack = 11u * 256u, room = staging_room(h);
     const size_t row_bytes = (size_t)W * per_texel;
     const uint32_t band = room > slack ? (uint32_t)std::min<uint64_t>(H, (room - slack) / row_bytes) : 0u;
     if (band == 0u) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for one row of the G-buffer's staging planes");
@@ -3294,7 +3293,7 @@ int rt_test_scene_blob(rt_handle* h, void* out, uint64_t bytes, uint32_t layout_
 }
 
 // tests/test_gpu_intersect.py: intersect_scene for host-given rays, on the uploaded scene, with the arguments and the
-// instantiation a render launches (scene_args, launch_variant) unless `flags` force one.
+// instantiation a render launches (query_args, render_takes_simple) unless `flags` force one.
 int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint8_t* active, uint64_t n, int flags,
                       uint32_t* out) {
     if (!h || (n && (!ro || !rd || !out))) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
@@ -3310,10 +3309,9 @@ int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint
     for (uint64_t i = 0; i < n; ++i)
         if (rd[3 * i] == 0.0f && rd[3 * i + 1] == 0.0f && rd[3 * i + 2] == 0.0f)
             return fail(h, RT_ERR_INVALID_ARGUMENT, "zero direction");
-    RenderArgs a{};
-    scene_args(h, a);
+    const RenderArgs a = query_args(h, nullptr);
     const bool stats = (flags & RT_TEST_ISECT_STATS) != 0;
-    bool simple = !a.many_mesh && a.simple && !stats;  // launch_variant's choice
+    bool simple = render_takes_simple(a) && !stats;  // (the counter instantiations are the general code)
     if (flags & RT_TEST_ISECT_GENERAL) simple = false;
     if (flags & RT_TEST_ISECT_SIMPLE) {
         if (a.many_mesh || !h->plain_materials)

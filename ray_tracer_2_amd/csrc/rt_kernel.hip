@@ -32,6 +32,8 @@
 // parity tests require bit-identical images.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "rt_device.h"
 #include "rt_texture.h"
 #include "rt_transc.h"
@@ -1509,6 +1511,43 @@ DEV f3 focus_point_of(const A& a, const CameraConsts& c, uint32_t x, uint32_t y)
                            f3{a.camera.view_params[0], a.camera.view_params[1], a.camera.view_params[2]};
     return mat_xyz(&a.camera.cam_to_world[0][0], local_focus, 1.0f);
 }
+
+// wgsl:502-515: the debug views' ray of texel (x, y) of a width x height frame, from the camera's origin through the
+// texel's focus point, not normalised.  rt_debug_kernel, rt_pick and rt_render_gbuffer agree bit for bit because
+// they all take it from here.
+struct TexelRay {
+    f3 origin, d;
+};
+template <class A>
+DEV TexelRay texel_ray_of(const A& a, uint32_t width, uint32_t height, uint32_t x, uint32_t y) {
+    CameraConsts c = camera_consts(a);
+    c.sx = (float)width;
+    c.sy = (float)height;
+    return TexelRay{c.origin, focus_point_of(a, c, x, y) - c.origin};
+}
+
+DEV bool finite3(f3 v) { return rtm::abs_(v.x) < __builtin_inff() && rtm::abs_(v.y) < __builtin_inff() && rtm::abs_(v.z) < __builtin_inff(); }
+
+// Which rt_ray (include/rt_abi.h) a query traces: finite origin and direction, rd = normalize3(d) finite and not zero,
+// tmax > 0 (false for NaN) and a zero padding word (p0: its bits).  Every other ray gets a miss record.
+DEV bool ray_is_valid(f3 ro, f3 d, f3 rd, float tmax, uint32_t p0) {
+    return finite3(ro) && finite3(d) && finite3(rd) && (rd.x != 0.0f || rd.y != 0.0f || rd.z != 0.0f) &&
+           tmax > 0.0f && p0 == 0u;
+}
+
+// What rt_hit says about who was hit, from intersect_scene's closest hit: the object from its material, the
+// primitive (a sphere's index, or the winning triangle), the flags, and the barycentrics (zero for a sphere).
+struct HitIds {
+    uint32_t object, primitive, flags;
+    float bary_u, bary_v;
+};
+template <bool SIMPLE>
+DEV HitIds hit_ids_of(const RenderArgs& a, const Hit& h, const Isect& I) {
+    const bool sphere = !SIMPLE && I.object < 0;
+    return HitIds{(h.mat_off - a.lay.mat_off) / MATERIAL_BYTES, sphere ? (uint32_t)(-I.object - 1) : (I.win_tri & 0x7fffffffu),
+                  1u | (h.backface ? 2u : 0u), sphere ? 0.0f : I.win_u, sphere ? 0.0f : I.win_v};
+}
+
 // frame row of a pixel from its output row (they differ in the compact strip layout)
 template <class A>
 DEV uint32_t frame_row_of(const A& a, uint32_t out_row) {
@@ -2584,18 +2623,11 @@ __global__ void __launch_bounds__(BLOCK_THREADS) rt_debug_kernel(const RenderArg
     if (tile >= a.tiles_x * a.tiles_y) return;
     const PixelCoord px = pixel_of(a, tile, threadIdx.x & 63u);
     if (!px.valid) return;
-    const float sx = (float)a.params.width, sy = (float)a.params.height;
-    const float fx = (float)px.x, fy = (float)px.y;
-    const float* __restrict__ c2w = &a.camera.cam_to_world[0][0];
-    const f3 cam_origin{c2w[12], c2w[13], c2w[14]};
-    const float uvx = fx / (sx - 1.0f), uvy = fy / (sy - 1.0f);
-    const f3 local_focus = f3{uvx - 0.5f, uvy - 0.5f, 1.0f} *
-                           f3{a.camera.view_params[0], a.camera.view_params[1], a.camera.view_params[2]};
-    const f3 focus_point = mat_xyz(c2w, local_focus, 1.0f);
-    f3 rd = normalize3(focus_point - cam_origin);
+    const TexelRay ray = texel_ray_of(a, a.params.width, a.params.height, px.x, px.y);
+    f3 rd = normalize3(ray.d);
     int s0 = 0, s1 = 0;
     Isect isect;
-    Hit hit = intersect_scene<LDS, true, TLAS>(a, cam_origin, rd, stack, s0, s1, isect);
+    Hit hit = intersect_scene<LDS, true, TLAS>(a, ray.origin, rd, stack, s0, s1, isect);
     const float scale = (float)a.params.debug_scale;
     f4 out{1.0f, 0.0f, 1.0f, 1.0f};
     switch (a.params.debug_flag) {
@@ -2811,12 +2843,36 @@ size_t render_lds_bytes(const RenderArgs& a) {
     return stacks + cost_tables + lane_state + cache + scene;
 }
 
-// Dynamic LDS above 64 KiB (deep-BVH stacks) has to be opted into per kernel.
-template <typename K>
-static void launch_k(K kernel, uint32_t blocks, size_t lds, hipStream_t stream, const RenderArgs& a) {
+// Dynamic LDS above 64 KiB (deep-BVH stacks) has to be opted into per kernel: every launch with the render kernels' LDS
+// map goes through launch_k.
+template <class K>
+static void allow_lds(K kernel, size_t lds) {
     if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a);
+}
+template <class K, class... Args>
+static void launch_k(K kernel, uint32_t blocks, size_t lds, hipStream_t stream, const Args&... args) {
+    allow_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, args...);
+}
+
+// The SIMPLE instantiations exist for the product kernels (no counters) of the few-mesh scenes: whether a render of
+// these arguments takes one.
+bool render_takes_simple(const RenderArgs& a) { return a.many_mesh == 0u && a.simple != 0u && a.count_tests == 0u; }
+
+// THE choice of the instantiation <LDS, TLAS, SIMPLE> of a launch on the scene of `a`: f(lds, tlas, simple) is called
+// with three std::true_type / std::false_type tags.  LDS: the scene is staged into the LDS.  TLAS: the many-mesh code
+// (top-level trees, root-box culling), only compiled into the kernels that need it (register budget).  SIMPLE: only
+// few-mesh scenes have it, and only where the caller wants it (`simple`: render_takes_simple, or a test's forcing).
+template <class F>
+static void with_instantiation(const RenderArgs& a, bool simple, F&& f) {
+    auto scene_kind = [&](auto lds) {
+        if (a.many_mesh != 0u) f(lds, std::true_type{}, std::false_type{});
+        else if (simple) f(lds, std::false_type{}, std::true_type{});
+        else f(lds, std::false_type{}, std::false_type{});
+    };
+    if (a.lds_scene) scene_kind(std::true_type{});
+    else scene_kind(std::false_type{});
 }
 
 // Which instantiations exist (the product library; every one of them is what some BASELINE config or test runs):
@@ -2825,55 +2881,40 @@ static void launch_k(K kernel, uint32_t blocks, size_t lds, hipStream_t stream, 
 //   one wave per tile (small launches) <LDS | global> x <few-mesh: general, SIMPLE | many-mesh: general> =  6
 // Counter launches always take the persistent kernel; a scene that fits the LDS has no mesh worth deferring (the host
 // never asks: rt_api.hip render_impl).  -DRT_EXPERIMENTS=1 adds the hybrid launches and the wavefront kernels.
-template <bool LDS, bool TLAS>
-static void launch_variant(const RenderArgs& a, uint32_t ntiles, size_t lds, hipStream_t stream) {
-    const uint32_t tile_blocks = (ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    // the SIMPLE instantiations exist for the product kernels (no counters) of the few-mesh scenes
-    const bool simple = !TLAS && a.simple != 0u && a.count_tests == 0u;
-    if (a.params.debug_flag != 0) {
-        launch_k(rt_debug_kernel<LDS, TLAS>, tile_blocks, lds, stream, a);
-    } else if (a.kernel_variant == 1 && a.count_tests == 0u) {
-        if (simple) launch_k(rt_render_tiles_kernel<LDS, false, TLAS, !TLAS>, tile_blocks, lds, stream, a);
-        else launch_k(rt_render_tiles_kernel<LDS, false, TLAS, false>, tile_blocks, lds, stream, a);
-    } else {
-        uint32_t blocks = a.persistent_blocks < tile_blocks ? a.persistent_blocks : tile_blocks;
-        if (blocks == 0) blocks = 1;
-        // a launch of a deferred-walk sequence (PARK): few-mesh scenes read from global memory
-        constexpr bool CAN_PARK = !TLAS && !LDS;
-        const bool park = CAN_PARK && (a.park != 0u || a.q_in != nullptr);
-#if RT_EXPERIMENTS
-        if (LDS && !TLAS && (a.park != 0u || a.q_in != nullptr)) {  // (host: hybrid launches only -- the small blob is staged)
-            if (simple) launch_k(rt_render_persistent_kernel<LDS, false, TLAS, !TLAS, !TLAS, LDS && !TLAS>, blocks, lds, stream, a);
-            else launch_k(rt_render_persistent_kernel<LDS, false, TLAS, !TLAS, false, LDS && !TLAS>, blocks, lds, stream, a);
-            return;
-        }
-#endif
-        if (park) {
-            if (a.count_tests) launch_k(rt_render_persistent_kernel<LDS, true, TLAS, CAN_PARK, false>, blocks, lds, stream, a);
-            else if (simple) launch_k(rt_render_persistent_kernel<LDS, false, TLAS, CAN_PARK, CAN_PARK>, blocks, lds, stream, a);
-            else launch_k(rt_render_persistent_kernel<LDS, false, TLAS, CAN_PARK, false>, blocks, lds, stream, a);
-        } else {
-            if (a.count_tests) launch_k(rt_render_persistent_kernel<LDS, true, TLAS, false, false>, blocks, lds, stream, a);
-            else if (simple) launch_k(rt_render_persistent_kernel<LDS, false, TLAS, false, !TLAS>, blocks, lds, stream, a);
-            else launch_k(rt_render_persistent_kernel<LDS, false, TLAS, false, false>, blocks, lds, stream, a);
-        }
-    }
-}
-
 hipError_t launch_render(const RenderArgs& a, hipStream_t stream) {
-    uint32_t ntiles = a.tiles_x * a.tiles_y;
+    const uint32_t ntiles = a.tiles_x * a.tiles_y;
     if (ntiles == 0) return hipSuccess;
-    size_t lds = render_lds_bytes(a);
-    // the many-mesh code (top-level trees, root-box culling) is only compiled into the kernels
-    // that need it (register budget)
-    const bool tlas = a.many_mesh != 0;
-    if (a.lds_scene) {
-        if (tlas) launch_variant<true, true>(a, ntiles, lds, stream);
-        else launch_variant<true, false>(a, ntiles, lds, stream);
-    } else {
-        if (tlas) launch_variant<false, true>(a, ntiles, lds, stream);
-        else launch_variant<false, false>(a, ntiles, lds, stream);
-    }
+    const size_t lds = render_lds_bytes(a);
+    const uint32_t tile_blocks = (ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    with_instantiation(a, render_takes_simple(a), [&](auto lds_tag, auto tlas_tag, auto simple_tag) {
+        constexpr bool LDS = decltype(lds_tag)::value, TLAS = decltype(tlas_tag)::value, SIMPLE = decltype(simple_tag)::value;
+        if (a.params.debug_flag != 0) {
+            launch_k(rt_debug_kernel<LDS, TLAS>, tile_blocks, lds, stream, a);
+        } else if (a.kernel_variant == 1 && a.count_tests == 0u) {
+            launch_k(rt_render_tiles_kernel<LDS, false, TLAS, SIMPLE>, tile_blocks, lds, stream, a);
+        } else {
+            uint32_t blocks = a.persistent_blocks < tile_blocks ? a.persistent_blocks : tile_blocks;
+            if (blocks == 0) blocks = 1;
+            auto persistent = [&](auto park_tag, auto hyb_tag) {  // (counters: the general code, SIMPLE is off with them)
+                constexpr bool PARK = decltype(park_tag)::value, HYB = decltype(hyb_tag)::value;
+                if constexpr (!HYB) {
+                    if (a.count_tests) return launch_k(rt_render_persistent_kernel<LDS, true, TLAS, PARK, false>, blocks, lds, stream, a);
+                }
+                launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB>, blocks, lds, stream, a);
+            };
+            // a launch of a deferred-walk sequence (PARK): few-mesh scenes read from global memory
+            const bool park = a.park != 0u || a.q_in != nullptr;
+            if constexpr (!TLAS && !LDS) {
+                if (park) return persistent(std::true_type{}, std::false_type{});
+            }
+#if RT_EXPERIMENTS
+            if constexpr (!TLAS && LDS) {  // (host: hybrid launches only -- the small blob is staged)
+                if (park) return persistent(std::true_type{}, std::true_type{});
+            }
+#endif
+            persistent(std::false_type{}, std::false_type{});
+        }
+    });
     return hipGetLastError();
 }
 
@@ -2881,13 +2922,8 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t stream) {
 hipError_t launch_walk(const RenderArgs& a, uint32_t compute_units, hipStream_t stream) {
     const size_t lds = (size_t)(a.stack_entries ? a.stack_entries : 1u) * (a.stack_wide ? 128u : 64u) * sizeof(uint32_t) * WAVES_PER_BLOCK;
     const uint32_t blocks = compute_units * 8u;
-    if (a.count_tests) {
-        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rt_walk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(rt_walk_kernel<true>, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a);
-    } else {
-        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rt_walk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(rt_walk_kernel<false>, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a);
-    }
+    if (a.count_tests) launch_k(rt_walk_kernel<true>, blocks, lds, stream, a);
+    else launch_k(rt_walk_kernel<false>, blocks, lds, stream, a);
     return hipGetLastError();
 }
 
@@ -2908,436 +2944,15 @@ hipError_t launch_blend_frames(const BlendArgs& b, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// Ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick; include/rt_abi.h): intersect_scene for rays the host gives,
-// on the uploaded scene, in the instantiation a render of it takes (scene_args, launch_variant).  A persistent grid:
-// every workgroup stages an LDS scene once and then takes rays with a grid stride, one lane per ray, with the prologue
-// and stack layout of the render kernels.  rays: rt_ray records (32 B: origin, tmax, dir, _p0).  ANY = false writes one
-// rt_hit (64 B) per ray, ANY = true one u32 (occluded) per ray.  A ray with a non-finite component, a direction whose
-// normalize3 is not finite and non-zero, tmax <= 0 or NaN, or _p0 != 0 gets a miss record.
-// ---------------------------------------------------------------------------
-template <bool LDS, bool TLAS, bool SIMPLE, bool ANY>
-__global__ void __launch_bounds__(BLOCK_THREADS) rt_query_kernel(const RenderArgs a, const float4* __restrict__ rays,
-                                                                 unsigned long long n, void* __restrict__ out,
-                                                                 uint32_t prune_tmax) {
-    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
-    const unsigned long long stride = (unsigned long long)gridDim.x * BLOCK_THREADS;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK_THREADS + threadIdx.x; i < n; i += stride) {
-        const float4 r0 = rays[2 * i], r1 = rays[2 * i + 1];
-        const f3 ro{r0.x, r0.y, r0.z}, d{r1.x, r1.y, r1.z};
-        const float tmax = r0.w;
-        const f3 rd = normalize3(d);
-        auto finite3 = [](f3 v) { return rtm::abs_(v.x) < __builtin_inff() && rtm::abs_(v.y) < __builtin_inff() && rtm::abs_(v.z) < __builtin_inff(); };
-        const bool valid = finite3(ro) && finite3(d) && finite3(rd) && (rd.x != 0.0f || rd.y != 0.0f || rd.z != 0.0f) &&
-                           tmax > 0.0f && fbits(r1.w) == 0u;
-        int node_tests = 0, tri_tests = 0;
-        Isect I;
-        if constexpr (ANY) {
-            bool occluded = false;
-            if (valid) occluded = intersect_scene<LDS, false, TLAS, false, SIMPLE, false, true>(a, ro, rd, stack, node_tests, tri_tests, I, tmax, prune_tmax != 0u).hit;
-            static_cast<uint32_t*>(out)[i] = occluded ? 1u : 0u;
-        } else {
-            Hit h{};
-            if (valid) h = intersect_scene<LDS, false, TLAS, false, SIMPLE, false, false, true>(a, ro, rd, stack, node_tests, tri_tests, I);
-            float4* o = static_cast<float4*>(out) + 4 * i;
-            if (valid && h.hit && h.dst < tmax) {
-                const bool sphere = !SIMPLE && I.object < 0;
-                const uint32_t object = (h.mat_off - a.lay.mat_off) / MATERIAL_BYTES;
-                const uint32_t prim = sphere ? (uint32_t)(-I.object - 1) : (I.win_tri & 0x7fffffffu);
-                const float bu = sphere ? 0.0f : I.win_u, bv = sphere ? 0.0f : I.win_v;
-                o[0] = make_float4(h.dst, __uint_as_float(object), __uint_as_float(prim), __uint_as_float(1u | (h.backface ? 2u : 0u)));
-                o[1] = make_float4(h.point.x, h.point.y, h.point.z, bu);
-                o[2] = make_float4(h.normal.x, h.normal.y, h.normal.z, bv);
-                o[3] = make_float4(h.u, h.v, 0.0f, 0.0f);
-            } else {
-                o[0] = make_float4(__builtin_inff(), __uint_as_float(0xffffffffu), __uint_as_float(0xffffffffu), 0.0f);
-                o[1] = o[2] = o[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-    }
-}
-
-// rt_pick: the ray rt_debug_kernel traces for texel (x, y) -- the same operations -- as one rt_ray with tmax = +inf
-__global__ void rt_pick_ray_kernel(const RenderArgs a, uint32_t x, uint32_t y, float4* __restrict__ ray) {
-    const float sx = (float)a.params.width, sy = (float)a.params.height;
-    const float fx = (float)x, fy = (float)y;
-    const float* __restrict__ c2w = &a.camera.cam_to_world[0][0];
-    const f3 cam_origin{c2w[12], c2w[13], c2w[14]};
-    const float uvx = fx / (sx - 1.0f), uvy = fy / (sy - 1.0f);
-    const f3 local_focus = f3{uvx - 0.5f, uvy - 0.5f, 1.0f} *
-                           f3{a.camera.view_params[0], a.camera.view_params[1], a.camera.view_params[2]};
-    const f3 focus_point = mat_xyz(c2w, local_focus, 1.0f);
-    const f3 d = focus_point - cam_origin;  // (not normalised here: the query kernel's normalize3 is rt_debug_kernel's)
-    ray[0] = make_float4(cam_origin.x, cam_origin.y, cam_origin.z, __builtin_inff());
-    ray[1] = make_float4(d.x, d.y, d.z, 0.0f);
-}
-
-hipError_t launch_pick_ray(const RenderArgs& a, uint32_t x, uint32_t y, float4* ray, hipStream_t stream) {
-    hipLaunchKernelGGL(rt_pick_ray_kernel, dim3(1), dim3(1), 0, stream, a, x, y, ray);
-    return hipGetLastError();
-}
-
-// any: occlusion (out: u32 per ray), else closest hit (out: rt_hit per ray).  The persistent grid: at least `blocks`
-// workgroups (the render's persistent grid), raised to what the query kernel itself keeps resident on compute_units CUs
-// -- its registers allow more waves per SIMD than the render kernels' budget (measured: the render's grid of 4 waves
-// per SIMD was slower than one workgroup per 256 rays) -- and at most one workgroup per 256 rays.
-hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long long n, void* out, bool any, bool prune_tmax,
-                        uint32_t blocks, uint32_t compute_units, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const size_t lds = render_lds_bytes(a);
-    const unsigned long long need = (n + BLOCK_THREADS - 1) / BLOCK_THREADS;
-    auto go = [&](auto kernel) {
-        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK_THREADS, lds) == hipSuccess && per_cu > 0 &&
-            (unsigned long long)per_cu * compute_units > blocks)
-            blocks = (uint32_t)per_cu * compute_units;
-        if (need < blocks) blocks = (uint32_t)need;
-        if (blocks == 0) blocks = 1;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, static_cast<const float4*>(rays), n, out,
-                           prune_tmax ? 1u : 0u);
-    };
-    // launch_variant's choice: the SIMPLE instantiation for the few-mesh product kernels of a plain scene
-    const bool tlas = a.many_mesh != 0u, simple = !tlas && a.simple != 0u;
-    if (a.lds_scene) {
-        if (tlas) any ? go(rt_query_kernel<true, true, false, true>) : go(rt_query_kernel<true, true, false, false>);
-        else if (simple) any ? go(rt_query_kernel<true, false, true, true>) : go(rt_query_kernel<true, false, true, false>);
-        else any ? go(rt_query_kernel<true, false, false, true>) : go(rt_query_kernel<true, false, false, false>);
-    } else {
-        if (tlas) any ? go(rt_query_kernel<false, true, false, true>) : go(rt_query_kernel<false, true, false, false>);
-        else if (simple) any ? go(rt_query_kernel<false, false, true, true>) : go(rt_query_kernel<false, false, true, false>);
-        else any ? go(rt_query_kernel<false, false, false, true>) : go(rt_query_kernel<false, false, false, false>);
-    }
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// First-hit buffers of a frame (rt_render_gbuffer; include/rt_abi.h): for every texel of rows
-// [row0, row0 + rows) the ray rt_debug_kernel / rt_pick_ray_kernel generate for it -- the same operations --, validated
-// and intersected as rt_query_kernel does it for rt_pick (same instantiation, EXPORT), and the hit written channel by
-// channel into the planes that are not NULL (wave-uniform branches: a channel that is off costs nothing, the texture
-// filter included).  One wave per chunk of 64 texels (the queries' persistent grid was measured a sixth slower here) -- for
-// the few-mesh kernels 64 consecutive texels of the band in row-major order (the planes are tightly packed, so the band is ONE array:
-// every store of a wave is one contiguous run for any width), for the many-mesh kernels (TLAS), whose walk gains a fifth
-// from coherent rays, a tile of 8x8 texels (runs of 8 texels per row); measured, DESIGN.md section 2.10.
-// Every channel is ONE store per lane of the texel's 1, 4, 8, 12 or 16 contiguous bytes (the planes of 2 and 3 floats
-// are only 4-byte aligned: global memory takes such a store): lane after lane a run's bytes are contiguous, so one
-// instruction fills every 32-byte sector it touches but the run's two ends.
-// The wave index is read from the first lane, so the chunk's place in the frame is wave-uniform; a plane is addressed from
-// the chunk's first texel in it -- a scalar base, passed through scalar_base so that the compiler keeps it apart from the
-// lane's part instead of holding eleven per-lane 64-bit addresses across the walk -- plus the lane's texel within the
-// chunk, a 32-bit element index.
-// ---------------------------------------------------------------------------
-template <class T>
-DEV T* scalar_base(T* p) {
-    unsigned long long b = reinterpret_cast<unsigned long long>(p);
-    asm("" : "+s"(b));  // (no instruction: the value is wave-uniform and lives in a scalar register pair from here on)
-    return reinterpret_cast<T*>(b);
-}
-// The planes are written once and read by nobody in the launch: streaming stores keep them from displacing the scene in L2.
-// base: the chunk's first texel in the plane; e: this lane's texel from there.  (global-address-space pointers:
-// global_store, not flat_store -- the integer round trip of scalar_base forgets the address space)
-#define RT_GLOBAL(T, p) ((__attribute__((address_space(1))) T*)(void*)(p))
-template <class T>
-DEV void store_plane(T* base, uint32_t e, T v) { __builtin_nontemporal_store(v, RT_GLOBAL(T, base + e)); }
-DEV void store_plane(float4* base, uint32_t e, float4 v) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, RT_GLOBAL(v4f, base + e));
-}
-DEV void store_plane2(float* base, uint32_t e, float x, float y) {
-    typedef float v2f __attribute__((ext_vector_type(2), aligned(4)));
-    __builtin_nontemporal_store(v2f{x, y}, RT_GLOBAL(v2f, base + 2u * (size_t)e));
-}
-DEV void store_plane3(float* base, uint32_t e, float x, float y, float z) {
-    typedef float v3f __attribute__((ext_vector_type(3), aligned(4)));
-    __builtin_nontemporal_store(v3f{x, y, z}, RT_GLOBAL(v3f, base + 3u * (size_t)e));
-}
-
-template <bool LDS, bool TLAS, bool SIMPLE>
-__global__ void __launch_bounds__(BLOCK_THREADS) rt_gbuffer_kernel(const RenderArgs a, const GBufferArgs g) {
-    constexpr bool TILES = TLAS;
-    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6)));
-    const uint32_t chunk = wave;
-    const uint32_t n = g.rows * g.width;  // (<= 2^31 - 1: the host checks)
-    const uint32_t tiles_x = (g.width + 7u) >> 3;
-    // this lane's texel from the chunk's first one, in the planes (a tile's rows beyond the band wrap: never stored)
-    const uint32_t e = TILES ? (lane >> 3) * g.width + (lane & 7u) : lane;
-    const float sx = (float)g.width, sy = (float)g.height;
-    const float* __restrict__ c2w = &a.camera.cam_to_world[0][0];
-    const f3 cam_origin{c2w[12], c2w[13], c2w[14]};
-    auto finite3 = [](f3 v) { return rtm::abs_(v.x) < __builtin_inff() && rtm::abs_(v.y) < __builtin_inff() && rtm::abs_(v.z) < __builtin_inff(); };
-    {
-        uint32_t x, yl, first;  // this lane's texel in the band; the chunk's first texel in the planes
-        bool inside;
-        if constexpr (!TILES) {
-            first = chunk * 64u;
-            const uint32_t i = first + lane;
-            inside = i < n;
-            yl = i / g.width;
-            x = i - yl * g.width;
-        } else {
-            const uint32_t ty = chunk / tiles_x, x0 = (chunk - ty * tiles_x) << 3;
-            x = x0 + (lane & 7u);
-            yl = ty * 8u + (lane >> 3);
-            inside = yl < g.rows && x < g.width;
-            first = ty * 8u * g.width + x0;
-        }
-        // wgsl:502-515, as rt_debug_kernel
-        const float fx = (float)x, fy = (float)(g.row0 + yl);
-        const float uvx = fx / (sx - 1.0f), uvy = fy / (sy - 1.0f);
-        const f3 local_focus = f3{uvx - 0.5f, uvy - 0.5f, 1.0f} *
-                               f3{a.camera.view_params[0], a.camera.view_params[1], a.camera.view_params[2]};
-        const f3 focus_point = mat_xyz(c2w, local_focus, 1.0f);
-        const f3 d = focus_point - cam_origin;
-        const f3 rd = normalize3(d);
-        // rt_query_kernel's validity of the rt_ray (cam_origin, +inf, d, 0) and its closest hit
-        const bool valid = inside && finite3(cam_origin) && finite3(d) && finite3(rd) && (rd.x != 0.0f || rd.y != 0.0f || rd.z != 0.0f);
-        if (g.dir && inside) store_plane3(scalar_base(g.dir + 3u * (size_t)first), e, rd.x, rd.y, rd.z);  // (before the walk: nothing of the ray outlives it)
-        int node_tests = 0, tri_tests = 0;
-        Isect I;
-        Hit h{};
-        if (valid) h = intersect_scene<LDS, false, TLAS, false, SIMPLE, false, false, true>(a, cam_origin, rd, stack, node_tests, tri_tests, I);
-        const bool hit = valid && h.hit && h.dst < __builtin_inff();
-        const bool sphere = !SIMPLE && I.object < 0;
-        if (g.depth && inside) store_plane(scalar_base(g.depth + first), e, hit ? h.dst : __builtin_inff());
-        if (g.object && inside) store_plane(scalar_base(g.object + first), e, hit ? (h.mat_off - a.lay.mat_off) / MATERIAL_BYTES : 0xffffffffu);
-        if (g.primitive && inside) store_plane(scalar_base(g.primitive + first), e, hit ? (sphere ? (uint32_t)(-I.object - 1) : (I.win_tri & 0x7fffffffu)) : 0xffffffffu);
-        if (g.flags && inside) store_plane(scalar_base(g.flags + first), e, hit ? (uint8_t)(1u | (h.backface ? 2u : 0u)) : (uint8_t)0u);
-        if (g.point && inside) store_plane3(scalar_base(g.point + 3u * (size_t)first), e, hit ? h.point.x : 0.0f, hit ? h.point.y : 0.0f, hit ? h.point.z : 0.0f);
-        if (g.normal && inside) store_plane3(scalar_base(g.normal + 3u * (size_t)first), e, hit ? h.normal.x : 0.0f, hit ? h.normal.y : 0.0f, hit ? h.normal.z : 0.0f);
-        if (g.bary && inside) store_plane2(scalar_base(g.bary + 2u * (size_t)first), e, hit && !sphere ? I.win_u : 0.0f, hit && !sphere ? I.win_v : 0.0f);
-        if (g.texcoord && inside) store_plane2(scalar_base(g.texcoord + 2u * (size_t)first), e, hit ? h.u : 0.0f, hit ? h.v : 0.0f);
-        if (g.albedo) {  // `color` of wgsl:453-458
-            float4 color = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (hit) {
-                const int flag = ldi<LDS>(a, h.mat_off + M_FLAG), diffuse_index = ldi<LDS>(a, h.mat_off + M_DIFFUSE_IDX);
-                if (!SIMPLE && flag == RT_MATERIAL_TEXTURE && diffuse_index != -1) {
-                    const f4 s = sample_texture(a, diffuse_index, h.u, h.v);
-                    color = make_float4(s.x, s.y, s.z, s.w);
-                } else {
-                    color = ld4<LDS>(a, h.mat_off + M_COLOR);
-                }
-            }
-            if (inside) store_plane(scalar_base(g.albedo + first), e, color);
-        }
-        if (g.emission) {  // wgsl:450
-            float4 em = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (hit) {
-                const float4 ec = ld4<LDS>(a, h.mat_off + M_EMISSION);
-                const float es = ldf<LDS>(a, h.mat_off + M_EMISSION_S);
-                em = make_float4(ec.x * es, ec.y * es, ec.z * es, ec.w * es);
-            }
-            if (inside) store_plane(scalar_base(g.emission + first), e, em);
-        }
-    }
-}
-
-// grid: one wave per chunk (the workgroups of the last partial one have waves without a chunk: they stage and leave).
-// Measured against the queries' persistent grid, which restages an LDS scene less often: DESIGN.md section 2.10.
-hipError_t launch_gbuffer(const RenderArgs& a, const GBufferArgs& g, hipStream_t stream) {
-    const bool tlas = a.many_mesh != 0u, simple = !tlas && a.simple != 0u;  // launch_variant's choice
-    const uint32_t chunks = gbuffer_chunks(g, tlas);
-    if (chunks == 0) return hipSuccess;
-    const size_t lds = render_lds_bytes(a);
-    const uint32_t blocks = (chunks + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    auto go = [&](auto kernel) {
-        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, g);
-    };
-    if (a.lds_scene) {
-        if (tlas) go(rt_gbuffer_kernel<true, true, false>);
-        else if (simple) go(rt_gbuffer_kernel<true, false, true>);
-        else go(rt_gbuffer_kernel<true, false, false>);
-    } else {
-        if (tlas) go(rt_gbuffer_kernel<false, true, false>);
-        else if (simple) go(rt_gbuffer_kernel<false, false, true>);
-        else go(rt_gbuffer_kernel<false, false, false>);
-    }
-    return hipGetLastError();
-}
-
-#ifndef RT_TEST_ENTRIES
-#define RT_TEST_ENTRIES 0
-#endif
-#if RT_TEST_ENTRIES   // (the test library only: ray_tracer_2_amd/librt2_mi355x_test.so, include/rt_test_abi.h)
-// ---------------------------------------------------------------------------
-// Test-only: the device's evaluation of the implementation-defined builtins (rt_transc.h), IEEE
-// division / sqrt, the RNG and the texture filter, one element per thread, so that
-// tests/test_gpu_device_units.py can compare them bit for bit with the host compile of the same
-// headers (the oracle) -- including the edge values whole-image parity tests almost never reach
-// (rand() == 0 -> log(0), rand() == 1, trig sign bits at exact zeros, subnormals, inf, NaN).
-// fn: 0 log, 1 cos, 2 sin, 3 exp, 4 exp2, 5 log2, 6 pow(x, y), 7 acos, 8 atan2(x, y), 9 sqrt, 10 x / y
-// (the oracle's numbering), 11 rand() of RNG state bits x -> float, 12 the generator's u32 output for
-// state x, 13 trig_signbits(x), 14 rand_normal_dist() of state x, 15 f32(u32 x) * 2^-32 (rand()'s
-// conversion for a raw generator output), 16 normalize(x, y, x*y).x (division by a sqrt), 17 rcp_(x), 18 sqrt_dev(x)
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) rt_units_kernel(int fn, const float* __restrict__ x, const float* __restrict__ y,
-                                                       float* __restrict__ out, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float a = x[i], b = y[i];
-    float r = 0.0f;
-    switch (fn) {
-        case 0: r = rtm::log_(a); break;
-        case 1: r = rtm::cos_(a); break;
-        case 2: r = rtm::sin_(a); break;
-        case 3: r = rtm::exp_(a); break;
-        case 4: r = rtm::exp2_(a); break;
-        case 5: r = rtm::log2_(a); break;
-        case 6: r = rtm::pow_(a, b); break;
-        case 7: r = rtm::acos_(a); break;
-        case 8: r = rtm::atan2_(a, b); break;
-        case 9: r = rtm::sqrt_(a); break;
-        case 10: r = a / b; break;
-        case 11: { uint32_t s = __float_as_uint(a); r = rand_(s); break; }
-        case 12: { uint32_t s = __float_as_uint(a); r = __uint_as_float(next_random_number(s)); break; }
-        case 13: r = __uint_as_float(rtm::trig_signbits(a)); break;
-        case 14: { uint32_t s = __float_as_uint(a); r = rand_normal_dist(s); break; }
-        case 15: r = (float)__float_as_uint(a) * 0x1p-32f; break;
-        case 16: r = normalize3(f3{a, b, a * b}).x; break;
-        case 17: r = rcp_(a); break;
-        case 18: r = sqrt_dev(a); break;
-        default: break;
-    }
-    out[i] = r;
-}
-
-__global__ void __launch_bounds__(256) rt_units_texture_kernel(const uint8_t* rgba8, uint32_t width, uint32_t height,
-                                                               const float* srgb_lut, const float* __restrict__ uv,
-                                                               float* __restrict__ out, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    typedef const __attribute__((address_space(1))) uint32_t* GWords;
-    typedef const __attribute__((address_space(1))) float* GFloats;
-    float o[4];
-    rtm::sample_bilinear_words((GWords)(const void*)rgba8, width, height, (GFloats)(const void*)srgb_lut, uv[2 * i], uv[2 * i + 1], o);
-    out[4 * i] = o[0]; out[4 * i + 1] = o[1]; out[4 * i + 2] = o[2]; out[4 * i + 3] = o[3];
-}
-
-// Every float x the short forms serve: rcp_core(x) against the compiler's IEEE 1.0f / x (which = 0), sqrt_core(x)
-// against its sqrt (which = 1), and the sky's shortcuts against their literal forms -- sky_gradient_t (2) and
-// ground_to_sky_t (3) for every float in [-1.5, 1.5] plus NaN and the infinities, sun_term (4) for every float in
-// [0, 1.5] (max(0, .) never hands it anything negative) -- bit for bit.  out[0] = floats checked, out[1] = mismatches,
-// out[2] = a mismatching bit pattern.
-__global__ void __launch_bounds__(256) rt_sweep_kernel(int which, unsigned long long* out) {
-    unsigned long long checked = 0, bad = 0;
-    for (unsigned long long b = (unsigned long long)blockIdx.x * 256u + threadIdx.x; b < (1ull << 32); b += (unsigned long long)gridDim.x * 256u) {
-        const float x = __uint_as_float((uint32_t)b);
-        bool in_range;
-        if (which == 0) in_range = rcp_in_range(x);
-        else if (which == 1) in_range = sqrt_in_range(x);
-        else if (which == 4) in_range = (x >= 0.0f && x <= 1.5f) || x != x;
-        else in_range = rtm::abs_(x) <= 1.5f || x != x || rtm::abs_(x) == __uint_as_float(0x7f800000u);
-        if (!in_range) continue;
-        float q = which == 0 ? 1.0f / x : which == 1 ? rtm::sqrt_(x) : which == 2 ? sky_gradient_t_literal(x)
-                                                     : which == 3 ? ground_to_sky_t_literal(x) : sun_literal(x);
-        asm volatile("" : "+v"(q));
-        const float f = which == 0 ? rcp_core(x) : which == 1 ? sqrt_core(x) : which == 2 ? sky_gradient_t(x)
-                                                 : which == 3 ? ground_to_sky_t(x) : sun_term(x);
-        checked += 1;
-        const bool both_nan = f != f && q != q;  // (NaN sign and payload are outside the arithmetic contract)
-        if (!both_nan && __float_as_uint(f) != __float_as_uint(q)) {
-            bad += 1;
-            out[2] = b;
-        }
-    }
-    atomicAdd(&out[0], checked);
-    if (bad) atomicAdd(&out[1], bad);
-}
-hipError_t launch_sweep(int which, unsigned long long* out, hipStream_t stream) {
-    hipLaunchKernelGGL(rt_sweep_kernel, dim3(4096), dim3(256), 0, stream, which, out);
-    return hipGetLastError();
-}
-
-// Test-only: intersect_scene for rays the host chooses (rt_test_intersect, tests/test_gpu_intersect.py), one lane per ray,
-// with the prologue and stack of rt_debug_kernel and the instantiation launch_variant would take (or the one the caller
-// forces).  A lane whose `active` byte is 0 stays out of intersect_scene, as lanes do in the partial waves the vote and
-// the refill create.  Record per ray (16 words, RT_TEST_ISECT_WORDS): hit, dst, point xyz, normal xyz, u, v, backface,
-// winner (mesh index, or n_meshes + sphere index; ~0 on a miss), node tests, triangle tests, instantiation bits, 0.
-template <bool LDS, bool TLAS, bool SIMPLE, bool STATS>
-__global__ void __launch_bounds__(BLOCK_THREADS) rt_test_intersect_kernel(const RenderArgs a, const float* __restrict__ ro,
-                                                                          const float* __restrict__ rd,
-                                                                          const uint8_t* __restrict__ active,
-                                                                          unsigned long long n, uint32_t* __restrict__ out) {
-    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
-    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK_THREADS + threadIdx.x;
-    if (i >= n || (active != nullptr && active[i] == 0u)) return;
-    const f3 o{ro[3 * i], ro[3 * i + 1], ro[3 * i + 2]}, d{rd[3 * i], rd[3 * i + 1], rd[3 * i + 2]};
-    int node_tests = 0, tri_tests = 0;
-    Isect unused;
-    const Hit h = intersect_scene<LDS, STATS, TLAS, false, SIMPLE>(a, o, d, stack, node_tests, tri_tests, unused);
-    uint32_t* r = out + i * 16u;
-    r[0] = h.hit ? 1u : 0u;
-    r[1] = __float_as_uint(h.dst);
-    r[2] = __float_as_uint(h.point.x); r[3] = __float_as_uint(h.point.y); r[4] = __float_as_uint(h.point.z);
-    r[5] = __float_as_uint(h.normal.x); r[6] = __float_as_uint(h.normal.y); r[7] = __float_as_uint(h.normal.z);
-    r[8] = __float_as_uint(h.u);
-    r[9] = __float_as_uint(h.v);
-    r[10] = h.backface ? 1u : 0u;
-    r[11] = h.hit ? (h.mat_off - a.lay.mat_off) / MATERIAL_BYTES : 0xffffffffu;
-    r[12] = (uint32_t)node_tests;
-    r[13] = (uint32_t)tri_tests;
-    r[14] = (TLAS ? 1u : 0u) | (SIMPLE ? 2u : 0u) | (STATS ? 32u : 0u) | (LDS ? 64u : 0u);
-    r[15] = 0u;
-}
-
-// simple: the SIMPLE instantiation (few-mesh scenes only: the host checks), stats: the counter instantiation
-hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const float* rd, const uint8_t* active,
-                                 unsigned long long n, bool simple, bool stats, uint32_t* out, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const size_t lds = render_lds_bytes(a);
-    const uint32_t blocks = (uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-    auto go = [&](auto kernel) {
-        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, ro, rd, active, n, out);
-    };
-    const bool lds_scene = a.lds_scene != 0u, tlas = a.many_mesh != 0u;
-    if (lds_scene) {
-        if (tlas) stats ? go(rt_test_intersect_kernel<true, true, false, true>) : go(rt_test_intersect_kernel<true, true, false, false>);
-        else if (simple) stats ? go(rt_test_intersect_kernel<true, false, true, true>) : go(rt_test_intersect_kernel<true, false, true, false>);
-        else stats ? go(rt_test_intersect_kernel<true, false, false, true>) : go(rt_test_intersect_kernel<true, false, false, false>);
-    } else {
-        if (tlas) stats ? go(rt_test_intersect_kernel<false, true, false, true>) : go(rt_test_intersect_kernel<false, true, false, false>);
-        else if (simple) stats ? go(rt_test_intersect_kernel<false, false, true, true>) : go(rt_test_intersect_kernel<false, false, true, false>);
-        else stats ? go(rt_test_intersect_kernel<false, false, false, true>) : go(rt_test_intersect_kernel<false, false, false, false>);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_units(int fn, const float* x, const float* y, float* out, unsigned long long n, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_units_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, fn, x, y, out, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_units_texture(const uint8_t* rgba8, uint32_t width, uint32_t height, const float* srgb_lut, const float* uv,
-                                float* out, unsigned long long n, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_units_texture_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, rgba8, width, height,
-                       srgb_lut, uv, out, n);
-    return hipGetLastError();
-}
-#endif  // RT_TEST_ENTRIES
-
 hipError_t launch_primary(const RenderArgs& a, void* table, bool with_hits, hipStream_t stream) {
     const uint32_t ntiles = a.tiles_x * a.tiles_y;
     if (ntiles == 0) return hipSuccess;
     const size_t lds = render_lds_bytes(a);
     const uint32_t blocks = (ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    auto go = [&](auto kernel) {
-        if (lds > 64u * 1024u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK_THREADS), lds, stream, a, (uint4*)table, with_hits ? 1u : 0u);
-    };
-    const bool tlas = a.many_mesh != 0;
-    if (a.lds_scene) {
-        if (tlas) go(rt_primary_kernel<true, true>);
-        else go(rt_primary_kernel<true, false>);
-    } else {
-        if (tlas) go(rt_primary_kernel<false, true>);
-        else go(rt_primary_kernel<false, false>);
-    }
+    with_instantiation(a, false, [&](auto lds_tag, auto tlas_tag, auto) {
+        launch_k(rt_primary_kernel<decltype(lds_tag)::value, decltype(tlas_tag)::value>, blocks, lds, stream, a, (uint4*)table,
+                 with_hits ? 1u : 0u);
+    });
     return hipGetLastError();
 }
 
@@ -3350,5 +2965,14 @@ hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width
                        height, world, pad_texels);
     return hipGetLastError();
 }
+
+#include "rt_queries.inl"  // rt_query_kernel, rt_pick_ray_kernel, rt_gbuffer_kernel and their launchers
+
+#ifndef RT_TEST_ENTRIES
+#define RT_TEST_ENTRIES 0
+#endif
+#if RT_TEST_ENTRIES   // (the test library only: ray_tracer_2_amd/librt2_mi355x_test.so, include/rt_test_abi.h)
+#include "rt_test_kernels.inl"
+#endif
 
 }  // namespace rtd

@@ -1,0 +1,150 @@
+// rt_test_kernels.inl -- TEST LIBRARY ONLY (-DRT_TEST_ENTRIES=1; included by rt_kernel.hip inside namespace rtd): the kernels
+// behind include/rt_test_abi.h with their launchers.
+// ---------------------------------------------------------------------------
+// Test-only: the device's evaluation of the implementation-defined builtins (rt_transc.h), IEEE
+// division / sqrt, the RNG and the texture filter, one element per thread, so that
+// tests/test_gpu_device_units.py can compare them bit for bit with the host compile of the same
+// headers (the oracle) -- including the edge values whole-image parity tests almost never reach
+// (rand() == 0 -> log(0), rand() == 1, trig sign bits at exact zeros, subnormals, inf, NaN).
+// fn: 0 log, 1 cos, 2 sin, 3 exp, 4 exp2, 5 log2, 6 pow(x, y), 7 acos, 8 atan2(x, y), 9 sqrt, 10 x / y
+// (the oracle's numbering), 11 rand() of RNG state bits x -> float, 12 the generator's u32 output for
+// state x, 13 trig_signbits(x), 14 rand_normal_dist() of state x, 15 f32(u32 x) * 2^-32 (rand()'s
+// conversion for a raw generator output), 16 normalize(x, y, x*y).x (division by a sqrt), 17 rcp_(x), 18 sqrt_dev(x)
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) rt_units_kernel(int fn, const float* __restrict__ x, const float* __restrict__ y,
+                                                       float* __restrict__ out, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float a = x[i], b = y[i];
+    float r = 0.0f;
+    switch (fn) {
+        case 0: r = rtm::log_(a); break;
+        case 1: r = rtm::cos_(a); break;
+        case 2: r = rtm::sin_(a); break;
+        case 3: r = rtm::exp_(a); break;
+        case 4: r = rtm::exp2_(a); break;
+        case 5: r = rtm::log2_(a); break;
+        case 6: r = rtm::pow_(a, b); break;
+        case 7: r = rtm::acos_(a); break;
+        case 8: r = rtm::atan2_(a, b); break;
+        case 9: r = rtm::sqrt_(a); break;
+        case 10: r = a / b; break;
+        case 11: { uint32_t s = __float_as_uint(a); r = rand_(s); break; }
+        case 12: { uint32_t s = __float_as_uint(a); r = __uint_as_float(next_random_number(s)); break; }
+        case 13: r = __uint_as_float(rtm::trig_signbits(a)); break;
+        case 14: { uint32_t s = __float_as_uint(a); r = rand_normal_dist(s); break; }
+        case 15: r = (float)__float_as_uint(a) * 0x1p-32f; break;
+        case 16: r = normalize3(f3{a, b, a * b}).x; break;
+        case 17: r = rcp_(a); break;
+        case 18: r = sqrt_dev(a); break;
+        default: break;
+    }
+    out[i] = r;
+}
+
+__global__ void __launch_bounds__(256) rt_units_texture_kernel(const uint8_t* rgba8, uint32_t width, uint32_t height,
+                                                               const float* srgb_lut, const float* __restrict__ uv,
+                                                               float* __restrict__ out, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    typedef const __attribute__((address_space(1))) uint32_t* GWords;
+    typedef const __attribute__((address_space(1))) float* GFloats;
+    float o[4];
+    rtm::sample_bilinear_words((GWords)(const void*)rgba8, width, height, (GFloats)(const void*)srgb_lut, uv[2 * i], uv[2 * i + 1], o);
+    out[4 * i] = o[0]; out[4 * i + 1] = o[1]; out[4 * i + 2] = o[2]; out[4 * i + 3] = o[3];
+}
+
+// Every float x the short forms serve: rcp_core(x) against the compiler's IEEE 1.0f / x (which = 0), sqrt_core(x)
+// against its sqrt (which = 1), and the sky's shortcuts against their literal forms -- sky_gradient_t (2) and
+// ground_to_sky_t (3) for every float in [-1.5, 1.5] plus NaN and the infinities, sun_term (4) for every float in
+// [0, 1.5] (max(0, .) never hands it anything negative) -- bit for bit.  out[0] = floats checked, out[1] = mismatches,
+// out[2] = a mismatching bit pattern.
+__global__ void __launch_bounds__(256) rt_sweep_kernel(int which, unsigned long long* out) {
+    unsigned long long checked = 0, bad = 0;
+    for (unsigned long long b = (unsigned long long)blockIdx.x * 256u + threadIdx.x; b < (1ull << 32); b += (unsigned long long)gridDim.x * 256u) {
+        const float x = __uint_as_float((uint32_t)b);
+        bool in_range;
+        if (which == 0) in_range = rcp_in_range(x);
+        else if (which == 1) in_range = sqrt_in_range(x);
+        else if (which == 4) in_range = (x >= 0.0f && x <= 1.5f) || x != x;
+        else in_range = rtm::abs_(x) <= 1.5f || x != x || rtm::abs_(x) == __uint_as_float(0x7f800000u);
+        if (!in_range) continue;
+        float q = which == 0 ? 1.0f / x : which == 1 ? rtm::sqrt_(x) : which == 2 ? sky_gradient_t_literal(x)
+                                                     : which == 3 ? ground_to_sky_t_literal(x) : sun_literal(x);
+        asm volatile("" : "+v"(q));
+        const float f = which == 0 ? rcp_core(x) : which == 1 ? sqrt_core(x) : which == 2 ? sky_gradient_t(x)
+                                                 : which == 3 ? ground_to_sky_t(x) : sun_term(x);
+        checked += 1;
+        const bool both_nan = f != f && q != q;  // (NaN sign and payload are outside the arithmetic contract)
+        if (!both_nan && __float_as_uint(f) != __float_as_uint(q)) {
+            bad += 1;
+            out[2] = b;
+        }
+    }
+    atomicAdd(&out[0], checked);
+    if (bad) atomicAdd(&out[1], bad);
+}
+hipError_t launch_sweep(int which, unsigned long long* out, hipStream_t stream) {
+    hipLaunchKernelGGL(rt_sweep_kernel, dim3(4096), dim3(256), 0, stream, which, out);
+    return hipGetLastError();
+}
+
+// Test-only: intersect_scene for rays the host chooses (rt_test_intersect, tests/test_gpu_intersect.py), one lane per ray,
+// with the prologue and stack of rt_debug_kernel and the instantiation launch_render would take (or the one the caller
+// forces).  A lane whose `active` byte is 0 stays out of intersect_scene, as lanes do in the partial waves the vote and
+// the refill create.  Record per ray (16 words, RT_TEST_ISECT_WORDS): hit, dst, point xyz, normal xyz, u, v, backface,
+// winner (mesh index, or n_meshes + sphere index; ~0 on a miss), node tests, triangle tests, instantiation bits, 0.
+template <bool LDS, bool TLAS, bool SIMPLE, bool STATS>
+__global__ void __launch_bounds__(BLOCK_THREADS) rt_test_intersect_kernel(const RenderArgs a, const float* __restrict__ ro,
+                                                                          const float* __restrict__ rd,
+                                                                          const uint8_t* __restrict__ active,
+                                                                          unsigned long long n, uint32_t* __restrict__ out) {
+    uint32_t* stack = stack_of<total_in_lds(LDS)>(block_prologue<LDS>(a));
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    if (i >= n || (active != nullptr && active[i] == 0u)) return;
+    const f3 o{ro[3 * i], ro[3 * i + 1], ro[3 * i + 2]}, d{rd[3 * i], rd[3 * i + 1], rd[3 * i + 2]};
+    int node_tests = 0, tri_tests = 0;
+    Isect unused;
+    const Hit h = intersect_scene<LDS, STATS, TLAS, false, SIMPLE>(a, o, d, stack, node_tests, tri_tests, unused);
+    uint32_t* r = out + i * 16u;
+    r[0] = h.hit ? 1u : 0u;
+    r[1] = __float_as_uint(h.dst);
+    r[2] = __float_as_uint(h.point.x); r[3] = __float_as_uint(h.point.y); r[4] = __float_as_uint(h.point.z);
+    r[5] = __float_as_uint(h.normal.x); r[6] = __float_as_uint(h.normal.y); r[7] = __float_as_uint(h.normal.z);
+    r[8] = __float_as_uint(h.u);
+    r[9] = __float_as_uint(h.v);
+    r[10] = h.backface ? 1u : 0u;
+    r[11] = h.hit ? hit_ids_of<SIMPLE>(a, h, unused).object : 0xffffffffu;
+    r[12] = (uint32_t)node_tests;
+    r[13] = (uint32_t)tri_tests;
+    r[14] = (TLAS ? 1u : 0u) | (SIMPLE ? 2u : 0u) | (STATS ? 32u : 0u) | (LDS ? 64u : 0u);
+    r[15] = 0u;
+}
+
+// simple: the SIMPLE instantiation (few-mesh scenes only: the host checks), stats: the counter instantiation
+hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const float* rd, const uint8_t* active,
+                                 unsigned long long n, bool simple, bool stats, uint32_t* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t lds = render_lds_bytes(a);
+    const uint32_t blocks = (uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
+    with_instantiation(a, simple, [&](auto lds_tag, auto tlas_tag, auto simple_tag) {
+        constexpr bool LDS = decltype(lds_tag)::value, TLAS = decltype(tlas_tag)::value, SIMPLE = decltype(simple_tag)::value;
+        if (stats) launch_k(rt_test_intersect_kernel<LDS, TLAS, SIMPLE, true>, blocks, lds, stream, a, ro, rd, active, n, out);
+        else launch_k(rt_test_intersect_kernel<LDS, TLAS, SIMPLE, false>, blocks, lds, stream, a, ro, rd, active, n, out);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_units(int fn, const float* x, const float* y, float* out, unsigned long long n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_units_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, fn, x, y, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_units_texture(const uint8_t* rgba8, uint32_t width, uint32_t height, const float* srgb_lut, const float* uv,
+                                float* out, unsigned long long n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_units_texture_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, rgba8, width, height,
+                       srgb_lut, uv, out, n);
+    return hipGetLastError();
+}

@@ -1,4 +1,4 @@
-"""Whole-frame first-hit buffers (include/rt_abi.h: rt_render_gbuffer; rt_kernel.hip: rt_gbuffer_kernel), pinned bit for bit
+"""Whole-frame first-hit buffers (include/rt_abi.h: rt_render_gbuffer; rt_queries.inl: rt_gbuffer_kernel), pinned bit for bit
 to three things that exist without it: the oracle (its debug views, which generate the rays themselves, and
 oracle.intersect on the frame's own directions), the merged ray queries (rt_intersect_rays where normalising a direction
 again leaves its bits alone, rt_pick on a sample everywhere) and the uploaded triangles and materials.  Then: channel
@@ -224,16 +224,31 @@ def test_frame_equals_oracle_queries_and_pick(rt, oracle, tracer, name):
         _set(tracer, {})
 
 
-def test_full_size_frame_against_the_oracle_depth_view(rt, oracle, tracer, cornell):
-    W, H = 1920, 1080
-    _set(tracer, {})
-    tracer.load_scene(cornell)
+def check_depth_against_the_oracle_view(rt, oracle, tracer, arrays, W, H):
+    tracer.load_scene(arrays)
     g = tracer.render_gbuffer(rt.make_params(W, H, 1, 1), ("depth", "flags"))
-    view = oracle.render(rt.make_params(W, H, 1, 1, skybox=1, frames=0, debug_flag=2, debug_scale=1), cornell)[0]
+    view = oracle.render(rt.make_params(W, H, 1, 1, skybox=1, frames=0, debug_flag=2, debug_scale=1), arrays)[0]
     hit = (g["flags"] & 1) != 0
     assert hit.mean() >= MIN_HIT_SHARE
     assert np.array_equal(view[..., 3] == 1.0, hit)
     assert np.all(same_bits(view[..., 0], g["depth"])[hit]) and np.all(np.isposinf(g["depth"][~hit]))
+
+
+def test_full_size_frame_against_the_oracle_depth_view(rt, oracle, tracer, cornell):
+    _set(tracer, {})
+    check_depth_against_the_oracle_view(rt, oracle, tracer, cornell, 1920, 1080)
+
+
+def test_deep_chain_frame_against_the_oracle_depth_view(rt, oracle, tracer, cornell):
+    """The same comparison on the chain BVH of 36 levels with wide stacks: 36 entries x 128 dwords x 4 B x 4 waves =
+    73,728 B of dynamic LDS, so the G-buffer launch opts into more than 64 KiB."""
+    from _deep_chain import deep_chain_scene
+    _set(tracer, {})
+    tracer.set_option("stack_wide", 1)
+    try:
+        check_depth_against_the_oracle_view(rt, oracle, tracer, deep_chain_scene(rt, cornell, levels=36), 64, 36)
+    finally:
+        tracer.set_option("stack_wide", -1)
 
 
 @pytest.mark.parametrize("name", ["texture_test", "sponza_hetero"])

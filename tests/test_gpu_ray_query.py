@@ -1,4 +1,4 @@
-"""The public ray queries (include/rt_abi.h: rt_intersect_rays, rt_occluded_rays, rt_pick; rt_kernel.hip: rt_query_kernel)
+"""The public ray queries (include/rt_abi.h: rt_intersect_rays, rt_occluded_rays, rt_pick; rt_queries.inl: rt_query_kernel)
 against the test library's per-ray probe (rt_test_intersect) and the oracle (oracle.intersect) bit for bit, on the ray
 families of tests/_ray_families.py; the triangle index and barycentrics against the uploaded triangles; the tmax filter;
 the occlusion contract; picking against the debug views; and that queries leave a render sequence untouched."""
@@ -155,14 +155,25 @@ def test_tmax_filter_and_occlusion(rt, tracer, name):
               f"prune_tmax differs on {int((pr != occ).sum())}")
 
 
-@pytest.mark.parametrize("name", ["cornell", "room", "texture_test"])
-def test_pick_equals_the_debug_views(rt, tracer, name):
+@pytest.mark.parametrize("name", ["cornell", "room", "texture_test", "deep_chain"])
+def test_pick_equals_the_debug_views(rt, tracer, cornell, name):
+    """"deep_chain": 36 levels with wide stacks, 73,728 B of dynamic LDS -- the launches of rt_pick's query kernel and of the
+    debug views opt into more than 64 KiB."""
     import os
+    from _deep_chain import deep_chain_scene
     from conftest import GOLDEN
     arrays = (rt.SceneArrays.load(os.path.join(GOLDEN, "texture_test_scene.npz")) if name == "texture_test"
-              else RF.scene(rt, name))
-    tracer.load_scene(arrays)
-    W, H = 24, 16
+              else deep_chain_scene(rt, cornell, levels=36) if name == "deep_chain" else RF.scene(rt, name))
+    W, H = (64, 36) if name == "deep_chain" else (24, 16)
+    tracer.set_option("stack_wide", 1 if name == "deep_chain" else -1)
+    try:
+        tracer.load_scene(arrays)
+        _pick_against_the_debug_views(rt, tracer, arrays, name, W, H)
+    finally:
+        tracer.set_option("stack_wide", -1)
+
+
+def _pick_against_the_debug_views(rt, tracer, arrays, name, W, H):
     views = {}
     for flag in (2, 1):
         tracer.render(rt.make_params(W, H, 1, 1, skybox=1, frames=0, debug_flag=flag, debug_scale=1))

@@ -47,9 +47,24 @@ int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint
                       uint32_t* out);
 
 /* Test-only: the uploaded scene's blob as the kernels read it (out may be NULL; else bytes >= its size, which
- * layout_out[9] gives), its SceneLayout (csrc/rt_device.h, 12 words) and its device address.  Waits for the launches
+ * layout_out[9] gives), its SceneLayout (csrc/rt_scene_format.h, 12 words) and its device address.  Waits for the launches
  * enqueued on the handle's streams. */
 int rt_test_scene_blob(rt_handle* h, void* out, uint64_t bytes, uint32_t layout_out[12], uint64_t* device_ptr);
+
+/* Test-only, no device and no handle: the host packer (csrc/host/scene_pack.h) on scene arrays -- both phases, as
+ * rt_upload_scene runs them -- with the five options it reads: options = {tlas, forest, flat2, tlas_min, defer_min_nodes}.
+ * Two calls, like rt_test_scene_blob: out = NULL returns the sizes (layout_out[9] = bytes of the blob); else bytes >= that
+ * and out receives the blob as the device would hold it: head, tail, zero padding.  layout_out: the SceneLayout
+ * (csrc/rt_scene_format.h, 12 words).  facts_out, RT_TEST_PACK_FACTS words: the instance phase's n_items, n_tlas_records,
+ * n_forest_entries, tlas_entries, has_tlas, has_forest, plain_materials, have_defer, defer_mesh, defer_xform,
+ * defer_internal; the geometry phase's max_height, max_leaf_ref, top_mesh_records, top_mesh_base, roots_are_unions,
+ * any_deep; and 1 when a second run of the instance phase on the same geometry facts gave the same head and layout.
+ * Returns the packer's code; error text: rt_last_error(NULL). */
+#define RT_TEST_PACK_FACTS 18
+int rt_test_pack_scene(const rt_sphere* spheres, uint32_t n_spheres, const rt_mesh_uniform* meshes, uint32_t n_meshes,
+                       const rt_packed_triangle* triangles, uint32_t n_triangles, const rt_node* nodes, uint32_t n_nodes,
+                       const int32_t options[5], void* out, uint64_t bytes, uint32_t layout_out[12],
+                       uint32_t facts_out[RT_TEST_PACK_FACTS]);
 
 /* Test-only: raw copy of a buffer of the last wavefront sequence (which: 0 path state, 1 hit records, 2 the two slot
  * lists, 3 the per-round list counts; layouts in csrc/rt_device.h), or (which = 4) the pixels parked in front of each round

@@ -134,9 +134,17 @@ QUERY_HOST_MEMORY, QUERY_PRUNE_TMAX = 1, 2
 REFIT_HOST_MEMORY = 1
 MISS = 0xFFFFFFFF
 
-# SceneLayout (csrc/rt_device.h): the 12 words rt_test_scene_blob returns; the head of the blob is [0, wide_off)
+# SceneLayout (csrc/rt_scene_format.h): the 12 words rt_test_scene_blob returns; the head of the blob is [0, wide_off)
 SCENE_LAYOUT_FIELDS = ("mesh_off", "wide_off", "tri_off", "shade_off", "mat_off", "sphere_off", "item_off", "tlas_off",
                        "forest_off", "bytes", "_pad0", "_pad1")
+
+# the fact words of rt_test_pack_scene (include/rt_test_abi.h), in order
+PACK_FACT_FIELDS = ("n_items", "n_tlas_records", "n_forest_entries", "tlas_entries", "has_tlas", "has_forest", "plain_materials",
+                    "have_defer", "defer_mesh", "defer_xform", "defer_internal", "max_height", "max_leaf_ref",
+                    "top_mesh_records", "top_mesh_base", "roots_are_unions", "any_deep", "rerun_same")
+# item kinds and record flags of the blob (csrc/rt_scene_format.h)
+ITEM_TLAS, ITEM_NEW_XFORM, ITEM_FOREST, ITEM_FLAT2, ITEM_DEFER, ITEM_DEFER_CULL, ITEM_PRUNE = 1, 2, 4, 8, 16, 32, 64
+DMESH_GLASS, DMESH_DEEP, FOREST_CULLABLE, TLAS_REF_GLASS = 2, 4, 0x100, 0x40000000
 
 RT_OK = 0
 MATERIAL_DEFAULT, MATERIAL_GLASS, MATERIAL_TEXTURE = 0, 1, 2

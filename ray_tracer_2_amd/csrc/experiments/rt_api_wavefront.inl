@@ -10,7 +10,7 @@ static int wavefront_prepare(rt_handle* h, const rt_params* params, const Render
     const uint64_t wf_slots64 = (uint64_t)wf_frame_slots * (n_batch ? n_batch : 1u);
     const uint64_t wf_rounds64 = params->number_of_bounces < 0 ? 0ull
         : (uint64_t)(params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) * ((uint64_t)params->number_of_bounces + 1ull);
-    bool wavefront = h->wavefront != 0 && a.many_mesh != 0 && !h->any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0 &&
+    bool wavefront = h->wavefront != 0 && a.many_mesh != 0 && !h->geom.any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0 &&
                      params->width <= 0xffffu && params->height <= 0xffffu && wf_slots64 < (1ull << 31) && wf_rounds64 <= 1024ull;
     const size_t wf_bytes_per_slot = (WF_STATE_PLANES + WF_HIT_PLANES) * sizeof(float4) + 2 * sizeof(uint32_t) + PIXEL_MEMO_DWORDS * sizeof(uint32_t);
     if (wavefront && h->wf_capacity < wf_slots64) {

@@ -9,17 +9,16 @@
 
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <set>
 #include <string>
 #include <vector>
 
 #include "host/bvh.h"  // (rt2::refit_select / refit_bvh: the selection rule shared with the host refit)
+#include "host/scene_pack.h"  // (the host packer: scene arrays -> blob)
 #include "rt_device.h"
 #include "rt_refit.h"
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
@@ -69,32 +68,8 @@ hipError_t diag_wave_times(unsigned long long* out);
 
 using namespace rtd;
 
-// Per-mesh facts of an uploaded scene that depend only on its triangles, nodes and offsets (rt_upload_scene's geometry
-// phase, rt_update_instances reuses them): O(meshes), no triangle or node array is kept on the host.
-struct MeshGeom {
-    uint32_t node_offset = 0, triangle_offset = 0, triangles = 0;  // as uploaded: an update must keep them
-    uint32_t wide_base = 0, internal = 0;                           // first wide record, internal nodes
-    uint32_t root_idx = 0, root_count = 0;                          // the root: record index, or triangle index + count (leaf)
-    uint32_t tri_lo = 0xffffffffu, tri_hi = 0u;                     // triangle range of the leaves
-    uint32_t node_lo = 0, node_hi = 0;                              // interval of the nodes the root reaches (a refit's selection)
-    uint32_t need = 0;                                              // stack entries of its walk
-    float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};             // the root node's box
-    bool deep = false;          // height >= 32: the shader's literal stack (DMESH_DEEP)
-    bool contains = false;      // internal root whose box provably contains its children's (finite, proper)
-    bool unions = true;         // (internal root) the root box contains the union of two proper child boxes: roots_are_unions
-    bool flat2_shape = false;   // internal, not deep, two leaf children (ITEM_FLAT2 when the scene allows it)
-    bool hierarchy_ok = false;  // not deep, and a proper bounding hierarchy (cross-mesh pruning)
-};
-struct SceneGeom {
-    std::vector<MeshGeom> mesh;
-    uint32_t n_nodes = 0, n_triangles = 0, n_wide = 0;
-    uint32_t max_height = 0, max_leaf_ref = 0;  // (largest triangle count of a leaf that can go on a stack)
-    uint32_t top_mesh_records = 0, top_mesh_base = 0;
-    bool roots_are_unions = true, any_deep = false;
-    uint64_t tail_bytes() const {
-        return (uint64_t)n_wide * WIDE_REC_BYTES + (uint64_t)n_triangles * (TRI_ISECT_BYTES + TRI_SHADE_BYTES);
-    }
-};
+// The host packer (host/scene_pack.h): the facts of an uploaded scene that the handle keeps.
+using rt2::InstanceFacts, rt2::MeshGeom, rt2::SceneGeom;
 
 // The frame layout a buffer, a table or a history was made for: the image size and the strip split.  The default (zero)
 // shape is "nothing made yet": it equals no shape a launch can have (render_impl refuses world == 0).
@@ -164,14 +139,11 @@ struct rt_handle {
     // frame batches (rt_render_frames): scratch images of the frames in flight
     float4* batch_scratch = nullptr;
     size_t batch_scratch_texels = 0;
-    // deferred walks (RenderArgs::park): the deferred mesh found at upload, the two park queues, their counters
-    bool have_defer = false;
-    uint32_t defer_mesh = 0, defer_xform = 0, defer_internal = 0;  // (internal nodes of its BVH)
+    // deferred walks (RenderArgs::park; the deferred mesh found at upload: inst.have_defer): the two park queues, their counters
 #if RT_WALK2
     float4* walk2 = nullptr;           // experiment: two-level records of the deferred mesh (rt_device.h)
     uint32_t walk2_base = 0;
 #endif
-    int defer_min_nodes = 1024;  // option "defer_min_nodes": smallest BVH (internal nodes) that is worth deferring (next upload; tests lower it)
     // option "sort_rounds": walk-and-resume rounds of a deferred-walk sequence; 0 = off, -1 (default) = automatic: by
     // the work of the launch in units of one 1920 x 1080 frame at 16 samples per pixel and the size of the big mesh
     // (render_impl; none below 8 units, or 2 for a mesh of 400 k internal nodes and more: a round has a fixed cost, its
@@ -182,7 +154,6 @@ struct rt_handle {
     // without a literal-stack mesh).  Off by default: measured slower than the inline kernels -- sponza-sized stand-in
     // 10.65 -> 11.3 ms per frame, 200-mesh stand-in 5.0 -> 7.4 (tools/experiments/README.md)
     int wavefront = 0;
-    bool any_deep = false;            // some mesh is walked with the shader's literal stack (not in the walk kernel)
     float4* wf_state = nullptr;
     float4* wf_hit = nullptr;
     uint32_t* wf_lists = nullptr;     // two lists of wf_capacity slots
@@ -268,7 +239,7 @@ struct rt_handle {
     std::vector<int> multi_comm_devices;  // the device list the communicators were made for
     std::set<int> multi_peers_enabled;
     int multi_rccl = 1;  // option "multi_rccl"
-    uint32_t top_base = 0, top_available = 0;  // breadth-first numbered top records of the biggest mesh's BVH
+    uint32_t top_available = 0;  // breadth-first numbered top records of the biggest mesh's BVH (from geom.top_mesh_base on)
     // option "lds_top": 0 off (default: measured slower), -1 what fits beside the stacks at full
     // occupancy, N records
     int lds_top = 0;
@@ -280,7 +251,6 @@ struct rt_handle {
     int lds_tlas = 0;
     int fast_miss = 1;  // option "fast_miss"
     int park_levels = 1;  // option "park_levels": the parking launches run the deferred walk's first two levels inline
-    uint32_t n_tlas_records = 0;
     float4* own_image = nullptr;  // allocated by rt_create; `image` may be rebound
     float4* multi_gathered = nullptr;  // rt_render_multi root: [world][pad_texels]
     float4* multi_frame = nullptr;     // rt_render_multi root: assembled full frame
@@ -322,13 +292,12 @@ struct rt_handle {
     float* srgb_lut = nullptr;
     // scene
     bool have_scene = false;
-    float4* blob = nullptr;  // the scene, see rt_device.h
+    float4* blob = nullptr;  // the scene, see rt_scene_format.h
     SceneGeom geom;          // the geometry phase's facts of the uploaded scene (rt_update_instances)
+    InstanceFacts inst;      // the instance phase's decisions of the last upload / update: layout, items, trees, deferred mesh
     std::vector<rt_mesh_uniform> inst_meshes;  // the instance phase's inputs of the last upload / update (rt_refit_triangles
     std::vector<rt_sphere> inst_spheres;       // reruns it)
-    SceneLayout lay{};
     bool lds_scene = false;
-    bool roots_are_unions = false;  // every internal root's box is the exact union of its children's
     int cull_roots = -1;            // option: -1 auto (many meshes), 0 off, 1 on (if provable)
     // option "cross_prune": cross-mesh pruning in the many-mesh product kernels (RenderArgs::cross_prune).  OFF by default since
     // round 5: its exactness rests on "a triangle hit at t is not found under a box entered far beyond t", which holds for
@@ -340,20 +309,14 @@ struct rt_handle {
     int force_global = 0;  // option "lds_scene" = 0 disables LDS staging (tuning / tests)
     DTexture* textures = nullptr;
     std::vector<uint8_t*> texture_data;
-    uint32_t n_meshes = 0, n_spheres = 0, n_textures = 0, n_nodes = 0, n_triangles = 0;
-    uint32_t stack_entries = 1, tlas_entries = 1, n_items = 0;
-    bool has_tlas = false;
+    uint32_t n_textures = 0;
+    uint32_t stack_entries = 1;
     bool stack_wide = false, stack_must_wide = false;
     int force_stack_wide = -1;  // option "stack_wide": -1 auto, 0 one-dword entries when legal, 1 two-dword entries
-    bool has_forest = false;
-    bool plain_materials = false;  // no spheres, no glass, no textured material (rt_upload_scene)
     int specialise = 1;            // option "specialise": 0 = always the general kernels
     int pixel_cache_opt = 1;  // option "pixel_cache"
     int vote_eighths = -1, vote_patience = -1;  // options "vote_eighths", "vote_patience" (-1: by the kind of launch, render_impl)
-    int use_tlas = 1;  // option "tlas": 0 = every mesh is a single item (takes effect at the next upload)
-    int use_forest = 1;  // option "forest": 0 = no forest items (takes effect at the next upload)
-    int use_flat2 = 1;   // option "flat2": 0 = meshes with a two-leaf BVH are not run as straight-line items (next upload)
-    int tlas_min = (int)TLAS_MIN_MESHES;  // option "tlas_min": smallest run of meshes that gets a top-level tree
+    rt2::PackOptions pack;  // options "tlas", "forest", "flat2", "tlas_min", "defer_min_nodes" (they take effect at the next upload; tests lower the last)
     rt_camera_uniform camera{};
     int count_tests = 0;
     uint32_t last_launch[4] = {0, 0, 0, 0};  // rt_last_launch (entries 4 and 5 are computed when asked)
@@ -523,45 +486,6 @@ int upload(rt_handle* h, T*& dst, const T* src, size_t n) {
     return RT_OK;
 }
 
-// Height (in edges) of the subtree under `root`, with index validation and a
-// visit budget that catches cycles.  Iterative: explicit (node, depth) stack.
-int mesh_bvh_height(const rt_node* nodes, uint32_t n_nodes, uint32_t node_offset,
-                    uint32_t tri_offset, uint32_t n_triangles, uint32_t& height, std::string& why) {
-    if (node_offset >= n_nodes) {
-        why = "mesh node_offset out of range";
-        return RT_ERR_INDEX_RANGE;
-    }
-    std::vector<std::pair<uint32_t, uint32_t>> st;
-    st.emplace_back(node_offset, 0u);
-    uint64_t visits = 0;
-    height = 0;
-    while (!st.empty()) {
-        auto [idx, depth] = st.back();
-        st.pop_back();
-        if (++visits > (uint64_t)n_nodes + 1) {
-            why = "BVH has a cycle";
-            return RT_ERR_INDEX_RANGE;
-        }
-        const rt_node& nd = nodes[idx];
-        if (depth > height) height = depth;
-        if (nd.count > 0) {
-            if ((uint64_t)tri_offset + nd.first + nd.count > n_triangles) {
-                why = "leaf triangle range out of bounds";
-                return RT_ERR_INDEX_RANGE;
-            }
-        } else {
-            uint64_t a = (uint64_t)node_offset + nd.left, b = (uint64_t)node_offset + nd.right;
-            if (a >= n_nodes || b >= n_nodes) {
-                why = "BVH child index out of range";
-                return RT_ERR_INDEX_RANGE;
-            }
-            st.emplace_back((uint32_t)a, depth + 1);
-            st.emplace_back((uint32_t)b, depth + 1);
-        }
-    }
-    return RT_OK;
-}
-
 }  // namespace
 
 namespace {
@@ -697,619 +621,24 @@ void rt_destroy(rt_handle* h) {
 
 }  // extern "C"
 
-// ---- rt_upload_scene / rt_update_instances: one upload in two phases ---------------------------------------------------
-// The blob (rt_device.h) is a head -- mesh records, materials, spheres, items, top-level trees, forest entries -- and a
-// tail from wide_off on: wide BVH records, triangle intersection records, shade records.  The tail holds record and
-// triangle indices, never byte offsets, so its bytes do not depend on where it starts.  The geometry phase builds the tail
-// and the per-mesh facts that depend only on triangles / nodes / offsets (kept on the handle: O(meshes)); the instance
-// phase builds the head from those facts and the transforms, materials and spheres.  rt_upload_scene runs both,
-// rt_update_instances only the second.
 namespace {
 
-struct WideRec { float4 q[4]; };
-
-int build_geometry(rt_handle* h, const rt_mesh_uniform* meshes, uint32_t n_meshes, const rt_packed_triangle* triangles,
-                   uint32_t n_triangles, const rt_node* nodes, uint32_t n_nodes, SceneGeom& g, std::vector<float4>& tail) {
-    // ---- validation + wide BVH records ---------------------------------
-    std::vector<WideRec> wide;
-    g.mesh.assign(n_meshes, MeshGeom{});
-    g.n_nodes = n_nodes;
-    g.n_triangles = n_triangles;
-    std::vector<uint32_t> wide_index(n_nodes, 0xffffffffu);  // per original node
-    for (uint32_t i = 0; i < n_meshes; ++i) {
-        const rt_mesh_uniform& m = meshes[i];
-        MeshGeom& mg = g.mesh[i];
-        mg.node_offset = m.node_offset;
-        mg.triangle_offset = m.triangle_offset;
-        mg.triangles = m.triangles;
-        uint32_t height = 0;
-        std::string why;
-        int rc = mesh_bvh_height(nodes, n_nodes, m.node_offset, m.triangle_offset, n_triangles, height, why);
-        if (rc != RT_OK) return fail(h, rc, "mesh " + std::to_string(i) + ": " + why);
-        // The shader's stack holds 32 entries (wgsl:297); with the near child kept in
-        // registers this kernel needs `height` entries and the shader height + 1.  A
-        // tree of height >= 32 can overflow the shader's stack; such a mesh is traversed
-        // with the shader's literal push/pop and clamped indices (DMESH_DEEP), which
-        // needs the full 32 entries.
-        mg.deep = height + 1 > RT_BVH_STACK;
-        const uint32_t need = mg.deep ? RT_BVH_STACK : height;
-        if (need > g.max_height) g.max_height = need;
-        mg.need = need;
-        // Wide records: internal nodes in DFS pre-order, indexed per mesh.
-        // (Meshes may alias node ranges; records are built per mesh.)
-        mg.wide_base = (uint32_t)wide.size();
-        mg.node_lo = mg.node_hi = m.node_offset;
-        const rt_node* mn = nodes + m.node_offset;
-        for (int k = 0; k < 3; ++k) { mg.box_lo[k] = mn[0].aabb_min[k]; mg.box_hi[k] = mn[0].aabb_max[k]; }
-        // (child and root indices are absolute: triangle index into the scene's triangle
-        // array, wide-record index into the scene's record array)
-        if (mn[0].count > 0) {
-            mg.root_idx = m.triangle_offset + mn[0].first;
-            mg.root_count = mn[0].count;
-            mg.tri_lo = mg.root_idx;
-            mg.tri_hi = mg.root_idx + mg.root_count;
-            continue;
-        }
-        mg.root_idx = mg.wide_base;
-        mg.root_count = 0;
-        // Record order: the first TOP_BFS internal nodes breadth-first from the root (any prefix of
-        // them is a "top of the tree": what the render kernels stage into LDS for a big mesh), the
-        // rest in depth-first pre-order below them.
-        std::vector<uint32_t> order;  // original mesh-local indices of internal nodes
-        std::vector<uint32_t> frontier{0u}, st;
-        constexpr size_t TOP_BFS = 2048;
-        for (size_t q = 0; q < frontier.size(); ++q) {
-            const uint32_t n = frontier[q];
-            if (order.size() >= TOP_BFS) { st.push_back(n); continue; }
-            wide_index[m.node_offset + n] = (uint32_t)order.size();
-            order.push_back(n);
-            if (mn[mn[n].left].count == 0) frontier.push_back(mn[n].left);
-            if (mn[mn[n].right].count == 0) frontier.push_back(mn[n].right);
-        }
-        std::reverse(st.begin(), st.end());  // (pop order = breadth-first order of the cut)
-        while (!st.empty()) {
-            uint32_t n = st.back();
-            st.pop_back();
-            wide_index[m.node_offset + n] = (uint32_t)order.size();
-            order.push_back(n);
-            if (mn[mn[n].right].count == 0) st.push_back(mn[n].right);
-            if (mn[mn[n].left].count == 0) st.push_back(mn[n].left);
-        }
-        if (order.size() > g.top_mesh_records) {  // the biggest BVH gets the LDS-staged top
-            g.top_mesh_records = (uint32_t)order.size();
-            g.top_mesh_base = mg.wide_base;
-        }
-        for (uint32_t n : order) {
-            mg.node_hi = std::max({mg.node_hi, m.node_offset + mn[n].left, m.node_offset + mn[n].right});
-            const rt_node &ca = mn[mn[n].left], &cb = mn[mn[n].right];
-            auto kind = [&](const rt_node& c, uint32_t local, uint32_t& idx, uint32_t& cnt) {
-                if (c.count > 0) {
-                    idx = m.triangle_offset + c.first;
-                    cnt = c.count;
-                    if (cnt > g.max_leaf_ref) g.max_leaf_ref = cnt;
-                    mg.tri_lo = std::min(mg.tri_lo, idx);
-                    mg.tri_hi = std::max(mg.tri_hi, idx + cnt);
-                } else {
-                    idx = mg.wide_base + wide_index[m.node_offset + local];
-                    cnt = 0;
-                }
-            };
-            uint32_t ai, ac, bi, bc;
-            kind(ca, mn[n].left, ai, ac);
-            kind(cb, mn[n].right, bi, bc);
-            auto asf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-            WideRec w;
-            w.q[0] = make_float4(ca.aabb_min[0], ca.aabb_max[0], ca.aabb_min[1], ca.aabb_max[1]);
-            w.q[1] = make_float4(ca.aabb_min[2], ca.aabb_max[2], asf(ai), asf(ac));
-            w.q[2] = make_float4(cb.aabb_min[0], cb.aabb_max[0], cb.aabb_min[1], cb.aabb_max[1]);
-            w.q[3] = make_float4(cb.aabb_min[2], cb.aabb_max[2], asf(bi), asf(bc));
-            wide.push_back(w);
-        }
-    }
-    g.n_wide = (uint32_t)wide.size();
-    for (uint32_t i = 0; i < n_meshes; ++i) {
-        MeshGeom& mg = g.mesh[i];
-        mg.internal = (i + 1 < n_meshes ? g.mesh[i + 1].wide_base : g.n_wide) - mg.wide_base;
-        const rt_node* mn = nodes + meshes[i].node_offset;
-        g.any_deep = g.any_deep || mg.deep;
-        // (the root box provably contains its children's boxes -- root_box_ok below adds "walked with the ordinary
-        // stack"; the root-box shortcut, roots_are_unions, needs the same containment of proper child boxes)
-        if (mn[0].count == 0) {
-            const rt_node &ca = mn[mn[0].left], &cb = mn[mn[0].right];
-            bool contains = true, unions = true;
-            for (int k = 0; k < 3; ++k) {
-                const float lo_k = ca.aabb_min[k] < cb.aabb_min[k] ? ca.aabb_min[k] : cb.aabb_min[k];
-                const float hi_k = ca.aabb_max[k] > cb.aabb_max[k] ? ca.aabb_max[k] : cb.aabb_max[k];
-                // the root box may also be larger than the union (still conservative)
-                if (!(mn[0].aabb_min[k] <= lo_k && mn[0].aabb_max[k] >= hi_k)) contains = unions = false;
-                // (and the children must be proper boxes, or the interval argument does not hold)
-                if (!(ca.aabb_min[k] <= ca.aabb_max[k] && cb.aabb_min[k] <= cb.aabb_max[k])) contains = unions = false;
-                if (!(mn[0].aabb_min[k] - mn[0].aabb_min[k] == 0.0f && mn[0].aabb_max[k] - mn[0].aabb_max[k] == 0.0f)) contains = false;  // finite
-            }
-            mg.contains = contains;
-            mg.unions = unions;
-            if (!unions) g.roots_are_unions = false;
-            // (root with two leaf children: a straight-line item in the few-mesh kernels, ITEM_FLAT2)
-            mg.flat2_shape = !mg.deep && ca.count > 0 && cb.count > 0;
-        }
-        // A proper bounding hierarchy (cross-mesh pruning, build_instances): finite boxes, every child box inside its
-        // parent's, every leaf triangle inside its leaf's box (true of the reference's builder; verified, since BVHs may
-        // be foreign).  Only asked of meshes walked with the ordinary stack.
-        if (!mg.deep) {
-            auto finite_box = [](const rt_node& n) {
-                for (int k = 0; k < 3; ++k)
-                    if (!(n.aabb_min[k] <= n.aabb_max[k] && n.aabb_min[k] - n.aabb_min[k] == 0.0f && n.aabb_max[k] - n.aabb_max[k] == 0.0f)) return false;
-                return true;
-            };
-            auto hierarchy_ok = [&]() {
-                std::vector<uint32_t> st{0u};
-                while (!st.empty()) {
-                    const rt_node& n = mn[st.back()];
-                    st.pop_back();
-                    if (!finite_box(n)) return false;
-                    if (n.count > 0) {
-                        for (uint32_t t = 0; t < n.count; ++t) {
-                            const rt_packed_triangle& p = triangles[meshes[i].triangle_offset + n.first + t];
-                            for (const float* v : {p.v1, p.v2, p.v3})
-                                for (int k = 0; k < 3; ++k)
-                                    if (!(v[k] >= n.aabb_min[k] && v[k] <= n.aabb_max[k])) return false;
-                        }
-                    } else {
-                        for (uint32_t c : {n.left, n.right}) {
-                            const rt_node& ch = mn[c];
-                            for (int k = 0; k < 3; ++k)
-                                if (!(ch.aabb_min[k] >= n.aabb_min[k] && ch.aabb_max[k] <= n.aabb_max[k])) return false;
-                            st.push_back(c);
-                        }
-                    }
-                }
-                return true;
-            };
-            mg.hierarchy_ok = hierarchy_ok();
-        }
-    }
-    // ---- the tail: wide records, then the triangle re-layout (see rt_device.h) ----
-    const uint64_t tail_bytes = g.tail_bytes();
-    if (tail_bytes > 0xfffffff0ull) return fail(h, RT_ERR_CAPACITY, "scene larger than 4 GiB");
-    tail.assign(tail_bytes / 16, make_float4(0, 0, 0, 0));
-    if (!wide.empty()) memcpy(tail.data(), wide.data(), wide.size() * sizeof(WideRec));
-    const size_t tri_off = (size_t)g.n_wide * WIDE_REC_BYTES, shade_off = tri_off + (size_t)n_triangles * TRI_ISECT_BYTES;
-    // The subtractions and the cross product are wgsl:261-263, evaluated once here in binary32.
-    for (uint32_t t = 0; t < n_triangles; ++t) {
-        const rt_packed_triangle& p = triangles[t];
-        float abx = p.v2[0] - p.v1[0], aby = p.v2[1] - p.v1[1], abz = p.v2[2] - p.v1[2];
-        float acx = p.v3[0] - p.v1[0], acy = p.v3[1] - p.v1[1], acz = p.v3[2] - p.v1[2];
-        float nx = aby * acz - abz * acy;
-        float ny = abz * acx - abx * acz;
-        float nz = abx * acy - aby * acx;
-        float4* ti = tail.data() + (tri_off + (size_t)t * TRI_ISECT_BYTES) / 16;
-        ti[0] = make_float4(p.v1[0], p.v1[1], p.v1[2], nx);
-        ti[1] = make_float4(abx, aby, abz, ny);
-        ti[2] = make_float4(acx, acy, acz, nz);
-        float4* ts = tail.data() + (shade_off + (size_t)t * TRI_SHADE_BYTES) / 16;
-        ts[0] = make_float4(p.n1[0], p.n1[1], p.n1[2], p.uv10);
-        ts[1] = make_float4(p.n2[0], p.n2[1], p.n2[2], p.uv11);
-        ts[2] = make_float4(p.n3[0], p.n3[1], p.n3[2], p.uv20);
-        ts[3] = make_float4(p.uv21, p.uv30, p.uv31, 0.0f);
-    }
-    return RT_OK;
-}
-
-// What the instance phase decides: the head of the blob and the handle state that goes with it.
-struct SceneInstances {
-    SceneLayout lay{};
-    std::vector<float4> head;  // [0, lay.wide_off)
-    uint32_t n_items = 0, n_tlas_records = 0, n_forest_entries = 0, tlas_entries = 1;
-    bool has_tlas = false, has_forest = false, plain_materials = false;
-    bool have_defer = false;
-    uint32_t defer_mesh = 0, defer_xform = 0, defer_internal = 0;
-};
-
-int build_instances(rt_handle* h, const SceneGeom& g, const rt_sphere* spheres, uint32_t n_spheres,
-                    const rt_mesh_uniform* meshes, uint32_t n_meshes, SceneInstances& out) {
-    const std::vector<MeshGeom>& mg = g.mesh;
-    // ---- mesh-loop items and top-level trees -------------------------------------
-    // Runs of consecutive meshes with bit-identical world_to_model share a local space.
-    // Within a run, meshes with an internal, non-deep root whose box provably contains its
-    // children's go under a TLAS when there are enough of them; every other mesh is a
-    // single item.  (Visit order is free: rt_kernel.hip breaks distance ties by mesh index.)
-    struct Item { uint32_t kind, a, b, n; };
-    std::vector<Item> items;
-    std::vector<WideRec> tlas;
-    struct ForestEntry { float4 q[3]; };
-    std::vector<ForestEntry> forest_entries;
-    uint32_t tlas_depth = 0;
-    // (root_box_ok: the root box provably contains its children's boxes and the mesh is walked with the ordinary stack)
-    auto root_box_ok = [&](uint32_t i) { return !mg[i].deep && mg[i].contains; };
-    // (a tree's reference to a mesh has 9 bits for the mesh and 21 for its root record, rt_device.h)
-    auto tree_ok = [&](uint32_t i) { return root_box_ok(i) && i <= TLAS_REF_MESH_MASK && mg[i].root_idx <= TLAS_REF_ROOT_MASK; };
-    struct Box { float lo[3], hi[3]; };
-    auto asf2 = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-    // recursive split over the root boxes; returns the child reference (idx, count)
-    uint32_t tlas_max_depth = 0;  // set per tree: depth of the balanced tree + 6
-    auto ceil_log2 = [](size_t n) { uint32_t d = 0; while (((size_t)1 << d) < n) ++d; return d; };
-    std::function<void(std::vector<uint32_t>&, size_t, size_t, uint32_t, uint32_t&, uint32_t&, Box&)> build_tlas =
-        [&](std::vector<uint32_t>& ms, size_t b0, size_t e0, uint32_t depth, uint32_t& idx, uint32_t& cnt, Box& box) {
-            if (depth > tlas_depth) tlas_depth = depth;
-            if (e0 - b0 == 1) {
-                const MeshGeom& r = mg[ms[b0]];
-                for (int k = 0; k < 3; ++k) { box.lo[k] = r.box_lo[k]; box.hi[k] = r.box_hi[k]; }
-                idx = r.root_idx | (ms[b0] << TLAS_REF_MESH_SHIFT) |
-                      (meshes[ms[b0]].material.flag == RT_MATERIAL_GLASS ? TLAS_REF_GLASS : 0u);
-                cnt = 1;
-                return;
-            }
-            // Split: surface-area heuristic over the root boxes, swept along each axis in centroid order (the
-            // boxes are few -- one per mesh -- so the full sweep is affordable; a median split put the scene-wide
-            // floor and ceiling meshes of the many-mesh stand-in into the same subtrees as the columns next to
-            // their centroids).  Any split is a correct one: the tree only has to contain its root boxes.
-            auto centroid_less = [&](int axis) {
-                return [&, axis](uint32_t x, uint32_t y) {
-                    const MeshGeom &rx = mg[x], &ry = mg[y];
-                    const float cx = rx.box_lo[axis] + rx.box_hi[axis], cy = ry.box_lo[axis] + ry.box_hi[axis];
-                    return cx < cy || (cx == cy && x < y);
-                };
-            };
-            auto half_area = [](const double* lo3, const double* hi3) {
-                const double dx = hi3[0] - lo3[0], dy = hi3[1] - lo3[1], dz = hi3[2] - lo3[2];
-                return dx * dy + dy * dz + dz * dx;
-            };
-            const size_t cnt_here = e0 - b0;
-            int best_axis = 0;
-            size_t best_left = cnt_here / 2;
-            double best_cost = DBL_MAX;
-            std::vector<double> right_area(cnt_here);
-            for (int axis = 0; axis < 3; ++axis) {
-                std::sort(ms.begin() + b0, ms.begin() + e0, centroid_less(axis));
-                double lo3[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi3[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-                for (size_t q = cnt_here; q-- > 1;) {  // right_area[q]: boxes q .. end
-                    const MeshGeom& r = mg[ms[b0 + q]];
-                    for (int k = 0; k < 3; ++k) {
-                        if (r.box_lo[k] < lo3[k]) lo3[k] = r.box_lo[k];
-                        if (r.box_hi[k] > hi3[k]) hi3[k] = r.box_hi[k];
-                    }
-                    right_area[q] = half_area(lo3, hi3);
-                }
-                for (int k = 0; k < 3; ++k) { lo3[k] = DBL_MAX; hi3[k] = -DBL_MAX; }
-                for (size_t q = 1; q < cnt_here; ++q) {  // left = boxes 0 .. q-1
-                    const MeshGeom& r = mg[ms[b0 + q - 1]];
-                    for (int k = 0; k < 3; ++k) {
-                        if (r.box_lo[k] < lo3[k]) lo3[k] = r.box_lo[k];
-                        if (r.box_hi[k] > hi3[k]) hi3[k] = r.box_hi[k];
-                    }
-                    const double cost = half_area(lo3, hi3) * (double)q + right_area[q] * (double)(cnt_here - q);
-                    if (cost < best_cost) { best_cost = cost; best_axis = axis; best_left = q; }
-                }
-            }
-            // (every lane keeps a tree stack of depth + 2 entries in LDS: a subtree that would not fit below the
-            // depth limit any other way is split in the middle)
-            if (depth + ceil_log2(cnt_here) >= tlas_max_depth) best_left = cnt_here / 2;
-            std::sort(ms.begin() + b0, ms.begin() + e0, centroid_less(best_axis));
-            const size_t mid = b0 + best_left;
-            const uint32_t me = (uint32_t)tlas.size();
-            tlas.emplace_back();
-            uint32_t ai, ac, bi, bc;
-            Box ba, bb;
-            build_tlas(ms, b0, mid, depth + 1, ai, ac, ba);
-            build_tlas(ms, mid, e0, depth + 1, bi, bc, bb);
-            WideRec w;
-            w.q[0] = make_float4(ba.lo[0], ba.hi[0], ba.lo[1], ba.hi[1]);
-            w.q[1] = make_float4(ba.lo[2], ba.hi[2], asf2(ai), asf2(ac));
-            w.q[2] = make_float4(bb.lo[0], bb.hi[0], bb.lo[1], bb.hi[1]);
-            w.q[3] = make_float4(bb.lo[2], bb.hi[2], asf2(bi), asf2(bc));
-            tlas[me] = w;
-            for (int k = 0; k < 3; ++k) {  // exact union (min/max are exact)
-                box.lo[k] = ba.lo[k] < bb.lo[k] ? ba.lo[k] : bb.lo[k];
-                box.hi[k] = ba.hi[k] > bb.hi[k] ? ba.hi[k] : bb.hi[k];
-            }
-            idx = me;
-            cnt = 0;
-        };
-    // Forest items are walked by the few-mesh kernels only: none when the scene gets a top-level
-    // tree anywhere or has enough meshes for automatic root-box culling (many-mesh kernels).
-    bool any_tlas = false;
-    if (h->use_tlas)
-        for (uint32_t i0 = 0; i0 < n_meshes;) {
-            uint32_t i1 = i0 + 1, ok = 0;
-            while (i1 < n_meshes && memcmp(meshes[i1].world_to_model, meshes[i0].world_to_model, 64) == 0) ++i1;
-            for (uint32_t i = i0; i < i1; ++i) ok += tree_ok(i) ? 1u : 0u;
-            if (ok >= (uint32_t)h->tlas_min) any_tlas = true;
-            i0 = i1;
-        }
-    const bool allow_forest = h->use_forest && !any_tlas && n_meshes < 16;
-    // meshes whose root has two leaf children run as straight-line code in the few-mesh kernels (ITEM_FLAT2)
-    auto is_flat2 = [&](uint32_t i) { return h->use_flat2 && !any_tlas && n_meshes < 16 && mg[i].flat2_shape; };
-    for (uint32_t i0 = 0; i0 < n_meshes;) {
-        uint32_t i1 = i0 + 1;
-        while (i1 < n_meshes && memcmp(meshes[i1].world_to_model, meshes[i0].world_to_model, 64) == 0) ++i1;
-        std::vector<uint32_t> grouped;
-        if (h->use_tlas)
-            for (uint32_t i = i0; i < i1; ++i)
-                if (tree_ok(i)) grouped.push_back(i);
-        if (grouped.size() < (size_t)h->tlas_min) grouped.clear();
-        // the other meshes of the run with an internal, non-deep root (and the run's
-        // model_to_world as well) form a forest when there are at least two of them
-        std::vector<uint32_t> forest;
-        if (allow_forest) {
-            size_t g2 = 0;
-            for (uint32_t i = i0; i < i1; ++i) {
-                if (g2 < grouped.size() && grouped[g2] == i) { ++g2; continue; }
-                if (mg[i].root_count == 0 && !mg[i].deep && !is_flat2(i) && memcmp(meshes[i].model_to_world, meshes[i0].model_to_world, 64) == 0)
-                    forest.push_back(i);
-            }
-            if (forest.size() < 2) forest.clear();
-        }
-        bool first = true;
-        auto flag = [&]() { uint32_t f = first ? ITEM_NEW_XFORM : 0u; first = false; return f; };
-        size_t g2 = 0, fo = 0;
-        for (uint32_t i = i0; i < i1; ++i) {
-            if (g2 < grouped.size() && grouped[g2] == i) { ++g2; continue; }
-            if (fo < forest.size() && forest[fo] == i) { ++fo; continue; }
-            items.push_back(Item{flag() | (is_flat2(i) ? ITEM_FLAT2 : 0u), i, i0, 1});
-        }
-        for (size_t f0 = 0; f0 < forest.size(); f0 += FOREST_MAX_MEMBERS) {
-            const size_t f1 = std::min(forest.size(), f0 + (size_t)FOREST_MAX_MEMBERS);
-            items.push_back(Item{ITEM_FOREST | flag(), (uint32_t)forest_entries.size(), i0, (uint32_t)(f1 - f0)});
-            for (size_t f = f0; f < f1; ++f) {
-                const uint32_t i = forest[f];
-                const MeshGeom& r = mg[i];
-                ForestEntry e;
-                uint32_t fl = (meshes[i].material.flag == RT_MATERIAL_GLASS ? DMESH_GLASS : 0u) |
-                              (root_box_ok(i) ? FOREST_CULLABLE : 0u);
-                e.q[0] = make_float4(asf2(r.root_idx), asf2(i), asf2(fl), 0.0f);
-                e.q[1] = make_float4(r.box_lo[0], r.box_hi[0], r.box_lo[1], r.box_hi[1]);
-                e.q[2] = make_float4(r.box_lo[2], r.box_hi[2], 0.0f, 0.0f);
-                forest_entries.push_back(e);
-            }
-        }
-        if (!grouped.empty()) {
-            std::vector<uint32_t> ms = grouped;
-            uint32_t ridx, rcnt;
-            Box rb;
-            tlas_max_depth = 1 + ceil_log2(ms.size()) + 6;
-            build_tlas(ms, 0, ms.size(), 1, ridx, rcnt, rb);
-            items.push_back(Item{ITEM_TLAS | flag(), ridx, i0, (uint32_t)grouped.size()});
-        }
-        i0 = i1;
-    }
-    // Number the tree records breadth-first from the roots (all trees together): any prefix of the array is then
-    // "the top levels", which is what option "lds_tlas" stages into LDS when the whole tree does not fit.
-    if (!tlas.empty()) {
-        std::vector<uint32_t> order, new_of(tlas.size(), 0xffffffffu);
-        auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-        for (const Item& it : items)
-            if (it.kind & ITEM_TLAS) order.push_back(it.a);
-        for (size_t q = 0; q < order.size(); ++q) {
-            const WideRec& w = tlas[order[q]];
-            if (bits(w.q[1].w) == 0u) order.push_back(bits(w.q[1].z));  // child a is a tree node
-            if (bits(w.q[3].w) == 0u) order.push_back(bits(w.q[3].z));
-        }
-        if (order.size() == tlas.size()) {
-            for (size_t q = 0; q < order.size(); ++q) new_of[order[q]] = (uint32_t)q;
-            std::vector<WideRec> re(tlas.size());
-            for (size_t q = 0; q < order.size(); ++q) {
-                WideRec w = tlas[order[q]];
-                if (bits(w.q[1].w) == 0u) w.q[1].z = asf2(new_of[bits(w.q[1].z)]);
-                if (bits(w.q[3].w) == 0u) w.q[3].z = asf2(new_of[bits(w.q[3].z)]);
-                re[q] = w;
-            }
-            tlas.swap(re);
-            for (Item& it : items)
-                if (it.kind & ITEM_TLAS) it.a = new_of[it.a];
-        }
-    }
-    // ---- cross-mesh pruning (RenderArgs::cross_prune): which items may be cut, and the order of the loop ----
-    // An item gets ITEM_PRUNE when every mesh of it (a) has the model_to_world of the mesh that gives the item's
-    // local ray, bit for bit -- the kernel's bound on the world distance is derived from that matrix --, (b) is
-    // not glass (no backface culling: a ray leaving a surface is not culled against the coplanar triangles next
-    // to it, the one place where the triangle test's parameter is noise), (c) is walked with
-    // the ordinary stack, and (d) has a BVH that is a proper bounding hierarchy (MeshGeom::hierarchy_ok).
-    auto mesh_prune_ok = [&](uint32_t i, uint32_t xform_mesh) {
-        return !mg[i].deep && meshes[i].material.flag != RT_MATERIAL_GLASS && mg[i].hierarchy_ok &&
-               memcmp(meshes[i].model_to_world, meshes[xform_mesh].model_to_world, 64) == 0;
-    };
-    if (any_tlas || n_meshes >= 16) {  // (the scenes the many-mesh kernels render)
-        // members of a tree, per tree item (the trees are not renumbered again below)
-        auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-        for (Item& it : items) {
-            bool ok = true;
-            if (it.kind & ITEM_TLAS) {
-                std::vector<uint32_t> st{it.a};
-                while (!st.empty() && ok) {
-                    const WideRec w = tlas[st.back()];
-                    st.pop_back();
-                    for (int c = 0; c < 2 && ok; ++c) {
-                        const uint32_t idx = bits(w.q[2 * c + 1].z), cnt = bits(w.q[2 * c + 1].w);
-                        if (cnt == 0u) st.push_back(idx);
-                        else ok = mesh_prune_ok((idx >> TLAS_REF_MESH_SHIFT) & TLAS_REF_MESH_MASK, it.b);
-                    }
-                }
-            } else if (it.kind & ITEM_FOREST) {
-                ok = false;  // (few-mesh kernels only)
-            } else {
-                ok = mg[it.a].root_count == 0u && mesh_prune_ok(it.a, it.b);
-            }
-            if (ok) it.kind |= ITEM_PRUNE;
-        }
-        // The loop's order is free (ties between equal world distances go to the lower mesh index, rt_kernel.hip):
-        // first the meshes whose root is a leaf (the whole wave tests their triangles in step), then the other
-        // single meshes, then the trees, so that the long walks start with a closest hit to prune against.  Inside
-        // a class the order stays; an item opens its local space when its class's previous item had another one.
-        std::vector<Item> ordered;
-        for (int cls = 0; cls < 3; ++cls) {
-            bool first = true;
-            uint32_t prev_b = 0;
-            for (const Item& it0 : items) {
-                const int c = (it0.kind & ITEM_TLAS) ? 2 : ((it0.kind & ITEM_FOREST) || mg[it0.a].root_count == 0u) ? 1 : 0;
-                if (c != cls) continue;
-                Item it = it0;
-                it.kind &= ~(uint32_t)ITEM_NEW_XFORM;
-                if (first || it.b != prev_b) it.kind |= ITEM_NEW_XFORM;
-                first = false;
-                prev_b = it.b;
-                ordered.push_back(it);
-            }
-        }
-        // (classes follow each other: the first item of a class whose local space is the previous class's last one
-        // need not open it again)
-        for (size_t k = 1; k < ordered.size(); ++k)
-            if (ordered[k].b == ordered[k - 1].b) ordered[k].kind &= ~(uint32_t)ITEM_NEW_XFORM;
-        items.swap(ordered);
-    }
-    // (one entry is always there: the many-mesh kernels, which the debug views use too,
-    // run single meshes through the same stack)
-    out.tlas_entries = tlas.empty() ? 1u : tlas_depth + 2u;
-    out.has_tlas = !tlas.empty();
-
-    // ---- the deferred mesh (RenderArgs::park) ----------------------------------------------
-    // The biggest single-mesh item of a few-mesh scene with a real BVH:
-    // its item goes to the end of the mesh loop (the loop's order is free), where a launch can stop in front
-    // of it.
-    out.have_defer = false;
-    if (!any_tlas && n_meshes < 16) {
-        size_t best_k = items.size();
-        uint32_t best_big = 0;
-        for (size_t k = 0; k < items.size(); ++k) {
-            const Item& it = items[k];
-            if (it.kind & (ITEM_TLAS | ITEM_FOREST | ITEM_FLAT2)) continue;
-            const uint32_t mi = it.a;
-            if (mg[mi].root_count != 0) continue;
-            const uint32_t internal = mg[mi].internal;
-            if (internal >= (uint32_t)h->defer_min_nodes && internal > best_big) { best_big = internal; best_k = k; }
-        }
-        if (best_k < items.size()) {
-            Item d = items[best_k];
-            items.erase(items.begin() + (std::ptrdiff_t)best_k);
-            // (the item that followed it in the same local space now opens that space)
-            if ((d.kind & ITEM_NEW_XFORM) && best_k < items.size() && !(items[best_k].kind & ITEM_NEW_XFORM)) items[best_k].kind |= ITEM_NEW_XFORM;
-            d.kind |= ITEM_NEW_XFORM | ITEM_DEFER | (mg[d.a].contains ? ITEM_DEFER_CULL : 0u);
-            items.push_back(d);
-            out.have_defer = true;
-            out.defer_mesh = d.a;
-            out.defer_xform = d.b;
-            out.defer_internal = best_big;
-        }
-    }
-
-    // ---- blob layout ------------------------------------------------------
-    SceneLayout lay{};
-    uint64_t off = 0;
-    // (the per-scene sections first, the per-node / per-triangle arrays last: the small blob of the hybrid launches has
-    // the same sections with shorter arrays, so every offset up to wide_off is the same in both -- the primary-ray memo
-    // keeps a material's byte offset across launches that read different blobs)
-    lay.mesh_off = (uint32_t)off;   off += (uint64_t)n_meshes * MESH_REC_BYTES;
-    lay.mat_off = (uint32_t)off;    off += (uint64_t)(n_meshes + n_spheres) * MATERIAL_BYTES;
-    lay.sphere_off = (uint32_t)off; off += (uint64_t)n_spheres * SPHERE_BYTES;
-    lay.item_off = (uint32_t)off;   off += (uint64_t)items.size() * ITEM_BYTES;
-    lay.tlas_off = (uint32_t)off;   off += (uint64_t)tlas.size() * WIDE_REC_BYTES;
-    lay.forest_off = (uint32_t)off; off += (uint64_t)forest_entries.size() * FOREST_ENTRY_BYTES;
-    lay.wide_off = (uint32_t)off;   off += (uint64_t)g.n_wide * WIDE_REC_BYTES;
-    lay.tri_off = (uint32_t)off;    off += (uint64_t)g.n_triangles * TRI_ISECT_BYTES;
-    lay.shade_off = (uint32_t)off;  off += (uint64_t)g.n_triangles * TRI_SHADE_BYTES;
-    if (off == 0) off = 16;
-    if (off > 0xfffffff0ull) return fail(h, RT_ERR_CAPACITY, "scene larger than 4 GiB");
-    lay.bytes = (uint32_t)off;
-    std::vector<float4>& head = out.head;
-    head.assign(lay.wide_off / 16, make_float4(0, 0, 0, 0));
-    auto asf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-    for (uint32_t i = 0; i < n_meshes; ++i) {
-        const rt_mesh_uniform& m = meshes[i];
-        float4* r = head.data() + (lay.mesh_off + (size_t)i * MESH_REC_BYTES) / 16;
-        memcpy(r, m.world_to_model, 64);
-        memcpy(r + 4, m.model_to_world, 64);
-        uint32_t flags = 0;
-        if (m.material.flag == RT_MATERIAL_GLASS) flags |= DMESH_GLASS;
-        if (mg[i].deep) flags |= DMESH_DEEP;
-        r[8] = make_float4(asf(flags), asf(mg[i].root_idx), asf(mg[i].root_count), asf(m.triangle_offset));
-        {
-            // S >= the largest absolute row sum of model_to_world's 3 x 3 part ([col][row]), C >= the largest
-            // absolute translation component: in double, then rounded up (cross-mesh pruning's error terms)
-            double S = 0.0, C = 0.0;
-            for (int row = 0; row < 3; ++row) {
-                const double rs = std::fabs((double)m.model_to_world[0][row]) + std::fabs((double)m.model_to_world[1][row]) +
-                                  std::fabs((double)m.model_to_world[2][row]);
-                if (!(rs <= S)) S = rs;  // (NaN sticks)
-                const double tc = std::fabs((double)m.model_to_world[3][row]);
-                if (!(tc <= C)) C = tc;
-            }
-            auto up = [](double d) { float f = (float)d; if ((double)f < d) f = std::nextafter(f, INFINITY); return f; };
-            r[9] = make_float4(asf(mg[i].wide_base), up(S), up(C), 0.0f);
-        }
-        r[10] = make_float4(mg[i].box_lo[0], mg[i].box_hi[0], mg[i].box_lo[1], mg[i].box_hi[1]);
-        r[11] = make_float4(mg[i].box_lo[2], mg[i].box_hi[2], 0.0f, 0.0f);
-        memcpy(head.data() + (lay.mat_off + (size_t)i * MATERIAL_BYTES) / 16, &m.material, MATERIAL_BYTES);
-    }
-    if (!tlas.empty()) memcpy(head.data() + lay.tlas_off / 16, tlas.data(), tlas.size() * sizeof(WideRec));
-    if (!forest_entries.empty())
-        memcpy(head.data() + lay.forest_off / 16, forest_entries.data(), forest_entries.size() * sizeof(ForestEntry));
-    for (size_t k = 0; k < items.size(); ++k) {
-        const Item& it = items[k];
-        const bool single = (it.kind & (ITEM_TLAS | ITEM_FOREST)) == 0;
-        head[lay.item_off / 16 + 2 * k] = make_float4(asf(it.kind), asf(it.a), asf(it.b), asf(single ? mg[it.a].wide_base : it.n));
-        if (single) head[lay.item_off / 16 + 2 * k + 1] = head[(lay.mesh_off + (size_t)it.a * MESH_REC_BYTES) / 16 + 8];
-    }
-    for (uint32_t i = 0; i < n_spheres; ++i) {
-        head[(lay.sphere_off + (size_t)i * SPHERE_BYTES) / 16] =
-            make_float4(spheres[i].pos[0], spheres[i].pos[1], spheres[i].pos[2], spheres[i].radius);
-        memcpy(head.data() + (lay.mat_off + (size_t)(n_meshes + i) * MATERIAL_BYTES) / 16,
-               &spheres[i].material, MATERIAL_BYTES);
-    }
-    out.lay = lay;
-    out.n_items = (uint32_t)items.size();
-    out.n_tlas_records = (uint32_t)tlas.size();
-    out.n_forest_entries = (uint32_t)forest_entries.size();
-    out.has_forest = !forest_entries.empty();
-    {
-        bool plain = n_spheres == 0;
-        for (uint32_t i = 0; i < n_meshes && plain; ++i) {
-            const rt_material& m = meshes[i].material;
-            if (m.flag == RT_MATERIAL_GLASS || (m.flag == RT_MATERIAL_TEXTURE && m.diffuse_index != -1)) plain = false;
-        }
-        out.plain_materials = plain;
-    }
-    return RT_OK;
-}
-
-// The handle state of an uploaded scene (after its blob is on the device): the geometry facts and the instance phase's
-// decisions, then the kernel shape that follows from the layout.
-void commit_scene(rt_handle* h, const SceneGeom& g, const SceneInstances& s, uint32_t n_spheres, const rt_camera_uniform& camera) {
-    const SceneLayout& lay = s.lay;
-    h->roots_are_unions = g.roots_are_unions;
-    h->lay = lay;
-    h->n_meshes = (uint32_t)g.mesh.size();
-    h->n_spheres = n_spheres;
-    h->n_nodes = g.n_nodes;
-    h->n_triangles = g.n_triangles;
+// The handle state of an uploaded scene, after its blob is on the device and h->geom / h->inst hold its facts: what
+// follows from the layout and the kernels' LDS map.
+void commit_scene(rt_handle* h, const rt_camera_uniform& camera) {
+    const SceneGeom& g = h->geom;
+    const InstanceFacts& s = h->inst;
     h->stack_entries = g.max_height ? g.max_height : 1;
     // One-dword stack entries hold 7 bits of leaf count and 24 bits of triangle index; they cost
     // a few instructions per push/pop, so they are used when they buy occupancy: when two-dword
     // entries would not leave room for the scene blob and the primary-ray memo in LDS.
-    {
-        const uint64_t fixed = 8u * 3u * 4u * WAVES_PER_BLOCK + (uint64_t)(LANE_STATE_DWORDS + PIXEL_MEMO_DWORDS) * 64u * 4u * WAVES_PER_BLOCK +
-                               (uint64_t)s.tlas_entries * 64u * 4u * WAVES_PER_BLOCK;
-        const uint64_t wide_stacks = (uint64_t)h->stack_entries * 128u * 4u * WAVES_PER_BLOCK;
-        const bool wide_fits = lay.bytes + fixed + wide_stacks <= LDS_BUDGET_BYTES;
-        h->stack_must_wide = g.max_leaf_ref > 127u || g.n_triangles > (1u << 24);
-        h->stack_wide = h->stack_must_wide || wide_fits;
-    }
-    h->tlas_entries = s.tlas_entries;
-    h->has_tlas = s.has_tlas;
-    h->n_tlas_records = s.n_tlas_records;
-    h->any_deep = g.any_deep;
-    h->has_forest = s.has_forest;
-    h->plain_materials = s.plain_materials;
-    h->n_items = s.n_items;
-    h->top_base = g.top_mesh_base;
+    const bool wide_fits = s.lay.bytes + wave_lds_bytes(h->stack_entries, true, s.tlas_entries, true, true) <= LDS_BUDGET_BYTES;
+    h->stack_must_wide = g.max_leaf_ref > 127u || g.n_triangles > (1u << 24);
+    h->stack_wide = h->stack_must_wide || wide_fits;
     h->top_available = g.top_mesh_records >= 64 ? std::min<uint32_t>(g.top_mesh_records, 2048u) : 0u;
-    h->have_defer = s.have_defer;
-    h->defer_mesh = s.defer_mesh;
-    h->defer_xform = s.defer_xform;
-    h->defer_internal = s.defer_internal;
     // LDS residency: blob + the four waves' stacks, cost tables and lane state within the
     // per-workgroup budget (the primary-ray memo goes to LDS only if it still fits, see render_impl)
-    uint64_t stacks = ((uint64_t)h->stack_entries * (h->stack_wide ? 128u : 64u) + (uint64_t)h->tlas_entries * 64u) * sizeof(uint32_t) * WAVES_PER_BLOCK +
-                      8u * 3u * 4u * WAVES_PER_BLOCK + (uint64_t)LANE_STATE_DWORDS * 64u * 4u * WAVES_PER_BLOCK;
-    h->lds_scene = (uint64_t)lay.bytes + stacks <= LDS_BUDGET_BYTES;
+    h->lds_scene = s.lay.bytes + wave_lds_bytes(h->stack_entries, h->stack_wide, s.tlas_entries, true, false) <= LDS_BUDGET_BYTES;
     h->camera = camera;
     h->have_scene = true;
     h->history = FrameShape{};
@@ -1322,6 +651,37 @@ int drain_streams(rt_handle* h) {
     for (PipeSlot& ps : h->pipe)
         if (ps.stream) HIP_TRY(h, hipStreamSynchronize(ps.stream));
     return RT_OK;
+}
+
+// Where rt_update_instances / rt_refit_triangles (`who`) write the head of `lay`, once every launch that may read the blob
+// is complete (the streams are drained): the blob itself while the head keeps its size; else a new blob, allocated before
+// the drain, zeroed when the scene is empty (16 zero bytes), with the old blob's tail copied device to device on the
+// handle's stream -- on any failure it is freed and the failure reported.  The caller writes the head (a refit: its boxes
+// and triangle records first), synchronises and adopts the blob.
+int drop_new_blob(rt_handle* h, float4* fresh, int rc) {  // (the current blob is not a new one: left alone)
+    if (fresh == h->blob) return rc;
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(fresh);
+    return rc;
+}
+int blob_for_head(rt_handle* h, const char* who, const SceneLayout& lay, uint64_t tail_bytes, float4*& fresh) {
+    fresh = h->blob;
+    if (lay.wide_off == h->inst.lay.wide_off) return drain_streams(h);
+    if (hipMalloc((void**)&fresh, lay.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, RT_ERR_OUT_OF_MEMORY, std::string(who) + ": no device memory for the resized scene");
+    }
+    if (int rc = drain_streams(h); rc != RT_OK) return drop_new_blob(h, fresh, rc);
+    hipError_t e = (uint64_t)lay.wide_off + tail_bytes != lay.bytes ? hipMemsetAsync(fresh, 0, lay.bytes, h->stream) : hipSuccess;
+    if (e == hipSuccess && tail_bytes)
+        e = hipMemcpyAsync((char*)fresh + lay.wide_off, (const char*)h->blob + h->inst.lay.wide_off, tail_bytes, hipMemcpyDeviceToDevice, h->stream);
+    return e == hipSuccess ? RT_OK : drop_new_blob(h, fresh, fail(h, RT_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e)));
+}
+// ... and, once the stream has completed everything written into it, a new blob takes the old one's place.
+void adopt_blob(rt_handle* h, float4* fresh) {
+    if (fresh == h->blob) return;
+    free_dev(h->blob);
+    h->blob = fresh;
 }
 
 }  // namespace
@@ -1347,72 +707,47 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
 
     try {
         SceneGeom g;
-        std::vector<float4> tail;
-        int rc = build_geometry(h, meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, g, tail);
-        if (rc != RT_OK) return rc;
-        SceneInstances s;
-        if ((rc = build_instances(h, g, spheres, n_spheres, meshes, n_meshes, s)) != RT_OK) return rc;
+        InstanceFacts s;
+        std::vector<rt2::Quad> head, tail;  // [0, lay.wide_off) and [lay.wide_off, lay.bytes) of the blob
+        std::string why;
+        int rc = rt2::pack_geometry(meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, g, tail, why);
+        if (rc == RT_OK) rc = rt2::pack_instances(h->pack, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
+        if (rc != RT_OK) return fail(h, rc, why);
         const SceneLayout& lay = s.lay;
         std::vector<rt_mesh_uniform> inst_meshes(meshes, meshes + n_meshes);
         std::vector<rt_sphere> inst_spheres(spheres, spheres + n_spheres);
 #if RT_WALK2
         free_dev(h->walk2);
         h->walk2 = nullptr;
-        if (s.have_defer) {
+        if (s.have_defer) {  // per internal node of the deferred mesh: its record, then copies of its children's records
             const uint32_t base = g.mesh[s.defer_mesh].wide_base;
-            const WideRec* wide = reinterpret_cast<const WideRec*>(tail.data());  // (the tail starts with the wide records)
-            std::vector<float4> w2((size_t)s.defer_internal * 12u, make_float4(0, 0, 0, 0));
-            auto bitsof = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+            const rt2::Rec2* wide = reinterpret_cast<const rt2::Rec2*>(tail.data());  // (the tail starts with the wide records)
+            std::vector<rt2::Rec2> w2((size_t)s.defer_internal * 3u, rt2::Rec2{});
             for (uint32_t k = 0; k < s.defer_internal; ++k) {
-                const WideRec& w = wide[base + k];
-                for (int q = 0; q < 4; ++q) w2[(size_t)k * 12 + q] = w.q[q];
-                if (bitsof(w.q[1].w) == 0u) for (int q = 0; q < 4; ++q) w2[(size_t)k * 12 + 4 + q] = wide[bitsof(w.q[1].z)].q[q];
-                if (bitsof(w.q[3].w) == 0u) for (int q = 0; q < 4; ++q) w2[(size_t)k * 12 + 8 + q] = wide[bitsof(w.q[3].z)].q[q];
+                w2[(size_t)k * 3] = wide[base + k];
+                for (int c = 0; c < 2; ++c)
+                    if (const rt2::Child ch = rt2::read_rec2(wide[base + k], c); ch.count == 0u) w2[(size_t)k * 3 + 1 + c] = wide[ch.idx];
             }
-            HIP_TRY(h, hipMalloc((void**)&h->walk2, w2.size() * sizeof(float4)));
-            HIP_TRY(h, hipMemcpy(h->walk2, w2.data(), w2.size() * sizeof(float4), hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMalloc((void**)&h->walk2, w2.size() * sizeof(rt2::Rec2)));
+            HIP_TRY(h, hipMemcpy(h->walk2, w2.data(), w2.size() * sizeof(rt2::Rec2), hipMemcpyHostToDevice));
             h->walk2_base = base;
         }
 #endif
         free_scene(h);
         HIP_TRY(h, hipMalloc((void**)&h->blob, lay.bytes));
-        if ((uint64_t)lay.wide_off + tail.size() * sizeof(float4) != lay.bytes)  // (an empty scene: 16 zero bytes)
+        if ((uint64_t)lay.wide_off + tail.size() * sizeof(rt2::Quad) != lay.bytes)  // (an empty scene: 16 zero bytes)
             HIP_TRY(h, hipMemsetAsync(h->blob, 0, lay.bytes, h->stream));
-        if (!s.head.empty())
-            HIP_TRY(h, hipMemcpyAsync(h->blob, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        if (!head.empty())
+            HIP_TRY(h, hipMemcpyAsync(h->blob, head.data(), head.size() * sizeof(rt2::Quad), hipMemcpyHostToDevice, h->stream));
         if (!tail.empty())
-            HIP_TRY(h, hipMemcpyAsync((char*)h->blob + lay.wide_off, tail.data(), tail.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-        // ---- the small blob of the hybrid launches (experiments build only) ----
-        std::vector<float4> small;
-        SceneLayout sl{};
-        uint32_t small_need = 1;
-        bool small_ok = false;
+            HIP_TRY(h, hipMemcpyAsync((char*)h->blob + lay.wide_off, tail.data(), tail.size() * sizeof(rt2::Quad), hipMemcpyHostToDevice, h->stream));
 #if RT_EXPERIMENTS
-        {
-            // (the names the fragment reads: the whole blob and the per-mesh arrays of the geometry phase)
-            std::vector<float4> blob(s.head);
-            blob.insert(blob.end(), tail.begin(), tail.end());
-            blob.resize(lay.bytes / 16, make_float4(0, 0, 0, 0));
-            std::vector<uint32_t> wide_base(n_meshes), tri_lo(n_meshes), tri_hi(n_meshes), mesh_need(n_meshes);
-            for (uint32_t i = 0; i < n_meshes; ++i) {
-                wide_base[i] = g.mesh[i].wide_base;
-                tri_lo[i] = g.mesh[i].tri_lo;
-                tri_hi[i] = g.mesh[i].tri_hi;
-                mesh_need[i] = g.mesh[i].need;
-            }
-            const std::vector<char> wide(g.n_wide), items(s.n_items), tlas(s.n_tlas_records), forest_entries(s.n_forest_entries);
-            const bool have_defer = s.have_defer;
-            const uint32_t defer_mesh = s.defer_mesh, defer_internal = s.defer_internal;
-#include "experiments/rt_api_hybrid_blob.inl"   // (statement fragment: fills small / sl / small_need / small_ok)
-        }
+#include "experiments/rt_api_hybrid_blob.inl"   // (statement fragment: the small blob of the hybrid launches, from g, s, head, tail)
 #endif
-        if (small_ok && (rc = upload(h, h->small_blob, small.data(), small.size())) != RT_OK) return rc;
-        h->small_ok = small_ok;
-        h->small_lay = sl;
-        h->small_stack_entries = small_need;
         HIP_TRY(h, hipStreamSynchronize(h->stream));  // host staging vectors die here
-        commit_scene(h, g, s, n_spheres, scene->camera);
         h->geom = std::move(g);
+        h->inst = s;
+        commit_scene(h, scene->camera);
         h->inst_meshes.swap(inst_meshes);
         h->inst_spheres.swap(inst_spheres);
     } catch (const std::bad_alloc&) {
@@ -1447,44 +782,23 @@ int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sp
 #endif
     HIP_TRY(h, hipSetDevice(h->device));
     try {
-        SceneInstances s;
-        int rc = build_instances(h, g, spheres, n_spheres, meshes, n_meshes, s);
-        if (rc != RT_OK) return rc;
+        InstanceFacts s;
+        std::vector<rt2::Quad> head;
+        std::string why;
+        int rc = rt2::pack_instances(h->pack, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
+        if (rc != RT_OK) return fail(h, rc, why);
         std::vector<rt_mesh_uniform> inst_meshes(meshes, meshes + n_meshes);
         std::vector<rt_sphere> inst_spheres(spheres, spheres + n_spheres);
-        const SceneLayout& lay = s.lay;
-        const uint64_t tail_bytes = g.tail_bytes();
-        if (lay.wide_off == h->lay.wide_off) {
-            // the head in place: after every launch that may read it, and complete before the next one
-            if ((rc = drain_streams(h)) != RT_OK) return rc;
-            if (!s.head.empty())
-                HIP_TRY(h, hipMemcpyAsync(h->blob, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));  // (host staging vector dies here)
-        } else {
-            // a new blob: the new head from the host, the old tail device to device, the old blob freed after both
-            float4* fresh = nullptr;
-            if (hipMalloc((void**)&fresh, lay.bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(h, RT_ERR_OUT_OF_MEMORY, "rt_update_instances: no device memory for the resized scene");
-            }
-            rc = drain_streams(h);
-            hipError_t e = hipSuccess;
-            if (rc == RT_OK && (uint64_t)lay.wide_off + tail_bytes != lay.bytes)  // (an empty scene: 16 zero bytes)
-                e = hipMemsetAsync(fresh, 0, lay.bytes, h->stream);
-            if (rc == RT_OK && e == hipSuccess && !s.head.empty())
-                e = hipMemcpyAsync(fresh, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream);
-            if (rc == RT_OK && e == hipSuccess && tail_bytes)
-                e = hipMemcpyAsync((char*)fresh + lay.wide_off, (const char*)h->blob + h->lay.wide_off, tail_bytes,
-                                   hipMemcpyDeviceToDevice, h->stream);
-            if (rc == RT_OK && e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (rc != RT_OK || e != hipSuccess) {
-                (void)hipFree(fresh);
-                return rc != RT_OK ? rc : fail(h, RT_ERR_DEVICE, std::string("rt_update_instances: ") + hipGetErrorString(e));
-            }
-            free_dev(h->blob);
-            h->blob = fresh;
-        }
-        commit_scene(h, g, s, n_spheres, scene->camera);
+        // The head in place -- after every launch that may read it, and complete before the next one -- or, when its size
+        // changes, in a new blob: the old tail device to device, the new head from the host, the old blob freed after both.
+        float4* target;
+        if ((rc = blob_for_head(h, "rt_update_instances", s.lay, g.tail_bytes(), target)) != RT_OK) return rc;
+        hipError_t e = head.empty() ? hipSuccess : hipMemcpyAsync(target, head.data(), head.size() * sizeof(rt2::Quad), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (host staging vector dies here)
+        if (e != hipSuccess) return drop_new_blob(h, target, fail(h, RT_ERR_DEVICE, std::string("rt_update_instances: ") + hipGetErrorString(e)));
+        adopt_blob(h, target);
+        h->inst = s;
+        commit_scene(h, scene->camera);
         h->inst_meshes.swap(inst_meshes);
         h->inst_spheres.swap(inst_spheres);
         h->generation += 1;
@@ -1600,9 +914,9 @@ int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32
             return hip_fail("hipMemcpyAsync", e);
         // ---- fit: the scratch only (the blob's wide records are read for their references, which a refit keeps) ----
         a.blob = h->blob;
-        a.wide_off = h->lay.wide_off;
-        a.tri_off = h->lay.tri_off;
-        a.shade_off = h->lay.shade_off;
+        a.wide_off = h->inst.lay.wide_off;
+        a.tri_off = h->inst.lay.tri_off;
+        a.shade_off = h->inst.lay.shade_off;
         if ((e = launch_refit_fit(a, h->stream)) != hipSuccess) return hip_fail("launch_refit_fit", e);
         if (!table.empty() && (e = hipMemcpyAsync(results.data(), a.results, table.size() * sizeof(RefitResult), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
             return hip_fail("hipMemcpyAsync", e);
@@ -1625,48 +939,28 @@ int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32
         g2.roots_are_unions = true;
         for (const MeshGeom& mg : g2.mesh)
             if (mg.root_count == 0 && !mg.unions) g2.roots_are_unions = false;
-        SceneInstances s;
-        if (int rc = build_instances(h, g2, h->inst_spheres.data(), (uint32_t)h->inst_spheres.size(), h->inst_meshes.data(),
-                                     (uint32_t)h->inst_meshes.size(), s); rc != RT_OK)
-            return done(rc);
+        InstanceFacts s;
+        std::vector<rt2::Quad> head;
+        if (int rc = rt2::pack_instances(h->pack, g2, h->inst_spheres.data(), (uint32_t)h->inst_spheres.size(), h->inst_meshes.data(),
+                                         (uint32_t)h->inst_meshes.size(), s, head, why); rc != RT_OK)
+            return done(fail(h, rc, why));
         // ---- write: from here on nothing is refused ----
         const SceneLayout& lay = s.lay;
-        float4* target = h->blob;
-        if (lay.wide_off != h->lay.wide_off) {  // a resized head: a new blob, the old tail copied, then refitted there
-            if (hipMalloc((void**)&target, lay.bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return done(fail(h, RT_ERR_OUT_OF_MEMORY, "rt_refit_triangles: no device memory for the resized scene"));
-            }
-        }
-        auto drop_target = [&](int rc) {
-            if (target != h->blob) { (void)hipStreamSynchronize(h->stream); (void)hipFree(target); }
-            return rc;
-        };
-        if (int rc = drain_streams(h); rc != RT_OK) return done(drop_target(rc));  // (every launch that may read the blob)
-        const uint64_t tail_bytes = g2.tail_bytes();
-        if (target != h->blob) {
-            if ((uint64_t)lay.wide_off + tail_bytes != lay.bytes && (e = hipMemsetAsync(target, 0, lay.bytes, h->stream)) != hipSuccess)
-                return drop_target(hip_fail("hipMemsetAsync", e));
-            if (tail_bytes && (e = hipMemcpyAsync((char*)target + lay.wide_off, (const char*)h->blob + h->lay.wide_off, tail_bytes,
-                                                  hipMemcpyDeviceToDevice, h->stream)) != hipSuccess)
-                return drop_target(hip_fail("hipMemcpyAsync", e));
-        }
+        float4* target;  // (a resized head: a new blob, the old tail copied, then refitted there)
+        if (int rc = blob_for_head(h, "rt_refit_triangles", lay, g2.tail_bytes(), target); rc != RT_OK) return done(rc);
         a.blob = target;
         a.wide_off = lay.wide_off;
         a.tri_off = lay.tri_off;
         a.shade_off = lay.shade_off;
-        if ((e = launch_refit_write(a, h->stream)) != hipSuccess) return drop_target(hip_fail("launch_refit_write", e));
-        if (!s.head.empty() &&
-            (e = hipMemcpyAsync(target, s.head.data(), s.head.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-            return drop_target(hip_fail("hipMemcpyAsync", e));
-        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return drop_target(hip_fail("hipStreamSynchronize", e));
-        if (target != h->blob) {
-            free_dev(h->blob);
-            h->blob = target;
-        }
-        const rt_camera_uniform camera = h->camera;
-        commit_scene(h, g2, s, (uint32_t)h->inst_spheres.size(), camera);
+        if ((e = launch_refit_write(a, h->stream)) != hipSuccess) return drop_new_blob(h, target, hip_fail("launch_refit_write", e));
+        if (!head.empty() &&
+            (e = hipMemcpyAsync(target, head.data(), head.size() * sizeof(rt2::Quad), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+            return drop_new_blob(h, target, hip_fail("hipMemcpyAsync", e));
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return drop_new_blob(h, target, hip_fail("hipStreamSynchronize", e));
+        adopt_blob(h, target);
         h->geom = std::move(g2);
+        h->inst = s;
+        commit_scene(h, h->camera);
         h->generation += 1;
         return done(RT_OK);
     } catch (const std::bad_alloc&) {
@@ -1757,17 +1051,17 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
         if (value < 0 || value > 2) return fail(h, RT_ERR_INVALID_ARGUMENT, "pixel_cache must be 0, 1 or 2 (memo in global memory)");
         h->pixel_cache_opt = value;
     } else if (n == "tlas") {
-        h->use_tlas = value ? 1 : 0;
+        h->pack.tlas = value ? 1 : 0;
     } else if (n == "stack_wide") {
         if (value < -1 || value > 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "stack_wide must be -1 (auto), 0 or 1");
         h->force_stack_wide = value;
     } else if (n == "forest") {
-        h->use_forest = value ? 1 : 0;
+        h->pack.forest = value ? 1 : 0;
     } else if (n == "flat2") {
-        h->use_flat2 = value ? 1 : 0;
+        h->pack.flat2 = value ? 1 : 0;
     } else if (n == "tlas_min") {
         if (value < 2) return fail(h, RT_ERR_INVALID_ARGUMENT, "tlas_min must be >= 2");
-        h->tlas_min = value;
+        h->pack.tlas_min = value;
     } else if (n == "cull_roots") {
         if (value < -1 || value > 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "cull_roots must be -1 (auto), 0 or 1");
         h->cull_roots = value;
@@ -1778,7 +1072,7 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
         h->force_global = value ? 0 : 1;
     } else if (n == "defer_min_nodes") {
         if (value < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "defer_min_nodes must be >= 1 (takes effect at the next rt_upload_scene)");
-        h->defer_min_nodes = value;
+        h->pack.defer_min_nodes = value;
     } else if (n == "sort_rounds") {
         if (value < -1 || value > 64) return fail(h, RT_ERR_INVALID_ARGUMENT, "sort_rounds must be -1 (automatic), 0 (off) or 1 .. 64");
         h->sort_rounds = value;
@@ -1873,32 +1167,32 @@ static int wavefront_run(rt_handle*, const RenderArgs&, const WavefrontPlan&) { 
 // test library's per-ray probe (rt_test_intersect), which therefore walks exactly what a render walks.
 static void scene_args(const rt_handle* h, RenderArgs& a) {
     a.blob = h->blob;
-    a.lay = h->lay;
+    a.lay = h->inst.lay;
     // (an explicitly requested deferred-walk sequence -- option "sort_rounds" > 0, tests -- reads the scene in place: the
     // parking instantiations exist for global-memory scenes only; the automatic setting never defers a mesh of a scene
     // that fits the LDS)
-    a.lds_scene = (h->lds_scene && !h->force_global && !(h->sort_rounds > 0 && h->have_defer)) ? 1u : 0u;
-    a.cull_roots = (h->roots_are_unions && (h->cull_roots == 1 || (h->cull_roots < 0 && h->n_meshes >= 16))) ? 1u : 0u;
-    a.many_mesh = (h->has_tlas || (a.cull_roots && !h->has_forest)) ? 1u : 0u;
+    a.lds_scene = (h->lds_scene && !h->force_global && !(h->sort_rounds > 0 && h->inst.have_defer)) ? 1u : 0u;
+    a.cull_roots = (h->geom.roots_are_unions && (h->cull_roots == 1 || (h->cull_roots < 0 && h->geom.mesh.size() >= 16))) ? 1u : 0u;
+    a.many_mesh = (h->inst.has_tlas || (a.cull_roots && !h->inst.has_forest)) ? 1u : 0u;
     a.forest_cull = h->cull_roots != 0 ? 1u : 0u;
     a.cross_prune = h->cross_prune != 0 ? 1u : 0u;
     {
         uint32_t ds, dv;
         memcpy(&ds, &h->camera.defocus_strength, 4);
         memcpy(&dv, &h->camera.diverge_strength, 4);
-        a.simple = (h->specialise && h->plain_materials && ds == 0u && dv == 0u) ? 1u : 0u;  // (both strengths +0)
+        a.simple = (h->specialise && h->inst.plain_materials && ds == 0u && dv == 0u) ? 1u : 0u;  // (both strengths +0)
     }
     a.textures = h->textures;
     a.srgb_lut = h->srgb_lut;
-    a.n_meshes = h->n_meshes;
-    a.n_spheres = h->n_spheres;
+    a.n_meshes = (uint32_t)h->geom.mesh.size();
+    a.n_spheres = (uint32_t)h->inst_spheres.size();
     a.n_textures = h->n_textures;
     a.stack_entries = h->stack_entries;
-    a.tlas_entries = h->tlas_entries;
+    a.tlas_entries = h->inst.tlas_entries;
     a.stack_wide = (h->stack_must_wide || (h->force_stack_wide < 0 ? h->stack_wide : h->force_stack_wide != 0)) ? 1u : 0u;
     // (the global-memory kernels park a pending mesh hit of 5 dwords in the stack column, intersect_scene)
     if (!a.lds_scene && a.stack_entries < (a.stack_wide ? 3u : 5u)) a.stack_entries = a.stack_wide ? 3u : 5u;
-    a.n_items = h->n_items;
+    a.n_items = h->inst.n_items;
 }
 
 // What the steps of one render_impl call decide and share.
@@ -2017,7 +1311,7 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
     }
     // LDS-staged top of the big mesh's BVH (global-memory scenes): as many of its breadth-first numbered
     // records as fit beside the stacks without costing a workgroup per CU, or what option "lds_top" says
-    a.top_base = h->top_base;
+    a.top_base = h->geom.top_mesh_base;
     a.top_count = 0;
     if (RT_EXPERIMENTS && !a.lds_scene && h->top_available && h->lds_top != 0) {
         const size_t used = render_lds_bytes(a);
@@ -2026,16 +1320,16 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
         a.top_count = std::min(fit, h->top_available);
     }
     a.tlas_lds = 0;
-    if (RT_EXPERIMENTS && !a.lds_scene && a.many_mesh && h->has_tlas && h->lds_tlas != 0 && params->debug_flag == 0) {
+    if (RT_EXPERIMENTS && !a.lds_scene && a.many_mesh && h->inst.has_tlas && h->lds_tlas != 0 && params->debug_flag == 0) {
         // 1: as many of the breadth-first numbered records (the top levels first) as fit without costing a workgroup per
         // CU; 2: the whole tree if the LDS can hold it at all
-        const size_t used = render_lds_bytes(a), need = (size_t)h->n_tlas_records * WIDE_REC_BYTES;
+        const size_t used = render_lds_bytes(a), need = (size_t)h->inst.n_tlas_records * WIDE_REC_BYTES;
         const uint32_t per_cu_now = blocks_per_cu_for(used);
         const size_t room = CU_LDS_BYTES / per_cu_now > used ? CU_LDS_BYTES / per_cu_now - used : 0;
         if (h->lds_tlas == 2) {
-            if (used + need <= 64u * 1024u) a.tlas_lds = h->n_tlas_records;
+            if (used + need <= 64u * 1024u) a.tlas_lds = h->inst.n_tlas_records;
         } else {
-            a.tlas_lds = std::min<uint32_t>(h->n_tlas_records, (uint32_t)(room / WIDE_REC_BYTES));
+            a.tlas_lds = std::min<uint32_t>(h->inst.n_tlas_records, (uint32_t)(room / WIDE_REC_BYTES));
         }
     }
     a.persistent_blocks = persistent_blocks_for(h, render_lds_bytes(a));
@@ -2056,12 +1350,12 @@ static void plan_rounds(const rt_handle* h, const rt_params* params, const Rende
     const size_t park_records = (size_t)pl.need_texels * (pl.n_batch ? pl.n_batch : 1u);
     const size_t park_bytes = ((park_records + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4);  // per queue
     uint32_t n_rounds = h->sort_rounds > 0 ? (uint32_t)h->sort_rounds : 0u;
-    if (h->sort_rounds < 0 && h->have_defer) {
+    if (h->sort_rounds < 0 && h->inst.have_defer) {
         // (work of the launch in units of one 1920 x 1080 frame at 16 samples per pixel)
         const double units = (double)park_records * (double)(params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) / (1920.0 * 1080.0 * 16.0);
         // (tuned on the config 3 and config 5 stand-ins: the longer the walks -- the bigger the mesh's BVH --, the
         // earlier a round pays for its fixed cost)
-        if (h->defer_internal >= 400000u)
+        if (h->inst.defer_internal >= 400000u)
             // (config 5 stand-in at 3840 x 2160, 64 spp, 16 frames per launch = 256 units: 102.9 / 98.4 / 96.8 / 96.8 / 97.3 ms
             // per frame with 8 / 12 / 16 / 24 / 32 rounds)
             // (32 frames per launch = 512 units: 95.6 ms with 16 rounds, 95.0 with 24)
@@ -2077,7 +1371,7 @@ static void plan_rounds(const rt_handle* h, const rt_params* params, const Rende
     pl.park_records = park_records;
     pl.park_bytes = park_bytes;
     pl.n_rounds = n_rounds;
-    pl.rounds = n_rounds > 0 && h->have_defer && a.many_mesh == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
+    pl.rounds = n_rounds > 0 && h->inst.have_defer && a.many_mesh == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
                 params->rays_per_pixel > 0 && a.lds_scene == 0u;
 }
 
@@ -2097,7 +1391,7 @@ static void vote_thresholds(const rt_handle* h, RenderArgs& a, const LaunchPlan&
 // S is the stream this frame's sampling launch and its bookkeeping run on.
 static int pipeline_acquire(rt_handle* h, const rt_params* params, const RenderArgs& a, LaunchPlan& pl) {
     const uint64_t need_texels = pl.need_texels;
-    const bool wavefront_wanted = RT_EXPERIMENTS && h->wavefront != 0 && a.many_mesh != 0 && !h->any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0;
+    const bool wavefront_wanted = RT_EXPERIMENTS && h->wavefront != 0 && a.many_mesh != 0 && !h->geom.any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0;
     const int pipeline_opt = h->pipeline < 0 ? automatic_pipeline_depth(pl.shape.world) : h->pipeline;
     if (!h->queues_noted && pipeline_opt != 0 && (hw_queues_requested() < 5 || pipeline_opt + 1 > hw_queues_requested())) {
         // Not an error, said once (rt_last_error after a call that returned RT_OK): the pipeline is limited by, or
@@ -2395,8 +1689,8 @@ static int launch_pipelined(rt_handle* h, const rt_params* params, RenderArgs& a
 static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
     if (!h->park_counts) HIP_TRY(h, hipMalloc((void**)&h->park_counts, 72 * sizeof(uint32_t)));
     HIP_TRY(h, hipMemsetAsync(h->park_counts, 0, 72 * sizeof(uint32_t), h->stream));
-    a.defer_mesh = h->defer_mesh;
-    a.defer_xform = h->defer_xform;
+    a.defer_mesh = h->inst.defer_mesh;
+    a.defer_xform = h->inst.defer_xform;
 #if RT_WALK2
     a.walk2 = h->walk2;
     a.walk2_base = h->walk2_base;
@@ -2420,7 +1714,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
         ah.lds_scene = 1;
         ah.hybrid = 1;
         ah.big_blob = h->blob;
-        ah.big_shade_off = h->lay.shade_off;
+        ah.big_shade_off = h->inst.lay.shade_off;
         ah.top_count = 0;
         ah.stack_entries = h->small_stack_entries ? h->small_stack_entries : 1u;
         ah.stack_wide = 0;
@@ -3280,14 +2574,54 @@ int rt_test_device_units(rt_handle* h, int fn, const float* x, const float* y, f
 int rt_test_scene_blob(rt_handle* h, void* out, uint64_t bytes, uint32_t layout_out[12], uint64_t* device_ptr) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    if (out && bytes < h->lay.bytes) return fail(h, RT_ERR_INVALID_ARGUMENT, "output smaller than the blob");
+    if (out && bytes < h->inst.lay.bytes) return fail(h, RT_ERR_INVALID_ARGUMENT, "output smaller than the blob");
     static_assert(sizeof(SceneLayout) == 12 * sizeof(uint32_t), "SceneLayout is 12 words");
-    if (layout_out) memcpy(layout_out, &h->lay, sizeof(SceneLayout));
+    if (layout_out) memcpy(layout_out, &h->inst.lay, sizeof(SceneLayout));
     if (device_ptr) *device_ptr = (uint64_t)(uintptr_t)h->blob;
     if (out) {
         HIP_TRY(h, hipSetDevice(h->device));
         if (int rc = drain_streams(h); rc != RT_OK) return rc;
-        HIP_TRY(h, hipMemcpy(out, h->blob, h->lay.bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(out, h->blob, h->inst.lay.bytes, hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
+// tests/test_scene_pack_host.py, tests/test_gpu_scene_pack.py: the host packer on scene arrays, without a device -- both
+// phases as rt_upload_scene runs them, the blob assembled as the device would hold it (head, tail, zero padding), and the
+// instance phase run again on the same geometry facts, as rt_update_instances would.
+int rt_test_pack_scene(const rt_sphere* spheres, uint32_t n_spheres, const rt_mesh_uniform* meshes, uint32_t n_meshes,
+                       const rt_packed_triangle* triangles, uint32_t n_triangles, const rt_node* nodes, uint32_t n_nodes,
+                       const int32_t options[5], void* out, uint64_t bytes, uint32_t layout_out[12], uint32_t facts_out[RT_TEST_PACK_FACTS]) {
+    if (!options || (n_spheres && !spheres) || (n_meshes && !meshes) || (n_triangles && !triangles) || (n_nodes && !nodes))
+        return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null array with non-zero count");
+    try {
+        const rt2::PackOptions opt{options[0], options[1], options[2], options[3], options[4]};
+        SceneGeom g;
+        InstanceFacts s, again;
+        std::vector<rt2::Quad> head, head_again, tail;
+        std::string why;
+        int rc = rt2::pack_geometry(meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, g, tail, why);
+        if (rc == RT_OK) rc = rt2::pack_instances(opt, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
+        if (rc == RT_OK) rc = rt2::pack_instances(opt, g, spheres, n_spheres, meshes, n_meshes, again, head_again, why);
+        if (rc != RT_OK) return fail(nullptr, rc, why);
+        const size_t head_bytes = head.size() * sizeof(rt2::Quad);
+        const bool same = head.size() == head_again.size() && (head.empty() || memcmp(head.data(), head_again.data(), head_bytes) == 0) &&
+                          memcmp(&s.lay, &again.lay, sizeof(SceneLayout)) == 0;
+        if (out && bytes < s.lay.bytes) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "output smaller than the blob");
+        if (layout_out) memcpy(layout_out, &s.lay, sizeof(SceneLayout));
+        if (facts_out) {
+            const uint32_t f[RT_TEST_PACK_FACTS] = {s.n_items, s.n_tlas_records, s.n_forest_entries, s.tlas_entries, s.has_tlas, s.has_forest, s.plain_materials,
+                                                    s.have_defer, s.defer_mesh, s.defer_xform, s.defer_internal, g.max_height, g.max_leaf_ref, g.top_mesh_records,
+                                                    g.top_mesh_base, g.roots_are_unions, g.any_deep, same};
+            memcpy(facts_out, f, sizeof(f));
+        }
+        if (out) {
+            memset(out, 0, s.lay.bytes);
+            if (!head.empty()) memcpy(out, head.data(), head_bytes);
+            if (!tail.empty()) memcpy((char*)out + s.lay.wide_off, tail.data(), tail.size() * sizeof(rt2::Quad));
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
     }
     return RT_OK;
 }
@@ -3314,7 +2648,7 @@ int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint
     bool simple = render_takes_simple(a) && !stats;  // (the counter instantiations are the general code)
     if (flags & RT_TEST_ISECT_GENERAL) simple = false;
     if (flags & RT_TEST_ISECT_SIMPLE) {
-        if (a.many_mesh || !h->plain_materials)
+        if (a.many_mesh || !h->inst.plain_materials)
             return fail(h, RT_ERR_INVALID_ARGUMENT, "the SIMPLE instantiation needs a few-mesh scene without spheres, glass or textures");
         simple = true;
     }

@@ -2830,17 +2830,14 @@ hipError_t diag_read(unsigned long long* out, bool reset) {
 
 // Launchers (called from rt_api.hip)
 size_t render_lds_bytes(const RenderArgs& a) {
-    size_t stacks = ((size_t)(a.stack_entries ? a.stack_entries : 1u) * (a.stack_wide ? 128u : 64u) + (size_t)a.tlas_entries * 64u) *
-                    sizeof(uint32_t) * WAVES_PER_BLOCK;
-    size_t cost_tables = 8u * 3u * sizeof(uint32_t) * WAVES_PER_BLOCK;
-    size_t lane_state = total_in_lds(a.lds_scene != 0u) ? (size_t)LANE_STATE_DWORDS * 64u * sizeof(uint32_t) * WAVES_PER_BLOCK : 0u;
-    size_t cache = a.pixel_cache == 1u ? (size_t)PIXEL_MEMO_DWORDS * 64u * sizeof(uint32_t) * WAVES_PER_BLOCK : 0u;
     // (= 4 x wave_region_dwords + the cost tables, see the LDS map)
+    const size_t waves = (size_t)wave_lds_bytes(a.stack_entries ? a.stack_entries : 1u, a.stack_wide != 0u, a.tlas_entries,
+                                                total_in_lds(a.lds_scene != 0u), a.pixel_cache == 1u);
     size_t scene = a.lds_scene ? a.lay.bytes : 0u;
 #if RT_EXPERIMENTS
     if (!a.lds_scene) scene = ((size_t)a.top_count + a.tlas_lds) * WIDE_REC_BYTES;
 #endif
-    return stacks + cost_tables + lane_state + cache + scene;
+    return waves + scene;
 }
 
 // Dynamic LDS above 64 KiB (deep-BVH stacks) has to be opted into per kernel: every launch with the render kernels' LDS

@@ -4,11 +4,11 @@
 //   fit   -- parent links of the selected meshes' wide records, then one launch that folds every leaf child's box from
 //            the new triangles and carries the unions up the tree with arrival counters: a record is finished by the
 //            last of its own thread and its internal children's threads to arrive.  Boxes go to scratch (one slot per
-//            record), and per mesh the root box and the predicates build_geometry evaluates (contains, the union test,
+//            record), and per mesh the root box and the predicates pack_geometry evaluates (contains, the union test,
 //            a proper bounding hierarchy) go to a small result table, the only thing the host reads back.
 //   write -- the scratch boxes into the wide records, and the triangle intersection / shade records of the range.
 // The box rule is csrc/rt_refit.h, shared with the host refit (host/bvh.cpp), and the triangle records are computed with
-// the unfused binary32 operations of build_geometry (this file is compiled with -ffp-contract=off), so the blob ends up
+// the unfused binary32 operations of pack_geometry (this file is compiled with -ffp-contract=off), so the blob ends up
 // with the bytes rt_upload_scene gives for the same arrays.
 //
 // Hand-off between workgroups (cdna_hip_programming Guideline 16, counter form with write-through payload): every box word
@@ -56,7 +56,7 @@ __device__ __forceinline__ void record_refs(const RefitArgs& a, uint32_t r, uint
     idx[1] = bits_of(q3.z); cnt[1] = bits_of(q3.w);
 }
 
-__device__ __forceinline__ bool finite_box(const float lo[3], const float hi[3]) {  // (build_geometry's finite_box)
+__device__ __forceinline__ bool finite_box(const float lo[3], const float hi[3]) {  // (pack_geometry's finite_box)
     for (int k = 0; k < 3; ++k)
         if (!(lo[k] <= hi[k] && lo[k] - lo[k] == 0.0f && hi[k] - hi[k] == 0.0f)) return false;
     return true;
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(REFIT_THREADS) rt_refit_fit_kernel(RefitArgs a
             hi[c] = rt_box_max(ahi[c], bhi[c]);
         }
         if (!finite_box(alo, ahi) || !finite_box(blo, bhi) || !inside(alo, ahi, lo, hi) || !inside(blo, bhi, lo, hi)) proper = false;
-        if (k == m.slot0) {  // the root: build_geometry's root predicates, with the same comparisons
+        if (k == m.slot0) {  // the root: pack_geometry's root predicates, with the same comparisons
             bool contains = true, unions = true;
             for (int c = 0; c < 3; ++c) {
                 const float lo_c = alo[c] < blo[c] ? alo[c] : blo[c];
@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(REFIT_THREADS) rt_refit_records_kernel(RefitAr
     }
 }
 
-// build_geometry's triangle re-layout (rt_device.h): intersection record (v1, n.x), (ab, n.y), (ac, n.z); shade record
+// pack_geometry's triangle re-layout (rt_scene_format.h): intersection record (v1, n.x), (ab, n.y), (ac, n.z); shade record
 // (n1, uv10), (n2, uv11), (n3, uv20), (uv21, uv30, uv31, 0).  The subtractions and the cross product are wgsl:261-263.
 __global__ void __launch_bounds__(REFIT_THREADS) rt_refit_triangles_kernel(RefitArgs a) {
     const uint32_t t = blockIdx.x * REFIT_THREADS + threadIdx.x;

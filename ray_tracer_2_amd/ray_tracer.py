@@ -236,6 +236,33 @@ class RayTracer:
         self._check(self._L.rt_test_scene_blob(self._h, out.ctypes.data, out.nbytes, C.byref(lay), C.byref(ptr)))
         return out, np.array(lay, np.uint32), int(ptr.value)
 
+    PACK_OPTIONS = dict(tlas=1, forest=1, flat2=1, tlas_min=8, defer_min_nodes=1024)   # (the handle's defaults)
+
+    @staticmethod
+    def pack_scene(arrays, **options):
+        """(blob bytes as uint8, SceneLayout as 12 uint32, fact words as RT_TEST_PACK_FACTS uint32 -- A.PACK_FACT_FIELDS) of
+        `arrays` as the host packer lays them out under `options` (PACK_OPTIONS: what set_option would have set before
+        update_buffers): rt_test_pack_scene, no device and no handle."""
+        from .lib import load_test
+        L, a = load_test(), arrays
+        opt = dict(RayTracer.PACK_OPTIONS)
+        if set(options) - set(opt):
+            raise ValueError(f"unknown packer options {sorted(set(options) - set(opt))}")
+        opt.update(options)
+        o = (C.c_int32 * 5)(*(int(opt[k]) for k in RayTracer.PACK_OPTIONS))
+        lay, facts = (C.c_uint32 * 12)(), (C.c_uint32 * 18)()
+        args = (a.spheres.ctypes.data, a.spheres.shape[0], a.meshes.ctypes.data, a.meshes.shape[0], a.triangles.ctypes.data,
+                a.triangles.shape[0], a.nodes.ctypes.data, a.nodes.shape[0], C.byref(o))
+        out = None
+        for _ in range(2):
+            rc = L.rt_test_pack_scene(*args, None if out is None else out.ctypes.data, 0 if out is None else out.nbytes,
+                                      C.byref(lay), C.byref(facts))
+            if rc < 0:
+                raise RtError(rc, L.rt_last_error(None).decode())
+            if out is None:
+                out = np.empty(lay[9], np.uint8)
+        return out, np.array(lay, np.uint32), np.array(facts, np.uint32)
+
     # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick) and frame-wide first hits (rt_render_gbuffer) ----
     def trace_rays(self, origins, dirs, tmax=None):
         """Closest hit of rays (origins[i], dirs[i]) on the uploaded scene, as a render's walk computes it; a hit at

@@ -2,6 +2,9 @@
 // (csrc/host/obj_loader.cpp, png_decode.cpp, scene.cpp, bvh.cpp) behind the C API of csrc/host/scene_capi.cpp, built
 // with AddressSanitizer + UndefinedBehaviorSanitizer on the CPU, fed one file per line of a manifest:
 //     <mode> <path>        mode = obj (rt_scene_add_obj with its MTL, then rt_scene_build) | png (decode_png_file)
+//                                 | pack (both phases of the host packer, csrc/host/scene_pack.cpp, on the arrays of a file:
+//                                   four u32 counts -- spheres, meshes, triangles, nodes -- then the four arrays as
+//                                   include/rt_abi.h lays them out; memory safety and return codes only, no blob bits)
 // Prints "BEGIN <path>" before and "END <rc>" after each file, so that a sanitizer abort names its input.
 // The reference panics on a file it cannot read (src/core/asset.rs:72-75,118); here every malformed input has to come
 // back as an error code.
@@ -9,14 +12,42 @@
 #include <fstream>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/rt_abi.h"
 #include "../../ray_tracer_2_amd/csrc/host/scene.h"
+#include "../../ray_tracer_2_amd/csrc/host/scene_pack.h"
 
 namespace rt2 {
 // (the device-side plane search lives in csrc/rt_bvh_search.hip; not part of this CPU build)
 LevelSearch make_device_level_search(int, const float*, size_t) { throw std::runtime_error("HIP: no device in the sanitizer build"); }
 }  // namespace rt2
+
+// The arrays of a `pack` file, each in a heap block of exactly its size (so that a read past an end is a report).
+template <typename T>
+static bool read_array(std::ifstream& in, uint32_t n, std::vector<T>& out) {
+    out.resize(n);
+    return n == 0 || (bool)in.read(reinterpret_cast<char*>(out.data()), (std::streamsize)n * sizeof(T));
+}
+static int pack_file(const std::string& path) {
+    std::ifstream in(path, std::ios::binary);
+    uint32_t n[4];
+    std::vector<rt_sphere> spheres;
+    std::vector<rt_mesh_uniform> meshes;
+    std::vector<rt_packed_triangle> triangles;
+    std::vector<rt_node> nodes;
+    if (!in.read(reinterpret_cast<char*>(n), sizeof(n)) || !read_array(in, n[0], spheres) || !read_array(in, n[1], meshes) ||
+        !read_array(in, n[2], triangles) || !read_array(in, n[3], nodes))
+        return RT_ERR_IO;
+    rt2::SceneGeom g;
+    rt2::InstanceFacts facts;
+    std::vector<rt2::Quad> head, tail;
+    std::string why;
+    int rc = rt2::pack_geometry(meshes.data(), n[1], triangles.data(), n[2], nodes.data(), n[3], g, tail, why);
+    if (rc == RT_OK) rc = rt2::pack_instances(rt2::PackOptions{}, g, spheres.data(), n[0], meshes.data(), n[1], facts, head, why);
+    if (rc == RT_OK && ((uint64_t)head.size() * 16u != facts.lay.wide_off || facts.lay.wide_off + g.tail_bytes() > facts.lay.bytes)) rc = -100;
+    return rc;
+}
 
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
@@ -46,6 +77,8 @@ int main(int argc, char** argv) {
             rt2::Image img;
             rc = rt2::decode_png_file(path, img) ? RT_OK : RT_ERR_IO;
             if (rc == RT_OK && img.rgba.size() != (size_t)img.width * img.height * 4) rc = -100;  // (a decoder that lies about its output)
+        } else if (mode == "pack") {
+            rc = pack_file(path);
         } else {
             rc = -101;
         }

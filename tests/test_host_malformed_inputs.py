@@ -1,5 +1,5 @@
-"""Malformed OBJ / MTL / PNG files against the host loaders built with AddressSanitizer + UndefinedBehaviorSanitizer
-(CPU build of csrc/host/*.cpp behind the C API, tests/cpp/host_sanitizer_driver.cpp).
+"""Malformed OBJ / MTL / PNG files against the host loaders, and malformed BVHs against the host packer, built with
+AddressSanitizer + UndefinedBehaviorSanitizer (CPU build of csrc/host/*.cpp, tests/cpp/host_sanitizer_driver.cpp).
 
 The reference panics on a file it cannot read or parse (src/core/asset.rs:72-75,118: `.expect`, `.unwrap`).  The
 drop-in must not take the host process down: every malformed input has to come back as an error code (RT_ERR_IO /
@@ -161,3 +161,30 @@ def test_malformed_inputs_come_back_as_error_codes_under_asan_and_ubsan(tmp_path
     assert not bad, bad
     # the valid files do load, and most of the hand-written malformed ones are refused (not silently accepted)
     assert sum(rc != OK for (_, p, _), rc in zip(files, ended) if "mut_" not in p) >= 30
+
+
+def test_malformed_and_unusual_bvhs_through_the_packer_under_asan_and_ubsan(rt, tmp_path):
+    """Both phases of the host packer (csrc/host/scene_pack.cpp) on foreign BVHs: a child cycle, a child index past
+    n_nodes, a leaf range past n_triangles and a node_offset past n_nodes come back as RT_ERR_INDEX_RANGE; two meshes that
+    alias one node range, a leaf-only root and a scene without meshes pack (RT_OK) -- without a sanitizer report either way.
+    Memory safety and return codes only: this build does not have the product's floating-point flags."""
+    import _scene_pack_cases as P
+    from ray_tracer_2_amd.build import build_host_sanitizer_driver
+    exe = build_host_sanitizer_driver()
+    cases = [(name, arrays, P.INDEX_RANGE) for name, arrays in P.malformed(rt)]
+    cases += [("aliased_meshes", P.aliased_meshes(rt), OK), ("leaf_only_root", P.leaf_only_root(rt), OK),
+              ("zero_meshes", P.three_spheres(rt), OK), ("empty", P.empty_scene(rt), OK)]
+    assert len(cases) == 8
+    for name, a, _ in cases:
+        with open(tmp_path / f"{name}.pack", "wb") as f:
+            f.write(np.array([len(a.spheres), len(a.meshes), len(a.triangles), len(a.nodes)], np.uint32).tobytes())
+            for arr in (a.spheres, a.meshes, a.triangles, a.nodes):
+                f.write(arr.tobytes())
+    manifest = tmp_path / "pack_manifest.txt"
+    manifest.write_text("".join(f"pack {tmp_path / (name + '.pack')}\n" for name, _, _ in cases))
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:allocator_may_return_null=0:max_allocation_size_mb=2048",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    out = subprocess.run([exe, str(manifest)], capture_output=True, text=True, timeout=300, env=env, errors="replace")
+    ended = [int(ln[4:]) for ln in out.stdout.splitlines() if ln.startswith("END ")]
+    assert out.returncode == 0 and out.stderr == "" and len(ended) == len(cases), out.stderr[-4000:]
+    assert ended == [rc for _, _, rc in cases], list(zip((name for name, _, _ in cases), ended))

@@ -441,6 +441,10 @@ int rt_bind_image(rt_handle* h, void* device_ptr, uint64_t texels);
  *   defer_min_nodes       >= 1 (1024) (upload)    smallest BVH (internal nodes) whose mesh may be the deferred one
  *   fast_miss             0 / 1 (1)               a memoised primary ray that leaves the scene ends its pixel in one step: the
  *                                                 remaining samples are that segment again and their light is added in order
+ *   roulette_skip         0 / 1 (1)               the samples of a pixel that die at the russian roulette of their memoised
+ *                                                 primary hit (a plain material: no glass, no texture) are found from the RNG
+ *                                                 state alone and not shaded: their light is added in order, the RNG jumps
+ *                                                 their 12 draws, their segment is counted as served from the memo; no texel changes
  *   park_levels           0 / 1 (1)               a parking launch runs the deferred walk's first two levels inline and parks
  *                                                 only the rays that reach a grandchild box (0: every ray that can hit the root box)
  *   multi_rccl            0 / 1 / 2 (1)           gather of rt_render_multi: device-to-device copies / RCCL between

@@ -19,7 +19,9 @@ extern "C" {
  * 4 exp2, 5 log2, 6 pow(x,y), 7 acos, 8 atan2(x,y), 9 sqrt, 10 x/y, 11 rand() from RNG state bits x,
  * 12 next_random_number of state x (bits), 13 trig_signbits(x) (bits), 14 rand_normal_dist() from
  * state x, 15 f32(u32 bits x) * 2^-32, 16 normalize(x, y, x*y).x, 17 the kernels' reciprocal rcp_(x), 18 their
- * sqrt_dev(x).  The second call filters one RGBA8 sRGB texture at n (u, v) pairs (wgsl:455 as csrc/rt_texture.h defines
+ * sqrt_dev(x), 19 the RNG jumps of the roulette skip for state x (bits), y (bits) selecting the value: 0 / 1 the generator's
+ * output 5 steps on, by one jump / by stepping next_random_number; 2 / 3 the output 12 steps on; 4 / 5 the state 12 steps
+ * on.  The second call filters one RGBA8 sRGB texture at n (u, v) pairs (wgsl:455 as csrc/rt_texture.h defines
  * it).  The third compares the kernels' short reciprocal (which = 0) / square root (which = 1) with the compiler's IEEE
  * 1.0f / x / sqrt on the device for EVERY float in the range the short form serves, and the sky's three shortcuts
  * (which = 2, 3, 4: wgsl:215-218 with the branches of smoothstep / pow taken apart) with their literal forms for every

@@ -250,6 +250,7 @@ struct rt_handle {
     // two-path load, 10.67 -> 11.98 ms)
     int lds_tlas = 0;
     int fast_miss = 1;  // option "fast_miss"
+    int roulette_skip = 1;  // option "roulette_skip"
     int park_levels = 1;  // option "park_levels": the parking launches run the deferred walk's first two levels inline
     float4* own_image = nullptr;  // allocated by rt_create; `image` may be rebound
     float4* multi_gathered = nullptr;  // rt_render_multi root: [world][pad_texels]
@@ -1098,6 +1099,8 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
         h->frame_ahead_failed = false;
     } else if (n == "fast_miss") {
         h->fast_miss = value ? 1 : 0;
+    } else if (n == "roulette_skip") {
+        h->roulette_skip = value ? 1 : 0;
     } else if (n == "park_levels") {
         h->park_levels = value ? 1 : 0;
     } else if (n == "hybrid") {
@@ -1342,6 +1345,7 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
         a.pixel_cache_mem = h->pixel_cache_mem;
     }
     a.fast_miss = h->fast_miss != 0 && a.pixel_cache != 0u ? 1u : 0u;
+    a.roulette_skip = h->roulette_skip != 0 && a.pixel_cache != 0u ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1728,6 +1732,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
         }
         if (!ah.pixel_cache) ah.primary = nullptr;
         ah.fast_miss = h->fast_miss != 0 && ah.pixel_cache != 0u ? 1u : 0u;
+        ah.roulette_skip = h->roulette_skip != 0 && ah.pixel_cache != 0u ? 1u : 0u;
         if (render_lds_bytes(ah) > LDS_BUDGET_BYTES) hybrid = false;
         ah.persistent_blocks = h->persistent_blocks;
         ah.park_levels = 0;  // (the small blob has no record of the big mesh's BVH)

@@ -151,8 +151,9 @@ struct RenderArgs {
     // the undeferred loop, so the image is the same bit for bit; the last launch of a sequence has park = 0 and
     // walks what is left inline.
     uint32_t fast_miss;           // != 0: a memoised primary ray that misses ends its pixel in one step (path_end, option "fast_miss")
+    uint32_t roulette_skip;       // != 0: the samples that die at the roulette of a memoised primary hit are not shaded (path_step's pre-step, option "roulette_skip")
     uint32_t park;
-    uint32_t park_levels;         // != 0: a ray parks only if the walk's first two levels reach a grandchild box (option "park_levels")
+    uint32_t park_levels;        // != 0: a ray parks only if the walk's first two levels reach a grandchild box (option "park_levels")
     float4* q_in;                 // park records to resume instead of tiles (null: the work items are tiles)
     const uint32_t* q_in_count;   // their number (written by the launch before)
     float4* q_out;                // where this launch parks

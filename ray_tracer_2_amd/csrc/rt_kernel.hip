@@ -180,10 +180,33 @@ DEV f3 mat_xyz(P m, f3 v, float w) {
 }
 
 // ---- RNG (wgsl:164-206) ---------------------------------------------------
-DEV uint32_t next_random_number(uint32_t& s) {
-    s = s * 747796405u + 2891336453u;
+constexpr uint32_t RNG_LCG_A = 747796405u, RNG_LCG_C = 2891336453u;
+// the generator's output for the (already advanced) state s
+DEV uint32_t rng_output(uint32_t s) {
     uint32_t r = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
     return (r >> 22u) ^ r;
+}
+DEV uint32_t next_random_number(uint32_t& s) {
+    s = s * RNG_LCG_A + RNG_LCG_C;
+    return rng_output(s);
+}
+// k steps of the LCG in one: s -> s * A^k + C (A^(k-1) + ... + A + 1) (mod 2^32), exact integer arithmetic
+struct LcgJump {
+    uint32_t a, c;
+};
+constexpr LcgJump lcg_jump(uint32_t k) {
+    LcgJump j{1u, 0u};
+    for (uint32_t i = 0; i < k; ++i) j = LcgJump{j.a * RNG_LCG_A, j.c * RNG_LCG_A + RNG_LCG_C};
+    return j;
+}
+static_assert(lcg_jump(1).a == RNG_LCG_A && lcg_jump(1).c == RNG_LCG_C, "one step is the generator's own");
+static_assert(lcg_jump(4).a == 2200120369u && lcg_jump(4).c == 878960812u, "4 steps: the two disks' draws of a sample's start");
+static_assert(lcg_jump(5).a == 2975532453u && lcg_jump(5).c == 3598456993u, "5 steps: up to the is_spec draw");
+static_assert(lcg_jump(12).a == 1985007505u && lcg_jump(12).c == 200982212u, "12 steps: up to the roulette draw of a primary segment");
+template <uint32_t K>
+DEV uint32_t rng_jump(uint32_t s) {
+    constexpr LcgJump j = lcg_jump(K);
+    return s * j.a + j.c;
 }
 // f32(r) / 4294967295.0: the divisor rounds to 2^32 in f32 and a division by
 // a power of two is exact, so this equals the multiplication by 2^-32 bit for
@@ -271,6 +294,10 @@ DEV uint32_t fbits(float f) { return __float_as_uint(f); }
 // than it saves -- config 3 stand-in 5.276 -> 5.260 ms per frame without it, config 5 geometry 3.152 -> 3.116)
 #ifndef RT_PRESTEP_PARK
 #define RT_PRESTEP_PARK 0
+#endif
+// The roulette skip of the pre-step (roulette_skip below, option "roulette_skip"); -DRT_ROULETTE_SKIP=0 compiles it out.
+#ifndef RT_ROULETTE_SKIP
+#define RT_ROULETTE_SKIP 1
 #endif
 #ifndef RT_TOP_BRANCH
 #define RT_TOP_BRANCH 1
@@ -1754,7 +1781,7 @@ DEV uint32_t path_begin(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32
         if (st & MEMO_RAY) {
             // the two disks' angle and radius draws: four steps of the generator's LCG
             // s -> s * 747796405 + 2891336453 (mod 2^32) in one, (A^4, C (A^3 + A^2 + A + 1)); exact
-            s.rng = s.rng * 2200120369u + 878960812u;
+            s.rng = rng_jump<4>(s.rng);
             s.ro = f3{a.memo_ro[0], a.memo_ro[1], a.memo_ro[2]};
             reuse_hit = !STATS && (st & MEMO_HIT_VALID) != 0u;
         } else {
@@ -1959,6 +1986,64 @@ DEV bool path_end(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_t mod
     return false;
 }
 
+// Roulette skip (option "roulette_skip"; the pre-step of path_step).  A sample whose memoised primary ray hits a plain
+// material -- not glass, no texture -- reaches its russian roulette after a fixed number of draws: 4 (the two disks) + 1
+// (is_spec) + 6 (rand_unit_sphere) + 1 (the roulette's own).  Its throughput there is `color` or `specular_color` and its
+// light `emitted`, constants of the pixel, so whether it dies is a function of the RNG state at its start alone: the
+// is_spec value is the output of the state 5 steps on, the roulette value that of the state 12 steps on.  A sample that
+// dies leaves nothing behind but total += emitted, j += 1, the RNG 12 steps on and its counted segment; those are applied
+// here, sample after sample, without shading it -- the float operations that make the two thresholds and the light are
+// path_end's, on path_end's operands.  The first sample that survives is left to the pre-step with the RNG untouched: it
+// makes the same draws again.  Returns true when the pixel's last sample died here.
+template <bool LDS, bool TOTAL_LDS, bool SIMPLE>
+DEV bool roulette_skip(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_t memo_word, uint32_t& n_segments, uint32_t& more_reused) {
+    if ((memo_word & MEMO_HIT) == 0u) return false;
+    const uint32_t mo = memo_word & ~15u;  // (memo_hit_load)
+    if constexpr (!SIMPLE) {
+        const int flag = ldi<LDS>(a, mo + M_FLAG);
+        if (flag == RT_MATERIAL_GLASS) return false;
+        if (flag == RT_MATERIAL_TEXTURE && ldi<LDS>(a, mo + M_DIFFUSE_IDX) != -1) return false;
+    }
+    const float4 msc = ld4<LDS>(a, mo + M_ABSORB_S);  // (absorb_s, emission_s, smoothness, specular)
+    const float4 ec = ld4<LDS>(a, mo + M_EMISSION);
+    const float4 cc = ld4<LDS>(a, mo + M_COLOR);
+    const float4 sc = ld4<LDS>(a, mo + M_SPECCOL);
+    const float es = msc.y;
+    const f4 one{1, 1, 1, 1};
+    const f4 emitted{ec.x * es, ec.y * es, ec.z * es, ec.w * es};
+    const f4 L0 = f4{0, 0, 0, 0} + emitted * one;  // s.light + emitted * T
+    const f4 Tc = one * f4{cc.x, cc.y, cc.z, cc.w}, Ts = one * f4{sc.x, sc.y, sc.z, sc.w};
+    const float p_diffuse = max_(Tc.x, max_(Tc.y, Tc.z)), p_spec = max_(Ts.x, max_(Ts.y, Ts.z));
+    const int32_t rpp = a.params.rays_per_pixel;
+    uint32_t rng = s.rng, dead = 0u;
+    f4 t = s.total;
+    if constexpr (TOTAL_LDS)
+        t = f4{__uint_as_float(ls[0]), __uint_as_float(ls[64]), __uint_as_float(ls[128]), __uint_as_float(ls[192])};
+    while (s.j + (int32_t)dead < rpp) {
+        const bool is_spec = msc.w >= (float)rng_output(rng_jump<5>(rng)) * 0x1p-32f;  // (rand_'s conversion)
+        const float p = is_spec ? p_spec : p_diffuse;
+        const uint32_t rng12 = rng_jump<12>(rng);
+        if (!((float)rng_output(rng12) * 0x1p-32f >= p)) break;  // it survives
+        DIAG(32);
+        t = t + L0;  // total += incoming_light
+        rng = rng12;
+        dead += 1u;
+    }
+    if (dead == 0u) return false;
+    if constexpr (TOTAL_LDS) {
+        ls[0] = __float_as_uint(t.x); ls[64] = __float_as_uint(t.y); ls[128] = __float_as_uint(t.z); ls[192] = __float_as_uint(t.w);
+    } else {
+        s.total = t;
+    }
+    s.rng = rng;
+    s.j += (int32_t)dead;
+    n_segments += dead;
+    more_reused += dead;
+    const uint32_t rays = (s.meta & 0xffffu) + dead;
+    s.meta = (s.meta & 0xffff0000u) | (rays < 0xffffu ? rays : 0xffffu);
+    return s.j >= rpp;
+}
+
 // returns PATH_CONTINUE, PATH_PIXEL_DONE (the pixel's last sample ended) or PATH_PARK (the pixel was parked in front
 // of the deferred mesh, RenderArgs::park)
 enum : uint32_t { PATH_CONTINUE = 0, PATH_PIXEL_DONE = 1, PATH_PARK = 2 };
@@ -1984,8 +2069,13 @@ DEV uint32_t path_step(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_
                 rd = f3{__uint_as_float(pc[0]), __uint_as_float(pc[64]), __uint_as_float(pc[128])};
             });
             if ((st & (MEMO_RAY | MEMO_HIT_VALID)) == (MEMO_RAY | MEMO_HIT_VALID)) {
+#if RT_ROULETTE_SKIP
+                // the samples that die at this hit's roulette, counted as served from the memo like FAST_MISS's
+                if (a.roulette_skip != 0u && roulette_skip<LDS, total_in_lds(LDS), SIMPLE>(a, s, ls, st, n_segments, more_reused))  // (wave-uniform switch)
+                    return PATH_PIXEL_DONE;
+#endif
                 s.rd = rd;
-                s.rng = s.rng * 2200120369u + 878960812u;  // (the two disks' four draws: path_begin)
+                s.rng = rng_jump<4>(s.rng);  // (the two disks' four draws: path_begin)
                 s.ro = f3{a.memo_ro[0], a.memo_ro[1], a.memo_ro[2]};
                 s.T = f4{1, 1, 1, 1};
                 s.light = f4{0, 0, 0, 0};

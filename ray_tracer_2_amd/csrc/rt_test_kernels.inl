@@ -9,7 +9,9 @@
 // fn: 0 log, 1 cos, 2 sin, 3 exp, 4 exp2, 5 log2, 6 pow(x, y), 7 acos, 8 atan2(x, y), 9 sqrt, 10 x / y
 // (the oracle's numbering), 11 rand() of RNG state bits x -> float, 12 the generator's u32 output for
 // state x, 13 trig_signbits(x), 14 rand_normal_dist() of state x, 15 f32(u32 x) * 2^-32 (rand()'s
-// conversion for a raw generator output), 16 normalize(x, y, x*y).x (division by a sqrt), 17 rcp_(x), 18 sqrt_dev(x)
+// conversion for a raw generator output), 16 normalize(x, y, x*y).x (division by a sqrt), 17 rcp_(x), 18 sqrt_dev(x),
+// 19 the roulette skip's RNG jumps for state x, y (bits) selecting: 0 / 1 the generator's output 5 steps on by jumping /
+// by stepping, 2 / 3 the output 12 steps on, 4 / 5 the state 12 steps on
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) rt_units_kernel(int fn, const float* __restrict__ x, const float* __restrict__ y,
                                                        float* __restrict__ out, unsigned long long n) {
@@ -37,6 +39,19 @@ __global__ void __launch_bounds__(256) rt_units_kernel(int fn, const float* __re
         case 16: r = normalize3(f3{a, b, a * b}).x; break;
         case 17: r = rcp_(a); break;
         case 18: r = sqrt_dev(a); break;
+        case 19: {  // the roulette skip's jumps against the generator stepped 12 times; y (bits) selects the value
+            const uint32_t s0 = __float_as_uint(a), which = __float_as_uint(b);
+            uint32_t s = s0, out5 = 0u, out12 = 0u;
+            for (int k = 1; k <= 12; ++k) {
+                const uint32_t o = next_random_number(s);
+                if (k == 5) out5 = o;
+                if (k == 12) out12 = o;
+            }
+            const uint32_t v = which == 0u ? rng_output(rng_jump<5>(s0)) : which == 1u ? out5 : which == 2u ? rng_output(rng_jump<12>(s0))
+                             : which == 3u ? out12 : which == 4u ? rng_jump<12>(s0) : s;
+            r = __uint_as_float(v);
+            break;
+        }
         default: break;
     }
     out[i] = r;

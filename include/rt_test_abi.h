@@ -81,6 +81,39 @@ int rt_test_rccl_gather(const char* lib_path, int n_ranks);
  * and whether the host counts as one that waits for every frame.  0 = the call renders its own frame only. */
 int rt_test_frame_ahead_depth(int lds_scene, uint64_t texels, int rays_per_pixel, int number_of_bounces, int host_waits);
 
+/* The option table (csrc/host/launch_options.cpp), no device and no handle.  rt_test_option_table: row `index` -- its name
+ * and info_out = {lower bound, upper bound of the values it can hold (INT_MIN / INT_MAX: none), default, flags};
+ * RT_ERR_INVALID_ARGUMENT past the last row.  rt_test_set_option: the setter behind rt_set_option on a fresh set of options -- returns its code, error text
+ * in rt_last_error(NULL); stored_out = {the value of that option the library would act on now (0 for an unknown name),
+ * the side effects rt_set_option owes its handle: the RT_TEST_OPT_DROPS_PRIMARY / RESETS_TILES / CLEARS_AHEAD_FAILED bits}. */
+#define RT_TEST_OPTION_NAME_BYTES 32
+#define RT_TEST_OPT_BOOLEAN 1             /* any non-zero value stores 1 */
+#define RT_TEST_OPT_UPLOAD 2              /* takes effect at the next rt_upload_scene */
+#define RT_TEST_OPT_EXPERIMENT 4          /* a library without RT_EXPERIMENTS accepts 0 only */
+#define RT_TEST_OPT_DROPS_PRIMARY 8       /* invalidates the primary tables */
+#define RT_TEST_OPT_RESETS_TILES 16       /* resets the tile history */
+#define RT_TEST_OPT_CLEARS_AHEAD_FAILED 32
+#define RT_TEST_OPT_ONE_IS_AUTO 64        /* 1 is stored as -1 */
+#define RT_TEST_OPT_NOT_ONE 128           /* 1 is refused inside the range */
+int rt_test_option_table(uint32_t index, char name_out[RT_TEST_OPTION_NAME_BYTES], int32_t info_out[4]);
+int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
+
+/* One launch rule of csrc/host/launch_options.h (no device, no handle); option values go in as rt_test_set_option stored
+ * them.  in / out per rule:
+ *   VOTES    {vote_eighths, vote_patience, in a deferred-walk sequence, scene in global memory or many-mesh} -> {eighths, patience}
+ *   ROUNDS   {pixels x frames of the launch, rays_per_pixel, internal nodes of the deferred mesh} -> {automatic rounds}
+ *   VARIANT  {kernel_variant, persistent_blocks, tiles, frames of the batch (0: single frame), counters on} -> {variant}
+ *   DEPTH    {pipeline, GPU_MAX_HW_QUEUES, world} -> {frames in flight}
+ *   BATCH    {frames of the sequence, most frames per launch} -> {frames per launch}
+ *   GRID     {LDS bytes per workgroup, persistent_blocks} -> {workgroups per CU, persistent grid} */
+#define RT_TEST_RULE_VOTES 0
+#define RT_TEST_RULE_ROUNDS 1
+#define RT_TEST_RULE_VARIANT 2
+#define RT_TEST_RULE_DEPTH 3
+#define RT_TEST_RULE_BATCH 4
+#define RT_TEST_RULE_GRID 5
+int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
+
 /* Test-only: the BVH builder's SAH plane search (find_best_split, bvh.rs:299-351) for host-given nodes, without a build
  * around it: device -1 runs the host search (csrc/host/bvh.cpp: make_host_level_search, no GPU needed), device >= 0 the
  * kernels of csrc/rt_bvh_search.hip (make_device_level_search).  tri9: nine floats per triangle (centroid, min, max; any

@@ -15,11 +15,11 @@ ORACLE_SO = os.path.join(ROOT, "oracle", "_build", "librt_oracle.so")
 
 PRODUCT_SOURCES = [
     "rt_kernel.hip", "rt_api.hip", "rt_bvh_search.hip", "rt_refit.hip", "host/obj_loader.cpp", "host/bvh.cpp", "host/scene.cpp", "host/scene_pack.cpp",
-    "host/png_decode.cpp", "host/scene_capi.cpp", "host/ray_tracer.cpp",
+    "host/launch_options.cpp", "host/png_decode.cpp", "host/scene_capi.cpp", "host/ray_tracer.cpp",
 ]
 PRODUCT_HEADERS = [
     "rt_queries.inl", "rt_test_kernels.inl", "rt_transc.h", "rt_texture.h", "rt_srgb_lut.h", "rt_device.h", "rt_scene_format.h", "rt_rccl.h", "rt_refit.h", "host/glam_math.h",
-    "host/obj_loader.h", "host/bvh.h", "host/scene.h", "host/scene_pack.h", "host/ray_tracer.hpp",
+    "host/obj_loader.h", "host/bvh.h", "host/scene.h", "host/scene_pack.h", "host/launch_options.h", "host/ray_tracer.hpp",
     "../../include/rt_abi.h", "../../include/rt_test_abi.h", "experiments/rt_wavefront.inl", "experiments/rt_wavefront_launch.inl", "experiments/rt_api_wavefront.inl", "experiments/rt_api_hybrid_blob.inl",
 ]
 
@@ -118,9 +118,9 @@ HOST_SANITIZER_DRIVER = os.path.join(ROOT, "tests", "_build", "host_sanitizer_dr
 
 
 def build_host_sanitizer_driver(force=False):
-    """tests/cpp/host_sanitizer_driver.cpp + the host loaders (OBJ / MTL / PNG / scene / BVH, no HIP) with
+    """tests/cpp/host_sanitizer_driver.cpp + the host units (OBJ / MTL / PNG / scene / BVH / packer / option table, no HIP) with
     AddressSanitizer and UndefinedBehaviorSanitizer, CPU only (tests/test_host_malformed_inputs.py)."""
-    host = [os.path.join(CSRC, "host", f) for f in ("obj_loader.cpp", "bvh.cpp", "scene.cpp", "scene_pack.cpp", "png_decode.cpp", "scene_capi.cpp")]
+    host = [os.path.join(CSRC, "host", f) for f in ("obj_loader.cpp", "bvh.cpp", "scene.cpp", "scene_pack.cpp", "launch_options.cpp", "png_decode.cpp", "scene_capi.cpp")]
     src = os.path.join(ROOT, "tests", "cpp", "host_sanitizer_driver.cpp")
     deps = [src, *host] + [os.path.join(CSRC, h) for h in PRODUCT_HEADERS if h.startswith("host/") or h in ("rt_refit.h", "rt_scene_format.h")] + [os.path.join(ROOT, "include", "rt_abi.h")]
     if not force and not _newer(HOST_SANITIZER_DRIVER, deps):

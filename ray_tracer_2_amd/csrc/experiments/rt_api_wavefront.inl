@@ -10,7 +10,7 @@ static int wavefront_prepare(rt_handle* h, const rt_params* params, const Render
     const uint64_t wf_slots64 = (uint64_t)wf_frame_slots * (n_batch ? n_batch : 1u);
     const uint64_t wf_rounds64 = params->number_of_bounces < 0 ? 0ull
         : (uint64_t)(params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) * ((uint64_t)params->number_of_bounces + 1ull);
-    bool wavefront = h->wavefront != 0 && a.many_mesh != 0 && !h->geom.any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0 &&
+    bool wavefront = h->opt.wavefront != 0 && a.many_mesh != 0 && !h->geom.any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0 &&
                      params->width <= 0xffffu && params->height <= 0xffffu && wf_slots64 < (1ull << 31) && wf_rounds64 <= 1024ull;
     const size_t wf_bytes_per_slot = (WF_STATE_PLANES + WF_HIT_PLANES) * sizeof(float4) + 2 * sizeof(uint32_t) + PIXEL_MEMO_DWORDS * sizeof(uint32_t);
     if (wavefront && h->wf_capacity < wf_slots64) {
@@ -35,7 +35,7 @@ static int wavefront_prepare(rt_handle* h, const rt_params* params, const Render
                 free_dev(h->wf_state);
                 free_dev(h->wf_hit);
                 free_dev(h->wf_lists);
-                if (h->wavefront > 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "wavefront: no device memory for the path slots");
+                if (h->opt.wavefront > 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "wavefront: no device memory for the path slots");
                 wavefront = false;
             } else {
                 h->wf_capacity = blocks64 * 64;
@@ -74,7 +74,7 @@ static int wavefront_run(rt_handle* h, const RenderArgs& a, const WavefrontPlan&
     const uint32_t R = (uint32_t)wf_rounds64;
     HIP_TRY(h, hipMemsetAsync(h->wf_counts, 0, ((size_t)R + 2) * sizeof(uint32_t), h->stream));
     RenderArgs w = a;
-    w.pixel_cache = h->pixel_cache_opt ? 3u : 0u;   // (0: no memo; every sample traverses)
+    w.pixel_cache = h->opt.pixel_cache ? 3u : 0u;   // (0: no memo; every sample traverses)
     w.pixel_cache_mem = h->pixel_cache_mem;
     if (!w.pixel_cache) w.primary = nullptr;
     w.tile_order = nullptr;
@@ -88,7 +88,7 @@ static int wavefront_run(rt_handle* h, const RenderArgs& a, const WavefrontPlan&
     uint32_t* lists[2] = {h->wf_lists, h->wf_lists + h->wf_capacity};
     const uint32_t shade_blocks = h->compute_units * 4u;  // (the shade kernel is compiled for 4 waves per SIMD: 128 VGPRs)
     const size_t wlds = wf_walk_lds_bytes(w);
-    const uint32_t walk_blocks = h->compute_units * blocks_per_cu_for(wlds);
+    const uint32_t walk_blocks = h->compute_units * rt2::blocks_per_cu_for(wlds);
     w.wf_round0 = 1;
     w.wf_list_in = nullptr;
     w.wf_count_in = nullptr;

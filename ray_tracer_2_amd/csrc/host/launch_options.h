@@ -1,0 +1,176 @@
+// launch_options.h -- the options of rt_set_option in one table, and the rules that turn them into a launch.  Plain C++
+// without HIP, like the host packer: set, refused and evaluated on a machine without a GPU (tests/test_options_host.py,
+// tests/test_launch_rules_host.py).  include/rt_abi.h documents every option; rt_api.hip keeps what needs the handle's
+// buffers, the device's memory or a stream.
+#ifndef RT_LAUNCH_OPTIONS_H
+#define RT_LAUNCH_OPTIONS_H
+
+#include <algorithm>
+#include <climits>
+
+#include "scene_pack.h"  // PackOptions (and <string>, <cstring>, include/rt_abi.h: rt_params, the codes)
+
+#ifndef RT_EXPERIMENTS
+#define RT_EXPERIMENTS 0
+#endif
+#ifndef RT_MIN_WAVES
+#define RT_MIN_WAVES 5
+#endif
+
+namespace rt2 {
+
+// The kernels' figures that the rules read (csrc/rt_device.h, which needs HIP: rt_api.hip asserts that they agree).
+constexpr uint32_t BLOCKS_PER_CU = RT_MIN_WAVES, WAVES_PER_BLOCK = 4, MAX_BATCH_FRAMES = 64, PIPE_MAX = 8;  // (PIPE_MAX: most frames in flight)
+constexpr size_t CU_LDS_BYTES = 160u * 1024u;
+
+// Every value rt_set_option sets, under the option's name, with its default.
+struct Options {
+    int kernel_variant = -1, persistent_blocks = 0;  // (persistent_blocks: 0 until rt_create has asked the device, CUs x BLOCKS_PER_CU)
+    int specialise = 1, lds_scene = 1, stack_wide = -1, cull_roots = -1, cross_prune = 0;  // which kernels run, and on what
+    int pixel_cache = 1, primary_table = 1, primary_hits = 1, memo_in_table = 1, primary_per_slot = 1, fast_miss = 1, roulette_skip = 1;  // the pixel memo
+    int vote_eighths = -1, vote_patience = -1;
+    int tile_feedback = 1, tile_feedback_period = 8;
+    int pipeline = -1, pipeline_when_idle = 0, frame_ahead = -1;  // one-frame calls
+    int batch_frames = 32, batch_tile_major = 1, multi_rccl = 1;  // frame sequences, the gather of rt_render_multi
+    int sort_rounds = -1, park_levels = 1, max_device_mb = 0;  // deferred walks; the cap on what the library allocates on its own
+    int lds_top = 0, lds_tlas = 0, hybrid = 0, wavefront = 0;  // (the experiments build's)
+    PackOptions pack;  // tlas, forest, flat2, tlas_min, defer_min_nodes
+    size_t max_device_bytes() const { return (size_t)max_device_mb << 20; }
+};
+
+enum : uint32_t {
+    OPT_BOOLEAN = 1u,               // any non-zero value stores 1 (else: lo <= value <= hi is accepted)
+    OPT_UPLOAD = 2u,                // takes effect at the next rt_upload_scene
+    OPT_EXPERIMENT = 4u,            // a library without RT_EXPERIMENTS accepts 0 only
+    OPT_DROPS_PRIMARY = 8u,         // the primary tables hold hits found under the other setting
+    OPT_RESETS_TILES = 16u,         // the tile history starts again
+    OPT_CLEARS_AHEAD_FAILED = 32u,  // the automatic frames rendered ahead may try again
+    OPT_ONE_IS_AUTO = 64u,          // 1 is stored as -1
+    OPT_NOT_ONE = 128u,             // 1 is refused inside the range
+    OPT_EFFECTS = OPT_DROPS_PRIMARY | OPT_RESETS_TILES | OPT_CLEARS_AHEAD_FAILED,  // what rt_set_option owes its handle
+};
+struct OptionRow {
+    const char* name;
+    int& (*at)(Options&);
+    uint32_t flags;
+    int lo, hi;           // the values it can hold (INT_MIN / INT_MAX: no bound)
+    const char* must_be;  // the error text after "<name> must be "
+};
+const OptionRow* option_row(size_t index);  // (null past the last row)
+
+// Sets `name` to `value`: the text of a refusal (empty: set), the row (null: unknown name) and the OPT_EFFECTS (none after
+// a refusal).
+struct SetResult {
+    uint32_t effects = 0;
+    const OptionRow* row = nullptr;
+    std::string error;
+    int code() const { return error.empty() ? RT_OK : RT_ERR_INVALID_ARGUMENT; }
+};
+SetResult set_option(Options& opt, const char* name, int value);
+
+// ---- the rules that read them: plain arithmetic over the options and a few numbers of the launch ----
+
+// Frames in flight of the pipelined single frames; `queues`: the hardware queues the host asked the runtime for.
+// The pipeline keeps up to four streams of a handle busy, and ROCm maps a process's streams onto GPU_MAX_HW_QUEUES hardware
+// queues (default 4): with a fifth stream in the process -- the null stream, a framework's copy stream -- two of them
+// share a queue and, if those are two of the pipeline's, their launches serialise (measured: 1.30 -> 1.42 ms per frame,
+// 1.34 -> 1.60 at two frames in flight).  The library does not touch the environment (the variable is the host's, read
+// when the HIP runtime initialises: INTEGRATION.md section 3; the Python package and bench.py set it before they load
+// anything): the automatic depth is four frames in flight when the host has asked for five queues or more, three
+// otherwise (1.29 against 1.23 ms per frame on four queues).  A rank of a strip split whose share no longer fills the
+// machine (world >= 4: 518 K pixels and fewer for 328 K resident lanes) runs seven frames deep when the host has asked for
+// twelve queues or more -- room for the seven streams beside the host's own (a framework's compute and copy streams,
+// RCCL's): a frame's latency is then set by its longest pixel chain, not by its work (rank 0's share of config 2 at
+// world 8: 0.226 -> 0.207 ms per frame; profiles/r04_strip_pipeline_depth.txt).
+inline int pipeline_depth(const Options& opt, int queues, uint32_t world) {
+    if (opt.pipeline >= 0) return opt.pipeline;
+    if (world >= 4 && queues >= 12) return 7;
+    return queues >= 5 ? 4 : 3;
+}
+
+// How many frames a call that continues an accumulation renders at once (0: just its own).  `counters`: rt_set_counters;
+// `failed`: a batch could not be set up once; `scene_in_lds`: the uploaded scene fits the LDS; `host_waits`: the call
+// found the handle's stream idle.  Automatic: only when the host runs ahead of the device -- a host that waits for every
+// frame gets its frame from a launch of its own, never behind frames it has not asked for --, and then only for scenes
+// staged in LDS (rays of known cost) and shares so small that a launch of their own leaves lanes idle -- in units of a
+// config-2 frame (1920 x 1080, 8 spp, 5 segments: 1.13 ms), batches of about 4 ms: 28 frames for a strip share of eight
+// ranks (0.201 ms per frame pipelined -> 0.16), 14 for one of four (0.404 -> 0.30), 7 for one of two (0.647 -> 0.59), and
+// none for the whole frame, whose pipelined launches (1.15 ms) a batch of three (1.2 ms) does not beat
+// (tools/strip_scaling.py, profiles/r04_strip_scaling.txt).
+inline uint32_t ahead_depth(const Options& opt, const rt_params& params, bool counters, bool failed, bool scene_in_lds,
+                            uint64_t need_texels, bool host_waits) {
+    if (params.debug_flag != 0 || params.rays_per_pixel <= 0 || counters || params.frames < 1) return 0;
+    if (opt.frame_ahead >= 0) return opt.frame_ahead >= 2 ? std::min<uint32_t>((uint32_t)opt.frame_ahead, MAX_BATCH_FRAMES) : 0u;
+    if (failed || host_waits) return 0;
+    const double segments = (double)need_texels * (double)params.rays_per_pixel *
+                            (double)((params.number_of_bounces < 0 ? 0 : params.number_of_bounces) + 1);
+    // (Scenes read from global memory: rays of unknown cost -- the rule of round 4, "up to 8 frames and about 33 ms by a
+    // work estimate", guessed a frame time and needed a timing probe to take the guess back; a host that wants batches on
+    // such a scene asks for them: frame_ahead = 8 gives config 5's geometry 4.43 -> 3.40 ms per call.)
+    if (!scene_in_lds || !opt.lds_scene) return 0;
+    const double ms = segments / (1920.0 * 1080.0 * 8.0 * 5.0) * 1.13;
+    const double d = 4.0 / (ms > 1e-3 ? ms : 1e-3);
+    const uint32_t n = d >= (double)MAX_BATCH_FRAMES ? MAX_BATCH_FRAMES : (uint32_t)d;
+    return n >= 6u ? n : 0u;
+}
+
+// Rounds of an automatic deferred-walk sequence (option "sort_rounds" = -1) over `park_records` pixels (times frames of
+// the batch) and a deferred mesh of `defer_internal` internal nodes; 0: none.
+inline uint32_t automatic_rounds(size_t park_records, int rays_per_pixel, uint32_t defer_internal) {
+    // (work of the launch in units of one 1920 x 1080 frame at 16 samples per pixel)
+    const double units = (double)park_records * (double)(rays_per_pixel > 0 ? rays_per_pixel : 0) / (1920.0 * 1080.0 * 16.0);
+    // (tuned on the config 3 and config 5 stand-ins: the longer the walks -- the bigger the mesh's BVH --, the earlier a
+    // round pays for its fixed cost, its longest chain of dependent segments, which only a big launch amortises)
+    if (defer_internal >= 400000u)
+        // (config 5 stand-in at 3840 x 2160, 64 spp, 16 frames per launch = 256 units: 102.9 / 98.4 / 96.8 / 96.8 / 97.3 ms
+        // per frame with 8 / 12 / 16 / 24 / 32 rounds)
+        // (32 frames per launch = 512 units: 95.6 ms with 16 rounds, 95.0 with 24)
+        return units >= 384.0 ? 24u : units >= 96.0 ? 16u : units >= 48.0 ? 12u : units >= 24.0 ? 8u : units >= 12.0 ? 4u : units >= 4.0 ? 3u : units >= 2.0 ? 2u : 0u;
+    return units >= 24.0 ? 6u : units >= 12.0 ? 4u : units >= 8.0 ? 3u : 0u;
+}
+
+// The intersection vote (path_begin).  `rounds`: inside a deferred-walk sequence; `costly`: scene read from global memory
+// or walked by the many-mesh kernels.  The more a traversal costs beside the rest of an iteration, the longer it pays to
+// let the lanes on memoised primary segments catch up first: 6/8 of the lanes or 3 iterations when the scene is in LDS
+// and walked by the few-mesh kernels (config 2: 1.221 ms per frame; 1.222 with 7/8 and 16, 1.366 with 8/8), 7/8 or 16
+// iterations otherwise (sponza-sized stand-in 10.69 -> 10.21 ms, 200-mesh stand-in 5.00 -> 4.85), every lane or 16
+// iterations in a deferred-walk sequence, whose resumed pixels arrive in every phase (config 3 stand-in 5.86 -> 5.45,
+// config 5 geometry 3.35 -> 3.22; profiles/r03_experiments/ab_*_vote*.txt).
+inline void vote_thresholds(const Options& opt, bool rounds, bool costly, uint32_t& eighths, uint32_t& patience) {
+    eighths = opt.vote_eighths >= 0 ? (uint32_t)opt.vote_eighths : rounds ? 8u : costly ? 7u : 6u;
+    patience = opt.vote_patience >= 0 ? (uint32_t)opt.vote_patience : (rounds || costly) ? 16u : 3u;
+}
+
+// 0 persistent waves with lane refill, 1 one wave per tile.
+inline uint32_t kernel_variant_for(const Options& opt, uint64_t tiles, uint32_t n_batch, bool counters) {
+    // auto: with about one tile per resident wave there is nothing to refill from, and the
+    // plain one-wave-per-tile dispatch is a little faster (tools/strip_scaling.py)
+    const uint32_t resident_waves = (uint32_t)opt.persistent_blocks * WAVES_PER_BLOCK;
+    uint32_t variant = opt.kernel_variant >= 0 ? (uint32_t)opt.kernel_variant : (tiles * 4 <= (uint64_t)resident_waves * 5 ? 1u : 0u);
+    if (n_batch) variant = 0;   // (frame, tile) work items are the persistent kernel's
+    if (counters) variant = 0;  // (the counter instantiations exist for the persistent kernel only)
+    return variant;
+}
+
+// Frames per launch of a sequence of n_frames cut into batches of equal size of at most `cap` (>= 1) frames (20 frames at
+// 16 per launch: 10 + 10, not 16 + 4)
+inline uint32_t equal_batch(uint32_t n_frames, uint32_t cap) {
+    const uint32_t launches = (n_frames + cap - 1) / cap;
+    return launches ? (n_frames + launches - 1) / launches : 0;
+}
+
+// workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
+inline uint32_t blocks_per_cu_for(size_t lds_bytes) {
+    const uint32_t per_cu = lds_bytes ? (uint32_t)(CU_LDS_BYTES / lds_bytes) : BLOCKS_PER_CU;
+    return per_cu > BLOCKS_PER_CU ? BLOCKS_PER_CU : per_cu < 1u ? 1u : per_cu;
+}
+// ... and the persistent grid at that occupancy (option "persistent_blocks" counts BLOCKS_PER_CU per CU)
+inline uint32_t persistent_blocks_for(const Options& opt, size_t lds_bytes) {
+    const uint32_t blocks = (uint32_t)opt.persistent_blocks;
+    const uint32_t fit = (blocks / BLOCKS_PER_CU) * blocks_per_cu_for(lds_bytes);
+    return fit < blocks && fit > 0 ? fit : blocks;
+}
+
+}  // namespace rt2
+
+#endif

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "host/bvh.h"  // (rt2::refit_select / refit_bvh: the selection rule shared with the host refit)
+#include "host/launch_options.h"  // (the option table and the launch rules: plain C++, tested on the CPU)
 #include "host/scene_pack.h"  // (the host packer: scene arrays -> blob)
 #include "rt_device.h"
 #include "rt_refit.h"
@@ -108,7 +109,7 @@ struct CounterRing {
     }
 };
 
-// One frame in flight of the pipelined single frames (rt_handle::pipeline): what is per slot.
+// One frame in flight of the pipelined single frames (option "pipeline"): what is per slot.
 struct PipeSlot {
     hipStream_t stream = nullptr;
     hipEvent_t sampled = nullptr;     // frame sampled into `scratch` (recorded on `stream`)
@@ -144,47 +145,16 @@ struct rt_handle {
     float4* walk2 = nullptr;           // experiment: two-level records of the deferred mesh (rt_device.h)
     uint32_t walk2_base = 0;
 #endif
-    // option "sort_rounds": walk-and-resume rounds of a deferred-walk sequence; 0 = off, -1 (default) = automatic: by
-    // the work of the launch in units of one 1920 x 1080 frame at 16 samples per pixel and the size of the big mesh
-    // (render_impl; none below 8 units, or 2 for a mesh of 400 k internal nodes and more: a round has a fixed cost, its
-    // longest chain of dependent segments, that only a big launch amortises) -- and off when the two park queues (224 B per pixel and frame of the
-    // batch, each) would take more than a quarter of the free device memory
-    int sort_rounds = -1;
-    // wavefront sequences (RenderArgs::wf_*): option "wavefront" 0 (default) = off, 1 = whenever legal (many-mesh scenes
-    // without a literal-stack mesh).  Off by default: measured slower than the inline kernels -- sponza-sized stand-in
-    // 10.65 -> 11.3 ms per frame, 200-mesh stand-in 5.0 -> 7.4 (tools/experiments/README.md)
-    int wavefront = 0;
     float4* wf_state = nullptr;
     float4* wf_hit = nullptr;
     uint32_t* wf_lists = nullptr;     // two lists of wf_capacity slots
     uint32_t* wf_counts = nullptr;
     size_t wf_capacity = 0, wf_counts_capacity = 0;
-    // Hybrid launches of a deferred-walk sequence (option "hybrid"): everything but the deferred mesh's BVH and triangles
-    // -- mesh records, materials, items, the small meshes' records and triangles -- as a blob of its own that the
-    // parking render launches stage into LDS (they never walk the big mesh); only a winner on the big mesh reads its
-    // shading record from the full blob.
-    // Pipelined single frames (option "pipeline"): consecutive rt_render calls sample into two or three scratch images, each
-    // on an internal stream of its own, and are blended in frame order on the handle's stream, so frame k + 1's launch takes the CUs that
-    // frame k's draining waves free -- every frame stays observable (rt_read_image after any call returns that frame).
-    int pipeline = -1;                                 // option "pipeline": frames in flight (0 = off, 2 .. 4, -1 = automatic_pipeline_depth(); config 2: 1.51 / 1.27 / 1.23 / 1.20 ms per frame; 5 and 6: 1.25, 1.24)
-    static constexpr int PIPE_MAX = 8;                 // most frames in flight (option "pipeline")
-    // option "pipeline_when_idle" (default 0): a frame that finds the handle's stream idle -- a host that renders, reads and
-    // only then renders again, the reference's present loop -- has nothing to overlap with and takes the plain in-place
-    // launch (no scratch image, no blend kernel, no event hops); 1 = pipeline such frames too
-    int pipeline_when_idle = 0;
-    // Frames rendered ahead (option "frame_ahead"): a host that accumulates calls rt_render with the same parameters and
-    // frames = f, f + 1, f + 2, ...  When a share is so small that one launch per frame cannot keep the lanes full (a strip
-    // share of four or eight ranks, a small window), the call for frame f renders frames f .. f + d - 1 in ONE batched launch
-    // (the persistent kernel refills its lanes across frames) into the batch scratch images and blends frame f only; the
-    // calls for f + 1 .. f + d - 1 find their frame rendered and only blend it -- same bits, same image after every call.
-    // A call that does not continue the sequence (other parameters, camera, scene, option, strip layout) drops what is left.
-    // Automatic (-1) only batches for a host that runs AHEAD of the device -- its call finds the handle's stream busy, so
-    // nobody is waiting for this frame alone.  A host that renders, waits and renders again never has its frame held back
-    // behind frames it has not asked for (round 5: VERDICT / ADVICE round 4 -- its longest wait had grown from 1.5 to 8 ms);
-    // such a host opts in with an explicit depth (frame_ahead = 2 .. 64).
-    int frame_ahead = -1;                              // -1 automatic (ahead_depth()), 0 off, 2 .. RT_MAX_BATCH_FRAMES frames
+    rt2::Options opt;                                  // what rt_set_option sets (host/launch_options.h)
+    // Frames rendered ahead (option "frame_ahead", include/rt_abi.h; the depth: rt2::ahead_depth): the call for frame f
+    // renders frames f .. f + d - 1 in one batched launch into the batch scratch images; the next d - 1 calls only blend theirs.
     bool frame_ahead_failed = false;                   // the batch could not be set up once (memory): automatic stays off
-    uint32_t ahead_ramp = 2;                           // automatic: batches of 2, 4, 8, ... frames up to ahead_depth() while the
+    uint32_t ahead_ramp = 2;                           // automatic: batches of 2, 4, 8, ... frames up to the depth while the
                                                        // sequence goes on, so that a host that stops after n frames has had
                                                        // at most n rendered in vain; back to 2 when the sequence breaks
     uint64_t generation = 0;                           // bumped by everything that changes what a frame looks like
@@ -209,7 +179,7 @@ struct rt_handle {
     hipStream_t copy_stream = nullptr;
     hipEvent_t snapshot_taken = nullptr, snapshot_read = nullptr;
     bool snapshot_read_pending = false;                // a read of the staging buffer was queued since the last snapshot
-    PipeSlot pipe[PIPE_MAX];
+    PipeSlot pipe[rt2::PIPE_MAX];
     hipEvent_t pipe_book = nullptr;                    // the last tile-order / primary-table rebuild (recorded on a pipe stream)
     hipEvent_t pipe_main = nullptr;                    // the last launch that was not pipelined (recorded on the handle's stream)
     bool pipe_book_set = false, pipe_main_set = false;
@@ -220,12 +190,9 @@ struct rt_handle {
     SceneLayout small_lay{};
     uint32_t small_stack_entries = 1;
     bool small_ok = false;
-    int hybrid = 0;  // option "hybrid" (default 0: measured no faster -- config 3 stand-in 6.04 -> 6.11 ms, config 5 geometry 3.49 -> 3.48)
     float4* park_queue[2] = {nullptr, nullptr};
     size_t park_capacity = 0;  // records per queue
     uint32_t* park_counts = nullptr;
-    int batch_tile_major = 1;  // option "batch_tile_major": (tile, frame) instead of (frame, tile) order of a batch's work items
-    int batch_frames_opt = 32;  // option "batch_frames": frames per launch of rt_render_frames (1..RT_MAX_BATCH_FRAMES)
     // rt_render_multi: what the root's stream has to finish before this handle's image may be overwritten
     // (owned by THIS handle, created on the root's device -- an event is recorded on a stream of its own device --,
     // so that destroying the root first leaves nothing dangling)
@@ -238,20 +205,7 @@ struct rt_handle {
     std::vector<void*> multi_comms;       // ncclComm_t per rank
     std::vector<int> multi_comm_devices;  // the device list the communicators were made for
     std::set<int> multi_peers_enabled;
-    int multi_rccl = 1;  // option "multi_rccl"
     uint32_t top_available = 0;  // breadth-first numbered top records of the biggest mesh's BVH (from geom.top_mesh_base on)
-    // option "lds_top": 0 off (default: measured slower), -1 what fits beside the stacks at full
-    // occupancy, N records
-    int lds_top = 0;
-    // option "lds_tlas": top-level tree records staged into LDS when the scene is read from global memory: 0 off,
-    // 1 when they fit beside the stacks without costing a workgroup per CU, 2 always (if they fit the LDS at all)
-    // (default 0: measured slower both ways on the sponza-sized stand-in, DESIGN.md section 5.4 -- the whole tree costs
-    // two workgroups per CU, 10.64 -> 13.47 ms; the 42 top records that fit at full occupancy make every tree fetch a
-    // two-path load, 10.67 -> 11.98 ms)
-    int lds_tlas = 0;
-    int fast_miss = 1;  // option "fast_miss"
-    int roulette_skip = 1;  // option "roulette_skip"
-    int park_levels = 1;  // option "park_levels": the parking launches run the deferred walk's first two levels inline
     float4* own_image = nullptr;  // allocated by rt_create; `image` may be rebound
     float4* multi_gathered = nullptr;  // rt_render_multi root: [world][pad_texels]
     float4* multi_frame = nullptr;     // rt_render_multi root: assembled full frame
@@ -265,7 +219,6 @@ struct rt_handle {
     CounterRing work;  // ring of per-launch tile counters (launches on the handle's stream)
     uint32_t* pixel_cache_mem = nullptr;  // primary-ray cache when LDS has no room (persistent kernel)
     size_t pixel_cache_words = 0;
-    int kernel_variant = -1;  // -1 auto, 0 persistent + lane refill, 1 one wave per tile
     // tile-cost feedback: rays per tile of the previous frame order the next frame's tiles
     uint32_t* tile_cost[2] = {nullptr, nullptr};
     uint32_t* tile_order = nullptr;
@@ -273,22 +226,13 @@ struct rt_handle {
     int cost_slot = 0;
     FrameShape history;  // the frame layout the tile costs and the tile order were recorded for
     PrimaryTable primary;  // the shared table (every stream's frames read it); the slots' own: PipeSlot::primary
-    int primary_per_slot = 1;
     // A frame whose camera is not the previous frame's (the camera is MOVING) renders without a table: every pixel computes its
     // own memo (its primary ray is traversed once, by its first sample) -- building a table that the next frame throws away
     // costs more than it saves (config 2: 1.32 ms per frame of a moving camera with a table per frame, 1.24 without).
     rt_camera_uniform last_frame_camera{};
     bool last_frame_camera_valid = false;
-    int use_primary = 1;  // option "primary_table"
-    int primary_hits = 1; // option "primary_hits": the table also holds the primary rays' hits, so that the frames of an
-                          // accumulation (still camera, src/core/app.rs:44-53) traverse no primary ray at all
-    int memo_in_table = 1; // option "memo_in_table": kernels whose memo has no room in LDS read it straight from a complete
-                          // primary table (RenderArgs::pixel_cache == 4) instead of copying it into a global-memory buffer
-    int tile_feedback = 1;
-    int tile_feedback_period = 8;  // frames an order is kept before it is refreshed
     bool have_order = false, costs_ready = false;
     uint32_t order_age = 0;
-    uint32_t persistent_blocks = 0;
     uint32_t compute_units = 1;  // of the device (rt_create); sizes the walk kernel's grid whatever "persistent_blocks" says
     float* srgb_lut = nullptr;
     // scene
@@ -298,53 +242,24 @@ struct rt_handle {
     InstanceFacts inst;      // the instance phase's decisions of the last upload / update: layout, items, trees, deferred mesh
     std::vector<rt_mesh_uniform> inst_meshes;  // the instance phase's inputs of the last upload / update (rt_refit_triangles
     std::vector<rt_sphere> inst_spheres;       // reruns it)
-    bool lds_scene = false;
-    int cull_roots = -1;            // option: -1 auto (many meshes), 0 off, 1 on (if provable)
-    // option "cross_prune": cross-mesh pruning in the many-mesh product kernels (RenderArgs::cross_prune).  OFF by default since
-    // round 5: its exactness rests on "a triangle hit at t is not found under a box entered far beyond t", which holds for
-    // every random ray ever compared (102 G) but NOT for a ray that grazes a far triangle at ~1e-6 rad from an origin within
-    // ~1e-4 of that triangle's plane in a generic orientation -- there the shader's own t = dot(ao, n) / det is a quotient of
-    // two cancelling sums (tools/prune_directed.py: leaf-box entry up to 1.55 t; tests/test_gpu_prune_directed.py: 1 texel of
-    // 2 M directed rays differs).  A host that prefers 45 % less time on many-mesh scenes over that switches it on.
-    int cross_prune = 0;
-    int force_global = 0;  // option "lds_scene" = 0 disables LDS staging (tuning / tests)
+    bool lds_scene = false;  // the scene fits the LDS beside the stacks (commit_scene; option "lds_scene" = 0 overrides)
     DTexture* textures = nullptr;
     std::vector<uint8_t*> texture_data;
     uint32_t n_textures = 0;
     uint32_t stack_entries = 1;
     bool stack_wide = false, stack_must_wide = false;
-    int force_stack_wide = -1;  // option "stack_wide": -1 auto, 0 one-dword entries when legal, 1 two-dword entries
-    int specialise = 1;            // option "specialise": 0 = always the general kernels
-    int pixel_cache_opt = 1;  // option "pixel_cache"
-    int vote_eighths = -1, vote_patience = -1;  // options "vote_eighths", "vote_patience" (-1: by the kind of launch, render_impl)
-    rt2::PackOptions pack;  // options "tlas", "forest", "flat2", "tlas_min", "defer_min_nodes" (they take effect at the next upload; tests lower the last)
     rt_camera_uniform camera{};
     int count_tests = 0;
     uint32_t last_launch[4] = {0, 0, 0, 0};  // rt_last_launch (entries 4 and 5 are computed when asked)
     bool queues_noted = false;               // the note about GPU_MAX_HW_QUEUES has been left in `err` once
-    // option "max_device_mb" (0 = no cap): upper bound on the device memory the library takes on its OWN initiative -- batch
-    // and pipeline scratch images, primary tables, global-memory memos, the park queues of deferred walks, the snapshot
-    // (not the image, the scene and the textures, which are the host's data).  A feature that does not fit runs the
-    // plainer path (smaller batches, no pipeline, no table, no deferred walks); rt_last_launch reports what is held.
-    size_t max_device_bytes = 0;
     std::string err;
 };
 
 namespace {
 
-// The pipelined single frames (rt_handle::pipeline) keep up to four streams of a handle busy, and ROCm maps a process's
-// streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): with a fifth stream in the process -- the null stream, a
-// framework's copy stream -- two of them share a queue and, if those are two of the pipeline's, their launches serialise
-// (measured: 1.30 -> 1.42 ms per frame, 1.34 -> 1.60 at two frames in flight).  The library does not touch the
-// environment (the variable is the host's, read when the HIP runtime initialises: INTEGRATION.md section 3; the Python
-// package and bench.py set it before they load anything): the automatic depth is four frames in flight when the host
-// has asked for five queues or more, three otherwise (1.29 against 1.23 ms per frame on four queues).  A rank of a
-// strip split whose share no longer fills the machine (world >= 4: 518 K pixels and fewer for 328 K resident lanes) runs
-// seven frames deep when the host has asked for twelve queues or more -- room for the seven streams beside the host's own
-// (a framework's compute and copy streams, RCCL's): a frame's latency is then set by its longest pixel chain, not by its
-// work (rank 0's share of config 2 at world 8: 0.226 -> 0.207 ms per frame; profiles/r04_strip_pipeline_depth.txt).
-// (The variable is read ONCE, when the first handle is created -- the HIP runtime reads it once too, at initialisation: a
-// host that changes it later would otherwise be given a depth for queues it does not have)
+// GPU_MAX_HW_QUEUES as the host set it (rt2::pipeline_depth says why it matters).  The variable is read ONCE, when
+// the first handle is created -- the HIP runtime reads it once too, at initialisation: a host that changes it later would
+// otherwise be given a depth for queues it does not have, ADVICE round 4.
 int hw_queues_requested() {
     static const int queues = [] {
         const char* v = getenv("GPU_MAX_HW_QUEUES");
@@ -353,12 +268,6 @@ int hw_queues_requested() {
     }();
     return queues;
 }
-int automatic_pipeline_depth(uint32_t world) {
-    const int queues = hw_queues_requested();
-    if (world >= 4 && queues >= 12) return 7;
-    return queues >= 5 ? 4 : 3;
-}
-
 thread_local std::string g_err;
 
 int fail(rt_handle* h, int code, const std::string& msg) {
@@ -367,7 +276,7 @@ int fail(rt_handle* h, int code, const std::string& msg) {
     return code;
 }
 
-// bytes of device memory the handle holds on its own initiative (see rt_handle::max_device_bytes)
+// bytes of device memory the handle holds on its own initiative (what option "max_device_mb" bounds)
 size_t optional_bytes(const rt_handle* h) {
     size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary.texels * 64u +
                2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity;
@@ -379,9 +288,9 @@ size_t optional_bytes(const rt_handle* h) {
 }
 // may the handle take `extra` more bytes (after giving back `freed` of what it holds)?
 bool fits_cap(const rt_handle* h, size_t extra, size_t freed = 0) {
-    if (h->max_device_bytes == 0) return true;
+    if (h->opt.max_device_mb == 0) return true;
     const size_t held = optional_bytes(h);
-    return (held > freed ? held - freed : 0) + extra <= h->max_device_bytes;
+    return (held > freed ? held - freed : 0) + extra <= h->opt.max_device_bytes();
 }
 
 #define HIP_TRY(h, expr)                                                                   \
@@ -417,17 +326,8 @@ int regrow(rt_handle* h, T*& p, size_t& have, size_t need, hipStream_t reader) {
     return replace_dev(h, (void**)&p, have, need, sizeof(T));
 }
 
-// workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
-constexpr size_t CU_LDS_BYTES = (160u * 1024u);
-uint32_t blocks_per_cu_for(size_t lds_bytes) {
-    const uint32_t per_cu = lds_bytes ? (uint32_t)(CU_LDS_BYTES / lds_bytes) : BLOCKS_PER_CU;
-    return per_cu > BLOCKS_PER_CU ? BLOCKS_PER_CU : per_cu < 1u ? 1u : per_cu;
-}
-// ... and the persistent grid of the handle at that occupancy (option "persistent_blocks" counts BLOCKS_PER_CU per CU)
-uint32_t persistent_blocks_for(const rt_handle* h, size_t lds_bytes) {
-    const uint32_t fit = (h->persistent_blocks / BLOCKS_PER_CU) * blocks_per_cu_for(lds_bytes);
-    return fit < h->persistent_blocks && fit > 0 ? fit : h->persistent_blocks;
-}
+// (host/launch_options.h repeats these figures of rt_device.h)
+static_assert(rt2::BLOCKS_PER_CU == BLOCKS_PER_CU && rt2::WAVES_PER_BLOCK == WAVES_PER_BLOCK && rt2::MAX_BATCH_FRAMES == RT_MAX_BATCH_FRAMES, "");
 
 // The blend weight pair of frame `frames` (wgsl:157-158): two separate IEEE operations, as the shader rounds them
 // (i32 arithmetic wraps in the shader; frames = -1 gives +inf there too)
@@ -559,7 +459,7 @@ int rt_create(int device_ordinal, uint32_t max_width, uint32_t max_height, rt_ha
         hipDeviceProp_t prop;
         HIP_TRY(h, hipGetDeviceProperties(&prop, device_ordinal));
         // 4 waves per SIMD (the render kernels' register budget) = 4 workgroups of 4 waves per CU
-        h->persistent_blocks = (uint32_t)prop.multiProcessorCount * BLOCKS_PER_CU;
+        h->opt.persistent_blocks = prop.multiProcessorCount * (int)BLOCKS_PER_CU;
         h->compute_units = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 1u;
     }
     static const float lut[256] = {RT_SRGB_LUT_VALUES};
@@ -712,7 +612,7 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
         std::vector<rt2::Quad> head, tail;  // [0, lay.wide_off) and [lay.wide_off, lay.bytes) of the blob
         std::string why;
         int rc = rt2::pack_geometry(meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, g, tail, why);
-        if (rc == RT_OK) rc = rt2::pack_instances(h->pack, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
+        if (rc == RT_OK) rc = rt2::pack_instances(h->opt.pack, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
         if (rc != RT_OK) return fail(h, rc, why);
         const SceneLayout& lay = s.lay;
         std::vector<rt_mesh_uniform> inst_meshes(meshes, meshes + n_meshes);
@@ -786,7 +686,7 @@ int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sp
         InstanceFacts s;
         std::vector<rt2::Quad> head;
         std::string why;
-        int rc = rt2::pack_instances(h->pack, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
+        int rc = rt2::pack_instances(h->opt.pack, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
         if (rc != RT_OK) return fail(h, rc, why);
         std::vector<rt_mesh_uniform> inst_meshes(meshes, meshes + n_meshes);
         std::vector<rt_sphere> inst_spheres(spheres, spheres + n_spheres);
@@ -942,7 +842,7 @@ int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32
             if (mg.root_count == 0 && !mg.unions) g2.roots_are_unions = false;
         InstanceFacts s;
         std::vector<rt2::Quad> head;
-        if (int rc = rt2::pack_instances(h->pack, g2, h->inst_spheres.data(), (uint32_t)h->inst_spheres.size(), h->inst_meshes.data(),
+        if (int rc = rt2::pack_instances(h->opt.pack, g2, h->inst_spheres.data(), (uint32_t)h->inst_spheres.size(), h->inst_meshes.data(),
                                          (uint32_t)h->inst_meshes.size(), s, head, why); rc != RT_OK)
             return done(fail(h, rc, why));
         // ---- write: from here on nothing is refused ----
@@ -1015,112 +915,12 @@ int rt_set_camera(rt_handle* h, const rt_camera_uniform* camera) {
 
 int rt_set_option(rt_handle* h, const char* name, int value) {
     if (!h || !name) return RT_ERR_INVALID_ARGUMENT;
-    std::string n(name);
     h->generation += 1;  // (frames rendered ahead under the old setting are dropped: render_single)
-    if (n == "kernel_variant") {
-        if (value < -1 || value > 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "kernel_variant must be -1 (auto), 0 or 1");
-        h->kernel_variant = value;
-    } else if (n == "persistent_blocks") {
-        if (value < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "persistent_blocks must be >= 1");
-        h->persistent_blocks = (uint32_t)value;
-    } else if (n == "tile_feedback") {
-        h->tile_feedback = value ? 1 : 0;
-        h->history = FrameShape{};
-    } else if (n == "primary_table") {
-        h->use_primary = value ? 1 : 0;
-    } else if (n == "primary_hits") {
-        h->primary_hits = value ? 1 : 0;
-        invalidate_primary_tables(h);
-    } else if (n == "max_device_mb") {
-        if (value < 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "max_device_mb must be >= 0 (0 = no cap)");
-        h->max_device_bytes = (size_t)value << 20;
-    } else if (n == "memo_in_table") {
-        h->memo_in_table = value ? 1 : 0;
-    } else if (n == "primary_per_slot") {
-        h->primary_per_slot = value ? 1 : 0;
-    } else if (n == "tile_feedback_period") {
-        if (value < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "tile_feedback_period must be >= 1");
-        h->tile_feedback_period = value;
-        h->history = FrameShape{};
-    } else if (n == "vote_eighths") {
-        if (value < -1 || value > 8) return fail(h, RT_ERR_INVALID_ARGUMENT, "vote_eighths must be -1 (automatic) or 0..8");
-        h->vote_eighths = value;
-    } else if (n == "vote_patience") {
-        if (value < -1) return fail(h, RT_ERR_INVALID_ARGUMENT, "vote_patience must be -1 (automatic) or >= 0");
-        h->vote_patience = value;
-    } else if (n == "pixel_cache") {
-        if (value < 0 || value > 2) return fail(h, RT_ERR_INVALID_ARGUMENT, "pixel_cache must be 0, 1 or 2 (memo in global memory)");
-        h->pixel_cache_opt = value;
-    } else if (n == "tlas") {
-        h->pack.tlas = value ? 1 : 0;
-    } else if (n == "stack_wide") {
-        if (value < -1 || value > 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "stack_wide must be -1 (auto), 0 or 1");
-        h->force_stack_wide = value;
-    } else if (n == "forest") {
-        h->pack.forest = value ? 1 : 0;
-    } else if (n == "flat2") {
-        h->pack.flat2 = value ? 1 : 0;
-    } else if (n == "tlas_min") {
-        if (value < 2) return fail(h, RT_ERR_INVALID_ARGUMENT, "tlas_min must be >= 2");
-        h->pack.tlas_min = value;
-    } else if (n == "cull_roots") {
-        if (value < -1 || value > 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "cull_roots must be -1 (auto), 0 or 1");
-        h->cull_roots = value;
-    } else if (n == "cross_prune") {
-        h->cross_prune = value ? 1 : 0;
-        invalidate_primary_tables(h);   // (the primary hits in the tables were found by the other walk)
-    } else if (n == "lds_scene") {
-        h->force_global = value ? 0 : 1;
-    } else if (n == "defer_min_nodes") {
-        if (value < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "defer_min_nodes must be >= 1 (takes effect at the next rt_upload_scene)");
-        h->pack.defer_min_nodes = value;
-    } else if (n == "sort_rounds") {
-        if (value < -1 || value > 64) return fail(h, RT_ERR_INVALID_ARGUMENT, "sort_rounds must be -1 (automatic), 0 (off) or 1 .. 64");
-        h->sort_rounds = value;
-    } else if (!RT_EXPERIMENTS && (n == "lds_top" || n == "wavefront" || n == "hybrid" || n == "lds_tlas")) {
-        // (0 = "off" is what this build does anyway: scripts that reset their options keep working)
-        if (value != 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "option " + n + " belongs to the measured-slower experiments: "
-                                    "build with -DRT_EXPERIMENTS=1 (tools/build_variant.sh exp -DRT_EXPERIMENTS=1)");
-    } else if (n == "lds_top") {
-        if (value < -1 || value > 2048) return fail(h, RT_ERR_INVALID_ARGUMENT, "lds_top must be -1 (auto), 0 (off) or a record count <= 2048");
-        h->lds_top = value;
-    } else if (n == "wavefront") {
-        if (value < 0 || value > 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "wavefront must be 0 (off) or 1 (whenever legal)");
-        h->wavefront = value;
-    } else if (n == "pipeline") {
-        if (value < -1 || value > rt_handle::PIPE_MAX) return fail(h, RT_ERR_INVALID_ARGUMENT, "pipeline must be -1 (automatic), 0 (off) or 2 .. 8 (frames in flight)");
-        h->pipeline = value == 1 ? -1 : value;
-    } else if (n == "pipeline_when_idle") {
-        h->pipeline_when_idle = value ? 1 : 0;
-    } else if (n == "frame_ahead") {
-        if (value < -1 || value == 1 || value > (int)RT_MAX_BATCH_FRAMES)
-            return fail(h, RT_ERR_INVALID_ARGUMENT, "frame_ahead must be -1 (automatic), 0 (off) or 2 .. 64 (frames per batch)");
-        h->frame_ahead = value;
-        h->frame_ahead_failed = false;
-    } else if (n == "fast_miss") {
-        h->fast_miss = value ? 1 : 0;
-    } else if (n == "roulette_skip") {
-        h->roulette_skip = value ? 1 : 0;
-    } else if (n == "park_levels") {
-        h->park_levels = value ? 1 : 0;
-    } else if (n == "hybrid") {
-        h->hybrid = value ? 1 : 0;
-    } else if (n == "lds_tlas") {
-        if (value < 0 || value > 2) return fail(h, RT_ERR_INVALID_ARGUMENT, "lds_tlas must be 0 (off), 1 (when it costs no occupancy) or 2 (whenever it fits)");
-        h->lds_tlas = value;
-    } else if (n == "multi_rccl") {
-        if (value < 0 || value > 2) return fail(h, RT_ERR_INVALID_ARGUMENT, "multi_rccl must be 0 (peer copies), 1 (RCCL between distinct devices) or 2 (RCCL always)");
-        h->multi_rccl = value;
-    } else if (n == "specialise") {
-        h->specialise = value ? 1 : 0;
-    } else if (n == "batch_tile_major") {
-        h->batch_tile_major = value ? 1 : 0;
-    } else if (n == "batch_frames") {
-        if (value < 1 || value > (int)RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "batch_frames must be 1..64");
-        h->batch_frames_opt = value;
-    } else {
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown option " + n);
-    }
+    const rt2::SetResult r = rt2::set_option(h->opt, name, value);
+    if (r.code() != RT_OK) return fail(h, r.code(), r.error);
+    if (r.effects & rt2::OPT_DROPS_PRIMARY) invalidate_primary_tables(h);
+    if (r.effects & rt2::OPT_RESETS_TILES) h->history = FrameShape{};
+    if (r.effects & rt2::OPT_CLEARS_AHEAD_FAILED) h->frame_ahead_failed = false;
     return RT_OK;
 }
 
@@ -1174,16 +974,16 @@ static void scene_args(const rt_handle* h, RenderArgs& a) {
     // (an explicitly requested deferred-walk sequence -- option "sort_rounds" > 0, tests -- reads the scene in place: the
     // parking instantiations exist for global-memory scenes only; the automatic setting never defers a mesh of a scene
     // that fits the LDS)
-    a.lds_scene = (h->lds_scene && !h->force_global && !(h->sort_rounds > 0 && h->inst.have_defer)) ? 1u : 0u;
-    a.cull_roots = (h->geom.roots_are_unions && (h->cull_roots == 1 || (h->cull_roots < 0 && h->geom.mesh.size() >= 16))) ? 1u : 0u;
+    a.lds_scene = (h->lds_scene && h->opt.lds_scene && !(h->opt.sort_rounds > 0 && h->inst.have_defer)) ? 1u : 0u;
+    a.cull_roots = (h->geom.roots_are_unions && (h->opt.cull_roots == 1 || (h->opt.cull_roots < 0 && h->geom.mesh.size() >= 16))) ? 1u : 0u;
     a.many_mesh = (h->inst.has_tlas || (a.cull_roots && !h->inst.has_forest)) ? 1u : 0u;
-    a.forest_cull = h->cull_roots != 0 ? 1u : 0u;
-    a.cross_prune = h->cross_prune != 0 ? 1u : 0u;
+    a.forest_cull = h->opt.cull_roots != 0 ? 1u : 0u;
+    a.cross_prune = h->opt.cross_prune != 0 ? 1u : 0u;
     {
         uint32_t ds, dv;
         memcpy(&ds, &h->camera.defocus_strength, 4);
         memcpy(&dv, &h->camera.diverge_strength, 4);
-        a.simple = (h->specialise && h->inst.plain_materials && ds == 0u && dv == 0u) ? 1u : 0u;  // (both strengths +0)
+        a.simple = (h->opt.specialise && h->inst.plain_materials && ds == 0u && dv == 0u) ? 1u : 0u;  // (both strengths +0)
     }
     a.textures = h->textures;
     a.srgb_lut = h->srgb_lut;
@@ -1192,7 +992,7 @@ static void scene_args(const rt_handle* h, RenderArgs& a) {
     a.n_textures = h->n_textures;
     a.stack_entries = h->stack_entries;
     a.tlas_entries = h->inst.tlas_entries;
-    a.stack_wide = (h->stack_must_wide || (h->force_stack_wide < 0 ? h->stack_wide : h->force_stack_wide != 0)) ? 1u : 0u;
+    a.stack_wide = (h->stack_must_wide || (h->opt.stack_wide < 0 ? h->stack_wide : h->opt.stack_wide != 0)) ? 1u : 0u;
     // (the global-memory kernels park a pending mesh hit of 5 dwords in the stack column, intersect_scene)
     if (!a.lds_scene && a.stack_entries < (a.stack_wide ? 3u : 5u)) a.stack_entries = a.stack_wide ? 3u : 5u;
     a.n_items = h->inst.n_items;
@@ -1238,7 +1038,7 @@ static int prepare_batch_scratch(rt_handle* h, RenderArgs& a, const LaunchPlan& 
         // Room for the largest batch the options allow, not just this one: a later, larger batch of the same shape
         // (a warm-up of 5 frames, then 20) must not re-allocate -- a hipMalloc of hundreds of megabytes costs tens of
         // milliseconds -- in the middle of a host's frame sequence.
-        const uint64_t slots = std::max<uint64_t>(n_batch, std::min<uint64_t>((uint64_t)h->batch_frames_opt, RT_MAX_BATCH_FRAMES));
+        const uint64_t slots = std::max<uint64_t>(n_batch, std::min<uint64_t>((uint64_t)h->opt.batch_frames, RT_MAX_BATCH_FRAMES));
         const size_t old_bytes = h->batch_scratch_texels * sizeof(float4);
         if (!fits_cap(h, scratch_stride * n_batch * sizeof(float4), old_bytes))
             return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the scratch images of this batch");
@@ -1264,7 +1064,7 @@ static int prepare_batch_scratch(rt_handle* h, RenderArgs& a, const LaunchPlan& 
     }
     a.batch_frames = n_batch;
     a.batch_stride = scratch_stride;
-    a.batch_tile_major = (uint32_t)h->batch_tile_major;
+    a.batch_tile_major = (uint32_t)h->opt.batch_tile_major;
     return RT_OK;
 }
 
@@ -1298,17 +1098,11 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
     uint32_t strips = (params->height + 7) / 8;
     a.tiles_y = strips / world + (rank < strips % world ? 1 : 0);
     a.count_tests = (uint32_t)h->count_tests;
-    // auto: with about one tile per resident wave there is nothing to refill from, and the
-    // plain one-wave-per-tile dispatch is a little faster (tools/strip_scaling.py)
-    const uint32_t resident_waves = h->persistent_blocks * WAVES_PER_BLOCK;
-    a.kernel_variant = h->kernel_variant >= 0 ? (uint32_t)h->kernel_variant
-                                              : ((uint64_t)a.tiles_x * a.tiles_y * 4 <= (uint64_t)resident_waves * 5 ? 1u : 0u);
-    if (n_batch) a.kernel_variant = 0;  // (frame, tile) work items are the persistent kernel's
-    if (a.count_tests) a.kernel_variant = 0;  // (the counter instantiations exist for the persistent kernel only)
+    a.kernel_variant = rt2::kernel_variant_for(h->opt, (uint64_t)a.tiles_x * a.tiles_y, n_batch, a.count_tests != 0u);
     // (all fields that size the LDS are set by now)
     a.pixel_cache = 0;
     a.pixel_cache_mem = nullptr;
-    if (h->pixel_cache_opt == 1) {
+    if (h->opt.pixel_cache == 1) {
         a.pixel_cache = 1;
         if (render_lds_bytes(a) > LDS_BUDGET_BYTES) a.pixel_cache = 0;  // no room in LDS
     }
@@ -1316,36 +1110,36 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
     // records as fit beside the stacks without costing a workgroup per CU, or what option "lds_top" says
     a.top_base = h->geom.top_mesh_base;
     a.top_count = 0;
-    if (RT_EXPERIMENTS && !a.lds_scene && h->top_available && h->lds_top != 0) {
+    if (RT_EXPERIMENTS && !a.lds_scene && h->top_available && h->opt.lds_top != 0) {
         const size_t used = render_lds_bytes(a);
         uint32_t fit = used < LDS_BUDGET_BYTES ? (uint32_t)((LDS_BUDGET_BYTES - used) / WIDE_REC_BYTES) : 0u;
-        if (h->lds_top > 0) fit = (uint32_t)h->lds_top;
+        if (h->opt.lds_top > 0) fit = (uint32_t)h->opt.lds_top;
         a.top_count = std::min(fit, h->top_available);
     }
     a.tlas_lds = 0;
-    if (RT_EXPERIMENTS && !a.lds_scene && a.many_mesh && h->inst.has_tlas && h->lds_tlas != 0 && params->debug_flag == 0) {
+    if (RT_EXPERIMENTS && !a.lds_scene && a.many_mesh && h->inst.has_tlas && h->opt.lds_tlas != 0 && params->debug_flag == 0) {
         // 1: as many of the breadth-first numbered records (the top levels first) as fit without costing a workgroup per
         // CU; 2: the whole tree if the LDS can hold it at all
         const size_t used = render_lds_bytes(a), need = (size_t)h->inst.n_tlas_records * WIDE_REC_BYTES;
-        const uint32_t per_cu_now = blocks_per_cu_for(used);
-        const size_t room = CU_LDS_BYTES / per_cu_now > used ? CU_LDS_BYTES / per_cu_now - used : 0;
-        if (h->lds_tlas == 2) {
+        const uint32_t per_cu_now = rt2::blocks_per_cu_for(used);
+        const size_t room = rt2::CU_LDS_BYTES / per_cu_now > used ? rt2::CU_LDS_BYTES / per_cu_now - used : 0;
+        if (h->opt.lds_tlas == 2) {
             if (used + need <= 64u * 1024u) a.tlas_lds = h->inst.n_tlas_records;
         } else {
             a.tlas_lds = std::min<uint32_t>(h->inst.n_tlas_records, (uint32_t)(room / WIDE_REC_BYTES));
         }
     }
-    a.persistent_blocks = persistent_blocks_for(h, render_lds_bytes(a));
-    const size_t memo_words = (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
-    if (h->pixel_cache_opt && a.pixel_cache == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
+    a.persistent_blocks = rt2::persistent_blocks_for(h->opt, render_lds_bytes(a));
+    const size_t memo_words = (size_t)h->opt.persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
+    if (h->opt.pixel_cache && a.pixel_cache == 0 && a.kernel_variant == 0 && params->debug_flag == 0 &&
         (h->pixel_cache_words >= memo_words || fits_cap(h, memo_words * sizeof(uint32_t), h->pixel_cache_words * sizeof(uint32_t)))) {
         // persistent kernel: a fixed number of waves, so the cache can live in global memory
         if (int rc = regrow(h, h->pixel_cache_mem, h->pixel_cache_words, memo_words, h->stream); rc != RT_OK) return rc;
         a.pixel_cache = 2;
         a.pixel_cache_mem = h->pixel_cache_mem;
     }
-    a.fast_miss = h->fast_miss != 0 && a.pixel_cache != 0u ? 1u : 0u;
-    a.roulette_skip = h->roulette_skip != 0 && a.pixel_cache != 0u ? 1u : 0u;
+    a.fast_miss = h->opt.fast_miss != 0 && a.pixel_cache != 0u ? 1u : 0u;
+    a.roulette_skip = h->opt.roulette_skip != 0 && a.pixel_cache != 0u ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1353,19 +1147,9 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
 static void plan_rounds(const rt_handle* h, const rt_params* params, const RenderArgs& a, LaunchPlan& pl) {
     const size_t park_records = (size_t)pl.need_texels * (pl.n_batch ? pl.n_batch : 1u);
     const size_t park_bytes = ((park_records + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4);  // per queue
-    uint32_t n_rounds = h->sort_rounds > 0 ? (uint32_t)h->sort_rounds : 0u;
-    if (h->sort_rounds < 0 && h->inst.have_defer) {
-        // (work of the launch in units of one 1920 x 1080 frame at 16 samples per pixel)
-        const double units = (double)park_records * (double)(params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) / (1920.0 * 1080.0 * 16.0);
-        // (tuned on the config 3 and config 5 stand-ins: the longer the walks -- the bigger the mesh's BVH --, the
-        // earlier a round pays for its fixed cost)
-        if (h->inst.defer_internal >= 400000u)
-            // (config 5 stand-in at 3840 x 2160, 64 spp, 16 frames per launch = 256 units: 102.9 / 98.4 / 96.8 / 96.8 / 97.3 ms
-            // per frame with 8 / 12 / 16 / 24 / 32 rounds)
-            // (32 frames per launch = 512 units: 95.6 ms with 16 rounds, 95.0 with 24)
-            n_rounds = units >= 384.0 ? 24u : units >= 96.0 ? 16u : units >= 48.0 ? 12u : units >= 24.0 ? 8u : units >= 12.0 ? 4u : units >= 4.0 ? 3u : units >= 2.0 ? 2u : 0u;
-        else
-            n_rounds = units >= 24.0 ? 6u : units >= 12.0 ? 4u : units >= 8.0 ? 3u : 0u;
+    uint32_t n_rounds = h->opt.sort_rounds > 0 ? (uint32_t)h->opt.sort_rounds : 0u;
+    if (h->opt.sort_rounds < 0 && h->inst.have_defer) {
+        n_rounds = rt2::automatic_rounds(park_records, params->rays_per_pixel, h->inst.defer_internal);
         if (n_rounds && h->park_capacity < park_records) {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || 2 * park_bytes > free_b / 2) n_rounds = 0;  // (both queues within half of what is free: 288 GB are there to be used)
@@ -1379,30 +1163,23 @@ static void plan_rounds(const rt_handle* h, const rt_params* params, const Rende
                 params->rays_per_pixel > 0 && a.lds_scene == 0u;
 }
 
-// The intersection vote (path_begin).  The more a traversal costs beside the rest of an iteration, the longer it pays
-// to let the lanes on memoised primary segments catch up first: 6/8 of the lanes or 3 iterations when the scene is in
-// LDS and walked by the few-mesh kernels (config 2: 1.221 ms per frame; 1.222 with 7/8 and 16, 1.366 with 8/8), 7/8 or
-// 16 iterations otherwise (sponza-sized stand-in 10.69 -> 10.21 ms, 200-mesh stand-in 5.00 -> 4.85), every lane or 16
-// iterations in a deferred-walk sequence, whose resumed pixels arrive in every phase (config 3 stand-in 5.86 -> 5.45,
-// config 5 geometry 3.35 -> 3.22; profiles/r03_experiments/ab_*_vote*.txt).
+// The intersection vote (path_begin): rt2::vote_thresholds.
 static void vote_thresholds(const rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
-    const bool costly = a.lds_scene == 0u || a.many_mesh != 0u;
-    a.vote_eighths = h->vote_eighths >= 0 ? (uint32_t)h->vote_eighths : pl.rounds ? 8u : costly ? 7u : 6u;
-    a.vote_patience = h->vote_patience >= 0 ? (uint32_t)h->vote_patience : (pl.rounds || costly) ? 16u : 3u;
+    rt2::vote_thresholds(h->opt, pl.rounds, a.lds_scene == 0u || a.many_mesh != 0u, a.vote_eighths, a.vote_patience);
 }
 
 // Pipelined single frames: a plain one-frame launch (no batch, no sequence of launches).
 // S is the stream this frame's sampling launch and its bookkeeping run on.
 static int pipeline_acquire(rt_handle* h, const rt_params* params, const RenderArgs& a, LaunchPlan& pl) {
     const uint64_t need_texels = pl.need_texels;
-    const bool wavefront_wanted = RT_EXPERIMENTS && h->wavefront != 0 && a.many_mesh != 0 && !h->geom.any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0;
-    const int pipeline_opt = h->pipeline < 0 ? automatic_pipeline_depth(pl.shape.world) : h->pipeline;
+    const bool wavefront_wanted = RT_EXPERIMENTS && h->opt.wavefront != 0 && a.many_mesh != 0 && !h->geom.any_deep && params->debug_flag == 0 && params->rays_per_pixel > 0;
+    const int pipeline_opt = rt2::pipeline_depth(h->opt, hw_queues_requested(), pl.shape.world);
     if (!h->queues_noted && pipeline_opt != 0 && (hw_queues_requested() < 5 || pipeline_opt + 1 > hw_queues_requested())) {
         // Not an error, said once (rt_last_error after a call that returned RT_OK): the pipeline is limited by, or
         // oversubscribes, the hardware queues the host asked the runtime for.
         h->queues_noted = true;
         h->err = "note: GPU_MAX_HW_QUEUES is " + std::to_string(hw_queues_requested()) + " (read when the first handle was created): " +
-                 (h->pipeline < 0 ? "the frame pipeline runs " + std::to_string(pipeline_opt) + " frames deep instead of 4"
+                 (h->opt.pipeline < 0 ? "the frame pipeline runs " + std::to_string(pipeline_opt) + " frames deep instead of 4"
                                   : "option pipeline = " + std::to_string(pipeline_opt) + " needs " + std::to_string(pipeline_opt + 1) + " queues, its streams will share queues and serialise") +
                  "; export GPU_MAX_HW_QUEUES=8 (12 for strip shares of >= 4 ranks) before the HIP runtime initialises (INTEGRATION.md section 3)";
     }
@@ -1418,7 +1195,7 @@ static int pipeline_acquire(rt_handle* h, const rt_params* params, const RenderA
         for (uint32_t k = 0; k < pipe_depth; ++k) have += h->pipe[k].scratch ? 1u : 0u;
         if (!fits_cap(h, (size_t)(pipe_depth - have) * h->pipe_scratch_texels * sizeof(float4))) pipe = false;
     }
-    if (pipe && h->pipeline_when_idle == 0) {
+    if (pipe && h->opt.pipeline_when_idle == 0) {
         // Every pipelined frame ends with its blend on the handle's stream: an idle stream means no frame is in flight,
         // i.e. this frame has nothing to overlap with (yet).  It takes the plain launch; the frames a host issues while
         // this one runs are pipelined behind it.
@@ -1478,7 +1255,7 @@ static hipError_t barrier_other(rt_handle* h, LaunchPlan& pl) {
         const hipError_t e = hipStreamWaitEvent(pl.S, h->pipe_main, 0);
         if (e != hipSuccess) return e;
     }
-    for (uint32_t k = 0; k < (uint32_t)rt_handle::PIPE_MAX; ++k)
+    for (uint32_t k = 0; k < rt2::PIPE_MAX; ++k)
         if (k != pl.pslot && h->pipe[k].sampled_set) {
             const hipError_t e = hipStreamWaitEvent(pl.S, h->pipe[k].sampled, 0);
             if (e != hipSuccess) return e;
@@ -1526,12 +1303,12 @@ static int bind_primary_table(rt_handle* h, const rt_params* params, RenderArgs&
     // (option max_device_mb: a table that would have to be allocated beyond the cap is done without -- every pixel then
     // computes its own memo; a slot table likewise falls back to the shared one)
     const bool table_fits = h->primary.texels >= texels || fits_cap(h, texels * 64u, h->primary.texels * 64u);
-    if (!(h->use_primary && table_fits && a.pixel_cache != 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 && !(camera_moved && pl.n_batch == 0)))
+    if (!(h->opt.primary_table && table_fits && a.pixel_cache != 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 && !(camera_moved && pl.n_batch == 0)))
         return RT_OK;
     // (the counter kernels re-intersect every segment, so a launch with counters neither needs nor fills the hits)
-    const bool want_hits = h->primary_hits != 0 && a.count_tests == 0u;
+    const bool want_hits = h->opt.primary_hits != 0 && a.count_tests == 0u;
     PrimaryTable& own = h->pipe[pl.pslot].primary;
-    const bool use_own = pl.pipe && !primary_table_serves(h->primary, texels, h->camera, pl.shape, want_hits) && h->primary_per_slot != 0 &&
+    const bool use_own = pl.pipe && !primary_table_serves(h->primary, texels, h->camera, pl.shape, want_hits) && h->opt.primary_per_slot != 0 &&
                          (own.texels >= texels || fits_cap(h, texels * 64u, own.texels * 64u));
     PrimaryTable& t = use_own ? own : h->primary;
     if (!primary_table_serves(t, texels, h->camera, pl.shape, want_hits)) {
@@ -1553,7 +1330,7 @@ static int bind_memo(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
     // With a complete table a lane's memo EQUALS its table entry for the pixel's whole life: the kernels whose memo has no
     // room in LDS read the entry in place (pixel_cache = 4) instead of copying it into a buffer in global memory --
     // that copy was most of what the global-memory kernels wrote and half of what they read.
-    if (a.pixel_cache == 2u && a.lds_scene == 0u && a.primary != nullptr && a.primary_complete != 0u && h->memo_in_table != 0) {
+    if (a.pixel_cache == 2u && a.lds_scene == 0u && a.primary != nullptr && a.primary_complete != 0u && h->opt.memo_in_table != 0) {
         a.pixel_cache = 4u;
         a.pixel_cache_mem = nullptr;
     }
@@ -1562,7 +1339,7 @@ static int bind_memo(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
     // the pipelined frame of slot 0 when pipe_main_need is false (a frame that found the stream idle).
     if (pl.pipe && a.pixel_cache == 2u) {
         PipeSlot& slot = h->pipe[pl.pslot];
-        const size_t need = (size_t)h->persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
+        const size_t need = (size_t)h->opt.persistent_blocks * WAVES_PER_BLOCK * PIXEL_MEMO_DWORDS * 64u;
         if (int rc = regrow(h, slot.memo, slot.memo_words, need, h->stream); rc != RT_OK) return rc;
         a.pixel_cache_mem = slot.memo;
     }
@@ -1582,7 +1359,7 @@ static int prepare_park_queues(rt_handle* h, LaunchPlan& pl) {
         (void)hipGetLastError();
         free_dev(h->park_queue[0]);
         free_dev(h->park_queue[1]);
-        if (h->sort_rounds > 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "sort_rounds: no device memory for the park queues");
+        if (h->opt.sort_rounds > 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "sort_rounds: no device memory for the park queues");
         pl.rounds = false;
     } else {
         h->park_capacity = pl.park_records;
@@ -1596,12 +1373,12 @@ static int prepare_park_queues(rt_handle* h, LaunchPlan& pl) {
 // `tile_feedback_period` frames (costs are recorded in the frame before a refresh), not every frame.
 static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, LaunchPlan& pl) {
     const uint32_t n_tiles = pl.n_tiles;
-    if (!(h->tile_feedback && params->debug_flag == 0 && n_tiles <= h->tile_capacity && n_tiles > 0 && a.kernel_variant == 0)) return RT_OK;
+    if (!(h->opt.tile_feedback && params->debug_flag == 0 && n_tiles <= h->tile_capacity && n_tiles > 0 && a.kernel_variant == 0)) return RT_OK;
     if (h->history != pl.shape) {
         h->have_order = false;
         h->costs_ready = false;
     }
-    if (h->costs_ready && (!h->have_order || h->order_age >= (uint32_t)h->tile_feedback_period)) {
+    if (h->costs_ready && (!h->have_order || h->order_age >= (uint32_t)h->opt.tile_feedback_period)) {
         const long long per_tile = 64ll * (params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) *
                                    (params->number_of_bounces >= 0 ? params->number_of_bounces + 1 : 0);
         const uint32_t max_cost = per_tile > 0xffffffffll ? 0xffffffffu : (uint32_t)per_tile;
@@ -1613,7 +1390,7 @@ static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, L
     }
     const uint32_t frames_now = pl.n_batch ? pl.n_batch : 1u;
     if (h->have_order) a.tile_order = h->tile_order;
-    if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->tile_feedback_period) {
+    if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->opt.tile_feedback_period) {
         h->cost_slot ^= 1;
         a.tile_cost = h->tile_cost[h->cost_slot];
         pl.wrote_tables = true;
@@ -1701,7 +1478,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
 #endif
     const uint32_t R = pl.n_rounds;
     a.park = 1;
-    a.park_levels = (uint32_t)h->park_levels;
+    a.park_levels = (uint32_t)h->opt.park_levels;
     a.q_in = nullptr;
     a.q_in_count = nullptr;
     a.q_out = h->park_queue[0];
@@ -1711,7 +1488,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
     // the big mesh reads its shading record from the full blob.  The last launch (park = 0) and rt_walk_kernel
     // read the full blob as before.
     RenderArgs ah = a;
-    bool hybrid = RT_EXPERIMENTS && h->hybrid != 0 && h->small_ok && !a.lds_scene && a.count_tests == 0 && a.kernel_variant == 0;
+    bool hybrid = RT_EXPERIMENTS && h->opt.hybrid != 0 && h->small_ok && !a.lds_scene && a.count_tests == 0 && a.kernel_variant == 0;
     if (hybrid) {
         ah.blob = h->small_blob;
         ah.lay = h->small_lay;
@@ -1722,7 +1499,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
         ah.top_count = 0;
         ah.stack_entries = h->small_stack_entries ? h->small_stack_entries : 1u;
         ah.stack_wide = 0;
-        ah.pixel_cache = h->pixel_cache_opt ? 1u : 0u;
+        ah.pixel_cache = h->opt.pixel_cache ? 1u : 0u;
         if (ah.pixel_cache && render_lds_bytes(ah) > LDS_BUDGET_BYTES) {
             // (the global-memory memo buffer; the plain launches may read theirs in place from the table -- pixel_cache 4 --,
             // which the LDS-scene kernels of the hybrid launches have not compiled in: a parked pixel's memo is rebuilt from
@@ -1731,10 +1508,10 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
             ah.pixel_cache_mem = h->pixel_cache_mem;
         }
         if (!ah.pixel_cache) ah.primary = nullptr;
-        ah.fast_miss = h->fast_miss != 0 && ah.pixel_cache != 0u ? 1u : 0u;
-        ah.roulette_skip = h->roulette_skip != 0 && ah.pixel_cache != 0u ? 1u : 0u;
+        ah.fast_miss = h->opt.fast_miss != 0 && ah.pixel_cache != 0u ? 1u : 0u;
+        ah.roulette_skip = h->opt.roulette_skip != 0 && ah.pixel_cache != 0u ? 1u : 0u;
         if (render_lds_bytes(ah) > LDS_BUDGET_BYTES) hybrid = false;
-        ah.persistent_blocks = h->persistent_blocks;
+        ah.persistent_blocks = (uint32_t)h->opt.persistent_blocks;
         ah.park_levels = 0;  // (the small blob has no record of the big mesh's BVH)
     }
     if (!hybrid) ah = a;
@@ -1850,17 +1627,15 @@ static int render_frames_impl(rt_handle* h, const rt_params* params, uint32_t n_
     if (n_frames == 1) return render_single(h, params, rank, world);  // (one frame per call: rt_render's path)
     rt_params p = *params;
     uint32_t done = 0;
-    // batches of equal size (20 frames at 16 per launch: 10 + 10, not 16 + 4)
-    uint32_t cap = (uint32_t)h->batch_frames_opt;
-    if (h->max_device_bytes != 0 && world != 0 && rank < world) {   // (option max_device_mb: as many scratch frames as fit; 1 = plain launches)
+    uint32_t cap = (uint32_t)h->opt.batch_frames;
+    if (h->opt.max_device_mb != 0 && world != 0 && rank < world) {   // (option max_device_mb: as many scratch frames as fit; 1 = plain launches)
         const uint64_t texels = FrameShape{params->width, params->height, rank, world}.texels();
         const size_t other = optional_bytes(h) - h->batch_scratch_texels * sizeof(float4);
-        const size_t room = h->max_device_bytes > other ? h->max_device_bytes - other : 0;
+        const size_t room = h->opt.max_device_bytes() > other ? h->opt.max_device_bytes() - other : 0;
         const uint64_t fit = texels ? room / (texels * sizeof(float4)) : cap;
         if (fit < cap) cap = fit >= 2 ? (uint32_t)fit : 1u;
     }
-    const uint32_t launches = (n_frames + cap - 1) / cap;
-    const uint32_t per = launches ? (n_frames + launches - 1) / launches : 0;
+    const uint32_t per = rt2::equal_batch(n_frames, cap);
     while (done < n_frames) {
         uint32_t n = n_frames - done;
         if (n > per) n = per;
@@ -1878,30 +1653,6 @@ static bool same_frame_params(const rt_params& a, const rt_params& b, int32_t b_
     return a.width == b.width && a.height == b.height && a.number_of_bounces == b.number_of_bounces &&
            a.rays_per_pixel == b.rays_per_pixel && a.skybox == b.skybox && a.frames == b_frames && a.accumulate == b.accumulate &&
            a.debug_flag == b.debug_flag && a.debug_scale == b.debug_scale;
-}
-
-// How many frames a call that continues an accumulation renders at once (0: just its own).  Automatic: only when the
-// host runs ahead of the device (`host_waits` false: the call found the stream busy) -- a host that waits for every frame
-// gets its frame from a launch of its own, never behind frames it has not asked for --, and then only for scenes staged
-// in LDS (rays of known cost) and shares so small that a launch of their own leaves lanes idle -- in units of a
-// config-2 frame (1920 x 1080, 8 spp, 5 segments: 1.13 ms), batches of about 4 ms: 28 frames for a strip share of eight
-// ranks (0.201 ms per frame pipelined -> 0.16), 14 for one of four (0.404 -> 0.30), 7 for one of two (0.647 -> 0.59),
-// and none for the whole frame, whose pipelined launches (1.15 ms) a batch of three (1.2 ms) does not beat
-// (tools/strip_scaling.py, profiles/r04_strip_scaling.txt).
-static uint32_t ahead_depth(const rt_handle* h, const rt_params* params, uint64_t need_texels, bool host_waits) {
-    if (params->debug_flag != 0 || params->rays_per_pixel <= 0 || h->count_tests != 0 || params->frames < 1) return 0;
-    if (h->frame_ahead >= 0) return h->frame_ahead >= 2 ? std::min<uint32_t>((uint32_t)h->frame_ahead, RT_MAX_BATCH_FRAMES) : 0u;
-    if (h->frame_ahead_failed || host_waits) return 0;
-    const double segments = (double)need_texels * (double)params->rays_per_pixel *
-                            (double)((params->number_of_bounces < 0 ? 0 : params->number_of_bounces) + 1);
-    // (Scenes read from global memory: rays of unknown cost -- the rule of round 4, "up to 8 frames and about 33 ms by a
-    // work estimate", guessed a frame time and needed a timing probe to take the guess back; a host that wants batches on
-    // such a scene asks for them: frame_ahead = 8 gives config 5's geometry 4.43 -> 3.40 ms per call.)
-    if (!h->lds_scene || h->force_global) return 0;
-    const double ms = segments / (1920.0 * 1080.0 * 8.0 * 5.0) * 1.13;
-    const double d = 4.0 / (ms > 1e-3 ? ms : 1e-3);
-    const uint32_t n = d >= (double)RT_MAX_BATCH_FRAMES ? RT_MAX_BATCH_FRAMES : (uint32_t)d;
-    return n >= 6u ? n : 0u;
 }
 
 // blend slot `slot` of the frames rendered ahead into the image: wgsl:157-158 with the frame's own weight
@@ -1951,10 +1702,10 @@ static int render_single(rt_handle* h, const rt_params* params, uint32_t rank, u
     if (continues && h->have_scene && world != 0 && rank < world && params->width != 0 && params->height != 0) {
         const uint64_t need_texels = FrameShape{params->width, params->height, rank, world}.texels();
         // (a host that WAITS for its frames finds the stream idle; one that runs ahead of the device finds it busy)
-        const bool host_waits = h->frame_ahead < 0 && !(hipSetDevice(h->device) == hipSuccess && hipStreamQuery(h->stream) == hipErrorNotReady);
+        const bool host_waits = h->opt.frame_ahead < 0 && !(hipSetDevice(h->device) == hipSuccess && hipStreamQuery(h->stream) == hipErrorNotReady);
         (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure: not for the launchers' hipGetLastError)
-        uint32_t d = ahead_depth(h, params, need_texels, host_waits);
-        if (h->frame_ahead < 0 && d >= 2) {
+        uint32_t d = rt2::ahead_depth(h->opt, *params, h->count_tests != 0, h->frame_ahead_failed, h->lds_scene, need_texels, host_waits);
+        if (h->opt.frame_ahead < 0 && d >= 2) {
             // (room for the full depth at once: the batches on the way up would each re-allocate the scratch images -- a
             // stream synchronisation apiece)
             if (h->batch_scratch_texels < need_texels * d && fits_cap(h, need_texels * d * sizeof(float4), h->batch_scratch_texels * sizeof(float4)) &&
@@ -1990,7 +1741,7 @@ static int render_single(rt_handle* h, const rt_params* params, uint32_t rank, u
                 return rc;
             }
             // (no room for the batch: this handle renders its frames one by one from now on)
-            if (h->frame_ahead < 0) h->frame_ahead_failed = true;
+            if (h->opt.frame_ahead < 0) h->frame_ahead_failed = true;
             (void)hipGetLastError();
         }
     }
@@ -2047,8 +1798,8 @@ static int render_multi_impl(rt_handle** per_gpu, int n_gpus, const rt_params* p
     for (int r = 0; r < n_gpus; ++r)
         for (int q = 0; q < r; ++q)
             if (per_gpu[r]->device == per_gpu[q]->device) distinct = false;
-    bool use_rccl = distinct && ((root->multi_rccl == 1 && n_gpus > 1) || root->multi_rccl == 2);
-    if (root->multi_rccl == 2 && !distinct)
+    bool use_rccl = distinct && ((root->opt.multi_rccl == 1 && n_gpus > 1) || root->opt.multi_rccl == 2);
+    if (root->opt.multi_rccl == 2 && !distinct)
         return fail(root, RT_ERR_INVALID_ARGUMENT, "multi_rccl = 2 (RCCL always) needs one device per handle: a communicator cannot "
                                                    "hold two ranks of one device (multi_rccl = 1 uses device-to-device copies there)");
     // root-side staging, grown on demand
@@ -2088,9 +1839,9 @@ static int render_multi_impl(rt_handle** per_gpu, int n_gpus, const rt_params* p
                 }
             }
             if (!why.empty()) {
-                if (root->multi_rccl == 2) return fail(root, RT_ERR_DEVICE, why + " (option multi_rccl = 0 selects device-to-device copies)");
+                if (root->opt.multi_rccl == 2) return fail(root, RT_ERR_DEVICE, why + " (option multi_rccl = 0 selects device-to-device copies)");
                 root->err = "rt_render_multi: " + why + "; gathering with device-to-device copies instead";
-                root->multi_rccl = 0;  // (do not try again on every frame)
+                root->opt.multi_rccl = 0;  // (do not try again on every frame)
                 use_rccl = false;
             }
         }
@@ -2215,9 +1966,9 @@ static RenderArgs query_args(const rt_handle* h, const rt_params* params) {
 // Device memory a host-memory call may stage through: at most 64 MB, within what option max_device_mb leaves.
 static size_t staging_room(const rt_handle* h) {
     size_t room = (size_t)64 << 20;
-    if (h->max_device_bytes != 0) {
+    if (h->opt.max_device_mb != 0) {
         const size_t held = optional_bytes(h);
-        room = std::min(room, h->max_device_bytes > held ? h->max_device_bytes - held : 0);
+        room = std::min(room, h->opt.max_device_bytes() > held ? h->opt.max_device_bytes() - held : 0);
     }
     return room;
 }
@@ -2236,7 +1987,7 @@ static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, s
         return fail(h, RT_ERR_INVALID_ARGUMENT, "device rays / results not aligned (16 bytes; 4 for occlusion flags)");
     HIP_TRY(h, hipSetDevice(h->device));
     const RenderArgs a = query_args(h, nullptr);
-    const uint32_t blocks = persistent_blocks_for(h, render_lds_bytes(a));
+    const uint32_t blocks = rt2::persistent_blocks_for(h->opt, render_lds_bytes(a));
     if (!host) {
         HIP_TRY(h, launch_query(a, rays, n, out, any, prune, blocks, h->compute_units, h->stream));
         return RT_OK;
@@ -2484,7 +2235,7 @@ int rt_last_launch(rt_handle* h, uint32_t out[6]) {
     if (!h || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
     for (int k = 0; k < 4; ++k) out[k] = h->last_launch[k];
     out[4] = (uint32_t)((optional_bytes(h) + (1u << 20) - 1) >> 20);   // MiB held on the library's own initiative (option max_device_mb)
-    out[5] = (uint32_t)(h->max_device_bytes >> 20);                     // the cap (0 = none)
+    out[5] = (uint32_t)h->opt.max_device_mb;                              // the cap (0 = none)
     return RT_OK;
 }
 
@@ -2742,18 +2493,76 @@ int rt_test_read_wavefront(rt_handle* h, int which, void* out, uint64_t bytes) {
     return RT_OK;
 }
 
-// Test-only, no GPU needed: the automatic depth of option "frame_ahead" (ahead_depth) for a one-frame call that continues an
-// accumulation -- scene staged in LDS or read from global memory, texels of the call's share, samples per pixel, bounces,
+// Test-only, no GPU needed: the automatic depth of option "frame_ahead" (rt2::ahead_depth) for a one-frame call that continues
+// an accumulation -- scene staged in LDS or read from global memory, texels of the call's share, samples per pixel, bounces,
 // and whether the host counts as one that waits for its frames.  tests/test_frame_ahead_policy.py pins the documented
 // figures with it.
 int rt_test_frame_ahead_depth(int lds_scene, uint64_t texels, int rays_per_pixel, int number_of_bounces, int host_waits) {
-    rt_handle h;
-    h.lds_scene = lds_scene != 0;
     rt_params p{};
     p.rays_per_pixel = rays_per_pixel;
     p.number_of_bounces = number_of_bounces;
     p.frames = 1;
-    return (int)ahead_depth(&h, &p, texels, host_waits != 0);
+    return (int)rt2::ahead_depth(rt2::Options{}, p, false, false, lds_scene != 0, texels, host_waits != 0);
+}
+
+// Test-only, no device and no handle (tests/test_options_host.py): row `index` of the option table, and the setter on a
+// fresh set of options.
+int rt_test_option_table(uint32_t index, char name_out[RT_TEST_OPTION_NAME_BYTES], int32_t info_out[4]) {
+    static_assert(RT_TEST_OPT_BOOLEAN == rt2::OPT_BOOLEAN && RT_TEST_OPT_UPLOAD == rt2::OPT_UPLOAD && RT_TEST_OPT_EXPERIMENT == rt2::OPT_EXPERIMENT &&
+                      RT_TEST_OPT_DROPS_PRIMARY == rt2::OPT_DROPS_PRIMARY && RT_TEST_OPT_RESETS_TILES == rt2::OPT_RESETS_TILES &&
+                      RT_TEST_OPT_CLEARS_AHEAD_FAILED == rt2::OPT_CLEARS_AHEAD_FAILED && RT_TEST_OPT_ONE_IS_AUTO == rt2::OPT_ONE_IS_AUTO &&
+                      RT_TEST_OPT_NOT_ONE == rt2::OPT_NOT_ONE,
+                  "include/rt_test_abi.h repeats the flags of host/launch_options.h");
+    const rt2::OptionRow* row = rt2::option_row(index);
+    if (!row || !name_out || !info_out || strlen(row->name) >= RT_TEST_OPTION_NAME_BYTES) return RT_ERR_INVALID_ARGUMENT;
+    rt2::Options fresh;
+    strcpy(name_out, row->name);
+    const int32_t info[4] = {row->lo, row->hi, row->at(fresh), (int32_t)row->flags};
+    memcpy(info_out, info, sizeof(info));
+    return RT_OK;
+}
+int rt_test_set_option(const char* name, int value, int32_t stored_out[2]) {
+    if (!name || !stored_out) return RT_ERR_INVALID_ARGUMENT;
+    rt2::Options opt;
+    const rt2::SetResult r = rt2::set_option(opt, name, value);
+    stored_out[0] = r.row ? r.row->at(opt) : 0;
+    stored_out[1] = (int32_t)r.effects;
+    return r.code() == RT_OK ? RT_OK : fail(nullptr, r.code(), r.error);
+}
+
+// Test-only, no device and no handle (tests/test_launch_rules_host.py): one launch rule of host/launch_options.h on the
+// option values given (what rt_test_set_option stored for them).
+int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
+    if (!in || !out) return RT_ERR_INVALID_ARGUMENT;
+    rt2::Options opt;
+    uint32_t a = 0, b = 0;
+    switch (which) {
+        case RT_TEST_RULE_VOTES:
+            opt.vote_eighths = (int)in[0];
+            opt.vote_patience = (int)in[1];
+            rt2::vote_thresholds(opt, in[2] != 0, in[3] != 0, a, b);
+            break;
+        case RT_TEST_RULE_ROUNDS: a = rt2::automatic_rounds((size_t)in[0], (int)in[1], (uint32_t)in[2]); break;
+        case RT_TEST_RULE_VARIANT:
+            opt.kernel_variant = (int)in[0];
+            opt.persistent_blocks = (int)in[1];
+            a = rt2::kernel_variant_for(opt, (uint64_t)in[2], (uint32_t)in[3], in[4] != 0);
+            break;
+        case RT_TEST_RULE_DEPTH:
+            opt.pipeline = (int)in[0];
+            a = (uint32_t)rt2::pipeline_depth(opt, (int)in[1], (uint32_t)in[2]);
+            break;
+        case RT_TEST_RULE_BATCH: a = in[1] >= 1 ? rt2::equal_batch((uint32_t)in[0], (uint32_t)in[1]) : 0u; break;
+        case RT_TEST_RULE_GRID:
+            opt.persistent_blocks = (int)in[1];
+            a = rt2::blocks_per_cu_for((size_t)in[0]);
+            b = rt2::persistent_blocks_for(opt, (size_t)in[0]);
+            break;
+        default: return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "unknown rule");
+    }
+    out[0] = a;
+    out[1] = b;
+    return RT_OK;
 }
 
 // Test-only: the grouped gather of rt_render_multi against the RCCL-shaped library at `lib_path`, on fake buffers and

@@ -5,9 +5,12 @@
 //                                 | pack (both phases of the host packer, csrc/host/scene_pack.cpp, on the arrays of a file:
 //                                   four u32 counts -- spheres, meshes, triangles, nodes -- then the four arrays as
 //                                   include/rt_abi.h lays them out; memory safety and return codes only, no blob bits)
+//                                 | options (no file: the option setter, csrc/host/launch_options.cpp, with every name of its
+//                                   table at a grid of values, and with names it has to refuse)
 // Prints "BEGIN <path>" before and "END <rc>" after each file, so that a sanitizer abort names its input.
 // The reference panics on a file it cannot read (src/core/asset.rs:72-75,118); here every malformed input has to come
 // back as an error code.
+#include <climits>
 #include <cstdio>
 #include <fstream>
 #include <stdexcept>
@@ -15,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_abi.h"
+#include "../../ray_tracer_2_amd/csrc/host/launch_options.h"
 #include "../../ray_tracer_2_amd/csrc/host/scene.h"
 #include "../../ray_tracer_2_amd/csrc/host/scene_pack.h"
 
@@ -49,6 +53,34 @@ static int pack_file(const std::string& path) {
     return rc;
 }
 
+// Every row's name and six names without a row (a 4 KiB one, one with bytes >= 0x80), each at the grid of
+// tests/golden/option_behaviour.json: an accepted value is stored inside the row's range with the row's effects, a refusal
+// stores nothing, has a text and no effect.
+static int set_options() {
+    static const int values[] = {INT_MIN, -2, -1, 0, 1, 2, 3, 7, 8, 9, 63, 64, 65, 2048, 2049, INT_MAX};
+    std::vector<std::string> names = {"", "Pipeline", "pipeline ", "no_such_option", std::string(4096, 'p'), "pipeline\x80\xff"};
+    for (size_t k = 0; rt2::option_row(k); ++k) names.push_back(rt2::option_row(k)->name);
+    for (size_t k = 0; k < names.size(); ++k)
+        for (const int value : values) {
+            rt2::Options opt;
+            const rt2::SetResult r = rt2::set_option(opt, names[k].c_str(), value);
+            if ((r.row != nullptr) != (k >= 6)) return -100;
+            if (r.code() != RT_OK && (r.code() != RT_ERR_INVALID_ARGUMENT || r.error.empty() || r.effects != 0u)) return -101;
+            if (!r.row) {
+                if (r.code() == RT_OK || r.error != "unknown option " + names[k]) return -102;
+                continue;
+            }
+            rt2::Options fresh;
+            const int stored = r.row->at(opt), before = r.row->at(fresh);
+            if (r.code() != RT_OK) {
+                if (stored != before) return -103;
+            } else if (stored < r.row->lo || stored > r.row->hi || r.effects != (r.row->flags & rt2::OPT_EFFECTS)) {
+                return -104;
+            }
+        }
+    return RT_OK;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::ifstream manifest(argv[1]);
@@ -79,6 +111,8 @@ int main(int argc, char** argv) {
             if (rc == RT_OK && img.rgba.size() != (size_t)img.width * img.height * 4) rc = -100;  // (a decoder that lies about its output)
         } else if (mode == "pack") {
             rc = pack_file(path);
+        } else if (mode == "options") {
+            rc = set_options();
         } else {
             rc = -101;
         }

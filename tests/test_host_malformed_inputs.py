@@ -188,3 +188,18 @@ def test_malformed_and_unusual_bvhs_through_the_packer_under_asan_and_ubsan(rt, 
     ended = [int(ln[4:]) for ln in out.stdout.splitlines() if ln.startswith("END ")]
     assert out.returncode == 0 and out.stderr == "" and len(ended) == len(cases), out.stderr[-4000:]
     assert ended == [rc for _, _, rc in cases], list(zip((name for name, _, _ in cases), ended))
+
+
+def test_option_names_and_values_through_the_setter_under_asan_and_ubsan(tmp_path):
+    """The option setter (csrc/host/launch_options.cpp) with every name of its table and with names it has to refuse -- empty,
+    wrong case, trailing blank, unknown, 4 KiB long, bytes >= 0x80 -- at the value grid of tests/golden/option_behaviour.json:
+    codes, texts and stored values consistent with the table, without a sanitizer report."""
+    from ray_tracer_2_amd.build import build_host_sanitizer_driver
+    exe = build_host_sanitizer_driver()
+    manifest = tmp_path / "options_manifest.txt"
+    manifest.write_text("options -\n")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:allocator_may_return_null=0:max_allocation_size_mb=2048",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    out = subprocess.run([exe, str(manifest)], capture_output=True, text=True, timeout=300, env=env, errors="replace")
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]
+    assert [ln for ln in out.stdout.splitlines() if ln.startswith("END ")] == ["END 0"], out.stdout

@@ -105,14 +105,28 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
  *   VARIANT  {kernel_variant, persistent_blocks, tiles, frames of the batch (0: single frame), counters on} -> {variant}
  *   DEPTH    {pipeline, GPU_MAX_HW_QUEUES, world} -> {frames in flight}
  *   BATCH    {frames of the sequence, most frames per launch} -> {frames per launch}
- *   GRID     {LDS bytes per workgroup, persistent_blocks} -> {workgroups per CU, persistent grid} */
+ *   GRID     {LDS bytes per workgroup, persistent_blocks} -> {workgroups per CU, persistent grid}
+ *   FRAME_GROUP {frames of the batch, tiles of the launch, resident waves, tile-major order, rounds planned,
+ *                scene in global memory or many-mesh}
+ *               -> {frames per work item, the compile-time cap RT_FRAME_GROUP} */
 #define RT_TEST_RULE_VOTES 0
 #define RT_TEST_RULE_ROUNDS 1
 #define RT_TEST_RULE_VARIANT 2
 #define RT_TEST_RULE_DEPTH 3
 #define RT_TEST_RULE_BATCH 4
 #define RT_TEST_RULE_GRID 5
+#define RT_TEST_RULE_FRAME_GROUP 6
 int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
+
+/* The frame groups of a handle's batches (RenderArgs::frame_group: the frames of a pixel that one lane renders back to
+ * back).  force >= 0 sets the group size of the handle's later batches, 0 = the rule decides (frame_group_for); a
+ * frame-major order, a deferred-walk sequence and a library built with -DRT_FRAME_GROUP=1 still render with 1.
+ * force < 0 changes nothing.  last_out (may be NULL): the group size of the handle's last launch. */
+int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out);
+
+/* The rays per 8x8 tile that the handle's last cost-recording launch counted (option "tile_feedback": the first frame of
+ * a batch, or a single frame): n_tiles counts in tile order, read after everything queued on the handle is done. */
+int rt_test_tile_costs(rt_handle* h, uint32_t* out, uint32_t n_tiles);
 
 /* Test-only: the BVH builder's SAH plane search (find_best_split, bvh.rs:299-351) for host-given nodes, without a build
  * around it: device -1 runs the host search (csrc/host/bvh.cpp: make_host_level_search, no GPU needed), device >= 0 the

@@ -159,6 +159,37 @@ inline uint32_t equal_batch(uint32_t n_frames, uint32_t cap) {
     return launches ? (n_frames + launches - 1) / launches : 0;
 }
 
+// Frames of a batch that a lane renders back to back for the pixel it took (RenderArgs::frame_group; 1: every frame of a
+// tile is a work item of its own).  The work items of a grouped launch are (tile, group) pairs, ceil(n_batch / G) groups
+// per tile: a lane that finishes its pixel's frame starts the pixel's next frame itself, with the memo it already holds,
+// instead of handing the pixel back to be taken -- and its 64-byte table entry to be read -- once per frame.  Groups
+// need the tile-major order (a tile's frames are neighbours there) and a plain launch (the launches of a deferred-walk
+// sequence hand pixels on through park records), and they are taken by the few-mesh kernels on a scene staged in LDS
+// only (`costly`, as for the vote, is every other launch: on the 200-mesh stand-in at 16 frames per launch groups of 4
+// were 2.4 % SLOWER, 4.436 -> 4.543 ms per frame, on the sponza-sized one at 64 per launch 0.5 %: their items are long as
+// it is).
+// What a group saves grows as 1 - 1 / G; what it costs is the launch's tail, which lasts as long as an item, G frames of a
+// tile.  Config 2 at 64 frames per launch (405 tile-frames per resident wave): 1.019 ms per frame ungrouped, 0.943 /
+// 0.896 / 0.882 / 0.899 with G = 2 / 4 / 8 / 16; at 20 per launch (127 per wave): 1.026, and 0.948 / 0.916 / 0.950 / 1.035
+// (profiles/frame_groups_ab.txt).  So G is the largest value up to FRAME_GROUP_CAP and n_batch that leaves the launch
+// FRAME_GROUP_MIN_ITEMS_PER_WAVE items per resident wave -- 8 at 64 frames per launch of the whole frame, 5 at 20, 1 (no
+// groups) for a strip share of eight ranks, 0.8 tiles per resident wave, at the 28 frames of its batches -- and then the
+// smallest value that needs no more groups (20 frames at 8 per group: 7 + 7 + 6, not 8 + 8 + 4; the same number of
+// pixels taken, a shorter longest item).  -DRT_FRAME_GROUP=1 compiles the groups out of the kernels.
+#ifndef RT_FRAME_GROUP
+#define RT_FRAME_GROUP 8
+#endif
+constexpr uint32_t FRAME_GROUP_CAP = RT_FRAME_GROUP, FRAME_GROUP_MIN_ITEMS_PER_WAVE = 24;
+static_assert(FRAME_GROUP_CAP >= 1 && FRAME_GROUP_CAP <= MAX_BATCH_FRAMES, "RT_FRAME_GROUP: 1 .. 64");
+inline uint32_t frame_group_for(uint32_t n_batch, uint64_t tiles, uint32_t resident_waves, bool tile_major, bool rounds,
+                                bool costly = false) {
+    if (n_batch < 2u || !tile_major || rounds || costly) return 1u;
+    uint32_t g = std::min(FRAME_GROUP_CAP, n_batch);
+    while (g > 1u && tiles * ((n_batch + g - 1u) / g) < (uint64_t)resident_waves * FRAME_GROUP_MIN_ITEMS_PER_WAVE) g -= 1u;
+    const uint32_t groups = (n_batch + g - 1u) / g;
+    return (n_batch + groups - 1u) / groups;
+}
+
 // workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
 inline uint32_t blocks_per_cu_for(size_t lds_bytes) {
     const uint32_t per_cu = lds_bytes ? (uint32_t)(CU_LDS_BYTES / lds_bytes) : BLOCKS_PER_CU;

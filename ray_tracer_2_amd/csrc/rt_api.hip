@@ -251,6 +251,7 @@ struct rt_handle {
     rt_camera_uniform camera{};
     int count_tests = 0;
     uint32_t last_launch[4] = {0, 0, 0, 0};  // rt_last_launch (entries 4 and 5 are computed when asked)
+    uint32_t frame_group_forced = 0, last_frame_group = 1;  // rt_test_frame_group (0: rt2::frame_group_for decides)
     bool queues_noted = false;               // the note about GPU_MAX_HW_QUEUES has been left in `err` once
     std::string err;
 };
@@ -1168,6 +1169,21 @@ static void vote_thresholds(const rt_handle* h, RenderArgs& a, const LaunchPlan&
     rt2::vote_thresholds(h->opt, pl.rounds, a.lds_scene == 0u || a.many_mesh != 0u, a.vote_eighths, a.vote_patience);
 }
 
+// Frames of a batch per work item (RenderArgs::frame_group): rt2::frame_group_for, for every launch that has a batch --
+// rt_render_frames, its strips, the frames rendered ahead.
+static void frame_groups(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
+    // (`costly` as for the vote; the one-wave-per-tile kernel and a launch without samples take no groups either)
+    const bool tile_major = a.batch_tile_major != 0u;
+    const bool costly = a.lds_scene == 0u || a.many_mesh != 0u || a.kernel_variant != 0u || a.params.rays_per_pixel <= 0;
+    uint32_t g = rt2::frame_group_for(pl.n_batch, (uint64_t)a.tiles_x * a.tiles_y, a.persistent_blocks * WAVES_PER_BLOCK, tile_major, pl.rounds,
+                                      costly);
+    // (a forced size -- the test library's -- stands in for the cap and the item floor only)
+    if (h->frame_group_forced != 0u && rt2::FRAME_GROUP_CAP > 1u &&
+        rt2::frame_group_for(pl.n_batch, ~0ull, 1u, tile_major, pl.rounds, costly) > 1u)
+        g = std::min(h->frame_group_forced, pl.n_batch);
+    a.frame_group = h->last_frame_group = g;
+}
+
 // Pipelined single frames: a plain one-frame launch (no batch, no sequence of launches).
 // S is the stream this frame's sampling launch and its bookkeeping run on.
 static int pipeline_acquire(rt_handle* h, const rt_params* params, const RenderArgs& a, LaunchPlan& pl) {
@@ -1582,6 +1598,7 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
     if ((rc = choose_kernel_shape(h, params, a, pl)) != RT_OK) return rc;
     plan_rounds(h, params, a, pl);
     vote_thresholds(h, a, pl);
+    frame_groups(h, a, pl);
     if ((rc = pipeline_acquire(h, params, a, pl)) != RT_OK) return rc;
     if ((rc = bind_primary_table(h, params, a, pl)) != RT_OK) return rc;
     if ((rc = bind_memo(h, a, pl)) != RT_OK) return rc;
@@ -2558,10 +2575,35 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
             a = rt2::blocks_per_cu_for((size_t)in[0]);
             b = rt2::persistent_blocks_for(opt, (size_t)in[0]);
             break;
+        case RT_TEST_RULE_FRAME_GROUP:
+            a = rt2::frame_group_for((uint32_t)in[0], (uint64_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0, in[5] != 0);
+            b = rt2::FRAME_GROUP_CAP;
+            break;
         default: return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "unknown rule");
     }
     out[0] = a;
     out[1] = b;
+    return RT_OK;
+}
+
+// Test-only: the frame groups of handle `h` (RenderArgs::frame_group).  force >= 0 sets the group size of its later batches
+// (0: rt2::frame_group_for decides; an order or a launch sequence that takes no groups still gets 1, as does a library
+// built with -DRT_FRAME_GROUP=1); last_out: the group size of the handle's last launch.
+int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out) {
+    if (!h || force > (int)RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "frame group: -1 (leave), 0 (the rule), 1..64");
+    if (force >= 0) h->frame_group_forced = (uint32_t)force;
+    if (last_out) *last_out = h->last_frame_group;
+    return RT_OK;
+}
+
+// Test-only: the rays per tile that the handle's last cost-recording launch counted (tile_feedback: the first frame of a
+// batch, or the single frame), n_tiles of them, once everything queued on the handle is done.
+int rt_test_tile_costs(rt_handle* h, uint32_t* out, uint32_t n_tiles) {
+    if (!h || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!h->tile_cost[h->cost_slot]) return fail(h, RT_ERR_INVALID_ARGUMENT, "the handle has no tile-cost tables");
+    if (n_tiles > h->tile_capacity) return fail(h, RT_ERR_INVALID_ARGUMENT, "more tiles than the handle's frame size has");
+    if (int rc = rt_synchronize(h); rc != RT_OK) return rc;
+    HIP_TRY(h, hipMemcpy(out, h->tile_cost[h->cost_slot], (size_t)n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

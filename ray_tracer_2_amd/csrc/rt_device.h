@@ -192,7 +192,19 @@ struct RenderArgs {
     uint32_t wf_round0;            // 1 => the shade launch that takes the pixels: slots 0 .. wf_slots - 1, no hits yet
     uint32_t wf_slots;             // slots of the launch = wf_frame_slots x frames
     uint32_t wf_frame_slots;       // slots per frame = tiles x 64 (whole 8x8 tiles; pixels outside the image stay empty)
+    // Frame groups (persistent kernel, batch_frames >= 2 in tile-major order; host/launch_options.h: frame_group_for):
+    // >= 2: the work items are (tile, group) pairs, group g = batch frames g * frame_group .. min(batch_frames,
+    // (g + 1) * frame_group) - 1, and the lane that took a pixel renders the group's frames of that pixel back to back.
+    // 0 / 1: (tile, frame) items.  (The last member: the fields above keep their places in the kernarg segment.)
+    uint32_t frame_group;
 };
+// -DRT_FRAME_GROUP=1 compiles the frame groups out of the kernels (RT_FRAME_GROUP caps the G of the rule and has its
+// default there: host/launch_options.h)
+#if defined(RT_FRAME_GROUP) && RT_FRAME_GROUP <= 1
+constexpr bool FRAME_GROUPS = false;
+#else
+constexpr bool FRAME_GROUPS = true;
+#endif
 constexpr uint32_t WF_STATE_PLANES = 6, WF_HIT_PLANES = 2;
 // Park record of a pixel: 14 x 16 B, stored in blocks of 64 records, plane by plane (plane p of record i of block b at
 // float4 index (b * PARK_PLANES + p) * 64 + i), so that the lanes of a wave, which hold consecutive records, store and

@@ -1526,8 +1526,14 @@ struct PixelState {
     int32_t seg;
     bool fresh;
     uint32_t meta;         // rays of this pixel so far (bits 0-15, saturating) | cost-table slot (bits 16-18)
-                           // | index of the pixel's frame inside a frame batch (bits 19-31)
+                           // | index of the pixel's frame inside a frame batch (bits 19-24: at most 63) | frames of the
+                           // pixel's frame group still to come on this lane (bits 25-30; RenderArgs::frame_group)
 };
+// the batch frame of PixelState::meta, and what restarting the pixel for the group's next frame adds to the word's upper half
+// (GROUPS: the kernels whose lanes restart pixels -- everywhere else the bits above the frame are zero)
+template <bool GROUPS>
+DEV uint32_t meta_batch_frame(uint32_t meta) { return GROUPS ? (meta >> 19) & 63u : meta >> 19; }
+constexpr uint32_t META_FRAMES_LEFT_SHIFT = 25, META_NEXT_FRAME = (1u << 19) - (1u << META_FRAMES_LEFT_SHIFT);
 
 // wgsl:479-482: the pixel's focus point
 template <class A>
@@ -1739,6 +1745,17 @@ DEV void pixel_cache_begin(const RenderArgs& a, const A& ca, const CameraConsts&
         pc[0] = __float_as_uint(rd.x); pc[64] = __float_as_uint(rd.y); pc[128] = __float_as_uint(rd.z);
         pc[12 * 64] = constant_ray ? MEMO_RAY : 0u;
     });
+}
+
+// Frame groups (RenderArgs::frame_group): the lane goes on with the next frame of the pixel whose memo it holds.  With a
+// complete table the memo is the pixel's table entry, bit for bit, in every frame (RenderArgs::primary_complete) -- what
+// pixel_cache_begin would load again.  Otherwise memo_hit_store has completed it with the hit of this frame's first
+// sample, which a lane that takes the pixel afresh computes again: the hit is marked absent, so that the first sample of
+// every frame traverses and the `reused` counter stays what one launch per frame counts.  (The other words of a memo
+// without MEMO_HIT_VALID are never read; with pixel_cache == 4 the table is complete.)
+DEV void memo_next_frame(const RenderArgs& a, uint32_t* ls) {
+    if (a.pixel_cache != 0u && a.primary_complete == 0u)
+        with_memo(a, ls, [&](auto pc) { pc[12 * 64] = pc[12 * 64] & ~(uint32_t)MEMO_HIT_VALID; });
 }
 
 // One iteration of the per-lane state machine = path_begin (start the next sample, decide what
@@ -2235,7 +2252,7 @@ DEV void park_load(const RenderArgs& a, uint32_t slot, PixelState& s, uint32_t* 
 }
 
 // wgsl:498 + 154-161
-template <bool LDS, class A>
+template <bool LDS, bool GROUPS = false, class A>
 DEV void pixel_finish(const A& a, const PixelState& s, const uint32_t* ls) {
     float n = (float)a.params.rays_per_pixel;
     f4 total = s.total;
@@ -2244,7 +2261,7 @@ DEV void pixel_finish(const A& a, const PixelState& s, const uint32_t* ls) {
     // wgsl:498: total / f32(rays_per_pixel).  When the count is a power of two its reciprocal is
     // exact, and x * (1/n) and x / n are the same real number rounded once: the same float.
     const float r = a.spp_reciprocal;  // 0: not a power of two
-    const uint32_t bf = s.meta >> 19;
+    const uint32_t bf = meta_batch_frame<GROUPS>(s.meta);
     if (r != 0.0f) store_texel(a, s.x, s.out_row, bf, f4{total.x * r, total.y * r, total.z * r, total.w * r});
     else store_texel(a, s.x, s.out_row, bf, f4{total.x / n, total.y / n, total.z / n, total.w / n});
 }
@@ -2338,7 +2355,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_tiles_k
 // wave's current tile, so the wave stays full until the frame runs out.  The
 // per-pixel RNG stream depends only on the pixel's coordinates, so the image
 // does not depend on which lane rendered which pixel.
-template <bool LDS, bool STATS, bool TLAS, bool PARK, bool SIMPLE, bool HYB = false>
+// GROUPS: the instantiations that render a batch in frame groups (RenderArgs::frame_group; launch_render) -- a kernel of
+// their own, so that every other launch runs the code it ran before there were groups.
+template <bool LDS, bool STATS, bool TLAS, bool PARK, bool SIMPLE, bool HYB = false, bool GROUPS = false>
 __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persistent_kernel(const RenderArgs a) {
 #if defined(RT_DIAG) || defined(RT_WAVE_TIMES)
     const unsigned long long t_wave_start = __builtin_amdgcn_s_memrealtime();
@@ -2357,7 +2376,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
     // work items: (frame, tile) pairs, or -- a later launch of the sorting rounds -- blocks of 64 park records
     const bool resuming = PARK && a.q_in != nullptr;  // (PARK: the instantiations the deferred-walk sequences launch)
     const uint32_t n_parked = resuming ? *a.q_in_count : 0u;
-    const uint32_t n_items = resuming ? (n_parked + 63u) >> 6 : n_tiles * (a.batch_frames ? a.batch_frames : 1u);
+    // (frame groups: (tile, group) pairs; never in a deferred-walk sequence, whose pixels change lanes through park records)
+    // (... nor without samples: such a pixel is stored where it is taken, once per frame)
+    static_assert(!GROUPS || (FRAME_GROUPS && LDS && !TLAS && !PARK && !HYB), "frame groups: the LDS-scene few-mesh kernels");
+    const bool grouped = GROUPS && a.frame_group > 1u && a.batch_frames != 0u && a.batch_tile_major != 0u && have_samples;
+    const uint32_t n_groups = grouped ? (a.batch_frames + a.frame_group - 1u) / a.frame_group : 0u;
+    const uint32_t n_items = resuming ? (n_parked + 63u) >> 6 : n_tiles * (grouped ? n_groups : a.batch_frames ? a.batch_frames : 1u);
     // (a launch with fewer items than waves -- the later rounds of a deferred-walk sequence -- would otherwise consist
     // of thousands of pulls queueing up on one address: the waves beyond the items never pull)
     bool exhausted = PARK && blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6) >= n_items;
@@ -2389,7 +2413,11 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
                     pool_left = n_parked - pool_base < 64u ? n_parked - pool_base : 64u;
                 } else {
                     pool_frame = 0u;
-                    if (a.batch_frames != 0u) {
+                    if (grouped) {  // (tile, group) order: a tile's groups back to back; pool_frame = the group's first frame
+                        const uint32_t tt = t / n_groups;
+                        pool_frame = (t - tt * n_groups) * a.frame_group;
+                        t = tt;
+                    } else if (a.batch_frames != 0u) {
                         if (a.batch_tile_major != 0u) {  // (tile, frame) order: a tile's frames back to back
                             const uint32_t tt = t / a.batch_frames;
                             pool_frame = t - tt * a.batch_frames;
@@ -2431,10 +2459,14 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
                         pixel_begin<total_in_lds(LDS)>(ca, cam, s, ls, px.x, px.y, px.out_row, pool_frame);
                         pixel_cache_begin<false, !LDS>(a, ca, cam, s, ls);
                         s.meta = ((pull_seq & (COST_SLOTS - 1u)) << 16) | (pool_frame << 19);
+                        if (grouped) {  // the group's frames behind this one: the lane restarts the pixel for each (below)
+                            const uint32_t left = a.batch_frames - pool_frame - 1u;
+                            s.meta |= (left < a.frame_group - 1u ? left : a.frame_group - 1u) << META_FRAMES_LEFT_SHIFT;
+                        }
                         if (have_samples) {
                             active = true;
                         } else {
-                            pixel_finish<total_in_lds(LDS)>(ca, s, ls);  // 0 / 0 = NaN, as the shader would store
+                            pixel_finish<total_in_lds(LDS), GROUPS>(ca, s, ls);  // 0 / 0 = NaN, as the shader would store
                             if (a.tile_cost && pool_frame == 0u) tile_cost_add(a, cost_tbl, s);
                         }
                     }
@@ -2458,9 +2490,24 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
             resume_slot = 0xffffffffu;
             if (step == PATH_PIXEL_DONE) {
                 DIAG(16);
-                pixel_finish<total_in_lds(LDS)>(cold_args(), s, ls);
-                if (a.tile_cost && (s.meta >> 19) == 0u) tile_cost_add(a, cost_tbl, s);
+                pixel_finish<total_in_lds(LDS), GROUPS>(cold_args(), s, ls);
+                if (a.tile_cost && meta_batch_frame<GROUPS>(s.meta) == 0u) tile_cost_add(a, cost_tbl, s);
                 active = false;
+                if constexpr (GROUPS) {
+                    if ((s.meta >> META_FRAMES_LEFT_SHIFT) != 0u) {
+                        // Frame group: the same pixel's next frame, on this lane.  What taking the pixel afresh would do
+                        // (pixel_begin: the frame's seed, an empty sum, sample 0) except for the memo, which is the
+                        // pixel's and not the frame's: the lane goes on with the one it holds (memo_next_frame).
+                        const uint32_t carried = (s.meta & 0xffff0000u) + META_NEXT_FRAME;
+                        // (the launch's own arguments, not cold_args(): with the re-read copy the headline instantiation's
+                        // frame grew from 0 to 20 B)
+                        pixel_begin<total_in_lds(LDS)>(a, camera_consts(a), s, ls, s.x, frame_row_of(a, s.out_row), s.out_row,
+                                                       meta_batch_frame<true>(carried));
+                        memo_next_frame(a, ls);
+                        s.meta = carried;
+                        active = true;
+                    }
+                }
             }
         }
         if (step == PATH_PARK) active = false;  // (parked by path_step)
@@ -2965,6 +3012,7 @@ static void with_instantiation(const RenderArgs& a, bool simple, F&& f) {
 // Which instantiations exist (the product library; every one of them is what some BASELINE config or test runs):
 //   persistent <LDS | global> x <few-mesh: general, SIMPLE, counters | many-mesh: general, counters>   = 10
 //   + the deferred-walk launches, global-memory few-mesh scenes only: general, SIMPLE, counters            =  3
+//   + batches in frame groups, LDS few-mesh scenes only: general, SIMPLE, counters                           =  3
 //   one wave per tile (small launches) <LDS | global> x <few-mesh: general, SIMPLE | many-mesh: general> =  6
 // Counter launches always take the persistent kernel; a scene that fits the LDS has no mesh worth deferring (the host
 // never asks: rt_api.hip render_impl).  -DRT_EXPERIMENTS=1 adds the hybrid launches and the wavefront kernels.
@@ -2985,7 +3033,15 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t stream) {
             auto persistent = [&](auto park_tag, auto hyb_tag) {  // (counters: the general code, SIMPLE is off with them)
                 constexpr bool PARK = decltype(park_tag)::value, HYB = decltype(hyb_tag)::value;
                 if constexpr (!HYB) {
+                    if constexpr (FRAME_GROUPS && LDS && !TLAS && !PARK) {
+                        if (a.count_tests && a.frame_group > 1u)
+                            return launch_k(rt_render_persistent_kernel<LDS, true, TLAS, PARK, false, false, true>, blocks, lds, stream, a);
+                    }
                     if (a.count_tests) return launch_k(rt_render_persistent_kernel<LDS, true, TLAS, PARK, false>, blocks, lds, stream, a);
+                }
+                // frame groups (host/launch_options.h: frame_group_for asks for them on these kernels only)
+                if constexpr (FRAME_GROUPS && LDS && !TLAS && !PARK && !HYB) {
+                    if (a.frame_group > 1u) return launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB, true>, blocks, lds, stream, a);
                 }
                 launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB>, blocks, lds, stream, a);
             };

@@ -8,7 +8,7 @@ Each file is split per kernel (`.type NAME,@function` ... `.Lfunc_endN`).  Label
 the file (.LBB<n>_, .Lfunc_end<n>, .LJTI<n>_, ...) are renumbered and comments (the `%bb.` ones among them) dropped, so
 that moving code between files or reordering functions cannot show up as a difference.  Printed per kernel: identical
 or different, instruction counts, and vgpr / sgpr / agpr / scratch / LDS from the metadata, with the waves-per-SIMD tier
-floor(512 / roundup(vgpr, 8)).  Exit status 1 when the two files do not hold the same set of kernels.
+floor(512 / roundup(vgpr, 8)).  Instantiations renamed by a new trailing `false` template argument are matched to their old names.  Exit status 1 when the two files do not hold the same set of kernels.
 """
 import re
 import sys
@@ -69,6 +69,15 @@ def main(argv):
         print(__doc__)
         return 2
     (md_a, body_a), (md_b, body_b) = load(argv[1]), load(argv[2])
+    # A template that gained a trailing bool argument renames its old instantiations (`...Lb0EEEvNS_` -> `...Lb0ELb0EEEvNS_`):
+    # a kernel of the first file that is missing from the second is compared with the second's kernel of that longer name
+    # (argument false), under the first file's name.
+    for name in sorted(set(md_a) - set(md_b)):
+        longer = name.replace("EEEvNS_", "ELb0EEEvNS_", 1)
+        if longer != name and longer in md_b and longer not in md_a:
+            md_b[name] = md_b.pop(longer)
+            body_b[name] = [l.replace(longer, name) for l in body_b.pop(longer)]
+            print(f"  compared under its old name: {longer}")
     only_a, only_b = sorted(set(md_a) - set(md_b)), sorted(set(md_b) - set(md_a))
     print(f"kernels: {len(md_a)} in {argv[1]}, {len(md_b)} in {argv[2]}; name sets {'equal' if not only_a and not only_b else 'DIFFER'}")
     for n in only_a:

@@ -566,6 +566,43 @@ typedef struct rt_gbuffer {
 enum { RT_GBUFFER_HOST_MEMORY = 1 };
 int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* out, int flags);
 
+/* Radiance along rays the caller supplies: the path tracer (`trace`, wgsl:398-471) for rays that
+ * need not come from the library's pinhole camera -- light probes, lightmap texels, panoramic / fisheye / orthographic /
+ * cube-map cameras, re-sampling chosen pixels.  For ray i the call runs `frag`'s sample loop (wgsl:486-498) with the ray
+ * held fixed, bit for bit:
+ *     state = seed;
+ *     for each of params->rays_per_pixel samples: four draws of the generator (the ones `frag` spends on the camera
+ *         jitter, wgsl:488-492), then total += trace(ray, &state) -- `trace` normalises dir (wgsl:400);
+ *     out[i] = total / f32(rays_per_pixel), all four components.
+ * So a ray with origin = cam_to_world[3], dir = texel (x, y) of rt_render_gbuffer's `dir` plane and
+ * seed = y * width + x + |frames| * 719393 (u32 arithmetic) gets the bits rt_render writes to that texel for
+ * frames <= 0 under a camera without jitter (both strengths +0, no component of the camera origin or of the texel's
+ * focus point being -0).
+ * Of `params` only number_of_bounces (>= 0), rays_per_pixel (>= 1) and skybox matter (other values of the first two:
+ * RT_ERR_INVALID_ARGUMENT); width, height, frames, accumulate and the debug fields are ignored.  The handle's camera,
+ * image, primary tables and options do not enter the result (the options that choose the scene's instantiation and
+ * placement at upload apply and, as for a render, never change a bit).
+ * A ray with a non-finite component, a direction whose normalisation is not finite and non-zero, or _p0 != 0 gets
+ * (0, 0, 0, 0) (never an error).
+ * Memory, ordering and limits as rt_intersect_rays: without RT_RADIANCE_HOST_MEMORY `rays` and `rgba32f_out` are device
+ * pointers on the handle's device (16-byte aligned) and the call is asynchronous on the handle's stream, after every
+ * earlier call on the handle and before every later one; with it they are host pointers, staged through a temporary
+ * device buffer of at most 64 MB per chunk (48 bytes per ray), counted against option "max_device_mb" while held
+ * (RT_ERR_OUT_OF_MEMORY when not even one ray fits), and the call returns when the results are on the host.
+ * n = 0 is a no-op; n > 2^31 - 1 gives RT_ERR_CAPACITY; no scene: RT_ERR_NO_SCENE; null handle / params / rays / out,
+ * unknown flags or misaligned device pointers: RT_ERR_INVALID_ARGUMENT.  On any error nothing is written.
+ * Like the ray queries the call leaves the image, the primary tables, a frame_ahead batch in flight, the pipeline slots,
+ * rt_get_stats and rt_last_launch as they are, and ignores rt_set_counters. */
+typedef struct rt_path_ray {       /* 32 bytes, two 16-byte loads */
+    float origin[3];
+    uint32_t seed;                 /* the ray's RNG state before its first sample (wgsl:475 for a pixel) */
+    float dir[3];                  /* any finite non-zero length */
+    uint32_t _p0;                  /* must be 0 */
+} rt_path_ray;
+enum { RT_RADIANCE_HOST_MEMORY = 1 };
+int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* rays, uint64_t n,
+                     float* rgba32f_out /* [n][4] */, int flags);
+
 /* The test-only entry points (rt_test_*: the kernels' arithmetic building blocks evaluated element-wise on the device, raw
  * copies of sequence buffers, the RCCL gather against a stub, the frame_ahead policy) are NOT exported by the product
  * library: include/rt_test_abi.h declares them and ray_tracer_2_amd/librt2_mi355x_test.so -- the same sources compiled

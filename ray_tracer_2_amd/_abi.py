@@ -89,6 +89,10 @@ class Hit(C.Structure):  # rt_hit: a ray query's closest-hit record
                 ("normal", f32 * 3), ("bary_v", f32), ("tex_u", f32), ("tex_v", f32), ("_p1", f32 * 2)]
 
 
+class PathRay(C.Structure):  # rt_path_ray: a radiance query's input
+    _fields_ = [("origin", f32 * 3), ("seed", u32), ("dir", f32 * 3), ("_p0", u32)]
+
+
 class GBuffer(C.Structure):  # rt_gbuffer: the planes rt_render_gbuffer writes (a NULL plane is not produced)
     _fields_ = [("struct_bytes", u32), ("_p0", u32), ("depth", C.c_void_p), ("dir", C.c_void_p), ("point", C.c_void_p),
                 ("normal", C.c_void_p), ("bary", C.c_void_p), ("texcoord", C.c_void_p), ("albedo", C.c_void_p),
@@ -129,9 +133,12 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<u4"), ("primitive", "<u4"), ("f
                       ("bary_u", "<f4"), ("normal", "<f4", 3), ("bary_v", "<f4"), ("tex_u", "<f4"), ("tex_v", "<f4"),
                       ("_p1", "<f4", 2)])
 assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
+PATH_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("seed", "<u4"), ("dir", "<f4", 3), ("_p0", "<u4")])
+assert PATH_RAY_DTYPE.itemsize == C.sizeof(PathRay) == 32
 HIT_HIT, HIT_BACKFACE = 1, 2
 QUERY_HOST_MEMORY, QUERY_PRUNE_TMAX = 1, 2
 REFIT_HOST_MEMORY = 1
+RADIANCE_HOST_MEMORY = 1
 MISS = 0xFFFFFFFF
 
 # SceneLayout (csrc/rt_scene_format.h): the 12 words rt_test_scene_blob returns; the head of the blob is [0, wide_off)

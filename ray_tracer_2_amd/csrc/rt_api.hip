@@ -44,6 +44,8 @@ hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long lon
                         uint32_t blocks, uint32_t compute_units, hipStream_t stream);
 hipError_t launch_pick_ray(const RenderArgs& a, uint32_t x, uint32_t y, float4* ray, hipStream_t stream);
 hipError_t launch_gbuffer(const RenderArgs& a, const GBufferArgs& g, hipStream_t stream);
+hipError_t launch_radiance(const RenderArgs& a, const void* rays, uint32_t n, void* out, uint32_t* next_ray, uint32_t compute_units,
+                           hipStream_t stream);
 hipError_t launch_wf_shade(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_wf_walk(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
 size_t wf_walk_lds_bytes(const RenderArgs& a);
@@ -1990,6 +1992,32 @@ static size_t staging_room(const rt_handle* h) {
     return room;
 }
 
+// The loop of a host-memory call (the ray queries, rt_render_gbuffer, rt_radiance_rays): one temporary device buffer of
+// `bytes` (what_for: its name in the out-of-memory message), then step(buf, i0, m, what) for the chunks [i0, i0 + m) of the
+// call's n items.  A step queues its chunk's copies and launch on the handle's stream; when one of them fails it names it in
+// `what` and returns its error.  The stream is drained after every chunk -- the buffer is used again, and the results are on
+// the host when the call returns -- and before the buffer is freed, whatever happened.
+extern "C++" {
+template <class Step>
+static int staged_chunks(rt_handle* h, size_t bytes, uint64_t n, uint64_t chunk, const char* what_for, Step&& step) {
+    auto hip_fail = [&](const char* what, hipError_t e) { return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
+    uint8_t* buf = nullptr;
+    hipError_t e = hipMalloc((void**)&buf, bytes);
+    if (e != hipSuccess)
+        return e == hipErrorOutOfMemory ? fail(h, RT_ERR_OUT_OF_MEMORY, std::string("no device memory for ") + what_for) : hip_fail("hipMalloc", e);
+    int rc = RT_OK;
+    for (uint64_t i0 = 0; rc == RT_OK && i0 < n; i0 += chunk) {
+        const char* what = "hipStreamSynchronize";
+        e = step(buf, i0, std::min<uint64_t>(chunk, n - i0), what);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(what, e);
+    }
+    if (rc != RT_OK) (void)hipStreamSynchronize(h->stream);  // (nothing may still use the buffer when it is freed)
+    free_dev(buf);
+    return rc;
+}
+}  // extern "C++" (a template among the C entry points)
+
 // out_bytes: bytes of output per ray (sizeof(rt_hit) or 4)
 static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, size_t out_bytes, int flags, bool any) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
@@ -2009,31 +2037,18 @@ static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, s
         HIP_TRY(h, launch_query(a, rays, n, out, any, prune, blocks, h->compute_units, h->stream));
         return RT_OK;
     }
-    // host memory: chunks of at most 64 MB of device memory (rays and results), within option max_device_mb
+    // host memory: chunks of at most 64 MB of device memory (rays, then results), within option max_device_mb
     const size_t per_ray = sizeof(rt_ray) + out_bytes;
     const uint64_t chunk = std::min<uint64_t>(n, staging_room(h) / per_ray);
     if (chunk == 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for a query's staging buffers");
-    void* d_rays = nullptr;
-    void* d_out = nullptr;
-    int rc = RT_OK;
-    auto hip_fail = [&](const char* what, hipError_t e) { return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
-    hipError_t e = hipMalloc(&d_rays, chunk * sizeof(rt_ray));
-    if (e == hipSuccess) e = hipMalloc(&d_out, chunk * out_bytes);
-    if (e != hipSuccess) {
-        rc = e == hipErrorOutOfMemory ? fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for a query's staging buffers")
-                                      : hip_fail("hipMalloc", e);
-    }
-    for (uint64_t i0 = 0; rc == RT_OK && i0 < n; i0 += chunk) {
-        const uint64_t m = std::min<uint64_t>(chunk, n - i0);
-        if ((e = hipMemcpyAsync(d_rays, rays + i0, m * sizeof(rt_ray), hipMemcpyHostToDevice, h->stream)) != hipSuccess) { rc = hip_fail("hipMemcpyAsync", e); break; }
-        if ((e = launch_query(a, d_rays, m, d_out, any, prune, blocks, h->compute_units, h->stream)) != hipSuccess) { rc = hip_fail("launch_query", e); break; }
-        if ((e = hipMemcpyAsync(static_cast<uint8_t*>(out) + i0 * out_bytes, d_out, m * out_bytes, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) { rc = hip_fail("hipMemcpyAsync", e); break; }
-        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) { rc = hip_fail("hipStreamSynchronize", e); break; }
-    }
-    if (rc != RT_OK) (void)hipStreamSynchronize(h->stream);  // (nothing may still use the buffers when they are freed)
-    free_dev(d_rays);
-    free_dev(d_out);
-    return rc;
+    return staged_chunks(h, chunk * per_ray, n, chunk, "a query's staging buffers", [&](uint8_t* buf, uint64_t i0, uint64_t m, const char*& what) {
+        uint8_t* d_out = buf + chunk * sizeof(rt_ray);
+        hipError_t e = hipSuccess;
+        if (what = "hipMemcpyAsync", (e = hipMemcpyAsync(buf, rays + i0, m * sizeof(rt_ray), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+        if (what = "launch_query", (e = launch_query(a, buf, m, d_out, any, prune, blocks, h->compute_units, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        return hipMemcpyAsync(static_cast<uint8_t*>(out) + i0 * out_bytes, d_out, m * out_bytes, hipMemcpyDeviceToHost, h->stream);
+    });
 }
 
 int rt_intersect_rays(rt_handle* h, const rt_ray* rays, uint64_t n, rt_hit* hits, int flags) {
@@ -2113,38 +2128,81 @@ int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* o
     const size_t row_bytes = (size_t)W * per_texel;
     const uint32_t band = room > slack ? (uint32_t)std::min<uint64_t>(H, (room - slack) / row_bytes) : 0u;
     if (band == 0u) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for one row of the G-buffer's staging planes");
-    auto hip_fail = [&](const char* what, hipError_t e) { return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
-    uint8_t* d_buf = nullptr;
-    void* d_ptr[11] = {};
+    size_t plane_off[11] = {};
     size_t off = 0;
     for (int c = 0; c < 11; ++c) {
         if (!ptr[c]) continue;
-        d_ptr[c] = (void*)off;   // (offset for now)
+        plane_off[c] = off;
         off = (off + (size_t)band * W * bytes[c] + 255u) & ~(size_t)255u;
     }
-    hipError_t e = hipMalloc((void**)&d_buf, off);
-    if (e != hipSuccess)
-        return e == hipErrorOutOfMemory ? fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the G-buffer's staging planes") : hip_fail("hipMalloc", e);
-    for (int c = 0; c < 11; ++c)
-        if (ptr[c]) d_ptr[c] = d_buf + (size_t)d_ptr[c];
-    bind(d_ptr);
-    int rc = RT_OK;
-    for (uint32_t r0 = 0; rc == RT_OK && r0 < H; r0 += band) {
-        g.row0 = r0;
-        g.rows = std::min(band, H - r0);
-        if ((e = launch_gbuffer(a, g, h->stream)) != hipSuccess) { rc = hip_fail("launch_gbuffer", e); break; }
-        for (int c = 0; c < 11 && rc == RT_OK; ++c) {
+    return staged_chunks(h, off, H, band, "the G-buffer's staging planes", [&](uint8_t* buf, uint64_t r0, uint64_t rows, const char*& what) {
+        void* d_ptr[11] = {};
+        for (int c = 0; c < 11; ++c)
+            if (ptr[c]) d_ptr[c] = buf + plane_off[c];
+        bind(d_ptr);
+        g.row0 = (uint32_t)r0;
+        g.rows = (uint32_t)rows;
+        hipError_t e = hipSuccess;
+        if (what = "launch_gbuffer", (e = launch_gbuffer(a, g, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        for (int c = 0; c < 11 && e == hipSuccess; ++c) {
             if (!ptr[c]) continue;
             const size_t row = (size_t)W * bytes[c];
-            if ((e = hipMemcpyAsync(static_cast<uint8_t*>(ptr[c]) + r0 * row, d_ptr[c], g.rows * row, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-                rc = hip_fail("hipMemcpyAsync", e);
+            e = hipMemcpyAsync(static_cast<uint8_t*>(ptr[c]) + r0 * row, d_ptr[c], rows * row, hipMemcpyDeviceToHost, h->stream);
         }
-        if (rc != RT_OK) break;
-        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) { rc = hip_fail("hipStreamSynchronize", e); break; }
+        return e;
+    });
+}
+
+// ---- radiance along rays the host gives (include/rt_abi.h: rt_radiance_rays; rt_queries.inl: rt_radiance_kernel) ----
+// Launched like a query: the arguments a render of the scene takes, the caller's bounces, samples and skybox, nothing read
+// but the scene and the rays and nothing written but the caller's output (and a launch counter of the handle's ring).
+static_assert(sizeof(rt_path_ray) == 32, "rt_path_ray layout");
+
+int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* rays, uint64_t n, float* rgba32f_out, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_RADIANCE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (n == 0) return RT_OK;
+    if (!params || !rays || !rgba32f_out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (params->number_of_bounces < 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "number_of_bounces must be >= 0");
+    if (params->rays_per_pixel < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "rays_per_pixel must be >= 1");
+    if (n > 0x7fffffffull) return fail(h, RT_ERR_CAPACITY, "more than 2^31 - 1 rays");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    const bool host = (flags & RT_RADIANCE_HOST_MEMORY) != 0;
+    if (!host && ((((uintptr_t)rays) | ((uintptr_t)rgba32f_out)) & 15u) != 0u)
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "device rays / results not aligned (16 bytes)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    RenderArgs a = query_args(h, nullptr);
+    a.params.number_of_bounces = params->number_of_bounces;
+    a.params.rays_per_pixel = params->rays_per_pixel;
+    a.params.skybox = params->skybox;
+    a.spp_reciprocal = (params->rays_per_pixel & (params->rays_per_pixel - 1)) == 0 ? 1.0f / (float)params->rays_per_pixel : 0.0f;  // (frame_constants)
+    // SIMPLE from the scene alone: the rays are the caller's, the handle's camera has no part in them
+    a.simple = (h->opt.specialise && h->inst.plain_materials) ? 1u : 0u;
+    // The first hit of a ray serves all its samples from the lane's LDS memo, wherever a workgroup's LDS can hold one (a
+    // ray of one sample has nothing to reuse); with it path_end's and the pre-step's shortcuts on that memo.
+    a.pixel_cache = params->rays_per_pixel > 1 ? 1u : 0u;
+    if (a.pixel_cache && render_lds_bytes(a) > rt2::CU_LDS_BYTES) a.pixel_cache = 0u;
+    a.fast_miss = a.roulette_skip = a.pixel_cache;
+    uint32_t* next_ray = nullptr;
+    if (!host) {
+        HIP_TRY(h, h->work.next(h->stream, next_ray));
+        HIP_TRY(h, launch_radiance(a, rays, (uint32_t)n, rgba32f_out, next_ray, h->compute_units, h->stream));
+        return RT_OK;
     }
-    if (rc != RT_OK) (void)hipStreamSynchronize(h->stream);  // (nothing may still use the buffer when it is freed)
-    free_dev(d_buf);
-    return rc;
+    // host memory: chunks of at most 64 MB of device memory (rays, then results: 48 bytes per ray), within option max_device_mb
+    const size_t per_ray = sizeof(rt_path_ray) + sizeof(float4);
+    const uint64_t chunk = std::min<uint64_t>(n, staging_room(h) / per_ray);
+    if (chunk == 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for a radiance call's staging buffers");
+    return staged_chunks(h, chunk * per_ray, n, chunk, "a radiance call's staging buffers", [&](uint8_t* buf, uint64_t i0, uint64_t m, const char*& what) {
+        uint8_t* d_out = buf + chunk * sizeof(rt_path_ray);
+        hipError_t e = hipSuccess;
+        if (what = "hipMemcpyAsync", (e = hipMemcpyAsync(buf, rays + i0, m * sizeof(rt_path_ray), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+        if (what = "CounterRing::next", (e = h->work.next(h->stream, next_ray)) != hipSuccess) return e;
+        if (what = "launch_radiance", (e = launch_radiance(a, buf, (uint32_t)m, d_out, next_ray, h->compute_units, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        return hipMemcpyAsync(rgba32f_out + 4 * i0, d_out, m * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
+    });
 }
 
 int rt_synchronize(rt_handle* h) {

@@ -3109,7 +3109,7 @@ hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width
     return hipGetLastError();
 }
 
-#include "rt_queries.inl"  // rt_query_kernel, rt_pick_ray_kernel, rt_gbuffer_kernel and their launchers
+#include "rt_queries.inl"  // rt_query_kernel, rt_pick_ray_kernel, rt_gbuffer_kernel, rt_radiance_kernel and their launchers
 
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0

@@ -1,4 +1,4 @@
-// rt_queries.inl -- the ray-query, pick and G-buffer kernels with their launchers (included by rt_kernel.hip inside
+// rt_queries.inl -- the ray-query, pick, G-buffer and radiance kernels with their launchers (included by rt_kernel.hip inside
 // namespace rtd, behind the render kernels and the launch helpers they share: launch_k, with_instantiation).
 // ---------------------------------------------------------------------------
 // Ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick; include/rt_abi.h): intersect_scene for rays the host gives,
@@ -208,6 +208,176 @@ hipError_t launch_gbuffer(const RenderArgs& a, const GBufferArgs& g, hipStream_t
     with_instantiation(a, render_takes_simple(a), [&](auto lds_tag, auto tlas_tag, auto simple_tag) {
         launch_k(rt_gbuffer_kernel<decltype(lds_tag)::value, decltype(tlas_tag)::value, decltype(simple_tag)::value>, blocks, lds,
                  stream, a, g);
+    });
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Radiance queries (rt_radiance_rays; include/rt_abi.h): `frag`'s sample loop (wgsl:486-498) for rays
+// the host gives, the ray held fixed -- per ray: state = seed; per sample the four draws of the camera jitter (a jump, as
+// path_begin makes them for a constant primary ray), then total += trace(ray, &state); out = total / f32(rays_per_pixel).
+// rays: rt_path_ray records (32 B: origin, seed, dir, _p0).  One lane per ray in persistent waves with the render kernel's
+// refill: a wave claims 64 consecutive rays from a shared counter and hands them to its lanes as they finish theirs
+// (ballot + mbcnt), so no lane waits for the wave's slowest ray.  out[i] is ray i's whoever computed it.
+// The ray is the same for every sample, so its first hit is the pixel memo's case: with RenderArgs::pixel_cache == 1 the
+// lane keeps the hit of sample 0 in its LDS memo (memo_hit_store) and samples 1.. take it from there (memo_hit_load) --
+// with them path_end's fast_miss and the pre-step's roulette_skip, which are defined on that memo.  pixel_cache == 0 (the
+// host found no room in the LDS): every sample traverses.  Shading, roulette and the sum are path_end's; the ray itself
+// is read again from `rays` at every sample (two 16-byte loads) rather than held in six registers across the walk.
+// A ray that rt_query_kernel would call invalid (tmax = +INF) gets zeros.
+// ---------------------------------------------------------------------------
+// the ray of record i, normalised as trace does it (wgsl:400); returns whether a query traces it (ray_is_valid)
+template <bool SQ>
+DEV bool path_ray_of(const float4* __restrict__ rays, uint32_t i, f3& ro, f3& rd, uint32_t& seed) {
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+    const f3 d{r1.x, r1.y, r1.z};
+    ro = f3{r0.x, r0.y, r0.z};
+    rd = normalize3<SQ>(d);
+    seed = fbits(r0.w);
+    return ray_is_valid(ro, d, rd, __builtin_inff(), fbits(r1.w));
+}
+
+// A lane takes ray i (pixel_begin's counterpart: PixelState::x is the ray's index, the memo holds a ray and no hit yet)
+template <bool TOTAL_LDS>
+DEV void ray_begin(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_t i, uint32_t seed) {
+    s.x = i;
+    s.out_row = 0u;
+    s.rng = seed;
+    if constexpr (TOTAL_LDS) {
+        ls[0] = 0u; ls[64] = 0u; ls[128] = 0u; ls[192] = 0u;  // total = 0
+    }
+    s.total = f4{0, 0, 0, 0};
+    s.j = 0;
+    s.fresh = true;
+    s.seg = 0;
+    s.meta = 0;
+    if (a.pixel_cache != 0u) with_memo(a, ls, [&](auto pc) { pc[12 * 64] = MEMO_RAY; });
+}
+
+// The start of a sample (path_begin's counterpart for a ray of the host's): the jitter's four draws, the ray, a new path
+template <bool SQ>
+DEV void ray_path_begin(PixelState& s, const float4* __restrict__ rays) {
+    s.rng = rng_jump<4>(s.rng);  // (wgsl:488-492: the two disks' angle and radius draws, never read)
+    uint32_t seed;
+    (void)path_ray_of<SQ>(rays, s.x, s.ro, s.rd, seed);
+    s.T = f4{1, 1, 1, 1};
+    s.light = f4{0, 0, 0, 0};
+    s.seg = 0;
+    s.fresh = false;
+}
+
+template <bool LDS, bool TLAS, bool SIMPLE>
+__global__ void __launch_bounds__(BLOCK_THREADS) rt_radiance_kernel(const RenderArgs a, const float4* __restrict__ rays, uint32_t n,
+                                                                    float4* __restrict__ out, uint32_t* __restrict__ next_ray) {
+    constexpr bool TOTAL_LDS = total_in_lds(LDS);
+    uint32_t* ls = block_prologue<LDS>(a);
+    uint32_t* stack = stack_of<TOTAL_LDS>(ls);
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool cache_on = a.pixel_cache != 0u;  // wave-uniform
+    uint32_t pool_base = 0, pool_left = 0;      // wave-uniform: the rays the wave has claimed and not handed out
+    bool exhausted = false, active = false;
+    PixelState s;
+    ray_begin<TOTAL_LDS>(a, s, ls, 0u, 0u);
+    s.T = f4{1, 1, 1, 1};
+    s.light = f4{0, 0, 0, 0};
+    s.ro = f3{0, 0, 0};
+    s.rd = f3{0, 0, 1};
+    uint32_t n_segments = 0, more_reused = 0;  // (path_end's counters: nobody reads them here)
+    int node_tests = 0, tri_tests = 0;
+    for (;;) {
+        const unsigned long long idle = __ballot(!active);
+        if (idle != 0ull && !exhausted) {
+            if (pool_left == 0u) {
+                uint32_t t = 0;
+                if (lane == 0u) t = atomicAdd(next_ray, 64u);  // (n <= 2^31 - 1 and every wave stops at its first claim beyond n: no wrap)
+                t = __builtin_amdgcn_readfirstlane(t);
+                if (t >= n) {
+                    exhausted = true;
+                } else {
+                    pool_base = t;
+                    pool_left = n - t < 64u ? n - t : 64u;
+                }
+            }
+            if (pool_left != 0u) {
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (!active && rank < pool_left) {
+                    const uint32_t i = pool_base + rank;
+                    f3 ro, rd;
+                    uint32_t seed;
+                    if (path_ray_of<!LDS>(rays, i, ro, rd, seed)) {
+                        ray_begin<TOTAL_LDS>(a, s, ls, i, seed);
+                        active = true;
+                    } else {
+                        out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    }
+                }
+                const uint32_t n_idle = (uint32_t)__popcll(idle);
+                const uint32_t took = n_idle < pool_left ? n_idle : pool_left;
+                pool_base += took;
+                pool_left -= took;
+            }
+        }
+        if (__ballot(active) == 0ull) {
+            if (exhausted) break;
+            continue;
+        }
+        if (active) {
+            bool done = false;
+            if (s.fresh) {
+                // The sample's first segment from the memo, then on to its next one in this same iteration (path_step's
+                // pre-step): the lanes that are past their ray's first sample join this iteration's traversal.
+                uint32_t st = 0u;
+                if (cache_on) with_memo(a, ls, [&](auto pc) { st = pc[12 * 64]; });
+                const bool memo = (st & MEMO_HIT_VALID) != 0u;
+#if RT_ROULETTE_SKIP
+                if (memo && a.roulette_skip != 0u && roulette_skip<LDS, TOTAL_LDS, SIMPLE>(a, s, ls, st, n_segments, more_reused)) done = true;
+#endif
+                if (!done) {
+                    ray_path_begin<!LDS>(s, rays);
+                    if (memo) {
+                        Hit mh;
+                        mh.hit = false;
+                        mh.suspended = false;
+                        memo_hit_load<false, false>(a, s, ls, mh);
+                        done = path_end<LDS, TOTAL_LDS, SIMPLE, true>(a, s, ls, STEP_REUSE, mh, n_segments, &more_reused);
+                    }
+                }
+            }
+            if (!done && !s.fresh) {
+                Isect I;
+                const Hit hit = intersect_scene<LDS, false, TLAS, false, SIMPLE>(a, s.ro, s.rd, stack, node_tests, tri_tests, I);
+                memo_hit_store<false, false, false>(a, s, ls, hit);  // (the first segment of the ray's first sample)
+                done = path_end<LDS, TOTAL_LDS, SIMPLE, true>(a, s, ls, STEP_TRAVERSE, hit, n_segments, &more_reused);
+            }
+            if (done) {  // wgsl:498, as pixel_finish
+                f4 total = s.total;
+                if constexpr (TOTAL_LDS)
+                    total = f4{__uint_as_float(ls[0]), __uint_as_float(ls[64]), __uint_as_float(ls[128]), __uint_as_float(ls[192])};
+                const float r = a.spp_reciprocal, spp = (float)a.params.rays_per_pixel;
+                out[s.x] = r != 0.0f ? make_float4(total.x * r, total.y * r, total.z * r, total.w * r)
+                                     : make_float4(total.x / spp, total.y / spp, total.z / spp, total.w / spp);
+                active = false;
+            }
+        }
+    }
+}
+
+// The persistent grid: what the kernel keeps resident on compute_units CUs, at most one wave per 64 rays.  next_ray: a
+// zeroed counter of the launch's own.
+hipError_t launch_radiance(const RenderArgs& a, const void* rays, uint32_t n, void* out, uint32_t* next_ray, uint32_t compute_units,
+                           hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t lds = render_lds_bytes(a);
+    const uint32_t need = (n + BLOCK_THREADS - 1) / BLOCK_THREADS;
+    with_instantiation(a, a.many_mesh == 0u && a.simple != 0u, [&](auto lds_tag, auto tlas_tag, auto simple_tag) {
+        auto kernel = rt_radiance_kernel<decltype(lds_tag)::value, decltype(tlas_tag)::value, decltype(simple_tag)::value>;
+        allow_lds(kernel, lds);  // (before the occupancy is asked for)
+        int per_cu = 0;
+        uint32_t blocks = compute_units * BLOCKS_PER_CU;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK_THREADS, lds) == hipSuccess && per_cu > 0)
+            blocks = (uint32_t)per_cu * compute_units;
+        if (need < blocks) blocks = need;
+        launch_k(kernel, blocks, lds, stream, a, static_cast<const float4*>(rays), n, static_cast<float4*>(out), next_ray);
     });
     return hipGetLastError();
 }

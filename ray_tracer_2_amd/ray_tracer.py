@@ -263,7 +263,7 @@ class RayTracer:
                 out = np.empty(lay[9], np.uint8)
         return out, np.array(lay, np.uint32), np.array(facts, np.uint32)
 
-    # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick) and frame-wide first hits (rt_render_gbuffer) ----
+    # ---- ray queries (rt_intersect_rays, rt_occluded_rays, rt_pick), frame-wide first hits (rt_render_gbuffer), radiance (rt_radiance_rays) ----
     def trace_rays(self, origins, dirs, tmax=None):
         """Closest hit of rays (origins[i], dirs[i]) on the uploaded scene, as a render's walk computes it; a hit at
         t >= tmax[i] is reported as a miss (tmax None: unbounded).  numpy inputs: a synchronous call that returns a
@@ -348,6 +348,64 @@ class RayTracer:
         ext.wait_stream(cur)
         self._check(self._L.rt_render_gbuffer(self._h, C.byref(params), C.byref(g), 0))
         cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launch: _device_query)
+        return out
+
+    def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):
+        """Radiance along rays of the caller's (rt_radiance_rays): for ray i `frag`'s sample loop with the ray held fixed --
+        state = seeds[i]; per sample four draws (the camera jitter's) and total += trace(ray); total / samples -- as an
+        (n, 4) float32 array.  With origin = cam_to_world[3], dirs = the `dir` plane of render_gbuffer and
+        seeds = pixel_seeds(width, height, frames) that is the frame render writes for frames <= 0 under a jitter-free
+        camera, bit for bit.  numpy inputs (origins, dirs: (n, 3) floats; seeds: (n,) uint32): a synchronous call that
+        returns numpy.  Tensors on this handle's device (origins, dirs: (n, 3) float32; seeds: (n,) int32 holding the
+        u32 bits, or uint32): an asynchronous call ordered after the current torch stream's work, returns a tensor.
+        Invalid rays (non-finite components, a direction that cannot be normalised) get zeros."""
+        bounces, samples = int(bounces), int(samples)
+        if bounces < 0:
+            raise ValueError("bounces must be >= 0")
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        params = A.make_params(0, 0, bounces, samples, skybox=1 if skybox else 0)
+        if any(hasattr(v, "data_ptr") for v in (origins, dirs, seeds)):
+            import torch
+            if not all(isinstance(v, torch.Tensor) for v in (origins, dirs, seeds)):
+                raise ValueError("mix of device tensors and host arrays")
+            for v in (origins, dirs, seeds):
+                if v.device.type != "cuda" or v.device.index != self.device:
+                    raise ValueError(f"ray tensors must be on cuda:{self.device}, not {v.device}")
+            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
+                raise ValueError("origins and dirs must be float32 tensors")
+            if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise ValueError(f"seeds must be an int32 (the u32 bits) or uint32 tensor, not {seeds.dtype}")
+            if origins.dim() != 2 or origins.shape[1] != 3 or tuple(dirs.shape) != tuple(origins.shape):
+                raise ValueError("origins and dirs must both have shape (n, 3)")
+            n = origins.shape[0]
+            if tuple(seeds.shape) != (n,):
+                raise ValueError("seeds must have shape (n,)")
+            bits = seeds.view(torch.int32).reshape(n, 1).view(torch.float32)
+            pad = torch.zeros((n, 1), dtype=torch.float32, device=origins.device)   # (_p0 = 0)
+            rays = torch.cat([origins, bits, dirs, pad], dim=1).contiguous()
+            out = torch.empty((n, 4), dtype=torch.float32, device=origins.device)
+            self._device_query(lambda h, r, m, o, f: self._L.rt_radiance_rays(h, C.byref(params), r, m, o, f), rays, out, 0)
+            return out
+        o, d, sd = np.asarray(origins), np.asarray(dirs), np.asarray(seeds)
+        for name, v in (("origins", o), ("dirs", d)):
+            if v.dtype.kind != "f":
+                raise ValueError(f"{name} must be a floating-point array, not {v.dtype}")
+        if sd.dtype != np.uint32:
+            raise ValueError(f"seeds must be a uint32 array, not {sd.dtype}")
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("origins and dirs must both have shape (n, 3)")
+        n = o.shape[0]
+        if sd.shape != (n,):
+            raise ValueError("seeds must have shape (n,)")
+        rays = np.zeros(n, A.PATH_RAY_DTYPE)
+        rays["origin"] = o
+        rays["dir"] = d
+        rays["seed"] = sd
+        out = np.zeros((n, 4), np.float32)
+        if n:
+            self._check(self._L.rt_radiance_rays(self._h, C.byref(params), rays.ctypes.data, n, out.ctypes.data,
+                                                 A.RADIANCE_HOST_MEMORY))
         return out
 
     @staticmethod
@@ -444,6 +502,14 @@ class RayTracer:
 
     def strip_texels(self, width, height, rank, world):
         return int(self._L.rt_strip_texels(width, height, rank, world))
+
+
+def pixel_seeds(width, height, frames):
+    """The RNG seeds of a width x height frame's pixels (wgsl:475: y * width + x + |frames| * 719393 in u32 arithmetic),
+    row-major, as a (width * height,) uint32 array: RayTracer.radiance's `seeds` for the rays of that frame."""
+    width, height, frames = int(width), int(height), int(frames)
+    i = np.arange(width * height, dtype=np.uint64)
+    return ((i + np.uint64(abs(frames)) * np.uint64(719393)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
 
 def normalize3_f32(v):

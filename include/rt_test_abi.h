@@ -48,6 +48,39 @@ int rt_test_device_sample_texture(rt_handle* h, const rt_texture_desc* tex, cons
 int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint8_t* active, uint64_t n, int flags,
                       uint32_t* out);
 
+/* Test-only: the kernels' shading step (path_end: sky, glass, diffuse / specular mix, emission, texture, russian roulette,
+ * end-of-sample bookkeeping; which = RT_TEST_SHADE_PATH_END) or the pre-step's roulette skip (roulette_skip; which =
+ * RT_TEST_SHADE_ROULETTE_SKIP) for n host-given lane states on the uploaded scene's materials and textures, one lane per
+ * case, with the prologue of the render kernels and the instantiation a render would take -- unless `flags` force the
+ * general (RT_TEST_SHADE_GENERAL) or the SIMPLE one (RT_TEST_SHADE_SIMPLE: refused on a many-mesh scene or one with
+ * spheres, glass or textures).  RT_TEST_SHADE_NO_FAST_MISS takes path_end's FAST_MISS = false instantiation (the counter
+ * builds') instead of the product's; RT_TEST_SHADE_TOTAL_REGS the one that keeps the pixel sum in registers instead of
+ * the lane's LDS state.  The arguments are a render's (a copy of the handle's) with pixel_cache = 0 and fast_miss = 0 and
+ * the call's number_of_bounces, rays_per_pixel and skybox.  A case whose `active` byte is 0 (active may be NULL: all
+ * cases) stays out of the call and its record stays zero.  Floats may be anything, non-finite values included.
+ * RT_ERR_INVALID_ARGUMENT, before anything reaches the device: an object index outside the scene, a mode other than
+ * RT_TEST_SHADE_STEP_END / _STEP_TRAVERSE, an unknown `which` or flag, both GENERAL and SIMPLE, n > RT_TEST_SHADE_MAX_CASES.
+ * Case, RT_TEST_SHADE_WORDS u32 words (floats as bits): rd xyz, T xyzw, light xyzw, total xyzw, RNG state, seg, j, mode,
+ * hit, dst, point xyz, normal xyz, u, v, backface, object (mesh index, or number of meshes + sphere index: word 11 of the
+ * intersect record), meta (PixelState::meta: the pixel's ray count in bits 0-15).  The roulette skip reads object, RNG
+ * state, j, total and meta only (its memo word is the object's material | hit).
+ * Record, RT_TEST_SHADE_WORDS words: ro xyz (zero going in), rd xyz, T xyzw, light xyzw, total xyzw (from the LDS where it
+ * lives there), RNG state, seg, j, fresh, the return value, the n_segments increment, meta, the instantiation that ran (1
+ * many-mesh, 2 SIMPLE, 32 FAST_MISS = false, 64 scene in LDS, 128 pixel sum in LDS), the more_reused increment (the roulette
+ * skip's dead count), zeros. */
+#define RT_TEST_SHADE_WORDS 32
+#define RT_TEST_SHADE_MAX_CASES (1ull << 20)
+#define RT_TEST_SHADE_PATH_END 0
+#define RT_TEST_SHADE_ROULETTE_SKIP 1
+#define RT_TEST_SHADE_STEP_END 0
+#define RT_TEST_SHADE_STEP_TRAVERSE 3
+#define RT_TEST_SHADE_GENERAL 1
+#define RT_TEST_SHADE_NO_FAST_MISS 2
+#define RT_TEST_SHADE_SIMPLE 4
+#define RT_TEST_SHADE_TOTAL_REGS 8
+int rt_test_shade(rt_handle* h, int which, const uint32_t* cases, const uint8_t* active, uint64_t n, int number_of_bounces,
+                  int rays_per_pixel, int skybox, int flags, uint32_t* out);
+
 /* Test-only: the uploaded scene's blob as the kernels read it (out may be NULL; else bytes >= its size, which
  * layout_out[9] gives), its SceneLayout (csrc/rt_scene_format.h, 12 words) and its device address.  Waits for the launches
  * enqueued on the handle's streams. */

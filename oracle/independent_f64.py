@@ -44,18 +44,6 @@ class Rng:
     def rand(self, mask=None):
         return self.next(mask).astype(np.float64) / 4294967295.0   # :165 (2^32 - 1, exactly, in double)
 
-    def normal(self, mask=None):   # :181-185
-        theta = 2.0 * PI * self.rand(mask)
-        with np.errstate(divide="ignore"):
-            rho = np.sqrt(-2.0 * np.log(self.rand(mask)))
-        return rho * np.cos(theta)
-
-    def unit_sphere(self, mask=None):   # :168-174
-        x = self.normal(mask)
-        y = self.normal(mask)
-        z = self.normal(mask)
-        return normalize(np.stack([x, y, z], -1))
-
     def in_unit_disk(self, mask=None):   # :202-206
         angle = self.rand(mask) * 2.0 * PI
         r = np.sqrt(self.rand(mask))
@@ -446,14 +434,6 @@ def ambiguity(scene, ro, rd):
     return out
 
 
-def refract(I, N, eta):   # WGSL builtin
-    d = dot(N, I)
-    k = 1.0 - eta * eta * (1.0 - d * d)
-    with np.errstate(invalid="ignore"):
-        r = eta[:, None] * I - (eta * d + np.sqrt(np.maximum(k, 0.0)))[:, None] * N
-    return np.where((k < 0.0)[:, None], 0.0, r)
-
-
 def primary_rays(scene, W, H, rng=None):
     """frag :473-495 for every pixel (x fastest); with rng: the four jitter draws per sample."""
     y, x = np.mgrid[0:H, 0:W]
@@ -470,6 +450,233 @@ def primary_rays(scene, W, H, rng=None):
         kx, ky = rng.in_unit_disk()                                          # :492
         focus = focus + right * (kx * scene.diverge / W)[:, None] + up * (ky * scene.diverge / W)[:, None]
     return origin, normalize(focus - origin)                                 # :494
+
+
+# ---- one segment behind the intersection: trace :405-468 for given hits ------------------------------------------------------
+F32_MAX = float(np.finfo(np.float32).max)
+PIN_TOL = 1e-5       # the comparison tolerance the ill-conditioning bounds are measured against (tests/test_f64_pin.py)
+
+
+def r32(x):
+    """x with binary32's RANGE: what overflows there is infinite here too (a double holds 2^129 and 1 / 1e-40; the shader's
+    numbers do not, and inf * 0 or inf - inf further on are NaN for it).  The precision stays the double's."""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.abs(x) > F32_MAX, np.copysign(np.inf, x), x)
+
+
+def _len(v):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.sqrt(r32(dot(v, v)))
+
+
+def _unit(v, err_v, ops):
+    """normalize(v) and a bound of binary32's error of it, as a fraction of the unit length: v itself is off by err_v (absolute,
+    propagated from its operands) plus `ops` roundings of at most 2^-24 |v|_max each on the way to it, and dividing by the
+    length |v| turns an absolute error e into e / |v| -- (err_v + ops * 2^-24 * |v|_max) / |v| + 3 * 2^-24 for the dot, the
+    square root and the scaling.  A short sum of long operands (|v| << |v|_max is impossible, but |v| << its operands is
+    what mix() of two opposite directions gives: the caller passes the operands' size in err_v) is what this catches."""
+    ln = _len(v)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        u = v / ln[..., None]
+        err = (err_v + ops * U32 * np.abs(v).max(-1)) / ln + 3.0 * U32
+    return u, np.where(np.isfinite(err), err, 0.0)   # (a zero or non-finite v: NaN on both sides, nothing to bound)
+
+
+def wsign(x):
+    """WGSL sign() with the one choice it leaves open made as both comparisons failing make it: sign(NaN) = 0."""
+    with np.errstate(invalid="ignore"):
+        return np.where(x > 0.0, 1.0, np.where(x < 0.0, -1.0, 0.0))
+
+
+def _sphere(rng, mask):
+    """rand_unit_sphere :168-174 (three rand_normal_dist :181-185, then normalize) for the states under `mask`, and E_s: the
+    bound of binary32's error of the result per unit length (scatter's docstring).  Per component x = rho cos(theta): theta
+    carries 6e-7 (10u) and cos_ 2u, so rho 12u; rho = sqrt(-2 log r) carries delta(rho^2) = 2 delta(r) / r = 2u, that is
+    2u / (2 rho) -- and never more than sqrt(2u), reached at rho = 0 (r rounds to 1.0 in binary32 and not here)."""
+    comps, errs = [], []
+    for _ in range(3):
+        theta = 2.0 * PI * rng.rand(mask)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rho = np.sqrt(-2.0 * np.log(rng.rand(mask)))
+            comps.append(rho * np.cos(theta))
+            errs.append(12.0 * U32 * rho + np.minimum(U32 / rho, np.sqrt(2.0 * U32)))
+    xyz = np.stack(comps, -1)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ln = np.sqrt(dot(xyz, xyz))
+        e = np.sqrt(sum(x * x for x in errs)) / ln + 3.0 * U32
+        unit = xyz / ln[:, None]
+    return unit, np.where(np.isfinite(e), e, 0.0)
+
+
+def scatter(scene, cases, skybox=1):
+    """trace :405-468 for given hits: the sky on a miss (:406-411), glass (:414-436), everything else (:437-460) and the russian
+    roulette with its rescale (:462-466), on arrays of n cases.  cases: dict of rd (n, 3), T (n, 4), light (n, 4), rng (n u32
+    states), hit (n bool), dst (n), point (n, 3), normal (n, 3), uv (n, 2), backface (n bool), which (n material indices: mesh
+    materials first, then the spheres'), and optionally ro (n, 3; default zero).  Returns dict of ro, rd, T, light, rng (the
+    states afterwards), goes_on (n bool: hit and survived the roulette) and ambiguous (n bool).
+
+    ambiguous: binary32 may legitimately decide or land elsewhere.  Every decision has a margin |quantity - threshold| and a
+    tolerance, a first-order bound of binary32's error of the quantity with u = 2^-24; a case is ambiguous when a margin is
+    below its tolerance:
+      specular >= r, r >= p   r = f32(bits) * 2^-32 there against bits / (2^32 - 1) here: u r + 2^-32 apart, doubled; p is a
+                              product of two or three binary32 factors (absorption: an exp_ as well, a texture: the bilinear
+                              filter's 12 operations): 16 u |p|
+      reflectance > r         cos_theta is a 3-term dot of unit vectors (3u), (1 - cos)^5 carries 5 x 4u (1 - cos)^4 <= 20u and
+                              the pow_ polynomial a few u more; r0 a reciprocal, a quotient and a square (8u max(1, r0)); the sum
+                              and the product 3u: under 40u max(1, reflectance), 64u used
+      ior * sin > 1           1 - cos^2 is good to 8u (absolute), so sin = sqrt(.) to 4u / sin, and to sqrt(8u) where sin^2 < 8u;
+                              the product adds 4u |ior sin|
+      k < 0                   k = 1 - eta^2 (1 - d^2): d is a 3-term dot of unit vectors (3u absolute), so d^2 carries 6u |d| and
+                              1 - d^2 another u; eta^2 2u of itself (eta may be a rounded reciprocal) and the product u: eta^2
+                              (6 |d| + 2 + 3 (1 - d^2)) u, and the last difference u |k|
+      the hemisphere flip     sign(dot(n, s)) of the unit-sphere sample s: its angle theta = 2 pi r is off by up to 3 roundings of
+                              2 pi 2^-25 (r, the product, the constant) = 6e-7 and cos_ by 2u, so a component of the unnormalised
+                              (x, y, z) by rho (10u + 2u) and, through log near r = 1, u / rho (_sphere): E_s per unit length;
+                              tolerance 2 E_s |n|
+      the origin offset       sign(dot(n, rd')) of the new direction: 4u |n| + 2 |n| (rd's bound below)
+    and when an OUTPUT is ill-conditioned: a normalised vector whose bound from _unit (operation count x 2^-24 / length, plus
+    what its operands carry) exceeds the comparison tolerance PIN_TOL, or a light sum that cancels: light + emitted * T with
+    the product rounded twice and the sum once is off by u (2 |product| + |sum|), more than PIN_TOL max(|sum|, 1e-3)."""
+    n = cases["rd"].shape[0]
+    f = lambda k: np.array(cases[k], np.float64)  # noqa: E731
+    rd, T, light = f("rd"), f("T"), f("light")
+    ro = f("ro") if "ro" in cases else np.zeros((n, 3))
+    hit = np.asarray(cases["hit"], bool)
+    rng = Rng(np.asarray(cases["rng"]))
+    amb = np.zeros(n, bool)
+    goes_on = np.zeros(n, bool)
+    miss = ~hit
+    if skybox and miss.any():                               # :406-411
+        env = environment_light(rd[miss])
+        new_light = r32(light[miss] + r32(T[miss] * env))
+        # the sun is pow(m, 500) of a 3-term dot m (3u, and the pow_ polynomial's own few u on a logarithm that is multiplied
+        # by 500): good to 500 x 4u of itself -- 1e-4 where the ray looks into it; the rest of the sky to 16u
+        with np.errstate(invalid="ignore", over="ignore"):
+            sun = np.power(np.maximum(0.0, dot(rd[miss], np.array([0.1, 1.0, 0.1]))), 500.0) * 0.1
+            e = np.abs(T[miss]) * (2000.0 * U32 * sun + 16.0 * U32 * np.abs(env).max(-1))[:, None] + U32 * np.abs(new_light)
+            amb[miss] |= (np.isfinite(e) & (e > PIN_TOL * np.maximum(np.abs(new_light), 1e-3))).any(-1)
+        light[miss] = new_light
+    if not hit.any():
+        return dict(ro=ro, rd=rd, T=T, light=light, rng=rng.s.astype(np.uint32), goes_on=goes_on, ambiguous=amb)
+    wm = np.asarray(cases["which"], np.int64)
+    nrm, dsth, bf, uvm, point = f("normal"), f("dst"), np.asarray(cases["backface"], bool), f("uv"), f("point")
+    ro = np.where(hit[:, None], point, ro)                  # :413
+    nlen = np.sqrt(dot(nrm, nrm))
+    glass = hit & (scene.mat_flag[wm] == 1)
+    err_rd = np.zeros(n)
+    p_tol = np.zeros(n)
+    tex_err = np.zeros(n)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
+        # ---- glass :414-436 ----
+        g = np.nonzero(glass)[0]
+        if g.size:
+            mi = wm[g]
+            e = r32(r32(-dsth[g][:, None] * scene.mat_absorption[mi][:, :3]) * scene.mat_absorption_strength[mi][:, None])
+            Tg_in = np.concatenate([r32(T[g][:, :3] * np.exp(e)), np.ones((g.size, 1))], -1)
+            T[g] = np.where(bf[g][:, None], Tg_in, T[g])                                # :415-418
+            p_tol[g] = np.where(bf[g], 16.0, 2.0)
+            ior = np.where(bf[g], scene.mat_ior[mi], r32(1.0 / scene.mat_ior[mi]))      # :420
+            d_in, ng = rd[g], nrm[g]
+            refl = d_in - 2.0 * dot(ng, d_in)[:, None] * ng                             # :422
+            dd = dot(ng, d_in)                                                          # refract :423 (WGSL builtin)
+            eta2 = r32(ior * ior)
+            k = 1.0 - r32(eta2 * (1.0 - dd * dd))
+            refr = r32(ior[:, None] * d_in) - r32(r32(ior * dd) + np.sqrt(np.maximum(k, 0.0)))[:, None] * ng
+            refr = np.where((k < 0.0)[:, None], 0.0, refr)
+            tol_k = U32 * (np.abs(eta2) * (6.0 * np.abs(dd) + 2.0 + 3.0 * np.abs(1.0 - dd * dd)) + np.abs(k))
+            tol_k = np.where(np.isfinite(tol_k), tol_k, 0.0)
+            amb[g] |= np.isfinite(k) & (np.abs(k) < tol_k)
+            err_refr = np.where(np.isfinite(k) & (k > 0.0), tol_k / (2.0 * np.sqrt(np.maximum(k, tol_k))), 0.0) + 8.0 * U32 * (1.0 + np.abs(ior))
+            err_refr = np.where(np.isfinite(err_refr), err_refr, 0.0)
+            cos_t = np.minimum(dot(-d_in, ng), 1.0)
+            s2 = 1.0 - cos_t * cos_t
+            sin_t = np.sqrt(s2)
+            cannot = r32(ior * sin_t) > 1.0
+            sin_safe = np.sqrt(np.maximum(s2, 0.0))
+            tol_sin = 4.0 * U32 / np.maximum(sin_safe, np.sqrt(8.0 * U32))
+            q = r32(ior * sin_safe)
+            amb[g] |= np.isfinite(q) & (np.abs(q - 1.0) < np.abs(ior) * tol_sin + 4.0 * U32 * np.abs(q))
+            r0 = r32(r32((1.0 - ior) / (1.0 + ior)) ** 2)
+            schlick = r0 + r32((1.0 - r0) * np.power(1.0 - cos_t, 5.0))                  # :208-212
+            draw = np.zeros(n, bool)
+            draw[g[~cannot]] = True                                                     # `||` short-circuits: no draw when cannot_refract (:428)
+            rr = rng.rand(draw)[g]
+            follow = cannot | (schlick > rr)
+            amb[g] |= ~cannot & np.isfinite(schlick) & (np.abs(schlick - rr) < 64.0 * U32 * np.maximum(1.0, np.abs(schlick)))
+            gm = np.zeros(n, bool)
+            gm[g] = True
+            sph, e_s = _sphere(rng, gm)                                                 # :430 (rand_direction :187-193)
+            sph, e_s = sph[g], e_s[g]
+            diffuse, e_d = _unit(ng + sph, e_s, 1.0)
+            spec, smooth = scene.mat_specular[mi], scene.mat_smoothness[mi]
+            e_in = np.abs(1.0 - spec) * e_d + np.abs(spec) * 8.0 * U32 * (1.0 + nlen[g] ** 2) + 3.0 * U32 * (np.abs(1.0 - spec) + np.abs(spec))
+            refl, e_refl = _unit(mix(diffuse, refl, spec[:, None]), np.where(np.isfinite(e_in), e_in, 0.0), 0.0)       # :432
+            e_in = np.abs(1.0 - smooth) * e_d + np.abs(smooth) * err_refr + 3.0 * U32 * (np.abs(1.0 - smooth) + np.abs(smooth))
+            refr, e_refr = _unit(mix(-diffuse, refr, smooth[:, None]), np.where(np.isfinite(e_in), e_in, 0.0), 0.0)    # :433
+            nd = np.where(follow[:, None], refl, refr)
+            err_rd[g] = np.where(follow, e_refl, e_refr)
+            rd[g] = nd
+            sg = dot(ng, nd)
+            amb[g] |= np.isfinite(sg) & (np.abs(sg) < nlen[g] * (4.0 * U32 + 2.0 * err_rd[g]))
+            ro[g] = point[g] + 1e-4 * ng * wsign(sg)[:, None]                         # :436
+        # ---- everything else :437-460 ----
+        o = np.nonzero(hit & ~glass)[0]
+        if o.size:
+            om = np.zeros(n, bool)
+            om[o] = True
+            mi = wm[o]
+            r1 = rng.rand(om)[o]
+            spc = scene.mat_specular[mi]
+            is_spec = spc >= r1                                                          # :438
+            amb[o] |= np.isfinite(spc) & (np.abs(spc - r1) < 2.0 * (U32 * np.maximum(r1, np.abs(spc)) + 2.0 ** -32))
+            sph, e_s = _sphere(rng, om)                                                 # :448 (rand_hemisphere :176-179)
+            sph, e_s = sph[o], e_s[o]
+            no = nrm[o]
+            sd = dot(no, sph)
+            amb[o] |= np.isfinite(sd) & (np.abs(sd) < 2.0 * e_s * nlen[o])
+            diffuse = sph * wsign(sd)[:, None]
+            specular_dir = rd[o] - 2.0 * dot(no, rd[o])[:, None] * no                    # reflect :449
+            emitted = r32(scene.mat_emission_color[mi] * scene.mat_emission_strength[mi][:, None])
+            add = r32(emitted * T[o])
+            new_light = r32(light[o] + add)                                              # :452
+            amb[o] |= (U32 * (2.0 * np.abs(add) + np.abs(new_light)) > PIN_TOL * np.maximum(np.abs(new_light), 1e-3)).any(-1)
+            light[o] = new_light
+            t = scene.mat_smoothness[mi] * is_spec
+            e_in = np.abs(1.0 - t) * e_s + np.abs(t) * 8.0 * U32 * (1.0 + nlen[o] ** 2) + 3.0 * U32 * (np.abs(1.0 - t) + np.abs(t))
+            rd[o], err_rd[o] = _unit(mix(diffuse, specular_dir, t[:, None]), np.where(np.isfinite(e_in), e_in, 0.0), 0.0)   # :451
+            col = scene.mat_color[mi].copy()
+            tex = (scene.mat_flag[mi] == 2) & (scene.mat_diffuse_index[mi] != -1)          # :454
+            p_tol[o] = np.where(tex & ~is_spec, 16.0, 2.0)
+            for ti in np.unique(scene.mat_diffuse_index[mi][tex]):
+                sel = tex & (scene.mat_diffuse_index[mi] == ti)
+                if 0 <= int(ti) < len(scene.textures):
+                    tex_ = scene.textures[int(ti)]
+                    uu, vv = uvm[o][sel, 0], uvm[o][sel, 1]
+                    col[sel] = sample_texture(tex_, uu, vv)                                                    # :455
+                    # the sample position u * width - 0.5 is rounded twice (2u of itself, du in u) and the filter's weights
+                    # move with it: the colour by what the (piecewise linear) filter gives du and dv away, on either side,
+                    # plus the filter's 12 operations on the colour itself
+                    du = 2.0 * U32 * (np.abs(uu) + 1.0 / tex_.shape[1])
+                    dv = 2.0 * U32 * (np.abs(vv) + 1.0 / tex_.shape[0])
+                    moved = [np.abs(sample_texture(tex_, uu + a * du, vv + b * dv) - col[sel]) for a, b in ((1, 0), (-1, 0), (0, 1), (0, -1))]
+                    e_c = np.maximum(moved[0], moved[1]) + np.maximum(moved[2], moved[3]) + 12.0 * U32 * np.abs(col[sel])
+                    e_c = np.where((np.abs(uu * tex_.shape[1]) + np.abs(vv * tex_.shape[0]) < 2.0 ** 22)[:, None], e_c, 1.0)   # (no fraction left)
+                    e_t = np.where(np.isfinite(e_c), e_c, 0.0) * np.abs(T[o][sel]) * ~is_spec[sel][:, None]
+                    tex_err[o[sel]] = e_t[:, :3].max(-1)
+                    amb[o[sel]] |= (e_t > PIN_TOL * np.maximum(np.abs(T[o][sel] * col[sel]), 1e-3)).any(-1)
+                else:
+                    col[sel] = 0.0   # (the reference binds 1 x 1 zero textures to the unused slots)
+            T[o] = r32(T[o] * np.where(is_spec[:, None], scene.mat_specular_color[mi], col))                   # :459
+        amb |= hit & (err_rd > PIN_TOL)
+        h = np.nonzero(hit)[0]
+        p = np.fmax.reduce(T[h, :3], -1)                    # :462 (max() of WGSL returns the other operand for a NaN)
+        r2 = rng.rand(hit)[h]
+        die = r2 >= p                                       # :463
+        amb[h] |= np.isfinite(p) & (np.abs(r2 - p) < 2.0 * (U32 * r2 + 2.0 ** -32) + p_tol[h] * U32 * np.abs(p) + tex_err[h])
+        live = h[~die]
+        goes_on[live] = True
+        T[live] = r32(T[live] * r32(1.0 / p[~die])[:, None])   # :466
+    return dict(ro=ro, rd=rd, T=T, light=light, rng=rng.s.astype(np.uint32), goes_on=goes_on, ambiguous=amb)
 
 
 def render_frame(scene, W, H, bounces, spp, frames, skybox=1):
@@ -490,74 +697,11 @@ def render_frame(scene, W, H, bounces, spp, frames, skybox=1):
                 break
             idx = np.nonzero(alive)[0]
             hit, dst, point, normal, uvh, which, backface = closest_hit(scene, ro[idx], rd[idx])
-            miss = idx[~hit]
-            if skybox and miss.size:                        # :406-411
-                light[miss] += T[miss] * environment_light(rd[miss])
-            alive[miss] = False
-            h = idx[hit]
-            if h.size == 0:
-                break
-            wm, nrm, dsth, bf, uvm = which[hit], normal[hit], dst[hit], backface[hit], uvh[hit]
-            ro[h] = point[hit]                              # :413
-            glass = scene.mat_flag[wm] == 1
-            # ---- glass :414-436 ----
-            g = np.nonzero(glass)[0]
-            if g.size:
-                hg = h[g]
-                gm = np.zeros(n, bool)
-                gm[hg] = True
-                mi = wm[g]
-                Tg = T[hg].copy()
-                absorb = np.exp(-dsth[g][:, None] * scene.mat_absorption[mi][:, :3] * scene.mat_absorption_strength[mi][:, None])
-                Tg_in = np.concatenate([Tg[:, :3] * absorb, np.ones((g.size, 1))], -1)
-                Tg = np.where(bf[g][:, None], Tg_in, Tg)                                    # :415-418
-                ior = np.where(bf[g], scene.mat_ior[mi], 1.0 / scene.mat_ior[mi])           # :420
-                d_in, ng = rd[hg], nrm[g]
-                refl = d_in - 2.0 * dot(ng, d_in)[:, None] * ng                             # :422
-                refr = refract(d_in, ng, ior)                                               # :423
-                cos_t = np.minimum(dot(-d_in, ng), 1.0)
-                sin_t = np.sqrt(1.0 - cos_t * cos_t)
-                cannot = ior * sin_t > 1.0
-                r0 = ((1.0 - ior) / (1.0 + ior)) ** 2
-                schlick = r0 + (1.0 - r0) * np.power(1.0 - cos_t, 5.0)                       # :208-212
-                draw = np.zeros(n, bool)
-                draw[hg[~cannot]] = True                                                    # `||` short-circuits: no draw when cannot_refract (:428)
-                follow = cannot | (schlick > rng.rand(draw)[hg])
-                diffuse = normalize(ng + rng.unit_sphere(gm)[hg])                           # :430 (rand_direction :187-193)
-                refl = normalize(mix(diffuse, refl, scene.mat_specular[mi][:, None]))       # :432
-                refr = normalize(mix(-diffuse, refr, scene.mat_smoothness[mi][:, None]))    # :433
-                nd = np.where(follow[:, None], refl, refr)
-                rd[hg] = nd
-                ro[hg] = point[hit][g] + 1e-4 * ng * np.sign(dot(ng, nd))[:, None]          # :436
-                T[hg] = Tg
-            # ---- everything else :437-460 ----
-            o = np.nonzero(~glass)[0]
-            if o.size:
-                ho = h[o]
-                om = np.zeros(n, bool)
-                om[ho] = True
-                mi = wm[o]
-                is_spec = scene.mat_specular[mi] >= rng.rand(om)[ho]            # :438
-                sph = rng.unit_sphere(om)[ho]                                   # :448 (rand_hemisphere :176-179)
-                no = nrm[o]
-                diffuse = sph * np.sign(dot(no, sph))[:, None]
-                specular_dir = rd[ho] - 2.0 * dot(no, rd[ho])[:, None] * no     # reflect :449
-                light[ho] += scene.mat_emission_color[mi] * scene.mat_emission_strength[mi][:, None] * T[ho]   # :452
-                rd[ho] = normalize(mix(diffuse, specular_dir, (scene.mat_smoothness[mi] * is_spec)[:, None]))   # :451
-                col = scene.mat_color[mi].copy()
-                tex = (scene.mat_flag[mi] == 2) & (scene.mat_diffuse_index[mi] != -1)                         # :454
-                for ti in np.unique(scene.mat_diffuse_index[mi][tex]):
-                    sel = tex & (scene.mat_diffuse_index[mi] == ti)
-                    col[sel] = sample_texture(scene.textures[int(ti)], uvm[o][sel, 0], uvm[o][sel, 1])         # :455
-                T[ho] *= np.where(is_spec[:, None], scene.mat_specular_color[mi], col)                         # :459
-            hm = np.zeros(n, bool)
-            hm[h] = True
-            p = T[h, :3].max(-1)                            # :462
-            die = rng.rand(hm)[h] >= p                      # :463
-            alive[h[die]] = False
-            live = h[~die]
-            with np.errstate(divide="ignore", invalid="ignore"):
-                T[live] *= (1.0 / p[~die])[:, None]         # :466
+            s = scatter(scene, dict(ro=ro[idx], rd=rd[idx], T=T[idx], light=light[idx], rng=rng.s[idx], hit=hit, dst=dst, point=point,
+                                    normal=normal, uv=uvh, backface=backface, which=which), skybox)
+            ro[idx], rd[idx], T[idx], light[idx] = s["ro"], s["rd"], s["T"], s["light"]
+            rng.s[idx] = s["rng"].astype(np.uint64)
+            alive[idx] = s["goes_on"]
         total += light                                      # :496
     return (total / spp).reshape(H, W, 4)                   # :498
 

@@ -39,6 +39,7 @@ def load():
         L.oracle_rand.argtypes = [C.POINTER(C.c_uint32)]
         L.oracle_hardware_threads.restype = C.c_int
         L.oracle_intersect.restype = C.c_int
+        L.oracle_shade.restype = C.c_int
         _lib = L
     return _lib
 
@@ -110,6 +111,23 @@ def intersect(arrays, ro, rd):
                             C.c_void_p(arrays.meshes.ctypes.data), C.c_void_p(arrays.triangles.ctypes.data),
                             C.c_void_p(arrays.nodes.ctypes.data), C.c_void_p(ro.ctypes.data), C.c_void_p(rd.ctypes.data),
                             C.c_uint64(ro.shape[0]), C.c_void_p(out.ctypes.data))
+    assert rc == 0
+    return out
+
+
+def shade(arrays, cases, number_of_bounces, rays_per_pixel, skybox=1):
+    """One step of trace's loop behind the intersection (wgsl:405-468) with path_end's bookkeeping, per (n, 32) u32 case
+    record of the kernels' shading probe (include/rt_test_abi.h, rt_test_shade), on the materials and textures of `arrays`:
+    the (n, 32) u32 records of the probe, instantiation word 0."""
+    L = load()
+    cases = np.ascontiguousarray(cases, np.uint32)
+    assert cases.ndim == 2 and cases.shape[1] == 32
+    out = np.zeros_like(cases)
+    descs, nt = arrays.texture_descs()
+    rc = L.oracle_shade(C.byref(arrays.uniform), C.c_void_p(arrays.spheres.ctypes.data), C.c_void_p(arrays.meshes.ctypes.data),
+                        descs, C.c_uint32(nt), C.c_void_p(cases.ctypes.data), C.c_uint64(cases.shape[0]),
+                        C.c_int32(int(number_of_bounces)), C.c_int32(int(rays_per_pixel)), C.c_int32(int(skybox)),
+                        C.c_void_p(out.ctypes.data))
     assert rc == 0
     return out
 

@@ -402,6 +402,65 @@ static inline vec4 texture_sample_level(const Ctx& c, int index, vec2 uv) {
     return vec4{out[0], out[1], out[2], out[3]};
 }
 
+// One iteration of trace's loop behind the intersection (wgsl:405-468): the sky on a miss; on a hit the new origin, the glass
+// or the diffuse / specular scatter, emission, the texture lookup, and the russian roulette with its rescale.  Returns
+// whether the path goes on (false: it missed, or died at the roulette).  trace calls it per segment; oracle_shade calls it
+// for hits the caller supplies.
+static bool shade_segment(const Ctx& c, Ray& ray, const Hit& hit, vec4& incoming_light, uint32_t* seed) {
+    if (!hit.hit) {
+        if (c.params.skybox != 0) {
+            incoming_light = incoming_light + ray.transmittance * get_environment_light(ray);
+        }
+        return false;
+    }
+    ray.origin = hit.hit_point;
+    const rt_material& m = hit.material;
+    if (m.flag == RT_MATERIAL_GLASS) {
+        if (hit.backface) {
+            vec3 absorb{m.absorption[0], m.absorption[1], m.absorption[2]};
+            vec3 e = ((-hit.dst) * absorb) * m.absorption_strength;
+            vec3 t3{ray.transmittance.x, ray.transmittance.y, ray.transmittance.z};
+            vec3 x = t3 * vec3{rtm::exp_(e.x), rtm::exp_(e.y), rtm::exp_(e.z)};
+            ray.transmittance = vec4{x.x, x.y, x.z, 1.0f};
+        }
+        float ior = hit.backface ? m.ior : (1.0f / m.ior);
+        vec3 reflect_dir = reflect(ray.dir, hit.normal);
+        vec3 refract_dir = refract(ray.dir, hit.normal, ior);
+        float cos_theta = wmin(dot(-ray.dir, hit.normal), 1.0f);
+        float sin_theta = rtm::sqrt_(1.0f - cos_theta * cos_theta);
+        bool cannot_refract = ior * sin_theta > 1.0f;
+        bool follow_reflection = cannot_refract || reflectance(cos_theta, ior) > rand_(seed);
+        vec3 diffuse_dir = normalize(hit.normal + rand_direction(seed));
+        reflect_dir = normalize(mix(diffuse_dir, reflect_dir, m.specular));
+        refract_dir = normalize(mix(-diffuse_dir, refract_dir, m.smoothness));
+        ray.dir = follow_reflection ? reflect_dir : refract_dir;
+        ray.origin = hit.hit_point + (1e-4f * hit.normal) * wsign(dot(hit.normal, ray.dir));
+    } else {
+        bool is_specular_bounce = m.specular >= rand_(seed);
+        vec3 normal = hit.normal;  // wgsl:439-447: the normal-map branch is dead code
+        vec3 diffuse_dir = rand_hemisphere(normal, seed);
+        vec3 specular_dir = reflect(ray.dir, normal);
+        vec4 emitted_light = vec4{m.emission_color[0], m.emission_color[1], m.emission_color[2],
+                                  m.emission_color[3]} * m.emission_strength;
+        ray.dir = normalize(mix(diffuse_dir, specular_dir, m.smoothness * (is_specular_bounce ? 1.0f : 0.0f)));
+        incoming_light = incoming_light + emitted_light * ray.transmittance;
+        vec4 color;
+        if (m.flag == RT_MATERIAL_TEXTURE && m.diffuse_index != -1) {
+            color = texture_sample_level(c, m.diffuse_index, hit.uv);
+        } else {
+            color = vec4{m.color[0], m.color[1], m.color[2], m.color[3]};
+        }
+        vec4 spec{m.specular_color[0], m.specular_color[1], m.specular_color[2], m.specular_color[3]};
+        ray.transmittance = ray.transmittance * (is_specular_bounce ? spec : color);
+    }
+    float p = wmax(ray.transmittance.x, wmax(ray.transmittance.y, ray.transmittance.z));
+    bool die = rand_(seed) >= p;
+    if (die) return false;
+    ray.transmittance = ray.transmittance * (1.0f / p);
+    ray.inv_dir = 1.0f / ray.dir;
+    return true;
+}
+
 // wgsl:398-471
 static vec4 trace(const Ctx& c, const Ray& incident_ray, uint32_t* seed, uint64_t* segments,
                   int32_t stats_total[2], TranscriptBuf* tb) {
@@ -413,59 +472,10 @@ static vec4 trace(const Ctx& c, const Ray& incident_ray, uint32_t* seed, uint64_
     for (int32_t i = (int32_t)ray.bounces; i <= c.params.number_of_bounces; i += 1) {
         Hit hit = calculate_ray_collions(c, ray, _stats);
         *segments += 1;
-        if (!hit.hit) {
-            if (tb && tb->n < tb->cap) tb->rec[tb->n++] = Transcript{-1, -1, INF, *seed};
-            if (c.params.skybox != 0) {
-                incoming_light = incoming_light + ray.transmittance * get_environment_light(ray);
-            }
-            break;
-        }
-        ray.origin = hit.hit_point;
-        const rt_material& m = hit.material;
-        if (m.flag == RT_MATERIAL_GLASS) {
-            if (hit.backface) {
-                vec3 absorb{m.absorption[0], m.absorption[1], m.absorption[2]};
-                vec3 e = ((-hit.dst) * absorb) * m.absorption_strength;
-                vec3 t3{ray.transmittance.x, ray.transmittance.y, ray.transmittance.z};
-                vec3 x = t3 * vec3{rtm::exp_(e.x), rtm::exp_(e.y), rtm::exp_(e.z)};
-                ray.transmittance = vec4{x.x, x.y, x.z, 1.0f};
-            }
-            float ior = hit.backface ? m.ior : (1.0f / m.ior);
-            vec3 reflect_dir = reflect(ray.dir, hit.normal);
-            vec3 refract_dir = refract(ray.dir, hit.normal, ior);
-            float cos_theta = wmin(dot(-ray.dir, hit.normal), 1.0f);
-            float sin_theta = rtm::sqrt_(1.0f - cos_theta * cos_theta);
-            bool cannot_refract = ior * sin_theta > 1.0f;
-            bool follow_reflection = cannot_refract || reflectance(cos_theta, ior) > rand_(seed);
-            vec3 diffuse_dir = normalize(hit.normal + rand_direction(seed));
-            reflect_dir = normalize(mix(diffuse_dir, reflect_dir, m.specular));
-            refract_dir = normalize(mix(-diffuse_dir, refract_dir, m.smoothness));
-            ray.dir = follow_reflection ? reflect_dir : refract_dir;
-            ray.origin = hit.hit_point + (1e-4f * hit.normal) * wsign(dot(hit.normal, ray.dir));
-        } else {
-            bool is_specular_bounce = m.specular >= rand_(seed);
-            vec3 normal = hit.normal;  // wgsl:439-447: the normal-map branch is dead code
-            vec3 diffuse_dir = rand_hemisphere(normal, seed);
-            vec3 specular_dir = reflect(ray.dir, normal);
-            vec4 emitted_light = vec4{m.emission_color[0], m.emission_color[1], m.emission_color[2],
-                                      m.emission_color[3]} * m.emission_strength;
-            ray.dir = normalize(mix(diffuse_dir, specular_dir, m.smoothness * (is_specular_bounce ? 1.0f : 0.0f)));
-            incoming_light = incoming_light + emitted_light * ray.transmittance;
-            vec4 color;
-            if (m.flag == RT_MATERIAL_TEXTURE && m.diffuse_index != -1) {
-                color = texture_sample_level(c, m.diffuse_index, hit.uv);
-            } else {
-                color = vec4{m.color[0], m.color[1], m.color[2], m.color[3]};
-            }
-            vec4 spec{m.specular_color[0], m.specular_color[1], m.specular_color[2], m.specular_color[3]};
-            ray.transmittance = ray.transmittance * (is_specular_bounce ? spec : color);
-        }
-        float p = wmax(ray.transmittance.x, wmax(ray.transmittance.y, ray.transmittance.z));
-        bool die = rand_(seed) >= p;
-        if (tb && tb->n < tb->cap) tb->rec[tb->n++] = Transcript{hit.mesh, hit.tri, hit.dst, *seed};
-        if (die) break;
-        ray.transmittance = ray.transmittance * (1.0f / p);
-        ray.inv_dir = 1.0f / ray.dir;
+        const bool goes_on = shade_segment(c, ray, hit, incoming_light, seed);
+        if (tb && tb->n < tb->cap)
+            tb->rec[tb->n++] = hit.hit ? Transcript{hit.mesh, hit.tri, hit.dst, *seed} : Transcript{-1, -1, INF, *seed};
+        if (!goes_on) break;
     }
     stats_total[0] += _stats[0];
     stats_total[1] += _stats[1];
@@ -708,6 +718,79 @@ int oracle_intersect(const rt_scene_uniform* scene, const rt_sphere* spheres, co
         r[13] = (uint32_t)st[1];
         r[14] = 0u;
         r[15] = 0u;
+    }
+    return 0;
+}
+
+// The kernels' shading probe (include/rt_test_abi.h, rt_test_shade with RT_TEST_SHADE_PATH_END) on the same case records:
+// shade_segment for the hit a case supplies, with the scene's materials and textures, plus the bookkeeping the kernels'
+// path_end wraps around it (frag's loop, wgsl:486-497, one segment at a time): the segment counters, `seg > nb`,
+// total += light, j and "the pixel is done".  Records: 32 u32 words per case, instantiation word 0.
+int oracle_shade(const rt_scene_uniform* scene, const rt_sphere* spheres, const rt_mesh_uniform* meshes,
+                 const rt_texture_desc* textures, uint32_t n_textures, const uint32_t* cases, uint64_t n,
+                 int32_t number_of_bounces, int32_t rays_per_pixel, int32_t skybox, uint32_t* out) {
+    if (!scene || (n && (!cases || !out))) return -1;
+    std::vector<rtm::TexView> tv(n_textures);
+    for (uint32_t i = 0; i < n_textures; ++i) tv[i] = rtm::TexView{textures[i].rgba8, textures[i].width, textures[i].height};
+    orc::Ctx c{};
+    c.scene = *scene;
+    c.spheres = spheres;
+    c.meshes = meshes;
+    c.textures = tv.data();
+    c.n_textures = n_textures;
+    c.params.number_of_bounces = number_of_bounces;
+    c.params.rays_per_pixel = rays_per_pixel;
+    c.params.skybox = skybox;
+    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
+    auto flt = [](uint32_t b) { float f; memcpy(&f, &b, 4); return f; };
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t* k = cases + i * 32u;
+        uint32_t* r = out + i * 32u;
+        if (k[30] >= scene->meshes + scene->spheres) return -1;
+        orc::Ray ray{};
+        ray.origin = orc::vec3{0.0f, 0.0f, 0.0f};
+        ray.dir = orc::vec3{flt(k[0]), flt(k[1]), flt(k[2])};
+        ray.transmittance = orc::vec4{flt(k[3]), flt(k[4]), flt(k[5]), flt(k[6])};
+        orc::vec4 light{flt(k[7]), flt(k[8]), flt(k[9]), flt(k[10])};
+        orc::vec4 total{flt(k[11]), flt(k[12]), flt(k[13]), flt(k[14])};
+        uint32_t rng = k[15], meta = k[31], n_segments = 0;
+        int32_t seg = (int32_t)k[16], j = (int32_t)k[17];
+        orc::Hit hit{};
+        hit.hit = k[19] != 0u;
+        hit.dst = flt(k[20]);
+        hit.hit_point = orc::vec3{flt(k[21]), flt(k[22]), flt(k[23])};
+        hit.normal = orc::vec3{flt(k[24]), flt(k[25]), flt(k[26])};
+        hit.uv = orc::vec2{flt(k[27]), flt(k[28])};
+        hit.backface = k[29] != 0u;
+        hit.material = k[30] < scene->meshes ? meshes[k[30]].material : spheres[k[30] - scene->meshes].material;
+        bool end_path = true;
+        if (k[18] != 0u) {  // (not STEP_END: a segment is shaded)
+            n_segments = 1;
+            if ((meta & 0xffffu) != 0xffffu) meta += 1;
+            if (orc::shade_segment(c, ray, hit, light, &rng)) {
+                seg += 1;
+                end_path = seg > number_of_bounces;
+            }
+        }
+        bool done = false;
+        if (end_path) {  // wgsl:496
+            total = total + light;
+            j += 1;
+            done = j >= rays_per_pixel;
+        }
+        r[0] = bits(ray.origin.x); r[1] = bits(ray.origin.y); r[2] = bits(ray.origin.z);
+        r[3] = bits(ray.dir.x); r[4] = bits(ray.dir.y); r[5] = bits(ray.dir.z);
+        r[6] = bits(ray.transmittance.x); r[7] = bits(ray.transmittance.y); r[8] = bits(ray.transmittance.z); r[9] = bits(ray.transmittance.w);
+        r[10] = bits(light.x); r[11] = bits(light.y); r[12] = bits(light.z); r[13] = bits(light.w);
+        r[14] = bits(total.x); r[15] = bits(total.y); r[16] = bits(total.z); r[17] = bits(total.w);
+        r[18] = rng;
+        r[19] = (uint32_t)seg;
+        r[20] = (uint32_t)j;
+        r[21] = end_path ? 1u : 0u;
+        r[22] = done ? 1u : 0u;
+        r[23] = n_segments;
+        r[24] = meta;
+        for (int w = 25; w < 32; ++w) r[w] = 0u;
     }
     return 0;
 }

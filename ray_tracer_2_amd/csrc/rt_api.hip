@@ -56,6 +56,8 @@ hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const flo
                                  unsigned long long n, bool simple, bool stats, uint32_t* out, hipStream_t stream);
 hipError_t launch_units_texture(const uint8_t* rgba8, uint32_t width, uint32_t height, const float* srgb_lut, const float* uv,
                                 float* out, unsigned long long n, hipStream_t stream);
+hipError_t launch_test_shade(const RenderArgs& a, int which, const uint32_t* cases, const uint8_t* active, unsigned long long n,
+                             bool simple, bool fast_miss, bool total_lds, uint32_t* out, hipStream_t stream);
 #endif
 hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
@@ -2504,6 +2506,68 @@ int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint
     free_dev(drd);
     free_dev(dact);
     free_dev(dout);
+    return RT_OK;
+}
+
+// tests/test_gpu_shade.py: path_end / roulette_skip for host-given lane states and hits, on the uploaded scene's materials
+// and textures, with the arguments of a render (query_args) minus the pixel memo and the instantiation it launches
+// (render_takes_simple) unless `flags` force one.  Everything is checked here: nothing the kernel indexes with comes from
+// the cases unchecked.
+int rt_test_shade(rt_handle* h, int which, const uint32_t* cases, const uint8_t* active, uint64_t n, int number_of_bounces,
+                  int rays_per_pixel, int skybox, int flags, uint32_t* out) {
+    if (!h || (n && (!cases || !out))) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (which != RT_TEST_SHADE_PATH_END && which != RT_TEST_SHADE_ROULETTE_SKIP) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown function");
+    if (flags & ~(RT_TEST_SHADE_GENERAL | RT_TEST_SHADE_NO_FAST_MISS | RT_TEST_SHADE_SIMPLE | RT_TEST_SHADE_TOTAL_REGS))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    if ((flags & RT_TEST_SHADE_GENERAL) && (flags & RT_TEST_SHADE_SIMPLE))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "flags ask for both the general and the SIMPLE instantiation");
+    if (n > RT_TEST_SHADE_MAX_CASES) return fail(h, RT_ERR_INVALID_ARGUMENT, "too many cases");
+    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    RenderArgs a = query_args(h, nullptr);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t* c = cases + i * RT_TEST_SHADE_WORDS;
+        if (c[30] >= a.n_meshes + a.n_spheres) return fail(h, RT_ERR_INVALID_ARGUMENT, "object index outside the scene");
+        if (c[18] != RT_TEST_SHADE_STEP_END && c[18] != RT_TEST_SHADE_STEP_TRAVERSE) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown step mode");
+    }
+    a.params.number_of_bounces = number_of_bounces;
+    a.params.rays_per_pixel = rays_per_pixel;
+    a.params.skybox = skybox;
+    a.pixel_cache = 0u;  // (no memo: path_end's FAST_MISS reads none, and the LDS map holds none)
+    a.fast_miss = a.roulette_skip = 0u;
+    bool simple = render_takes_simple(a);
+    if (flags & RT_TEST_SHADE_GENERAL) simple = false;
+    if (flags & RT_TEST_SHADE_SIMPLE) {
+        if (a.many_mesh || !h->inst.plain_materials)
+            return fail(h, RT_ERR_INVALID_ARGUMENT, "the SIMPLE instantiation needs a few-mesh scene without spheres, glass or textures");
+        simple = true;
+    }
+    const bool total_lds = total_in_lds(a.lds_scene != 0u) && !(flags & RT_TEST_SHADE_TOTAL_REGS);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+    uint32_t *dcases = nullptr, *dout = nullptr;
+    uint8_t* dact = nullptr;
+    const size_t m = (size_t)(n ? n : 1), bytes = m * RT_TEST_SHADE_WORDS * sizeof(uint32_t), used = (size_t)n * RT_TEST_SHADE_WORDS * sizeof(uint32_t);
+    // One exit: whatever fails, the stream is drained before the buffers are freed (nothing queued may still point at them),
+    // and they are freed (staged_chunks' form).
+    const char* what = "hipMalloc";
+    hipError_t e = hipMalloc((void**)&dcases, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, bytes);
+    if (e == hipSuccess && active) e = hipMalloc((void**)&dact, m);
+    if (e == hipSuccess) {
+        what = "hipMemcpyAsync";
+        e = hipMemcpyAsync(dcases, cases, used, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && active) e = hipMemcpyAsync(dact, active, n, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) what = "hipMemsetAsync", e = hipMemsetAsync(dout, 0, bytes, h->stream);
+        if (e == hipSuccess)
+            what = "launch_test_shade", e = launch_test_shade(a, which, dcases, dact, n, simple, !(flags & RT_TEST_SHADE_NO_FAST_MISS), total_lds, dout, h->stream);
+        if (e == hipSuccess) what = "hipMemcpyAsync", e = hipMemcpyAsync(out, dout, used, hipMemcpyDeviceToHost, h->stream);
+        const hipError_t drained = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) what = "hipStreamSynchronize", e = drained;
+    }
+    free_dev(dcases);
+    free_dev(dact);
+    free_dev(dout);
+    if (e != hipSuccess) return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
     return RT_OK;
 }
 

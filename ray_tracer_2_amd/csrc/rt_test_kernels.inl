@@ -150,6 +150,99 @@ hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const flo
     return hipGetLastError();
 }
 
+// Test-only: path_end / roulette_skip for lane states the host chooses (rt_test_shade, tests/test_gpu_shade.py), one lane
+// per case, with the prologue of the render kernels (the scene staged where LDS, the lane's LDS state) and the product's
+// functions themselves, unchanged.  A lane whose `active` byte is 0 stays out of the call, as lanes do in the partial
+// waves the vote and the refill create.  Case and record: 32 words each (RT_TEST_SHADE_WORDS, include/rt_test_abi.h).
+// TOTAL_LDS is a parameter of its own here: the render kernels take total_in_lds(LDS), the callers that keep the sum in
+// registers (-DRT_TOTAL_IN_LDS=0, the experiments' wavefront kernels) the other one.
+static_assert(STEP_END == 0u && STEP_TRAVERSE == 3u, "RT_TEST_SHADE_STEP_END / _STEP_TRAVERSE of include/rt_test_abi.h");
+template <bool LDS, bool SIMPLE, bool FAST_MISS, bool TOTAL_LDS>
+__global__ void __launch_bounds__(BLOCK_THREADS) rt_test_shade_kernel(const RenderArgs a, int which, const uint32_t* __restrict__ cases,
+                                                                      const uint8_t* __restrict__ active, unsigned long long n,
+                                                                      uint32_t* __restrict__ out) {
+    uint32_t* ls = block_prologue<LDS>(a);
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    if (i >= n || (active != nullptr && active[i] == 0u)) return;
+    const uint32_t* c = cases + i * 32u;
+    auto f = [&](uint32_t k) { return __uint_as_float(c[k]); };
+    PixelState s;
+    s.x = 0u;
+    s.out_row = 0u;
+    s.ro = f3{0, 0, 0};
+    s.rd = f3{f(0), f(1), f(2)};
+    s.T = f4{f(3), f(4), f(5), f(6)};
+    s.light = f4{f(7), f(8), f(9), f(10)};
+    s.total = f4{f(11), f(12), f(13), f(14)};
+    s.rng = c[15];
+    s.seg = (int32_t)c[16];
+    s.j = (int32_t)c[17];
+    s.fresh = false;
+    s.meta = c[31];
+    if constexpr (TOTAL_LDS) {  // (the lane's LDS state only exists in the launches whose map has it: launch_test_shade)
+        ls[0] = c[11]; ls[64] = c[12]; ls[128] = c[13]; ls[192] = c[14];
+    }
+    Hit hit;
+    hit.hit = c[19] != 0u;
+    hit.dst = f(20);
+    hit.point = f3{f(21), f(22), f(23)};
+    hit.normal = f3{f(24), f(25), f(26)};
+    hit.u = f(27);
+    hit.v = f(28);
+    hit.backface = c[29] != 0u;
+    hit.mat_off = a.lay.mat_off + c[30] * MATERIAL_BYTES;  // (the host checked the index)
+    hit.suspended = false;
+    uint32_t n_segments = 0u, more_reused = 0u;
+    bool ret;
+    if (which == 0) {
+        ret = path_end<LDS, TOTAL_LDS, SIMPLE, FAST_MISS>(a, s, ls, c[18], hit, n_segments, &more_reused);
+    } else {
+        s.fresh = true;  // (the pre-step calls it in front of a sample)
+        ret = roulette_skip<LDS, TOTAL_LDS, SIMPLE>(a, s, ls, (hit.mat_off & ~15u) | MEMO_HIT | MEMO_RAY | MEMO_HIT_VALID, n_segments, more_reused);
+    }
+    f4 total = s.total;
+    if constexpr (TOTAL_LDS)
+        total = f4{__uint_as_float(ls[0]), __uint_as_float(ls[64]), __uint_as_float(ls[128]), __uint_as_float(ls[192])};
+    uint32_t* r = out + i * 32u;
+    r[0] = __float_as_uint(s.ro.x); r[1] = __float_as_uint(s.ro.y); r[2] = __float_as_uint(s.ro.z);
+    r[3] = __float_as_uint(s.rd.x); r[4] = __float_as_uint(s.rd.y); r[5] = __float_as_uint(s.rd.z);
+    r[6] = __float_as_uint(s.T.x); r[7] = __float_as_uint(s.T.y); r[8] = __float_as_uint(s.T.z); r[9] = __float_as_uint(s.T.w);
+    r[10] = __float_as_uint(s.light.x); r[11] = __float_as_uint(s.light.y); r[12] = __float_as_uint(s.light.z); r[13] = __float_as_uint(s.light.w);
+    r[14] = __float_as_uint(total.x); r[15] = __float_as_uint(total.y); r[16] = __float_as_uint(total.z); r[17] = __float_as_uint(total.w);
+    r[18] = s.rng;
+    r[19] = (uint32_t)s.seg;
+    r[20] = (uint32_t)s.j;
+    r[21] = s.fresh ? 1u : 0u;
+    r[22] = ret ? 1u : 0u;
+    r[23] = n_segments;
+    r[24] = s.meta;
+    r[25] = (a.many_mesh != 0u ? 1u : 0u) | (SIMPLE ? 2u : 0u) | (FAST_MISS ? 0u : 32u) | (LDS ? 64u : 0u) | (TOTAL_LDS ? 128u : 0u);
+    r[26] = more_reused;
+    r[27] = 0u; r[28] = 0u; r[29] = 0u; r[30] = 0u; r[31] = 0u;
+}
+
+// simple: the SIMPLE instantiation (few-mesh scenes only: the host checks); fast_miss / total_lds: path_end's FAST_MISS /
+// TOTAL_LDS.  total_lds needs total_in_lds(a.lds_scene): only then does the launch's LDS map hold the lane state.
+hipError_t launch_test_shade(const RenderArgs& a, int which, const uint32_t* cases, const uint8_t* active, unsigned long long n,
+                             bool simple, bool fast_miss, bool total_lds, uint32_t* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (total_lds && !total_in_lds(a.lds_scene != 0u)) return hipErrorInvalidValue;
+    const size_t lds = render_lds_bytes(a);
+    const uint32_t blocks = (uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
+    with_instantiation(a, simple, [&](auto lds_tag, auto, auto simple_tag) {
+        constexpr bool LDS = decltype(lds_tag)::value, SIMPLE = decltype(simple_tag)::value;
+        auto go = [&](auto fm_tag, auto tl_tag) {
+            launch_k(rt_test_shade_kernel<LDS, SIMPLE, decltype(fm_tag)::value, decltype(tl_tag)::value>, blocks, lds, stream, a, which,
+                     cases, active, n, out);
+        };
+        if (fast_miss && total_lds) go(std::true_type{}, std::true_type{});
+        else if (fast_miss) go(std::true_type{}, std::false_type{});
+        else if (total_lds) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+    });
+    return hipGetLastError();
+}
+
 hipError_t launch_units(int fn, const float* x, const float* y, float* out, unsigned long long n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_units_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, fn, x, y, out, n);

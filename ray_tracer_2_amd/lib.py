@@ -35,7 +35,7 @@ EXPORTS = [
 ]
 # every symbol include/rt_test_abi.h declares (the test library only)
 TEST_EXPORTS = ["rt_test_device_units", "rt_test_sweep", "rt_test_device_sample_texture", "rt_test_read_wavefront",
-                "rt_test_rccl_gather", "rt_test_frame_ahead_depth", "rt_test_intersect", "rt_test_scene_blob", "rt_test_pack_scene", "rt_test_sah_search",
+                "rt_test_rccl_gather", "rt_test_frame_ahead_depth", "rt_test_intersect", "rt_test_shade", "rt_test_scene_blob", "rt_test_pack_scene", "rt_test_sah_search",
                 "rt_test_option_table", "rt_test_set_option", "rt_test_launch_rule", "rt_test_frame_group", "rt_test_tile_costs"]
 
 _lib = None
@@ -164,6 +164,7 @@ def _bind(L, with_test_entries):
             "rt_test_read_wavefront": (i32, [vp, i32, vp, u64]),
             "rt_test_rccl_gather": (i32, [C.c_char_p, i32]),
             "rt_test_intersect": (i32, [vp, vp, vp, vp, u64, i32, vp]),
+            "rt_test_shade": (i32, [vp, i32, vp, vp, u64, i32, i32, i32, i32, vp]),
             "rt_test_scene_blob": (i32, [vp, vp, u64, P(u32 * 12), P(u64)]),
             "rt_test_pack_scene": (i32, [vp, u32, vp, u32, vp, u32, vp, u32, P(C.c_int32 * 5), vp, u64, P(u32 * 12), P(u32 * 18)]),
             "rt_test_sah_search": (i32, [i32, vp, u64, vp, vp, vp, u32, vp]),

@@ -226,6 +226,28 @@ class RayTracer:
                                               n, flags, out.ctypes.data))
         return out
 
+    # ---- test-only: the kernels' shading step for chosen lane states and hits (tests/test_gpu_shade.py) ----
+    def shade(self, cases, number_of_bounces, rays_per_pixel, skybox=1, active=None, roulette_skip=False, general=False,
+              simple=False, fast_miss=True, total_regs=False):
+        """path_end (roulette_skip=True: the pre-step's roulette skip) on the uploaded scene's materials for the (n, 32) u32
+        case records of include/rt_test_abi.h (rt_test_shade), one lane per case, in the instantiation a render would take
+        (general / simple force one; fast_miss=False: the counter builds' path_end; total_regs: the pixel sum in
+        registers).  Returns the (n, 32) u32 records; inactive cases (active[i] == 0) stay out and stay zero."""
+        cases = np.ascontiguousarray(cases, np.uint32)
+        if cases.ndim != 2 or cases.shape[1] != 32:
+            raise ValueError("cases are (n, 32) u32 records")
+        n = cases.shape[0]
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(active, np.uint8).ravel()
+            if act.size != n:
+                raise ValueError("one active flag per case")
+        out = np.zeros((n, 32), np.uint32)
+        flags = (1 if general else 0) | (0 if fast_miss else 2) | (4 if simple else 0) | (8 if total_regs else 0)
+        self._check(self._L.rt_test_shade(self._h, 1 if roulette_skip else 0, cases.ctypes.data, None if act is None else act.ctypes.data,
+                                          n, int(number_of_bounces), int(rays_per_pixel), int(skybox), flags, out.ctypes.data))
+        return out
+
     # ---- test-only: the scene blob (tests/test_gpu_scene_edits.py) ----
     def scene_blob(self):
         """(blob bytes as uint8, SceneLayout as 12 uint32 -- A.SCENE_LAYOUT_FIELDS --, device address) of the uploaded scene

@@ -12,6 +12,8 @@ Box-Muller, disk), :214-221 (pow, smoothstep), :245-251 (acos, atan2), :455 (tex
 import numpy as np
 import pytest
 
+from _rng_edge import A_LCG, C_LCG, M_OUT, edge_states, state_before  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 FN = {"log": 0, "cos": 1, "sin": 2, "exp": 3, "exp2": 4, "log2": 5, "pow": 6, "acos": 7, "atan2": 8, "sqrt": 9,
@@ -46,28 +48,6 @@ def rand_values(rng, n):
 @pytest.fixture(scope="module")
 def rng():
     return np.random.RandomState(20261004)
-
-
-A_LCG, C_LCG, M_OUT = 747796405, 2891336453, 277803737   # wgsl:195-200
-
-
-def state_before(output):
-    """The RNG state s for which next_random_number(s) returns `output` (the generator is a
-    permutation of u32: invert the two xorshifts, the odd multiplications and the LCG step)."""
-    w = output ^ (output >> 22)
-    x = (w * pow(M_OUT, -1, 2 ** 32)) % 2 ** 32
-    k = (x >> 28) + 4                      # the top four bits pass through the xorshift unchanged
-    s1, shift = x, k
-    while shift < 32:                      # s1 = x ^ (s1 >> k)
-        s1 = x ^ (s1 >> k)
-        shift += k
-    assert ((((s1 >> ((s1 >> 28) + 4)) ^ s1) * M_OUT) % 2 ** 32) == w
-    return ((s1 - C_LCG) * pow(A_LCG, -1, 2 ** 32)) % 2 ** 32
-
-
-def edge_states():
-    """States whose next rand() is exactly 0.0 or rounds to 1.0 (r >= 0xffffff80)."""
-    return np.array([state_before(0)] + [state_before(r) for r in range(0xffffff80, 0x100000000)], np.uint32)
 
 
 @pytest.fixture(scope="module")

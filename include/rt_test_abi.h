@@ -141,7 +141,11 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
  *   GRID     {LDS bytes per workgroup, persistent_blocks} -> {workgroups per CU, persistent grid}
  *   FRAME_GROUP {frames of the batch, tiles of the launch, resident waves, tile-major order, rounds planned,
  *                scene in global memory or many-mesh}
- *               -> {frames per work item, the compile-time cap RT_FRAME_GROUP} */
+ *               -> {frames per work item, the compile-time cap RT_FRAME_GROUP}
+ *   FRAME_TAPER {frames of the batch, head group size G, resident waves, the order's max_cost, the cost floor, tiles,
+ *                the address of a u32 array: the tiles' costs, then RT_TEST_TAPER_WORDS words that receive the table,
+ *                alpha (0: the shipped constant)}
+ *               -> {segments of the table, the alpha used}: frame_taper_table over the costs' histogram, on the host */
 #define RT_TEST_RULE_VOTES 0
 #define RT_TEST_RULE_ROUNDS 1
 #define RT_TEST_RULE_VARIANT 2
@@ -149,6 +153,8 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
 #define RT_TEST_RULE_BATCH 4
 #define RT_TEST_RULE_GRID 5
 #define RT_TEST_RULE_FRAME_GROUP 6
+#define RT_TEST_RULE_FRAME_TAPER 7
+#define RT_TEST_TAPER_WORDS 28 /* {segments, items, frames of the batch, G}, then {first rank, group size, first item} x 8 */
 int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
 
 /* The frame groups of a handle's batches (RenderArgs::frame_group: the frames of a pixel that one lane renders back to
@@ -156,6 +162,17 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
  * frame-major order, a deferred-walk sequence and a library built with -DRT_FRAME_GROUP=1 still render with 1.
  * force < 0 changes nothing.  last_out (may be NULL): the group size of the handle's last launch. */
 int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out);
+
+/* The taper of a handle's grouped batches (RenderArgs::frame_taper: the tile order cut into segments, each with a group
+ * size of its own).  n_segments >= 1 forces the segments {first_rank[k], size[k]} -- first ranks ascending from 0, sizes
+ * 1..64, at most 8 -- on the handle's later batches in place of the rule's table; a batch that takes no groups (see
+ * rt_test_frame_group) ignores them.  0: the rule decides again; < 0 changes nothing.  table_out (may be NULL):
+ * RT_TEST_TAPER_WORDS words, the table of the handle's last launch, zeros if it ran without one. */
+int rt_test_frame_taper(rt_handle* h, int n_segments, const uint32_t* first_rank, const uint32_t* size, uint32_t* table_out);
+/* The device's evaluation of the taper rule on n_tiles host-given costs (the kernel that runs behind a new tile order),
+ * every input the caller's -- rule FRAME_TAPER of rt_test_launch_rule is the host's evaluation of the same function. */
+int rt_test_frame_taper_rule(rt_handle* h, const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor,
+                             uint32_t n_batch, uint32_t head, uint32_t waves, uint32_t alpha, uint32_t* table_out);
 
 /* The rays per 8x8 tile that the handle's last cost-recording launch counted (option "tile_feedback": the first frame of
  * a batch, or a single frame): n_tiles counts in tile order, read after everything queued on the handle is done. */

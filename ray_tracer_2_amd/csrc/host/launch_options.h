@@ -176,10 +176,15 @@ inline uint32_t equal_batch(uint32_t n_frames, uint32_t cap) {
 // groups) for a strip share of eight ranks, 0.8 tiles per resident wave, at the 28 frames of its batches -- and then the
 // smallest value that needs no more groups (20 frames at 8 per group: 7 + 7 + 6, not 8 + 8 + 4; the same number of
 // pixels taken, a shorter longest item).  -DRT_FRAME_GROUP=1 compiles the groups out of the kernels.
+// The taper (frame_taper_table, below) cuts that tail where it arises: the tiles pulled while little work is left behind
+// them get groups of G / 2, G / 4, ... 1 frames, so the launch ends on items of one frame and G prices the head alone.
 #ifndef RT_FRAME_GROUP
 #define RT_FRAME_GROUP 8
 #endif
-constexpr uint32_t FRAME_GROUP_CAP = RT_FRAME_GROUP, FRAME_GROUP_MIN_ITEMS_PER_WAVE = 24;
+#ifndef RT_FRAME_GROUP_FLOOR  // (the item floor, for tools/build_variant.sh: profiles/frame_taper_ab.txt section 6)
+#define RT_FRAME_GROUP_FLOOR 24
+#endif
+constexpr uint32_t FRAME_GROUP_CAP = RT_FRAME_GROUP, FRAME_GROUP_MIN_ITEMS_PER_WAVE = RT_FRAME_GROUP_FLOOR;
 static_assert(FRAME_GROUP_CAP >= 1 && FRAME_GROUP_CAP <= MAX_BATCH_FRAMES, "RT_FRAME_GROUP: 1 .. 64");
 inline uint32_t frame_group_for(uint32_t n_batch, uint64_t tiles, uint32_t resident_waves, bool tile_major, bool rounds,
                                 bool costly = false) {
@@ -188,6 +193,109 @@ inline uint32_t frame_group_for(uint32_t n_batch, uint64_t tiles, uint32_t resid
     while (g > 1u && tiles * ((n_batch + g - 1u) / g) < (uint64_t)resident_waves * FRAME_GROUP_MIN_ITEMS_PER_WAVE) g -= 1u;
     const uint32_t groups = (n_batch + g - 1u) / g;
     return (n_batch + groups - 1u) / groups;
+}
+
+// The taper of a grouped launch (RenderArgs::frame_taper): the tile order, heaviest first, is cut into at most
+// TAPER_MAX_SEGMENTS segments of ranks, and the tiles of a segment are cut into ceil(n / g) groups of the segment's own g
+// frames.  The table: TAPER_HEAD_WORDS words {segments, items of the launch, n, G}, then per segment {first rank of the
+// tile order, g, first item index}.  The rule reads the tile costs (rays per tile of an earlier frame) as a histogram over
+// TAPER_BINS bins in the order's own sense -- frame_taper_bin: bin 0 holds the heaviest tiles, a bin's tiles are
+// neighbours in the order --, count[b] tiles in bin b and weight[b] = the sum of their effective costs c' = max(cost -
+// floor, 0) (frame_taper_effective; `floor`: the rays a tile is charged for segments that the primary table serves at
+// almost no cost, 64 x rays_per_pixel when the launch has a complete table: sky tiles count as no work).  With R(b) =
+// the weight of bins b and later, bin b takes the largest g of G, ceil(G / 2), ceil(G / 4), ..., 1 with
+//     g x (weight[b] / count[b]) x alpha x waves <= n x R(b):
+// an item is at most 1 / alpha of what every resident wave still has to do when the item is pulled.  A bin without
+// effective cost takes G (sky tiles keep their groups: their takes would cost more than the tail they leave), neighbours
+// of equal g merge, empty bins are skipped, and while more than TAPER_MAX_SEGMENTS segments result the bins are merged
+// in pairs and the rule runs again.  G <= 1, n < 2 or waves = 0: one segment of G.  The host and rt_frame_taper_kernel
+// evaluate this one function (products in double: the same IEEE operations in the same order on both sides); count and
+// weight are scratch (merged in place).  -DRT_FRAME_TAPER=0 compiles the taper out of the kernels and the host.
+#ifndef RT_FRAME_TAPER
+#define RT_FRAME_TAPER 1
+#endif
+#ifndef RT_FRAME_TAPER_ALPHA
+#define RT_FRAME_TAPER_ALPHA 4
+#endif
+#ifdef __HIP__
+#define RT_RULE_FN __host__ __device__ inline
+#else
+#define RT_RULE_FN inline
+#endif
+constexpr uint32_t TAPER_MAX_SEGMENTS = 8, TAPER_BINS = 64, TAPER_HEAD_WORDS = 4, TAPER_WORDS = TAPER_HEAD_WORDS + 3u * TAPER_MAX_SEGMENTS;
+constexpr uint32_t TILE_ORDER_BINS = 2048;  // (rt_tile_order_kernel's counting sort; a taper bin is TILE_ORDER_BINS / TAPER_BINS of them)
+constexpr uint32_t FRAME_TAPER_ALPHA = RT_FRAME_TAPER_ALPHA;
+static_assert(TILE_ORDER_BINS % TAPER_BINS == 0 && FRAME_TAPER_ALPHA >= 1, "taper bins are whole runs of order bins");
+RT_RULE_FN uint32_t frame_taper_bin(uint32_t cost, uint32_t max_cost) {
+    const unsigned long long scale = max_cost ? max_cost : 1u;
+    const unsigned long long b = (unsigned long long)(cost < max_cost ? cost : max_cost) * (TILE_ORDER_BINS - 1u) / scale;
+    return ((TILE_ORDER_BINS - 1u) - (uint32_t)b) / (TILE_ORDER_BINS / TAPER_BINS);
+}
+RT_RULE_FN uint32_t frame_taper_effective(uint32_t cost, uint32_t cost_floor) { return cost > cost_floor ? cost - cost_floor : 0u; }
+RT_RULE_FN void frame_taper_table(uint32_t* count, unsigned long long* weight, uint32_t bins, uint32_t n, uint32_t head, uint32_t waves,
+                                  uint32_t alpha, uint32_t* table) {
+    const uint32_t G = head ? head : 1u;
+    const bool plain = G <= 1u || n < 2u || waves == 0u;
+    for (;;) {
+        unsigned long long behind = 0;
+        for (uint32_t b = 0; b < bins; ++b) behind += weight[b];
+        uint32_t segments = 0, rank = 0, item = 0, last = 0;
+        bool over = false;
+        for (uint32_t b = 0; b < bins && !over; ++b) {
+            if (count[b] == 0u) continue;
+            uint32_t g = G;
+            if (!plain) {
+                const double have = (double)n * (double)behind * (double)count[b];
+                while (g > 1u && (double)g * (double)alpha * (double)waves * (double)weight[b] > have) g = (g + 1u) / 2u;
+            }
+            if (segments == 0u || g != last) {
+                if (segments == TAPER_MAX_SEGMENTS) {
+                    over = true;
+                    break;
+                }
+                uint32_t* seg = table + TAPER_HEAD_WORDS + 3u * segments;
+                seg[0] = rank;
+                seg[1] = g;
+                seg[2] = item;
+                segments += 1u;
+                last = g;
+            }
+            rank += count[b];
+            item += count[b] * ((n + g - 1u) / g);
+            behind -= weight[b];
+        }
+        if (!over) {
+            if (segments == 0u) {  // (no tiles)
+                table[TAPER_HEAD_WORDS] = 0u;
+                table[TAPER_HEAD_WORDS + 1u] = G;
+                table[TAPER_HEAD_WORDS + 2u] = 0u;
+                segments = 1u;
+            }
+            table[0] = segments;
+            table[1] = item;
+            table[2] = n;
+            table[3] = G;
+            for (uint32_t w = TAPER_HEAD_WORDS + 3u * segments; w < TAPER_WORDS; ++w) table[w] = 0u;
+            return;
+        }
+        const uint32_t half = (bins + 1u) / 2u;  // (at TAPER_MAX_SEGMENTS bins and fewer nothing is over)
+        for (uint32_t b = 0; b < half; ++b) {
+            const bool two = 2u * b + 1u < bins;
+            count[b] = count[2u * b] + (two ? count[2u * b + 1u] : 0u);
+            weight[b] = weight[2u * b] + (two ? weight[2u * b + 1u] : 0ull);
+        }
+        bins = half;
+    }
+}
+// ... and its histogram on the host, from the costs themselves (the device builds the same one: rt_frame_taper_kernel)
+inline void frame_taper_histogram(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor, uint32_t* count,
+                                  unsigned long long* weight) {
+    for (uint32_t b = 0; b < TAPER_BINS; ++b) count[b] = 0u, weight[b] = 0ull;
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        const uint32_t b = frame_taper_bin(cost[t], max_cost);
+        count[b] += 1u;
+        weight[b] += frame_taper_effective(cost[t], cost_floor);
+    }
 }
 
 // workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)

@@ -37,6 +37,8 @@ bool render_takes_simple(const RenderArgs& a);
 size_t render_lds_bytes(const RenderArgs& a);
 hipError_t launch_tile_order(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t* order,
                              hipStream_t stream);
+hipError_t launch_frame_taper(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor, uint32_t n_batch,
+                              uint32_t head, uint32_t waves, uint32_t alpha, uint32_t* table, hipStream_t stream);
 hipError_t launch_primary(const RenderArgs& a, void* table, bool with_hits, hipStream_t stream);
 hipError_t launch_blend_frames(const BlendArgs& b, hipStream_t stream);
 hipError_t launch_walk(const RenderArgs& a, uint32_t compute_units, hipStream_t stream);
@@ -226,6 +228,13 @@ struct rt_handle {
     // tile-cost feedback: rays per tile of the previous frame order the next frame's tiles
     uint32_t* tile_cost[2] = {nullptr, nullptr};
     uint32_t* tile_order = nullptr;
+    // The taper of the grouped launches (RenderArgs::frame_taper): two tables of rt2::TAPER_WORDS words -- the one that
+    // rt_frame_taper_kernel wrote behind the last tile order, good for batches of taper_batch frames in groups of
+    // taper_head (0: none), and the one a test forces (rt_test_frame_taper: its segments' first ranks and group sizes).
+    uint32_t* frame_taper = nullptr;
+    uint32_t taper_batch = 0, taper_head = 0;
+    const uint32_t* last_taper = nullptr;  // the table of the last launch (null: it ran untapered)
+    std::vector<uint32_t> taper_forced;
     uint32_t tile_capacity = 0;
     int cost_slot = 0;
     FrameShape history;  // the frame layout the tile costs and the tile order were recorded for
@@ -460,6 +469,7 @@ int rt_create(int device_ordinal, uint32_t max_width, uint32_t max_height, rt_ha
     h->tile_capacity = ((max_width + 7) / 8) * ((max_height + 7) / 8 + 1);
     for (int k = 0; k < 2; ++k) HIP_TRY(h, hipMalloc((void**)&h->tile_cost[k], (size_t)h->tile_capacity * sizeof(uint32_t)));
     HIP_TRY(h, hipMalloc((void**)&h->tile_order, (size_t)h->tile_capacity * sizeof(uint32_t)));
+    HIP_TRY(h, hipMalloc((void**)&h->frame_taper, 2u * rt2::TAPER_WORDS * sizeof(uint32_t)));
     {
         hipDeviceProp_t prop;
         HIP_TRY(h, hipGetDeviceProperties(&prop, device_ordinal));
@@ -516,6 +526,7 @@ void rt_destroy(rt_handle* h) {
     free_dev(h->tile_cost[0]);
     free_dev(h->tile_cost[1]);
     free_dev(h->tile_order);
+    free_dev(h->frame_taper);
     free_dev(h->srgb_lut);
     for (auto& e : h->ev_pool) {
         (void)hipEventDestroy(e.first);
@@ -1398,18 +1409,32 @@ static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, L
         h->have_order = false;
         h->costs_ready = false;
     }
+    if (!h->have_order) h->taper_head = 0;  // (a table cuts the order it was written behind)
     if (h->costs_ready && (!h->have_order || h->order_age >= (uint32_t)h->opt.tile_feedback_period)) {
         const long long per_tile = 64ll * (params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) *
                                    (params->number_of_bounces >= 0 ? params->number_of_bounces + 1 : 0);
         const uint32_t max_cost = per_tile > 0xffffffffll ? 0xffffffffu : (uint32_t)per_tile;
         HIP_TRY(h, barrier_other(h, pl));
         HIP_TRY(h, launch_tile_order(h->tile_cost[h->cost_slot], n_tiles, max_cost, h->tile_order, pl.S));
+        // ... and, for a grouped launch, the taper of that order from the same costs (rt2::frame_taper_table).  Segments
+        // that a complete primary table serves are counted as rays and cost next to nothing: the floor takes them out.
+        h->taper_head = 0;
+        if (RT_FRAME_TAPER != 0 && a.frame_group > 1u && h->frame_taper) {
+            const long long served = a.primary_complete != 0u ? 64ll * params->rays_per_pixel : 0ll;
+            HIP_TRY(h, launch_frame_taper(h->tile_cost[h->cost_slot], n_tiles, max_cost, served > 0xffffffffll ? 0xffffffffu : (uint32_t)served,
+                                          pl.n_batch, a.frame_group, a.persistent_blocks * WAVES_PER_BLOCK, rt2::FRAME_TAPER_ALPHA,
+                                          h->frame_taper, pl.S));
+            h->taper_batch = pl.n_batch;
+            h->taper_head = a.frame_group;
+        }
         h->have_order = true;
         h->order_age = 0;
         h->costs_ready = false;
     }
     const uint32_t frames_now = pl.n_batch ? pl.n_batch : 1u;
     if (h->have_order) a.tile_order = h->tile_order;
+    // (the table of another batch size or group size, or no order yet: the launch runs untapered)
+    if (h->have_order && a.frame_group > 1u && h->taper_head == a.frame_group && h->taper_batch == pl.n_batch) a.frame_taper = h->frame_taper;
     if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->opt.tile_feedback_period) {
         h->cost_slot ^= 1;
         a.tile_cost = h->tile_cost[h->cost_slot];
@@ -1419,6 +1444,35 @@ static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, L
     }
     h->order_age += frames_now;
     h->history = pl.shape;
+    return RT_OK;
+}
+
+// Test-only (rt_test_frame_taper): the forced segments as this launch's table, in place of the rule's -- for a launch that
+// takes groups at all (frame_groups).  The items are counted here, for this batch's frames and this launch's tiles; a
+// first rank past the tiles gives an empty segment.
+static int forced_taper(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
+    if (RT_FRAME_TAPER != 0 && a.frame_group > 1u && !h->taper_forced.empty() && h->frame_taper) {
+        uint32_t table[rt2::TAPER_WORDS] = {};
+        const uint32_t segments = (uint32_t)h->taper_forced.size() / 2u;
+        uint32_t item = 0;
+        for (uint32_t k = 0; k < segments; ++k) {
+            const uint32_t rank = std::min(h->taper_forced[2 * k], pl.n_tiles), g = h->taper_forced[2 * k + 1];
+            const uint32_t next = k + 1 < segments ? std::min(h->taper_forced[2 * k + 2], pl.n_tiles) : pl.n_tiles;
+            uint32_t* seg = table + rt2::TAPER_HEAD_WORDS + 3 * k;
+            seg[0] = rank;
+            seg[1] = g;
+            seg[2] = item;
+            item += (next - rank) * ((pl.n_batch + g - 1u) / g);
+        }
+        table[0] = segments;
+        table[1] = item;
+        table[2] = pl.n_batch;
+        table[3] = a.frame_group;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));  // (an earlier batch may still read the table)
+        HIP_TRY(h, hipMemcpy(h->frame_taper + rt2::TAPER_WORDS, table, sizeof(table), hipMemcpyHostToDevice));
+        a.frame_taper = h->frame_taper + rt2::TAPER_WORDS;
+    }
+    h->last_taper = a.frame_group > 1u ? a.frame_taper : nullptr;  // (the slot is q_out's in a launch that parks)
     return RT_OK;
 }
 
@@ -1615,6 +1669,7 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
     if ((rc = wavefront_prepare(h, params, a, pl.n_tiles, n_batch, pl.wf, pl.rounds)) != RT_OK) return rc;
     if ((rc = prepare_park_queues(h, pl)) != RT_OK) return rc;
     if ((rc = tile_feedback(h, params, a, pl)) != RT_OK) return rc;
+    if ((rc = forced_taper(h, a, pl)) != RT_OK) return rc;
     if ((rc = timing_events(h, pl)) != RT_OK) return rc;
     note_launch(h, params, a, pl);
     if (pl.pipe && pl.pipe_barrier) {   // the tables this frame rewrote: later frames of the other stream wait for them
@@ -2701,6 +2756,20 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
             a = rt2::frame_group_for((uint32_t)in[0], (uint64_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0, in[5] != 0);
             b = rt2::FRAME_GROUP_CAP;
             break;
+        case RT_TEST_RULE_FRAME_TAPER: {
+            static_assert(RT_TEST_TAPER_WORDS == rt2::TAPER_WORDS, "include/rt_test_abi.h: the taper table");
+            // (in[6]: the address of n_tiles costs followed by room for the table)
+            uint32_t* words = (uint32_t*)(uintptr_t)in[6];
+            const uint32_t n_tiles = (uint32_t)in[5];
+            if (!words || in[5] < 0 || in[5] > (1ll << 24)) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "frame taper rule: costs and at most 2^24 tiles");
+            uint32_t count[rt2::TAPER_BINS];
+            unsigned long long weight[rt2::TAPER_BINS];
+            rt2::frame_taper_histogram(words, n_tiles, (uint32_t)in[3], (uint32_t)in[4], count, weight);
+            b = in[7] > 0 ? (uint32_t)in[7] : rt2::FRAME_TAPER_ALPHA;
+            rt2::frame_taper_table(count, weight, rt2::TAPER_BINS, (uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], b, words + n_tiles);
+            a = words[n_tiles];
+            break;
+        }
         default: return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "unknown rule");
     }
     out[0] = a;
@@ -2715,6 +2784,50 @@ int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out) {
     if (!h || force > (int)RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "frame group: -1 (leave), 0 (the rule), 1..64");
     if (force >= 0) h->frame_group_forced = (uint32_t)force;
     if (last_out) *last_out = h->last_frame_group;
+    return RT_OK;
+}
+
+// Test-only: the taper of handle `h` (RenderArgs::frame_taper).  n_segments >= 1 forces the segments {first_rank[k],
+// size[k]} on its later grouped batches, bypassing the rule; 0 gives the rule its say again; < 0 changes nothing.
+// table_out: the table the handle's last launch ran with, zeros if it ran untapered.
+int rt_test_frame_taper(rt_handle* h, int n_segments, const uint32_t* first_rank, const uint32_t* size, uint32_t* table_out) {
+    if (!h) return RT_ERR_INVALID_ARGUMENT;
+    if (n_segments > (int)rt2::TAPER_MAX_SEGMENTS || (n_segments > 0 && (!first_rank || !size)))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "frame taper: at most 8 segments, each with a first rank and a group size");
+    if (n_segments >= 0) {
+        std::vector<uint32_t> forced;
+        for (int k = 0; k < n_segments; ++k) {
+            if (first_rank[k] < (k ? first_rank[k - 1] : 0u) || (k == 0 && first_rank[0] != 0u) || size[k] < 1u || size[k] > RT_MAX_BATCH_FRAMES)
+                return fail(h, RT_ERR_INVALID_ARGUMENT, "frame taper: first ranks ascending from 0, group sizes 1..64");
+            forced.push_back(first_rank[k]);
+            forced.push_back(size[k]);
+        }
+        h->taper_forced = forced;
+    }
+    if (table_out) {
+        memset(table_out, 0, rt2::TAPER_WORDS * sizeof(uint32_t));
+        if (int rc = rt_synchronize(h); rc != RT_OK) return rc;
+        if (h->last_taper) HIP_TRY(h, hipMemcpy(table_out, h->last_taper, rt2::TAPER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
+// Test-only: the device's evaluation of the taper rule (rt_frame_taper_kernel) on n_tiles host-given tile costs -- what
+// tile_feedback launches behind a new tile order, with every input the caller's.
+int rt_test_frame_taper_rule(rt_handle* h, const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor, uint32_t n_batch,
+                             uint32_t head, uint32_t waves, uint32_t alpha, uint32_t* table_out) {
+    if (!h || !table_out || (n_tiles && !cost)) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_tiles > (1u << 24) || head > RT_MAX_BATCH_FRAMES || n_batch > RT_MAX_BATCH_FRAMES)
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "frame taper rule: at most 2^24 tiles, 64 frames");
+    HIP_TRY(h, hipSetDevice(h->device));
+    uint32_t* dev = nullptr;
+    HIP_TRY(h, hipMalloc((void**)&dev, ((size_t)n_tiles + rt2::TAPER_WORDS) * sizeof(uint32_t)));
+    hipError_t e = n_tiles ? hipMemcpy(dev + rt2::TAPER_WORDS, cost, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) e = launch_frame_taper(dev + rt2::TAPER_WORDS, n_tiles, max_cost, cost_floor, n_batch, head, waves, alpha, dev, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(table_out, dev, rt2::TAPER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    free_dev(dev);
+    HIP_TRY(h, e);
     return RT_OK;
 }
 

@@ -156,7 +156,15 @@ struct RenderArgs {
     uint32_t park_levels;        // != 0: a ray parks only if the walk's first two levels reach a grandchild box (option "park_levels")
     float4* q_in;                 // park records to resume instead of tiles (null: the work items are tiles)
     const uint32_t* q_in_count;   // their number (written by the launch before)
-    float4* q_out;                // where this launch parks
+    // (one slot of the kernarg segment for two launches that exclude each other -- a grouped launch never parks, its
+    // instantiations have no PARK --, so that every field keeps its place and no kernel's argument offsets move)
+    union {
+        float4* q_out;            // where this launch parks
+        // The taper of a grouped launch (host/launch_options.h: frame_taper_table), or null: every tile in groups of
+        // frame_group.  rt2::TAPER_WORDS words: {segments, items, batch_frames, frame_group}, then {first rank of the tile
+        // order, frames per group, first item index} per segment: a segment's tiles are cut into groups of its own size.
+        const uint32_t* frame_taper;
+    };
     uint32_t* q_out_count;
     uint32_t defer_mesh, defer_xform;  // the deferred mesh and the mesh whose matrices give its local ray
 #if RT_WALK2
@@ -204,6 +212,12 @@ struct RenderArgs {
 constexpr bool FRAME_GROUPS = false;
 #else
 constexpr bool FRAME_GROUPS = true;
+#endif
+// -DRT_FRAME_TAPER=0 compiles the taper out of the grouped kernels (its default and its rule: host/launch_options.h)
+#if defined(RT_FRAME_TAPER) && RT_FRAME_TAPER == 0
+constexpr bool FRAME_TAPER = false;
+#else
+constexpr bool FRAME_TAPER = FRAME_GROUPS;
 #endif
 constexpr uint32_t WF_STATE_PLANES = 6, WF_HIT_PLANES = 2;
 // Park record of a pixel: 14 x 16 B, stored in blocks of 64 records, plane by plane (plane p of record i of block b at

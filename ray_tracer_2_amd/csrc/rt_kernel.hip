@@ -34,6 +34,7 @@
 
 #include <type_traits>
 
+#include "host/launch_options.h"  // (rt2::frame_taper_table and its constants: the rule the host evaluates too)
 #include "rt_device.h"
 #include "rt_texture.h"
 #include "rt_transc.h"
@@ -1619,6 +1620,8 @@ enum : uint32_t { MEMO_HIT = 1u, MEMO_BACKFACE = 2u, MEMO_RAY = 4u, MEMO_HIT_VAL
 // from hoisting those loads -- and every wave-uniform float computation that depends on them
 // (there is no scalar float ALU: they would be parked in VGPRs) -- out of the render loop.
 typedef const __attribute__((address_space(4))) RenderArgs ColdArgs;
+typedef const __attribute__((address_space(4))) uint32_t ColdWord;  // (a table that no kernel of the launch writes: scalar loads)
+constexpr uint32_t POOL_GROUP_SHIFT = 8;  // pool_frame of a grouped kernel: the item's first frame | its group length << 8
 DEV ColdArgs& cold_args() {
     ColdArgs* p = (ColdArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
@@ -2381,7 +2384,11 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
     static_assert(!GROUPS || (FRAME_GROUPS && LDS && !TLAS && !PARK && !HYB), "frame groups: the LDS-scene few-mesh kernels");
     const bool grouped = GROUPS && a.frame_group > 1u && a.batch_frames != 0u && a.batch_tile_major != 0u && have_samples;
     const uint32_t n_groups = grouped ? (a.batch_frames + a.frame_group - 1u) / a.frame_group : 0u;
-    const uint32_t n_items = resuming ? (n_parked + 63u) >> 6 : n_tiles * (grouped ? n_groups : a.batch_frames ? a.batch_frames : 1u);
+    // (a tapered launch, RenderArgs::frame_taper: the table holds the items of its segments)
+    const bool tapered = GROUPS && FRAME_TAPER && grouped && a.frame_taper != nullptr;
+    const uint32_t n_items = resuming  ? (n_parked + 63u) >> 6
+                             : tapered ? ((ColdWord*)a.frame_taper)[1]
+                                       : n_tiles * (grouped ? n_groups : a.batch_frames ? a.batch_frames : 1u);
     // (a launch with fewer items than waves -- the later rounds of a deferred-walk sequence -- would otherwise consist
     // of thousands of pulls queueing up on one address: the waves beyond the items never pull)
     bool exhausted = PARK && blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6) >= n_items;
@@ -2413,7 +2420,36 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
                     pool_left = n_parked - pool_base < 64u ? n_parked - pool_base : 64u;
                 } else {
                     pool_frame = 0u;
-                    if (grouped) {  // (tile, group) order: a tile's groups back to back; pool_frame = the group's first frame
+                    uint32_t group_len = a.frame_group;  // (GROUPS) the frames of this item's group
+                    bool cut = false;
+                    if constexpr (GROUPS && FRAME_TAPER) {
+                        // Tapered launch: the item against the segment table -- the last segment that starts at or before it,
+                        // then (rank, group) inside the segment as below, with the segment's own group length.  A cold path:
+                        // the table is re-read here through the kernarg segment, by scalar loads, and nothing of it stays
+                        // in registers across the render loop.
+                        ColdWord* tb = (ColdWord*)cold_args().frame_taper;
+                        if (grouped && tb != nullptr) {
+                            const uint32_t n_segments = tb[0];
+                            uint32_t rank0 = tb[rt2::TAPER_HEAD_WORDS], item0 = tb[rt2::TAPER_HEAD_WORDS + 2u];
+                            group_len = tb[rt2::TAPER_HEAD_WORDS + 1u];
+                            for (uint32_t k = 1; k < n_segments && k < rt2::TAPER_MAX_SEGMENTS; ++k) {
+                                const uint32_t first = tb[rt2::TAPER_HEAD_WORDS + 3u * k + 2u];
+                                if (first <= t) {
+                                    rank0 = tb[rt2::TAPER_HEAD_WORDS + 3u * k];
+                                    group_len = tb[rt2::TAPER_HEAD_WORDS + 3u * k + 1u];
+                                    item0 = first;
+                                }
+                            }
+                            group_len = group_len < 1u ? 1u : group_len > RT_MAX_BATCH_FRAMES ? RT_MAX_BATCH_FRAMES : group_len;
+                            const uint32_t per_tile = (a.batch_frames + group_len - 1u) / group_len;
+                            const uint32_t tt = (t - item0) / per_tile;
+                            pool_frame = (t - item0 - tt * per_tile) * group_len;
+                            t = rank0 + tt < n_tiles ? rank0 + tt : n_tiles - 1u;  // (a table is never trusted with an address)
+                            cut = true;
+                        }
+                    }
+                    if (cut) {  // (decoded against the table, above)
+                    } else if (grouped) {  // (tile, group) order: a tile's groups back to back; pool_frame = the group's first frame
                         const uint32_t tt = t / n_groups;
                         pool_frame = (t - tt * n_groups) * a.frame_group;
                         t = tt;
@@ -2436,6 +2472,8 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
                     }
                     // (a batch records the costs of its first frame)
                     if (a.tile_cost && lane == 0 && pool_frame == 0u) tile_cost_pull(a, cost_tbl, pull_seq & (COST_SLOTS - 1u), t);
+                    // (the group's length rides in pool_frame's spare bits from the pull to the takes of its pixels)
+                    if constexpr (GROUPS && FRAME_TAPER) pool_frame |= group_len << POOL_GROUP_SHIFT;
                 }
             }
             if (pool_left != 0) {
@@ -2453,21 +2491,23 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
                     const uint32_t q = pool_base + rank;
                     ColdArgs& ca = cold_args();
                     const PixelCoord px = pixel_at(ca, pool_txy & 0xffffu, pool_txy >> 16, q & 63u);  // (q >> 6 is the pulled tile)
+                    const uint32_t item_frame = GROUPS && FRAME_TAPER ? pool_frame & ((1u << POOL_GROUP_SHIFT) - 1u) : pool_frame;
                     if (px.valid) {
                         DIAG(15);
                         const CameraConsts cam = camera_consts(ca);
-                        pixel_begin<total_in_lds(LDS)>(ca, cam, s, ls, px.x, px.y, px.out_row, pool_frame);
+                        pixel_begin<total_in_lds(LDS)>(ca, cam, s, ls, px.x, px.y, px.out_row, item_frame);
                         pixel_cache_begin<false, !LDS>(a, ca, cam, s, ls);
-                        s.meta = ((pull_seq & (COST_SLOTS - 1u)) << 16) | (pool_frame << 19);
+                        s.meta = ((pull_seq & (COST_SLOTS - 1u)) << 16) | (item_frame << 19);
                         if (grouped) {  // the group's frames behind this one: the lane restarts the pixel for each (below)
-                            const uint32_t left = a.batch_frames - pool_frame - 1u;
-                            s.meta |= (left < a.frame_group - 1u ? left : a.frame_group - 1u) << META_FRAMES_LEFT_SHIFT;
+                            const uint32_t left = a.batch_frames - item_frame - 1u;
+                            const uint32_t behind = (GROUPS && FRAME_TAPER ? pool_frame >> POOL_GROUP_SHIFT : a.frame_group) - 1u;
+                            s.meta |= (left < behind ? left : behind) << META_FRAMES_LEFT_SHIFT;
                         }
                         if (have_samples) {
                             active = true;
                         } else {
                             pixel_finish<total_in_lds(LDS), GROUPS>(ca, s, ls);  // 0 / 0 = NaN, as the shader would store
-                            if (a.tile_cost && pool_frame == 0u) tile_cost_add(a, cost_tbl, s);
+                            if (a.tile_cost && item_frame == 0u) tile_cost_add(a, cost_tbl, s);
                         }
                     }
                 }
@@ -2945,6 +2985,54 @@ __global__ void __launch_bounds__(1024) rt_tile_order_kernel(const uint32_t* __r
 hipError_t launch_tile_order(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t* order,
                              hipStream_t stream) {
     hipLaunchKernelGGL(rt_tile_order_kernel, dim3(1), dim3(1024), 0, stream, cost, n_tiles, max_cost, order);
+    return hipGetLastError();
+}
+
+// The segment table of the grouped launch that follows a new tile order (RenderArgs::frame_taper): the costs the order
+// was sorted by, as the histogram of host/launch_options.h -- rt2::frame_taper_bin is the order's own bin_of over runs of
+// its bins, so a taper bin's tiles are neighbours in the order --, then the rule itself, rt2::frame_taper_table, the code the
+// host evaluates, on one lane.  A wave whose tiles share a bin (rows of sky, of wall) adds them up before it touches the
+// LDS.  One workgroup, on the order's stream right behind rt_tile_order_kernel.
+static_assert(ORDER_BINS == rt2::TILE_ORDER_BINS, "the taper's bins are runs of the order's");
+__global__ void __launch_bounds__(1024) rt_frame_taper_kernel(const uint32_t* __restrict__ cost, uint32_t n_tiles, uint32_t max_cost,
+                                                                uint32_t cost_floor, uint32_t n_batch, uint32_t head, uint32_t waves,
+                                                                uint32_t alpha, uint32_t* __restrict__ table) {
+    __shared__ uint32_t count[rt2::TAPER_BINS];
+    __shared__ unsigned long long weight[rt2::TAPER_BINS];
+    const uint32_t tid = threadIdx.x;
+    if (tid < rt2::TAPER_BINS) {
+        count[tid] = 0u;
+        weight[tid] = 0ull;
+    }
+    __syncthreads();
+    for (uint32_t base = 0; base < n_tiles; base += 1024u) {  // (base + 1024 <= 2^32: the host's tile capacity)
+        const uint32_t t = base + tid;
+        const bool have = t < n_tiles;
+        const uint32_t c = have ? cost[t] : 0u;
+        const uint32_t bin = have ? rt2::frame_taper_bin(c, max_cost) : 0xffffffffu;
+        unsigned long long w = have ? rt2::frame_taper_effective(c, cost_floor) : 0u;
+        const uint32_t bin0 = __builtin_amdgcn_readfirstlane(bin);
+        if (__all(bin == bin0)) {
+            if (bin0 != 0xffffffffu) {
+                for (uint32_t d = 32; d >= 1; d >>= 1) w += __shfl_xor(w, d);
+                if ((tid & 63u) == 0u) {
+                    atomicAdd(&count[bin0], 64u);
+                    atomicAdd(&weight[bin0], w);
+                }
+            }
+        } else if (have) {
+            atomicAdd(&count[bin], 1u);
+            atomicAdd(&weight[bin], w);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) rt2::frame_taper_table(count, weight, rt2::TAPER_BINS, n_batch, head, waves, alpha, table);
+}
+
+hipError_t launch_frame_taper(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor, uint32_t n_batch,
+                              uint32_t head, uint32_t waves, uint32_t alpha, uint32_t* table, hipStream_t stream) {
+    hipLaunchKernelGGL(rt_frame_taper_kernel, dim3(1), dim3(1024), 0, stream, cost, n_tiles, max_cost, cost_floor, n_batch, head, waves,
+                       alpha, table);
     return hipGetLastError();
 }
 

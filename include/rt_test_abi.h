@@ -142,6 +142,8 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
  *   FRAME_GROUP {frames of the batch, tiles of the launch, resident waves, tile-major order, rounds planned,
  *                scene in global memory or many-mesh}
  *               -> {frames per work item, the compile-time cap RT_FRAME_GROUP}
+ *   FRAME_GROUP_TAPERED the same inputs: the head of a launch that carries a taper table (frame_group_tapered_for)
+ *               -> {frames per work item, the cap RT_FRAME_GROUP_TAPERED | the item floor RT_FRAME_GROUP_FLOOR_TAPERED << 16}
  *   FRAME_TAPER {frames of the batch, head group size G, resident waves, the order's max_cost, the cost floor, tiles,
  *                the address of a u32 array: the tiles' costs, then RT_TEST_TAPER_WORDS words that receive the table,
  *                alpha (0: the shipped constant)}
@@ -154,11 +156,13 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
 #define RT_TEST_RULE_GRID 5
 #define RT_TEST_RULE_FRAME_GROUP 6
 #define RT_TEST_RULE_FRAME_TAPER 7
+#define RT_TEST_RULE_FRAME_GROUP_TAPERED 8
 #define RT_TEST_TAPER_WORDS 28 /* {segments, items, frames of the batch, G}, then {first rank, group size, first item} x 8 */
 int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
 
 /* The frame groups of a handle's batches (RenderArgs::frame_group: the frames of a pixel that one lane renders back to
- * back).  force >= 0 sets the group size of the handle's later batches, 0 = the rule decides (frame_group_for); a
+ * back).  force >= 0 sets the group size of the handle's later batches, with or without a taper table, 0 = the rules
+ * decide (frame_group_for, and frame_group_tapered_for for a launch that carries a table); a
  * frame-major order, a deferred-walk sequence and a library built with -DRT_FRAME_GROUP=1 still render with 1.
  * force < 0 changes nothing.  last_out (may be NULL): the group size of the handle's last launch. */
 int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out);

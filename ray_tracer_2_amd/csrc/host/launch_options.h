@@ -178,21 +178,48 @@ inline uint32_t equal_batch(uint32_t n_frames, uint32_t cap) {
 // pixels taken, a shorter longest item).  -DRT_FRAME_GROUP=1 compiles the groups out of the kernels.
 // The taper (frame_taper_table, below) cuts that tail where it arises: the tiles pulled while little work is left behind
 // them get groups of G / 2, G / 4, ... 1 frames, so the launch ends on items of one frame and G prices the head alone.
+// A launch that carries a taper table therefore takes its head from the same rule under a cap and a floor of its own,
+// FRAME_GROUP_CAP_TAPERED and FRAME_GROUP_MIN_ITEMS_PER_WAVE_TAPERED (frame_group_tapered_for): a whole batch and 6 items
+// per resident wave.  Config 2 under the taper, ms per frame by the head: 64 per launch 0.8641 / 0.8558 / 0.8486 / 0.8448 /
+// 0.8433 / 0.8427 with heads of 8 / 11 / 16 / 22 / 32 / 64; 20 per launch 0.8908 / 0.8799 / 0.8717 / 0.8685 with 5 / 7 / 10 / 20
+// (profiles/frame_head_ab.txt; the taper's alpha stays 4: 2 and 8 are slower under every head).  So the whole frame's
+// batches start from items of a whole batch -- 64 at 64 frames per launch, 20 at 20: its 32,400 tiles alone are 6.3 items
+// per resident wave --, and a strip share of eight ranks from groups of 8 at 64 frames per launch and of 3 at its 28.
+// A launch without a table -- the first launch of a shape, another batch size, no tile order yet, option tile_feedback
+// off -- keeps the cap and the floor above (8 / 5 / 2 / 1 for the same four launches): untapered, groups of 16 are slower
+// than groups of 8, so a long head never runs without its table (rt_api.hip: tile_feedback decides).
 #ifndef RT_FRAME_GROUP
 #define RT_FRAME_GROUP 8
 #endif
 #ifndef RT_FRAME_GROUP_FLOOR  // (the item floor, for tools/build_variant.sh: profiles/frame_taper_ab.txt section 6)
 #define RT_FRAME_GROUP_FLOOR 24
 #endif
+#ifndef RT_FRAME_GROUP_TAPERED  // (the cap and the floor of a launch with a taper table, for tools/build_variant.sh)
+#define RT_FRAME_GROUP_TAPERED 64
+#endif
+#ifndef RT_FRAME_GROUP_FLOOR_TAPERED
+#define RT_FRAME_GROUP_FLOOR_TAPERED 6
+#endif
 constexpr uint32_t FRAME_GROUP_CAP = RT_FRAME_GROUP, FRAME_GROUP_MIN_ITEMS_PER_WAVE = RT_FRAME_GROUP_FLOOR;
+// (-DRT_FRAME_GROUP=1 compiles the groups out: no head either)
+constexpr uint32_t FRAME_GROUP_CAP_TAPERED = FRAME_GROUP_CAP > 1u ? RT_FRAME_GROUP_TAPERED : 1u,
+                   FRAME_GROUP_MIN_ITEMS_PER_WAVE_TAPERED = RT_FRAME_GROUP_FLOOR_TAPERED;
 static_assert(FRAME_GROUP_CAP >= 1 && FRAME_GROUP_CAP <= MAX_BATCH_FRAMES, "RT_FRAME_GROUP: 1 .. 64");
+// (a head is at most a batch: the kernels' fields hold MAX_BATCH_FRAMES -- rt_kernel.hip asserts them beside the fields)
+static_assert(FRAME_GROUP_CAP_TAPERED >= 1 && FRAME_GROUP_CAP_TAPERED <= MAX_BATCH_FRAMES, "RT_FRAME_GROUP_TAPERED: 1 .. 64");
 inline uint32_t frame_group_for(uint32_t n_batch, uint64_t tiles, uint32_t resident_waves, bool tile_major, bool rounds,
-                                bool costly = false) {
+                                bool costly = false, uint32_t cap = FRAME_GROUP_CAP, uint32_t floor = FRAME_GROUP_MIN_ITEMS_PER_WAVE) {
     if (n_batch < 2u || !tile_major || rounds || costly) return 1u;
-    uint32_t g = std::min(FRAME_GROUP_CAP, n_batch);
-    while (g > 1u && tiles * ((n_batch + g - 1u) / g) < (uint64_t)resident_waves * FRAME_GROUP_MIN_ITEMS_PER_WAVE) g -= 1u;
+    uint32_t g = std::max(std::min(cap, n_batch), 1u);
+    while (g > 1u && tiles * ((n_batch + g - 1u) / g) < (uint64_t)resident_waves * floor) g -= 1u;
     const uint32_t groups = (n_batch + g - 1u) / g;
     return (n_batch + groups - 1u) / groups;
+}
+// ... and the head of a launch that carries a taper table: the same rule under the tapered cap and floor
+inline uint32_t frame_group_tapered_for(uint32_t n_batch, uint64_t tiles, uint32_t resident_waves, bool tile_major, bool rounds,
+                                        bool costly = false) {
+    return frame_group_for(n_batch, tiles, resident_waves, tile_major, rounds, costly, FRAME_GROUP_CAP_TAPERED,
+                           FRAME_GROUP_MIN_ITEMS_PER_WAVE_TAPERED);
 }
 
 // The taper of a grouped launch (RenderArgs::frame_taper): the tile order, heaviest first, is cut into at most

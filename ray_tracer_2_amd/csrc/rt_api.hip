@@ -1031,6 +1031,7 @@ struct LaunchPlan {
     bool took_idle_path = false; // this frame would have been pipelined, found nothing in flight and takes the plain launch
     bool wrote_tables = false;   // this launch rewrites a table later launches read (tile order, tile costs, primary table)
     uint32_t n_tiles = 0;
+    uint32_t tapered_head = 0;   // the frame group this launch takes if it carries a taper table (frame_groups; 0, 1: none)
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;  // the launch's (start, stop) events
 };
 
@@ -1185,18 +1186,24 @@ static void vote_thresholds(const rt_handle* h, RenderArgs& a, const LaunchPlan&
 }
 
 // Frames of a batch per work item (RenderArgs::frame_group): rt2::frame_group_for, for every launch that has a batch --
-// rt_render_frames, its strips, the frames rendered ahead.
-static void frame_groups(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
+// rt_render_frames, its strips, the frames rendered ahead.  This is the size of a launch without a taper table;
+// pl.tapered_head is the longer head (rt2::frame_group_tapered_for) that tile_feedback gives the launch once it knows
+// that the launch carries a table written for that head.
+static void frame_groups(rt_handle* h, RenderArgs& a, LaunchPlan& pl) {
     // (`costly` as for the vote; the one-wave-per-tile kernel and a launch without samples take no groups either)
     const bool tile_major = a.batch_tile_major != 0u;
     const bool costly = a.lds_scene == 0u || a.many_mesh != 0u || a.kernel_variant != 0u || a.params.rays_per_pixel <= 0;
     uint32_t g = rt2::frame_group_for(pl.n_batch, (uint64_t)a.tiles_x * a.tiles_y, a.persistent_blocks * WAVES_PER_BLOCK, tile_major, pl.rounds,
                                       costly);
-    // (a forced size -- the test library's -- stands in for the cap and the item floor only)
+    uint32_t head = RT_FRAME_TAPER != 0 ? rt2::frame_group_tapered_for(pl.n_batch, (uint64_t)a.tiles_x * a.tiles_y,
+                                                                       a.persistent_blocks * WAVES_PER_BLOCK, tile_major, pl.rounds, costly)
+                                        : 0u;
+    // (a forced size -- the test library's -- stands in for the caps and the item floors only)
     if (h->frame_group_forced != 0u && rt2::FRAME_GROUP_CAP > 1u &&
         rt2::frame_group_for(pl.n_batch, ~0ull, 1u, tile_major, pl.rounds, costly) > 1u)
-        g = std::min(h->frame_group_forced, pl.n_batch);
+        g = head = std::min(h->frame_group_forced, pl.n_batch);
     a.frame_group = h->last_frame_group = g;
+    pl.tapered_head = head;
 }
 
 // Pipelined single frames: a plain one-frame launch (no batch, no sequence of launches).
@@ -1419,13 +1426,13 @@ static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, L
         // ... and, for a grouped launch, the taper of that order from the same costs (rt2::frame_taper_table).  Segments
         // that a complete primary table serves are counted as rays and cost next to nothing: the floor takes them out.
         h->taper_head = 0;
-        if (RT_FRAME_TAPER != 0 && a.frame_group > 1u && h->frame_taper) {
+        if (RT_FRAME_TAPER != 0 && pl.tapered_head > 1u && h->frame_taper) {
             const long long served = a.primary_complete != 0u ? 64ll * params->rays_per_pixel : 0ll;
             HIP_TRY(h, launch_frame_taper(h->tile_cost[h->cost_slot], n_tiles, max_cost, served > 0xffffffffll ? 0xffffffffu : (uint32_t)served,
-                                          pl.n_batch, a.frame_group, a.persistent_blocks * WAVES_PER_BLOCK, rt2::FRAME_TAPER_ALPHA,
+                                          pl.n_batch, pl.tapered_head, a.persistent_blocks * WAVES_PER_BLOCK, rt2::FRAME_TAPER_ALPHA,
                                           h->frame_taper, pl.S));
             h->taper_batch = pl.n_batch;
-            h->taper_head = a.frame_group;
+            h->taper_head = pl.tapered_head;
         }
         h->have_order = true;
         h->order_age = 0;
@@ -1433,8 +1440,13 @@ static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, L
     }
     const uint32_t frames_now = pl.n_batch ? pl.n_batch : 1u;
     if (h->have_order) a.tile_order = h->tile_order;
-    // (the table of another batch size or group size, or no order yet: the launch runs untapered)
-    if (h->have_order && a.frame_group > 1u && h->taper_head == a.frame_group && h->taper_batch == pl.n_batch) a.frame_taper = h->frame_taper;
+    // The launch takes the tapered head exactly when it carries the table written for this batch size and that head --
+    // held from an earlier refresh, or written just above.  (The table of another batch size or head, or no order yet:
+    // the launch runs untapered, in the groups frame_groups gave it.)
+    if (h->have_order && pl.tapered_head > 1u && h->taper_head == pl.tapered_head && h->taper_batch == pl.n_batch) {
+        a.frame_group = h->last_frame_group = pl.tapered_head;
+        a.frame_taper = h->frame_taper;
+    }
     if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->opt.tile_feedback_period) {
         h->cost_slot ^= 1;
         a.tile_cost = h->tile_cost[h->cost_slot];
@@ -2756,6 +2768,10 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
             a = rt2::frame_group_for((uint32_t)in[0], (uint64_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0, in[5] != 0);
             b = rt2::FRAME_GROUP_CAP;
             break;
+        case RT_TEST_RULE_FRAME_GROUP_TAPERED:
+            a = rt2::frame_group_tapered_for((uint32_t)in[0], (uint64_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0, in[5] != 0);
+            b = rt2::FRAME_GROUP_CAP_TAPERED | rt2::FRAME_GROUP_MIN_ITEMS_PER_WAVE_TAPERED << 16;
+            break;
         case RT_TEST_RULE_FRAME_TAPER: {
             static_assert(RT_TEST_TAPER_WORDS == rt2::TAPER_WORDS, "include/rt_test_abi.h: the taper table");
             // (in[6]: the address of n_tiles costs followed by room for the table)
@@ -2778,7 +2794,8 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
 }
 
 // Test-only: the frame groups of handle `h` (RenderArgs::frame_group).  force >= 0 sets the group size of its later batches
-// (0: rt2::frame_group_for decides; an order or a launch sequence that takes no groups still gets 1, as does a library
+// (0: rt2::frame_group_for decides, and rt2::frame_group_tapered_for for a launch that carries a taper table; an order or a
+// launch sequence that takes no groups still gets 1, as does a library
 // built with -DRT_FRAME_GROUP=1); last_out: the group size of the handle's last launch.
 int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out) {
     if (!h || force > (int)RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "frame group: -1 (leave), 0 (the rule), 1..64");

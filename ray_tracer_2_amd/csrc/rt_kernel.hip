@@ -1535,6 +1535,12 @@ struct PixelState {
 template <bool GROUPS>
 DEV uint32_t meta_batch_frame(uint32_t meta) { return GROUPS ? (meta >> 19) & 63u : meta >> 19; }
 constexpr uint32_t META_FRAMES_LEFT_SHIFT = 25, META_NEXT_FRAME = (1u << 19) - (1u << META_FRAMES_LEFT_SHIFT);
+// (the fields hold the longest head a rule can ask for, a whole batch: its last frame's index in bits 19-24, and the frames
+// behind a group's first one, a head less one, in the bits from 25 up)
+static_assert(RT_MAX_BATCH_FRAMES - 1u < (1u << (META_FRAMES_LEFT_SHIFT - 19u)), "PixelState::meta: the batch frame, bits 19-24");
+static_assert(RT_MAX_BATCH_FRAMES - 1u < (1u << (32u - META_FRAMES_LEFT_SHIFT)), "PixelState::meta: the frames left, from bit 25");
+static_assert(rt2::FRAME_GROUP_CAP <= RT_MAX_BATCH_FRAMES && rt2::FRAME_GROUP_CAP_TAPERED <= RT_MAX_BATCH_FRAMES,
+              "a frame group, tapered head or not, is at most a batch");
 
 // wgsl:479-482: the pixel's focus point
 template <class A>
@@ -1622,6 +1628,8 @@ enum : uint32_t { MEMO_HIT = 1u, MEMO_BACKFACE = 2u, MEMO_RAY = 4u, MEMO_HIT_VAL
 typedef const __attribute__((address_space(4))) RenderArgs ColdArgs;
 typedef const __attribute__((address_space(4))) uint32_t ColdWord;  // (a table that no kernel of the launch writes: scalar loads)
 constexpr uint32_t POOL_GROUP_SHIFT = 8;  // pool_frame of a grouped kernel: the item's first frame | its group length << 8
+static_assert(RT_MAX_BATCH_FRAMES <= (1u << POOL_GROUP_SHIFT) && RT_MAX_BATCH_FRAMES < (1u << (32u - POOL_GROUP_SHIFT)),
+              "pool_frame: a first frame below the shift, a group length (a head of up to a whole batch) above it");
 DEV ColdArgs& cold_args() {
     ColdArgs* p = (ColdArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));

@@ -603,6 +603,62 @@ enum { RT_RADIANCE_HOST_MEMORY = 1 };
 int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* rays, uint64_t n,
                      float* rgba32f_out /* [n][4] */, int flags);
 
+/* G-buffer-guided denoising of a rendered frame: the edge-avoiding a-trous filter of Dammertz et
+ * al. 2010 with its three edge terms in one exponent, guided by the planes rt_render_gbuffer writes.  The frame is
+ * width x height, row 0 = bottom, every plane tightly packed as the G-buffer's.  In binary32, unfused, in this order:
+ *   k_c = 1 / (sigma_color * sigma_color) (+INF gives 0), k_n and k_x likewise from sigma_normal and sigma_point;
+ *   pass i of `iterations` has step s = 2^i and k_c,i = k_c * 4^i (sigma_color halves per pass).
+ *   Texel p is FILTERABLE when some component of normal(p) is non-zero, every component of normal(p), point(p) and
+ *   color(p).rgb is finite, and emission is NULL or emission(p).rgb are all zero.  Every other texel (a miss, a lamp, a
+ *   non-finite sample) copies color(p) to out(p) bit for bit and is never a tap.
+ *   a'(p) = albedo(p) > 2^-10 ? albedo(p) : 2^-10 per component (1 with a NULL albedo);  c_0(p) = color(p).rgb / a'(p).
+ *   Pass i, for filterable p: over dy = -2..2 (outer), dx = -2..2 (inner), q = p + s (dx, dy) inside the frame and
+ *   filterable, with d2(a) = ((a0 a0 + a1 a1) + a2 a2) of the componentwise difference of the values at p and q:
+ *       e = (d2(c_i) k_c,i + d2(normal) k_n) + d2(point) k_x,   w = (h[dx] h[dy]) exp_(-e),  h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *       (exp_: csrc/rt_transc.h); a tap with w > 0 adds w c_i(q) to sum and w to wsum;   c_{i+1}(p) = sum / wsum.
+ *   out(p).rgb = c_n(p) a'(p), out(p).a = color(p).a.
+ *   The centre tap has e = 0 and adds 9/64, so wsum > 0 -- unless a finite colour overflows in the division by a' (3e38 /
+ *   0.5): then c_0(p) is infinite, the centre difference is inf - inf = NaN, every tap of p is skipped and out(p).rgb is
+ *   the NaN of 0 / 0.  Such a texel is still filterable by the rule above; a host that may hold colours near FLT_MAX over
+ *   albedos below 1 clamps them first.
+ * sigma_color is in units of demodulated radiance (colour divided by albedo), sigma_point in world units, sigma_normal in
+ * units of the difference of two unit normals (0 .. 2).
+ * rt_denoise_host (section 3) is this definition over host pointers, without a device; rt_denoise computes the same bits
+ * on the device.  Without RT_DENOISE_HOST_MEMORY the planes are device pointers on the handle's device (4-byte aligned;
+ * 16 for color, albedo, emission and out), `color` may be NULL for the handle's current image (rt_device_image or a
+ * bound image; width * height texels of it), `out` may be `color` or that image, and the call is asynchronous on the
+ * handle's stream, after every earlier call on the handle and before every later one.  With it they are host pointers,
+ * staged WHOLE through one temporary device buffer -- 40 to 72 bytes per texel, 149 MB for 1920 x 1080 with every plane:
+ * the one host-memory call that does not keep to chunks of 64 MB, because a pass reads up to 256 rows away and the frame
+ * cannot be cut into bands -- counted against option "max_device_mb" while held, and the call returns when `out` is on
+ * the host.  `out` may be the same pointer as `color`; any other overlap is undefined.
+ * The handle keeps 64 bytes of scratch per texel (a packed guide record and two colour images), allocated on first use,
+ * grown on demand, counted by rt_last_launch out[4] and bounded by option "max_device_mb" (RT_ERR_OUT_OF_MEMORY).
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle / desc / normal / point / out, null color on the host or
+ * with the flag, struct_bytes != sizeof(rt_denoise_desc), _p0 != 0, unknown flags, zero width or height, iterations
+ * outside 1 .. 8, a sigma that is NaN or <= 0, an infinite sigma_normal or sigma_point, misaligned device planes),
+ * RT_ERR_CAPACITY (width * height > 2^31 - 1, or more texels than the image has with a NULL color),
+ * RT_ERR_OUT_OF_MEMORY.  No scene is needed.
+ * Like the ray queries the call leaves the image (unless `out` is the image), the primary tables, a frame_ahead batch
+ * in flight, the pipeline slots, rt_get_stats and the launch words of rt_last_launch as they are. */
+typedef struct rt_denoise_desc {
+    uint32_t     struct_bytes;  /* = sizeof(rt_denoise_desc) */
+    uint32_t     _p0;           /* must be 0 */
+    uint32_t     width, height;
+    uint32_t     iterations;    /* n: 1 .. 8 passes, steps 1, 2, .. 2^(n-1) */
+    float        sigma_color;   /* > 0, may be +INF (no colour term) */
+    float        sigma_normal;  /* > 0, finite */
+    float        sigma_point;   /* > 0, finite */
+    const float* color;         /* [h][w][4] */
+    const float* normal;        /* [h][w][3] */
+    const float* point;         /* [h][w][3] */
+    const float* albedo;        /* [h][w][4] or NULL */
+    const float* emission;      /* [h][w][4] or NULL */
+    float*       out;           /* [h][w][4] */
+} rt_denoise_desc;
+enum { RT_DENOISE_HOST_MEMORY = 1 };
+int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags);
+
 /* The test-only entry points (rt_test_*: the kernels' arithmetic building blocks evaluated element-wise on the device, raw
  * copies of sequence buffers, the RCCL gather against a stub, the frame_ahead policy) are NOT exported by the product
  * library: include/rt_test_abi.h declares them and ray_tracer_2_amd/librt2_mi355x_test.so -- the same sources compiled
@@ -733,6 +789,12 @@ int rt_scene_subdivide_meshes(rt_scene* s, uint32_t n);
 /* ≙ the pixel loop of save_render_to_file (app.rs:408-460): gamma 1/2.2,
  * clamp, truncating u8, net vertical flip.  out: width*height*4 bytes. */
 int rt_export_rgba8(const float* rgba32f, uint32_t width, uint32_t height, uint8_t* out);
+
+/* The denoiser's definition (section 2: rt_denoise) in executable form: plain C++ over host pointers, no device.  `color`
+ * is required; `out` may be `color`.  The same argument errors as rt_denoise (no handle, no flags, no alignment rule),
+ * nothing written on an error, the reason in rt_last_error(NULL); RT_ERR_OUT_OF_MEMORY when the host has no room for the
+ * 64 bytes per texel of working memory. */
+int rt_denoise_host(const rt_denoise_desc* desc);
 
 #ifdef __cplusplus
 }

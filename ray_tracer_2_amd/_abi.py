@@ -105,6 +105,18 @@ GBUFFER_CHANNELS = {"depth": ("<f4", 0), "dir": ("<f4", 3), "point": ("<f4", 3),
                     "primitive": ("<u4", 0), "flags": ("u1", 0)}
 GBUFFER_HOST_MEMORY = 1
 
+
+class DenoiseDesc(C.Structure):  # rt_denoise_desc: a frame and its guides for rt_denoise / rt_denoise_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("iterations", u32),
+                ("sigma_color", f32), ("sigma_normal", f32), ("sigma_point", f32), ("color", C.c_void_p),
+                ("normal", C.c_void_p), ("point", C.c_void_p), ("albedo", C.c_void_p), ("emission", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
+# plane of rt_denoise_desc -> components per texel
+DENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission": 4, "out": 4}
+DENOISE_HOST_MEMORY = 1
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():

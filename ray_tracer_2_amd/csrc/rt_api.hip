@@ -22,6 +22,7 @@
 #include "host/scene_pack.h"  // (the host packer: scene arrays -> blob)
 #include "rt_device.h"
 #include "rt_refit.h"
+#include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0
@@ -63,6 +64,7 @@ hipError_t launch_test_shade(const RenderArgs& a, int which, const uint32_t* cas
 #endif
 hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
+hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -182,6 +184,9 @@ struct rt_handle {
     // stream of its own while the handle's stream renders the next frames
     float4* snapshot = nullptr;
     size_t snapshot_capacity = 0, snapshot_bytes = 0;  // bytes allocated / bytes of the last snapshot
+    // rt_denoise: per texel a guide record of two float4 and two colour images of one float4 each (64 B), kept between calls
+    float4* denoise_scratch = nullptr;
+    size_t denoise_texels = 0;
     hipStream_t copy_stream = nullptr;
     hipEvent_t snapshot_taken = nullptr, snapshot_read = nullptr;
     bool snapshot_read_pending = false;                // a read of the staging buffer was queued since the last snapshot
@@ -293,7 +298,8 @@ int fail(rt_handle* h, int code, const std::string& msg) {
 // bytes of device memory the handle holds on its own initiative (what option "max_device_mb" bounds)
 size_t optional_bytes(const rt_handle* h) {
     size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary.texels * 64u +
-               2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity;
+               2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity +
+               h->denoise_texels * 64u;
     for (const PipeSlot& ps : h->pipe) {
         if (ps.scratch) b += h->pipe_scratch_texels * sizeof(float4);
         b += ps.memo_words * sizeof(uint32_t) + ps.primary.texels * 64u;
@@ -508,6 +514,7 @@ void rt_destroy(rt_handle* h) {
     if (h->snapshot_taken) (void)hipEventDestroy(h->snapshot_taken);
     if (h->snapshot_read) (void)hipEventDestroy(h->snapshot_read);
     free_dev(h->snapshot);
+    free_dev(h->denoise_scratch);
     free_dev(h->wf_state);
     free_dev(h->wf_hit);
     free_dev(h->wf_lists);
@@ -2271,6 +2278,94 @@ int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* r
         if (what = "launch_radiance", (e = launch_radiance(a, buf, (uint32_t)m, d_out, next_ray, h->compute_units, h->stream)) != hipSuccess) return e;
         what = "hipMemcpyAsync";
         return hipMemcpyAsync(rgba32f_out + 4 * i0, d_out, m * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
+    });
+}
+
+// ---- denoising a rendered frame (include/rt_abi.h: rt_denoise, rt_denoise_host; rt_denoise.hip; host/denoise.cpp) ----
+// Launched like a query: nothing read but the caller's planes (or the image) and nothing written but `out` and the
+// handle's denoise scratch.
+int rt_denoise_host(const rt_denoise_desc* desc) {
+    try {
+        std::string err;
+        const int rc = rt2::denoise_host(desc, err);
+        return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+    } catch (const std::bad_alloc&) {
+        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+    }
+}
+
+int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_DENOISE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_DENOISE_HOST_MEMORY) != 0;
+    {
+        std::string err;
+        if (const int rc = rt2::denoise_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    }
+    const size_t texels = (size_t)desc->width * desc->height;
+    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // the scratch: grown on demand, within option max_device_mb
+    const size_t staging = host ? texels * (size_t)(16 + 12 + 12 + (desc->albedo ? 16 : 0) + (desc->emission ? 16 : 0)) + 5u * 256u : 0u;
+    if (h->denoise_texels < texels) {
+        if (!fits_cap(h, texels * 64u + staging, h->denoise_texels * 64u))
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's scratch images");
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
+        free_dev(h->denoise_scratch);
+        h->denoise_texels = 0;
+        const hipError_t e = hipMalloc((void**)&h->denoise_scratch, texels * 64u);
+        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the denoiser's scratch images");
+        HIP_TRY(h, e);
+        h->denoise_texels = texels;
+    } else if (!fits_cap(h, staging)) {
+        return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's staging planes");
+    }
+    DenoiseArgs a{};
+    a.width = desc->width;
+    a.height = desc->height;
+    a.iterations = (int)desc->iterations;
+    a.sigma_color = desc->sigma_color;
+    a.sigma_normal = desc->sigma_normal;
+    a.sigma_point = desc->sigma_point;
+    a.guide = h->denoise_scratch;
+    a.ping[0] = h->denoise_scratch + 2 * texels;
+    a.ping[1] = h->denoise_scratch + 3 * texels;
+    if (!host) {
+        const float* image = reinterpret_cast<const float*>(h->image);
+        a.color = desc->color ? desc->color : image;
+        a.normal = desc->normal; a.point = desc->point; a.albedo = desc->albedo; a.emission = desc->emission; a.out = desc->out;
+        if (a.color == image || (desc->out >= image && desc->out < image + 4 * h->image_texels)) {
+            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+        }
+        if (desc->out >= image && desc->out < image + 4 * h->image_texels) h->generation += 1;   // (the image changes, as by rt_write_image)
+        HIP_TRY(h, launch_denoise(a, h->stream));
+        return RT_OK;
+    }
+    // host memory: the whole frame through one temporary device buffer (a pass reads up to 256 rows away: no bands);
+    // each plane's part of it starts at a multiple of 256 bytes, and `out` takes the colour plane's place
+    const void* const src[5] = {desc->color, desc->normal, desc->point, desc->albedo, desc->emission};
+    static const uint32_t bytes[5] = {16, 12, 12, 16, 16};
+    size_t plane_off[5] = {}, off = 0;
+    for (int c = 0; c < 5; ++c) {
+        if (!src[c]) continue;
+        plane_off[c] = off;
+        off = (off + texels * bytes[c] + 255u) & ~(size_t)255u;
+    }
+    return staged_chunks(h, off, 1, 1, "the denoiser's staging planes", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
+        hipError_t e = hipSuccess;
+        what = "hipMemcpyAsync";
+        const float* d_ptr[5] = {};
+        for (int c = 0; c < 5 && e == hipSuccess; ++c) {
+            if (!src[c]) continue;
+            d_ptr[c] = reinterpret_cast<const float*>(buf + plane_off[c]);
+            e = hipMemcpyAsync(buf + plane_off[c], src[c], texels * bytes[c], hipMemcpyHostToDevice, h->stream);
+        }
+        if (e != hipSuccess) return e;
+        a.color = d_ptr[0]; a.normal = d_ptr[1]; a.point = d_ptr[2]; a.albedo = d_ptr[3]; a.emission = d_ptr[4];
+        a.out = reinterpret_cast<float*>(buf + plane_off[0]);
+        if (what = "launch_denoise", (e = launch_denoise(a, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        return hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream);
     });
 }
 

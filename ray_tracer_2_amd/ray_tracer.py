@@ -18,6 +18,57 @@ from . import _abi as A
 from .lib import RtError, load
 from .scene import Scene, SceneArrays
 
+# The denoiser's default widths (RayTracer.denoise, denoise_host): sigma_color in demodulated radiance (colour / albedo) --
+# wide, because the fireflies of a few samples per pixel are many units away from their neighbours, and halved per pass --,
+# sigma_normal in units of the difference of two unit normals, sigma_point in world units (the Cornell box is 2 across).
+DENOISE_SIGMA_COLOR, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_POINT = 4.0, 0.3, 1.0
+
+
+def _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point):
+    return A.DenoiseDesc(struct_bytes=C.sizeof(A.DenoiseDesc), width=W, height=H, iterations=int(iterations),
+                         sigma_color=float(sigma_color), sigma_normal=float(sigma_normal), sigma_point=float(sigma_point))
+
+
+def _denoise_numpy_planes(d, W, H, planes, color):
+    """Points the desc's input planes at contiguous float32 copies (or the arrays themselves); returns what must stay alive."""
+    keep = {}
+    for k, v in dict(planes, color=color).items():
+        a = np.ascontiguousarray(v, np.float32)
+        if a.shape != (H, W, A.DENOISE_PLANES[k]):
+            raise ValueError(f"plane {k} must have shape {(H, W, A.DENOISE_PLANES[k])}, not {a.shape}")
+        keep[k] = a
+        setattr(d, k, a.ctypes.data)
+    return keep
+
+
+def _denoise_numpy_out(d, W, H, out):
+    if out is None:
+        out = np.zeros((H, W, 4), np.float32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == (H, W, 4) and out.flags.c_contiguous
+              and out.flags.writeable):
+        raise ValueError(f"out must be a writeable contiguous float32 array of shape {(H, W, 4)}")
+    d.out = out.ctypes.data
+    return out
+
+
+def denoise_host(guides, color, iterations=3, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+                 sigma_point=DENOISE_SIGMA_POINT, out=None):
+    """rt_denoise_host: the denoiser's definition on the CPU (no device), with RayTracer.denoise's arguments for numpy
+    planes.  RayTracer.denoise computes the same bits on the GPU."""
+    planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
+    if "normal" not in planes or "point" not in planes:
+        raise ValueError("guides must hold the normal and point planes of render_gbuffer")
+    H, W = (int(v) for v in np.shape(planes["normal"])[:2])
+    d = _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point)
+    keep = _denoise_numpy_planes(d, W, H, planes, color)
+    res = _denoise_numpy_out(d, W, H, out)
+    L = load()
+    rc = L.rt_denoise_host(C.byref(d))
+    del keep
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+    return res
+
 
 class RayTracer:
     def __init__(self, device=0, max_width=1920, max_height=1080, lib=None):
@@ -370,6 +421,52 @@ class RayTracer:
         ext.wait_stream(cur)
         self._check(self._L.rt_render_gbuffer(self._h, C.byref(params), C.byref(g), 0))
         cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launch: _device_query)
+        return out
+
+    def denoise(self, guides, color=None, iterations=3, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+                sigma_point=DENOISE_SIGMA_POINT, out=None):
+        """The G-buffer-guided a-trous filter (rt_denoise; include/rt_abi.h has the definition) of the (H, W, 4) float32
+        frame `color`.  `guides`: the dict render_gbuffer returns for the same frame; it must hold `normal` and `point`,
+        and `albedo` (demodulation) and `emission` (lamps are left alone) are used when present.  `iterations`: 1 .. 8
+        passes with steps 1, 2, 4, ...  The sigmas' units: `sigma_color` demodulated radiance (colour / albedo; halved
+        per pass, inf switches the term off), `sigma_normal` the length of the difference of two unit normals,
+        `sigma_point` world units (scale it with the scene).
+        numpy planes: a synchronous call that returns a numpy array (`out`, when given: it may be `color`).  Torch tensors
+        on this handle's device: an asynchronous call ordered after the current torch stream's work, as
+        render_gbuffer(device=True) orders itself; returns a tensor; there color=None denoises the handle's image, into
+        `out` or a new tensor."""
+        planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
+        if "normal" not in planes or "point" not in planes:
+            raise ValueError("guides must hold the normal and point planes of render_gbuffer")
+        H, W = (int(v) for v in planes["normal"].shape[:2])
+        d = _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point)
+        if not any(hasattr(v, "data_ptr") for v in (*planes.values(), color, out)):
+            if color is None:
+                raise ValueError("color is required with numpy planes (color=None names the device image)")
+            keep = _denoise_numpy_planes(d, W, H, planes, color)
+            res = _denoise_numpy_out(d, W, H, out)
+            self._check(self._L.rt_denoise(self._h, C.byref(d), A.DENOISE_HOST_MEMORY))
+            del keep
+            return res
+        import torch
+        given = dict(planes, **({"color": color} if color is not None else {}), **({"out": out} if out is not None else {}))
+        for k, v in given.items():
+            if not isinstance(v, torch.Tensor):
+                raise ValueError("mix of device tensors and host arrays")
+            if v.device.type != "cuda" or v.device.index != self.device:
+                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
+            if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != (H, W, A.DENOISE_PLANES[k]):
+                raise ValueError(f"plane {k} must be a contiguous float32 tensor of shape {(H, W, A.DENOISE_PLANES[k])}")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        for k, v in dict(given, out=out).items():
+            setattr(d, k, v.data_ptr())
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
+        ext.wait_stream(cur)
+        self._check(self._L.rt_denoise(self._h, C.byref(d), 0))
+        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
         return out
 
     def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):

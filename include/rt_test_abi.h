@@ -21,7 +21,8 @@ extern "C" {
  * state x, 15 f32(u32 bits x) * 2^-32, 16 normalize(x, y, x*y).x, 17 the kernels' reciprocal rcp_(x), 18 their
  * sqrt_dev(x), 19 the RNG jumps of the roulette skip for state x (bits), y (bits) selecting the value: 0 / 1 the generator's
  * output 5 steps on, by one jump / by stepping next_random_number; 2 / 3 the output 12 steps on; 4 / 5 the state 12 steps
- * on.  The second call filters one RGBA8 sRGB texture at n (u, v) pairs (wgsl:455 as csrc/rt_texture.h defines
+ * on, 20 the RNG jump of the terminal skip for state x (bits), y (bits): 0 / 1 the generator's output 8 steps on, by one
+ * jump / by stepping next_random_number; 2 / 3 the state 8 steps on.  The second call filters one RGBA8 sRGB texture at n (u, v) pairs (wgsl:455 as csrc/rt_texture.h defines
  * it).  The third compares the kernels' short reciprocal (which = 0) / square root (which = 1) with the compiler's IEEE
  * 1.0f / x / sqrt on the device for EVERY float in the range the short form serves, and the sky's three shortcuts
  * (which = 2, 3, 4: wgsl:215-218 with the branches of smoothstep / pow taken apart) with their literal forms for every
@@ -147,7 +148,11 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
  *   FRAME_TAPER {frames of the batch, head group size G, resident waves, the order's max_cost, the cost floor, tiles,
  *                the address of a u32 array: the tiles' costs, then RT_TEST_TAPER_WORDS words that receive the table,
  *                alpha (0: the shipped constant)}
- *               -> {segments of the table, the alpha used}: frame_taper_table over the costs' histogram, on the host */
+ *               -> {segments of the table, the alpha used}: frame_taper_table over the costs' histogram, on the host
+ *   TERMINAL_SKIP {the address of a packed blob (rt_test_pack_scene's), the address of its 12 layout words, its n_items,
+ *                the number of meshes, the scene is staged in LDS and walked by the few-mesh kernels, the launch takes
+ *                SIMPLE, the launch counts tests, the address of three floats that receive terminal_c (zeros when refused)}
+ *               -> {terminal_skip_ok, the mask of the dark meshes}: terminal_skip_scene and terminal_skip_for */
 #define RT_TEST_RULE_VOTES 0
 #define RT_TEST_RULE_ROUNDS 1
 #define RT_TEST_RULE_VARIANT 2
@@ -158,7 +163,15 @@ int rt_test_set_option(const char* name, int value, int32_t stored_out[2]);
 #define RT_TEST_RULE_FRAME_TAPER 7
 #define RT_TEST_RULE_FRAME_GROUP_TAPERED 8
 #define RT_TEST_TAPER_WORDS 28 /* {segments, items, frames of the batch, G}, then {first rank, group size, first item} x 8 */
+#define RT_TEST_RULE_TERMINAL_SKIP 9
 int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
+
+/* The terminal skip of a handle's render launches (RenderArgs::terminal_dark: path segments that cannot matter leave the
+ * forest walk out).  on >= 0 switches it for the handle's later launches: 1, the default, lets the rule decide
+ * (terminal_skip_for), 0 makes every launch walk everything; on < 0 changes nothing.  last_out (may be NULL), four
+ * words: the dark-mesh mask the handle's last render launch ran with (0: it skipped nothing), then the bits of its
+ * terminal_c. */
+int rt_test_terminal_skip(rt_handle* h, int on, uint32_t last_out[4]);
 
 /* The frame groups of a handle's batches (RenderArgs::frame_group: the frames of a pixel that one lane renders back to
  * back).  force >= 0 sets the group size of the handle's later batches, with or without a taper table, 0 = the rules

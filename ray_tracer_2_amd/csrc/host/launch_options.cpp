@@ -70,4 +70,52 @@ SetResult set_option(Options& opt, const char* name, int value) {
     return r;
 }
 
+TerminalScene terminal_skip_scene(const Quad* head, const rtd::SceneLayout& lay, uint32_t n_items, uint32_t n_meshes) {
+    using namespace rtd;
+    TerminalScene t;
+    if (!head || n_meshes == 0u || n_meshes > 32u) return t;
+    auto finite = [](float f) { return (as_bits(f) & 0x7f800000u) != 0x7f800000u; };
+    bool colours_finite = true;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    bool have_c = false;
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        // rt_material: color, emission_color, specular_color, absorption, (absorption_strength, emission_strength, ...)
+        const Quad* m = head + (lay.mat_off + (size_t)i * MATERIAL_BYTES) / 16u;
+        const Quad &col = m[0], &ec = m[1], &sc = m[2];
+        const volatile float es = m[4].y;  // (the product as the kernels form it: one binary32 multiplication each)
+        const volatile float ex = ec.x * es, ey = ec.y * es, ez = ec.z * es, ew = ec.w * es;
+        if ((as_bits(ex) | as_bits(ey) | as_bits(ez) | as_bits(ew)) != 0u) continue;
+        t.dark |= 1u << i;
+        const float both[2][4] = {{col.x, col.y, col.z, col.w}, {sc.x, sc.y, sc.z, sc.w}};
+        for (const float* v : {both[0], both[1]}) {
+            for (int k = 0; k < 4; ++k) colours_finite = colours_finite && finite(v[k]);
+            for (int k = 0; k < 3; ++k) c[k] = have_c && !(v[k] > c[k]) ? c[k] : v[k];
+            have_c = true;
+        }
+    }
+    // the items in the kernels' order: everything from the first lane-sparse one on has to be dark
+    bool sparse_seen = false, all_dark_behind = true;
+    for (uint32_t it = 0; it < n_items; ++it) {
+        const Quad* q = head + (lay.item_off + (size_t)it * ITEM_BYTES) / 16u;
+        const uint32_t kind = as_bits(q[0].x), ia = as_bits(q[0].y);
+        if (kind & ITEM_TLAS) return TerminalScene{0u, t.dark, {0.0f, 0.0f, 0.0f}};
+        if (kind & ITEM_FOREST) {
+            sparse_seen = true;
+            const uint32_t n = as_bits(q[0].w);
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint32_t mesh = as_bits(head[(lay.forest_off + (size_t)(ia + j) * FOREST_ENTRY_BYTES) / 16u].y);
+                all_dark_behind = all_dark_behind && mesh < n_meshes && ((t.dark >> mesh) & 1u) != 0u;
+            }
+            continue;
+        }
+        if ((kind & ITEM_FLAT2) == 0u && as_bits(q[1].z) == 0u) sparse_seen = true;  // (an internal root, walked on its own)
+        if (sparse_seen) all_dark_behind = all_dark_behind && ia < n_meshes && ((t.dark >> ia) & 1u) != 0u;
+    }
+    if (sparse_seen && all_dark_behind && colours_finite && have_c) {
+        t.ok = 1u;
+        for (int k = 0; k < 3; ++k) t.c[k] = c[k];
+    }
+    return t;
+}
+
 }  // namespace rt2

@@ -325,6 +325,35 @@ inline void frame_taper_histogram(const uint32_t* cost, uint32_t n_tiles, uint32
     }
 }
 
+// The terminal skip (csrc/rt_kernel.hip: intersect_scene's TERM; RenderArgs::terminal_dark, ::terminal_c).  A path segment
+// whose path is certain to end at its hit -- the last allowed bounce, or a roulette value that no dark material's
+// throughput can reach -- and whose closest hit so far is a dark mesh leaves the lane-sparse items of the mesh loop out:
+// the forest items and the single meshes with an internal root that is not a two-leaf one.  That is exact when everything
+// it leaves out, and everything behind it, is dark too.  A mesh is DARK when the four products emission_color *
+// emission_strength are +0 bitwise.  terminal_skip_scene reads the packed head (the items in the order the kernels visit
+// them, the forest entries, the materials) and says
+//   ok   1 iff the scene has a lane-sparse item, every mesh of the first such item and of every item behind it is dark,
+//        no item is a top-level tree, there are at most 32 meshes (the mask) and every dark material's color and
+//        specular_color components are finite;
+//   dark bit i: mesh i is dark (all of them, wherever their items are);
+//   c    the componentwise maximum of color.xyz and specular_color.xyz over the dark meshes (ok only).
+// terminal_skip_for adds the launch: the few-mesh kernels on a scene staged in LDS in their SIMPLE instantiation -- no
+// glass, no texture, no sphere, so a hit makes 8 draws --, no counters (the shader's test counts stay exact), no parking.
+// The result is the mask the launch runs with, 0: nothing is skipped.  -DRT_TERMINAL_SKIP=0 compiles the skip out.
+#ifndef RT_TERMINAL_SKIP
+#define RT_TERMINAL_SKIP 1
+#endif
+struct TerminalScene {
+    uint32_t ok = 0, dark = 0;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+};
+TerminalScene terminal_skip_scene(const Quad* head, const rtd::SceneLayout& lay, uint32_t n_items, uint32_t n_meshes);
+inline uint32_t terminal_skip_for(const TerminalScene& t, bool scene_in_lds, bool many_mesh, bool takes_simple, bool counters, bool parks,
+                                  bool enabled = true) {
+    // (an experiments build has none: its wavefront sequence keeps two pointers in the arguments' slot, RenderArgs)
+    return RT_TERMINAL_SKIP != 0 && !RT_EXPERIMENTS && enabled && t.ok != 0u && scene_in_lds && !many_mesh && takes_simple && !counters && !parks ? t.dark : 0u;
+}
+
 // workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
 inline uint32_t blocks_per_cu_for(size_t lds_bytes) {
     const uint32_t per_cu = lds_bytes ? (uint32_t)(CU_LDS_BYTES / lds_bytes) : BLOCKS_PER_CU;

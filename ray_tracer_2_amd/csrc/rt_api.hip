@@ -270,6 +270,11 @@ struct rt_handle {
     int count_tests = 0;
     uint32_t last_launch[4] = {0, 0, 0, 0};  // rt_last_launch (entries 4 and 5 are computed when asked)
     uint32_t frame_group_forced = 0, last_frame_group = 1;  // rt_test_frame_group (0: rt2::frame_group_for decides)
+    // The terminal skip (RenderArgs::terminal_dark): what rt2::terminal_skip_scene said of the head of the last upload /
+    // update / refit, the switch (rt_test_terminal_skip: the test library's) and the mask of the last render launch.
+    rt2::TerminalScene terminal;
+    bool terminal_skip_on = true;
+    uint32_t last_terminal_dark = 0;
     bool queues_noted = false;               // the note about GPU_MAX_HW_QUEUES has been left in `err` once
     std::string err;
 };
@@ -671,6 +676,7 @@ int rt_upload_scene(rt_handle* h, const rt_scene_uniform* scene, const rt_sphere
         HIP_TRY(h, hipStreamSynchronize(h->stream));  // host staging vectors die here
         h->geom = std::move(g);
         h->inst = s;
+        h->terminal = rt2::terminal_skip_scene(head.data(), s.lay, s.n_items, n_meshes);
         commit_scene(h, scene->camera);
         h->inst_meshes.swap(inst_meshes);
         h->inst_spheres.swap(inst_spheres);
@@ -722,6 +728,7 @@ int rt_update_instances(rt_handle* h, const rt_scene_uniform* scene, const rt_sp
         if (e != hipSuccess) return drop_new_blob(h, target, fail(h, RT_ERR_DEVICE, std::string("rt_update_instances: ") + hipGetErrorString(e)));
         adopt_blob(h, target);
         h->inst = s;
+        h->terminal = rt2::terminal_skip_scene(head.data(), s.lay, s.n_items, n_meshes);  // (materials change in place)
         commit_scene(h, scene->camera);
         h->inst_meshes.swap(inst_meshes);
         h->inst_spheres.swap(inst_spheres);
@@ -884,6 +891,7 @@ int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32
         adopt_blob(h, target);
         h->geom = std::move(g2);
         h->inst = s;
+        h->terminal = rt2::terminal_skip_scene(head.data(), s.lay, s.n_items, (uint32_t)h->inst_meshes.size());
         commit_scene(h, h->camera);
         h->generation += 1;
         return done(RT_OK);
@@ -1164,6 +1172,11 @@ static int choose_kernel_shape(rt_handle* h, const rt_params* params, RenderArgs
     }
     a.fast_miss = h->opt.fast_miss != 0 && a.pixel_cache != 0u ? 1u : 0u;
     a.roulette_skip = h->opt.roulette_skip != 0 && a.pixel_cache != 0u ? 1u : 0u;
+    // the terminal skip (rt2::terminal_skip_for; a parking launch of the product reads its scene from global memory)
+    a.terminal_dark = rt2::terminal_skip_for(h->terminal, a.lds_scene != 0u, a.many_mesh != 0u, render_takes_simple(a), a.count_tests != 0u,
+                                             RT_EXPERIMENTS && h->opt.hybrid != 0, h->terminal_skip_on);
+    if (params->number_of_bounces >= (1 << 30)) a.terminal_dark = 0u;  // (the kernels borrow bit 30 of the segment number: PATH_TERMINAL)
+    for (int k = 0; k < 3; ++k) a.terminal_c[k] = a.terminal_dark != 0u ? h->terminal.c[k] : 0.0f;
     return RT_OK;
 }
 
@@ -1521,6 +1534,7 @@ static void note_launch(rt_handle* h, const rt_params* params, const RenderArgs&
     h->last_launch[2] = a.lds_scene;
     h->last_launch[3] = (a.many_mesh ? 1u : 0u) | (render_takes_simple(a) ? 2u : 0u) |
                         (a.kernel_variant == 1 ? 4u : 0u) | (pl.rounds ? 8u : 0u);
+    h->last_terminal_dark = params->debug_flag != 0 ? 0u : a.terminal_dark;
 }
 
 // Blend n frames of `texels` texels each out of `scratch` into the image, in frame order on the handle's stream:
@@ -2881,10 +2895,42 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
             a = words[n_tiles];
             break;
         }
+        case RT_TEST_RULE_TERMINAL_SKIP: {
+            // (in[0]: the address of a packed blob -- rt_test_pack_scene's --, in[1]: of its 12 layout words, in[7]: of three floats)
+            const rt2::Quad* head = (const rt2::Quad*)(uintptr_t)in[0];
+            const uint32_t* words = (const uint32_t*)(uintptr_t)in[1];
+            float* c_out = (float*)(uintptr_t)in[7];
+            if (!head || !words || !c_out || in[2] < 0 || in[3] < 0) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "terminal skip rule: a blob, its layout, room for terminal_c");
+            SceneLayout lay;
+            static_assert(sizeof(lay) == 12 * sizeof(uint32_t), "SceneLayout: 12 words");
+            memcpy(&lay, words, sizeof(lay));
+            const rt2::TerminalScene t = rt2::terminal_skip_scene(head, lay, (uint32_t)in[2], (uint32_t)in[3]);
+            a = rt2::terminal_skip_for(t, in[4] != 0, false, in[5] != 0, in[6] != 0, false);
+            b = t.dark;
+            for (int k = 0; k < 3; ++k) c_out[k] = a != 0u ? t.c[k] : 0.0f;
+            a = a != 0u ? 1u : 0u;
+            break;
+        }
         default: return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "unknown rule");
     }
     out[0] = a;
     out[1] = b;
+    return RT_OK;
+}
+
+// Test-only: the terminal skip of handle `h` (RenderArgs::terminal_dark).  on >= 0 switches it for the handle's later
+// launches (1: rt2::terminal_skip_for decides, the default; 0: no launch skips); last_out: the mask the handle's last
+// render launch ran with (0: it skipped nothing) and the bits of its terminal_c.
+int rt_test_terminal_skip(rt_handle* h, int on, uint32_t last_out[4]) {
+    if (!h) return RT_ERR_INVALID_ARGUMENT;
+    if (on >= 0) h->terminal_skip_on = on != 0;
+    if (last_out) {
+        last_out[0] = h->last_terminal_dark;
+        for (int k = 0; k < 3; ++k) {
+            const float c = h->last_terminal_dark != 0u ? h->terminal.c[k] : 0.0f;
+            memcpy(&last_out[1 + k], &c, 4);
+        }
+    }
     return RT_OK;
 }
 

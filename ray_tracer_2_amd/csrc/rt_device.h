@@ -191,8 +191,22 @@ struct RenderArgs {
     //   wf_hit:   2 planes: (closest, object code | any << 24 | sphere inside << 25, win_u, win_v) (win_tri, win_point)
     //             object code: mesh index, or 0x800000 | sphere index
     //   the primary-ray memo of a slot: pixel_cache_mem, 13 dwords per slot (pixel_cache == 3)
-    float4* wf_state;
-    float4* wf_hit;
+    // (the two planes' 16 bytes are one slot of the kernarg segment for two things that exclude each other, like q_out's:
+    // only the wavefront kernels of the experiments build read the planes, and that build has no terminal skip)
+    // Terminal skip (SIMPLE few-mesh render kernels on a scene staged in LDS; host/launch_options.h: terminal_skip_scene /
+    // terminal_skip_for; intersect_scene's TERM): bit i of terminal_dark: mesh i emits nothing; 0: the launch skips nothing
+    // (the rule refused, or the switch is off).  terminal_c: the componentwise maximum of color.xyz and specular_color.xyz
+    // over the dark meshes.
+    union {
+        struct {
+            float4* wf_state;
+            float4* wf_hit;
+        };
+        struct {
+            uint32_t terminal_dark;
+            float terminal_c[3];
+        };
+    };
     const uint32_t* wf_list_in;    // slots to shade (their hits are in wf_hit) / rays to walk
     const uint32_t* wf_count_in;
     uint32_t* wf_list_out;         // slots whose next segment needs a traversal

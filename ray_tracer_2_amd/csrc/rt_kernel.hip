@@ -203,6 +203,7 @@ constexpr LcgJump lcg_jump(uint32_t k) {
 static_assert(lcg_jump(1).a == RNG_LCG_A && lcg_jump(1).c == RNG_LCG_C, "one step is the generator's own");
 static_assert(lcg_jump(4).a == 2200120369u && lcg_jump(4).c == 878960812u, "4 steps: the two disks' draws of a sample's start");
 static_assert(lcg_jump(5).a == 2975532453u && lcg_jump(5).c == 3598456993u, "5 steps: up to the is_spec draw");
+static_assert(lcg_jump(8).a == 1124524385u && lcg_jump(8).c == 564359576u, "8 steps: up to the roulette draw of a plain hit (terminal skip)");
 static_assert(lcg_jump(12).a == 1985007505u && lcg_jump(12).c == 200982212u, "12 steps: up to the roulette draw of a primary segment");
 template <uint32_t K>
 DEV uint32_t rng_jump(uint32_t s) {
@@ -299,6 +300,10 @@ DEV uint32_t fbits(float f) { return __float_as_uint(f); }
 // The roulette skip of the pre-step (roulette_skip below, option "roulette_skip"); -DRT_ROULETTE_SKIP=0 compiles it out.
 #ifndef RT_ROULETTE_SKIP
 #define RT_ROULETTE_SKIP 1
+#endif
+// The terminal skip of the forest walk (intersect_scene's TERM; RenderArgs::terminal_dark); -DRT_TERMINAL_SKIP=0 compiles it out.
+#ifndef RT_TERMINAL_SKIP
+#define RT_TERMINAL_SKIP 1
 #endif
 #ifndef RT_TOP_BRANCH
 #define RT_TOP_BRANCH 1
@@ -602,9 +607,11 @@ DEV void traverse_flat2(const RenderArgs& a, uint32_t root_rec, bool cull, f3 lo
 // Skipping a member whose root box is missed is the monotonicity argument of intersect_scene
 // (FOREST_CULLABLE members only, finite ray only).
 // ANY: after a leaf that improved a member's best hit, probe(mesh, best) may end this lane's walk (traverse_mesh).
-template <bool LDS, bool STATS, bool SIMPLE, class Accept, bool ANY = false, class Probe = NoProbe>
+// SKIP and skip: this lane walks no member (intersect_scene's terminal skip: whatever the walk found would change nothing).
+template <bool LDS, bool STATS, bool SIMPLE, class Accept, bool ANY = false, class Probe = NoProbe, bool SKIP = false>
 DEV void traverse_forest(const RenderArgs& a, uint32_t entry0, uint32_t n_members, f3 lo, f3 ld, f3 inv,
-                         uint32_t* stack, Accept&& accept, int& node_tests, int& tri_tests, const Probe& probe = Probe{}) {
+                         uint32_t* stack, Accept&& accept, int& node_tests, int& tri_tests, const Probe& probe = Probe{},
+                         bool skip = false) {
     const bool finite_ray = rtm::abs_(inv.x) < INF && rtm::abs_(inv.y) < INF && rtm::abs_(inv.z) < INF &&
                             rtm::abs_(lo.x) < INF && rtm::abs_(lo.y) < INF && rtm::abs_(lo.z) < INF;
     const uint32_t e0 = a.lay.forest_off + entry0 * FOREST_ENTRY_BYTES;
@@ -620,6 +627,15 @@ DEV void traverse_forest(const RenderArgs& a, uint32_t entry0, uint32_t n_member
         else if (STATS) node_tests += 2;  // the shader's two root-level tests (wgsl:322)
     }
     TOC(t5, 5);
+    if constexpr (SKIP) {
+#if defined(RT_DIAG)
+        if (todo != 0u) {  // (the census of the terminal skip: lanes that enter the forest, and those of them it takes out)
+            DIAG(33);
+            if (skip) { DIAG(34); }
+        }
+#endif
+        if (skip) todo = 0u;
+    }
     const uint32_t tri0 = a.lay.tri_off;
     const LaneStack st{stack, a.stack_wide != 0u};
     uint32_t cur = 0, cur_count = 0, sp = 0, mesh = 0;
@@ -861,10 +877,36 @@ DEV Hit isect_finish(const RenderArgs& a, const Isect& I, f3 ro, f3 rd) {
 // hit -- and only the Isect is returned (Hit::hit = that candidate exists); with prune_tmax, boxes entered at or beyond
 // the local-space bound of DESIGN.md section 2.4 for tmax are skipped as well (not exact: the step-2 hypothesis of
 // cross_prune).
+// TERM (the render kernels' call in path_step, SIMPLE few-mesh kernels on a scene in LDS; RenderArgs::terminal_dark != 0):
+// the terminal skip.  Of a segment's hit, path_end uses the emitted light, the scatter and the next throughput; the last
+// two are dead when the path ends at the hit, and that is known before the segment is traversed -- at the last allowed
+// bounce (seg == number_of_bounces), or when the roulette is certain to kill it: at a plain material the hit makes 8
+// draws (is_spec, 6 of rand_unit_sphere, the roulette's: roulette_skip's counts), so the roulette value is the output of
+// the state 8 steps on, r8, and the path dies iff r8 >= p = max3(T * (is_spec ? specular_color : color)).  With T >= 0,
+// p <= B = max3(T * terminal_c) for every dark mesh (terminal_c: the componentwise maximum of both colours over the
+// meshes that emit nothing; IEEE multiplication and max are monotone, fmax drops a NaN on both sides alike, and a NaN
+// in T fails T >= 0).  Such a TERMINAL lane whose closest hit so far is a dark mesh, in front of items that are all dark
+// (the host's rule: the first lane-sparse item and everything behind it), ends with a dark closest hit whichever mesh
+// wins: the same light += (+0) * T, the same 8 draws, the end of the path; ro, rd and T, which differ, are overwritten
+// when the next sample starts.  So the lane leaves the sparse items out.  Not for primary segments (their hit goes into
+// the memo), not in counter or parking launches.  Whether the lane is terminal is the caller's answer (path_terminal,
+// asked before the traversal, where registers are to spare); it travels as bit PATH_TERMINAL of term_word, for which the
+// caller lends a word that is live across the traversal anyway (its segment number): a flag of its own was two more
+// scalar registers across the walk, and 8 bytes of scratch in the grouped kernel.
+constexpr uint32_t PATH_TERMINAL = 0x40000000u;
+[[maybe_unused]] DEV bool path_terminal(const RenderArgs& a, int32_t seg, uint32_t rng, f4 T) {  // (unused when compiled out)
+    if (a.terminal_dark == 0u || seg < 1) return false;  // (the first test: the wave-uniform switch)
+    if (seg >= a.params.number_of_bounces) return true;
+    const float r8 = (float)rng_output(rng_jump<8>(rng)) * 0x1p-32f;  // (rand_'s conversion)
+    const float B = max_(T.x * a.terminal_c[0], max_(T.y * a.terminal_c[1], T.z * a.terminal_c[2]));
+    return T.x >= 0.0f && T.y >= 0.0f && T.z >= 0.0f && r8 >= B;
+}
 template <bool LDS, bool STATS, bool TLAS, bool PARK = false, bool SIMPLE = false, bool HYB = false, bool ANY = false,
-          bool EXPORT = false>
+          bool EXPORT = false, bool TERM = false>
 DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int& node_tests,
-                        int& tri_tests, Isect& I_parked, float tmax = INF, bool prune_tmax = false) {
+                        int& tri_tests, Isect& I_parked, float tmax = INF, bool prune_tmax = false,
+                        uint32_t term_word = 0u) {
+    static_assert(!TERM || (SIMPLE && !TLAS && !STATS && !PARK && !ANY), "the terminal skip: SIMPLE few-mesh render launches only");
     // this lane's TLAS stack column sits behind the wave's BVH stack columns
     uint32_t* tstack = stack + stack_dwords(a);
     bool suspended = false;
@@ -950,6 +992,11 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
             stack[256] = i;
             have_pending = true;
         }
+    };
+    // (TERM) does this lane leave the lane-sparse item in front of it out?  Asked behind flush_pending(): I is current.
+    auto terminal_skip = [&]() {
+        if constexpr (TERM) return (term_word & PATH_TERMINAL) != 0u && I.any && ((a.terminal_dark >> (uint32_t)I.object) & 1u) != 0u;
+        else return false;
     };
     auto visit_mesh = [&](uint32_t i, float4 hdr) {
         const uint32_t flags = fbits(hdr.x);
@@ -1041,6 +1088,10 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                 traverse_forest<LDS, STATS, SIMPLE, decltype(any_deliver)&, true>(
                     a, ia, __builtin_amdgcn_readfirstlane(fbits(item.w)), lo, ld, inv, stack, any_deliver, node_tests,
                     tri_tests, any_probe);
+            else if constexpr (TERM)
+                traverse_forest<LDS, STATS, SIMPLE, decltype(accept_mesh_hit)&, false, NoProbe, true>(
+                    a, ia, __builtin_amdgcn_readfirstlane(fbits(item.w)), lo, ld, inv, stack, accept_mesh_hit, node_tests, tri_tests,
+                    NoProbe{}, terminal_skip());
             else
                 traverse_forest<LDS, STATS, SIMPLE>(a, ia, __builtin_amdgcn_readfirstlane(fbits(item.w)), lo, ld, inv, stack,
                                                     accept_mesh_hit, node_tests, tri_tests);
@@ -1114,7 +1165,16 @@ DEV Hit intersect_scene(const RenderArgs& a, f3 ro, f3 rd, uint32_t* stack, int&
                     else offer_later(ia, b);
                 }
             } else {
-                visit_mesh(ia, hdr);
+                if constexpr (TERM) {
+                    if (fbits(hdr.z) == 0u) {  // (an internal root: a walk of its own, lane-sparse like a forest's)
+                        flush_pending();
+                        if (!terminal_skip()) visit_mesh(ia, hdr);
+                    } else {
+                        visit_mesh(ia, hdr);
+                    }
+                } else {
+                    visit_mesh(ia, hdr);
+                }
             }
         } else {
             // Many-mesh kernels: one traversal loop serves single meshes and top-level trees, so the mesh walk is
@@ -2134,7 +2194,15 @@ DEV uint32_t path_step(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_
     } else if (mode == STEP_TRAVERSE) {
         TIC(t0);
         Isect I;
-        hit = intersect_scene<LDS, STATS, TLAS, PARK, SIMPLE, HYB>(a, s.ro, s.rd, stack_of<total_in_lds(LDS)>(ls), node_tests, tri_tests, I);
+        // (the terminal skip: the SIMPLE few-mesh kernels on a scene in LDS, where the host's rule can say yes)
+        constexpr bool TERM = RT_TERMINAL_SKIP != 0 && !RT_EXPERIMENTS && LDS && SIMPLE && !STATS && !TLAS && !PARK && !HYB;
+        if constexpr (TERM) {
+            if (path_terminal(a, s.seg, s.rng, s.T)) s.seg |= (int32_t)PATH_TERMINAL;  // (seg >= 0: the bit is free)
+            hit = intersect_scene<LDS, STATS, TLAS, PARK, SIMPLE, HYB, false, false, true>(
+                a, s.ro, s.rd, stack_of<total_in_lds(LDS)>(ls), node_tests, tri_tests, I, INF, false, (uint32_t)s.seg);
+            s.seg &= (int32_t)~PATH_TERMINAL;
+        } else
+            hit = intersect_scene<LDS, STATS, TLAS, PARK, SIMPLE, HYB>(a, s.ro, s.rd, stack_of<total_in_lds(LDS)>(ls), node_tests, tri_tests, I);
         TOC(t0, 0);
         if constexpr (PARK && !TLAS) {
             if (a.park != 0u) {  // (wave-uniform)

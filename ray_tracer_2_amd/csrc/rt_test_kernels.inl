@@ -52,6 +52,14 @@ __global__ void __launch_bounds__(256) rt_units_kernel(int fn, const float* __re
             r = __uint_as_float(v);
             break;
         }
+        case 20: {  // the terminal skip's jump against the generator stepped 8 times; y (bits) selects the value
+            const uint32_t s0 = __float_as_uint(a), which = __float_as_uint(b);
+            uint32_t s = s0, out8 = 0u;
+            for (int k = 1; k <= 8; ++k) out8 = next_random_number(s);
+            const uint32_t v = which == 0u ? rng_output(rng_jump<8>(s0)) : which == 1u ? out8 : which == 2u ? rng_jump<8>(s0) : s;
+            r = __uint_as_float(v);
+            break;
+        }
         default: break;
     }
     out[i] = r;

@@ -2,7 +2,8 @@
 """Divergence census (diagnostic build, -DRT_DIAG=1): for each code section,
 how many times a wave entered it and how many lanes were active on average.
     python tools/diag.py [variant]
-Builds ray_tracer_2_amd/librt2_mi355x_diag.so on first use (hipcc).
+Builds ray_tracer_2_amd/librt2_mi355x_diag.so on first use (hipcc); --build-only stops there, --prebuilt runs what an earlier
+--build-only left.  DIAG_NOTERM=1: the same census on a build without the terminal skip (librt2_mi355x_diag_noterm.so).
 """
 import ctypes as C
 import os
@@ -17,7 +18,12 @@ SECTIONS = {0: "iteration (path_step)", 1: "sample start (ray gen)", 3: "mesh tr
             4: "root-leaf tri: det", 5: "root-leaf tri: body", 6: "bvh: node visit", 7: "bvh: internal (2 aabb)",
             8: "bvh-leaf tri: det", 9: "bvh-leaf tri: body", 10: "mesh hit -> world", 11: "winner finalize",
             12: "miss: sky", 13: "shade: diffuse", 14: "shade: glass", 15: "refill: pixel_begin",
-            16: "pixel_finish", 28: "vote: nobody wants", 29: "vote: run, all want", 30: "vote: run, some reuse", 31: "vote: wait", 32: "roulette skip: dead sample", 17: "top tree: node (2 aabb)", 18: "top tree: mesh entry", 19: "shared walk: loop trip"}
+            16: "pixel_finish", 28: "vote: nobody wants", 29: "vote: run, all want", 30: "vote: run, some reuse", 31: "vote: wait", 32: "roulette skip: dead sample", 17: "top tree: node (2 aabb)", 18: "top tree: mesh entry", 19: "shared walk: loop trip",
+            33: "forest: lanes entering", 34: "forest: taken out (terminal)"}
+# DIAG_NOTERM=1: the census of a build without the terminal skip (-DRT_TERMINAL_SKIP=0), for the node passes before / after
+NOTERM = os.environ.get("DIAG_NOTERM") == "1"
+if NOTERM:
+    DIAG_SO = DIAG_SO.replace("_diag.so", "_diag_noterm.so")
 
 
 TIME_SO = os.path.join(ROOT, "ray_tracer_2_amd", "librt2_mi355x_diagt.so")
@@ -34,13 +40,19 @@ def build_timed():
 
 
 def build_diag():
-    build.build_product(extra_flags=("-DRT_DIAG=1",), out=DIAG_SO)
+    build.build_product(extra_flags=("-DRT_DIAG=1",) + (("-DRT_TERMINAL_SKIP=0",) if NOTERM else ()), out=DIAG_SO)
 
 
 def main():
     timed = "--time" in sys.argv
+    prebuilt = "--prebuilt" in sys.argv   # (run the library built earlier with --build-only: no compiler needed)
+    if prebuilt:
+        sys.argv.remove("--prebuilt")
     if timed:
         sys.argv.remove("--time")
+    if prebuilt:
+        pass
+    elif timed:
         build_timed()
     else:
         build_diag()

@@ -659,6 +659,83 @@ typedef struct rt_denoise_desc {
 enum { RT_DENOISE_HOST_MEMORY = 1 };
 int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags);
 
+/* Temporal accumulation across a camera move: the shader's per-texel accumulation (wgsl:154-161)
+ * with the history fetched from where each texel's hit point lay in the PREVIOUS frame.  Inputs: the current frame's
+ * colour and G-buffer planes (point, normal, optionally object: rt_render_gbuffer's), the previous frame's accumulated
+ * colour, a per-texel history length and its G-buffer planes, and the camera those were produced under.  Frames are
+ * width x height, row 0 = bottom, every plane tightly packed.  The scene itself is taken not to have moved.
+ * Everything is binary32 and unfused, in this order.
+ *   Once per call, on the host: V = mat4_inverse(prev_camera.cam_to_world) (glam's scalar cofactor inverse, csrc/host/
+ *   glam_math.h); pw, ph, fd = prev_camera.view_params.
+ *   Texel p = (x, y) is REPROJECTABLE when some component of normal(p) is non-zero, every component of normal(p) and
+ *   point(p) is finite, and object is NULL or object(p) != 0xffffffff.  A texel that is not (a miss, a NaN) gets
+ *   out(p) = color(p) bit for bit, out_history(p) = 1 and motion(p) = two quiet NaNs (0x7fc00000).
+ *   Projection, with X = point(p):  l_k = ((V[0][k] X0 + V[1][k] X1) + V[2][k] X2) + V[3][k] for k = 0, 1, 2 (column-major,
+ *   [col][row]);  ux = ((l0 / l2) * fd) / pw + 0.5;  uy = ((l1 / l2) * fd) / ph + 0.5;  fx = ux * (f32(W) - 1);
+ *   fy = uy * (f32(H) - 1) -- the inverse of the texel's focus point (wgsl:479-482).
+ *   ON SCREEN: l2 > 0, -1 < fx < W and -1 < fy < H (all false for NaN).  A texel that is not on screen takes the "no
+ *   history" result below, with motion = the two NaNs.
+ *   Snap, per axis: x0 = floor(fx) as an integer, tx = fx - f32(x0); with S = 1/64: if tx <= S then tx = 0, otherwise if
+ *   tx >= 1 - S then x0 += 1 and tx = 0.  A position within 1/64 texel of a texel centre takes that texel alone: a camera
+ *   that has not moved resamples nothing.   motion(p) = ((f32(x0) + tx) - f32(x), (f32(y0) + ty) - f32(y)).
+ *   Taps, in the order (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), with weights b = (1-tx)(1-ty), tx(1-ty), (1-tx)ty,
+ *   tx ty.  Tap q is VALID when b > 0; q is inside the frame; some component of prev_normal(q) is non-zero; prev_normal(q),
+ *   prev_point(q), all four components of prev_color(q) and prev_history(q) are finite; prev_history(q) >= 1; when both
+ *   object planes are given, prev_object(q) == object(p); with a = prev_point(q) - X and n = normal(p),
+ *   |(a0 n0 + a1 n1) + a2 n2| <= point_tolerance * l2; and with m = prev_normal(q), ((n0 m0 + n1 m1) + n2 m2) >= normal_cos.
+ *   A valid tap adds b * prev_color(q) (four components) to sum, b * prev_history(q) to hsum and b to wsum, in tap order,
+ *   all three from +0.
+ *   Blend.  If wsum > 0: prev = sum / wsum; n = hsum / wsum; n_c = n < max_history ? n : max_history; w = 1 / (n_c + 1);
+ *   out(p) = prev * (1 - w) + color(p) * w on all four components (two products, then the sum: wgsl:156-157);
+ *   out_history(p) = n_c + 1 -- but if some component of color(p) is not finite the sample is dropped: out(p) = prev and
+ *   out_history(p) = n_c.  If wsum is not > 0 there is no history: out(p) = color(p) bit for bit, out_history(p) = 1.
+ * Consequence: under an unmoved camera, with the same G-buffer on both sides, prev_history == k everywhere and `color` the
+ * raw sample of seed k (rt_render with frames = -k), every reprojectable texel takes one tap of weight 1 and `out` is what
+ * rt_render with frames = k leaves in the image, bit for bit, alpha included.
+ * Geometry that moved between the frames is out of scope: its texels fail the plane test and restart at history 1.
+ * point_tolerance is the distance from the current texel's tangent plane that a tap's hit point may have, per unit of view
+ * depth (the footprint of a texel grows with depth); normal_cos the least cosine between the two normals.
+ * rt_temporal_accumulate_host (section 3) is this definition over host pointers, without a device;
+ * rt_temporal_accumulate computes the same bits on the device.  Without RT_TEMPORAL_HOST_MEMORY the planes are device
+ * pointers on the handle's device (4-byte aligned; 16 for color, prev_color and out; 8 for motion), `color` may be NULL
+ * for the handle's current image (width * height texels of it), `out` may be `color` or that image, and the call is
+ * asynchronous on the handle's stream, after every earlier call on the handle and before every later one.  With the flag
+ * they are host pointers, staged WHOLE through one temporary device buffer (a gather can reach any row: no bands; 88 to
+ * 104 bytes per texel, `out` in the colour's place) that is counted against option "max_device_mb" while held (RT_ERR_OUT_OF_MEMORY past the cap), and
+ * the call returns when the outputs are on the host.
+ * `out` may be the same pointer as `color`.  out, out_history and motion must not overlap any prev_* plane, nor each
+ * other, nor any other input: undefined.  The call keeps no scratch between calls.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle or desc; a null plane other than object, prev_object,
+ * motion, and color on the device path; struct_bytes != sizeof(rt_temporal_desc); _p0 != 0; unknown flags; zero width or
+ * height; max_history NaN or below 1; point_tolerance NaN, <= 0 or infinite; normal_cos NaN or outside [-1, 1];
+ * misaligned device planes), RT_ERR_CAPACITY (width * height > 2^31 - 1, or more texels than the image has with a NULL
+ * color), RT_ERR_OUT_OF_MEMORY.  No scene is needed.
+ * Like the ray queries the call leaves the image (unless `out` is the image), the primary tables, a frame_ahead batch in
+ * flight, the pipeline slots, rt_get_stats and the launch words of rt_last_launch as they are. */
+typedef struct rt_temporal_desc {
+    uint32_t          struct_bytes;     /* = sizeof(rt_temporal_desc) */
+    uint32_t          _p0;              /* must be 0 */
+    uint32_t          width, height;
+    rt_camera_uniform prev_camera;      /* the camera the prev_* planes were produced under */
+    float             max_history;      /* >= 1, may be +INF: cap of the history length */
+    float             point_tolerance;  /* > 0, finite: plane distance allowed per unit of view depth */
+    float             normal_cos;       /* finite, in [-1, 1]: least dot product of the two normals */
+    const float*      color;            /* [h][w][4] current frame; device path: NULL = the handle's image */
+    const float*      point;            /* [h][w][3] current */
+    const float*      normal;           /* [h][w][3] current */
+    const uint32_t*   object;           /* [h][w] current, or NULL */
+    const float*      prev_color;       /* [h][w][4] accumulated history */
+    const float*      prev_history;     /* [h][w]    frames accumulated in prev_color, as a float >= 1 */
+    const float*      prev_point;       /* [h][w][3] */
+    const float*      prev_normal;      /* [h][w][3] */
+    const uint32_t*   prev_object;      /* [h][w] or NULL */
+    float*            out;              /* [h][w][4]; may be `color` */
+    float*            out_history;      /* [h][w] */
+    float*            motion;           /* [h][w][2] or NULL */
+} rt_temporal_desc;
+enum { RT_TEMPORAL_HOST_MEMORY = 1 };
+int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags);
+
 /* The test-only entry points (rt_test_*: the kernels' arithmetic building blocks evaluated element-wise on the device, raw
  * copies of sequence buffers, the RCCL gather against a stub, the frame_ahead policy) are NOT exported by the product
  * library: include/rt_test_abi.h declares them and ray_tracer_2_amd/librt2_mi355x_test.so -- the same sources compiled
@@ -795,6 +872,12 @@ int rt_export_rgba8(const float* rgba32f, uint32_t width, uint32_t height, uint8
  * nothing written on an error, the reason in rt_last_error(NULL); RT_ERR_OUT_OF_MEMORY when the host has no room for the
  * 64 bytes per texel of working memory. */
 int rt_denoise_host(const rt_denoise_desc* desc);
+
+/* Temporal accumulation's definition (section 2: rt_temporal_accumulate) in executable form: plain C++ over host
+ * pointers, no device, no working memory.  `color` is required; `out` may be `color`.  The same argument errors as
+ * rt_temporal_accumulate (no handle, no flags, no alignment rule), nothing written on an error, the reason in
+ * rt_last_error(NULL). */
+int rt_temporal_accumulate_host(const rt_temporal_desc* desc);
 
 #ifdef __cplusplus
 }

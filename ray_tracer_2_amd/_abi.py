@@ -117,6 +117,21 @@ class DenoiseDesc(C.Structure):  # rt_denoise_desc: a frame and its guides for r
 DENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission": 4, "out": 4}
 DENOISE_HOST_MEMORY = 1
 
+
+class TemporalDesc(C.Structure):  # rt_temporal_desc: two frames for rt_temporal_accumulate / rt_temporal_accumulate_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("prev_camera", CameraUniform),
+                ("max_history", f32), ("point_tolerance", f32), ("normal_cos", f32), ("color", C.c_void_p),
+                ("point", C.c_void_p), ("normal", C.c_void_p), ("object", C.c_void_p), ("prev_color", C.c_void_p),
+                ("prev_history", C.c_void_p), ("prev_point", C.c_void_p), ("prev_normal", C.c_void_p),
+                ("prev_object", C.c_void_p), ("out", C.c_void_p), ("out_history", C.c_void_p), ("motion", C.c_void_p)]
+
+
+# plane of rt_temporal_desc -> (numpy dtype, components per texel; 0: a plane of shape (H, W))
+TEMPORAL_PLANES = {"color": ("<f4", 4), "point": ("<f4", 3), "normal": ("<f4", 3), "object": ("<u4", 0),
+                   "prev_color": ("<f4", 4), "prev_history": ("<f4", 0), "prev_point": ("<f4", 3), "prev_normal": ("<f4", 3),
+                   "prev_object": ("<u4", 0), "out": ("<f4", 4), "out_history": ("<f4", 0), "motion": ("<f4", 2)}
+TEMPORAL_HOST_MEMORY = 1
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():

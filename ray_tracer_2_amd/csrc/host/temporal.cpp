@@ -1,0 +1,116 @@
+// host/temporal.cpp -- temporal accumulation's definition in executable form (include/rt_abi.h:
+// rt_temporal_accumulate_host), the argument rules and the once-per-call numbers it shares with
+// the device entry point.  Plain C++ over host pointers; the per-texel arithmetic is csrc/rt_temporal.h, which the device
+// kernel evaluates too.  Compiled with -ffp-contract=off.
+#if defined(__HIPCC__)
+// (the build compiles this C++ unit with hipcc as well: rt_temporal.h then marks its functions __host__ __device__
+// __forceinline__, which the runtime's headers define for plain C++)
+#include <hip/hip_runtime_api.h>
+#endif
+#include <cstring>
+
+#include "../rt_temporal_api.h"
+#include "glam_math.h"
+
+namespace rt2 {
+
+int temporal_check(const rt_temporal_desc* d, bool device, bool host_memory, std::string& err) {
+    auto bad = [&](int code, const char* msg) {
+        err = msg;
+        return code;
+    };
+    if (!d) return bad(RT_ERR_INVALID_ARGUMENT, "null rt_temporal_desc");
+    if (d->struct_bytes != sizeof(rt_temporal_desc)) return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_desc.struct_bytes is not sizeof(rt_temporal_desc)");
+    if (d->_p0 != 0u) return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_desc._p0 must be 0");
+    if (d->width == 0u || d->height == 0u) return bad(RT_ERR_INVALID_ARGUMENT, "zero width or height");
+    if (!(d->max_history >= 1.0f)) return bad(RT_ERR_INVALID_ARGUMENT, "max_history is NaN or below 1");
+    if (!(d->point_tolerance > 0.0f) || !rttp::is_finite(d->point_tolerance))
+        return bad(RT_ERR_INVALID_ARGUMENT, "point_tolerance is NaN, <= 0 or infinite");
+    if (!(d->normal_cos >= -1.0f && d->normal_cos <= 1.0f)) return bad(RT_ERR_INVALID_ARGUMENT, "normal_cos is NaN or outside [-1, 1]");
+    if (!d->point || !d->normal || !d->prev_color || !d->prev_history || !d->prev_point || !d->prev_normal || !d->out || !d->out_history)
+        return bad(RT_ERR_INVALID_ARGUMENT, "null point, normal, prev_color, prev_history, prev_point, prev_normal, out or out_history plane");
+    if (!d->color && (!device || host_memory)) return bad(RT_ERR_INVALID_ARGUMENT, "null color plane (only device planes may name the handle's image that way)");
+    if ((uint64_t)d->width * d->height > 0x7fffffffull) return bad(RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
+    if (device && !host_memory) {
+        const struct { const void* p; uintptr_t mask; const char* name; } planes[12] = {
+            {d->color, 15u, "color"}, {d->point, 3u, "point"}, {d->normal, 3u, "normal"}, {d->object, 3u, "object"},
+            {d->prev_color, 15u, "prev_color"}, {d->prev_history, 3u, "prev_history"}, {d->prev_point, 3u, "prev_point"},
+            {d->prev_normal, 3u, "prev_normal"}, {d->prev_object, 3u, "prev_object"}, {d->out, 15u, "out"},
+            {d->out_history, 3u, "out_history"}, {d->motion, 7u, "motion"}};
+        for (const auto& pl : planes)
+            if (((uintptr_t)pl.p & pl.mask) != 0u) {
+                err = std::string("device plane ") + pl.name + " is not aligned to " + std::to_string(pl.mask + 1u) + " bytes";
+                return RT_ERR_INVALID_ARGUMENT;
+            }
+    }
+    return RT_OK;
+}
+
+rttp::Call temporal_call(const rt_temporal_desc* d) {
+    Mat4 m;
+    std::memcpy(&m, d->prev_camera.cam_to_world, sizeof(m));
+    const Mat4 v = mat4_inverse(m);
+    rttp::Call c{};
+    for (int col = 0; col < 4; ++col)
+        for (int k = 0; k < 3; ++k) c.v[col][k] = v.c[col][k];
+    c.pw = d->prev_camera.view_params[0];
+    c.ph = d->prev_camera.view_params[1];
+    c.fd = d->prev_camera.view_params[2];
+    c.max_history = d->max_history;
+    c.point_tolerance = d->point_tolerance;
+    c.normal_cos = d->normal_cos;
+    c.width = d->width;
+    c.height = d->height;
+    return c;
+}
+
+int temporal_host(const rt_temporal_desc* d, std::string& err) {
+    if (const int rc = temporal_check(d, false, false, err); rc != RT_OK) return rc;
+    const rttp::Call c = temporal_call(d);
+    const int64_t W = d->width, H = d->height;
+    const bool match_object = d->object && d->prev_object;
+    const float nan = rttp::u2f(rttp::QUIET_NAN);
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t x = 0; x < W; ++x) {
+            const size_t p = (size_t)(y * W + x);
+            float color[4];   // (out may be color: the texel is read before it is written)
+            std::memcpy(color, d->color + 4 * p, sizeof(color));
+            const float* X = d->point + 3 * p;
+            const float* n = d->normal + 3 * p;
+            const uint32_t obj = d->object ? d->object[p] : 0u;
+            rttp::Result r;
+            std::memcpy(r.out, color, sizeof(color));
+            r.history = 1.0f;
+            float motion[2] = {nan, nan};
+            if (rttp::reprojectable(n, X, d->object != nullptr, obj)) {
+                const rttp::Where w = rttp::locate(c, X, (uint32_t)x, (uint32_t)y);
+                if (w.on_screen) {
+                    rttp::Tap taps[4];
+                    for (int i = 0; i < 4; ++i) {
+                        const int64_t qx = (int64_t)w.ax.i0 + rttp::tap_dx(i), qy = (int64_t)w.ay.i0 + rttp::tap_dy(i);
+                        rttp::Tap& t = taps[i];
+                        t.inside = qx >= 0 && qx < W && qy >= 0 && qy < H;
+                        // (a tap outside the frame reads the nearest texel inside, as the kernel does, and is refused)
+                        const int64_t cx = qx < 0 ? 0 : qx >= W ? W - 1 : qx, cy = qy < 0 ? 0 : qy >= H ? H - 1 : qy;
+                        const size_t q = (size_t)(cy * W + cx);
+                        for (int k = 0; k < 3; ++k) {
+                            t.n[k] = d->prev_normal[3 * q + k];
+                            t.x[k] = d->prev_point[3 * q + k];
+                        }
+                        std::memcpy(t.c, d->prev_color + 4 * q, sizeof(t.c));
+                        t.h = d->prev_history[q];
+                        t.obj = match_object ? d->prev_object[q] : 0u;
+                    }
+                    r = rttp::resolve(c, w, X, n, match_object, obj, color, taps);
+                    motion[0] = w.motion[0];
+                    motion[1] = w.motion[1];
+                }
+            }
+            std::memcpy(d->out + 4 * p, r.out, sizeof(r.out));
+            d->out_history[p] = r.history;
+            if (d->motion) std::memcpy(d->motion + 2 * p, motion, sizeof(motion));
+        }
+    return RT_OK;
+}
+
+}  // namespace rt2

@@ -23,6 +23,7 @@
 #include "rt_device.h"
 #include "rt_refit.h"
 #include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
+#include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0
@@ -65,6 +66,7 @@ hipError_t launch_test_shade(const RenderArgs& a, int which, const uint32_t* cas
 hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
+hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -2380,6 +2382,79 @@ int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags) {
         if (what = "launch_denoise", (e = launch_denoise(a, h->stream)) != hipSuccess) return e;
         what = "hipMemcpyAsync";
         return hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream);
+    });
+}
+
+// ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate, rt_temporal_accumulate_host; rt_temporal.hip;
+// host/temporal.cpp) ----
+// Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs;
+// no scratch is kept.
+int rt_temporal_accumulate_host(const rt_temporal_desc* desc) {
+    std::string err;
+    const int rc = rt2::temporal_host(desc, err);
+    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+}
+
+int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
+    {
+        std::string err;
+        if (const int rc = rt2::temporal_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    }
+    const size_t texels = (size_t)desc->width * desc->height;
+    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TemporalArgs a{};
+    a.call = rt2::temporal_call(desc);
+    if (!host) {
+        const float* image = reinterpret_cast<const float*>(h->image);
+        a.color = desc->color ? desc->color : image;
+        a.point = desc->point; a.normal = desc->normal; a.object = desc->object;
+        a.prev_color = desc->prev_color; a.prev_history = desc->prev_history; a.prev_point = desc->prev_point;
+        a.prev_normal = desc->prev_normal; a.prev_object = desc->prev_object;
+        a.out = desc->out; a.out_history = desc->out_history; a.motion = desc->motion;
+        const bool out_is_image = desc->out >= image && desc->out < image + 4 * h->image_texels;
+        if (a.color == image || out_is_image) {
+            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+        }
+        if (out_is_image) h->generation += 1;   // (the image changes, as by rt_write_image)
+        HIP_TRY(h, launch_temporal(a, h->stream));
+        return RT_OK;
+    }
+    // host memory: every plane whole through one temporary device buffer (a gather can reach any row: no bands); each
+    // plane's part of it starts at a multiple of 256 bytes, and `out` takes the colour plane's place
+    const void* const src[12] = {desc->color, desc->point, desc->normal, desc->object, desc->prev_color, desc->prev_history,
+                                 desc->prev_point, desc->prev_normal, desc->prev_object, nullptr, desc->out_history, desc->motion};
+    static const uint32_t bytes[12] = {16, 12, 12, 4, 16, 4, 12, 12, 4, 0, 4, 8};
+    size_t plane_off[12] = {}, off = 0;
+    for (int c = 0; c < 12; ++c) {
+        if (!src[c]) continue;
+        plane_off[c] = off;
+        off = (off + texels * bytes[c] + 255u) & ~(size_t)255u;
+    }
+    if (!fits_cap(h, off)) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the staging planes of temporal accumulation");
+    return staged_chunks(h, off, 1, 1, "the staging planes of temporal accumulation", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
+        hipError_t e = hipSuccess;
+        what = "hipMemcpyAsync";
+        void* d_ptr[12] = {};
+        for (int c = 0; c < 12 && e == hipSuccess; ++c) {
+            if (!src[c]) continue;
+            d_ptr[c] = buf + plane_off[c];
+            if (c < 9) e = hipMemcpyAsync(d_ptr[c], src[c], texels * bytes[c], hipMemcpyHostToDevice, h->stream);
+        }
+        if (e != hipSuccess) return e;
+        a.color = (const float*)d_ptr[0]; a.point = (const float*)d_ptr[1]; a.normal = (const float*)d_ptr[2];
+        a.object = (const uint32_t*)d_ptr[3]; a.prev_color = (const float*)d_ptr[4]; a.prev_history = (const float*)d_ptr[5];
+        a.prev_point = (const float*)d_ptr[6]; a.prev_normal = (const float*)d_ptr[7]; a.prev_object = (const uint32_t*)d_ptr[8];
+        a.out = (float*)d_ptr[0]; a.out_history = (float*)d_ptr[10]; a.motion = (float*)d_ptr[11];
+        if (what = "launch_temporal", (e = launch_temporal(a, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        if ((e = hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(desc->out_history, a.out_history, texels * 4u, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
+        if (desc->motion) e = hipMemcpyAsync(desc->motion, a.motion, texels * 8u, hipMemcpyDeviceToHost, h->stream);
+        return e;
     });
 }
 

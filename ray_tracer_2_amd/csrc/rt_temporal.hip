@@ -1,0 +1,93 @@
+// rt_temporal.hip -- the device kernel of temporal accumulation (include/rt_abi.h: rt_temporal_accumulate; DESIGN.md
+// section 2.14).
+//
+// One lane per current texel, a workgroup per tile of 32 x 8 texels (a wave: 32 x 2), so that the four taps of
+// neighbouring lanes fall into neighbouring texels of the previous frame and a wave's gather touches a few rows of it.
+// A lane reads its own texel's colour, point, normal and object word, leaves with the "no history" result when the texel
+// is not reprojectable or falls off the previous screen, and otherwise issues the loads of all four taps -- from the
+// previous frame's planes directly, a tap outside the frame from the nearest texel inside -- before any validity
+// arithmetic; what a tap adds is selected afterwards (rttp::resolve), so no branch stands between the loads.  out,
+// out_history and motion are written once and read by nobody in the launch: streaming stores.
+// The per-texel arithmetic is csrc/rt_temporal.h, shared with the host restatement (host/temporal.cpp); this file is
+// compiled with -ffp-contract=off, so the result is the host's bit for bit.
+//
+// Bounds: a lane outside the frame leaves before any access; a lane's own index p and every tap index q (both
+// coordinates clamped into the frame) are < width * height <= 2^31 - 1 (the entry point checks), and every address is
+// formed in 64 bits.  The snapped tap origin is in [-1, width] x [-1, height] (on screen: -1 < fx < width), so x0 + 1
+// does not overflow an int32.
+#include <hip/hip_runtime.h>
+
+#include "rt_temporal.h"
+#include "rt_temporal_api.h"
+
+namespace rtd {
+namespace {
+
+constexpr uint32_t TILE_W = 32, TILE_H = 8, TEMPORAL_THREADS = TILE_W * TILE_H;
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+#define RT_GLOBAL(T, p) ((__attribute__((address_space(1))) T*)(void*)(p))
+
+__device__ __forceinline__ void store_texel(const TemporalArgs& a, size_t p, const float out[4], float history, float mx, float my) {
+    __builtin_nontemporal_store(v4f{out[0], out[1], out[2], out[3]}, RT_GLOBAL(v4f, reinterpret_cast<float4*>(a.out) + p));
+    __builtin_nontemporal_store(history, RT_GLOBAL(float, a.out_history + p));
+    if (a.motion) __builtin_nontemporal_store(v2f{mx, my}, RT_GLOBAL(v2f, reinterpret_cast<float2*>(a.motion) + p));
+}
+
+__global__ void __launch_bounds__(TEMPORAL_THREADS) rt_temporal_kernel(const TemporalArgs a) {
+    const uint32_t W = a.call.width, H = a.call.height;
+    const uint32_t tiles_x = (W + TILE_W - 1) / TILE_W;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const uint32_t x = tx * TILE_W + (threadIdx.x & (TILE_W - 1)), y = ty * TILE_H + threadIdx.x / TILE_W;   // (< 2^31 + 32)
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + (size_t)x;
+    const float4 c4 = reinterpret_cast<const float4*>(a.color)[p];
+    const float color[4] = {c4.x, c4.y, c4.z, c4.w};
+    const float X[3] = {a.point[3 * p], a.point[3 * p + 1], a.point[3 * p + 2]};
+    const float n[3] = {a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2]};
+    const uint32_t obj = a.object ? a.object[p] : 0u;
+    const float nan = rttp::u2f(rttp::QUIET_NAN);
+    if (!rttp::reprojectable(n, X, a.object != nullptr, obj)) {
+        store_texel(a, p, color, 1.0f, nan, nan);
+        return;
+    }
+    const rttp::Where w = rttp::locate(a.call, X, x, y);
+    if (!w.on_screen) {
+        store_texel(a, p, color, 1.0f, nan, nan);
+        return;
+    }
+    const bool match_object = a.object && a.prev_object;
+    rttp::Tap taps[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        // (x0 is in [-1, W]: as unsigned, -1 wraps past W and fails the one comparison, like W and W + 1)
+        const int32_t qx = w.ax.i0 + rttp::tap_dx(i), qy = w.ay.i0 + rttp::tap_dy(i);
+        rttp::Tap& t = taps[i];
+        t.inside = (uint32_t)qx < W && (uint32_t)qy < H;
+        const uint32_t cx = qx < 0 ? 0u : (uint32_t)qx >= W ? W - 1u : (uint32_t)qx;
+        const uint32_t cy = qy < 0 ? 0u : (uint32_t)qy >= H ? H - 1u : (uint32_t)qy;
+        const size_t q = (size_t)cy * W + (size_t)cx;
+        const float4 pc = reinterpret_cast<const float4*>(a.prev_color)[q];
+        t.c[0] = pc.x; t.c[1] = pc.y; t.c[2] = pc.z; t.c[3] = pc.w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            t.n[k] = a.prev_normal[3 * q + k];
+            t.x[k] = a.prev_point[3 * q + k];
+        }
+        t.h = a.prev_history[q];
+        t.obj = match_object ? a.prev_object[q] : 0u;
+    }
+    const rttp::Result r = rttp::resolve(a.call, w, X, n, match_object, obj, color, taps);
+    store_texel(a, p, r.out, r.history, w.motion[0], w.motion[1]);
+}
+
+}  // namespace
+
+hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream) {
+    const uint32_t tiles = ((a.call.width + TILE_W - 1) / TILE_W) * ((a.call.height + TILE_H - 1) / TILE_H);   // (<= 2^31 / 8 + ...: fits)
+    hipLaunchKernelGGL(rt_temporal_kernel, dim3(tiles), dim3(TEMPORAL_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace rtd

@@ -70,6 +70,94 @@ def denoise_host(guides, color, iterations=3, sigma_color=DENOISE_SIGMA_COLOR, s
     return res
 
 
+# Temporal accumulation's default thresholds (RayTracer.temporal_accumulate, temporal_accumulate_host): a tap's hit point
+# may lie 1 % of the view depth off the current texel's tangent plane -- under the Cornell camera a fifth of a texel's
+# footprint at 67 x 45 and five footprints at 1920 x 1080; the distance is along the normal, so on a flat wall it is zero
+# but for rounding, and what the test refuses is another surface behind or in front --, and
+# the two normals may be up to acos(0.9) = 26 degrees apart.  DESIGN.md section 2.14 has what the quality test measured
+# with them.
+TEMPORAL_POINT_TOLERANCE, TEMPORAL_NORMAL_COS = 0.01, 0.9
+
+
+def _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos):
+    if not isinstance(prev_camera, A.CameraUniform):
+        raise ValueError("prev_camera must be a CameraUniform")
+    return A.TemporalDesc(struct_bytes=C.sizeof(A.TemporalDesc), width=W, height=H,
+                          prev_camera=A.CameraUniform.from_buffer_copy(bytes(prev_camera)), max_history=float(max_history),
+                          point_tolerance=float(point_tolerance), normal_cos=float(normal_cos))
+
+
+def _temporal_inputs(guides, prev_guides, prev_color, prev_history, color):
+    """The desc's input planes by name, from the two guide dicts (render_gbuffer's; each side's `object` plane is
+    optional), and the frame's size."""
+    for g, what in ((guides, "guides"), (prev_guides, "prev_guides")):
+        if "normal" not in g or "point" not in g:
+            raise ValueError(f"{what} must hold the normal and point planes of render_gbuffer")
+    planes = {"point": guides["point"], "normal": guides["normal"], "prev_color": prev_color, "prev_history": prev_history,
+              "prev_point": prev_guides["point"], "prev_normal": prev_guides["normal"]}
+    if "object" in guides:
+        planes["object"] = guides["object"]
+    if "object" in prev_guides:
+        planes["prev_object"] = prev_guides["object"]
+    if color is not None:
+        planes["color"] = color
+    H, W = (int(v) for v in np.shape(planes["normal"])[:2])
+    return planes, W, H
+
+
+def _temporal_shape(k, W, H):
+    n = A.TEMPORAL_PLANES[k][1]
+    return (H, W, n) if n else (H, W)
+
+
+def _temporal_numpy(d, W, H, planes, out, out_history, motion):
+    """Points the desc at contiguous copies of the numpy inputs (or the arrays themselves) and at the outputs; returns what
+    must stay alive and the three outputs (motion: None when it is not asked for)."""
+    keep = {}
+    for k, v in planes.items():
+        a = np.ascontiguousarray(v, np.dtype(A.TEMPORAL_PLANES[k][0]))
+        if a.shape != _temporal_shape(k, W, H):
+            raise ValueError(f"plane {k} must have shape {_temporal_shape(k, W, H)}, not {a.shape}")
+        keep[k] = a
+        setattr(d, k, a.ctypes.data)
+    res = {}
+    for k, v in (("out", out), ("out_history", out_history), ("motion", motion)):
+        if v is None or v is False:
+            res[k] = None
+            continue
+        if v is True:
+            v = np.zeros(_temporal_shape(k, W, H), np.float32)
+        elif not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.shape == _temporal_shape(k, W, H) and v.flags.c_contiguous
+                  and v.flags.writeable):
+            raise ValueError(f"{k} must be a writeable contiguous float32 array of shape {_temporal_shape(k, W, H)}")
+        res[k] = v
+        setattr(d, k, v.ctypes.data)
+    return keep, res
+
+
+def _temporal_result(res):
+    return (res["out"], res["out_history"]) if res["motion"] is None else (res["out"], res["out_history"], res["motion"])
+
+
+def temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history=float("inf"),
+                             point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
+                             motion=False):
+    """rt_temporal_accumulate_host: temporal accumulation's definition on the CPU (no device), with
+    RayTracer.temporal_accumulate's arguments for numpy planes.  RayTracer.temporal_accumulate computes the same bits on the
+    GPU."""
+    planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
+    if color is None:
+        raise ValueError("color is required on the host")
+    d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
+    keep, res = _temporal_numpy(d, W, H, planes, True if out is None else out, True if out_history is None else out_history, motion)
+    L = load()
+    rc = L.rt_temporal_accumulate_host(C.byref(d))
+    del keep
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+    return _temporal_result(res)
+
+
 class RayTracer:
     def __init__(self, device=0, max_width=1920, max_height=1080, lib=None):
         self._L = lib or load()   # (lib=load_test(): a handle of the test library, for the rt_test_* entry points)
@@ -468,6 +556,56 @@ class RayTracer:
         self._check(self._L.rt_denoise(self._h, C.byref(d), 0))
         cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
         return out
+
+    def temporal_accumulate(self, guides, prev_guides, prev_camera, prev_color, prev_history, color=None, max_history=float("inf"),
+                            point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
+                            motion=False):
+        """Temporal accumulation across a camera move (rt_temporal_accumulate; include/rt_abi.h has the definition): every
+        texel of the current frame `color` (H, W, 4) fetches the history `prev_color` (H, W, 4) / `prev_history` (H, W;
+        frames accumulated, as float32 >= 1) from where its hit point lay under `prev_camera` (a CameraUniform), through
+        bilinear taps validated against the two G-buffers, and blends itself in with the shader's accumulation at its own
+        weight.  `guides`, `prev_guides`: the dicts render_gbuffer returns for the two frames; each must hold `point` and
+        `normal`, and `object` is compared when both hold it.  `max_history` caps the history length (inf: a plain
+        running mean); `point_tolerance` is the distance off the texel's tangent plane a tap may lie, per unit of view
+        depth; `normal_cos` the least cosine between the two normals.  Returns (out, out_history), or with motion=True (or
+        an array / tensor to fill) (out, out_history, motion): motion is the screen-space offset, in texels, to the
+        position the history came from (NaN where nothing was reprojected).  out / out_history must not be any prev_*
+        plane; `out` may be `color`.
+        numpy planes: a synchronous call that returns numpy arrays.  Torch tensors on this handle's device: an asynchronous
+        call ordered after the current torch stream's work, as render_gbuffer(device=True) orders itself; returns tensors;
+        there color=None takes the handle's image as the current frame."""
+        planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
+        d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
+        outs = {"out": out, "out_history": out_history, "motion": None if motion is False or motion is True else motion}
+        if not any(hasattr(v, "data_ptr") for v in (*planes.values(), *outs.values())):
+            if color is None:
+                raise ValueError("color is required with numpy planes (color=None names the device image)")
+            keep, res = _temporal_numpy(d, W, H, planes, True if out is None else out, True if out_history is None else out_history, motion)
+            self._check(self._L.rt_temporal_accumulate(self._h, C.byref(d), A.TEMPORAL_HOST_MEMORY))
+            del keep
+            return _temporal_result(res)
+        import torch
+        dev = torch.device("cuda", self.device)
+        given = dict(planes, **{k: v for k, v in outs.items() if v is not None})
+        for k, v in given.items():
+            if not isinstance(v, torch.Tensor):
+                raise ValueError("mix of device tensors and host arrays")
+            if v.device.type != "cuda" or v.device.index != self.device:
+                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
+            kinds = (torch.float32,) if A.TEMPORAL_PLANES[k][0] == "<f4" else (torch.int32, getattr(torch, "uint32", torch.int32))   # (object: the u32 bits)
+            if v.dtype not in kinds or not v.is_contiguous() or tuple(v.shape) != _temporal_shape(k, W, H):
+                raise ValueError(f"plane {k} must be a contiguous {kinds[0]} tensor of shape {_temporal_shape(k, W, H)}")
+        for k in ("out", "out_history") + (("motion",) if motion is not False else ()):
+            if outs[k] is None:
+                outs[k] = given[k] = torch.empty(_temporal_shape(k, W, H), dtype=torch.float32, device=dev)
+        for k, v in given.items():
+            setattr(d, k, v.data_ptr())
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
+        ext.wait_stream(cur)
+        self._check(self._L.rt_temporal_accumulate(self._h, C.byref(d), 0))
+        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launch: _device_query)
+        return _temporal_result(outs)
 
     def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):
         """Radiance along rays of the caller's (rt_radiance_rays): for ray i `frag`'s sample loop with the ray held fixed --

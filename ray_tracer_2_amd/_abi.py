@@ -118,6 +118,20 @@ DENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission": 
 DENOISE_HOST_MEMORY = 1
 
 
+class VDenoiseDesc(C.Structure):  # rt_vdenoise_desc: a frame, its guides and its luminance moments for rt_denoise_variance / rt_luminance_moments
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("iterations", u32),
+                ("sigma_luminance", f32), ("sigma_normal", f32), ("sigma_point", f32), ("min_history", f32), ("_p1", u32),
+                ("color", C.c_void_p), ("normal", C.c_void_p), ("point", C.c_void_p), ("albedo", C.c_void_p),
+                ("emission", C.c_void_p), ("moments", C.c_void_p), ("history", C.c_void_p), ("out", C.c_void_p),
+                ("out_variance", C.c_void_p)]
+
+
+# plane of rt_vdenoise_desc -> components per texel; 0: a plane of shape (H, W)
+VDENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission": 4, "moments": 4, "history": 0, "out": 4,
+                   "out_variance": 0}
+VDENOISE_HOST_MEMORY = 1
+
+
 class TemporalDesc(C.Structure):  # rt_temporal_desc: two frames for rt_temporal_accumulate / rt_temporal_accumulate_host
     _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("prev_camera", CameraUniform),
                 ("max_history", f32), ("point_tolerance", f32), ("normal_cos", f32), ("color", C.c_void_p),

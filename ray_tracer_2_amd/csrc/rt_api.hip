@@ -24,6 +24,7 @@
 #include "rt_refit.h"
 #include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
 #include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
+#include "rt_vdenoise_api.h"  // (the variance-guided denoiser: its argument rules and host restatement, host/vdenoise.cpp; its launches, rt_vdenoise.hip)
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0
@@ -67,6 +68,8 @@ hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
+hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
+hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -2384,6 +2387,121 @@ int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags) {
         return hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream);
     });
 }
+
+// ---- variance-guided denoising (include/rt_abi.h: rt_denoise_variance, rt_luminance_moments and their _host forms;
+// rt_vdenoise.hip; host/vdenoise.cpp) ----
+// Launched like rt_denoise, in rt_denoise's scratch: each call of either rewrites every word of it that it later reads.
+int rt_denoise_variance_host(const rt_vdenoise_desc* desc) {
+    try {
+        std::string err;
+        const int rc = rt2::vdenoise_host(desc, err);
+        return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+    } catch (const std::bad_alloc&) {
+        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+    }
+}
+
+int rt_luminance_moments_host(const rt_vdenoise_desc* desc) {
+    std::string err;
+    const int rc = rt2::luminance_moments_host(desc, err);
+    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+}
+
+// The two entry points: moments_only is rt_luminance_moments, which needs no scratch and stages fewer planes.
+static int vdenoise_call(rt_handle* h, const rt_vdenoise_desc* desc, int flags, bool moments_only) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_VDENOISE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_VDENOISE_HOST_MEMORY) != 0;
+    {
+        std::string err;
+        if (const int rc = rt2::vdenoise_check(desc, moments_only, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    }
+    const size_t texels = (size_t)desc->width * desc->height;
+    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // the planes of the host-memory path, in staging order: the first five are rt_denoise's; `out` takes the colour's place
+    const bool with_moments = !moments_only && desc->moments, with_variance = !moments_only && desc->out_variance;
+    const void* const src[8] = {desc->color, desc->normal, desc->point, desc->albedo, desc->emission,
+                                with_moments ? desc->moments : nullptr, with_moments ? desc->history : nullptr,
+                                with_variance ? desc->out_variance : nullptr};
+    static const uint32_t bytes[8] = {16, 12, 12, 16, 16, 16, 4, 4};
+    size_t plane_off[8] = {}, staging = 0;
+    if (host)
+        for (int c = 0; c < 8; ++c) {
+            if (!src[c]) continue;
+            plane_off[c] = staging;
+            staging = (staging + texels * bytes[c] + 255u) & ~(size_t)255u;
+        }
+    // the scratch: rt_denoise's, grown on demand, within option max_device_mb
+    if (!moments_only && h->denoise_texels < texels) {
+        if (!fits_cap(h, texels * 64u + staging, h->denoise_texels * 64u))
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's scratch images");
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
+        free_dev(h->denoise_scratch);
+        h->denoise_texels = 0;
+        const hipError_t e = hipMalloc((void**)&h->denoise_scratch, texels * 64u);
+        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the denoiser's scratch images");
+        HIP_TRY(h, e);
+        h->denoise_texels = texels;
+    } else if (!fits_cap(h, staging)) {
+        return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's staging planes");
+    }
+    VDenoiseArgs a{};
+    a.width = desc->width;
+    a.height = desc->height;
+    if (!moments_only) {
+        a.iterations = (int)desc->iterations;
+        a.sigma_luminance = desc->sigma_luminance;
+        a.sigma_normal = desc->sigma_normal;
+        a.sigma_point = desc->sigma_point;
+        a.min_history = desc->min_history;
+        a.guide = h->denoise_scratch;
+        a.ping[0] = h->denoise_scratch + 2 * texels;
+        a.ping[1] = h->denoise_scratch + 3 * texels;
+    }
+    auto launch = [&](const char*& what) {
+        what = moments_only ? "launch_luminance_moments" : "launch_vdenoise";
+        return moments_only ? launch_luminance_moments(a, h->stream) : launch_vdenoise(a, h->stream);
+    };
+    if (!host) {
+        const float* image = reinterpret_cast<const float*>(h->image);
+        a.color = desc->color ? desc->color : image;
+        a.normal = desc->normal; a.point = desc->point; a.albedo = desc->albedo; a.emission = desc->emission; a.out = desc->out;
+        if (with_moments) { a.moments = desc->moments; a.history = desc->history; }
+        if (with_variance) a.out_variance = desc->out_variance;
+        const bool out_is_image = desc->out >= image && desc->out < image + 4 * h->image_texels;
+        if (a.color == image || out_is_image) {
+            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+        }
+        if (out_is_image) h->generation += 1;   // (the image changes, as by rt_write_image)
+        const char* what = nullptr;
+        HIP_TRY(h, launch(what));
+        return RT_OK;
+    }
+    // host memory: the whole frame through one temporary device buffer, each plane's part of it at a multiple of 256 bytes
+    return staged_chunks(h, staging, 1, 1, "the denoiser's staging planes", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
+        hipError_t e = hipSuccess;
+        what = "hipMemcpyAsync";
+        float* d_ptr[8] = {};
+        for (int c = 0; c < 8 && e == hipSuccess; ++c) {
+            if (!src[c]) continue;
+            d_ptr[c] = reinterpret_cast<float*>(buf + plane_off[c]);
+            if (c < 7) e = hipMemcpyAsync(d_ptr[c], src[c], texels * bytes[c], hipMemcpyHostToDevice, h->stream);
+        }
+        if (e != hipSuccess) return e;
+        a.color = d_ptr[0]; a.normal = d_ptr[1]; a.point = d_ptr[2]; a.albedo = d_ptr[3]; a.emission = d_ptr[4];
+        a.moments = d_ptr[5]; a.history = d_ptr[6];
+        a.out = d_ptr[0]; a.out_variance = d_ptr[7];
+        if ((e = launch(what)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        if ((e = hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
+        if (with_variance) e = hipMemcpyAsync(desc->out_variance, a.out_variance, texels * 4u, hipMemcpyDeviceToHost, h->stream);
+        return e;
+    });
+}
+
+int rt_denoise_variance(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, false); }
+int rt_luminance_moments(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, true); }
 
 // ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate, rt_temporal_accumulate_host; rt_temporal.hip;
 // host/temporal.cpp) ----

@@ -30,6 +30,7 @@ EXPORTS = [
     "rt_scene_destroy", "rt_upload_built_scene", "rt_scene_subdivide_meshes", "rt_export_rgba8",
     "rt_intersect_rays", "rt_occluded_rays", "rt_pick", "rt_render_gbuffer", "rt_radiance_rays",
     "rt_denoise", "rt_denoise_host", "rt_temporal_accumulate", "rt_temporal_accumulate_host",
+    "rt_denoise_variance", "rt_luminance_moments", "rt_denoise_variance_host", "rt_luminance_moments_host",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
     "rt_scene_set_sphere",
     "rt_refit_bvh", "rt_refit_triangles", "rt_refit_built_scene", "rt_scene_set_mesh_vertices", "rt_scene_triangle_order",
@@ -149,6 +150,10 @@ def _bind(L, with_test_entries):
         "rt_denoise_host": (i32, [P(A.DenoiseDesc)]),
         "rt_temporal_accumulate": (i32, [vp, P(A.TemporalDesc), i32]),
         "rt_temporal_accumulate_host": (i32, [P(A.TemporalDesc)]),
+        "rt_denoise_variance": (i32, [vp, P(A.VDenoiseDesc), i32]),
+        "rt_luminance_moments": (i32, [vp, P(A.VDenoiseDesc), i32]),
+        "rt_denoise_variance_host": (i32, [P(A.VDenoiseDesc)]),
+        "rt_luminance_moments_host": (i32, [P(A.VDenoiseDesc)]),
         "rt_update_instances": (i32, [vp, P(A.SceneUniform), vp, u32, vp, u32]),
         "rt_update_built_scene": (i32, [vp, vp]),
         "rt_scene_set_mesh_transform": (i32, [vp, u32, P(A.Transform)]),

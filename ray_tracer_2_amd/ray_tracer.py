@@ -158,6 +158,101 @@ def temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_
     return _temporal_result(res)
 
 
+# The variance-guided denoiser's defaults (RayTracer.denoise_variance, denoise_variance_host): a luminance difference of
+# sigma_luminance standard deviations of the local noise costs a factor e; a texel's accumulated moments give its variance
+# once min_history frames stand behind them, and the 7 x 7 window does before that.
+VDENOISE_SIGMA_LUMINANCE, VDENOISE_MIN_HISTORY = 4.0, 4.0
+
+
+def _vdenoise_shape(k, W, H):
+    n = A.VDENOISE_PLANES[k]
+    return (H, W, n) if n else (H, W)
+
+
+def _vdenoise_inputs(guides, color, moments, history):
+    """The desc's input planes by name and the frame's size."""
+    planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
+    if "normal" not in planes or "point" not in planes:
+        raise ValueError("guides must hold the normal and point planes of render_gbuffer")
+    if (moments is None) != (history is None):
+        raise ValueError("moments and history go together")
+    if moments is not None:
+        planes.update(moments=moments, history=history)
+    if color is not None:
+        planes["color"] = color
+    H, W = (int(v) for v in np.shape(planes["normal"])[:2])
+    return planes, W, H
+
+
+def _vdenoise_desc(W, H, iterations=1, sigma_luminance=VDENOISE_SIGMA_LUMINANCE, sigma_normal=DENOISE_SIGMA_NORMAL,
+                   sigma_point=DENOISE_SIGMA_POINT, min_history=VDENOISE_MIN_HISTORY):
+    return A.VDenoiseDesc(struct_bytes=C.sizeof(A.VDenoiseDesc), width=W, height=H, iterations=int(iterations),
+                          sigma_luminance=float(sigma_luminance), sigma_normal=float(sigma_normal), sigma_point=float(sigma_point),
+                          min_history=float(min_history))
+
+
+def _vdenoise_numpy(d, W, H, planes, outs):
+    """Points the desc at contiguous float32 copies of the numpy inputs (or the arrays themselves) and at the outputs
+    (None: not asked for; True: a new array); returns what must stay alive and the outputs by name."""
+    keep = {}
+    for k, v in planes.items():
+        a = np.ascontiguousarray(v, np.float32)
+        if a.shape != _vdenoise_shape(k, W, H):
+            raise ValueError(f"plane {k} must have shape {_vdenoise_shape(k, W, H)}, not {a.shape}")
+        keep[k] = a
+        setattr(d, k, a.ctypes.data)
+    res = {}
+    for k, v in outs.items():
+        if v is None or v is False:
+            res[k] = None
+            continue
+        if v is True:
+            v = np.zeros(_vdenoise_shape(k, W, H), np.float32)
+        elif not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.shape == _vdenoise_shape(k, W, H) and v.flags.c_contiguous
+                  and v.flags.writeable):
+            raise ValueError(f"{k} must be a writeable contiguous float32 array of shape {_vdenoise_shape(k, W, H)}")
+        res[k] = v
+        setattr(d, k, v.ctypes.data)
+    return keep, res
+
+
+def _vdenoise_result(res):
+    return res["out"] if res.get("out_variance") is None else (res["out"], res["out_variance"])
+
+
+def denoise_variance_host(guides, color, iterations=3, sigma_luminance=VDENOISE_SIGMA_LUMINANCE, sigma_normal=DENOISE_SIGMA_NORMAL,
+                          sigma_point=DENOISE_SIGMA_POINT, moments=None, history=None, min_history=VDENOISE_MIN_HISTORY, out=None,
+                          out_variance=None):
+    """rt_denoise_variance_host: the variance-guided denoiser's definition on the CPU (no device), with
+    RayTracer.denoise_variance's arguments for numpy planes.  RayTracer.denoise_variance computes the same bits on the GPU."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    planes, W, H = _vdenoise_inputs(guides, color, moments, history)
+    d = _vdenoise_desc(W, H, iterations, sigma_luminance, sigma_normal, sigma_point, min_history)
+    keep, res = _vdenoise_numpy(d, W, H, planes, {"out": True if out is None else out, "out_variance": out_variance})
+    L = load()
+    rc = L.rt_denoise_variance_host(C.byref(d))
+    del keep
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+    return _vdenoise_result(res)
+
+
+def luminance_moments_host(guides, color, out=None):
+    """rt_luminance_moments_host: RayTracer.luminance_moments on the CPU (no device), for numpy planes."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    planes, W, H = _vdenoise_inputs(guides, color, None, None)
+    d = _vdenoise_desc(W, H)
+    keep, res = _vdenoise_numpy(d, W, H, planes, {"out": True if out is None else out})
+    L = load()
+    rc = L.rt_luminance_moments_host(C.byref(d))
+    del keep
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+    return res["out"]
+
+
 class RayTracer:
     def __init__(self, device=0, max_width=1920, max_height=1080, lib=None):
         self._L = lib or load()   # (lib=load_test(): a handle of the test library, for the rt_test_* entry points)
@@ -556,6 +651,71 @@ class RayTracer:
         self._check(self._L.rt_denoise(self._h, C.byref(d), 0))
         cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
         return out
+
+    def _vdenoise_call(self, fn, d, W, H, planes, outs):
+        """rt_denoise_variance / rt_luminance_moments (`fn`: the name) on numpy planes (synchronous) or on torch tensors of this
+        handle's device (asynchronous, ordered after the current torch stream's work); outs: name -> None (not asked
+        for), True (a new one) or the array / tensor to fill."""
+        if not any(hasattr(v, "data_ptr") for v in (*planes.values(), *outs.values())):
+            if "color" not in planes:
+                raise ValueError("color is required with numpy planes (color=None names the device image)")
+            keep, res = _vdenoise_numpy(d, W, H, planes, outs)
+            self._check(getattr(self._L, fn)(self._h, C.byref(d), A.VDENOISE_HOST_MEMORY))
+            del keep
+            return res
+        import torch
+        dev = torch.device("cuda", self.device)
+        given = dict(planes, **{k: v for k, v in outs.items() if v is not None and v is not True and v is not False})
+        for k, v in given.items():
+            if not isinstance(v, torch.Tensor):
+                raise ValueError("mix of device tensors and host arrays")
+            if v.device.type != "cuda" or v.device.index != self.device:
+                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
+            if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != _vdenoise_shape(k, W, H):
+                raise ValueError(f"plane {k} must be a contiguous float32 tensor of shape {_vdenoise_shape(k, W, H)}")
+        res = {}
+        for k, v in outs.items():
+            if v is True:
+                v = given[k] = torch.empty(_vdenoise_shape(k, W, H), dtype=torch.float32, device=dev)
+            res[k] = None if v is None or v is False else v
+        for k, v in given.items():
+            setattr(d, k, v.data_ptr())
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
+        ext.wait_stream(cur)
+        self._check(getattr(self._L, fn)(self._h, C.byref(d), 0))
+        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
+        return res
+
+    def denoise_variance(self, guides, color=None, iterations=3, sigma_luminance=VDENOISE_SIGMA_LUMINANCE,
+                         sigma_normal=DENOISE_SIGMA_NORMAL, sigma_point=DENOISE_SIGMA_POINT, moments=None, history=None,
+                         min_history=VDENOISE_MIN_HISTORY, out=None, out_variance=None):
+        """The variance-guided a-trous filter (rt_denoise_variance; include/rt_abi.h has the definition) of the (H, W, 4)
+        float32 frame `color`: denoise's filter with the luminance edge term measured in standard deviations of each
+        texel's own noise, so that a frame with a long history is blurred less than a lone one.  `guides`: as for denoise.
+        `moments` (H, W, 4) / `history` (H, W): the luminance moments of the frames behind `color` -- luminance_moments
+        of each raw frame, accumulated by a temporal_accumulate call of their own -- and the frames accumulated in them;
+        where history < min_history, or without them, the variance comes from a 7 x 7 window of the frame itself.
+        `sigma_luminance`: the luminance difference, in standard deviations, that costs a tap a factor e.
+        `out_variance`: True, or an (H, W) array / tensor to fill, for the variance left in the filtered frame; the call then
+        returns (out, out_variance).
+        numpy planes: a synchronous call that returns numpy (`out`, when given: it may be `color`).  Torch tensors on this
+        handle's device: an asynchronous call ordered after the current torch stream's work; returns tensors; there
+        color=None denoises the handle's image."""
+        planes, W, H = _vdenoise_inputs(guides, color, moments, history)
+        d = _vdenoise_desc(W, H, iterations, sigma_luminance, sigma_normal, sigma_point, min_history)
+        res = self._vdenoise_call("rt_denoise_variance", d, W, H, planes,
+                                  {"out": True if out is None else out, "out_variance": out_variance})
+        return _vdenoise_result(res)
+
+    def luminance_moments(self, guides, color=None, out=None):
+        """The per-frame sample of the luminance moments (rt_luminance_moments): (l, l l, 0, 0) per filterable texel of
+        the frame `color`, l the luminance of colour / albedo, and zeros elsewhere, as an (H, W, 4) float32 array or
+        tensor.  Accumulated over frames by temporal_accumulate (color = this, prev_color = the accumulated moments), it
+        is what denoise_variance takes as `moments`.  numpy planes or torch tensors, as denoise_variance."""
+        planes, W, H = _vdenoise_inputs(guides, color, None, None)
+        res = self._vdenoise_call("rt_luminance_moments", _vdenoise_desc(W, H), W, H, planes, {"out": True if out is None else out})
+        return res["out"]
 
     def temporal_accumulate(self, guides, prev_guides, prev_camera, prev_color, prev_history, color=None, max_history=float("inf"),
                             point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,

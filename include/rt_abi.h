@@ -799,6 +799,105 @@ enum { RT_VDENOISE_HOST_MEMORY = 1 };
 int rt_denoise_variance(rt_handle* h, const rt_vdenoise_desc* desc, int flags);
 int rt_luminance_moments(rt_handle* h, const rt_vdenoise_desc* desc, int flags);
 
+/* Adaptive sampling: the link from rt_denoise_variance's out_variance back to the sampler.
+ * rt_adaptive_plan apportions a budget of rays over the texels of a frame in proportion to their standard deviation and
+ * writes the chosen texels' rays as one compacted rt_path_ray list; rt_radiance_rays traces that list; rt_adaptive_merge
+ * blends the traced samples into the accumulation.  Frames are width x height, row 0 = bottom, tightly packed; texel
+ * p = (x, y) has index y * width + x, "row-major order" below.
+ *
+ * rt_adaptive_plan.  Everything after the quantisation is integer arithmetic; the one float step is binary32, unfused.
+ *   M = the largest variance(p) over the texels whose variance is finite and > 0 (as floats, which for these values is
+ *   the order of their bit patterns as u32).
+ *   q(p) = (u32)((sqrt_(variance(p)) / sqrt_(M)) * 1048576.0f), truncating, for a texel with a finite variance > 0, and
+ *   0 for every other texel (0, negative, NaN, infinite) -- all of them when there is no M.  sqrt_ and the division are
+ *   correctly rounded (csrc/rt_transc.h), so q <= 2^20.
+ *   C(p) = the exclusive prefix sum of q in row-major order (u64); S = the sum of all q;
+ *   R = budget - min_samples * width * height;  F(c) = floor(c * R / S) exactly (a 128-bit product: mul_div_floor of
+ *   csrc/rt_adaptive.h);  e(p) = F(C(p) + q(p)) - F(C(p)), and 0 when S = 0;  n(p) = min(min_samples + e(p), max_samples).
+ *   That is largest-remainder apportionment with the rounding error carried along the scan order: before the clamp the
+ *   e(p) sum to R exactly (to 0 when S = 0).  What max_samples removes stays unspent (it is not redistributed).
+ *   counts(p) = n(p);  offsets(p) = the exclusive row-major prefix sum of n;
+ *   totals = { sum of n (<= budget), texels with n > min_samples, texels with min_samples + e > max_samples, 0 }.
+ *   For k < n(p), rays[offsets(p) + k] = { origin, seed = (y * width + x) + (first_frame + k) * 719393 in u32 arithmetic
+ *   (the seed of pixel p in frame first_frame + k, wgsl:475), dir(p) bit for bit, _p0 = 0 }.
+ *   rays[totals[0] .. budget) are 32 zero bytes each: rt_radiance_rays answers a zero direction with (0, 0, 0, 0) and no
+ *   work, so a caller traces `budget` rays without reading the total back.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle / desc / plane, struct_bytes, _p0 or _p1 != 0, unknown
+ * flags, zero width or height, budget outside 1 .. 2^31 - 1, max_samples outside 1 .. 65535, min_samples > max_samples,
+ * min_samples * width * height > budget, misaligned device planes), RT_ERR_CAPACITY (width * height > 2^31 - 1),
+ * RT_ERR_OUT_OF_MEMORY.
+ *
+ * rt_adaptive_merge.  One texel at a time, binary32, unfused, two products and then the sum (wgsl:156-157):
+ *   acc = color(p) (four components), hl = history(p), m = moments(p).  If hl is not finite, hl < 1, or some component of
+ *   color(p) is not finite there is no prior: hl = 0.
+ *   For k = 0 .. counts(p) - 1 in order, with c = radiance[offsets(p) + k] (a record at or past `budget` ends the texel's
+ *   samples: no read leaves the list) and, with moments, l = l(c.rgb / a'(p)) (rt_denoise_variance's l, rt_denoise's a';
+ *   a' = 1 with a NULL albedo):
+ *     some component of c not finite: the sample is dropped;
+ *     otherwise, hl = 0:  acc = c bit for bit, m = (l, l l, 0, 0), hl = 1;
+ *     otherwise:  n_c = hl < max_history ? hl : max_history;  w = 1 / (n_c + 1);  acc = acc * (1 - w) + c * w and
+ *     m = m * (1 - w) + (l, l l, 0, 0) * w on four components each;  hl = n_c + 1.
+ *   out(p) = acc, out_history(p) = hl, out_moments(p) = m -- and with hl still 0 (no prior and no valid sample)
+ *   out(p) = color(p) bit for bit, out_history(p) = 0, out_moments(p) = moments(p).
+ * A ray record is one unit of history whatever rays_per_pixel traced it with, as a frame is for rt_render.
+ * Consequence: with min_samples = max_samples = N, budget = N * width * height, first_frame = 0, history 0,
+ * max_history = +INF and a camera without jitter, plan -> rt_radiance_rays -> merge leaves what rt_render leaves after
+ * frames 0 .. N - 1, bit for bit, alpha included.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle / desc / radiance / counts / offsets / history / out /
+ * out_history, a null color on the host or with the flag, moments without out_moments or the reverse, struct_bytes,
+ * _p0 != 0, unknown flags, zero width or height, budget outside 1 .. 2^31 - 1, max_history NaN or below 1, misaligned
+ * device planes), RT_ERR_CAPACITY (width * height > 2^31 - 1, or more texels than the image has with a NULL color),
+ * RT_ERR_OUT_OF_MEMORY.
+ *
+ * Both: the _host forms (section 3) are these definitions over host pointers, without a device; the device calls compute
+ * the same bits.  Without the HOST_MEMORY flag the planes are device pointers on the handle's device (4-byte aligned; 16
+ * for rays, radiance, color, albedo, moments, out and out_moments) and the call is asynchronous on the handle's stream,
+ * after every earlier call on the handle and before every later one; merge's `color` may be NULL for the handle's image,
+ * and out / out_history / out_moments may be color / history / moments (or `out` the image); any other overlap is
+ * undefined.  With the flag they are host pointers, staged whole through one temporary device buffer that is counted
+ * against option "max_device_mb" while held, and the call returns when the outputs are on the host.  The plan keeps 32
+ * bytes of scratch per 1024 texels (the block sums of its two scans) on the handle, grown on demand, counted by
+ * rt_last_launch out[4] and bounded by "max_device_mb".  No scene is needed.  Like the denoisers the calls leave the image
+ * (unless `out` is the image), the primary tables, a frame_ahead batch in flight, the pipeline slots, rt_get_stats and
+ * the launch words of rt_last_launch as they are. */
+typedef struct rt_adaptive_plan_desc {
+    uint32_t        struct_bytes;   /* = sizeof(rt_adaptive_plan_desc) */
+    uint32_t        _p0;            /* must be 0 */
+    uint32_t        width, height;
+    uint32_t        budget;         /* 1 .. 2^31 - 1: the number of records in `rays` */
+    uint32_t        min_samples;    /* <= max_samples */
+    uint32_t        max_samples;    /* 1 .. 65535 */
+    uint32_t        first_frame;    /* the seed frame of a texel's sample 0 */
+    float           origin[3];      /* the origin of every ray */
+    uint32_t        _p1;            /* must be 0 */
+    const float*    variance;       /* [h][w] */
+    const float*    dir;            /* [h][w][3]: rt_render_gbuffer's `dir` plane */
+    uint32_t*       counts;         /* [h][w] out */
+    uint32_t*       offsets;        /* [h][w] out */
+    rt_path_ray*    rays;           /* [budget] out */
+    uint32_t*       totals;         /* [4] out */
+} rt_adaptive_plan_desc;
+typedef struct rt_adaptive_merge_desc {
+    uint32_t        struct_bytes;   /* = sizeof(rt_adaptive_merge_desc) */
+    uint32_t        _p0;            /* must be 0 */
+    uint32_t        width, height;
+    uint32_t        budget;         /* 1 .. 2^31 - 1: the number of records in `radiance` */
+    float           max_history;    /* >= 1, may be +INF */
+    const float*    radiance;       /* [budget][4]: what rt_radiance_rays wrote for the plan's rays */
+    const uint32_t* counts;         /* [h][w] the plan's */
+    const uint32_t* offsets;        /* [h][w] the plan's */
+    const float*    color;          /* [h][w][4]; device path: NULL = the handle's image */
+    const float*    history;        /* [h][w] */
+    const float*    albedo;         /* [h][w][4] or NULL */
+    const float*    moments;        /* [h][w][4] or NULL */
+    float*          out;            /* [h][w][4]; may be `color` */
+    float*          out_history;    /* [h][w]; may be `history` */
+    float*          out_moments;    /* [h][w][4], given exactly when `moments` is; may be `moments` */
+} rt_adaptive_merge_desc;
+enum { RT_ADAPTIVE_HOST_MEMORY = 1 };
+int rt_adaptive_plan(rt_handle* h, const rt_adaptive_plan_desc* desc, int flags);
+int rt_adaptive_merge(rt_handle* h, const rt_adaptive_merge_desc* desc, int flags);
+
 /* The test-only entry points (rt_test_*: the kernels' arithmetic building blocks evaluated element-wise on the device, raw
  * copies of sequence buffers, the RCCL gather against a stub, the frame_ahead policy) are NOT exported by the product
  * library: include/rt_test_abi.h declares them and ray_tracer_2_amd/librt2_mi355x_test.so -- the same sources compiled
@@ -948,6 +1047,12 @@ int rt_temporal_accumulate_host(const rt_temporal_desc* desc);
  * rt_last_error(NULL); RT_ERR_OUT_OF_MEMORY when the host has no room for the working memory. */
 int rt_denoise_variance_host(const rt_vdenoise_desc* desc);
 int rt_luminance_moments_host(const rt_vdenoise_desc* desc);
+
+/* Adaptive sampling's definitions (section 2: rt_adaptive_plan, rt_adaptive_merge) in executable form: plain C++ over host
+ * pointers, no device, no working memory.  merge's `color` is required.  The same argument errors as the device entry
+ * points (no handle, no flags, no alignment rule), nothing written on an error, the reason in rt_last_error(NULL). */
+int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc);
+int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc);
 
 #ifdef __cplusplus
 }

@@ -132,6 +132,29 @@ VDENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission":
 VDENOISE_HOST_MEMORY = 1
 
 
+class AdaptivePlanDesc(C.Structure):  # rt_adaptive_plan_desc: a variance plane and a ray budget for rt_adaptive_plan / rt_adaptive_plan_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("budget", u32), ("min_samples", u32),
+                ("max_samples", u32), ("first_frame", u32), ("origin", f32 * 3), ("_p1", u32), ("variance", C.c_void_p),
+                ("dir", C.c_void_p), ("counts", C.c_void_p), ("offsets", C.c_void_p), ("rays", C.c_void_p),
+                ("totals", C.c_void_p)]
+
+
+class AdaptiveMergeDesc(C.Structure):  # rt_adaptive_merge_desc: the traced samples and the accumulation for rt_adaptive_merge / rt_adaptive_merge_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("budget", u32), ("max_history", f32),
+                ("radiance", C.c_void_p), ("counts", C.c_void_p), ("offsets", C.c_void_p), ("color", C.c_void_p),
+                ("history", C.c_void_p), ("albedo", C.c_void_p), ("moments", C.c_void_p), ("out", C.c_void_p),
+                ("out_history", C.c_void_p), ("out_moments", C.c_void_p)]
+
+
+# frame-shaped plane of the two descs -> (numpy dtype, components per texel; 0: a plane of shape (H, W)); `rays`
+# ((budget,) PATH_RAY_DTYPE), `totals` ((4,) uint32) and `radiance` ((budget, 4) float32) are not frame-shaped
+ADAPTIVE_PLAN_PLANES = {"variance": ("<f4", 0), "dir": ("<f4", 3), "counts": ("<u4", 0), "offsets": ("<u4", 0)}
+ADAPTIVE_MERGE_PLANES = {"counts": ("<u4", 0), "offsets": ("<u4", 0), "color": ("<f4", 4), "history": ("<f4", 0),
+                         "albedo": ("<f4", 4), "moments": ("<f4", 4), "out": ("<f4", 4), "out_history": ("<f4", 0),
+                         "out_moments": ("<f4", 4)}
+ADAPTIVE_HOST_MEMORY = 1
+
+
 class TemporalDesc(C.Structure):  # rt_temporal_desc: two frames for rt_temporal_accumulate / rt_temporal_accumulate_host
     _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("prev_camera", CameraUniform),
                 ("max_history", f32), ("point_tolerance", f32), ("normal_cos", f32), ("color", C.c_void_p),

@@ -25,6 +25,7 @@
 #include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
 #include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
 #include "rt_vdenoise_api.h"  // (the variance-guided denoiser: its argument rules and host restatement, host/vdenoise.cpp; its launches, rt_vdenoise.hip)
+#include "rt_adaptive_api.h"  // (adaptive sampling: its argument rules and host restatement, host/adaptive.cpp; its launches, rt_adaptive.hip)
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
 #ifndef RT_TEST_ENTRIES
 #define RT_TEST_ENTRIES 0
@@ -70,6 +71,8 @@ hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
 hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
+hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
+hipError_t launch_adaptive_merge(const AdaptiveMergeArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -192,6 +195,9 @@ struct rt_handle {
     // rt_denoise: per texel a guide record of two float4 and two colour images of one float4 each (64 B), kept between calls
     float4* denoise_scratch = nullptr;
     size_t denoise_texels = 0;
+    // rt_adaptive_plan: the block sums of its two scans and a few words (rt_adaptive_api.h), kept between calls
+    void* adaptive_scratch = nullptr;
+    size_t adaptive_scratch_bytes = 0;
     hipStream_t copy_stream = nullptr;
     hipEvent_t snapshot_taken = nullptr, snapshot_read = nullptr;
     bool snapshot_read_pending = false;                // a read of the staging buffer was queued since the last snapshot
@@ -309,7 +315,7 @@ int fail(rt_handle* h, int code, const std::string& msg) {
 size_t optional_bytes(const rt_handle* h) {
     size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary.texels * 64u +
                2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity +
-               h->denoise_texels * 64u;
+               h->denoise_texels * 64u + h->adaptive_scratch_bytes;
     for (const PipeSlot& ps : h->pipe) {
         if (ps.scratch) b += h->pipe_scratch_texels * sizeof(float4);
         b += ps.memo_words * sizeof(uint32_t) + ps.primary.texels * 64u;
@@ -525,6 +531,7 @@ void rt_destroy(rt_handle* h) {
     if (h->snapshot_read) (void)hipEventDestroy(h->snapshot_read);
     free_dev(h->snapshot);
     free_dev(h->denoise_scratch);
+    free_dev(h->adaptive_scratch);
     free_dev(h->wf_state);
     free_dev(h->wf_hit);
     free_dev(h->wf_lists);
@@ -2502,6 +2509,149 @@ static int vdenoise_call(rt_handle* h, const rt_vdenoise_desc* desc, int flags, 
 
 int rt_denoise_variance(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, false); }
 int rt_luminance_moments(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, true); }
+
+// ---- adaptive sampling (include/rt_abi.h: rt_adaptive_plan, rt_adaptive_merge and their _host forms; rt_adaptive.hip;
+// host/adaptive.cpp) ----
+// Launched like the denoisers: nothing read but the caller's planes (or the image) and nothing written but the caller's
+// outputs and, by the plan, the handle's adaptive scratch.
+int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc) {
+    std::string err;
+    const int rc = rt2::adaptive_plan_host(desc, err);
+    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+}
+
+int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) {
+    std::string err;
+    const int rc = rt2::adaptive_merge_host(desc, err);
+    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
+}
+
+int rt_adaptive_plan(rt_handle* h, const rt_adaptive_plan_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_ADAPTIVE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_ADAPTIVE_HOST_MEMORY) != 0;
+    {
+        std::string err;
+        if (const int rc = rt2::adaptive_plan_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    }
+    const size_t texels = (size_t)desc->width * desc->height, budget = desc->budget;
+    HIP_TRY(h, hipSetDevice(h->device));
+    // the planes of the host-memory path, in staging order: variance, dir, counts, offsets, rays, totals
+    static const char* const what_for = "the adaptive plan's staging planes";
+    const size_t bytes[6] = {texels * 4u, texels * 12u, texels * 4u, texels * 4u, budget * sizeof(rt_path_ray), 16u};
+    size_t plane_off[6] = {}, staging = 0;
+    if (host)
+        for (int c = 0; c < 6; ++c) {
+            plane_off[c] = staging;
+            staging = (staging + bytes[c] + 255u) & ~(size_t)255u;
+        }
+    // the scratch: grown on demand, within option max_device_mb
+    const size_t need = adaptive_scratch_bytes(texels);
+    if (h->adaptive_scratch_bytes < need) {
+        if (!fits_cap(h, need + staging, h->adaptive_scratch_bytes))
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the adaptive plan's scratch");
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
+        free_dev(h->adaptive_scratch);
+        h->adaptive_scratch_bytes = 0;
+        const hipError_t e = hipMalloc(&h->adaptive_scratch, need);
+        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the adaptive plan's scratch");
+        HIP_TRY(h, e);
+        h->adaptive_scratch_bytes = need;
+    } else if (!fits_cap(h, staging)) {
+        return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("option max_device_mb leaves no room for ") + what_for);
+    }
+    AdaptivePlanArgs a{};
+    a.width = desc->width; a.height = desc->height; a.budget = desc->budget;
+    a.min_samples = desc->min_samples; a.max_samples = desc->max_samples; a.first_frame = desc->first_frame;
+    for (int k = 0; k < 3; ++k) a.origin[k] = desc->origin[k];
+    a.scratch = h->adaptive_scratch;
+    if (!host) {
+        a.variance = desc->variance; a.dir = desc->dir; a.counts = desc->counts; a.offsets = desc->offsets;
+        a.rays = desc->rays; a.totals = desc->totals;
+        HIP_TRY(h, launch_adaptive_plan(a, h->stream));
+        return RT_OK;
+    }
+    // host memory: every plane whole through one temporary device buffer, each at a multiple of 256 bytes
+    return staged_chunks(h, staging, 1, 1, what_for, [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
+        hipError_t e = hipSuccess;
+        what = "hipMemcpyAsync";
+        if ((e = hipMemcpyAsync(buf + plane_off[0], desc->variance, bytes[0], hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(buf + plane_off[1], desc->dir, bytes[1], hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+        a.variance = reinterpret_cast<const float*>(buf + plane_off[0]);
+        a.dir = reinterpret_cast<const float*>(buf + plane_off[1]);
+        a.counts = reinterpret_cast<uint32_t*>(buf + plane_off[2]);
+        a.offsets = reinterpret_cast<uint32_t*>(buf + plane_off[3]);
+        a.rays = buf + plane_off[4];
+        a.totals = reinterpret_cast<uint32_t*>(buf + plane_off[5]);
+        if (what = "launch_adaptive_plan", (e = launch_adaptive_plan(a, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        void* const dst[4] = {desc->counts, desc->offsets, desc->rays, desc->totals};
+        for (int c = 0; c < 4 && e == hipSuccess; ++c)
+            e = hipMemcpyAsync(dst[c], buf + plane_off[2 + c], bytes[2 + c], hipMemcpyDeviceToHost, h->stream);
+        return e;
+    });
+}
+
+int rt_adaptive_merge(rt_handle* h, const rt_adaptive_merge_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_ADAPTIVE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_ADAPTIVE_HOST_MEMORY) != 0;
+    {
+        std::string err;
+        if (const int rc = rt2::adaptive_merge_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    }
+    const size_t texels = (size_t)desc->width * desc->height, budget = desc->budget;
+    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    AdaptiveMergeArgs a{};
+    a.width = desc->width; a.height = desc->height; a.budget = desc->budget; a.max_history = desc->max_history;
+    if (!host) {
+        const float* image = reinterpret_cast<const float*>(h->image);
+        a.radiance = desc->radiance; a.counts = desc->counts; a.offsets = desc->offsets;
+        a.color = desc->color ? desc->color : image;
+        a.history = desc->history; a.albedo = desc->albedo; a.moments = desc->moments;
+        a.out = desc->out; a.out_history = desc->out_history; a.out_moments = desc->out_moments;
+        const bool out_is_image = desc->out >= image && desc->out < image + 4 * h->image_texels;
+        if (a.color == image || out_is_image) {
+            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+        }
+        if (out_is_image) h->generation += 1;   // (the image changes, as by rt_write_image)
+        HIP_TRY(h, launch_adaptive_merge(a, h->stream));
+        return RT_OK;
+    }
+    // host memory: every plane whole through one temporary device buffer, each at a multiple of 256 bytes; the outputs take
+    // the places of color, history and moments
+    const void* const src[7] = {desc->radiance, desc->counts, desc->offsets, desc->color, desc->history, desc->albedo, desc->moments};
+    const size_t bytes[7] = {budget * 16u, texels * 4u, texels * 4u, texels * 16u, texels * 4u, texels * 16u, texels * 16u};
+    size_t plane_off[7] = {}, staging = 0;
+    for (int c = 0; c < 7; ++c) {
+        if (!src[c]) continue;
+        plane_off[c] = staging;
+        staging = (staging + bytes[c] + 255u) & ~(size_t)255u;
+    }
+    if (!fits_cap(h, staging)) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the adaptive merge's staging planes");
+    return staged_chunks(h, staging, 1, 1, "the adaptive merge's staging planes", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
+        hipError_t e = hipSuccess;
+        what = "hipMemcpyAsync";
+        void* d_ptr[7] = {};
+        for (int c = 0; c < 7 && e == hipSuccess; ++c) {
+            if (!src[c]) continue;
+            d_ptr[c] = buf + plane_off[c];
+            e = hipMemcpyAsync(d_ptr[c], src[c], bytes[c], hipMemcpyHostToDevice, h->stream);
+        }
+        if (e != hipSuccess) return e;
+        a.radiance = (const float*)d_ptr[0]; a.counts = (const uint32_t*)d_ptr[1]; a.offsets = (const uint32_t*)d_ptr[2];
+        a.color = (const float*)d_ptr[3]; a.history = (const float*)d_ptr[4]; a.albedo = (const float*)d_ptr[5];
+        a.moments = (const float*)d_ptr[6];
+        a.out = (float*)d_ptr[3]; a.out_history = (float*)d_ptr[4]; a.out_moments = (float*)d_ptr[6];
+        if (what = "launch_adaptive_merge", (e = launch_adaptive_merge(a, h->stream)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        if ((e = hipMemcpyAsync(desc->out, a.out, bytes[3], hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(desc->out_history, a.out_history, bytes[4], hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
+        if (desc->out_moments) e = hipMemcpyAsync(desc->out_moments, a.out_moments, bytes[6], hipMemcpyDeviceToHost, h->stream);
+        return e;
+    });
+}
 
 // ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate, rt_temporal_accumulate_host; rt_temporal.hip;
 // host/temporal.cpp) ----

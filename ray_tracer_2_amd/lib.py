@@ -31,6 +31,7 @@ EXPORTS = [
     "rt_intersect_rays", "rt_occluded_rays", "rt_pick", "rt_render_gbuffer", "rt_radiance_rays",
     "rt_denoise", "rt_denoise_host", "rt_temporal_accumulate", "rt_temporal_accumulate_host",
     "rt_denoise_variance", "rt_luminance_moments", "rt_denoise_variance_host", "rt_luminance_moments_host",
+    "rt_adaptive_plan", "rt_adaptive_merge", "rt_adaptive_plan_host", "rt_adaptive_merge_host",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
     "rt_scene_set_sphere",
     "rt_refit_bvh", "rt_refit_triangles", "rt_refit_built_scene", "rt_scene_set_mesh_vertices", "rt_scene_triangle_order",
@@ -154,6 +155,10 @@ def _bind(L, with_test_entries):
         "rt_luminance_moments": (i32, [vp, P(A.VDenoiseDesc), i32]),
         "rt_denoise_variance_host": (i32, [P(A.VDenoiseDesc)]),
         "rt_luminance_moments_host": (i32, [P(A.VDenoiseDesc)]),
+        "rt_adaptive_plan": (i32, [vp, P(A.AdaptivePlanDesc), i32]),
+        "rt_adaptive_merge": (i32, [vp, P(A.AdaptiveMergeDesc), i32]),
+        "rt_adaptive_plan_host": (i32, [P(A.AdaptivePlanDesc)]),
+        "rt_adaptive_merge_host": (i32, [P(A.AdaptiveMergeDesc)]),
         "rt_update_instances": (i32, [vp, P(A.SceneUniform), vp, u32, vp, u32]),
         "rt_update_built_scene": (i32, [vp, vp]),
         "rt_scene_set_mesh_transform": (i32, [vp, u32, P(A.Transform)]),

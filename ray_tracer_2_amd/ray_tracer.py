@@ -253,6 +253,133 @@ def luminance_moments_host(guides, color, out=None):
     return res["out"]
 
 
+# Adaptive sampling's defaults (RayTracer.adaptive_plan / adaptive_samples, adaptive_plan_host): every texel gets at least
+# one new sample, so that its variance estimate keeps moving, and at most 16, so that one firefly cannot take the budget.
+ADAPTIVE_MIN_SAMPLES, ADAPTIVE_MAX_SAMPLES = 1, 16
+
+
+def _adaptive_shape(planes, k, W, H):
+    n = planes[k][1]
+    return (H, W, n) if n else (H, W)
+
+
+def _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame):
+    budget, min_samples, max_samples, first_frame = int(budget), int(min_samples), int(max_samples), int(first_frame)
+    if not 1 <= budget <= 0x7fffffff:
+        raise ValueError("budget must be 1 .. 2^31 - 1")
+    if min_samples < 0 or max_samples < 0 or not 0 <= first_frame <= 0xffffffff:
+        raise ValueError("min_samples, max_samples and first_frame must fit a uint32")
+    o = np.asarray(origin, np.float32).reshape(-1)
+    if o.shape != (3,):
+        raise ValueError("origin must have three components")
+    return A.AdaptivePlanDesc(struct_bytes=C.sizeof(A.AdaptivePlanDesc), width=W, height=H, budget=budget, min_samples=min_samples,
+                              max_samples=max_samples, first_frame=first_frame, origin=(C.c_float * 3)(*o.tolist()))
+
+
+def _adaptive_merge_desc(W, H, budget, max_history):
+    budget = int(budget)
+    if not 1 <= budget <= 0x7fffffff:
+        raise ValueError("budget must be 1 .. 2^31 - 1")
+    return A.AdaptiveMergeDesc(struct_bytes=C.sizeof(A.AdaptiveMergeDesc), width=W, height=H, budget=budget, max_history=float(max_history))
+
+
+def _adaptive_numpy_inputs(d, table, W, H, planes):
+    """Points the desc at contiguous copies of the numpy inputs (or the arrays themselves); returns what must stay alive."""
+    keep = {}
+    for k, v in planes.items():
+        a = np.ascontiguousarray(v, np.dtype(table[k][0]))
+        if a.shape != _adaptive_shape(table, k, W, H):
+            raise ValueError(f"plane {k} must have shape {_adaptive_shape(table, k, W, H)}, not {a.shape}")
+        keep[k] = a
+        setattr(d, k, a.ctypes.data)
+    return keep
+
+
+def _adaptive_numpy_outputs(d, table, W, H, outs):
+    """outs: name -> None (a new array) or the array to fill; returns the arrays by name."""
+    res = {}
+    for k, v in outs.items():
+        shape, dt = _adaptive_shape(table, k, W, H), np.dtype(table[k][0])
+        if v is None:
+            v = np.zeros(shape, dt)
+        elif not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous and v.flags.writeable):
+            raise ValueError(f"{k} must be a writeable contiguous {dt} array of shape {shape}")
+        res[k] = v
+        setattr(d, k, v.ctypes.data)
+    return res
+
+
+def _adaptive_plan_numpy(d, W, H, variance, dirs):
+    keep = _adaptive_numpy_inputs(d, A.ADAPTIVE_PLAN_PLANES, W, H, {"variance": variance, "dir": dirs})
+    res = _adaptive_numpy_outputs(d, A.ADAPTIVE_PLAN_PLANES, W, H, {"counts": None, "offsets": None})
+    res["rays"] = np.zeros(d.budget, A.PATH_RAY_DTYPE)
+    res["totals"] = np.zeros(4, np.uint32)
+    d.rays, d.totals = res["rays"].ctypes.data, res["totals"].ctypes.data
+    return keep, res
+
+
+def _adaptive_merge_numpy(d, W, H, radiance, planes, outs):
+    r = np.ascontiguousarray(radiance, np.float32)
+    if r.shape != (d.budget, 4):
+        raise ValueError(f"radiance must have shape {(d.budget, 4)}, not {r.shape}")
+    d.radiance = r.ctypes.data
+    keep = _adaptive_numpy_inputs(d, A.ADAPTIVE_MERGE_PLANES, W, H, planes)
+    keep["radiance"] = r
+    return keep, _adaptive_numpy_outputs(d, A.ADAPTIVE_MERGE_PLANES, W, H, outs)
+
+
+def _adaptive_merge_planes(counts, offsets, color, history, albedo, moments, out, out_history, out_moments):
+    """The merge's inputs and outputs by name, and the frame's size (from `counts`)."""
+    if moments is None and out_moments is not None:
+        raise ValueError("out_moments needs moments")
+    planes = {"counts": counts, "offsets": offsets, "history": history}
+    for k, v in (("color", color), ("albedo", albedo), ("moments", moments)):
+        if v is not None:
+            planes[k] = v
+    outs = {"out": out, "out_history": out_history}
+    if moments is not None:
+        outs["out_moments"] = out_moments
+    H, W = (int(v) for v in np.shape(counts)[:2]) if np.ndim(counts) == 2 else (0, 0)
+    if W == 0 or H == 0:
+        raise ValueError("counts must have shape (H, W)")
+    return planes, outs, W, H
+
+
+def _adaptive_merge_result(res):
+    return (res["out"], res["out_history"]) + ((res["out_moments"],) if "out_moments" in res else ())
+
+
+def adaptive_plan_host(variance, dirs, origin, budget, min_samples=ADAPTIVE_MIN_SAMPLES, max_samples=ADAPTIVE_MAX_SAMPLES, first_frame=0):
+    """rt_adaptive_plan_host: the plan's definition on the CPU (no device), with RayTracer.adaptive_plan's arguments for numpy
+    planes.  RayTracer.adaptive_plan computes the same bits on the GPU."""
+    H, W = (int(v) for v in np.shape(variance)) if np.ndim(variance) == 2 else (0, 0)
+    d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
+    keep, res = _adaptive_plan_numpy(d, W, H, variance, dirs)
+    L = load()
+    rc = L.rt_adaptive_plan_host(C.byref(d))
+    del keep
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+    return res["counts"], res["offsets"], res["rays"], res["totals"]
+
+
+def adaptive_merge_host(radiance, counts, offsets, color, history, max_history=float("inf"), albedo=None, moments=None, out=None,
+                        out_history=None, out_moments=None):
+    """rt_adaptive_merge_host: the merge's definition on the CPU (no device), with RayTracer.adaptive_merge's arguments for
+    numpy planes.  RayTracer.adaptive_merge computes the same bits on the GPU."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    planes, outs, W, H = _adaptive_merge_planes(counts, offsets, color, history, albedo, moments, out, out_history, out_moments)
+    d = _adaptive_merge_desc(W, H, np.shape(radiance)[0], max_history)
+    keep, res = _adaptive_merge_numpy(d, W, H, radiance, planes, outs)
+    L = load()
+    rc = L.rt_adaptive_merge_host(C.byref(d))
+    del keep
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+    return _adaptive_merge_result(res)
+
+
 class RayTracer:
     def __init__(self, device=0, max_width=1920, max_height=1080, lib=None):
         self._L = lib or load()   # (lib=load_test(): a handle of the test library, for the rt_test_* entry points)
@@ -716,6 +843,128 @@ class RayTracer:
         planes, W, H = _vdenoise_inputs(guides, color, None, None)
         res = self._vdenoise_call("rt_luminance_moments", _vdenoise_desc(W, H), W, H, planes, {"out": True if out is None else out})
         return res["out"]
+
+    def _adaptive_tensors(self, table, W, H, given):
+        """Checks the frame-shaped device tensors of an adaptive call (uint32 planes: int32 tensors holding the bits, or uint32)."""
+        import torch
+        for k, v in given.items():
+            if not isinstance(v, torch.Tensor):
+                raise ValueError("mix of device tensors and host arrays")
+            if v.device.type != "cuda" or v.device.index != self.device:
+                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
+            kinds = (torch.float32,) if table[k][0] == "<f4" else (torch.int32, getattr(torch, "uint32", torch.int32))
+            if v.dtype not in kinds or not v.is_contiguous() or tuple(v.shape) != _adaptive_shape(table, k, W, H):
+                raise ValueError(f"plane {k} must be a contiguous {kinds[0]} tensor of shape {_adaptive_shape(table, k, W, H)}")
+
+    def _on_handle_stream(self, call):
+        """Runs call() on the handle's stream, ordered after the current torch stream's work and before what follows on it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
+        ext.wait_stream(cur)
+        call()
+        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
+
+    def adaptive_plan(self, variance, dirs, origin, budget, min_samples=ADAPTIVE_MIN_SAMPLES, max_samples=ADAPTIVE_MAX_SAMPLES,
+                      first_frame=0):
+        """Apportions `budget` rays over the texels of a frame in proportion to their standard deviation (rt_adaptive_plan;
+        include/rt_abi.h has the definition).  `variance`: (H, W) float32, denoise_variance's out_variance; `dirs`: (H, W, 3),
+        the `dir` plane of render_gbuffer; `origin`: the camera position, the origin of every ray.  Every texel gets between
+        `min_samples` and `max_samples` rays; texel p's sample k has the seed of pixel p in frame first_frame + k.  Returns
+        (counts, offsets, rays, totals): (H, W) uint32 each, the `budget` rt_path_ray records (those past totals[0] are
+        zeros, which radiance answers with zeros) and (rays planned, texels above min_samples, texels clamped by
+        max_samples, 0).
+        numpy planes: a synchronous call that returns numpy (rays: PATH_RAY_DTYPE).  Torch tensors on this handle's device:
+        an asynchronous call ordered after the current torch stream's work; counts, offsets and totals are int32 tensors
+        holding the u32 bits, rays a (budget, 8) float32 tensor of the packed records."""
+        if not hasattr(variance, "data_ptr") and not hasattr(dirs, "data_ptr"):
+            H, W = (int(v) for v in np.shape(variance)) if np.ndim(variance) == 2 else (0, 0)
+            d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
+            keep, res = _adaptive_plan_numpy(d, W, H, variance, dirs)
+            self._check(self._L.rt_adaptive_plan(self._h, C.byref(d), A.ADAPTIVE_HOST_MEMORY))
+            del keep
+            return res["counts"], res["offsets"], res["rays"], res["totals"]
+        import torch
+        H, W = (int(v) for v in variance.shape) if hasattr(variance, "data_ptr") and variance.dim() == 2 else (0, 0)
+        d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
+        self._adaptive_tensors(A.ADAPTIVE_PLAN_PLANES, W, H, {"variance": variance, "dir": dirs})
+        dev = torch.device("cuda", self.device)
+        counts = torch.empty((H, W), dtype=torch.int32, device=dev)
+        offsets = torch.empty((H, W), dtype=torch.int32, device=dev)
+        rays = torch.empty((d.budget, 8), dtype=torch.float32, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        d.variance, d.dir, d.counts, d.offsets = variance.data_ptr(), dirs.data_ptr(), counts.data_ptr(), offsets.data_ptr()
+        d.rays, d.totals = rays.data_ptr(), totals.data_ptr()
+        self._on_handle_stream(lambda: self._check(self._L.rt_adaptive_plan(self._h, C.byref(d), 0)))
+        return counts, offsets, rays, totals
+
+    def adaptive_merge(self, radiance, counts, offsets, color, history, max_history=float("inf"), albedo=None, moments=None, out=None,
+                       out_history=None, out_moments=None):
+        """Blends the samples traced for a plan into the accumulation (rt_adaptive_merge; include/rt_abi.h has the definition):
+        texel p takes radiance[offsets[p] + k], k < counts[p], one at a time, each as one more unit of its history --
+        `color` (H, W, 4) and `history` (H, W; 0 or anything below 1: no prior) are the accumulation so far, `max_history`
+        caps the history length.  With `moments` (H, W, 4) the luminance moments of each sample (of radiance / albedo, with
+        `albedo` (H, W, 4) given) are accumulated the same way.  Returns (out, out_history) or (out, out_history,
+        out_moments); the outputs may be the inputs.
+        numpy planes: a synchronous call that returns numpy.  Torch tensors on this handle's device: an asynchronous call
+        ordered after the current torch stream's work; returns tensors; there color=None names the handle's image."""
+        planes, outs, W, H = _adaptive_merge_planes(counts, offsets, color, history, albedo, moments, out, out_history, out_moments)
+        d = _adaptive_merge_desc(W, H, radiance.shape[0] if np.ndim(radiance) == 2 else 0, max_history)
+        if not any(hasattr(v, "data_ptr") for v in (radiance, *planes.values(), *outs.values())):
+            if color is None:
+                raise ValueError("color is required with numpy planes (color=None names the device image)")
+            keep, res = _adaptive_merge_numpy(d, W, H, radiance, planes, outs)
+            self._check(self._L.rt_adaptive_merge(self._h, C.byref(d), A.ADAPTIVE_HOST_MEMORY))
+            del keep
+            return _adaptive_merge_result(res)
+        import torch
+        dev = torch.device("cuda", self.device)
+        given = dict(planes, **{k: v for k, v in outs.items() if v is not None})
+        self._adaptive_tensors(A.ADAPTIVE_MERGE_PLANES, W, H, given)
+        if not (isinstance(radiance, torch.Tensor) and radiance.device == dev and radiance.dtype == torch.float32
+                and radiance.is_contiguous() and tuple(radiance.shape) == (d.budget, 4)):
+            raise ValueError(f"radiance must be a contiguous float32 tensor of shape {(d.budget, 4)} on cuda:{self.device}")
+        for k in outs:
+            if outs[k] is None:
+                outs[k] = given[k] = torch.empty(_adaptive_shape(A.ADAPTIVE_MERGE_PLANES, k, W, H), dtype=torch.float32, device=dev)
+        d.radiance = radiance.data_ptr()
+        for k, v in given.items():
+            setattr(d, k, v.data_ptr())
+        self._on_handle_stream(lambda: self._check(self._L.rt_adaptive_merge(self._h, C.byref(d), 0)))
+        return _adaptive_merge_result(outs)
+
+    def adaptive_samples(self, guides, variance, color, history, budget, bounces, samples, origin, min_samples=ADAPTIVE_MIN_SAMPLES,
+                         max_samples=ADAPTIVE_MAX_SAMPLES, first_frame=0, max_history=float("inf"), moments=None, skybox=True,
+                         out=None, out_history=None, out_moments=None):
+        """One round of adaptive sampling: adaptive_plan on `variance` and guides["dir"], the planned rays traced by
+        rt_radiance_rays (`bounces`, `samples` per ray record, `skybox`: as radiance) straight from the packed record
+        buffer, and adaptive_merge of the result into `color` / `history` (and `moments`, demodulated by guides["albedo"]
+        when present).  `origin`: the camera position.  Returns (out, out_history[, out_moments], counts, totals).
+        numpy planes: three synchronous calls.  Torch tensors on this handle's device: the three calls are queued on the
+        handle's stream with no host synchronisation between them -- the list's tail past the planned total is zero
+        records, so nothing is read back --, ordered after the current torch stream's work; color=None names the handle's
+        image."""
+        bounces, samples = int(bounces), int(samples)
+        if bounces < 0:
+            raise ValueError("bounces must be >= 0")
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        if "dir" not in guides:
+            raise ValueError("guides must hold the dir plane of render_gbuffer")
+        params = A.make_params(0, 0, bounces, samples, skybox=1 if skybox else 0)
+        albedo = guides.get("albedo") if moments is not None else None
+        counts, offsets, rays, totals = self.adaptive_plan(variance, guides["dir"], origin, budget, min_samples, max_samples, first_frame)
+        n = int(rays.shape[0])
+        if hasattr(rays, "data_ptr"):
+            import torch
+            radiance = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            self._device_query(lambda h, r, m, o, f: self._L.rt_radiance_rays(h, C.byref(params), r, m, o, f), rays, radiance, 0)
+        else:
+            radiance = np.zeros((n, 4), np.float32)
+            self._check(self._L.rt_radiance_rays(self._h, C.byref(params), rays.ctypes.data, n, radiance.ctypes.data, A.RADIANCE_HOST_MEMORY))
+        res = self.adaptive_merge(radiance, counts, offsets, color, history, max_history, albedo, moments, out, out_history, out_moments)
+        return (*res, counts, totals)
 
     def temporal_accumulate(self, guides, prev_guides, prev_camera, prev_color, prev_history, color=None, max_history=float("inf"),
                             point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,

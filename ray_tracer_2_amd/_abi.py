@@ -113,8 +113,10 @@ class DenoiseDesc(C.Structure):  # rt_denoise_desc: a frame and its guides for r
                 ("out", C.c_void_p)]
 
 
-# plane of rt_denoise_desc -> components per texel
-DENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission": 4, "out": 4}
+# The plane tables of the frame passes, in the order of their desc's fields:
+# plane -> (numpy dtype, components per texel; 0: a plane of shape (H, W))
+DENOISE_PLANES = {"color": ("<f4", 4), "normal": ("<f4", 3), "point": ("<f4", 3), "albedo": ("<f4", 4), "emission": ("<f4", 4),
+                  "out": ("<f4", 4)}
 DENOISE_HOST_MEMORY = 1
 
 
@@ -126,9 +128,8 @@ class VDenoiseDesc(C.Structure):  # rt_vdenoise_desc: a frame, its guides and it
                 ("out_variance", C.c_void_p)]
 
 
-# plane of rt_vdenoise_desc -> components per texel; 0: a plane of shape (H, W)
-VDENOISE_PLANES = {"color": 4, "normal": 3, "point": 3, "albedo": 4, "emission": 4, "moments": 4, "history": 0, "out": 4,
-                   "out_variance": 0}
+VDENOISE_PLANES = {"color": ("<f4", 4), "normal": ("<f4", 3), "point": ("<f4", 3), "albedo": ("<f4", 4), "emission": ("<f4", 4),
+                   "moments": ("<f4", 4), "history": ("<f4", 0), "out": ("<f4", 4), "out_variance": ("<f4", 0)}
 VDENOISE_HOST_MEMORY = 1
 
 
@@ -146,8 +147,8 @@ class AdaptiveMergeDesc(C.Structure):  # rt_adaptive_merge_desc: the traced samp
                 ("out_history", C.c_void_p), ("out_moments", C.c_void_p)]
 
 
-# frame-shaped plane of the two descs -> (numpy dtype, components per texel; 0: a plane of shape (H, W)); `rays`
-# ((budget,) PATH_RAY_DTYPE), `totals` ((4,) uint32) and `radiance` ((budget, 4) float32) are not frame-shaped
+# the frame-shaped planes of the two descs; `rays` ((budget,) PATH_RAY_DTYPE), `totals` ((4,) uint32) and `radiance`
+# ((budget, 4) float32) are not frame-shaped
 ADAPTIVE_PLAN_PLANES = {"variance": ("<f4", 0), "dir": ("<f4", 3), "counts": ("<u4", 0), "offsets": ("<u4", 0)}
 ADAPTIVE_MERGE_PLANES = {"counts": ("<u4", 0), "offsets": ("<u4", 0), "color": ("<f4", 4), "history": ("<f4", 0),
                          "albedo": ("<f4", 4), "moments": ("<f4", 4), "out": ("<f4", 4), "out_history": ("<f4", 0),
@@ -163,7 +164,6 @@ class TemporalDesc(C.Structure):  # rt_temporal_desc: two frames for rt_temporal
                 ("prev_object", C.c_void_p), ("out", C.c_void_p), ("out_history", C.c_void_p), ("motion", C.c_void_p)]
 
 
-# plane of rt_temporal_desc -> (numpy dtype, components per texel; 0: a plane of shape (H, W))
 TEMPORAL_PLANES = {"color": ("<f4", 4), "point": ("<f4", 3), "normal": ("<f4", 3), "object": ("<u4", 0),
                    "prev_color": ("<f4", 4), "prev_history": ("<f4", 0), "prev_point": ("<f4", 3), "prev_normal": ("<f4", 3),
                    "prev_object": ("<u4", 0), "out": ("<f4", 4), "out_history": ("<f4", 0), "motion": ("<f4", 2)}

@@ -19,7 +19,7 @@ PRODUCT_SOURCES = [
 ]
 PRODUCT_HEADERS = [
     "rt_queries.inl", "rt_test_kernels.inl", "rt_transc.h", "rt_texture.h", "rt_srgb_lut.h", "rt_device.h", "rt_scene_format.h", "rt_rccl.h", "rt_refit.h", "rt_denoise.h", "rt_denoise_api.h", "rt_temporal.h", "rt_temporal_api.h", "rt_vdenoise.h", "rt_vdenoise_api.h", "rt_adaptive.h", "rt_adaptive_api.h", "host/glam_math.h",
-    "host/obj_loader.h", "host/bvh.h", "host/scene.h", "host/scene_pack.h", "host/launch_options.h", "host/ray_tracer.hpp",
+    "host/obj_loader.h", "host/bvh.h", "host/scene.h", "host/scene_pack.h", "host/launch_options.h", "host/plane_check.h", "host/ray_tracer.hpp",
     "../../include/rt_abi.h", "../../include/rt_test_abi.h", "experiments/rt_wavefront.inl", "experiments/rt_wavefront_launch.inl", "experiments/rt_api_wavefront.inl", "experiments/rt_api_hybrid_blob.inl",
 ]
 

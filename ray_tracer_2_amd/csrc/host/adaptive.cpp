@@ -11,24 +11,9 @@
 
 #include "../rt_adaptive.h"
 #include "../rt_adaptive_api.h"
+#include "plane_check.h"
 
 namespace rt2 {
-
-namespace {
-struct Plane {
-    const void* p;
-    uintptr_t mask;
-    const char* name;
-};
-int misaligned(const Plane* planes, int n, std::string& err) {
-    for (int i = 0; i < n; ++i)
-        if (((uintptr_t)planes[i].p & planes[i].mask) != 0u) {
-            err = std::string("device plane ") + planes[i].name + " is not aligned to " + std::to_string(planes[i].mask + 1u) + " bytes";
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-    return RT_OK;
-}
-}  // namespace
 
 int adaptive_plan_check(const rt_adaptive_plan_desc* d, bool device, bool host_memory, std::string& err) {
     auto bad = [&](int code, const char* msg) {
@@ -50,8 +35,8 @@ int adaptive_plan_check(const rt_adaptive_plan_desc* d, bool device, bool host_m
     if ((uint64_t)d->min_samples * texels > (uint64_t)d->budget)
         return bad(RT_ERR_INVALID_ARGUMENT, "min_samples * width * height is larger than the budget");
     if (device && !host_memory) {
-        const Plane planes[6] = {{d->variance, 3u, "variance"}, {d->dir, 3u, "dir"}, {d->counts, 3u, "counts"},
-                                 {d->offsets, 3u, "offsets"}, {d->rays, 15u, "rays"}, {d->totals, 3u, "totals"}};
+        const PlaneAlign planes[6] = {{d->variance, 3u, "variance"}, {d->dir, 3u, "dir"}, {d->counts, 3u, "counts"},
+                                      {d->offsets, 3u, "offsets"}, {d->rays, 15u, "rays"}, {d->totals, 3u, "totals"}};
         return misaligned(planes, 6, err);
     }
     return RT_OK;
@@ -75,10 +60,10 @@ int adaptive_merge_check(const rt_adaptive_merge_desc* d, bool device, bool host
         return bad(RT_ERR_INVALID_ARGUMENT, "the moments and out_moments planes go together: one is null and the other is not");
     if ((uint64_t)d->width * d->height > 0x7fffffffull) return bad(RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
     if (device && !host_memory) {
-        const Plane planes[10] = {{d->radiance, 15u, "radiance"}, {d->counts, 3u, "counts"}, {d->offsets, 3u, "offsets"},
-                                  {d->color, 15u, "color"}, {d->history, 3u, "history"}, {d->albedo, 15u, "albedo"},
-                                  {d->moments, 15u, "moments"}, {d->out, 15u, "out"}, {d->out_history, 3u, "out_history"},
-                                  {d->out_moments, 15u, "out_moments"}};
+        const PlaneAlign planes[10] = {{d->radiance, 15u, "radiance"}, {d->counts, 3u, "counts"}, {d->offsets, 3u, "offsets"},
+                                       {d->color, 15u, "color"}, {d->history, 3u, "history"}, {d->albedo, 15u, "albedo"},
+                                       {d->moments, 15u, "moments"}, {d->out, 15u, "out"}, {d->out_history, 3u, "out_history"},
+                                       {d->out_moments, 15u, "out_moments"}};
         return misaligned(planes, 10, err);
     }
     return RT_OK;

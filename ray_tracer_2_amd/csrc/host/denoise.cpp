@@ -12,6 +12,7 @@
 
 #include "../rt_denoise.h"
 #include "../rt_denoise_api.h"
+#include "plane_check.h"
 
 namespace rt2 {
 
@@ -33,14 +34,9 @@ int denoise_check(const rt_denoise_desc* d, bool device, bool host_memory, std::
     if (!d->color && (!device || host_memory)) return bad(RT_ERR_INVALID_ARGUMENT, "null color plane (only device planes may name the handle's image that way)");
     if ((uint64_t)d->width * d->height > 0x7fffffffull) return bad(RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
     if (device && !host_memory) {
-        const struct { const void* p; uintptr_t mask; const char* name; } planes[6] = {
-            {d->color, 15u, "color"}, {d->normal, 3u, "normal"}, {d->point, 3u, "point"},
-            {d->albedo, 15u, "albedo"}, {d->emission, 15u, "emission"}, {d->out, 15u, "out"}};
-        for (const auto& pl : planes)
-            if (((uintptr_t)pl.p & pl.mask) != 0u) {
-                err = std::string("device plane ") + pl.name + " is not aligned to " + std::to_string(pl.mask + 1u) + " bytes";
-                return RT_ERR_INVALID_ARGUMENT;
-            }
+        const PlaneAlign planes[6] = {{d->color, 15u, "color"}, {d->normal, 3u, "normal"}, {d->point, 3u, "point"},
+                                      {d->albedo, 15u, "albedo"}, {d->emission, 15u, "emission"}, {d->out, 15u, "out"}};
+        return misaligned(planes, 6, err);
     }
     return RT_OK;
 }

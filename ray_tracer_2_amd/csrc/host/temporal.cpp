@@ -11,6 +11,7 @@
 
 #include "../rt_temporal_api.h"
 #include "glam_math.h"
+#include "plane_check.h"
 
 namespace rt2 {
 
@@ -32,16 +33,12 @@ int temporal_check(const rt_temporal_desc* d, bool device, bool host_memory, std
     if (!d->color && (!device || host_memory)) return bad(RT_ERR_INVALID_ARGUMENT, "null color plane (only device planes may name the handle's image that way)");
     if ((uint64_t)d->width * d->height > 0x7fffffffull) return bad(RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
     if (device && !host_memory) {
-        const struct { const void* p; uintptr_t mask; const char* name; } planes[12] = {
+        const PlaneAlign planes[12] = {
             {d->color, 15u, "color"}, {d->point, 3u, "point"}, {d->normal, 3u, "normal"}, {d->object, 3u, "object"},
             {d->prev_color, 15u, "prev_color"}, {d->prev_history, 3u, "prev_history"}, {d->prev_point, 3u, "prev_point"},
             {d->prev_normal, 3u, "prev_normal"}, {d->prev_object, 3u, "prev_object"}, {d->out, 15u, "out"},
             {d->out_history, 3u, "out_history"}, {d->motion, 7u, "motion"}};
-        for (const auto& pl : planes)
-            if (((uintptr_t)pl.p & pl.mask) != 0u) {
-                err = std::string("device plane ") + pl.name + " is not aligned to " + std::to_string(pl.mask + 1u) + " bytes";
-                return RT_ERR_INVALID_ARGUMENT;
-            }
+        return misaligned(planes, 12, err);
     }
     return RT_OK;
 }

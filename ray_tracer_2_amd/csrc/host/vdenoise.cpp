@@ -13,6 +13,7 @@
 
 #include "../rt_vdenoise.h"
 #include "../rt_vdenoise_api.h"
+#include "plane_check.h"
 
 namespace rt2 {
 
@@ -41,15 +42,10 @@ int vdenoise_check(const rt_vdenoise_desc* d, bool moments_only, bool device, bo
     if (!d->color && (!device || host_memory)) return bad(RT_ERR_INVALID_ARGUMENT, "null color plane (only device planes may name the handle's image that way)");
     if ((uint64_t)d->width * d->height > 0x7fffffffull) return bad(RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
     if (device && !host_memory) {
-        const struct { const void* p; uintptr_t mask; const char* name; } planes[9] = {
-            {d->color, 15u, "color"}, {d->normal, 3u, "normal"}, {d->point, 3u, "point"},
-            {d->albedo, 15u, "albedo"}, {d->emission, 15u, "emission"}, {d->out, 15u, "out"},
-            {d->moments, 15u, "moments"}, {d->history, 3u, "history"}, {d->out_variance, 3u, "out_variance"}};
-        for (int i = 0; i < (moments_only ? 6 : 9); ++i)
-            if (((uintptr_t)planes[i].p & planes[i].mask) != 0u) {
-                err = std::string("device plane ") + planes[i].name + " is not aligned to " + std::to_string(planes[i].mask + 1u) + " bytes";
-                return RT_ERR_INVALID_ARGUMENT;
-            }
+        const PlaneAlign planes[9] = {{d->color, 15u, "color"}, {d->normal, 3u, "normal"}, {d->point, 3u, "point"},
+                                      {d->albedo, 15u, "albedo"}, {d->emission, 15u, "emission"}, {d->out, 15u, "out"},
+                                      {d->moments, 15u, "moments"}, {d->history, 3u, "history"}, {d->out_variance, 3u, "out_variance"}};
+        return misaligned(planes, moments_only ? 6 : 9, err);
     }
     return RT_OK;
 }

@@ -194,7 +194,7 @@ struct rt_handle {
     size_t snapshot_capacity = 0, snapshot_bytes = 0;  // bytes allocated / bytes of the last snapshot
     // rt_denoise: per texel a guide record of two float4 and two colour images of one float4 each (64 B), kept between calls
     float4* denoise_scratch = nullptr;
-    size_t denoise_texels = 0;
+    size_t denoise_scratch_bytes = 0;
     // rt_adaptive_plan: the block sums of its two scans and a few words (rt_adaptive_api.h), kept between calls
     void* adaptive_scratch = nullptr;
     size_t adaptive_scratch_bytes = 0;
@@ -315,7 +315,7 @@ int fail(rt_handle* h, int code, const std::string& msg) {
 size_t optional_bytes(const rt_handle* h) {
     size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary.texels * 64u +
                2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity +
-               h->denoise_texels * 64u + h->adaptive_scratch_bytes;
+               h->denoise_scratch_bytes + h->adaptive_scratch_bytes;
     for (const PipeSlot& ps : h->pipe) {
         if (ps.scratch) b += h->pipe_scratch_texels * sizeof(float4);
         b += ps.memo_words * sizeof(uint32_t) + ps.primary.texels * 64u;
@@ -2307,45 +2307,146 @@ int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* r
     });
 }
 
-// ---- denoising a rendered frame (include/rt_abi.h: rt_denoise, rt_denoise_host; rt_denoise.hip; host/denoise.cpp) ----
-// Launched like a query: nothing read but the caller's planes (or the image) and nothing written but `out` and the
-// handle's denoise scratch.
-int rt_denoise_host(const rt_denoise_desc* desc) {
+// ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
+// rt_adaptive_merge, rt_temporal_accumulate ----
+// Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
+// and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
+// arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
+// temporary device buffer on host memory.
+
+// One plane of a frame pass: read from `in`, written to `out`, or both -- an output that takes its input's place in the
+// staging buffer, as `out` takes `color`'s.  An entry with neither pointer is absent and takes no room.
+struct FramePlane {
+    const void* in;
+    void* out;
+    size_t bytes;
+};
+
+extern "C++" {
+// The staging buffer of the host-memory path: the planes that are there in table order, each at a multiple of 256 bytes.
+template <int N>
+static size_t staged_bytes(const FramePlane (&planes)[N], size_t* offsets = nullptr) {
+    size_t total = 0;
+    for (int c = 0; c < N; ++c) {
+        if (!planes[c].in && !planes[c].out) continue;
+        if (offsets) offsets[c] = total;
+        total = (total + planes[c].bytes + 255u) & ~(size_t)255u;
+    }
+    return total;
+}
+
+// launch(in, out) on the planes of the table, in[c] / out[c] null for an absent plane.  Device memory: the table's own
+// pointers, and the launch is queued.  Host memory: every plane whole through one temporary device buffer within option
+// max_device_mb (a pass may read any row: no bands) -- the inputs copied in, in[c] == out[c] the staged plane, the outputs
+// copied out, all in table order, and the stream drained (staged_chunks).
+template <int N, class Launch>
+static int frame_call(rt_handle* h, bool host, const FramePlane (&planes)[N], const char* what_for, const char* launch_name, Launch&& launch) {
+    const void* in[N] = {};
+    void* out[N] = {};
+    if (!host) {
+        for (int c = 0; c < N; ++c) in[c] = planes[c].in, out[c] = planes[c].out;
+        const hipError_t e = launch(in, out);
+        return e == hipSuccess ? RT_OK : fail(h, RT_ERR_DEVICE, std::string(launch_name) + "(a, h->stream): " + hipGetErrorString(e));
+    }
+    size_t offsets[N] = {};
+    const size_t total = staged_bytes(planes, offsets);
+    if (!fits_cap(h, total)) return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("option max_device_mb leaves no room for ") + what_for);
+    return staged_chunks(h, total, 1, 1, what_for, [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
+        hipError_t e = hipSuccess;
+        what = "hipMemcpyAsync";
+        for (int c = 0; c < N && e == hipSuccess; ++c) {
+            if (!planes[c].in && !planes[c].out) continue;
+            in[c] = out[c] = buf + offsets[c];
+            if (planes[c].in) e = hipMemcpyAsync(out[c], planes[c].in, planes[c].bytes, hipMemcpyHostToDevice, h->stream);
+        }
+        if (e != hipSuccess) return e;
+        if (what = launch_name, (e = launch(in, out)) != hipSuccess) return e;
+        what = "hipMemcpyAsync";
+        for (int c = 0; c < N && e == hipSuccess; ++c)
+            if (planes[c].out) e = hipMemcpyAsync(planes[c].out, out[c], planes[c].bytes, hipMemcpyDeviceToHost, h->stream);
+        return e;
+    });
+}
+
+// A scratch the handle keeps between calls (`what`: its name in the messages), grown to `need` bytes on demand within option
+// max_device_mb, together with the `staging` bytes the call is about to take (what_for: their name).  A call whose scratch
+// is large enough checks its staging alone -- on device memory too, where that is 0 bytes: such a call is refused once the
+// handle holds more than the cap, while the passes without a scratch (rt_temporal_accumulate, rt_adaptive_merge) go on.
+template <class T>
+static int grow_scratch(rt_handle* h, T*& scratch, size_t& held, size_t need, size_t staging, const char* what, const char* what_for) {
+    auto no_room = [&](const char* for_what) { return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("option max_device_mb leaves no room for ") + for_what); };
+    if (held >= need) return fits_cap(h, staging) ? RT_OK : no_room(what_for);
+    if (!fits_cap(h, need + staging, held)) return no_room(what);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
+    free_dev(scratch);
+    held = 0;
+    const hipError_t e = hipMalloc((void**)&scratch, need);
+    if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("no device memory for ") + what);
+    HIP_TRY(h, e);
+    held = need;
+    return RT_OK;
+}
+
+// A _host entry point: the host unit's restatement, its error kept for rt_last_error(NULL).
+template <class Desc>
+static int host_call(int (*restatement)(const Desc*, std::string&), const Desc* desc) {
     try {
         std::string err;
-        const int rc = rt2::denoise_host(desc, err);
+        const int rc = restatement(desc, err);
         return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
     } catch (const std::bad_alloc&) {
         return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
     }
 }
+}  // extern "C++" (templates among the C entry points)
+
+// The colour plane of a pass: the caller's, or for NULL (device memory only: the checks refuse it elsewhere) the handle's
+// image, which must hold the frame.
+static int frame_color(rt_handle* h, const float*& color, size_t texels) {
+    if (color) return RT_OK;
+    if (texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    color = reinterpret_cast<const float*>(h->image);
+    return RT_OK;
+}
+
+// Before a pass on device memory that reads `color` and writes `out`: a copy of the image that is still under way is
+// waited for when either is the image, and the image counts as changed when `out` lies in it, as by rt_write_image.
+static int image_access(rt_handle* h, const float* color, const float* out) {
+    const float* image = reinterpret_cast<const float*>(h->image);
+    const bool out_is_image = out >= image && out < image + 4 * h->image_texels;
+    if (color == image || out_is_image) {
+        if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+    }
+    if (out_is_image) h->generation += 1;
+    return RT_OK;
+}
+
+int rt_denoise_host(const rt_denoise_desc* desc) { return host_call(rt2::denoise_host, desc); }
+int rt_denoise_variance_host(const rt_vdenoise_desc* desc) { return host_call(rt2::vdenoise_host, desc); }
+int rt_luminance_moments_host(const rt_vdenoise_desc* desc) { return host_call(rt2::luminance_moments_host, desc); }
+int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc) { return host_call(rt2::adaptive_plan_host, desc); }
+int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) { return host_call(rt2::adaptive_merge_host, desc); }
+int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call(rt2::temporal_host, desc); }
+
+// ---- denoising a rendered frame (include/rt_abi.h: rt_denoise; rt_denoise.hip; host/denoise.cpp) ----
+static const char* const DENOISE_SCRATCH = "the denoiser's scratch images";
+static const char* const DENOISE_STAGING = "the denoiser's staging planes";
 
 int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (flags & ~RT_DENOISE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
     const bool host = (flags & RT_DENOISE_HOST_MEMORY) != 0;
-    {
-        std::string err;
-        if (const int rc = rt2::denoise_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    }
+    std::string err;
+    if (const int rc = rt2::denoise_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
     const size_t texels = (size_t)desc->width * desc->height;
-    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    // the scratch: grown on demand, within option max_device_mb
-    const size_t staging = host ? texels * (size_t)(16 + 12 + 12 + (desc->albedo ? 16 : 0) + (desc->emission ? 16 : 0)) + 5u * 256u : 0u;
-    if (h->denoise_texels < texels) {
-        if (!fits_cap(h, texels * 64u + staging, h->denoise_texels * 64u))
-            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's scratch images");
-        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
-        free_dev(h->denoise_scratch);
-        h->denoise_texels = 0;
-        const hipError_t e = hipMalloc((void**)&h->denoise_scratch, texels * 64u);
-        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the denoiser's scratch images");
-        HIP_TRY(h, e);
-        h->denoise_texels = texels;
-    } else if (!fits_cap(h, staging)) {
-        return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's staging planes");
-    }
+    const FramePlane planes[5] = {{color, desc->out, texels * 16u}, {desc->normal, nullptr, texels * 12u}, {desc->point, nullptr, texels * 12u},
+                                  {desc->albedo, nullptr, texels * 16u}, {desc->emission, nullptr, texels * 16u}};
+    if (int rc = grow_scratch(h, h->denoise_scratch, h->denoise_scratch_bytes, texels * 64u, host ? staged_bytes(planes) : 0u,
+                              DENOISE_SCRATCH, DENOISE_STAGING); rc != RT_OK) return rc;
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
     DenoiseArgs a{};
     a.width = desc->width;
     a.height = desc->height;
@@ -2356,103 +2457,37 @@ int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags) {
     a.guide = h->denoise_scratch;
     a.ping[0] = h->denoise_scratch + 2 * texels;
     a.ping[1] = h->denoise_scratch + 3 * texels;
-    if (!host) {
-        const float* image = reinterpret_cast<const float*>(h->image);
-        a.color = desc->color ? desc->color : image;
-        a.normal = desc->normal; a.point = desc->point; a.albedo = desc->albedo; a.emission = desc->emission; a.out = desc->out;
-        if (a.color == image || (desc->out >= image && desc->out < image + 4 * h->image_texels)) {
-            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-        }
-        if (desc->out >= image && desc->out < image + 4 * h->image_texels) h->generation += 1;   // (the image changes, as by rt_write_image)
-        HIP_TRY(h, launch_denoise(a, h->stream));
-        return RT_OK;
-    }
-    // host memory: the whole frame through one temporary device buffer (a pass reads up to 256 rows away: no bands);
-    // each plane's part of it starts at a multiple of 256 bytes, and `out` takes the colour plane's place
-    const void* const src[5] = {desc->color, desc->normal, desc->point, desc->albedo, desc->emission};
-    static const uint32_t bytes[5] = {16, 12, 12, 16, 16};
-    size_t plane_off[5] = {}, off = 0;
-    for (int c = 0; c < 5; ++c) {
-        if (!src[c]) continue;
-        plane_off[c] = off;
-        off = (off + texels * bytes[c] + 255u) & ~(size_t)255u;
-    }
-    return staged_chunks(h, off, 1, 1, "the denoiser's staging planes", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
-        hipError_t e = hipSuccess;
-        what = "hipMemcpyAsync";
-        const float* d_ptr[5] = {};
-        for (int c = 0; c < 5 && e == hipSuccess; ++c) {
-            if (!src[c]) continue;
-            d_ptr[c] = reinterpret_cast<const float*>(buf + plane_off[c]);
-            e = hipMemcpyAsync(buf + plane_off[c], src[c], texels * bytes[c], hipMemcpyHostToDevice, h->stream);
-        }
-        if (e != hipSuccess) return e;
-        a.color = d_ptr[0]; a.normal = d_ptr[1]; a.point = d_ptr[2]; a.albedo = d_ptr[3]; a.emission = d_ptr[4];
-        a.out = reinterpret_cast<float*>(buf + plane_off[0]);
-        if (what = "launch_denoise", (e = launch_denoise(a, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        return hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream);
+    return frame_call(h, host, planes, DENOISE_STAGING, "launch_denoise", [&](const void* const* in, void* const* out) {
+        a.color = (const float*)in[0]; a.out = (float*)out[0];
+        a.normal = (const float*)in[1]; a.point = (const float*)in[2]; a.albedo = (const float*)in[3]; a.emission = (const float*)in[4];
+        return launch_denoise(a, h->stream);
     });
 }
 
-// ---- variance-guided denoising (include/rt_abi.h: rt_denoise_variance, rt_luminance_moments and their _host forms;
-// rt_vdenoise.hip; host/vdenoise.cpp) ----
-// Launched like rt_denoise, in rt_denoise's scratch: each call of either rewrites every word of it that it later reads.
-int rt_denoise_variance_host(const rt_vdenoise_desc* desc) {
-    try {
-        std::string err;
-        const int rc = rt2::vdenoise_host(desc, err);
-        return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
-    } catch (const std::bad_alloc&) {
-        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-    }
-}
-
-int rt_luminance_moments_host(const rt_vdenoise_desc* desc) {
-    std::string err;
-    const int rc = rt2::luminance_moments_host(desc, err);
-    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
-}
-
-// The two entry points: moments_only is rt_luminance_moments, which needs no scratch and stages fewer planes.
+// ---- variance-guided denoising (include/rt_abi.h: rt_denoise_variance, rt_luminance_moments; rt_vdenoise.hip;
+// host/vdenoise.cpp) ----
+// Launched in rt_denoise's scratch: each call of either rewrites every word of it that it later reads.
+// The two entry points: moments_only is rt_luminance_moments, which needs no scratch and takes fewer planes.
 static int vdenoise_call(rt_handle* h, const rt_vdenoise_desc* desc, int flags, bool moments_only) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (flags & ~RT_VDENOISE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
     const bool host = (flags & RT_VDENOISE_HOST_MEMORY) != 0;
-    {
-        std::string err;
-        if (const int rc = rt2::vdenoise_check(desc, moments_only, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    }
+    std::string err;
+    if (const int rc = rt2::vdenoise_check(desc, moments_only, true, host, err); rc != RT_OK) return fail(h, rc, err);
     const size_t texels = (size_t)desc->width * desc->height;
-    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    // the planes of the host-memory path, in staging order: the first five are rt_denoise's; `out` takes the colour's place
+    // the first five are rt_denoise's
     const bool with_moments = !moments_only && desc->moments, with_variance = !moments_only && desc->out_variance;
-    const void* const src[8] = {desc->color, desc->normal, desc->point, desc->albedo, desc->emission,
-                                with_moments ? desc->moments : nullptr, with_moments ? desc->history : nullptr,
-                                with_variance ? desc->out_variance : nullptr};
-    static const uint32_t bytes[8] = {16, 12, 12, 16, 16, 16, 4, 4};
-    size_t plane_off[8] = {}, staging = 0;
-    if (host)
-        for (int c = 0; c < 8; ++c) {
-            if (!src[c]) continue;
-            plane_off[c] = staging;
-            staging = (staging + texels * bytes[c] + 255u) & ~(size_t)255u;
-        }
-    // the scratch: rt_denoise's, grown on demand, within option max_device_mb
-    if (!moments_only && h->denoise_texels < texels) {
-        if (!fits_cap(h, texels * 64u + staging, h->denoise_texels * 64u))
-            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's scratch images");
-        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
-        free_dev(h->denoise_scratch);
-        h->denoise_texels = 0;
-        const hipError_t e = hipMalloc((void**)&h->denoise_scratch, texels * 64u);
-        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the denoiser's scratch images");
-        HIP_TRY(h, e);
-        h->denoise_texels = texels;
-    } else if (!fits_cap(h, staging)) {
-        return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the denoiser's staging planes");
-    }
+    const FramePlane planes[8] = {{color, desc->out, texels * 16u}, {desc->normal, nullptr, texels * 12u}, {desc->point, nullptr, texels * 12u},
+                                  {desc->albedo, nullptr, texels * 16u}, {desc->emission, nullptr, texels * 16u},
+                                  {with_moments ? desc->moments : nullptr, nullptr, texels * 16u},
+                                  {with_moments ? desc->history : nullptr, nullptr, texels * 4u},
+                                  {nullptr, with_variance ? desc->out_variance : nullptr, texels * 4u}};
+    if (int rc = grow_scratch(h, h->denoise_scratch, h->denoise_scratch_bytes, moments_only ? 0u : texels * 64u,
+                              host ? staged_bytes(planes) : 0u, DENOISE_SCRATCH, DENOISE_STAGING); rc != RT_OK) return rc;
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
     VDenoiseArgs a{};
     a.width = desc->width;
     a.height = desc->height;
@@ -2466,129 +2501,42 @@ static int vdenoise_call(rt_handle* h, const rt_vdenoise_desc* desc, int flags, 
         a.ping[0] = h->denoise_scratch + 2 * texels;
         a.ping[1] = h->denoise_scratch + 3 * texels;
     }
-    auto launch = [&](const char*& what) {
-        what = moments_only ? "launch_luminance_moments" : "launch_vdenoise";
+    return frame_call(h, host, planes, DENOISE_STAGING, moments_only ? "launch_luminance_moments" : "launch_vdenoise",
+                      [&](const void* const* in, void* const* out) {
+        a.color = (const float*)in[0]; a.out = (float*)out[0];
+        a.normal = (const float*)in[1]; a.point = (const float*)in[2]; a.albedo = (const float*)in[3]; a.emission = (const float*)in[4];
+        a.moments = (const float*)in[5]; a.history = (const float*)in[6]; a.out_variance = (float*)out[7];
         return moments_only ? launch_luminance_moments(a, h->stream) : launch_vdenoise(a, h->stream);
-    };
-    if (!host) {
-        const float* image = reinterpret_cast<const float*>(h->image);
-        a.color = desc->color ? desc->color : image;
-        a.normal = desc->normal; a.point = desc->point; a.albedo = desc->albedo; a.emission = desc->emission; a.out = desc->out;
-        if (with_moments) { a.moments = desc->moments; a.history = desc->history; }
-        if (with_variance) a.out_variance = desc->out_variance;
-        const bool out_is_image = desc->out >= image && desc->out < image + 4 * h->image_texels;
-        if (a.color == image || out_is_image) {
-            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-        }
-        if (out_is_image) h->generation += 1;   // (the image changes, as by rt_write_image)
-        const char* what = nullptr;
-        HIP_TRY(h, launch(what));
-        return RT_OK;
-    }
-    // host memory: the whole frame through one temporary device buffer, each plane's part of it at a multiple of 256 bytes
-    return staged_chunks(h, staging, 1, 1, "the denoiser's staging planes", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
-        hipError_t e = hipSuccess;
-        what = "hipMemcpyAsync";
-        float* d_ptr[8] = {};
-        for (int c = 0; c < 8 && e == hipSuccess; ++c) {
-            if (!src[c]) continue;
-            d_ptr[c] = reinterpret_cast<float*>(buf + plane_off[c]);
-            if (c < 7) e = hipMemcpyAsync(d_ptr[c], src[c], texels * bytes[c], hipMemcpyHostToDevice, h->stream);
-        }
-        if (e != hipSuccess) return e;
-        a.color = d_ptr[0]; a.normal = d_ptr[1]; a.point = d_ptr[2]; a.albedo = d_ptr[3]; a.emission = d_ptr[4];
-        a.moments = d_ptr[5]; a.history = d_ptr[6];
-        a.out = d_ptr[0]; a.out_variance = d_ptr[7];
-        if ((e = launch(what)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        if ((e = hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
-        if (with_variance) e = hipMemcpyAsync(desc->out_variance, a.out_variance, texels * 4u, hipMemcpyDeviceToHost, h->stream);
-        return e;
     });
 }
 
 int rt_denoise_variance(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, false); }
 int rt_luminance_moments(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, true); }
 
-// ---- adaptive sampling (include/rt_abi.h: rt_adaptive_plan, rt_adaptive_merge and their _host forms; rt_adaptive.hip;
-// host/adaptive.cpp) ----
-// Launched like the denoisers: nothing read but the caller's planes (or the image) and nothing written but the caller's
-// outputs and, by the plan, the handle's adaptive scratch.
-int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc) {
-    std::string err;
-    const int rc = rt2::adaptive_plan_host(desc, err);
-    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
-}
-
-int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) {
-    std::string err;
-    const int rc = rt2::adaptive_merge_host(desc, err);
-    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
-}
-
+// ---- adaptive sampling (include/rt_abi.h: rt_adaptive_plan, rt_adaptive_merge; rt_adaptive.hip; host/adaptive.cpp) ----
 int rt_adaptive_plan(rt_handle* h, const rt_adaptive_plan_desc* desc, int flags) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (flags & ~RT_ADAPTIVE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
     const bool host = (flags & RT_ADAPTIVE_HOST_MEMORY) != 0;
-    {
-        std::string err;
-        if (const int rc = rt2::adaptive_plan_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    }
+    std::string err;
+    if (const int rc = rt2::adaptive_plan_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
     const size_t texels = (size_t)desc->width * desc->height, budget = desc->budget;
     HIP_TRY(h, hipSetDevice(h->device));
-    // the planes of the host-memory path, in staging order: variance, dir, counts, offsets, rays, totals
     static const char* const what_for = "the adaptive plan's staging planes";
-    const size_t bytes[6] = {texels * 4u, texels * 12u, texels * 4u, texels * 4u, budget * sizeof(rt_path_ray), 16u};
-    size_t plane_off[6] = {}, staging = 0;
-    if (host)
-        for (int c = 0; c < 6; ++c) {
-            plane_off[c] = staging;
-            staging = (staging + bytes[c] + 255u) & ~(size_t)255u;
-        }
-    // the scratch: grown on demand, within option max_device_mb
-    const size_t need = adaptive_scratch_bytes(texels);
-    if (h->adaptive_scratch_bytes < need) {
-        if (!fits_cap(h, need + staging, h->adaptive_scratch_bytes))
-            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the adaptive plan's scratch");
-        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
-        free_dev(h->adaptive_scratch);
-        h->adaptive_scratch_bytes = 0;
-        const hipError_t e = hipMalloc(&h->adaptive_scratch, need);
-        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the adaptive plan's scratch");
-        HIP_TRY(h, e);
-        h->adaptive_scratch_bytes = need;
-    } else if (!fits_cap(h, staging)) {
-        return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("option max_device_mb leaves no room for ") + what_for);
-    }
+    const FramePlane planes[6] = {{desc->variance, nullptr, texels * 4u}, {desc->dir, nullptr, texels * 12u}, {nullptr, desc->counts, texels * 4u},
+                                  {nullptr, desc->offsets, texels * 4u}, {nullptr, desc->rays, budget * sizeof(rt_path_ray)},
+                                  {nullptr, desc->totals, 16u}};
+    if (int rc = grow_scratch(h, h->adaptive_scratch, h->adaptive_scratch_bytes, adaptive_scratch_bytes(texels),
+                              host ? staged_bytes(planes) : 0u, "the adaptive plan's scratch", what_for); rc != RT_OK) return rc;
     AdaptivePlanArgs a{};
     a.width = desc->width; a.height = desc->height; a.budget = desc->budget;
     a.min_samples = desc->min_samples; a.max_samples = desc->max_samples; a.first_frame = desc->first_frame;
     for (int k = 0; k < 3; ++k) a.origin[k] = desc->origin[k];
     a.scratch = h->adaptive_scratch;
-    if (!host) {
-        a.variance = desc->variance; a.dir = desc->dir; a.counts = desc->counts; a.offsets = desc->offsets;
-        a.rays = desc->rays; a.totals = desc->totals;
-        HIP_TRY(h, launch_adaptive_plan(a, h->stream));
-        return RT_OK;
-    }
-    // host memory: every plane whole through one temporary device buffer, each at a multiple of 256 bytes
-    return staged_chunks(h, staging, 1, 1, what_for, [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
-        hipError_t e = hipSuccess;
-        what = "hipMemcpyAsync";
-        if ((e = hipMemcpyAsync(buf + plane_off[0], desc->variance, bytes[0], hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(buf + plane_off[1], desc->dir, bytes[1], hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
-        a.variance = reinterpret_cast<const float*>(buf + plane_off[0]);
-        a.dir = reinterpret_cast<const float*>(buf + plane_off[1]);
-        a.counts = reinterpret_cast<uint32_t*>(buf + plane_off[2]);
-        a.offsets = reinterpret_cast<uint32_t*>(buf + plane_off[3]);
-        a.rays = buf + plane_off[4];
-        a.totals = reinterpret_cast<uint32_t*>(buf + plane_off[5]);
-        if (what = "launch_adaptive_plan", (e = launch_adaptive_plan(a, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        void* const dst[4] = {desc->counts, desc->offsets, desc->rays, desc->totals};
-        for (int c = 0; c < 4 && e == hipSuccess; ++c)
-            e = hipMemcpyAsync(dst[c], buf + plane_off[2 + c], bytes[2 + c], hipMemcpyDeviceToHost, h->stream);
-        return e;
+    return frame_call(h, host, planes, what_for, "launch_adaptive_plan", [&](const void* const* in, void* const* out) {
+        a.variance = (const float*)in[0]; a.dir = (const float*)in[1];
+        a.counts = (uint32_t*)out[2]; a.offsets = (uint32_t*)out[3]; a.rays = out[4]; a.totals = (uint32_t*)out[5];
+        return launch_adaptive_plan(a, h->stream);
     });
 }
 
@@ -2596,133 +2544,54 @@ int rt_adaptive_merge(rt_handle* h, const rt_adaptive_merge_desc* desc, int flag
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (flags & ~RT_ADAPTIVE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
     const bool host = (flags & RT_ADAPTIVE_HOST_MEMORY) != 0;
-    {
-        std::string err;
-        if (const int rc = rt2::adaptive_merge_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    }
+    std::string err;
+    if (const int rc = rt2::adaptive_merge_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
     const size_t texels = (size_t)desc->width * desc->height, budget = desc->budget;
-    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
+    // the outputs take the places of color, history and moments
+    const FramePlane planes[7] = {{desc->radiance, nullptr, budget * 16u}, {desc->counts, nullptr, texels * 4u}, {desc->offsets, nullptr, texels * 4u},
+                                  {color, desc->out, texels * 16u}, {desc->history, desc->out_history, texels * 4u},
+                                  {desc->albedo, nullptr, texels * 16u}, {desc->moments, desc->out_moments, texels * 16u}};
     AdaptiveMergeArgs a{};
     a.width = desc->width; a.height = desc->height; a.budget = desc->budget; a.max_history = desc->max_history;
-    if (!host) {
-        const float* image = reinterpret_cast<const float*>(h->image);
-        a.radiance = desc->radiance; a.counts = desc->counts; a.offsets = desc->offsets;
-        a.color = desc->color ? desc->color : image;
-        a.history = desc->history; a.albedo = desc->albedo; a.moments = desc->moments;
-        a.out = desc->out; a.out_history = desc->out_history; a.out_moments = desc->out_moments;
-        const bool out_is_image = desc->out >= image && desc->out < image + 4 * h->image_texels;
-        if (a.color == image || out_is_image) {
-            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-        }
-        if (out_is_image) h->generation += 1;   // (the image changes, as by rt_write_image)
-        HIP_TRY(h, launch_adaptive_merge(a, h->stream));
-        return RT_OK;
-    }
-    // host memory: every plane whole through one temporary device buffer, each at a multiple of 256 bytes; the outputs take
-    // the places of color, history and moments
-    const void* const src[7] = {desc->radiance, desc->counts, desc->offsets, desc->color, desc->history, desc->albedo, desc->moments};
-    const size_t bytes[7] = {budget * 16u, texels * 4u, texels * 4u, texels * 16u, texels * 4u, texels * 16u, texels * 16u};
-    size_t plane_off[7] = {}, staging = 0;
-    for (int c = 0; c < 7; ++c) {
-        if (!src[c]) continue;
-        plane_off[c] = staging;
-        staging = (staging + bytes[c] + 255u) & ~(size_t)255u;
-    }
-    if (!fits_cap(h, staging)) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the adaptive merge's staging planes");
-    return staged_chunks(h, staging, 1, 1, "the adaptive merge's staging planes", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
-        hipError_t e = hipSuccess;
-        what = "hipMemcpyAsync";
-        void* d_ptr[7] = {};
-        for (int c = 0; c < 7 && e == hipSuccess; ++c) {
-            if (!src[c]) continue;
-            d_ptr[c] = buf + plane_off[c];
-            e = hipMemcpyAsync(d_ptr[c], src[c], bytes[c], hipMemcpyHostToDevice, h->stream);
-        }
-        if (e != hipSuccess) return e;
-        a.radiance = (const float*)d_ptr[0]; a.counts = (const uint32_t*)d_ptr[1]; a.offsets = (const uint32_t*)d_ptr[2];
-        a.color = (const float*)d_ptr[3]; a.history = (const float*)d_ptr[4]; a.albedo = (const float*)d_ptr[5];
-        a.moments = (const float*)d_ptr[6];
-        a.out = (float*)d_ptr[3]; a.out_history = (float*)d_ptr[4]; a.out_moments = (float*)d_ptr[6];
-        if (what = "launch_adaptive_merge", (e = launch_adaptive_merge(a, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        if ((e = hipMemcpyAsync(desc->out, a.out, bytes[3], hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(desc->out_history, a.out_history, bytes[4], hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
-        if (desc->out_moments) e = hipMemcpyAsync(desc->out_moments, a.out_moments, bytes[6], hipMemcpyDeviceToHost, h->stream);
-        return e;
+    return frame_call(h, host, planes, "the adaptive merge's staging planes", "launch_adaptive_merge", [&](const void* const* in, void* const* out) {
+        a.radiance = (const float*)in[0]; a.counts = (const uint32_t*)in[1]; a.offsets = (const uint32_t*)in[2];
+        a.color = (const float*)in[3]; a.out = (float*)out[3]; a.history = (const float*)in[4]; a.out_history = (float*)out[4];
+        a.albedo = (const float*)in[5]; a.moments = (const float*)in[6]; a.out_moments = (float*)out[6];
+        return launch_adaptive_merge(a, h->stream);
     });
 }
 
-// ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate, rt_temporal_accumulate_host; rt_temporal.hip;
-// host/temporal.cpp) ----
-// Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs;
-// no scratch is kept.
-int rt_temporal_accumulate_host(const rt_temporal_desc* desc) {
-    std::string err;
-    const int rc = rt2::temporal_host(desc, err);
-    return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
-}
-
+// ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate; rt_temporal.hip; host/temporal.cpp) ----
+// No scratch is kept.
 int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
     const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
-    {
-        std::string err;
-        if (const int rc = rt2::temporal_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    }
+    std::string err;
+    if (const int rc = rt2::temporal_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
     const size_t texels = (size_t)desc->width * desc->height;
-    if (!desc->color && texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
+    // `out` takes the colour plane's place
+    const FramePlane planes[11] = {{color, desc->out, texels * 16u}, {desc->point, nullptr, texels * 12u}, {desc->normal, nullptr, texels * 12u},
+                                   {desc->object, nullptr, texels * 4u}, {desc->prev_color, nullptr, texels * 16u},
+                                   {desc->prev_history, nullptr, texels * 4u}, {desc->prev_point, nullptr, texels * 12u},
+                                   {desc->prev_normal, nullptr, texels * 12u}, {desc->prev_object, nullptr, texels * 4u},
+                                   {nullptr, desc->out_history, texels * 4u}, {nullptr, desc->motion, texels * 8u}};
     TemporalArgs a{};
     a.call = rt2::temporal_call(desc);
-    if (!host) {
-        const float* image = reinterpret_cast<const float*>(h->image);
-        a.color = desc->color ? desc->color : image;
-        a.point = desc->point; a.normal = desc->normal; a.object = desc->object;
-        a.prev_color = desc->prev_color; a.prev_history = desc->prev_history; a.prev_point = desc->prev_point;
-        a.prev_normal = desc->prev_normal; a.prev_object = desc->prev_object;
-        a.out = desc->out; a.out_history = desc->out_history; a.motion = desc->motion;
-        const bool out_is_image = desc->out >= image && desc->out < image + 4 * h->image_texels;
-        if (a.color == image || out_is_image) {
-            if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-        }
-        if (out_is_image) h->generation += 1;   // (the image changes, as by rt_write_image)
-        HIP_TRY(h, launch_temporal(a, h->stream));
-        return RT_OK;
-    }
-    // host memory: every plane whole through one temporary device buffer (a gather can reach any row: no bands); each
-    // plane's part of it starts at a multiple of 256 bytes, and `out` takes the colour plane's place
-    const void* const src[12] = {desc->color, desc->point, desc->normal, desc->object, desc->prev_color, desc->prev_history,
-                                 desc->prev_point, desc->prev_normal, desc->prev_object, nullptr, desc->out_history, desc->motion};
-    static const uint32_t bytes[12] = {16, 12, 12, 4, 16, 4, 12, 12, 4, 0, 4, 8};
-    size_t plane_off[12] = {}, off = 0;
-    for (int c = 0; c < 12; ++c) {
-        if (!src[c]) continue;
-        plane_off[c] = off;
-        off = (off + texels * bytes[c] + 255u) & ~(size_t)255u;
-    }
-    if (!fits_cap(h, off)) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the staging planes of temporal accumulation");
-    return staged_chunks(h, off, 1, 1, "the staging planes of temporal accumulation", [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
-        hipError_t e = hipSuccess;
-        what = "hipMemcpyAsync";
-        void* d_ptr[12] = {};
-        for (int c = 0; c < 12 && e == hipSuccess; ++c) {
-            if (!src[c]) continue;
-            d_ptr[c] = buf + plane_off[c];
-            if (c < 9) e = hipMemcpyAsync(d_ptr[c], src[c], texels * bytes[c], hipMemcpyHostToDevice, h->stream);
-        }
-        if (e != hipSuccess) return e;
-        a.color = (const float*)d_ptr[0]; a.point = (const float*)d_ptr[1]; a.normal = (const float*)d_ptr[2];
-        a.object = (const uint32_t*)d_ptr[3]; a.prev_color = (const float*)d_ptr[4]; a.prev_history = (const float*)d_ptr[5];
-        a.prev_point = (const float*)d_ptr[6]; a.prev_normal = (const float*)d_ptr[7]; a.prev_object = (const uint32_t*)d_ptr[8];
-        a.out = (float*)d_ptr[0]; a.out_history = (float*)d_ptr[10]; a.motion = (float*)d_ptr[11];
-        if (what = "launch_temporal", (e = launch_temporal(a, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        if ((e = hipMemcpyAsync(desc->out, a.out, texels * 16u, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(desc->out_history, a.out_history, texels * 4u, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return e;
-        if (desc->motion) e = hipMemcpyAsync(desc->motion, a.motion, texels * 8u, hipMemcpyDeviceToHost, h->stream);
-        return e;
+    return frame_call(h, host, planes, "the staging planes of temporal accumulation", "launch_temporal", [&](const void* const* in, void* const* out) {
+        a.color = (const float*)in[0]; a.out = (float*)out[0]; a.point = (const float*)in[1]; a.normal = (const float*)in[2];
+        a.object = (const uint32_t*)in[3]; a.prev_color = (const float*)in[4]; a.prev_history = (const float*)in[5];
+        a.prev_point = (const float*)in[6]; a.prev_normal = (const float*)in[7]; a.prev_object = (const uint32_t*)in[8];
+        a.out_history = (float*)out[9]; a.motion = (float*)out[10];
+        return launch_temporal(a, h->stream);
     });
 }
 

@@ -24,50 +24,119 @@ from .scene import Scene, SceneArrays
 DENOISE_SIGMA_COLOR, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_POINT = 4.0, 0.3, 1.0
 
 
-def _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point):
-    return A.DenoiseDesc(struct_bytes=C.sizeof(A.DenoiseDesc), width=W, height=H, iterations=int(iterations),
-                         sigma_color=float(sigma_color), sigma_normal=float(sigma_normal), sigma_point=float(sigma_point))
+# ---- the planes of the frame passes (denoise, denoise_variance / luminance_moments, temporal_accumulate, adaptive_plan /
+# adaptive_merge): one set of helpers over the tables of _abi, plane -> (numpy dtype, components per texel) ----
+def _plane_shape(table, k, W, H):
+    """(H, W, n), (H, W) for n = 0, or the shape itself where a call's own table names one (a plane that is not frame-shaped)."""
+    n = table[k][1]
+    return n if isinstance(n, tuple) else (H, W, n) if n else (H, W)
 
 
-def _denoise_numpy_planes(d, W, H, planes, color):
-    """Points the desc's input planes at contiguous float32 copies (or the arrays themselves); returns what must stay alive."""
+def _numpy_inputs(d, table, W, H, planes):
+    """Points the desc at contiguous copies of the numpy inputs (or the arrays themselves); returns what must stay alive."""
     keep = {}
-    for k, v in dict(planes, color=color).items():
-        a = np.ascontiguousarray(v, np.float32)
-        if a.shape != (H, W, A.DENOISE_PLANES[k]):
-            raise ValueError(f"plane {k} must have shape {(H, W, A.DENOISE_PLANES[k])}, not {a.shape}")
+    for k, v in planes.items():
+        a = np.ascontiguousarray(v, np.dtype(table[k][0]))
+        if a.shape != _plane_shape(table, k, W, H):
+            raise ValueError(f"plane {k} must have shape {_plane_shape(table, k, W, H)}, not {a.shape}")
         keep[k] = a
         setattr(d, k, a.ctypes.data)
     return keep
 
 
-def _denoise_numpy_out(d, W, H, out):
-    if out is None:
-        out = np.zeros((H, W, 4), np.float32)
-    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == (H, W, 4) and out.flags.c_contiguous
-              and out.flags.writeable):
-        raise ValueError(f"out must be a writeable contiguous float32 array of shape {(H, W, 4)}")
-    d.out = out.ctypes.data
-    return out
+def _numpy_outputs(d, table, W, H, outs):
+    """Points the desc at the numpy outputs -- outs: name -> None or False (not asked for), True (a new array) or the array to
+    fill -- and returns them by name (None: not asked for)."""
+    res = {}
+    for k, v in outs.items():
+        if v is None or v is False:
+            res[k] = None
+            continue
+        shape, dt = _plane_shape(table, k, W, H), np.dtype(table[k][0])
+        if v is True:
+            v = np.zeros(shape, dt)
+        elif not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous and v.flags.writeable):
+            raise ValueError(f"{k} must be a writeable contiguous {dt} array of shape {shape}")
+        res[k] = v
+        setattr(d, k, v.ctypes.data)
+    return res
+
+
+def _tensor_planes(d, device, table, W, H, planes, outs):
+    """The same for torch tensors on cuda:`device`: checks the inputs and the outputs that are given (device, dtype -- a
+    uint32 plane is an int32 tensor holding the bits, or uint32 --, layout, shape), makes the outputs asked for with True,
+    points the desc at all of them and returns the outputs by name (None: not asked for)."""
+    import torch
+    dev = torch.device("cuda", device)
+    given = dict(planes, **{k: v for k, v in outs.items() if v is not None and v is not True and v is not False})
+    for k, v in given.items():
+        if not isinstance(v, torch.Tensor):
+            raise ValueError("mix of device tensors and host arrays")
+        if v.device.type != "cuda" or v.device.index != device:
+            raise ValueError(f"plane {k} must be on cuda:{device}, not {v.device}")
+        kinds = (torch.float32,) if table[k][0] == "<f4" else (torch.int32, getattr(torch, "uint32", torch.int32))
+        if v.dtype not in kinds or not v.is_contiguous() or tuple(v.shape) != _plane_shape(table, k, W, H):
+            name = str(kinds[0]).replace("torch.", "")
+            raise ValueError(f"plane {k} must be a contiguous {name} tensor of shape {_plane_shape(table, k, W, H)}")
+    res = {}
+    for k, v in outs.items():
+        if v is True:
+            v = given[k] = torch.empty(_plane_shape(table, k, W, H), dtype=torch.float32 if table[k][0] == "<f4" else torch.int32, device=dev)
+        res[k] = None if v is None or v is False else v
+    for k, v in given.items():
+        setattr(d, k, v.data_ptr())
+    return res
+
+
+def _host_call(name, d):
+    """A *_host entry point of the library on a filled desc."""
+    L = load()
+    rc = getattr(L, name)(C.byref(d))
+    if rc < 0:
+        raise RtError(rc, L.rt_last_error(None).decode())
+
+
+def _host_frame_call(name, d, table, W, H, planes, outs):
+    """A *_host entry point on numpy planes; returns the outputs by name."""
+    keep = _numpy_inputs(d, table, W, H, planes)
+    res = _numpy_outputs(d, table, W, H, outs)
+    _host_call(name, d)
+    del keep
+    return res
+
+
+def _new_or(out):
+    return True if out is None else out
+
+
+def _frame_size(plane):
+    """(W, H) of an (H, W) or (H, W, n) plane."""
+    H, W = (int(v) for v in np.shape(plane)[:2])
+    return W, H
+
+
+def _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point):
+    return A.DenoiseDesc(struct_bytes=C.sizeof(A.DenoiseDesc), width=W, height=H, iterations=int(iterations),
+                         sigma_color=float(sigma_color), sigma_normal=float(sigma_normal), sigma_point=float(sigma_point))
+
+
+def _denoise_inputs(guides, color):
+    """The desc's input planes by name and the frame's size."""
+    planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
+    if "normal" not in planes or "point" not in planes:
+        raise ValueError("guides must hold the normal and point planes of render_gbuffer")
+    if color is not None:
+        planes["color"] = color
+    return (planes, *_frame_size(planes["normal"]))
 
 
 def denoise_host(guides, color, iterations=3, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
                  sigma_point=DENOISE_SIGMA_POINT, out=None):
     """rt_denoise_host: the denoiser's definition on the CPU (no device), with RayTracer.denoise's arguments for numpy
     planes.  RayTracer.denoise computes the same bits on the GPU."""
-    planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
-    if "normal" not in planes or "point" not in planes:
-        raise ValueError("guides must hold the normal and point planes of render_gbuffer")
-    H, W = (int(v) for v in np.shape(planes["normal"])[:2])
+    planes, W, H = _denoise_inputs(guides, color)
     d = _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point)
-    keep = _denoise_numpy_planes(d, W, H, planes, color)
-    res = _denoise_numpy_out(d, W, H, out)
-    L = load()
-    rc = L.rt_denoise_host(C.byref(d))
-    del keep
-    if rc < 0:
-        raise RtError(rc, L.rt_last_error(None).decode())
-    return res
+    return _host_frame_call("rt_denoise_host", d, A.DENOISE_PLANES, W, H, planes, {"out": _new_or(out)})["out"]
 
 
 # Temporal accumulation's default thresholds (RayTracer.temporal_accumulate, temporal_accumulate_host): a tap's hit point
@@ -101,38 +170,7 @@ def _temporal_inputs(guides, prev_guides, prev_color, prev_history, color):
         planes["prev_object"] = prev_guides["object"]
     if color is not None:
         planes["color"] = color
-    H, W = (int(v) for v in np.shape(planes["normal"])[:2])
-    return planes, W, H
-
-
-def _temporal_shape(k, W, H):
-    n = A.TEMPORAL_PLANES[k][1]
-    return (H, W, n) if n else (H, W)
-
-
-def _temporal_numpy(d, W, H, planes, out, out_history, motion):
-    """Points the desc at contiguous copies of the numpy inputs (or the arrays themselves) and at the outputs; returns what
-    must stay alive and the three outputs (motion: None when it is not asked for)."""
-    keep = {}
-    for k, v in planes.items():
-        a = np.ascontiguousarray(v, np.dtype(A.TEMPORAL_PLANES[k][0]))
-        if a.shape != _temporal_shape(k, W, H):
-            raise ValueError(f"plane {k} must have shape {_temporal_shape(k, W, H)}, not {a.shape}")
-        keep[k] = a
-        setattr(d, k, a.ctypes.data)
-    res = {}
-    for k, v in (("out", out), ("out_history", out_history), ("motion", motion)):
-        if v is None or v is False:
-            res[k] = None
-            continue
-        if v is True:
-            v = np.zeros(_temporal_shape(k, W, H), np.float32)
-        elif not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.shape == _temporal_shape(k, W, H) and v.flags.c_contiguous
-                  and v.flags.writeable):
-            raise ValueError(f"{k} must be a writeable contiguous float32 array of shape {_temporal_shape(k, W, H)}")
-        res[k] = v
-        setattr(d, k, v.ctypes.data)
-    return keep, res
+    return (planes, *_frame_size(planes["normal"]))
 
 
 def _temporal_result(res):
@@ -149,13 +187,8 @@ def temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_
     if color is None:
         raise ValueError("color is required on the host")
     d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
-    keep, res = _temporal_numpy(d, W, H, planes, True if out is None else out, True if out_history is None else out_history, motion)
-    L = load()
-    rc = L.rt_temporal_accumulate_host(C.byref(d))
-    del keep
-    if rc < 0:
-        raise RtError(rc, L.rt_last_error(None).decode())
-    return _temporal_result(res)
+    outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
+    return _temporal_result(_host_frame_call("rt_temporal_accumulate_host", d, A.TEMPORAL_PLANES, W, H, planes, outs))
 
 
 # The variance-guided denoiser's defaults (RayTracer.denoise_variance, denoise_variance_host): a luminance difference of
@@ -164,23 +197,13 @@ def temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_
 VDENOISE_SIGMA_LUMINANCE, VDENOISE_MIN_HISTORY = 4.0, 4.0
 
 
-def _vdenoise_shape(k, W, H):
-    n = A.VDENOISE_PLANES[k]
-    return (H, W, n) if n else (H, W)
-
-
 def _vdenoise_inputs(guides, color, moments, history):
     """The desc's input planes by name and the frame's size."""
-    planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
-    if "normal" not in planes or "point" not in planes:
-        raise ValueError("guides must hold the normal and point planes of render_gbuffer")
+    planes, W, H = _denoise_inputs(guides, color)
     if (moments is None) != (history is None):
         raise ValueError("moments and history go together")
     if moments is not None:
         planes.update(moments=moments, history=history)
-    if color is not None:
-        planes["color"] = color
-    H, W = (int(v) for v in np.shape(planes["normal"])[:2])
     return planes, W, H
 
 
@@ -189,31 +212,6 @@ def _vdenoise_desc(W, H, iterations=1, sigma_luminance=VDENOISE_SIGMA_LUMINANCE,
     return A.VDenoiseDesc(struct_bytes=C.sizeof(A.VDenoiseDesc), width=W, height=H, iterations=int(iterations),
                           sigma_luminance=float(sigma_luminance), sigma_normal=float(sigma_normal), sigma_point=float(sigma_point),
                           min_history=float(min_history))
-
-
-def _vdenoise_numpy(d, W, H, planes, outs):
-    """Points the desc at contiguous float32 copies of the numpy inputs (or the arrays themselves) and at the outputs
-    (None: not asked for; True: a new array); returns what must stay alive and the outputs by name."""
-    keep = {}
-    for k, v in planes.items():
-        a = np.ascontiguousarray(v, np.float32)
-        if a.shape != _vdenoise_shape(k, W, H):
-            raise ValueError(f"plane {k} must have shape {_vdenoise_shape(k, W, H)}, not {a.shape}")
-        keep[k] = a
-        setattr(d, k, a.ctypes.data)
-    res = {}
-    for k, v in outs.items():
-        if v is None or v is False:
-            res[k] = None
-            continue
-        if v is True:
-            v = np.zeros(_vdenoise_shape(k, W, H), np.float32)
-        elif not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.shape == _vdenoise_shape(k, W, H) and v.flags.c_contiguous
-                  and v.flags.writeable):
-            raise ValueError(f"{k} must be a writeable contiguous float32 array of shape {_vdenoise_shape(k, W, H)}")
-        res[k] = v
-        setattr(d, k, v.ctypes.data)
-    return keep, res
 
 
 def _vdenoise_result(res):
@@ -229,13 +227,8 @@ def denoise_variance_host(guides, color, iterations=3, sigma_luminance=VDENOISE_
         raise ValueError("color is required on the host")
     planes, W, H = _vdenoise_inputs(guides, color, moments, history)
     d = _vdenoise_desc(W, H, iterations, sigma_luminance, sigma_normal, sigma_point, min_history)
-    keep, res = _vdenoise_numpy(d, W, H, planes, {"out": True if out is None else out, "out_variance": out_variance})
-    L = load()
-    rc = L.rt_denoise_variance_host(C.byref(d))
-    del keep
-    if rc < 0:
-        raise RtError(rc, L.rt_last_error(None).decode())
-    return _vdenoise_result(res)
+    outs = {"out": _new_or(out), "out_variance": out_variance}
+    return _vdenoise_result(_host_frame_call("rt_denoise_variance_host", d, A.VDENOISE_PLANES, W, H, planes, outs))
 
 
 def luminance_moments_host(guides, color, out=None):
@@ -243,24 +236,12 @@ def luminance_moments_host(guides, color, out=None):
     if color is None:
         raise ValueError("color is required on the host")
     planes, W, H = _vdenoise_inputs(guides, color, None, None)
-    d = _vdenoise_desc(W, H)
-    keep, res = _vdenoise_numpy(d, W, H, planes, {"out": True if out is None else out})
-    L = load()
-    rc = L.rt_luminance_moments_host(C.byref(d))
-    del keep
-    if rc < 0:
-        raise RtError(rc, L.rt_last_error(None).decode())
-    return res["out"]
+    return _host_frame_call("rt_luminance_moments_host", _vdenoise_desc(W, H), A.VDENOISE_PLANES, W, H, planes, {"out": _new_or(out)})["out"]
 
 
 # Adaptive sampling's defaults (RayTracer.adaptive_plan / adaptive_samples, adaptive_plan_host): every texel gets at least
 # one new sample, so that its variance estimate keeps moving, and at most 16, so that one firefly cannot take the budget.
 ADAPTIVE_MIN_SAMPLES, ADAPTIVE_MAX_SAMPLES = 1, 16
-
-
-def _adaptive_shape(planes, k, W, H):
-    n = planes[k][1]
-    return (H, W, n) if n else (H, W)
 
 
 def _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame):
@@ -283,66 +264,37 @@ def _adaptive_merge_desc(W, H, budget, max_history):
     return A.AdaptiveMergeDesc(struct_bytes=C.sizeof(A.AdaptiveMergeDesc), width=W, height=H, budget=budget, max_history=float(max_history))
 
 
-def _adaptive_numpy_inputs(d, table, W, H, planes):
-    """Points the desc at contiguous copies of the numpy inputs (or the arrays themselves); returns what must stay alive."""
-    keep = {}
-    for k, v in planes.items():
-        a = np.ascontiguousarray(v, np.dtype(table[k][0]))
-        if a.shape != _adaptive_shape(table, k, W, H):
-            raise ValueError(f"plane {k} must have shape {_adaptive_shape(table, k, W, H)}, not {a.shape}")
-        keep[k] = a
-        setattr(d, k, a.ctypes.data)
-    return keep
+def _adaptive_plan_call(variance, dirs, origin, budget, min_samples, max_samples, first_frame, tensors):
+    """The plan's desc, its plane table -- _abi's and the two planes that are not frame-shaped: the packed records, as
+    PATH_RAY_DTYPE on the host and as (budget, 8) float32 in a tensor, and the totals --, its inputs and its outputs."""
+    H, W = (int(v) for v in np.shape(variance)) if np.ndim(variance) == 2 else (0, 0)
+    d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
+    rays = ("<f4", (d.budget, 8)) if tensors else (A.PATH_RAY_DTYPE, (d.budget,))
+    table = dict(A.ADAPTIVE_PLAN_PLANES, rays=rays, totals=("<u4", (4,)))
+    return d, table, W, H, {"variance": variance, "dir": dirs}, {"counts": True, "offsets": True, "rays": True, "totals": True}
 
 
-def _adaptive_numpy_outputs(d, table, W, H, outs):
-    """outs: name -> None (a new array) or the array to fill; returns the arrays by name."""
-    res = {}
-    for k, v in outs.items():
-        shape, dt = _adaptive_shape(table, k, W, H), np.dtype(table[k][0])
-        if v is None:
-            v = np.zeros(shape, dt)
-        elif not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous and v.flags.writeable):
-            raise ValueError(f"{k} must be a writeable contiguous {dt} array of shape {shape}")
-        res[k] = v
-        setattr(d, k, v.ctypes.data)
-    return res
+def _adaptive_plan_result(res):
+    return res["counts"], res["offsets"], res["rays"], res["totals"]
 
 
-def _adaptive_plan_numpy(d, W, H, variance, dirs):
-    keep = _adaptive_numpy_inputs(d, A.ADAPTIVE_PLAN_PLANES, W, H, {"variance": variance, "dir": dirs})
-    res = _adaptive_numpy_outputs(d, A.ADAPTIVE_PLAN_PLANES, W, H, {"counts": None, "offsets": None})
-    res["rays"] = np.zeros(d.budget, A.PATH_RAY_DTYPE)
-    res["totals"] = np.zeros(4, np.uint32)
-    d.rays, d.totals = res["rays"].ctypes.data, res["totals"].ctypes.data
-    return keep, res
-
-
-def _adaptive_merge_numpy(d, W, H, radiance, planes, outs):
-    r = np.ascontiguousarray(radiance, np.float32)
-    if r.shape != (d.budget, 4):
-        raise ValueError(f"radiance must have shape {(d.budget, 4)}, not {r.shape}")
-    d.radiance = r.ctypes.data
-    keep = _adaptive_numpy_inputs(d, A.ADAPTIVE_MERGE_PLANES, W, H, planes)
-    keep["radiance"] = r
-    return keep, _adaptive_numpy_outputs(d, A.ADAPTIVE_MERGE_PLANES, W, H, outs)
-
-
-def _adaptive_merge_planes(counts, offsets, color, history, albedo, moments, out, out_history, out_moments):
-    """The merge's inputs and outputs by name, and the frame's size (from `counts`)."""
+def _adaptive_merge_call(radiance, counts, offsets, color, history, max_history, albedo, moments, out, out_history, out_moments):
+    """The merge's desc, its plane table -- _abi's and `radiance`, which is not frame-shaped --, its inputs and its outputs;
+    the frame's size is that of `counts`."""
     if moments is None and out_moments is not None:
         raise ValueError("out_moments needs moments")
-    planes = {"counts": counts, "offsets": offsets, "history": history}
+    planes = {"radiance": radiance, "counts": counts, "offsets": offsets, "history": history}
     for k, v in (("color", color), ("albedo", albedo), ("moments", moments)):
         if v is not None:
             planes[k] = v
-    outs = {"out": out, "out_history": out_history}
+    outs = {"out": _new_or(out), "out_history": _new_or(out_history)}
     if moments is not None:
-        outs["out_moments"] = out_moments
+        outs["out_moments"] = _new_or(out_moments)
     H, W = (int(v) for v in np.shape(counts)[:2]) if np.ndim(counts) == 2 else (0, 0)
     if W == 0 or H == 0:
         raise ValueError("counts must have shape (H, W)")
-    return planes, outs, W, H
+    d = _adaptive_merge_desc(W, H, np.shape(radiance)[0] if np.ndim(radiance) == 2 else 0, max_history)
+    return d, dict(A.ADAPTIVE_MERGE_PLANES, radiance=("<f4", (d.budget, 4))), W, H, planes, outs
 
 
 def _adaptive_merge_result(res):
@@ -352,15 +304,8 @@ def _adaptive_merge_result(res):
 def adaptive_plan_host(variance, dirs, origin, budget, min_samples=ADAPTIVE_MIN_SAMPLES, max_samples=ADAPTIVE_MAX_SAMPLES, first_frame=0):
     """rt_adaptive_plan_host: the plan's definition on the CPU (no device), with RayTracer.adaptive_plan's arguments for numpy
     planes.  RayTracer.adaptive_plan computes the same bits on the GPU."""
-    H, W = (int(v) for v in np.shape(variance)) if np.ndim(variance) == 2 else (0, 0)
-    d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
-    keep, res = _adaptive_plan_numpy(d, W, H, variance, dirs)
-    L = load()
-    rc = L.rt_adaptive_plan_host(C.byref(d))
-    del keep
-    if rc < 0:
-        raise RtError(rc, L.rt_last_error(None).decode())
-    return res["counts"], res["offsets"], res["rays"], res["totals"]
+    d, table, W, H, planes, outs = _adaptive_plan_call(variance, dirs, origin, budget, min_samples, max_samples, first_frame, False)
+    return _adaptive_plan_result(_host_frame_call("rt_adaptive_plan_host", d, table, W, H, planes, outs))
 
 
 def adaptive_merge_host(radiance, counts, offsets, color, history, max_history=float("inf"), albedo=None, moments=None, out=None,
@@ -369,15 +314,9 @@ def adaptive_merge_host(radiance, counts, offsets, color, history, max_history=f
     numpy planes.  RayTracer.adaptive_merge computes the same bits on the GPU."""
     if color is None:
         raise ValueError("color is required on the host")
-    planes, outs, W, H = _adaptive_merge_planes(counts, offsets, color, history, albedo, moments, out, out_history, out_moments)
-    d = _adaptive_merge_desc(W, H, np.shape(radiance)[0], max_history)
-    keep, res = _adaptive_merge_numpy(d, W, H, radiance, planes, outs)
-    L = load()
-    rc = L.rt_adaptive_merge_host(C.byref(d))
-    del keep
-    if rc < 0:
-        raise RtError(rc, L.rt_last_error(None).decode())
-    return _adaptive_merge_result(res)
+    d, table, W, H, planes, outs = _adaptive_merge_call(radiance, counts, offsets, color, history, max_history, albedo, moments, out,
+                                                        out_history, out_moments)
+    return _adaptive_merge_result(_host_frame_call("rt_adaptive_merge_host", d, table, W, H, planes, outs))
 
 
 class RayTracer:
@@ -452,11 +391,8 @@ class RayTracer:
                 raise ValueError("device triangles must have shape (n, 24)")
             t = t.contiguous()
             n = t.shape[0]
-            cur = torch.cuda.current_stream(t.device)
-            ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=t.device)
-            ext.wait_stream(cur)
-            self._check(self._L.rt_refit_triangles(self._h, t.data_ptr() if n else None, int(first), n, 0))
-            cur.wait_stream(ext)   # (the call has read t when it returns; later work on the stream follows the refit)
+            # (the call has read t when it returns; later work on the stream follows the refit)
+            self._on_handle_stream(lambda: self._check(self._L.rt_refit_triangles(self._h, t.data_ptr() if n else None, int(first), n, 0)))
             return
         t = np.ascontiguousarray(triangles).view(A.TRI_DTYPE).reshape(-1)
         self._check(self._L.rt_refit_triangles(self._h, t.ctypes.data if t.shape[0] else None, int(first), t.shape[0],
@@ -726,11 +662,7 @@ class RayTracer:
             dt, k = A.GBUFFER_CHANNELS[c]
             out[c] = torch.empty((H, W, k) if k else (H, W), dtype=kinds[dt], device=dev)
             setattr(g, c, out[c].data_ptr() if out[c].numel() else None)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
-        ext.wait_stream(cur)
-        self._check(self._L.rt_render_gbuffer(self._h, C.byref(params), C.byref(g), 0))
-        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launch: _device_query)
+        self._on_handle_stream(lambda: self._check(self._L.rt_render_gbuffer(self._h, C.byref(params), C.byref(g), 0)))
         return out
 
     def denoise(self, guides, color=None, iterations=3, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
@@ -745,73 +677,25 @@ class RayTracer:
         on this handle's device: an asynchronous call ordered after the current torch stream's work, as
         render_gbuffer(device=True) orders itself; returns a tensor; there color=None denoises the handle's image, into
         `out` or a new tensor."""
-        planes = {k: guides[k] for k in ("normal", "point", "albedo", "emission") if k in guides}
-        if "normal" not in planes or "point" not in planes:
-            raise ValueError("guides must hold the normal and point planes of render_gbuffer")
-        H, W = (int(v) for v in planes["normal"].shape[:2])
+        planes, W, H = _denoise_inputs(guides, color)
         d = _denoise_desc(W, H, iterations, sigma_color, sigma_normal, sigma_point)
-        if not any(hasattr(v, "data_ptr") for v in (*planes.values(), color, out)):
-            if color is None:
-                raise ValueError("color is required with numpy planes (color=None names the device image)")
-            keep = _denoise_numpy_planes(d, W, H, planes, color)
-            res = _denoise_numpy_out(d, W, H, out)
-            self._check(self._L.rt_denoise(self._h, C.byref(d), A.DENOISE_HOST_MEMORY))
-            del keep
-            return res
-        import torch
-        given = dict(planes, **({"color": color} if color is not None else {}), **({"out": out} if out is not None else {}))
-        for k, v in given.items():
-            if not isinstance(v, torch.Tensor):
-                raise ValueError("mix of device tensors and host arrays")
-            if v.device.type != "cuda" or v.device.index != self.device:
-                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
-            if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != (H, W, A.DENOISE_PLANES[k]):
-                raise ValueError(f"plane {k} must be a contiguous float32 tensor of shape {(H, W, A.DENOISE_PLANES[k])}")
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
-        for k, v in dict(given, out=out).items():
-            setattr(d, k, v.data_ptr())
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
-        ext.wait_stream(cur)
-        self._check(self._L.rt_denoise(self._h, C.byref(d), 0))
-        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
-        return out
+        return self._frame_call("rt_denoise", A.DENOISE_HOST_MEMORY, d, A.DENOISE_PLANES, W, H, planes, {"out": _new_or(out)})["out"]
 
-    def _vdenoise_call(self, fn, d, W, H, planes, outs):
-        """rt_denoise_variance / rt_luminance_moments (`fn`: the name) on numpy planes (synchronous) or on torch tensors of this
-        handle's device (asynchronous, ordered after the current torch stream's work); outs: name -> None (not asked
-        for), True (a new one) or the array / tensor to fill."""
+    def _frame_call(self, fn, host_flag, d, table, W, H, planes, outs):
+        """A frame pass (`fn`: the entry point's name) on numpy planes (synchronous, under `host_flag`) or on torch tensors of
+        this handle's device (asynchronous, ordered after the current torch stream's work).  planes: the inputs by name,
+        where a pass with a colour plane takes the handle's image when tensors come without one; outs: name -> None or
+        False (not asked for), True (a new one) or the array / tensor to fill.  Returns the outputs by name."""
         if not any(hasattr(v, "data_ptr") for v in (*planes.values(), *outs.values())):
-            if "color" not in planes:
+            if "color" in table and "color" not in planes:
                 raise ValueError("color is required with numpy planes (color=None names the device image)")
-            keep, res = _vdenoise_numpy(d, W, H, planes, outs)
-            self._check(getattr(self._L, fn)(self._h, C.byref(d), A.VDENOISE_HOST_MEMORY))
+            keep = _numpy_inputs(d, table, W, H, planes)
+            res = _numpy_outputs(d, table, W, H, outs)
+            self._check(getattr(self._L, fn)(self._h, C.byref(d), host_flag))
             del keep
             return res
-        import torch
-        dev = torch.device("cuda", self.device)
-        given = dict(planes, **{k: v for k, v in outs.items() if v is not None and v is not True and v is not False})
-        for k, v in given.items():
-            if not isinstance(v, torch.Tensor):
-                raise ValueError("mix of device tensors and host arrays")
-            if v.device.type != "cuda" or v.device.index != self.device:
-                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
-            if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != _vdenoise_shape(k, W, H):
-                raise ValueError(f"plane {k} must be a contiguous float32 tensor of shape {_vdenoise_shape(k, W, H)}")
-        res = {}
-        for k, v in outs.items():
-            if v is True:
-                v = given[k] = torch.empty(_vdenoise_shape(k, W, H), dtype=torch.float32, device=dev)
-            res[k] = None if v is None or v is False else v
-        for k, v in given.items():
-            setattr(d, k, v.data_ptr())
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
-        ext.wait_stream(cur)
-        self._check(getattr(self._L, fn)(self._h, C.byref(d), 0))
-        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
+        res = _tensor_planes(d, self.device, table, W, H, planes, outs)
+        self._on_handle_stream(lambda: self._check(getattr(self._L, fn)(self._h, C.byref(d), 0)))
         return res
 
     def denoise_variance(self, guides, color=None, iterations=3, sigma_luminance=VDENOISE_SIGMA_LUMINANCE,
@@ -831,8 +715,8 @@ class RayTracer:
         color=None denoises the handle's image."""
         planes, W, H = _vdenoise_inputs(guides, color, moments, history)
         d = _vdenoise_desc(W, H, iterations, sigma_luminance, sigma_normal, sigma_point, min_history)
-        res = self._vdenoise_call("rt_denoise_variance", d, W, H, planes,
-                                  {"out": True if out is None else out, "out_variance": out_variance})
+        res = self._frame_call("rt_denoise_variance", A.VDENOISE_HOST_MEMORY, d, A.VDENOISE_PLANES, W, H, planes,
+                               {"out": _new_or(out), "out_variance": out_variance})
         return _vdenoise_result(res)
 
     def luminance_moments(self, guides, color=None, out=None):
@@ -841,20 +725,9 @@ class RayTracer:
         tensor.  Accumulated over frames by temporal_accumulate (color = this, prev_color = the accumulated moments), it
         is what denoise_variance takes as `moments`.  numpy planes or torch tensors, as denoise_variance."""
         planes, W, H = _vdenoise_inputs(guides, color, None, None)
-        res = self._vdenoise_call("rt_luminance_moments", _vdenoise_desc(W, H), W, H, planes, {"out": True if out is None else out})
+        res = self._frame_call("rt_luminance_moments", A.VDENOISE_HOST_MEMORY, _vdenoise_desc(W, H), A.VDENOISE_PLANES, W, H, planes,
+                               {"out": _new_or(out)})
         return res["out"]
-
-    def _adaptive_tensors(self, table, W, H, given):
-        """Checks the frame-shaped device tensors of an adaptive call (uint32 planes: int32 tensors holding the bits, or uint32)."""
-        import torch
-        for k, v in given.items():
-            if not isinstance(v, torch.Tensor):
-                raise ValueError("mix of device tensors and host arrays")
-            if v.device.type != "cuda" or v.device.index != self.device:
-                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
-            kinds = (torch.float32,) if table[k][0] == "<f4" else (torch.int32, getattr(torch, "uint32", torch.int32))
-            if v.dtype not in kinds or not v.is_contiguous() or tuple(v.shape) != _adaptive_shape(table, k, W, H):
-                raise ValueError(f"plane {k} must be a contiguous {kinds[0]} tensor of shape {_adaptive_shape(table, k, W, H)}")
 
     def _on_handle_stream(self, call):
         """Runs call() on the handle's stream, ordered after the current torch stream's work and before what follows on it."""
@@ -864,7 +737,9 @@ class RayTracer:
         ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
         ext.wait_stream(cur)
         call()
-        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launches: _device_query)
+        # (the call's tensors belong to the current stream, which now waits for the launches: a later reuse of their memory is
+        # ordered after them -- no record_stream on the handle's stream, which rt_destroy may destroy before they are freed)
+        cur.wait_stream(ext)
 
     def adaptive_plan(self, variance, dirs, origin, budget, min_samples=ADAPTIVE_MIN_SAMPLES, max_samples=ADAPTIVE_MAX_SAMPLES,
                       first_frame=0):
@@ -878,26 +753,9 @@ class RayTracer:
         numpy planes: a synchronous call that returns numpy (rays: PATH_RAY_DTYPE).  Torch tensors on this handle's device:
         an asynchronous call ordered after the current torch stream's work; counts, offsets and totals are int32 tensors
         holding the u32 bits, rays a (budget, 8) float32 tensor of the packed records."""
-        if not hasattr(variance, "data_ptr") and not hasattr(dirs, "data_ptr"):
-            H, W = (int(v) for v in np.shape(variance)) if np.ndim(variance) == 2 else (0, 0)
-            d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
-            keep, res = _adaptive_plan_numpy(d, W, H, variance, dirs)
-            self._check(self._L.rt_adaptive_plan(self._h, C.byref(d), A.ADAPTIVE_HOST_MEMORY))
-            del keep
-            return res["counts"], res["offsets"], res["rays"], res["totals"]
-        import torch
-        H, W = (int(v) for v in variance.shape) if hasattr(variance, "data_ptr") and variance.dim() == 2 else (0, 0)
-        d = _adaptive_plan_desc(W, H, budget, origin, min_samples, max_samples, first_frame)
-        self._adaptive_tensors(A.ADAPTIVE_PLAN_PLANES, W, H, {"variance": variance, "dir": dirs})
-        dev = torch.device("cuda", self.device)
-        counts = torch.empty((H, W), dtype=torch.int32, device=dev)
-        offsets = torch.empty((H, W), dtype=torch.int32, device=dev)
-        rays = torch.empty((d.budget, 8), dtype=torch.float32, device=dev)
-        totals = torch.empty(4, dtype=torch.int32, device=dev)
-        d.variance, d.dir, d.counts, d.offsets = variance.data_ptr(), dirs.data_ptr(), counts.data_ptr(), offsets.data_ptr()
-        d.rays, d.totals = rays.data_ptr(), totals.data_ptr()
-        self._on_handle_stream(lambda: self._check(self._L.rt_adaptive_plan(self._h, C.byref(d), 0)))
-        return counts, offsets, rays, totals
+        tensors = hasattr(variance, "data_ptr") or hasattr(dirs, "data_ptr")
+        d, table, W, H, planes, outs = _adaptive_plan_call(variance, dirs, origin, budget, min_samples, max_samples, first_frame, tensors)
+        return _adaptive_plan_result(self._frame_call("rt_adaptive_plan", A.ADAPTIVE_HOST_MEMORY, d, table, W, H, planes, outs))
 
     def adaptive_merge(self, radiance, counts, offsets, color, history, max_history=float("inf"), albedo=None, moments=None, out=None,
                        out_history=None, out_moments=None):
@@ -909,30 +767,9 @@ class RayTracer:
         out_moments); the outputs may be the inputs.
         numpy planes: a synchronous call that returns numpy.  Torch tensors on this handle's device: an asynchronous call
         ordered after the current torch stream's work; returns tensors; there color=None names the handle's image."""
-        planes, outs, W, H = _adaptive_merge_planes(counts, offsets, color, history, albedo, moments, out, out_history, out_moments)
-        d = _adaptive_merge_desc(W, H, radiance.shape[0] if np.ndim(radiance) == 2 else 0, max_history)
-        if not any(hasattr(v, "data_ptr") for v in (radiance, *planes.values(), *outs.values())):
-            if color is None:
-                raise ValueError("color is required with numpy planes (color=None names the device image)")
-            keep, res = _adaptive_merge_numpy(d, W, H, radiance, planes, outs)
-            self._check(self._L.rt_adaptive_merge(self._h, C.byref(d), A.ADAPTIVE_HOST_MEMORY))
-            del keep
-            return _adaptive_merge_result(res)
-        import torch
-        dev = torch.device("cuda", self.device)
-        given = dict(planes, **{k: v for k, v in outs.items() if v is not None})
-        self._adaptive_tensors(A.ADAPTIVE_MERGE_PLANES, W, H, given)
-        if not (isinstance(radiance, torch.Tensor) and radiance.device == dev and radiance.dtype == torch.float32
-                and radiance.is_contiguous() and tuple(radiance.shape) == (d.budget, 4)):
-            raise ValueError(f"radiance must be a contiguous float32 tensor of shape {(d.budget, 4)} on cuda:{self.device}")
-        for k in outs:
-            if outs[k] is None:
-                outs[k] = given[k] = torch.empty(_adaptive_shape(A.ADAPTIVE_MERGE_PLANES, k, W, H), dtype=torch.float32, device=dev)
-        d.radiance = radiance.data_ptr()
-        for k, v in given.items():
-            setattr(d, k, v.data_ptr())
-        self._on_handle_stream(lambda: self._check(self._L.rt_adaptive_merge(self._h, C.byref(d), 0)))
-        return _adaptive_merge_result(outs)
+        d, table, W, H, planes, outs = _adaptive_merge_call(radiance, counts, offsets, color, history, max_history, albedo, moments, out,
+                                                            out_history, out_moments)
+        return _adaptive_merge_result(self._frame_call("rt_adaptive_merge", A.ADAPTIVE_HOST_MEMORY, d, table, W, H, planes, outs))
 
     def adaptive_samples(self, guides, variance, color, history, budget, bounces, samples, origin, min_samples=ADAPTIVE_MIN_SAMPLES,
                          max_samples=ADAPTIVE_MAX_SAMPLES, first_frame=0, max_history=float("inf"), moments=None, skybox=True,
@@ -985,36 +822,8 @@ class RayTracer:
         there color=None takes the handle's image as the current frame."""
         planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
         d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
-        outs = {"out": out, "out_history": out_history, "motion": None if motion is False or motion is True else motion}
-        if not any(hasattr(v, "data_ptr") for v in (*planes.values(), *outs.values())):
-            if color is None:
-                raise ValueError("color is required with numpy planes (color=None names the device image)")
-            keep, res = _temporal_numpy(d, W, H, planes, True if out is None else out, True if out_history is None else out_history, motion)
-            self._check(self._L.rt_temporal_accumulate(self._h, C.byref(d), A.TEMPORAL_HOST_MEMORY))
-            del keep
-            return _temporal_result(res)
-        import torch
-        dev = torch.device("cuda", self.device)
-        given = dict(planes, **{k: v for k, v in outs.items() if v is not None})
-        for k, v in given.items():
-            if not isinstance(v, torch.Tensor):
-                raise ValueError("mix of device tensors and host arrays")
-            if v.device.type != "cuda" or v.device.index != self.device:
-                raise ValueError(f"plane {k} must be on cuda:{self.device}, not {v.device}")
-            kinds = (torch.float32,) if A.TEMPORAL_PLANES[k][0] == "<f4" else (torch.int32, getattr(torch, "uint32", torch.int32))   # (object: the u32 bits)
-            if v.dtype not in kinds or not v.is_contiguous() or tuple(v.shape) != _temporal_shape(k, W, H):
-                raise ValueError(f"plane {k} must be a contiguous {kinds[0]} tensor of shape {_temporal_shape(k, W, H)}")
-        for k in ("out", "out_history") + (("motion",) if motion is not False else ()):
-            if outs[k] is None:
-                outs[k] = given[k] = torch.empty(_temporal_shape(k, W, H), dtype=torch.float32, device=dev)
-        for k, v in given.items():
-            setattr(d, k, v.data_ptr())
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=dev)
-        ext.wait_stream(cur)
-        self._check(self._L.rt_temporal_accumulate(self._h, C.byref(d), 0))
-        cur.wait_stream(ext)   # (the planes belong to the current stream, which now waits for the launch: _device_query)
-        return _temporal_result(outs)
+        outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
+        return _temporal_result(self._frame_call("rt_temporal_accumulate", A.TEMPORAL_HOST_MEMORY, d, A.TEMPORAL_PLANES, W, H, planes, outs))
 
     def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):
         """Radiance along rays of the caller's (rt_radiance_rays): for ray i `frag`'s sample loop with the ray held fixed --
@@ -1132,17 +941,9 @@ class RayTracer:
 
     def _device_query(self, fn, rays, out, flags):
         """Runs fn on the handle's stream, ordered after the current torch stream's work and before what follows on it."""
-        import torch
         n = rays.shape[0]
-        if n == 0:
-            return
-        cur = torch.cuda.current_stream(rays.device)
-        ext = torch.cuda.ExternalStream(self._L.rt_stream(self._h), device=rays.device)
-        ext.wait_stream(cur)
-        self._check(fn(self._h, rays.data_ptr(), n, out.data_ptr(), flags))
-        # (rays and out belong to the current stream, which now waits for the query: a later reuse of their memory is
-        # ordered after it -- no record_stream on the handle's stream, which rt_destroy may destroy before they are freed)
-        cur.wait_stream(ext)
+        if n:
+            self._on_handle_stream(lambda: self._check(fn(self._h, rays.data_ptr(), n, out.data_ptr(), flags)))
 
     def stats(self):
         s = A.Stats()

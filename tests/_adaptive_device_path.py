@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import ray_tracer_2_amd as rt  # noqa: E402
 from ray_tracer_2_amd import _abi as A  # noqa: E402
+import _over_cap as OC  # noqa: E402
 
 F32, U32 = np.float32, np.uint32
 dev = torch.device("cuda:0")
@@ -140,6 +141,34 @@ t._check(t._L.rt_adaptive_merge(t._h, C.byref(d), 0))
 t.synchronize()
 check_skewed(bufs, skew, planes, ("out", "out_history", "out_moments"), want, "merge at the least alignment")
 print("planes at their least alignment ok", flush=True)
+
+# a handle that already holds more than option max_device_mb allows (the denoiser's scratch, once the cap is lowered under
+# it): rt_adaptive_plan on device memory is refused, though its own scratch is there, and nothing is written;
+# rt_adaptive_merge allocates nothing and is done all the same
+og_host, og_dev, big_image = OC.frame(t)
+rng = np.random.default_rng(5)
+big_var, big_hist = rng.random((OC.H, OC.W), F32), rng.integers(1, 7, (OC.H, OC.W)).astype(F32)
+big_budget = 4 * OC.W * OC.H
+big_plan = rt.adaptive_plan_host(big_var, og_host["dir"], origin, big_budget, 1, 16, 4)
+big_rad = rng.random((big_budget, 4), F32)
+big_want = rt.adaptive_merge_host(big_rad, big_plan[0], big_plan[1], big_image, big_hist, 6.0)
+d_var, d_color = up(big_var), up(big_image)
+plan_outs = (torch.empty((OC.H, OC.W), dtype=torch.int32, device=dev), torch.empty((OC.H, OC.W), dtype=torch.int32, device=dev),
+             torch.empty((big_budget, 8), dtype=torch.float32, device=dev), torch.empty(4, dtype=torch.int32, device=dev))
+d = A.AdaptivePlanDesc(struct_bytes=C.sizeof(A.AdaptivePlanDesc), width=OC.W, height=OC.H, budget=big_budget, min_samples=1,
+                       max_samples=16, first_frame=4, origin=(C.c_float * 3)(*origin.tolist()))
+d.variance, d.dir = d_var.data_ptr(), og_dev["dir"].data_ptr()
+d.counts, d.offsets, d.rays, d.totals = (o.data_ptr() for o in plan_outs)
+torch.cuda.synchronize()
+plan_call = lambda: t._check(t._L.rt_adaptive_plan(t._h, C.byref(d), 0))  # noqa: E731
+plan_call()
+OC.hold_denoise_scratch(t, og_dev, d_color)
+OC.over_cap(t, plan_call, plan_outs, big_plan, True, "rt_adaptive_plan")
+merge_outs = (torch.empty((OC.H, OC.W, 4), dtype=torch.float32, device=dev), torch.empty((OC.H, OC.W), dtype=torch.float32, device=dev))
+merge_in = (up(big_rad), up(big_plan[0]), up(big_plan[1]), d_color, up(big_hist))
+merge_call = lambda: t.adaptive_merge(*merge_in, 6.0, out=merge_outs[0], out_history=merge_outs[1])  # noqa: E731
+merge_call()
+OC.over_cap(t, merge_call, merge_outs, big_want, False, "rt_adaptive_merge")
 t.close()
 
 # The scratch: 32 bytes per 1024 texels and a header of 256.  8192 x 4096 texels make 32768 blocks: 1 MiB and 256 bytes, which

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import ray_tracer_2_amd as rt  # noqa: E402
 from ray_tracer_2_amd import _abi as A  # noqa: E402
+import _over_cap as OC  # noqa: E402
 
 SIGMAS = (4.0, 0.3, 1.0)
 CHANNELS = ("normal", "point", "albedo", "emission")
@@ -90,5 +91,14 @@ for k in planes:
     if k != "out":
         assert np.array_equal(raw[k].cpu().numpy()[skew[k]:skew[k] + planes[k].nbytes], planes[k].view(np.uint8).ravel()), (k, "an input changed")
 print("planes at their least alignment ok", flush=True)
+
+# a handle that already holds more than option max_device_mb allows (its own scratch, once the cap is lowered under it):
+# rt_denoise on device memory is refused, and nothing is written
+host_g, dev_g, image = OC.frame(t)
+guides, color = {k: dev_g[k] for k in CHANNELS}, torch.from_numpy(image).to(dev)
+out = torch.empty((OC.H, OC.W, 4), dtype=torch.float32, device=dev)
+want = rt.denoise_host({k: host_g[k] for k in CHANNELS}, image, 2, *SIGMAS)
+t.denoise(guides, color, 2, *SIGMAS, out=out)
+OC.over_cap(t, lambda: t.denoise(guides, color, 2, *SIGMAS, out=out), (out,), (want,), True, "rt_denoise")
 t.close()
 print("device path ok")

@@ -17,6 +17,7 @@ sys.path.insert(0, HERE)
 import ray_tracer_2_amd as rt  # noqa: E402
 from ray_tracer_2_amd import _abi as A  # noqa: E402
 import _temporal_reference as R  # noqa: E402
+import _over_cap as OC  # noqa: E402
 
 CHANNELS = ("point", "normal", "object")
 CAP, TOL, NCOS = 3.0, 0.01, 0.9
@@ -125,5 +126,22 @@ for k in planes:
     if k not in ("out", "out_history", "motion"):
         assert np.array_equal(raw[k].cpu().numpy()[skew[k]:skew[k] + planes[k].nbytes], planes[k].view(np.uint8).ravel()), (k, "an input changed")
 print("planes at their least alignment ok", flush=True)
+
+# a handle that already holds more than option max_device_mb allows (the denoiser's scratch, once the cap is lowered under
+# it): rt_temporal_accumulate on device memory allocates nothing and is done all the same
+t.set_camera(base)
+host_pg, dev_pg, prev_image = OC.frame(t, 1)
+t.set_camera(moved)
+host_g, dev_g, image = OC.frame(t, 2)
+pick = lambda g: {k: g[k] for k in CHANNELS}  # noqa: E731
+history = np.random.default_rng(3).integers(1, 7, (OC.H, OC.W)).astype(np.float32)
+color, prev_color, prev_history = (torch.from_numpy(a).to(dev) for a in (image, prev_image, history))
+outs = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((OC.H, OC.W, 4), (OC.H, OC.W), (OC.H, OC.W, 2)))
+want = rt.temporal_accumulate_host(pick(host_g), pick(host_pg), base, prev_image, history, image, CAP, TOL, NCOS, motion=True)
+call = lambda: t.temporal_accumulate(pick(dev_g), pick(dev_pg), base, prev_color, prev_history, color, CAP, TOL, NCOS,  # noqa: E731
+                                     out=outs[0], out_history=outs[1], motion=outs[2])
+call()
+OC.hold_denoise_scratch(t, dev_g, color)
+OC.over_cap(t, call, outs, want, False, "rt_temporal_accumulate")
 t.close()
 print("device path ok")

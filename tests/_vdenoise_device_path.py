@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import ray_tracer_2_amd as rt  # noqa: E402
 from ray_tracer_2_amd import _abi as A  # noqa: E402
+import _over_cap as OC  # noqa: E402
 
 SIGMAS = (4.0, 0.3, 1.0)
 CHANNELS = ("normal", "point", "albedo", "emission")
@@ -101,7 +102,7 @@ for fn, outs, wants in ((t._L.rt_denoise_variance, ("out", "out_variance"), want
     d = desc(W, H, 4)
     raw, skew = {}, {}
     for k, v in planes.items():
-        skew[k] = 16 if A.VDENOISE_PLANES[k] == 4 else 4
+        skew[k] = 16 if A.VDENOISE_PLANES[k][1] == 4 else 4
         raw[k] = torch.zeros(v.nbytes + 64, dtype=torch.uint8, device=dev)
         assert raw[k].data_ptr() % 32 == 0
         raw[k][skew[k]:skew[k] + v.nbytes] = torch.from_numpy(v.view(np.uint8).ravel().copy()).to(dev)
@@ -118,5 +119,18 @@ for fn, outs, wants in ((t._L.rt_denoise_variance, ("out", "out_variance"), want
         if k not in outs:
             assert np.array_equal(raw[k].cpu().numpy()[skew[k]:skew[k] + planes[k].nbytes], planes[k].view(np.uint8).ravel()), (k, "an input changed")
 print("planes at their least alignment ok", flush=True)
+
+# a handle that already holds more than option max_device_mb allows (the denoisers' scratch, once the cap is lowered under
+# it): both calls on device memory are refused, rt_luminance_moments too, which uses no scratch, and nothing is written
+host_g, dev_g, image = OC.frame(t)
+guides, host_guides, color = {k: dev_g[k] for k in CHANNELS}, {k: host_g[k] for k in CHANNELS}, torch.from_numpy(image).to(dev)
+out = torch.empty((OC.H, OC.W, 4), dtype=torch.float32, device=dev)
+var = torch.empty((OC.H, OC.W), dtype=torch.float32, device=dev)
+want = rt.denoise_variance_host(host_guides, image, 2, *SIGMAS, out_variance=True)
+t.denoise_variance(guides, color, 2, *SIGMAS, out=out, out_variance=var)
+OC.over_cap(t, lambda: t.denoise_variance(guides, color, 2, *SIGMAS, out=out, out_variance=var), (out, var), want, True,
+            "rt_denoise_variance")
+OC.over_cap(t, lambda: t.luminance_moments(guides, color, out=out), (out,), (rt.luminance_moments_host(host_guides, image),), True,
+            "rt_luminance_moments")
 t.close()
 print("device path ok")

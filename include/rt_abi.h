@@ -692,7 +692,9 @@ int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags);
  * Consequence: under an unmoved camera, with the same G-buffer on both sides, prev_history == k everywhere and `color` the
  * raw sample of seed k (rt_render with frames = -k), every reprojectable texel takes one tap of weight 1 and `out` is what
  * rt_render with frames = k leaves in the image, bit for bit, alpha included.
- * Geometry that moved between the frames is out of scope: its texels fail the plane test and restart at history 1.
+ * Rigidly or affinely moved meshes and moved or resized spheres keep their history through rt_temporal_accumulate_moving
+ * (below).  Still out of scope: a mesh whose vertices moved (rt_refit_triangles) and the sky -- their texels fail the plane
+ * test or are misses, and restart at history 1.
  * point_tolerance is the distance from the current texel's tangent plane that a tap's hit point may have, per unit of view
  * depth (the footprint of a texel grows with depth); normal_cos the least cosine between the two normals.
  * rt_temporal_accumulate_host (section 3) is this definition over host pointers, without a device;
@@ -735,6 +737,68 @@ typedef struct rt_temporal_desc {
 } rt_temporal_desc;
 enum { RT_TEMPORAL_HOST_MEMORY = 1 };
 int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags);
+
+/* Temporal accumulation across moving objects: rt_temporal_accumulate with a table that says, per
+ * object word of the G-buffer (a mesh's index, or n_meshes + a sphere's index), how a point of the object in the CURRENT
+ * frame's world is carried to where the same surface point lay in the PREVIOUS frame's world.  rt_object_motions (section 3)
+ * fills the table from two scene states.  Everything is binary32 and unfused, in this order; what is not restated here is
+ * rt_temporal_accumulate's definition above, word for word.
+ *   `object` is required.  For a REPROJECTABLE texel p (so object(p) != 0xffffffff) with k = object(p):
+ *   k >= n_objects: the "no history" result -- out(p) = color(p) bit for bit, out_history(p) = 1, motion(p) = two quiet NaNs.
+ *   motions[k].moved == 0: the record's matrices are not read and the texel is worked exactly as by
+ *   rt_temporal_accumulate, with X = point(p) and n = normal(p) as they are.
+ *   Otherwise, with d = motions[k].d, nt = motions[k].nt, X = point(p), n = normal(p), for r = 0, 1, 2:
+ *     X'_r = ((d[0][r] X0 + d[1][r] X1) + d[2][r] X2) + d[3][r]
+ *     m_r  = (nt[0][r] n0 + nt[1][r] n1) + nt[2][r] n2
+ *     len  = sqrt((m0 m0 + m1 m1) + m2 m2)    (the correctly rounded square root)
+ *     n'_r = m_r / len                        (three divisions)
+ *   If some component of X' or n' is not finite (a zero len gives NaN or infinity): the "no history" result.  Otherwise the
+ *   texel is worked as by rt_temporal_accumulate with X' in the place of X and n' in the place of n throughout: the
+ *   projection and the on-screen test, the snap, motion(p), each tap's plane distance |(prev_point(q) - X') . n'| <=
+ *   point_tolerance * l2 and normal cosine n' . prev_normal(q), the object match (when prev_object is given) and the blend.
+ *   motion(p) is then the screen offset that the camera's and the object's move produce together.
+ * Consequence: with a table whose records all have moved == 0 (and every object word below n_objects) every output plane
+ * is rt_temporal_accumulate's bit for bit, for any camera move.
+ * What this keeps is an object's OWN history, not the lighting: a turning object's faces change their illumination, shadows
+ * and reflections move over surfaces that stand still, and the history lags behind them; max_history bounds the lag.
+ * A second call with the luminance moments as color / prev_color and the same table accumulates the moments that
+ * rt_denoise_variance takes for a moving object.
+ * Memory, asynchrony, aliasing and side effects are rt_temporal_accumulate's.  `motions` is on the side of the planes: a
+ * device pointer (16-byte aligned) without RT_TEMPORAL_HOST_MEMORY; with it a host pointer whose n_objects * 96 bytes are
+ * staged with the planes and counted against option "max_device_mb" with them.
+ * Errors, nothing written: rt_temporal_accumulate's (struct_bytes != sizeof(rt_temporal_motion_desc)), and
+ * RT_ERR_INVALID_ARGUMENT for a null motions, n_objects == 0, _p1 != 0, a null object plane, a misaligned device table. */
+typedef struct rt_object_motion {
+    float    d[4][3];    /* current world -> previous world, column-major [col][row]: X' = d * (X, 1) */
+    float    nt[3][3];   /* [col][row]: m = nt * n is the previous-world normal before normalisation */
+    uint32_t moved;      /* 0: the object stands still, the record's matrices are not read */
+    uint32_t _p[2];      /* 0 */
+} rt_object_motion;      /* 96 bytes */
+typedef struct rt_temporal_motion_desc {
+    uint32_t          struct_bytes;     /* = sizeof(rt_temporal_motion_desc) */
+    uint32_t          _p0;              /* must be 0 */
+    uint32_t          width, height;
+    rt_camera_uniform prev_camera;
+    float             max_history;
+    float             point_tolerance;
+    float             normal_cos;
+    const float*      color;
+    const float*      point;
+    const float*      normal;
+    const uint32_t*   object;           /* [h][w] current: required */
+    const float*      prev_color;
+    const float*      prev_history;
+    const float*      prev_point;
+    const float*      prev_normal;
+    const uint32_t*   prev_object;      /* [h][w] or NULL */
+    float*            out;
+    float*            out_history;
+    float*            motion;           /* [h][w][2] or NULL */
+    const rt_object_motion* motions;    /* [n_objects], indexed by the object word */
+    uint32_t          n_objects;        /* >= 1 */
+    uint32_t          _p1;              /* must be 0 */
+} rt_temporal_motion_desc;              /* rt_temporal_desc's fields in their order, then the table */
+int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags);
 
 /* Variance-guided denoising: the variance half of SVGF (Schied et al. 2017, sections 4.2 - 4.4)
  * over rt_denoise's guides.  rt_luminance_moments writes the per-frame sample of the luminance moments;
@@ -1040,6 +1104,23 @@ int rt_denoise_host(const rt_denoise_desc* desc);
  * rt_temporal_accumulate (no handle, no flags, no alignment rule), nothing written on an error, the reason in
  * rt_last_error(NULL). */
 int rt_temporal_accumulate_host(const rt_temporal_desc* desc);
+/* The same for rt_temporal_accumulate_moving: `motions` is a host pointer. */
+int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc);
+
+/* The motion table of rt_temporal_accumulate_moving from two states of one scene (the arrays rt_update_instances takes,
+ * before and after the edit): out[0, n_meshes + n_spheres), meshes first.  Plain C++, no device.  Binary32, unfused.
+ * With the product of two column-major matrices as glam's Mat4 * Mat4 (csrc/host/glam_math.h: mat4_mul),
+ *   (A B)[c][r] = ((A[0][r] B[c][0] + A[1][r] B[c][1]) + A[2][r] B[c][2]) + A[3][r] B[c][3]:
+ * Mesh k:  moved = the 128 bytes of world_to_model and model_to_world differ between prev_meshes[k] and meshes[k];
+ *   D = prev.model_to_world * cur.world_to_model and d[c][r] = D[c][r] (r < 3);
+ *   N = cur.model_to_world * prev.world_to_model and nt[c][r] = N[r][c] (c, r < 3) -- the transpose of N's 3 x 3, which is
+ *   the inverse transpose of d's linear part without an inversion.
+ * Sphere j, record n_meshes + j:  moved = the 16 bytes of pos and radius differ;  s = prev.radius / cur.radius;
+ *   d[c][r] = (c == r ? s : 0) for c < 3;  d[3][r] = prev.pos[r] - s * cur.pos[r];  nt = the identity.
+ * The matrices are filled whether or not `moved` is set; _p is 0.  An array may be NULL when its count is 0.
+ * RT_ERR_INVALID_ARGUMENT, nothing written: a null `out` with a non-zero total, a null array with a non-zero count. */
+int rt_object_motions(const rt_mesh_uniform* prev_meshes, const rt_mesh_uniform* meshes, uint32_t n_meshes,
+                      const rt_sphere* prev_spheres, const rt_sphere* spheres, uint32_t n_spheres, rt_object_motion* out);
 
 /* The variance-guided denoiser's definition (section 2: rt_denoise_variance, rt_luminance_moments) in executable form:
  * plain C++ over host pointers, no device.  `color` is required; `out` may be `color`.  The same argument errors as the

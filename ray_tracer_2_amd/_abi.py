@@ -169,6 +169,22 @@ TEMPORAL_PLANES = {"color": ("<f4", 4), "point": ("<f4", 3), "normal": ("<f4", 3
                    "prev_object": ("<u4", 0), "out": ("<f4", 4), "out_history": ("<f4", 0), "motion": ("<f4", 2)}
 TEMPORAL_HOST_MEMORY = 1
 
+
+class ObjectMotion(C.Structure):  # rt_object_motion: one record of rt_temporal_accumulate_moving's table
+    _fields_ = [("d", (f32 * 3) * 4), ("nt", (f32 * 3) * 3), ("moved", u32), ("_p", u32 * 2)]
+
+
+class TemporalMotionDesc(C.Structure):  # rt_temporal_motion_desc: rt_temporal_desc's fields, then the motion table
+    _fields_ = TemporalDesc._fields_ + [("motions", C.c_void_p), ("n_objects", u32), ("_p1", u32)]
+
+
+# rt_temporal_accumulate_moving's planes: TEMPORAL_PLANES and the table, which is not frame-shaped -- (n_objects,)
+# OBJECT_MOTION_DTYPE on the host, an (n_objects, 24) int32 tensor of the records' words on the device; the calls put its
+# shape in
+OBJECT_MOTION_DTYPE = np.dtype([("d", "<f4", (4, 3)), ("nt", "<f4", (3, 3)), ("moved", "<u4"), ("_p", "<u4", 2)])
+assert OBJECT_MOTION_DTYPE.itemsize == C.sizeof(ObjectMotion) == 96
+TEMPORAL_MOTION_PLANES = dict(TEMPORAL_PLANES, motions=(OBJECT_MOTION_DTYPE, None))
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():

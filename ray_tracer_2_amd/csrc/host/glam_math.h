@@ -143,6 +143,16 @@ inline Mat4 mat4_from_srt(Vec3 scale, Quat q, Vec3 t) {
     return m;
 }
 
+// glam scalar Mat4 * Mat4: column c of the product is a * (column c of b), and Mat4 * Vec4 adds the scaled axes in order:
+// ((x_axis * v.x + y_axis * v.y) + z_axis * v.z) + w_axis * v.w
+inline Mat4 mat4_mul(const Mat4& a, const Mat4& b) {
+    Mat4 m;
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r)
+            m.c[c][r] = ((a.c[0][r] * b.c[c][0] + a.c[1][r] * b.c[c][1]) + a.c[2][r] * b.c[c][2]) + a.c[3][r] * b.c[c][3];
+    return m;
+}
+
 // glam scalar Mat4::inverse (cofactor expansion after GLM compute_inverse)
 inline Mat4 mat4_inverse(const Mat4& s) {
     float m00 = s.c[0][0], m01 = s.c[0][1], m02 = s.c[0][2], m03 = s.c[0][3];

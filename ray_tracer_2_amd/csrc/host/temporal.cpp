@@ -1,5 +1,6 @@
 // host/temporal.cpp -- temporal accumulation's definition in executable form (include/rt_abi.h:
-// rt_temporal_accumulate_host), the argument rules and the once-per-call numbers it shares with
+// rt_temporal_accumulate_host and, with a motion table, rt_temporal_accumulate_moving_host -- one loop for both; DESIGN.md
+// section 2.14), the argument rules and the once-per-call numbers it shares with
 // the device entry point.  Plain C++ over host pointers; the per-texel arithmetic is csrc/rt_temporal.h, which the device
 // kernel evaluates too.  Compiled with -ffp-contract=off.
 #if defined(__HIPCC__)
@@ -61,8 +62,36 @@ rttp::Call temporal_call(const rt_temporal_desc* d) {
     return c;
 }
 
-int temporal_host(const rt_temporal_desc* d, std::string& err) {
-    if (const int rc = temporal_check(d, false, false, err); rc != RT_OK) return rc;
+rt_temporal_desc temporal_head(const rt_temporal_motion_desc* d) {
+    rt_temporal_desc head;
+    std::memcpy(&head, d, sizeof(head));
+    head.struct_bytes = sizeof(head);
+    return head;
+}
+
+int temporal_motion_check(const rt_temporal_motion_desc* d, bool device, bool host_memory, std::string& err) {
+    auto bad = [&](int code, const char* msg) {
+        err = msg;
+        return code;
+    };
+    if (!d) return bad(RT_ERR_INVALID_ARGUMENT, "null rt_temporal_motion_desc");
+    if (d->struct_bytes != sizeof(rt_temporal_motion_desc))
+        return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_motion_desc.struct_bytes is not sizeof(rt_temporal_motion_desc)");
+    const rt_temporal_desc head = temporal_head(d);
+    if (const int rc = temporal_check(&head, device, host_memory, err); rc != RT_OK) return rc;
+    if (d->_p1 != 0u) return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_motion_desc._p1 must be 0");
+    if (!d->motions) return bad(RT_ERR_INVALID_ARGUMENT, "null motions table");
+    if (d->n_objects == 0u) return bad(RT_ERR_INVALID_ARGUMENT, "n_objects is zero");
+    if (!d->object) return bad(RT_ERR_INVALID_ARGUMENT, "null object plane (a motion table is indexed by it)");
+    if (device && !host_memory) {
+        const PlaneAlign table[1] = {{d->motions, 15u, "motions"}};
+        return misaligned(table, 1, err);
+    }
+    return RT_OK;
+}
+
+// The loop of both host entry points: motions == nullptr is rt_temporal_accumulate_host.
+static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motions, uint32_t n_objects) {
     const rttp::Call c = temporal_call(d);
     const int64_t W = d->width, H = d->height;
     const bool match_object = d->object && d->prev_object;
@@ -79,7 +108,20 @@ int temporal_host(const rt_temporal_desc* d, std::string& err) {
             std::memcpy(r.out, color, sizeof(color));
             r.history = 1.0f;
             float motion[2] = {nan, nan};
-            if (rttp::reprojectable(n, X, d->object != nullptr, obj)) {
+            bool go = rttp::reprojectable(n, X, d->object != nullptr, obj);
+            float carried_x[3], carried_n[3];
+            if (go && motions) {
+                // a word outside the table has no history; a still object's texel goes on as it is; a moved one's is carried
+                go = rttp::in_table(obj, n_objects);
+                if (go && motions[obj].moved != 0u) {
+                    rttp::Motion m;
+                    std::memcpy(&m, motions + obj, sizeof(m));
+                    go = rttp::carry(m, X, n, carried_x, carried_n);
+                    X = carried_x;
+                    n = carried_n;
+                }
+            }
+            if (go) {
                 const rttp::Where w = rttp::locate(c, X, (uint32_t)x, (uint32_t)y);
                 if (w.on_screen) {
                     rttp::Tap taps[4];
@@ -107,6 +149,18 @@ int temporal_host(const rt_temporal_desc* d, std::string& err) {
             d->out_history[p] = r.history;
             if (d->motion) std::memcpy(d->motion + 2 * p, motion, sizeof(motion));
         }
+}
+
+int temporal_host(const rt_temporal_desc* d, std::string& err) {
+    if (const int rc = temporal_check(d, false, false, err); rc != RT_OK) return rc;
+    accumulate(d, nullptr, 0u);
+    return RT_OK;
+}
+
+int temporal_motion_host(const rt_temporal_motion_desc* d, std::string& err) {
+    if (const int rc = temporal_motion_check(d, false, false, err); rc != RT_OK) return rc;
+    const rt_temporal_desc head = temporal_head(d);
+    accumulate(&head, d->motions, d->n_objects);
     return RT_OK;
 }
 

@@ -69,6 +69,7 @@ hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
+hipError_t launch_temporal_motion(const TemporalMotionArgs& a, hipStream_t stream);
 hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
@@ -2308,7 +2309,7 @@ int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* r
 }
 
 // ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
-// rt_adaptive_merge, rt_temporal_accumulate ----
+// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving ----
 // Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
 // and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
 // arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
@@ -2427,6 +2428,7 @@ int rt_luminance_moments_host(const rt_vdenoise_desc* desc) { return host_call(r
 int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc) { return host_call(rt2::adaptive_plan_host, desc); }
 int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) { return host_call(rt2::adaptive_merge_host, desc); }
 int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call(rt2::temporal_host, desc); }
+int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc) { return host_call(rt2::temporal_motion_host, desc); }
 
 // ---- denoising a rendered frame (include/rt_abi.h: rt_denoise; rt_denoise.hip; host/denoise.cpp) ----
 static const char* const DENOISE_SCRATCH = "the denoiser's scratch images";
@@ -2592,6 +2594,38 @@ int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags
         a.prev_point = (const float*)in[6]; a.prev_normal = (const float*)in[7]; a.prev_object = (const uint32_t*)in[8];
         a.out_history = (float*)out[9]; a.motion = (float*)out[10];
         return launch_temporal(a, h->stream);
+    });
+}
+
+// With a motion table (include/rt_abi.h: rt_temporal_accumulate_moving): rt_temporal_accumulate's planes and the table, one
+// more input that is not frame-shaped.
+int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
+    std::string err;
+    if (const int rc = rt2::temporal_motion_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)desc->width * desc->height;
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
+    const FramePlane planes[12] = {{color, desc->out, texels * 16u}, {desc->point, nullptr, texels * 12u}, {desc->normal, nullptr, texels * 12u},
+                                   {desc->object, nullptr, texels * 4u}, {desc->prev_color, nullptr, texels * 16u},
+                                   {desc->prev_history, nullptr, texels * 4u}, {desc->prev_point, nullptr, texels * 12u},
+                                   {desc->prev_normal, nullptr, texels * 12u}, {desc->prev_object, nullptr, texels * 4u},
+                                   {nullptr, desc->out_history, texels * 4u}, {nullptr, desc->motion, texels * 8u},
+                                   {desc->motions, nullptr, (size_t)desc->n_objects * sizeof(rt_object_motion)}};
+    TemporalMotionArgs a{};
+    const rt_temporal_desc head = rt2::temporal_head(desc);
+    a.t.call = rt2::temporal_call(&head);
+    a.n_objects = desc->n_objects;
+    return frame_call(h, host, planes, "the staging planes of temporal accumulation", "launch_temporal_motion", [&](const void* const* in, void* const* out) {
+        a.t.color = (const float*)in[0]; a.t.out = (float*)out[0]; a.t.point = (const float*)in[1]; a.t.normal = (const float*)in[2];
+        a.t.object = (const uint32_t*)in[3]; a.t.prev_color = (const float*)in[4]; a.t.prev_history = (const float*)in[5];
+        a.t.prev_point = (const float*)in[6]; a.t.prev_normal = (const float*)in[7]; a.t.prev_object = (const uint32_t*)in[8];
+        a.t.out_history = (float*)out[9]; a.t.motion = (float*)out[10]; a.motions = (const rttp::Motion*)in[11];
+        return launch_temporal_motion(a, h->stream);
     });
 }
 

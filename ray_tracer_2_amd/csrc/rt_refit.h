@@ -17,19 +17,19 @@
 #include <cstdint>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define RT_HD __host__ __device__
+#define RT_REFIT_HD __host__ __device__
 #else
-#define RT_HD
+#define RT_REFIT_HD
 #endif
 
-RT_HD inline float rt_box_min(float a, float b) {
+RT_REFIT_HD inline float rt_box_min(float a, float b) {
     if (a < b) return a;
     if (b < a) return b;
     if (a == b) return __builtin_signbit(a) ? a : b;  // (-0 over +0)
     return a != a ? b : a;
 }
 
-RT_HD inline float rt_box_max(float a, float b) {
+RT_REFIT_HD inline float rt_box_max(float a, float b) {
     if (a > b) return a;
     if (b > a) return b;
     if (a == b) return __builtin_signbit(a) ? b : a;  // (+0 over -0)
@@ -37,14 +37,14 @@ RT_HD inline float rt_box_max(float a, float b) {
 }
 
 // One triangle's contribution to a leaf box fold (lo / hi hold the box so far).
-RT_HD inline void rt_box_fold(float lo[3], float hi[3], const float v1[3], const float v2[3], const float v3[3]) {
+RT_REFIT_HD inline void rt_box_fold(float lo[3], float hi[3], const float v1[3], const float v2[3], const float v3[3]) {
     for (int k = 0; k < 3; ++k) {
         lo[k] = rt_box_min(lo[k], rt_box_min(v1[k], rt_box_min(v2[k], v3[k])));
         hi[k] = rt_box_max(hi[k], rt_box_max(v1[k], rt_box_max(v2[k], v3[k])));
     }
 }
 
-RT_HD inline void rt_box_empty(float lo[3], float hi[3]) {
+RT_REFIT_HD inline void rt_box_empty(float lo[3], float hi[3]) {
     for (int k = 0; k < 3; ++k) {
         lo[k] = FLT_MAX;
         hi[k] = -FLT_MAX;

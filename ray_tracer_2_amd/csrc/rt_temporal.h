@@ -7,12 +7,16 @@
 //   locate  -- is the texel reprojectable, where does its hit point fall in the previous frame (project), is that on
 //              screen, and which texels and weights does the snapped position take (snap)?
 //   resolve -- given the four taps' previous values: which of them are valid, what do they add, and the blend.
+// With a motion table (rt_temporal_accumulate_moving) a moved object's texel goes through `carry` first, and locate and
+// resolve then work on the carried point and normal.
 // What an invalid tap adds is +0, chosen by a select after the tap's arithmetic: sum, hsum and wsum start at +0 and are
 // never -0, so adding +0 leaves them as they are, bit for bit, and no branch stands between the taps' loads.
 #ifndef RT_TEMPORAL_H
 #define RT_TEMPORAL_H
 
 #include <stdint.h>
+
+#include "rt_transc.h"   // (rtm::sqrt_, the correctly rounded square root of host and device)
 
 #if defined(__HIPCC__)
 #define RT_TP_HD __host__ __device__ __forceinline__
@@ -148,6 +152,34 @@ RT_TP_HD Result resolve(const Call& c, const Where& where, const float X[3], con
     }
     r.history = sample_ok ? n_c + 1.0f : n_c;
     return r;
+}
+
+// ---- moving objects (include/rt_abi.h: rt_temporal_accumulate_moving) ----
+// A record of the motion table, rt_object_motion's 96 bytes as both units read them: the device table is 16-byte aligned
+// (the entry point checks), the host loop copies a record into one of these.
+struct alignas(16) Motion {
+    float d[4][3];    // current world -> previous world, [col][row]
+    float nt[3][3];   // [col][row]: the previous-world normal before normalisation
+    uint32_t moved;
+    uint32_t _p[2];
+};
+
+// Which way a reprojectable texel with object word `obj` goes under a table of n_objects records (`object` is required
+// with a table, so a reprojectable texel's word is not NO_OBJECT): a word outside the table has no history; inside it, a
+// record with moved == 0 leaves the texel as it is -- its matrices are not read -- and any other carries it (carry).
+RT_TP_HD bool in_table(uint32_t obj, uint32_t n_objects) { return obj < n_objects; }
+
+// X, n of the current world -> X', n' of the previous world by a moved object's record.  False: some component is not
+// finite (a zero length included) and the texel has no history.
+RT_TP_HD bool carry(const Motion& m, const float X[3], const float n[3], float Xp[3], float np[3]) {
+    float v[3];
+    for (int r = 0; r < 3; ++r) {
+        Xp[r] = ((m.d[0][r] * X[0] + m.d[1][r] * X[1]) + m.d[2][r] * X[2]) + m.d[3][r];
+        v[r] = (m.nt[0][r] * n[0] + m.nt[1][r] * n[1]) + m.nt[2][r] * n[2];
+    }
+    const float len = rtm::sqrt_((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    for (int r = 0; r < 3; ++r) np[r] = v[r] / len;
+    return finite3(Xp) && finite3(np);
 }
 
 }  // namespace rttp

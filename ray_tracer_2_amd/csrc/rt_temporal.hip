@@ -1,5 +1,5 @@
-// rt_temporal.hip -- the device kernel of temporal accumulation (include/rt_abi.h: rt_temporal_accumulate; DESIGN.md
-// section 2.14).
+// rt_temporal.hip -- the device kernels of temporal accumulation (include/rt_abi.h: rt_temporal_accumulate,
+// rt_temporal_accumulate_moving).
 //
 // One lane per current texel, a workgroup per tile of 32 x 8 texels (a wave: 32 x 2), so that the four taps of
 // neighbouring lanes fall into neighbouring texels of the previous frame and a wave's gather touches a few rows of it.
@@ -14,7 +14,8 @@
 // Bounds: a lane outside the frame leaves before any access; a lane's own index p and every tap index q (both
 // coordinates clamped into the frame) are < width * height <= 2^31 - 1 (the entry point checks), and every address is
 // formed in 64 bits.  The snapped tap origin is in [-1, width] x [-1, height] (on screen: -1 < fx < width), so x0 + 1
-// does not overflow an int32.
+// does not overflow an int32.  The motion table (rt_temporal_motion_kernel) is read at record obj only after obj <
+// n_objects.
 #include <hip/hip_runtime.h>
 
 #include "rt_temporal.h"
@@ -82,11 +83,82 @@ __global__ void __launch_bounds__(TEMPORAL_THREADS) rt_temporal_kernel(const Tem
     store_texel(a, p, r.out, r.history, w.motion[0], w.motion[1]);
 }
 
+// rt_temporal_accumulate_moving: the same lane map and the same texel, with the motion table between the texel's own reads
+// and its projection.  (A kernel of its own and not a second instantiation of one routine: written that way, the compiler
+// scheduled rt_temporal_kernel differently, and that kernel is to stay what it was.)
+// The lane's object word -- `object` is required here -- picks its record: outside the table there is no history; a still
+// object's texel goes on as it is, without reading the record's matrices; a moved one's reads its 96 bytes (a wave's 64
+// adjacent texels hold a few objects at most: near-uniform addresses that stay in the cache; no LDS staging) and is
+// carried into the previous frame's world (rttp::carry) before anything looks at its point and normal.
+__global__ void __launch_bounds__(TEMPORAL_THREADS) rt_temporal_motion_kernel(const TemporalMotionArgs ma) {
+    const TemporalArgs& a = ma.t;
+    const uint32_t W = a.call.width, H = a.call.height;
+    const uint32_t tiles_x = (W + TILE_W - 1) / TILE_W;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const uint32_t x = tx * TILE_W + (threadIdx.x & (TILE_W - 1)), y = ty * TILE_H + threadIdx.x / TILE_W;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + (size_t)x;
+    const float4 c4 = reinterpret_cast<const float4*>(a.color)[p];
+    const float color[4] = {c4.x, c4.y, c4.z, c4.w};
+    float X[3] = {a.point[3 * p], a.point[3 * p + 1], a.point[3 * p + 2]};
+    float n[3] = {a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2]};
+    const uint32_t obj = a.object[p];
+    const float nan = rttp::u2f(rttp::QUIET_NAN);
+    // (obj < n_objects before the table is touched: nothing is read outside it)
+    if (!rttp::reprojectable(n, X, true, obj) || !rttp::in_table(obj, ma.n_objects)) {
+        store_texel(a, p, color, 1.0f, nan, nan);
+        return;
+    }
+    const rttp::Motion* m = ma.motions + obj;
+    if (m->moved != 0u) {
+        float cx[3], cn[3];
+        if (!rttp::carry(*m, X, n, cx, cn)) {
+            store_texel(a, p, color, 1.0f, nan, nan);
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[k] = cx[k], n[k] = cn[k];
+    }
+    const rttp::Where w = rttp::locate(a.call, X, x, y);
+    if (!w.on_screen) {
+        store_texel(a, p, color, 1.0f, nan, nan);
+        return;
+    }
+    const bool match_object = a.prev_object != nullptr;
+    rttp::Tap taps[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int32_t qx = w.ax.i0 + rttp::tap_dx(i), qy = w.ay.i0 + rttp::tap_dy(i);
+        rttp::Tap& t = taps[i];
+        t.inside = (uint32_t)qx < W && (uint32_t)qy < H;
+        const uint32_t cx = qx < 0 ? 0u : (uint32_t)qx >= W ? W - 1u : (uint32_t)qx;
+        const uint32_t cy = qy < 0 ? 0u : (uint32_t)qy >= H ? H - 1u : (uint32_t)qy;
+        const size_t q = (size_t)cy * W + (size_t)cx;
+        const float4 pc = reinterpret_cast<const float4*>(a.prev_color)[q];
+        t.c[0] = pc.x; t.c[1] = pc.y; t.c[2] = pc.z; t.c[3] = pc.w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            t.n[k] = a.prev_normal[3 * q + k];
+            t.x[k] = a.prev_point[3 * q + k];
+        }
+        t.h = a.prev_history[q];
+        t.obj = match_object ? a.prev_object[q] : 0u;
+    }
+    const rttp::Result r = rttp::resolve(a.call, w, X, n, match_object, obj, color, taps);
+    store_texel(a, p, r.out, r.history, w.motion[0], w.motion[1]);
+}
+
 }  // namespace
 
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream) {
     const uint32_t tiles = ((a.call.width + TILE_W - 1) / TILE_W) * ((a.call.height + TILE_H - 1) / TILE_H);   // (<= 2^31 / 8 + ...: fits)
     hipLaunchKernelGGL(rt_temporal_kernel, dim3(tiles), dim3(TEMPORAL_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_motion(const TemporalMotionArgs& a, hipStream_t stream) {
+    const uint32_t tiles = ((a.t.call.width + TILE_W - 1) / TILE_W) * ((a.t.call.height + TILE_H - 1) / TILE_H);
+    hipLaunchKernelGGL(rt_temporal_motion_kernel, dim3(tiles), dim3(TEMPORAL_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

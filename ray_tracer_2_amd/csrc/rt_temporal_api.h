@@ -1,10 +1,11 @@
 // rt_temporal_api.h -- what the units of temporal accumulation declare to each other (include/rt_abi.h:
-// rt_temporal_accumulate, rt_temporal_accumulate_host): the argument rules, the once-per-call numbers and the host
-// restatement (host/temporal.cpp), and the arguments of the device launch (rt_temporal.hip), all called by the entry points
+// rt_temporal_accumulate, rt_temporal_accumulate_host and their _moving forms): the argument rules, the once-per-call
+// numbers and the host restatement (host/temporal.cpp), and the arguments of the device launch (rt_temporal.hip), all called by the entry points
 // in rt_api.hip.  The arithmetic they share is csrc/rt_temporal.h.
 #ifndef RT_TEMPORAL_API_H
 #define RT_TEMPORAL_API_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -20,6 +21,17 @@ int temporal_check(const rt_temporal_desc* d, bool device, bool host_memory, std
 // The once-per-call numbers of a checked desc: V = mat4_inverse(prev_camera.cam_to_world) (host/glam_math.h), view_params.
 rttp::Call temporal_call(const rt_temporal_desc* d);
 int temporal_host(const rt_temporal_desc* d, std::string& err);
+
+// The _moving forms.  rt_temporal_motion_desc is rt_temporal_desc with the table behind it: its head, as an rt_temporal_desc
+// of its own (struct_bytes set), is what temporal_check and temporal_call are given.
+static_assert(offsetof(rt_temporal_motion_desc, motions) == sizeof(rt_temporal_desc) && sizeof(rt_temporal_motion_desc) == sizeof(rt_temporal_desc) + 16,
+              "rt_temporal_motion_desc is rt_temporal_desc and the table");
+static_assert(sizeof(rt_object_motion) == 96 && sizeof(rttp::Motion) == 96 && offsetof(rt_object_motion, nt) == offsetof(rttp::Motion, nt) &&
+              offsetof(rt_object_motion, moved) == offsetof(rttp::Motion, moved), "rttp::Motion is rt_object_motion");
+rt_temporal_desc temporal_head(const rt_temporal_motion_desc* d);
+// temporal_check on the head, then the table's own rules (on device memory the table is 16-byte aligned).
+int temporal_motion_check(const rt_temporal_motion_desc* d, bool device, bool host_memory, std::string& err);
+int temporal_motion_host(const rt_temporal_motion_desc* d, std::string& err);
 }  // namespace rt2
 
 namespace rtd {
@@ -37,6 +49,12 @@ struct TemporalArgs {
     float* out;                  // [h][w][4]; may be `color`
     float* out_history;          // [h][w]
     float* motion;               // [h][w][2] or null
+};
+// rt_temporal_accumulate_moving: the same planes (object is there) and the table, 16-byte aligned
+struct TemporalMotionArgs {
+    TemporalArgs t;
+    const rttp::Motion* motions;   // [n_objects]
+    uint32_t n_objects;
 };
 }  // namespace rtd
 

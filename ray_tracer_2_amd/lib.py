@@ -30,6 +30,7 @@ EXPORTS = [
     "rt_scene_destroy", "rt_upload_built_scene", "rt_scene_subdivide_meshes", "rt_export_rgba8",
     "rt_intersect_rays", "rt_occluded_rays", "rt_pick", "rt_render_gbuffer", "rt_radiance_rays",
     "rt_denoise", "rt_denoise_host", "rt_temporal_accumulate", "rt_temporal_accumulate_host",
+    "rt_temporal_accumulate_moving", "rt_temporal_accumulate_moving_host", "rt_object_motions",
     "rt_denoise_variance", "rt_luminance_moments", "rt_denoise_variance_host", "rt_luminance_moments_host",
     "rt_adaptive_plan", "rt_adaptive_merge", "rt_adaptive_plan_host", "rt_adaptive_merge_host",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
@@ -151,6 +152,9 @@ def _bind(L, with_test_entries):
         "rt_denoise_host": (i32, [P(A.DenoiseDesc)]),
         "rt_temporal_accumulate": (i32, [vp, P(A.TemporalDesc), i32]),
         "rt_temporal_accumulate_host": (i32, [P(A.TemporalDesc)]),
+        "rt_temporal_accumulate_moving": (i32, [vp, P(A.TemporalMotionDesc), i32]),
+        "rt_temporal_accumulate_moving_host": (i32, [P(A.TemporalMotionDesc)]),
+        "rt_object_motions": (i32, [vp, vp, u32, vp, vp, u32, vp]),
         "rt_denoise_variance": (i32, [vp, P(A.VDenoiseDesc), i32]),
         "rt_luminance_moments": (i32, [vp, P(A.VDenoiseDesc), i32]),
         "rt_denoise_variance_host": (i32, [P(A.VDenoiseDesc)]),

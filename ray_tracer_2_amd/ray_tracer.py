@@ -177,18 +177,68 @@ def _temporal_result(res):
     return (res["out"], res["out_history"]) if res["motion"] is None else (res["out"], res["out_history"], res["motion"])
 
 
+def _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history, point_tolerance, normal_cos,
+                   motions):
+    """The entry point's name stem, its desc, its plane table, the inputs by name and the frame's size: rt_temporal_accumulate
+    without a motion table, rt_temporal_accumulate_moving with one (`motions`: (n,) OBJECT_MOTION_DTYPE, or an (n, 24) int32
+    tensor of the records' words)."""
+    planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
+    d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
+    if motions is None:
+        return "rt_temporal_accumulate", d, A.TEMPORAL_PLANES, planes, W, H
+    if "object" not in planes:
+        raise ValueError("guides must hold the object plane of render_gbuffer: the motion table is indexed by it")
+    if hasattr(motions, "data_ptr"):
+        if motions.dim() != 2 or motions.shape[1] != 24 or motions.shape[0] < 1:
+            raise ValueError("a motion table on the device is an (n_objects, 24) int32 tensor of the records' words")
+        entry = ("<u4", (int(motions.shape[0]), 24))
+    else:
+        motions = np.asarray(motions)
+        if motions.dtype != A.OBJECT_MOTION_DTYPE or motions.ndim != 1 or motions.shape[0] < 1:
+            raise ValueError("a motion table is a one-dimensional OBJECT_MOTION_DTYPE array (object_motions) with a record or more")
+        entry = (A.OBJECT_MOTION_DTYPE, (int(motions.shape[0]),))
+    md = A.TemporalMotionDesc.from_buffer_copy(bytes(d) + bytes(C.sizeof(A.TemporalMotionDesc) - C.sizeof(A.TemporalDesc)))
+    md.struct_bytes, md.n_objects = C.sizeof(A.TemporalMotionDesc), entry[1][0]
+    planes["motions"] = motions
+    return "rt_temporal_accumulate_moving", md, dict(A.TEMPORAL_MOTION_PLANES, motions=entry), planes, W, H
+
+
 def temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history=float("inf"),
                              point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
-                             motion=False):
-    """rt_temporal_accumulate_host: temporal accumulation's definition on the CPU (no device), with
-    RayTracer.temporal_accumulate's arguments for numpy planes.  RayTracer.temporal_accumulate computes the same bits on the
-    GPU."""
-    planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
+                             motion=False, motions=None):
+    """rt_temporal_accumulate_host (with `motions`, a table of object_motions: rt_temporal_accumulate_moving_host): temporal
+    accumulation's definition on the CPU (no device), with RayTracer.temporal_accumulate's arguments for numpy planes.
+    RayTracer.temporal_accumulate computes the same bits on the GPU."""
+    fn, d, table, planes, W, H = _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history,
+                                                point_tolerance, normal_cos, motions)
     if color is None:
         raise ValueError("color is required on the host")
-    d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
     outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
-    return _temporal_result(_host_frame_call("rt_temporal_accumulate_host", d, A.TEMPORAL_PLANES, W, H, planes, outs))
+    return _temporal_result(_host_frame_call(fn + "_host", d, table, W, H, planes, outs))
+
+
+def object_motions(prev_arrays, arrays):
+    """rt_object_motions: the motion table that temporal_accumulate(..., motions=) takes, from two SceneArrays of one scene --
+    before and after its meshes' transforms and its spheres were edited (the same topology: ValueError when the mesh or
+    sphere counts differ).  Returns an (n_meshes + n_spheres,) OBJECT_MOTION_DTYPE array, indexed by the G-buffer's object
+    word: per object whether it moved, and the map that carries its points and normals from the current frame's world to
+    the previous frame's."""
+    def records(x, dtype):
+        a = np.ascontiguousarray(x)
+        if a.nbytes % dtype.itemsize:
+            raise ValueError(f"an array of {a.nbytes} bytes does not hold whole {dtype.itemsize}-byte records")
+        return a, a.nbytes // dtype.itemsize
+    (pm, npm), (m, nm) = records(prev_arrays.meshes, A.MESH_DTYPE), records(arrays.meshes, A.MESH_DTYPE)
+    (ps, nps), (s, ns) = records(prev_arrays.spheres, A.SPHERE_DTYPE), records(arrays.spheres, A.SPHERE_DTYPE)
+    if npm != nm or nps != ns:
+        raise ValueError(f"the two scene states differ in topology: {npm} and {nm} meshes, {nps} and {ns} spheres")
+    out = np.zeros(nm + ns, A.OBJECT_MOTION_DTYPE)
+    L = load()
+    rc = L.rt_object_motions(pm.ctypes.data if nm else None, m.ctypes.data if nm else None, nm,
+                             ps.ctypes.data if ns else None, s.ctypes.data if ns else None, ns, out.ctypes.data if nm + ns else None)
+    if rc < 0:
+        raise RtError(rc, "rt_object_motions refused its arguments")
+    return out
 
 
 # The variance-guided denoiser's defaults (RayTracer.denoise_variance, denoise_variance_host): a luminance difference of
@@ -805,7 +855,7 @@ class RayTracer:
 
     def temporal_accumulate(self, guides, prev_guides, prev_camera, prev_color, prev_history, color=None, max_history=float("inf"),
                             point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
-                            motion=False):
+                            motion=False, motions=None):
         """Temporal accumulation across a camera move (rt_temporal_accumulate; include/rt_abi.h has the definition): every
         texel of the current frame `color` (H, W, 4) fetches the history `prev_color` (H, W, 4) / `prev_history` (H, W;
         frames accumulated, as float32 >= 1) from where its hit point lay under `prev_camera` (a CameraUniform), through
@@ -817,13 +867,21 @@ class RayTracer:
         an array / tensor to fill) (out, out_history, motion): motion is the screen-space offset, in texels, to the
         position the history came from (NaN where nothing was reprojected).  out / out_history must not be any prev_*
         plane; `out` may be `color`.
+        `motions` (rt_temporal_accumulate_moving): the table of object_motions(prev_arrays, arrays) for a scene whose
+        meshes or spheres moved between the two frames -- `guides` must then hold `object`.  A moved object's texels fetch
+        the history of their own surface point, and `motion` is what the camera and the object produce together; an object
+        the table marks as still is worked as without a table.  What is kept is the object's own history, not the lighting
+        that changed around it: `max_history` bounds how long that lags.  A second call with the luminance moments as
+        color / prev_color and the same `motions` accumulates the moments denoise_variance takes for a moving object, as it
+        does for a moving camera.
         numpy planes: a synchronous call that returns numpy arrays.  Torch tensors on this handle's device: an asynchronous
         call ordered after the current torch stream's work, as render_gbuffer(device=True) orders itself; returns tensors;
-        there color=None takes the handle's image as the current frame."""
-        planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
-        d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
+        there color=None takes the handle's image as the current frame, and `motions` is an (n_objects, 24) int32 tensor of
+        the records' words (torch.from_numpy(table.view(np.int32).reshape(-1, 24)) moved to the device)."""
+        fn, d, table, planes, W, H = _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history,
+                                                    point_tolerance, normal_cos, motions)
         outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
-        return _temporal_result(self._frame_call("rt_temporal_accumulate", A.TEMPORAL_HOST_MEMORY, d, A.TEMPORAL_PLANES, W, H, planes, outs))
+        return _temporal_result(self._frame_call(fn, A.TEMPORAL_HOST_MEMORY, d, table, W, H, planes, outs))
 
     def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):
         """Radiance along rays of the caller's (rt_radiance_rays): for ray i `frag`'s sample loop with the ray held fixed --

@@ -8,7 +8,9 @@ does.
 
 Rows: one per camera move -- `unmoved`, `1 texel` and `16 texels` (the camera translated to its right by what shifts the
 image by about that much at the scene's mean depth; the row reports the mean |motion| the call itself measured and the share
-of hit texels that found history) --, `16x16`, the same call on a frame of 256 misses, which is what a call costs before it
+of hit texels that found history) --, two of the call with a motion table (rt_temporal_accumulate_moving) under the unmoved
+camera: `table, all still`, every record with moved == 0, and `table, both boxes moved`, the fixture's two boxes moved by
+update_instances between the frames (the row also reports the motion and the history found on the boxes' texels) --, `16x16`, the same call on a frame of 256 misses, which is what a call costs before it
 moves anything (the host's part and the launch), and `copy`, a device-to-device copy that moves the bytes the call must move: every
 input plane read once (92 B per texel) and every output written once (28 B per texel), so the copy reads and writes 60 B
 per texel.  Per row one JSON line: the median, the smallest and the largest window in ms per call, the bytes per second, and
@@ -93,6 +95,56 @@ def main():
         notes[name] = {"mean_motion_texels": round(float(np.linalg.norm(mo[found], axis=-1).mean()), 3),
                        "history_found": round(float(found.sum() / now_hit.sum()), 4)}
     tr.set_camera(base)
+
+    # the call with a motion table (rt_temporal_accumulate_moving), under the unmoved camera: `table, all still` on the
+    # frames of the `unmoved` row with a table of identical states, and `table, both boxes moved` on a current frame
+    # rendered after update_instances moved meshes 5 and 6 (0.06 / -0.04 along x, turned 0.05 / -0.08 rad about the
+    # vertical axis through their centroids), with the table of object_motions
+    def moved_mesh(meshes, k, shift, angle):
+        tri = arrays.triangles[int(meshes[k]["triangle_offset"]):int(meshes[k]["triangle_offset"]) + int(meshes[k]["triangles"])]
+        m2w = np.array(meshes[k]["model_to_world"], np.float64).T
+        v = np.concatenate([tri["v1"], tri["v2"], tri["v3"]]).astype(np.float64)
+        pivot = (v @ m2w[:3, :3].T + m2w[:3, 3]).mean(0)
+        c, s = np.cos(angle), np.sin(angle)
+        T = np.eye(4)
+        T[:3, :3] = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
+        T[:3, 3] = pivot - T[:3, :3] @ pivot + np.array([shift, 0.0, 0.0])
+        new = T @ m2w
+        meshes["model_to_world"][k], meshes["world_to_model"][k] = new.T, np.linalg.inv(new).T
+
+    meshes = arrays.meshes.copy()
+    moved_mesh(meshes, 5, 0.06, 0.05)
+    moved_mesh(meshes, 6, -0.04, -0.08)
+    moved = rt.SceneArrays(arrays.uniform, arrays.spheres, meshes, arrays.triangles, arrays.nodes, arrays.textures)
+    for name, state in (("table, all still", arrays), ("table, both boxes moved", moved)):
+        tr.update_instances(state)
+        color, g = frame(base)
+        table = rt.object_motions(arrays, state)
+        dev_table = torch.from_numpy(table.view(np.int32).reshape(-1, 24).copy()).to(dev)
+        d = A.TemporalMotionDesc(struct_bytes=C.sizeof(A.TemporalMotionDesc), width=W, height=H, prev_camera=type(base).from_buffer_copy(bytes(base)),
+                                 max_history=float("inf"), point_tolerance=rt.ray_tracer.TEMPORAL_POINT_TOLERANCE,
+                                 normal_cos=rt.ray_tracer.TEMPORAL_NORMAL_COS, color=color.data_ptr(), prev_color=prev_color.data_ptr(),
+                                 prev_history=prev_history.data_ptr(), out=out.data_ptr(), out_history=out_history.data_ptr(),
+                                 motion=motion.data_ptr(), motions=dev_table.data_ptr(), n_objects=len(table),
+                                 **{k: v.data_ptr() for k, v in g.items()}, **{"prev_" + k: v.data_ptr() for k, v in pg.items()})
+
+        def f(d=d, keep=(color, g, dev_table)):
+            ext.wait_stream(cur)
+            tr._check(tr._L.rt_temporal_accumulate_moving(tr._h, C.byref(d), 0))
+            cur.wait_stream(ext)
+        rows[name] = f
+        f()
+        torch.cuda.synchronize()
+        mo, hi, ob = motion.cpu().numpy(), out_history.cpu().numpy(), g["object"].cpu().numpy()
+        now_hit = (g["normal"].cpu().numpy() != 0).any(-1)
+        found = now_hit & (hi > 1)
+        boxes = (ob == 5) | (ob == 6)
+        notes[name] = {"mean_motion_texels": round(float(np.linalg.norm(mo[found], axis=-1).mean()), 3),
+                       "history_found": round(float(found.sum() / now_hit.sum()), 4),
+                       "objects_moved": int(table["moved"].sum()), "texels_of_moved_objects": int((boxes & (table["moved"][5] != 0)).sum()),
+                       "mean_motion_on_them": round(float(np.linalg.norm(mo[found & boxes], axis=-1).mean()), 3),
+                       "history_found_on_them": round(float((found & boxes).sum() / boxes.sum()), 4)}
+    tr.update_instances(arrays)
     # what a call costs before it moves anything: the same call on a 16 x 16 frame of misses
     tiny = {k: torch.zeros(16 * 16 * 4, dtype=torch.float32, device=dev) for k in A.TEMPORAL_PLANES}
     d16 = A.TemporalDesc(struct_bytes=C.sizeof(A.TemporalDesc), width=16, height=16, prev_camera=type(base).from_buffer_copy(bytes(base)),

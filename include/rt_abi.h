@@ -693,8 +693,9 @@ int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags);
  * raw sample of seed k (rt_render with frames = -k), every reprojectable texel takes one tap of weight 1 and `out` is what
  * rt_render with frames = k leaves in the image, bit for bit, alpha included.
  * Rigidly or affinely moved meshes and moved or resized spheres keep their history through rt_temporal_accumulate_moving
- * (below).  Still out of scope: a mesh whose vertices moved (rt_refit_triangles) and the sky -- their texels fail the plane
- * test or are misses, and restart at history 1.
+ * (below), and a mesh whose vertices moved (rt_refit_triangles) keeps it through rt_temporal_accumulate_deforming (below
+ * that).  Still out of scope: a mesh whose topology changed and the sky -- their texels fail the plane test or are misses,
+ * and restart at history 1.
  * point_tolerance is the distance from the current texel's tangent plane that a tap's hit point may have, per unit of view
  * depth (the footprint of a texel grows with depth); normal_cos the least cosine between the two normals.
  * rt_temporal_accumulate_host (section 3) is this definition over host pointers, without a device;
@@ -771,7 +772,8 @@ int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags
 typedef struct rt_object_motion {
     float    d[4][3];    /* current world -> previous world, column-major [col][row]: X' = d * (X, 1) */
     float    nt[3][3];   /* [col][row]: m = nt * n is the previous-world normal before normalisation */
-    uint32_t moved;      /* 0: the object stands still, the record's matrices are not read */
+    uint32_t moved;      /* 0: the object stands still, the record's matrices are not read; 2: DEFORMED for
+                            rt_temporal_accumulate_deforming (any non-zero value is "moved" to rt_temporal_accumulate_moving) */
     uint32_t _p[2];      /* 0 */
 } rt_object_motion;      /* 96 bytes */
 typedef struct rt_temporal_motion_desc {
@@ -799,6 +801,87 @@ typedef struct rt_temporal_motion_desc {
     uint32_t          _p1;              /* must be 0 */
 } rt_temporal_motion_desc;              /* rt_temporal_desc's fields in their order, then the table */
 int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags);
+
+/* Temporal accumulation across deforming meshes: rt_temporal_accumulate_moving with a third kind
+ * of record.  A mesh whose vertices moved (rt_refit_triangles) has no one map from the current world to the previous one,
+ * but the G-buffer says which triangle of the uploaded array each texel hit and where (primitive, bary, flags:
+ * rt_render_gbuffer's), and the caller still holds the triangles that rt_refit_triangles replaced: the previous-world
+ * position of a texel's surface point is the barycentric interpolation of the PREVIOUS triangle's vertices under the
+ * previous model_to_world.  rt_object_motions_deforming (section 3) fills the table.  Everything is binary32 and unfused,
+ * in this order; what is not restated here is rt_temporal_accumulate_moving's definition above, word for word.
+ *   motions[k].moved is read three ways: 0 -- the object stands still; 2 -- DEFORMED, below; any other value -- carried
+ *   rigidly, exactly as by rt_temporal_accumulate_moving.  (The two calls above take every non-zero value as moved.)
+ *   For a REPROJECTABLE texel p with k = object(p) < n_objects and motions[k].moved == 2, with t = primitive(p) and
+ *   (u, v) = bary(p):
+ *   t < tri_first, or t - tri_first >= n_prev_triangles, or u or v not finite: the "no history" result -- out(p) =
+ *   color(p) bit for bit, out_history(p) = 1, motion(p) = two quiet NaNs.  prev_triangles is read only after this test.
+ *   Otherwise, with T = prev_triangles[t - tri_first], d = motions[k].d, nt = motions[k].nt and w = (1 - u) - v, for
+ *   r = 0, 1, 2:
+ *     Xm_r = (T.v1_r * w + T.v2_r * u) + T.v3_r * v      (the order of the render kernel's normal interpolation)
+ *     X'_r = ((d[0][r] Xm0 + d[1][r] Xm1) + d[2][r] Xm2) + d[3][r]
+ *     g_r  = (T.n1_r * w + T.n2_r * u) + T.n3_r * v
+ *     m_r  = (nt[0][r] g0 + nt[1][r] g1) + nt[2][r] g2
+ *     len  = sqrt((m0 m0 + m1 m1) + m2 m2)               (the correctly rounded square root)
+ *     s    = (flags(p) & RT_HIT_BACKFACE) ? -1 : 1
+ *     n'_r = (m_r / len) * s
+ *   One normalisation, where the shader has two (of g, then of the transformed normal: wgsl:386): n' only feeds the
+ *   normal cosine and the plane distance, whose thresholds are far wider than the few ulp between the two.  The render
+ *   kernel's RT_HIT_BACKFACE on a triangle is exactly the factor -1 on its interpolated normal, hence s.
+ *   If some component of X' or n' is not finite (a degenerate previous triangle whose normals interpolate to zero length
+ *   gives NaN): the "no history" result.  Otherwise the texel is worked as by rt_temporal_accumulate with X' in the place
+ *   of X and n' in the place of n throughout: the projection and the on-screen test, the snap, motion(p), each tap's plane
+ *   distance and normal cosine, the object match and the blend.
+ *   A mesh that deforms and also moves rigidly needs nothing more: d is its previous model_to_world.
+ * Consequences: (a) with a table that has no record of moved == 2 every output plane is rt_temporal_accumulate_moving's bit
+ * for bit, whatever primitive, bary, flags and prev_triangles hold.  (b) With prev_triangles = the current triangles, an
+ * unmoved camera and the same G-buffer on both sides every deformed texel's X' lies within a few ulp of point(p), far
+ * inside the 1/64-texel snap; it takes its own texel as its one tap, motion(p) = (0, 0), and every output plane is
+ * rt_temporal_accumulate's bit for bit -- and so rt_render's own accumulation.
+ * What still lags or restarts: the lighting around a deforming object lags as it does around a moving one (max_history
+ * bounds it); a change of topology restarts (the primitive word then names another triangle or none); the sky restarts;
+ * a sphere given moved == 2 by a hand-made table restarts or fetches a wrong triangle's history -- its primitive word is
+ * read as a triangle index -- which rt_object_motions_deforming never produces.
+ * A second call with the luminance moments as color / prev_color and the same arguments accumulates the moments that
+ * rt_denoise_variance takes for a deforming object.
+ * Memory, asynchrony, aliasing and side effects are rt_temporal_accumulate_moving's.  primitive, bary, flags and
+ * prev_triangles are on the side of the planes: device pointers without RT_TEMPORAL_HOST_MEMORY (primitive and bary 4-byte
+ * aligned, flags 1, prev_triangles 16); with it host pointers, the three planes and the n_prev_triangles * 96 bytes staged
+ * with the rest and counted against option "max_device_mb" with them.  The call never reads the uploaded scene: no scene
+ * is needed.
+ * Errors, nothing written: rt_temporal_accumulate_moving's (struct_bytes != sizeof(rt_temporal_deform_desc)), and
+ * RT_ERR_INVALID_ARGUMENT for a null primitive, bary, flags or prev_triangles, n_prev_triangles == 0, tri_first +
+ * n_prev_triangles past 2^32, a misaligned device plane or triangle array. */
+typedef struct rt_temporal_deform_desc {
+    uint32_t          struct_bytes;     /* = sizeof(rt_temporal_deform_desc) */
+    uint32_t          _p0;              /* must be 0 */
+    uint32_t          width, height;
+    rt_camera_uniform prev_camera;
+    float             max_history;
+    float             point_tolerance;
+    float             normal_cos;
+    const float*      color;
+    const float*      point;
+    const float*      normal;
+    const uint32_t*   object;           /* [h][w] current: required */
+    const float*      prev_color;
+    const float*      prev_history;
+    const float*      prev_point;
+    const float*      prev_normal;
+    const uint32_t*   prev_object;      /* [h][w] or NULL */
+    float*            out;
+    float*            out_history;
+    float*            motion;           /* [h][w][2] or NULL */
+    const rt_object_motion* motions;    /* [n_objects], indexed by the object word */
+    uint32_t          n_objects;        /* >= 1 */
+    uint32_t          _p1;              /* must be 0 */
+    const uint32_t*   primitive;        /* [h][w]    current G-buffer: required */
+    const float*      bary;             /* [h][w][2] current G-buffer: required */
+    const uint8_t*    flags;            /* [h][w]    current G-buffer: required */
+    const rt_packed_triangle* prev_triangles;   /* [n_prev_triangles]: triangles [tri_first, tri_first + n) of the uploaded
+                                                   array as they were in the PREVIOUS frame */
+    uint32_t          tri_first, n_prev_triangles;   /* n >= 1 */
+} rt_temporal_deform_desc;              /* rt_temporal_motion_desc's fields in their order, then the triangle side */
+int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags);
 
 /* Variance-guided denoising: the variance half of SVGF (Schied et al. 2017, sections 4.2 - 4.4)
  * over rt_denoise's guides.  rt_luminance_moments writes the per-frame sample of the luminance moments;
@@ -1106,6 +1189,8 @@ int rt_denoise_host(const rt_denoise_desc* desc);
 int rt_temporal_accumulate_host(const rt_temporal_desc* desc);
 /* The same for rt_temporal_accumulate_moving: `motions` is a host pointer. */
 int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc);
+/* The same for rt_temporal_accumulate_deforming: motions, primitive, bary, flags and prev_triangles are host pointers. */
+int rt_temporal_accumulate_deforming_host(const rt_temporal_deform_desc* desc);
 
 /* The motion table of rt_temporal_accumulate_moving from two states of one scene (the arrays rt_update_instances takes,
  * before and after the edit): out[0, n_meshes + n_spheres), meshes first.  Plain C++, no device.  Binary32, unfused.
@@ -1121,6 +1206,15 @@ int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc);
  * RT_ERR_INVALID_ARGUMENT, nothing written: a null `out` with a non-zero total, a null array with a non-zero count. */
 int rt_object_motions(const rt_mesh_uniform* prev_meshes, const rt_mesh_uniform* meshes, uint32_t n_meshes,
                       const rt_sphere* prev_spheres, const rt_sphere* spheres, uint32_t n_spheres, rt_object_motion* out);
+/* The table of rt_temporal_accumulate_deforming: rt_object_motions' arguments and, per mesh, whether its vertices moved
+ * between the two states (deformed[k] != 0).  Such a mesh's record has moved = 2, d[c][r] = prev_meshes[k].
+ * model_to_world[c][r] (c < 4, r < 3) -- the previous triangle's model-space point goes straight to the previous world --
+ * and nt[c][r] = prev_meshes[k].model_to_world[c][r] (c, r < 3): the shader carries normals by model_to_world as
+ * directions (wgsl:386), not by the inverse transpose.  Every other record is rt_object_motions' byte for byte.
+ * RT_ERR_INVALID_ARGUMENT, nothing written: rt_object_motions', and a null `deformed` with n_meshes > 0. */
+int rt_object_motions_deforming(const rt_mesh_uniform* prev_meshes, const rt_mesh_uniform* meshes, uint32_t n_meshes,
+                                const rt_sphere* prev_spheres, const rt_sphere* spheres, uint32_t n_spheres,
+                                const uint8_t* deformed /* [n_meshes] */, rt_object_motion* out);
 
 /* The variance-guided denoiser's definition (section 2: rt_denoise_variance, rt_luminance_moments) in executable form:
  * plain C++ over host pointers, no device.  `color` is required; `out` may be `color`.  The same argument errors as the

@@ -184,6 +184,13 @@ class TemporalMotionDesc(C.Structure):  # rt_temporal_motion_desc: rt_temporal_d
 OBJECT_MOTION_DTYPE = np.dtype([("d", "<f4", (4, 3)), ("nt", "<f4", (3, 3)), ("moved", "<u4"), ("_p", "<u4", 2)])
 assert OBJECT_MOTION_DTYPE.itemsize == C.sizeof(ObjectMotion) == 96
 TEMPORAL_MOTION_PLANES = dict(TEMPORAL_PLANES, motions=(OBJECT_MOTION_DTYPE, None))
+OBJECT_DEFORMED = 2   # rt_object_motion.moved of a mesh whose vertices moved (rt_temporal_accumulate_deforming)
+
+
+class TemporalDeformDesc(C.Structure):  # rt_temporal_deform_desc: rt_temporal_motion_desc's fields, then the triangle side
+    _fields_ = TemporalMotionDesc._fields_ + [("primitive", C.c_void_p), ("bary", C.c_void_p), ("flags", C.c_void_p),
+                                              ("prev_triangles", C.c_void_p), ("tri_first", u32), ("n_prev_triangles", u32)]
+
 
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
@@ -207,6 +214,11 @@ MESH_DTYPE = np.dtype([("world_to_model", "<f4", (4, 4)), ("model_to_world", "<f
                        ("_p1", "<f4"), ("material", MATERIAL_DTYPE)])
 SPHERE_DTYPE = np.dtype([("pos", "<f4", 3), ("radius", "<f4"), ("material", MATERIAL_DTYPE)])
 assert NODE_DTYPE.itemsize == 48 and TRI_DTYPE.itemsize == 96
+# rt_temporal_accumulate_deforming's planes: TEMPORAL_MOTION_PLANES, the G-buffer's primitive, bary and flags planes of the
+# current frame and the previous triangles, which are not frame-shaped -- (n,) TRI_DTYPE on the host, an (n, 24) float32
+# tensor on the device, as refit_triangles takes them; the calls put the shape in
+TEMPORAL_DEFORM_PLANES = dict(TEMPORAL_MOTION_PLANES, primitive=("<u4", 0), bary=("<f4", 2), flags=("u1", 0),
+                              prev_triangles=(TRI_DTYPE, None))
 assert MESH_DTYPE.itemsize == 240 and SPHERE_DTYPE.itemsize == 112
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("dir", "<f4", 3), ("_p0", "<u4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<u4"), ("primitive", "<u4"), ("flags", "<u4"), ("point", "<f4", 3),

@@ -1,5 +1,5 @@
-// host/object_motions.cpp -- rt_object_motions (include/rt_abi.h, section 3): the motion table of
-// rt_temporal_accumulate_moving from two states of one scene.  Plain C++ without a device; binary32, unfused
+// host/object_motions.cpp -- rt_object_motions and rt_object_motions_deforming (include/rt_abi.h, section 3): the motion
+// table of rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming from two states of one scene.  Plain C++ without a device; binary32, unfused
 // (-ffp-contract=off), in the order the header states so that a numpy restatement gives the same bits.
 #include <cstring>
 
@@ -40,6 +40,26 @@ extern "C" int rt_object_motions(const rt_mesh_uniform* prev_meshes, const rt_me
             o.d[3][r] = was.pos[r] - s * now.pos[r];
             o.nt[r][r] = 1.0f;
         }
+    }
+    return RT_OK;
+}
+
+// rt_object_motions_deforming: that table, with the record of every mesh whose vertices moved replaced by the DEFORMED one
+// -- the previous model_to_world for the points and, as the shader carries normals, its 3 x 3 for the directions.
+extern "C" int rt_object_motions_deforming(const rt_mesh_uniform* prev_meshes, const rt_mesh_uniform* meshes, uint32_t n_meshes,
+                                           const rt_sphere* prev_spheres, const rt_sphere* spheres, uint32_t n_spheres,
+                                           const uint8_t* deformed, rt_object_motion* out) {
+    if (n_meshes && !deformed) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = rt_object_motions(prev_meshes, meshes, n_meshes, prev_spheres, spheres, n_spheres, out); rc != RT_OK) return rc;
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        if (!deformed[k]) continue;
+        rt_object_motion& o = out[k];
+        std::memset(&o, 0, sizeof(o));
+        o.moved = 2u;
+        for (int c = 0; c < 4; ++c)
+            for (int r = 0; r < 3; ++r) o.d[c][r] = prev_meshes[k].model_to_world[c][r];
+        for (int c = 0; c < 3; ++c)
+            for (int r = 0; r < 3; ++r) o.nt[c][r] = prev_meshes[k].model_to_world[c][r];
     }
     return RT_OK;
 }

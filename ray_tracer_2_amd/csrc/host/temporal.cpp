@@ -1,6 +1,6 @@
 // host/temporal.cpp -- temporal accumulation's definition in executable form (include/rt_abi.h:
-// rt_temporal_accumulate_host and, with a motion table, rt_temporal_accumulate_moving_host -- one loop for both; DESIGN.md
-// section 2.14), the argument rules and the once-per-call numbers it shares with
+// rt_temporal_accumulate_host and, with a motion table, rt_temporal_accumulate_moving_host and
+// rt_temporal_accumulate_deforming_host -- one loop for the three), the argument rules and the once-per-call numbers it shares with
 // the device entry point.  Plain C++ over host pointers; the per-texel arithmetic is csrc/rt_temporal.h, which the device
 // kernel evaluates too.  Compiled with -ffp-contract=off.
 #if defined(__HIPCC__)
@@ -90,8 +90,37 @@ int temporal_motion_check(const rt_temporal_motion_desc* d, bool device, bool ho
     return RT_OK;
 }
 
-// The loop of both host entry points: motions == nullptr is rt_temporal_accumulate_host.
-static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motions, uint32_t n_objects) {
+rt_temporal_motion_desc temporal_motion_head(const rt_temporal_deform_desc* d) {
+    rt_temporal_motion_desc head;
+    std::memcpy(&head, d, sizeof(head));
+    head.struct_bytes = sizeof(head);
+    return head;
+}
+
+int temporal_deform_check(const rt_temporal_deform_desc* d, bool device, bool host_memory, std::string& err) {
+    auto bad = [&](int code, const char* msg) {
+        err = msg;
+        return code;
+    };
+    if (!d) return bad(RT_ERR_INVALID_ARGUMENT, "null rt_temporal_deform_desc");
+    if (d->struct_bytes != sizeof(rt_temporal_deform_desc))
+        return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_deform_desc.struct_bytes is not sizeof(rt_temporal_deform_desc)");
+    const rt_temporal_motion_desc head = temporal_motion_head(d);
+    if (const int rc = temporal_motion_check(&head, device, host_memory, err); rc != RT_OK) return rc;
+    if (!d->primitive || !d->bary || !d->flags) return bad(RT_ERR_INVALID_ARGUMENT, "null primitive, bary or flags plane (a deformed texel's triangle is named by them)");
+    if (!d->prev_triangles) return bad(RT_ERR_INVALID_ARGUMENT, "null prev_triangles");
+    if (d->n_prev_triangles == 0u) return bad(RT_ERR_INVALID_ARGUMENT, "n_prev_triangles is zero");
+    if ((uint64_t)d->tri_first + d->n_prev_triangles > 0x100000000ull) return bad(RT_ERR_INVALID_ARGUMENT, "tri_first + n_prev_triangles is past 2^32");
+    if (device && !host_memory) {
+        const PlaneAlign side[4] = {{d->primitive, 3u, "primitive"}, {d->bary, 3u, "bary"}, {d->flags, 0u, "flags"}, {d->prev_triangles, 15u, "prev_triangles"}};
+        return misaligned(side, 4, err);
+    }
+    return RT_OK;
+}
+
+// The loop of the three host entry points: motions == nullptr is rt_temporal_accumulate_host; deform == nullptr with a
+// table is rt_temporal_accumulate_moving_host, where every non-zero `moved` is carried rigidly.
+static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motions, uint32_t n_objects, const rt_temporal_deform_desc* deform = nullptr) {
     const rttp::Call c = temporal_call(d);
     const int64_t W = d->width, H = d->height;
     const bool match_object = d->object && d->prev_object;
@@ -112,11 +141,23 @@ static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motion
             float carried_x[3], carried_n[3];
             if (go && motions) {
                 // a word outside the table has no history; a still object's texel goes on as it is; a moved one's is carried
+                // (three ways with the triangle side: still, deformed -- carried by its previous triangle --, rigid)
                 go = rttp::in_table(obj, n_objects);
                 if (go && motions[obj].moved != 0u) {
                     rttp::Motion m;
                     std::memcpy(&m, motions + obj, sizeof(m));
-                    go = rttp::carry(m, X, n, carried_x, carried_n);
+                    if (deform && m.moved == rttp::DEFORMED) {
+                        const uint32_t t = deform->primitive[p];
+                        const float u = deform->bary[2 * p], v = deform->bary[2 * p + 1];
+                        go = rttp::has_prev_triangle(t, deform->tri_first, deform->n_prev_triangles, u, v);
+                        if (go) {
+                            rttp::Tri tri;
+                            std::memcpy(&tri, deform->prev_triangles + (t - deform->tri_first), sizeof(tri));
+                            go = rttp::carry_deformed(m, tri, u, v, (deform->flags[p] & rttp::HIT_BACKFACE) != 0u, carried_x, carried_n);
+                        }
+                    } else {
+                        go = rttp::carry(m, X, n, carried_x, carried_n);
+                    }
                     X = carried_x;
                     n = carried_n;
                 }
@@ -161,6 +202,14 @@ int temporal_motion_host(const rt_temporal_motion_desc* d, std::string& err) {
     if (const int rc = temporal_motion_check(d, false, false, err); rc != RT_OK) return rc;
     const rt_temporal_desc head = temporal_head(d);
     accumulate(&head, d->motions, d->n_objects);
+    return RT_OK;
+}
+
+int temporal_deform_host(const rt_temporal_deform_desc* d, std::string& err) {
+    if (const int rc = temporal_deform_check(d, false, false, err); rc != RT_OK) return rc;
+    const rt_temporal_motion_desc mhead = temporal_motion_head(d);
+    const rt_temporal_desc head = temporal_head(&mhead);
+    accumulate(&head, d->motions, d->n_objects, d);
     return RT_OK;
 }
 

@@ -70,6 +70,7 @@ hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
 hipError_t launch_temporal_motion(const TemporalMotionArgs& a, hipStream_t stream);
+hipError_t launch_temporal_deform(const TemporalDeformArgs& a, hipStream_t stream);
 hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
@@ -2309,7 +2310,8 @@ int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* r
 }
 
 // ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
-// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving ----
+// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming (DESIGN.md
+// section 2.17) ----
 // Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
 // and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
 // arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
@@ -2429,6 +2431,7 @@ int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc) { return host_call(
 int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) { return host_call(rt2::adaptive_merge_host, desc); }
 int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call(rt2::temporal_host, desc); }
 int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc) { return host_call(rt2::temporal_motion_host, desc); }
+int rt_temporal_accumulate_deforming_host(const rt_temporal_deform_desc* desc) { return host_call(rt2::temporal_deform_host, desc); }
 
 // ---- denoising a rendered frame (include/rt_abi.h: rt_denoise; rt_denoise.hip; host/denoise.cpp) ----
 static const char* const DENOISE_SCRATCH = "the denoiser's scratch images";
@@ -2626,6 +2629,46 @@ int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* d
         a.t.prev_point = (const float*)in[6]; a.t.prev_normal = (const float*)in[7]; a.t.prev_object = (const uint32_t*)in[8];
         a.t.out_history = (float*)out[9]; a.t.motion = (float*)out[10]; a.motions = (const rttp::Motion*)in[11];
         return launch_temporal_motion(a, h->stream);
+    });
+}
+
+// With the triangle side (include/rt_abi.h: rt_temporal_accumulate_deforming): the moving call's planes and table, the
+// current G-buffer's primitive, bary and flags planes, and the previous triangles -- a second input that is not frame-shaped.
+int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
+    std::string err;
+    if (const int rc = rt2::temporal_deform_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)desc->width * desc->height;
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
+    const FramePlane planes[16] = {{color, desc->out, texels * 16u}, {desc->point, nullptr, texels * 12u}, {desc->normal, nullptr, texels * 12u},
+                                   {desc->object, nullptr, texels * 4u}, {desc->prev_color, nullptr, texels * 16u},
+                                   {desc->prev_history, nullptr, texels * 4u}, {desc->prev_point, nullptr, texels * 12u},
+                                   {desc->prev_normal, nullptr, texels * 12u}, {desc->prev_object, nullptr, texels * 4u},
+                                   {nullptr, desc->out_history, texels * 4u}, {nullptr, desc->motion, texels * 8u},
+                                   {desc->motions, nullptr, (size_t)desc->n_objects * sizeof(rt_object_motion)},
+                                   {desc->primitive, nullptr, texels * 4u}, {desc->bary, nullptr, texels * 8u}, {desc->flags, nullptr, texels},
+                                   {desc->prev_triangles, nullptr, (size_t)desc->n_prev_triangles * sizeof(rt_packed_triangle)}};
+    TemporalDeformArgs a{};
+    const rt_temporal_motion_desc mhead = rt2::temporal_motion_head(desc);
+    const rt_temporal_desc head = rt2::temporal_head(&mhead);
+    a.m.t.call = rt2::temporal_call(&head);
+    a.m.n_objects = desc->n_objects;
+    a.tri_first = desc->tri_first;
+    a.n_prev_triangles = desc->n_prev_triangles;
+    return frame_call(h, host, planes, "the staging planes of temporal accumulation", "launch_temporal_deform", [&](const void* const* in, void* const* out) {
+        TemporalArgs& t = a.m.t;
+        t.color = (const float*)in[0]; t.out = (float*)out[0]; t.point = (const float*)in[1]; t.normal = (const float*)in[2];
+        t.object = (const uint32_t*)in[3]; t.prev_color = (const float*)in[4]; t.prev_history = (const float*)in[5];
+        t.prev_point = (const float*)in[6]; t.prev_normal = (const float*)in[7]; t.prev_object = (const uint32_t*)in[8];
+        t.out_history = (float*)out[9]; t.motion = (float*)out[10]; a.m.motions = (const rttp::Motion*)in[11];
+        a.primitive = (const uint32_t*)in[12]; a.bary = (const float*)in[13]; a.flags = (const uint8_t*)in[14];
+        a.prev_triangles = (const rttp::Tri*)in[15];
+        return launch_temporal_deform(a, h->stream);
     });
 }
 

@@ -8,7 +8,8 @@
 //              screen, and which texels and weights does the snapped position take (snap)?
 //   resolve -- given the four taps' previous values: which of them are valid, what do they add, and the blend.
 // With a motion table (rt_temporal_accumulate_moving) a moved object's texel goes through `carry` first, and locate and
-// resolve then work on the carried point and normal.
+// resolve then work on the carried point and normal.  A deformed mesh's texel (rt_temporal_accumulate_deforming) is
+// carried by its previous triangle instead (`carry_deformed`).
 // What an invalid tap adds is +0, chosen by a select after the tap's arithmetic: sum, hsum and wsum start at +0 and are
 // never -0, so adding +0 leaves them as they are, bit for bit, and no branch stands between the taps' loads.
 #ifndef RT_TEMPORAL_H
@@ -179,6 +180,44 @@ RT_TP_HD bool carry(const Motion& m, const float X[3], const float n[3], float X
     }
     const float len = rtm::sqrt_((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     for (int r = 0; r < 3; ++r) np[r] = v[r] / len;
+    return finite3(Xp) && finite3(np);
+}
+
+// ---- deforming meshes (include/rt_abi.h: rt_temporal_accumulate_deforming) ----
+// A record whose `moved` is DEFORMED carries its texels by the previous frame's triangle, not by one map: m.d is the
+// previous model_to_world and m.nt its 3 x 3 (rt_object_motions_deforming).
+constexpr uint32_t DEFORMED = 2u;
+constexpr uint32_t HIT_BACKFACE = 2u;   // RT_HIT_BACKFACE of the G-buffer's flags plane
+
+// rt_packed_triangle's 96 bytes as both units read them: six 16-byte rows, v1|uv .. n3|uv.  The device array is 16-byte
+// aligned (the entry point checks), the host loop copies a record into one of these.
+struct alignas(16) Tri {
+    float v1[3], uv10, v2[3], uv11, v3[3], uv20, n1[3], uv21, n2[3], uv30, n3[3], uv31;
+};
+
+// May the previous triangle of a deformed texel be read?  t: its primitive word, (u, v): its barycentrics.  The array is
+// touched only after this says yes.
+RT_TP_HD bool has_prev_triangle(uint32_t t, uint32_t tri_first, uint32_t n_prev_triangles, float u, float v) {
+    return t >= tri_first && t - tri_first < n_prev_triangles && is_finite(u) && is_finite(v);
+}
+
+// The surface point (u, v) of the previous triangle T -> X', n' of the previous world by a deformed object's record: one
+// interpolation of the vertices and one of the normals in the render kernel's order, one normalisation, the backface
+// sign.  False: some component is not finite (normals that interpolate to zero length included) and the texel has no history.
+RT_TP_HD bool carry_deformed(const Motion& m, const Tri& T, float u, float v, bool backface, float Xp[3], float np[3]) {
+    const float w = (1.0f - u) - v;
+    float xm[3], g[3], q[3];
+    for (int r = 0; r < 3; ++r) {
+        xm[r] = (T.v1[r] * w + T.v2[r] * u) + T.v3[r] * v;
+        g[r] = (T.n1[r] * w + T.n2[r] * u) + T.n3[r] * v;
+    }
+    for (int r = 0; r < 3; ++r) {
+        Xp[r] = ((m.d[0][r] * xm[0] + m.d[1][r] * xm[1]) + m.d[2][r] * xm[2]) + m.d[3][r];
+        q[r] = (m.nt[0][r] * g[0] + m.nt[1][r] * g[1]) + m.nt[2][r] * g[2];
+    }
+    const float len = rtm::sqrt_((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
+    const float s = backface ? -1.0f : 1.0f;
+    for (int r = 0; r < 3; ++r) np[r] = (q[r] / len) * s;
     return finite3(Xp) && finite3(np);
 }
 

@@ -1,5 +1,5 @@
 // rt_temporal.hip -- the device kernels of temporal accumulation (include/rt_abi.h: rt_temporal_accumulate,
-// rt_temporal_accumulate_moving).
+// rt_temporal_accumulate_moving, rt_temporal_accumulate_deforming).
 //
 // One lane per current texel, a workgroup per tile of 32 x 8 texels (a wave: 32 x 2), so that the four taps of
 // neighbouring lanes fall into neighbouring texels of the previous frame and a wave's gather touches a few rows of it.
@@ -14,8 +14,10 @@
 // Bounds: a lane outside the frame leaves before any access; a lane's own index p and every tap index q (both
 // coordinates clamped into the frame) are < width * height <= 2^31 - 1 (the entry point checks), and every address is
 // formed in 64 bits.  The snapped tap origin is in [-1, width] x [-1, height] (on screen: -1 < fx < width), so x0 + 1
-// does not overflow an int32.  The motion table (rt_temporal_motion_kernel) is read at record obj only after obj <
-// n_objects.
+// does not overflow an int32.  The motion table (rt_temporal_motion_kernel, rt_temporal_deform_kernel) is read at record
+// obj only after obj < n_objects.  The previous triangles (rt_temporal_deform_kernel) are read at record t - tri_first only
+// after tri_first <= t and t - tri_first < n_prev_triangles (the range test comes before the triangle load; tri_first +
+// n_prev_triangles <= 2^32, the entry point checks), and the primitive, bary and flags planes at the lane's own p.
 #include <hip/hip_runtime.h>
 
 #include "rt_temporal.h"
@@ -148,6 +150,96 @@ __global__ void __launch_bounds__(TEMPORAL_THREADS) rt_temporal_motion_kernel(co
     store_texel(a, p, r.out, r.history, w.motion[0], w.motion[1]);
 }
 
+// rt_temporal_accumulate_deforming: the motion kernel's texel with a third kind of record.  (A body of its own, for the
+// reason given above: the two kernels before it are to stay what they were.)
+// A lane whose record says DEFORMED reads its primitive word and barycentrics, leaves with "no history" when the word is
+// outside [tri_first, tri_first + n_prev_triangles) or a barycentric is not finite -- the range test comes before the
+// triangle load --, and otherwise issues the six 16-byte loads of its previous triangle record (v1|uv .. n3|uv, 96 bytes,
+// 16-byte aligned; the uv word of each row is not used and the compiler does not fetch it) before any arithmetic on them.  A wave's 64 adjacent texels hold a handful of triangles: a near-uniform
+// gather like the motion table's, served by the cache; plain loads, no LDS staging (nothing is shared between lanes that
+// the cache does not already share, and the kernel is bound by the planes it streams).  The carried point and normal
+// (rttp::carry_deformed) then enter locate, the four taps' loads and resolve unchanged.  The lanes of still or rigid
+// objects do what rt_temporal_motion_kernel does.
+__global__ void __launch_bounds__(TEMPORAL_THREADS) rt_temporal_deform_kernel(const TemporalDeformArgs da) {
+    const TemporalMotionArgs& ma = da.m;
+    const TemporalArgs& a = ma.t;
+    const uint32_t W = a.call.width, H = a.call.height;
+    const uint32_t tiles_x = (W + TILE_W - 1) / TILE_W;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const uint32_t x = tx * TILE_W + (threadIdx.x & (TILE_W - 1)), y = ty * TILE_H + threadIdx.x / TILE_W;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + (size_t)x;
+    const float4 c4 = reinterpret_cast<const float4*>(a.color)[p];
+    const float color[4] = {c4.x, c4.y, c4.z, c4.w};
+    float X[3] = {a.point[3 * p], a.point[3 * p + 1], a.point[3 * p + 2]};
+    float n[3] = {a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2]};
+    const uint32_t obj = a.object[p];
+    const float nan = rttp::u2f(rttp::QUIET_NAN);
+    // (obj < n_objects before the table is touched: nothing is read outside it)
+    if (!rttp::reprojectable(n, X, true, obj) || !rttp::in_table(obj, ma.n_objects)) {
+        store_texel(a, p, color, 1.0f, nan, nan);
+        return;
+    }
+    const rttp::Motion* m = ma.motions + obj;
+    const uint32_t moved = m->moved;
+    if (moved == rttp::DEFORMED) {
+        const uint32_t t = da.primitive[p];
+        const float u = da.bary[2 * p], v = da.bary[2 * p + 1];   // (4-byte aligned: two loads)
+        const bool backface = (da.flags[p] & rttp::HIT_BACKFACE) != 0u;
+        // (t in [tri_first, tri_first + n_prev_triangles) before the array is touched: nothing is read outside it)
+        if (!rttp::has_prev_triangle(t, da.tri_first, da.n_prev_triangles, u, v)) {
+            store_texel(a, p, color, 1.0f, nan, nan);
+            return;
+        }
+        const float4* rows = reinterpret_cast<const float4*>(da.prev_triangles + (size_t)(t - da.tri_first));
+        const float4 r0 = rows[0], r1 = rows[1], r2 = rows[2], r3 = rows[3], r4 = rows[4], r5 = rows[5];
+        const rttp::Tri tri{{r0.x, r0.y, r0.z}, r0.w, {r1.x, r1.y, r1.z}, r1.w, {r2.x, r2.y, r2.z}, r2.w,
+                            {r3.x, r3.y, r3.z}, r3.w, {r4.x, r4.y, r4.z}, r4.w, {r5.x, r5.y, r5.z}, r5.w};
+        float cx[3], cn[3];
+        if (!rttp::carry_deformed(*m, tri, u, v, backface, cx, cn)) {
+            store_texel(a, p, color, 1.0f, nan, nan);
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[k] = cx[k], n[k] = cn[k];
+    } else if (moved != 0u) {
+        float cx[3], cn[3];
+        if (!rttp::carry(*m, X, n, cx, cn)) {
+            store_texel(a, p, color, 1.0f, nan, nan);
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[k] = cx[k], n[k] = cn[k];
+    }
+    const rttp::Where w = rttp::locate(a.call, X, x, y);
+    if (!w.on_screen) {
+        store_texel(a, p, color, 1.0f, nan, nan);
+        return;
+    }
+    const bool match_object = a.prev_object != nullptr;
+    rttp::Tap taps[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int32_t qx = w.ax.i0 + rttp::tap_dx(i), qy = w.ay.i0 + rttp::tap_dy(i);
+        rttp::Tap& t = taps[i];
+        t.inside = (uint32_t)qx < W && (uint32_t)qy < H;
+        const uint32_t cx = qx < 0 ? 0u : (uint32_t)qx >= W ? W - 1u : (uint32_t)qx;
+        const uint32_t cy = qy < 0 ? 0u : (uint32_t)qy >= H ? H - 1u : (uint32_t)qy;
+        const size_t q = (size_t)cy * W + (size_t)cx;
+        const float4 pc = reinterpret_cast<const float4*>(a.prev_color)[q];
+        t.c[0] = pc.x; t.c[1] = pc.y; t.c[2] = pc.z; t.c[3] = pc.w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            t.n[k] = a.prev_normal[3 * q + k];
+            t.x[k] = a.prev_point[3 * q + k];
+        }
+        t.h = a.prev_history[q];
+        t.obj = match_object ? a.prev_object[q] : 0u;
+    }
+    const rttp::Result r = rttp::resolve(a.call, w, X, n, match_object, obj, color, taps);
+    store_texel(a, p, r.out, r.history, w.motion[0], w.motion[1]);
+}
+
 }  // namespace
 
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream) {
@@ -159,6 +251,12 @@ hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream) {
 hipError_t launch_temporal_motion(const TemporalMotionArgs& a, hipStream_t stream) {
     const uint32_t tiles = ((a.t.call.width + TILE_W - 1) / TILE_W) * ((a.t.call.height + TILE_H - 1) / TILE_H);
     hipLaunchKernelGGL(rt_temporal_motion_kernel, dim3(tiles), dim3(TEMPORAL_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_deform(const TemporalDeformArgs& a, hipStream_t stream) {
+    const uint32_t tiles = ((a.m.t.call.width + TILE_W - 1) / TILE_W) * ((a.m.t.call.height + TILE_H - 1) / TILE_H);
+    hipLaunchKernelGGL(rt_temporal_deform_kernel, dim3(tiles), dim3(TEMPORAL_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

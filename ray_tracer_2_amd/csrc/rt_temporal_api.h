@@ -1,5 +1,5 @@
 // rt_temporal_api.h -- what the units of temporal accumulation declare to each other (include/rt_abi.h:
-// rt_temporal_accumulate, rt_temporal_accumulate_host and their _moving forms): the argument rules, the once-per-call
+// rt_temporal_accumulate, rt_temporal_accumulate_host and their _moving and _deforming forms): the argument rules, the once-per-call
 // numbers and the host restatement (host/temporal.cpp), and the arguments of the device launch (rt_temporal.hip), all called by the entry points
 // in rt_api.hip.  The arithmetic they share is csrc/rt_temporal.h.
 #ifndef RT_TEMPORAL_API_H
@@ -32,6 +32,21 @@ rt_temporal_desc temporal_head(const rt_temporal_motion_desc* d);
 // temporal_check on the head, then the table's own rules (on device memory the table is 16-byte aligned).
 int temporal_motion_check(const rt_temporal_motion_desc* d, bool device, bool host_memory, std::string& err);
 int temporal_motion_host(const rt_temporal_motion_desc* d, std::string& err);
+
+// The _deforming forms.  rt_temporal_deform_desc is rt_temporal_motion_desc with the triangle side behind it: its head, as
+// an rt_temporal_motion_desc of its own (struct_bytes set), is what temporal_motion_check is given.
+static_assert(offsetof(rt_temporal_deform_desc, primitive) == sizeof(rt_temporal_motion_desc) &&
+                  sizeof(rt_temporal_deform_desc) == sizeof(rt_temporal_motion_desc) + 40,
+              "rt_temporal_deform_desc is rt_temporal_motion_desc and the triangle side");
+static_assert(sizeof(rt_packed_triangle) == 96 && sizeof(rttp::Tri) == 96 && offsetof(rt_packed_triangle, v2) == offsetof(rttp::Tri, v2) &&
+                  offsetof(rt_packed_triangle, n1) == offsetof(rttp::Tri, n1) && offsetof(rt_packed_triangle, n3) == offsetof(rttp::Tri, n3),
+              "rttp::Tri is rt_packed_triangle");
+static_assert(rttp::HIT_BACKFACE == RT_HIT_BACKFACE, "the flags plane's backface bit");
+rt_temporal_motion_desc temporal_motion_head(const rt_temporal_deform_desc* d);
+// temporal_motion_check on the head, then the triangle side's own rules (on device memory: primitive and bary 4-byte
+// aligned, prev_triangles 16).
+int temporal_deform_check(const rt_temporal_deform_desc* d, bool device, bool host_memory, std::string& err);
+int temporal_deform_host(const rt_temporal_deform_desc* d, std::string& err);
 }  // namespace rt2
 
 namespace rtd {
@@ -55,6 +70,16 @@ struct TemporalMotionArgs {
     TemporalArgs t;
     const rttp::Motion* motions;   // [n_objects]
     uint32_t n_objects;
+};
+// rt_temporal_accumulate_deforming: those, the current G-buffer's triangle planes and the previous triangles [tri_first,
+// tri_first + n_prev_triangles) of the uploaded array, 16-byte aligned
+struct TemporalDeformArgs {
+    TemporalMotionArgs m;
+    const uint32_t* primitive;         // [h][w]
+    const float* bary;                 // [h][w][2]
+    const uint8_t* flags;              // [h][w]
+    const rttp::Tri* prev_triangles;   // [n_prev_triangles]
+    uint32_t tri_first, n_prev_triangles;
 };
 }  // namespace rtd
 

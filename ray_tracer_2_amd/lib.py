@@ -31,6 +31,7 @@ EXPORTS = [
     "rt_intersect_rays", "rt_occluded_rays", "rt_pick", "rt_render_gbuffer", "rt_radiance_rays",
     "rt_denoise", "rt_denoise_host", "rt_temporal_accumulate", "rt_temporal_accumulate_host",
     "rt_temporal_accumulate_moving", "rt_temporal_accumulate_moving_host", "rt_object_motions",
+    "rt_temporal_accumulate_deforming", "rt_temporal_accumulate_deforming_host", "rt_object_motions_deforming",
     "rt_denoise_variance", "rt_luminance_moments", "rt_denoise_variance_host", "rt_luminance_moments_host",
     "rt_adaptive_plan", "rt_adaptive_merge", "rt_adaptive_plan_host", "rt_adaptive_merge_host",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
@@ -155,6 +156,9 @@ def _bind(L, with_test_entries):
         "rt_temporal_accumulate_moving": (i32, [vp, P(A.TemporalMotionDesc), i32]),
         "rt_temporal_accumulate_moving_host": (i32, [P(A.TemporalMotionDesc)]),
         "rt_object_motions": (i32, [vp, vp, u32, vp, vp, u32, vp]),
+        "rt_temporal_accumulate_deforming": (i32, [vp, P(A.TemporalDeformDesc), i32]),
+        "rt_temporal_accumulate_deforming_host": (i32, [P(A.TemporalDeformDesc)]),
+        "rt_object_motions_deforming": (i32, [vp, vp, u32, vp, vp, u32, vp, vp]),
         "rt_denoise_variance": (i32, [vp, P(A.VDenoiseDesc), i32]),
         "rt_luminance_moments": (i32, [vp, P(A.VDenoiseDesc), i32]),
         "rt_denoise_variance_host": (i32, [P(A.VDenoiseDesc)]),

@@ -64,7 +64,7 @@ def _numpy_outputs(d, table, W, H, outs):
 
 def _tensor_planes(d, device, table, W, H, planes, outs):
     """The same for torch tensors on cuda:`device`: checks the inputs and the outputs that are given (device, dtype -- a
-    uint32 plane is an int32 tensor holding the bits, or uint32 --, layout, shape), makes the outputs asked for with True,
+    uint32 plane is an int32 tensor holding the bits, or uint32; a byte plane uint8 --, layout, shape), makes the outputs asked for with True,
     points the desc at all of them and returns the outputs by name (None: not asked for)."""
     import torch
     dev = torch.device("cuda", device)
@@ -74,7 +74,8 @@ def _tensor_planes(d, device, table, W, H, planes, outs):
             raise ValueError("mix of device tensors and host arrays")
         if v.device.type != "cuda" or v.device.index != device:
             raise ValueError(f"plane {k} must be on cuda:{device}, not {v.device}")
-        kinds = (torch.float32,) if table[k][0] == "<f4" else (torch.int32, getattr(torch, "uint32", torch.int32))
+        kinds = ((torch.float32,) if table[k][0] == "<f4" else (torch.uint8,) if table[k][0] == "u1" else
+                 (torch.int32, getattr(torch, "uint32", torch.int32)))
         if v.dtype not in kinds or not v.is_contiguous() or tuple(v.shape) != _plane_shape(table, k, W, H):
             name = str(kinds[0]).replace("torch.", "")
             raise ValueError(f"plane {k} must be a contiguous {name} tensor of shape {_plane_shape(table, k, W, H)}")
@@ -178,12 +179,15 @@ def _temporal_result(res):
 
 
 def _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history, point_tolerance, normal_cos,
-                   motions):
+                   motions, prev_triangles=None, tri_first=0):
     """The entry point's name stem, its desc, its plane table, the inputs by name and the frame's size: rt_temporal_accumulate
     without a motion table, rt_temporal_accumulate_moving with one (`motions`: (n,) OBJECT_MOTION_DTYPE, or an (n, 24) int32
-    tensor of the records' words)."""
+    tensor of the records' words), rt_temporal_accumulate_deforming with the previous triangles too (`prev_triangles`: n
+    TRI_DTYPE records, or an (n, 24) float32 tensor; `guides` then holds primitive, bary and flags)."""
     planes, W, H = _temporal_inputs(guides, prev_guides, prev_color, prev_history, color)
     d = _temporal_desc(W, H, prev_camera, max_history, point_tolerance, normal_cos)
+    if prev_triangles is not None and motions is None:
+        raise ValueError("prev_triangles needs the motion table that marks the deformed meshes (object_motions(..., deformed=))")
     if motions is None:
         return "rt_temporal_accumulate", d, A.TEMPORAL_PLANES, planes, W, H
     if "object" not in planes:
@@ -200,29 +204,56 @@ def _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, c
     md = A.TemporalMotionDesc.from_buffer_copy(bytes(d) + bytes(C.sizeof(A.TemporalMotionDesc) - C.sizeof(A.TemporalDesc)))
     md.struct_bytes, md.n_objects = C.sizeof(A.TemporalMotionDesc), entry[1][0]
     planes["motions"] = motions
-    return "rt_temporal_accumulate_moving", md, dict(A.TEMPORAL_MOTION_PLANES, motions=entry), planes, W, H
+    if prev_triangles is None:
+        return "rt_temporal_accumulate_moving", md, dict(A.TEMPORAL_MOTION_PLANES, motions=entry), planes, W, H
+    for k in ("primitive", "bary", "flags"):
+        if k not in guides:
+            raise ValueError(f"guides must hold the {k} plane of render_gbuffer: a deformed texel's previous triangle is named by it")
+        planes[k] = guides[k]
+    if hasattr(prev_triangles, "data_ptr"):
+        if prev_triangles.dim() != 2 or prev_triangles.shape[1] != 24 or prev_triangles.shape[0] < 1:
+            raise ValueError("previous triangles on the device are an (n, 24) float32 tensor, as refit_triangles takes them")
+        tri_entry = ("<f4", (int(prev_triangles.shape[0]), 24))
+    else:
+        prev_triangles = np.ascontiguousarray(prev_triangles)
+        if prev_triangles.dtype != A.TRI_DTYPE or prev_triangles.ndim != 1 or prev_triangles.shape[0] < 1:
+            raise ValueError("previous triangles are a one-dimensional TRI_DTYPE array with a record or more")
+        tri_entry = (A.TRI_DTYPE, (int(prev_triangles.shape[0]),))
+    tri_first = int(tri_first)
+    if tri_first < 0 or tri_first + tri_entry[1][0] > 1 << 32:
+        raise ValueError("tri_first must be >= 0 and tri_first + the number of previous triangles at most 2^32")
+    dd = A.TemporalDeformDesc.from_buffer_copy(bytes(md) + bytes(C.sizeof(A.TemporalDeformDesc) - C.sizeof(A.TemporalMotionDesc)))
+    dd.struct_bytes, dd.tri_first, dd.n_prev_triangles = C.sizeof(A.TemporalDeformDesc), tri_first, tri_entry[1][0]
+    planes["prev_triangles"] = prev_triangles
+    return ("rt_temporal_accumulate_deforming", dd, dict(A.TEMPORAL_DEFORM_PLANES, motions=entry, prev_triangles=tri_entry), planes,
+            W, H)
 
 
 def temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history=float("inf"),
                              point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
-                             motion=False, motions=None):
-    """rt_temporal_accumulate_host (with `motions`, a table of object_motions: rt_temporal_accumulate_moving_host): temporal
-    accumulation's definition on the CPU (no device), with RayTracer.temporal_accumulate's arguments for numpy planes.
-    RayTracer.temporal_accumulate computes the same bits on the GPU."""
+                             motion=False, motions=None, prev_triangles=None, tri_first=0):
+    """rt_temporal_accumulate_host (with `motions`, a table of object_motions: rt_temporal_accumulate_moving_host; with
+    `prev_triangles` / `tri_first` too: rt_temporal_accumulate_deforming_host): temporal accumulation's definition on the CPU
+    (no device), with RayTracer.temporal_accumulate's arguments for numpy planes.  RayTracer.temporal_accumulate computes the
+    same bits on the GPU."""
     fn, d, table, planes, W, H = _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history,
-                                                point_tolerance, normal_cos, motions)
+                                                point_tolerance, normal_cos, motions, prev_triangles, tri_first)
     if color is None:
         raise ValueError("color is required on the host")
     outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
     return _temporal_result(_host_frame_call(fn + "_host", d, table, W, H, planes, outs))
 
 
-def object_motions(prev_arrays, arrays):
+def object_motions(prev_arrays, arrays, deformed=None):
     """rt_object_motions: the motion table that temporal_accumulate(..., motions=) takes, from two SceneArrays of one scene --
     before and after its meshes' transforms and its spheres were edited (the same topology: ValueError when the mesh or
     sphere counts differ).  Returns an (n_meshes + n_spheres,) OBJECT_MOTION_DTYPE array, indexed by the G-buffer's object
     word: per object whether it moved, and the map that carries its points and normals from the current frame's world to
-    the previous frame's."""
+    the previous frame's.
+    `deformed` (rt_object_motions_deforming): the meshes whose vertices moved between the two states (refit_triangles) -- a
+    sequence of mesh indices, or a boolean array with an entry per mesh.  Their records say DEFORMED (moved == 2) and hold
+    the previous model_to_world; temporal_accumulate(..., motions=, prev_triangles=) carries their texels by the previous
+    frame's triangles."""
     def records(x, dtype):
         a = np.ascontiguousarray(x)
         if a.nbytes % dtype.itemsize:
@@ -234,8 +265,24 @@ def object_motions(prev_arrays, arrays):
         raise ValueError(f"the two scene states differ in topology: {npm} and {nm} meshes, {nps} and {ns} spheres")
     out = np.zeros(nm + ns, A.OBJECT_MOTION_DTYPE)
     L = load()
-    rc = L.rt_object_motions(pm.ctypes.data if nm else None, m.ctypes.data if nm else None, nm,
-                             ps.ctypes.data if ns else None, s.ctypes.data if ns else None, ns, out.ctypes.data if nm + ns else None)
+    args = (pm.ctypes.data if nm else None, m.ctypes.data if nm else None, nm, ps.ctypes.data if ns else None,
+            s.ctypes.data if ns else None, ns)
+    if deformed is None:
+        rc = L.rt_object_motions(*args, out.ctypes.data if nm + ns else None)
+    else:
+        marks = np.asarray(deformed)
+        if marks.dtype == np.bool_:
+            if marks.shape != (nm,):
+                raise ValueError(f"a boolean `deformed` has an entry per mesh: shape ({nm},), not {marks.shape}")
+            marks = marks.astype(np.uint8)
+        else:
+            which = marks.astype(np.int64).reshape(-1)
+            if which.size and (which.min() < 0 or which.max() >= nm):
+                raise ValueError(f"`deformed` names a mesh outside [0, {nm})")
+            marks = np.zeros(nm, np.uint8)
+            marks[which] = 1
+        marks = np.ascontiguousarray(np.append(marks, np.uint8(0)))   # (never empty: the pointer is not NULL)
+        rc = L.rt_object_motions_deforming(*args, marks.ctypes.data, out.ctypes.data if nm + ns else None)
     if rc < 0:
         raise RtError(rc, "rt_object_motions refused its arguments")
     return out
@@ -855,7 +902,7 @@ class RayTracer:
 
     def temporal_accumulate(self, guides, prev_guides, prev_camera, prev_color, prev_history, color=None, max_history=float("inf"),
                             point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
-                            motion=False, motions=None):
+                            motion=False, motions=None, prev_triangles=None, tri_first=0):
         """Temporal accumulation across a camera move (rt_temporal_accumulate; include/rt_abi.h has the definition): every
         texel of the current frame `color` (H, W, 4) fetches the history `prev_color` (H, W, 4) / `prev_history` (H, W;
         frames accumulated, as float32 >= 1) from where its hit point lay under `prev_camera` (a CameraUniform), through
@@ -874,12 +921,18 @@ class RayTracer:
         that changed around it: `max_history` bounds how long that lags.  A second call with the luminance moments as
         color / prev_color and the same `motions` accumulates the moments denoise_variance takes for a moving object, as it
         does for a moving camera.
+        `prev_triangles`, `tri_first` (rt_temporal_accumulate_deforming): for a mesh whose vertices moved between the two
+        frames (refit_triangles) -- `motions` is then object_motions(prev_arrays, arrays, deformed=...), `guides` must also
+        hold `primitive`, `bary` and `flags`, and `prev_triangles` are the uploaded triangles [tri_first, tri_first + n) as
+        they were in the previous frame: n TRI_DTYPE records, or an (n, 24) float32 tensor on the device, the forms
+        refit_triangles takes.  A deformed mesh's texels fetch the history of their own surface point on the previous
+        triangle; a texel whose triangle lies outside the range restarts, as does a mesh whose topology changed.
         numpy planes: a synchronous call that returns numpy arrays.  Torch tensors on this handle's device: an asynchronous
         call ordered after the current torch stream's work, as render_gbuffer(device=True) orders itself; returns tensors;
         there color=None takes the handle's image as the current frame, and `motions` is an (n_objects, 24) int32 tensor of
         the records' words (torch.from_numpy(table.view(np.int32).reshape(-1, 24)) moved to the device)."""
         fn, d, table, planes, W, H = _temporal_call(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history,
-                                                    point_tolerance, normal_cos, motions)
+                                                    point_tolerance, normal_cos, motions, prev_triangles, tri_first)
         outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
         return _temporal_result(self._frame_call(fn, A.TEMPORAL_HOST_MEMORY, d, table, W, H, planes, outs))
 

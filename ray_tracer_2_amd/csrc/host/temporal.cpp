@@ -16,13 +16,29 @@
 
 namespace rt2 {
 
-int temporal_check(const rt_temporal_desc* d, bool device, bool host_memory, std::string& err) {
+int temporal_check(const void* desc, TemporalKind kind, bool device, bool host_memory, rt_temporal_deform_desc& wide, std::string& err) {
     auto bad = [&](int code, const char* msg) {
         err = msg;
         return code;
     };
-    if (!d) return bad(RT_ERR_INVALID_ARGUMENT, "null rt_temporal_desc");
-    if (d->struct_bytes != sizeof(rt_temporal_desc)) return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_desc.struct_bytes is not sizeof(rt_temporal_desc)");
+    static const struct {
+        uint32_t bytes;
+        const char *null_desc, *bad_bytes;
+    } KINDS[3] = {
+        {sizeof(rt_temporal_desc), "null rt_temporal_desc", "rt_temporal_desc.struct_bytes is not sizeof(rt_temporal_desc)"},
+        {sizeof(rt_temporal_motion_desc), "null rt_temporal_motion_desc", "rt_temporal_motion_desc.struct_bytes is not sizeof(rt_temporal_motion_desc)"},
+        {sizeof(rt_temporal_deform_desc), "null rt_temporal_deform_desc", "rt_temporal_deform_desc.struct_bytes is not sizeof(rt_temporal_deform_desc)"}};
+    const auto& k = KINDS[(int)kind];
+    if (!desc) return bad(RT_ERR_INVALID_ARGUMENT, k.null_desc);
+    uint32_t struct_bytes;   // (the first word of all three)
+    std::memcpy(&struct_bytes, desc, sizeof(struct_bytes));
+    if (struct_bytes != k.bytes) return bad(RT_ERR_INVALID_ARGUMENT, k.bad_bytes);
+    // the kind's desc is a prefix of the widest (rt_temporal_api.h: the static_asserts); what lies behind it stays null or zero
+    wide = rt_temporal_deform_desc{};
+    std::memcpy(&wide, desc, struct_bytes);
+    const rt_temporal_deform_desc* d = &wide;
+    const bool device_planes = device && !host_memory;
+
     if (d->_p0 != 0u) return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_desc._p0 must be 0");
     if (d->width == 0u || d->height == 0u) return bad(RT_ERR_INVALID_ARGUMENT, "zero width or height");
     if (!(d->max_history >= 1.0f)) return bad(RT_ERR_INVALID_ARGUMENT, "max_history is NaN or below 1");
@@ -33,95 +49,62 @@ int temporal_check(const rt_temporal_desc* d, bool device, bool host_memory, std
         return bad(RT_ERR_INVALID_ARGUMENT, "null point, normal, prev_color, prev_history, prev_point, prev_normal, out or out_history plane");
     if (!d->color && (!device || host_memory)) return bad(RT_ERR_INVALID_ARGUMENT, "null color plane (only device planes may name the handle's image that way)");
     if ((uint64_t)d->width * d->height > 0x7fffffffull) return bad(RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
-    if (device && !host_memory) {
+    if (device_planes) {
         const PlaneAlign planes[12] = {
             {d->color, 15u, "color"}, {d->point, 3u, "point"}, {d->normal, 3u, "normal"}, {d->object, 3u, "object"},
             {d->prev_color, 15u, "prev_color"}, {d->prev_history, 3u, "prev_history"}, {d->prev_point, 3u, "prev_point"},
             {d->prev_normal, 3u, "prev_normal"}, {d->prev_object, 3u, "prev_object"}, {d->out, 15u, "out"},
             {d->out_history, 3u, "out_history"}, {d->motion, 7u, "motion"}};
-        return misaligned(planes, 12, err);
+        if (const int rc = misaligned(planes, 12, err); rc != RT_OK) return rc;
     }
-    return RT_OK;
-}
+    if (kind == TemporalKind::PLAIN) return RT_OK;
 
-rttp::Call temporal_call(const rt_temporal_desc* d) {
-    Mat4 m;
-    std::memcpy(&m, d->prev_camera.cam_to_world, sizeof(m));
-    const Mat4 v = mat4_inverse(m);
-    rttp::Call c{};
-    for (int col = 0; col < 4; ++col)
-        for (int k = 0; k < 3; ++k) c.v[col][k] = v.c[col][k];
-    c.pw = d->prev_camera.view_params[0];
-    c.ph = d->prev_camera.view_params[1];
-    c.fd = d->prev_camera.view_params[2];
-    c.max_history = d->max_history;
-    c.point_tolerance = d->point_tolerance;
-    c.normal_cos = d->normal_cos;
-    c.width = d->width;
-    c.height = d->height;
-    return c;
-}
-
-rt_temporal_desc temporal_head(const rt_temporal_motion_desc* d) {
-    rt_temporal_desc head;
-    std::memcpy(&head, d, sizeof(head));
-    head.struct_bytes = sizeof(head);
-    return head;
-}
-
-int temporal_motion_check(const rt_temporal_motion_desc* d, bool device, bool host_memory, std::string& err) {
-    auto bad = [&](int code, const char* msg) {
-        err = msg;
-        return code;
-    };
-    if (!d) return bad(RT_ERR_INVALID_ARGUMENT, "null rt_temporal_motion_desc");
-    if (d->struct_bytes != sizeof(rt_temporal_motion_desc))
-        return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_motion_desc.struct_bytes is not sizeof(rt_temporal_motion_desc)");
-    const rt_temporal_desc head = temporal_head(d);
-    if (const int rc = temporal_check(&head, device, host_memory, err); rc != RT_OK) return rc;
     if (d->_p1 != 0u) return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_motion_desc._p1 must be 0");
     if (!d->motions) return bad(RT_ERR_INVALID_ARGUMENT, "null motions table");
     if (d->n_objects == 0u) return bad(RT_ERR_INVALID_ARGUMENT, "n_objects is zero");
     if (!d->object) return bad(RT_ERR_INVALID_ARGUMENT, "null object plane (a motion table is indexed by it)");
-    if (device && !host_memory) {
+    if (device_planes) {
         const PlaneAlign table[1] = {{d->motions, 15u, "motions"}};
-        return misaligned(table, 1, err);
+        if (const int rc = misaligned(table, 1, err); rc != RT_OK) return rc;
     }
-    return RT_OK;
-}
+    if (kind == TemporalKind::MOVING) return RT_OK;
 
-rt_temporal_motion_desc temporal_motion_head(const rt_temporal_deform_desc* d) {
-    rt_temporal_motion_desc head;
-    std::memcpy(&head, d, sizeof(head));
-    head.struct_bytes = sizeof(head);
-    return head;
-}
-
-int temporal_deform_check(const rt_temporal_deform_desc* d, bool device, bool host_memory, std::string& err) {
-    auto bad = [&](int code, const char* msg) {
-        err = msg;
-        return code;
-    };
-    if (!d) return bad(RT_ERR_INVALID_ARGUMENT, "null rt_temporal_deform_desc");
-    if (d->struct_bytes != sizeof(rt_temporal_deform_desc))
-        return bad(RT_ERR_INVALID_ARGUMENT, "rt_temporal_deform_desc.struct_bytes is not sizeof(rt_temporal_deform_desc)");
-    const rt_temporal_motion_desc head = temporal_motion_head(d);
-    if (const int rc = temporal_motion_check(&head, device, host_memory, err); rc != RT_OK) return rc;
     if (!d->primitive || !d->bary || !d->flags) return bad(RT_ERR_INVALID_ARGUMENT, "null primitive, bary or flags plane (a deformed texel's triangle is named by them)");
     if (!d->prev_triangles) return bad(RT_ERR_INVALID_ARGUMENT, "null prev_triangles");
     if (d->n_prev_triangles == 0u) return bad(RT_ERR_INVALID_ARGUMENT, "n_prev_triangles is zero");
     if ((uint64_t)d->tri_first + d->n_prev_triangles > 0x100000000ull) return bad(RT_ERR_INVALID_ARGUMENT, "tri_first + n_prev_triangles is past 2^32");
-    if (device && !host_memory) {
+    if (device_planes) {
         const PlaneAlign side[4] = {{d->primitive, 3u, "primitive"}, {d->bary, 3u, "bary"}, {d->flags, 0u, "flags"}, {d->prev_triangles, 15u, "prev_triangles"}};
         return misaligned(side, 4, err);
     }
     return RT_OK;
 }
 
-// The loop of the three host entry points: motions == nullptr is rt_temporal_accumulate_host; deform == nullptr with a
-// table is rt_temporal_accumulate_moving_host, where every non-zero `moved` is carried rigidly.
-static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motions, uint32_t n_objects, const rt_temporal_deform_desc* deform = nullptr) {
-    const rttp::Call c = temporal_call(d);
+rttp::Call temporal_call(const rt_temporal_deform_desc& d) {
+    Mat4 m;
+    std::memcpy(&m, d.prev_camera.cam_to_world, sizeof(m));
+    const Mat4 v = mat4_inverse(m);
+    rttp::Call c{};
+    for (int col = 0; col < 4; ++col)
+        for (int k = 0; k < 3; ++k) c.v[col][k] = v.c[col][k];
+    c.pw = d.prev_camera.view_params[0];
+    c.ph = d.prev_camera.view_params[1];
+    c.fd = d.prev_camera.view_params[2];
+    c.max_history = d.max_history;
+    c.point_tolerance = d.point_tolerance;
+    c.normal_cos = d.normal_cos;
+    c.width = d.width;
+    c.height = d.height;
+    return c;
+}
+
+// The three host entry points: the check, then their one loop.  Without a table (PLAIN) no texel is carried; with one and
+// no triangle side (MOVING) every non-zero `moved` is carried rigidly.
+static int accumulate(const void* desc, TemporalKind kind, std::string& err) {
+    rt_temporal_deform_desc wide;
+    if (const int rc = temporal_check(desc, kind, false, false, wide, err); rc != RT_OK) return rc;
+    const rt_temporal_deform_desc* d = &wide;
+    const rttp::Call c = temporal_call(wide);
     const int64_t W = d->width, H = d->height;
     const bool match_object = d->object && d->prev_object;
     const float nan = rttp::u2f(rttp::QUIET_NAN);
@@ -139,21 +122,21 @@ static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motion
             float motion[2] = {nan, nan};
             bool go = rttp::reprojectable(n, X, d->object != nullptr, obj);
             float carried_x[3], carried_n[3];
-            if (go && motions) {
+            if (go && kind != TemporalKind::PLAIN) {
                 // a word outside the table has no history; a still object's texel goes on as it is; a moved one's is carried
                 // (three ways with the triangle side: still, deformed -- carried by its previous triangle --, rigid)
-                go = rttp::in_table(obj, n_objects);
-                if (go && motions[obj].moved != 0u) {
+                go = rttp::in_table(obj, d->n_objects);
+                if (go && d->motions[obj].moved != 0u) {
                     rttp::Motion m;
-                    std::memcpy(&m, motions + obj, sizeof(m));
-                    if (deform && m.moved == rttp::DEFORMED) {
-                        const uint32_t t = deform->primitive[p];
-                        const float u = deform->bary[2 * p], v = deform->bary[2 * p + 1];
-                        go = rttp::has_prev_triangle(t, deform->tri_first, deform->n_prev_triangles, u, v);
+                    std::memcpy(&m, d->motions + obj, sizeof(m));
+                    if (kind == TemporalKind::DEFORMING && m.moved == rttp::DEFORMED) {
+                        const uint32_t t = d->primitive[p];
+                        const float u = d->bary[2 * p], v = d->bary[2 * p + 1];
+                        go = rttp::has_prev_triangle(t, d->tri_first, d->n_prev_triangles, u, v);
                         if (go) {
                             rttp::Tri tri;
-                            std::memcpy(&tri, deform->prev_triangles + (t - deform->tri_first), sizeof(tri));
-                            go = rttp::carry_deformed(m, tri, u, v, (deform->flags[p] & rttp::HIT_BACKFACE) != 0u, carried_x, carried_n);
+                            std::memcpy(&tri, d->prev_triangles + (t - d->tri_first), sizeof(tri));
+                            go = rttp::carry_deformed(m, tri, u, v, (d->flags[p] & rttp::HIT_BACKFACE) != 0u, carried_x, carried_n);
                         }
                     } else {
                         go = rttp::carry(m, X, n, carried_x, carried_n);
@@ -190,27 +173,11 @@ static void accumulate(const rt_temporal_desc* d, const rt_object_motion* motion
             d->out_history[p] = r.history;
             if (d->motion) std::memcpy(d->motion + 2 * p, motion, sizeof(motion));
         }
-}
-
-int temporal_host(const rt_temporal_desc* d, std::string& err) {
-    if (const int rc = temporal_check(d, false, false, err); rc != RT_OK) return rc;
-    accumulate(d, nullptr, 0u);
     return RT_OK;
 }
 
-int temporal_motion_host(const rt_temporal_motion_desc* d, std::string& err) {
-    if (const int rc = temporal_motion_check(d, false, false, err); rc != RT_OK) return rc;
-    const rt_temporal_desc head = temporal_head(d);
-    accumulate(&head, d->motions, d->n_objects);
-    return RT_OK;
-}
-
-int temporal_deform_host(const rt_temporal_deform_desc* d, std::string& err) {
-    if (const int rc = temporal_deform_check(d, false, false, err); rc != RT_OK) return rc;
-    const rt_temporal_motion_desc mhead = temporal_motion_head(d);
-    const rt_temporal_desc head = temporal_head(&mhead);
-    accumulate(&head, d->motions, d->n_objects, d);
-    return RT_OK;
-}
+int temporal_host(const rt_temporal_desc* d, std::string& err) { return accumulate(d, TemporalKind::PLAIN, err); }
+int temporal_motion_host(const rt_temporal_motion_desc* d, std::string& err) { return accumulate(d, TemporalKind::MOVING, err); }
+int temporal_deform_host(const rt_temporal_deform_desc* d, std::string& err) { return accumulate(d, TemporalKind::DEFORMING, err); }
 
 }  // namespace rt2

@@ -68,9 +68,7 @@ hipError_t launch_test_shade(const RenderArgs& a, int which, const uint32_t* cas
 hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
-hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
-hipError_t launch_temporal_motion(const TemporalMotionArgs& a, hipStream_t stream);
-hipError_t launch_temporal_deform(const TemporalDeformArgs& a, hipStream_t stream);
+hipError_t launch_temporal(const TemporalArgs& a, rt2::TemporalKind kind, hipStream_t stream);
 hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
@@ -2571,106 +2569,51 @@ int rt_adaptive_merge(rt_handle* h, const rt_adaptive_merge_desc* desc, int flag
 }
 
 // ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate; rt_temporal.hip; host/temporal.cpp) ----
-// No scratch is kept.
-int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) {
+// No scratch is kept.  The three calls are one: `desc` is the kind's desc, which the check widens (rt_temporal_api.h), and
+// the rows of a part the kind does not have -- the motion table (rt_temporal_accumulate_moving: one more input that is not
+// frame-shaped), the current G-buffer's primitive, bary and flags planes and the previous triangles
+// (rt_temporal_accumulate_deforming: a second one) -- are absent from the table and take no room.
+static int temporal_accumulate(rt_handle* h, const void* desc, rt2::TemporalKind kind, int flags) {
     if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
     if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
     const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
     std::string err;
-    if (const int rc = rt2::temporal_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
+    rt_temporal_deform_desc d;
+    if (const int rc = rt2::temporal_check(desc, kind, true, host, d, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)d.width * d.height;
+    const float* color = d.color;
     if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
+    if (int rc = host ? RT_OK : image_access(h, color, d.out); rc != RT_OK) return rc;
     // `out` takes the colour plane's place
-    const FramePlane planes[11] = {{color, desc->out, texels * 16u}, {desc->point, nullptr, texels * 12u}, {desc->normal, nullptr, texels * 12u},
-                                   {desc->object, nullptr, texels * 4u}, {desc->prev_color, nullptr, texels * 16u},
-                                   {desc->prev_history, nullptr, texels * 4u}, {desc->prev_point, nullptr, texels * 12u},
-                                   {desc->prev_normal, nullptr, texels * 12u}, {desc->prev_object, nullptr, texels * 4u},
-                                   {nullptr, desc->out_history, texels * 4u}, {nullptr, desc->motion, texels * 8u}};
+    const FramePlane planes[16] = {{color, d.out, texels * 16u}, {d.point, nullptr, texels * 12u}, {d.normal, nullptr, texels * 12u},
+                                   {d.object, nullptr, texels * 4u}, {d.prev_color, nullptr, texels * 16u},
+                                   {d.prev_history, nullptr, texels * 4u}, {d.prev_point, nullptr, texels * 12u},
+                                   {d.prev_normal, nullptr, texels * 12u}, {d.prev_object, nullptr, texels * 4u},
+                                   {nullptr, d.out_history, texels * 4u}, {nullptr, d.motion, texels * 8u},
+                                   {d.motions, nullptr, (size_t)d.n_objects * sizeof(rt_object_motion)},
+                                   {d.primitive, nullptr, texels * 4u}, {d.bary, nullptr, texels * 8u}, {d.flags, nullptr, texels},
+                                   {d.prev_triangles, nullptr, (size_t)d.n_prev_triangles * sizeof(rt_packed_triangle)}};
+    static const char* const LAUNCH[3] = {"launch_temporal", "launch_temporal_motion", "launch_temporal_deform"};   // (the device error names the kind)
     TemporalArgs a{};
-    a.call = rt2::temporal_call(desc);
-    return frame_call(h, host, planes, "the staging planes of temporal accumulation", "launch_temporal", [&](const void* const* in, void* const* out) {
+    a.call = rt2::temporal_call(d);
+    a.n_objects = d.n_objects;
+    a.tri_first = d.tri_first;
+    a.n_prev_triangles = d.n_prev_triangles;
+    return frame_call(h, host, planes, "the staging planes of temporal accumulation", LAUNCH[(int)kind], [&](const void* const* in, void* const* out) {
         a.color = (const float*)in[0]; a.out = (float*)out[0]; a.point = (const float*)in[1]; a.normal = (const float*)in[2];
         a.object = (const uint32_t*)in[3]; a.prev_color = (const float*)in[4]; a.prev_history = (const float*)in[5];
         a.prev_point = (const float*)in[6]; a.prev_normal = (const float*)in[7]; a.prev_object = (const uint32_t*)in[8];
-        a.out_history = (float*)out[9]; a.motion = (float*)out[10];
-        return launch_temporal(a, h->stream);
-    });
-}
-
-// With a motion table (include/rt_abi.h: rt_temporal_accumulate_moving): rt_temporal_accumulate's planes and the table, one
-// more input that is not frame-shaped.
-int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::temporal_motion_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
-    const FramePlane planes[12] = {{color, desc->out, texels * 16u}, {desc->point, nullptr, texels * 12u}, {desc->normal, nullptr, texels * 12u},
-                                   {desc->object, nullptr, texels * 4u}, {desc->prev_color, nullptr, texels * 16u},
-                                   {desc->prev_history, nullptr, texels * 4u}, {desc->prev_point, nullptr, texels * 12u},
-                                   {desc->prev_normal, nullptr, texels * 12u}, {desc->prev_object, nullptr, texels * 4u},
-                                   {nullptr, desc->out_history, texels * 4u}, {nullptr, desc->motion, texels * 8u},
-                                   {desc->motions, nullptr, (size_t)desc->n_objects * sizeof(rt_object_motion)}};
-    TemporalMotionArgs a{};
-    const rt_temporal_desc head = rt2::temporal_head(desc);
-    a.t.call = rt2::temporal_call(&head);
-    a.n_objects = desc->n_objects;
-    return frame_call(h, host, planes, "the staging planes of temporal accumulation", "launch_temporal_motion", [&](const void* const* in, void* const* out) {
-        a.t.color = (const float*)in[0]; a.t.out = (float*)out[0]; a.t.point = (const float*)in[1]; a.t.normal = (const float*)in[2];
-        a.t.object = (const uint32_t*)in[3]; a.t.prev_color = (const float*)in[4]; a.t.prev_history = (const float*)in[5];
-        a.t.prev_point = (const float*)in[6]; a.t.prev_normal = (const float*)in[7]; a.t.prev_object = (const uint32_t*)in[8];
-        a.t.out_history = (float*)out[9]; a.t.motion = (float*)out[10]; a.motions = (const rttp::Motion*)in[11];
-        return launch_temporal_motion(a, h->stream);
-    });
-}
-
-// With the triangle side (include/rt_abi.h: rt_temporal_accumulate_deforming): the moving call's planes and table, the
-// current G-buffer's primitive, bary and flags planes, and the previous triangles -- a second input that is not frame-shaped.
-int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::temporal_deform_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
-    const FramePlane planes[16] = {{color, desc->out, texels * 16u}, {desc->point, nullptr, texels * 12u}, {desc->normal, nullptr, texels * 12u},
-                                   {desc->object, nullptr, texels * 4u}, {desc->prev_color, nullptr, texels * 16u},
-                                   {desc->prev_history, nullptr, texels * 4u}, {desc->prev_point, nullptr, texels * 12u},
-                                   {desc->prev_normal, nullptr, texels * 12u}, {desc->prev_object, nullptr, texels * 4u},
-                                   {nullptr, desc->out_history, texels * 4u}, {nullptr, desc->motion, texels * 8u},
-                                   {desc->motions, nullptr, (size_t)desc->n_objects * sizeof(rt_object_motion)},
-                                   {desc->primitive, nullptr, texels * 4u}, {desc->bary, nullptr, texels * 8u}, {desc->flags, nullptr, texels},
-                                   {desc->prev_triangles, nullptr, (size_t)desc->n_prev_triangles * sizeof(rt_packed_triangle)}};
-    TemporalDeformArgs a{};
-    const rt_temporal_motion_desc mhead = rt2::temporal_motion_head(desc);
-    const rt_temporal_desc head = rt2::temporal_head(&mhead);
-    a.m.t.call = rt2::temporal_call(&head);
-    a.m.n_objects = desc->n_objects;
-    a.tri_first = desc->tri_first;
-    a.n_prev_triangles = desc->n_prev_triangles;
-    return frame_call(h, host, planes, "the staging planes of temporal accumulation", "launch_temporal_deform", [&](const void* const* in, void* const* out) {
-        TemporalArgs& t = a.m.t;
-        t.color = (const float*)in[0]; t.out = (float*)out[0]; t.point = (const float*)in[1]; t.normal = (const float*)in[2];
-        t.object = (const uint32_t*)in[3]; t.prev_color = (const float*)in[4]; t.prev_history = (const float*)in[5];
-        t.prev_point = (const float*)in[6]; t.prev_normal = (const float*)in[7]; t.prev_object = (const uint32_t*)in[8];
-        t.out_history = (float*)out[9]; t.motion = (float*)out[10]; a.m.motions = (const rttp::Motion*)in[11];
+        a.out_history = (float*)out[9]; a.motion = (float*)out[10]; a.motions = (const rttp::Motion*)in[11];
         a.primitive = (const uint32_t*)in[12]; a.bary = (const float*)in[13]; a.flags = (const uint8_t*)in[14];
         a.prev_triangles = (const rttp::Tri*)in[15];
-        return launch_temporal_deform(a, h->stream);
+        return launch_temporal(a, kind, h->stream);
     });
 }
+
+int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::PLAIN, flags); }
+int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::MOVING, flags); }
+int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::DEFORMING, flags); }
 
 int rt_synchronize(rt_handle* h) {
     if (!h) return RT_ERR_INVALID_ARGUMENT;

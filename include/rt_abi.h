@@ -1229,6 +1229,89 @@ int rt_luminance_moments_host(const rt_vdenoise_desc* desc);
 int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc);
 int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc);
 
+/* Guided upsampling: a frame traced at a LOW resolution carried onto the G-buffer of a HIGH one by
+ * a joint bilateral filter -- bilinear taps of the low frame, each validated against the high texel's own first hit as
+ * rt_temporal_accumulate validates its history taps.  The low frame is w x h (lo_width x lo_height), the high frame W x H
+ * (width x height); both have row 0 at the bottom, every plane tightly packed, and both were produced under the SAME
+ * camera: lo_point, lo_normal and lo_object are rt_render_gbuffer's planes at w x h, depth .. emission its planes at
+ * W x H.  Any pair of sizes is allowed, equal and downscaling ones included.  Everything is binary32 and unfused, in this
+ * order.
+ *   Once per call, on the host: rx = (f32(w) - 1) / (f32(W) - 1), or 0 when W == 1; ry likewise from h and H.  Texel x of a
+ *   frame n wide looks through u = x / (n - 1) (wgsl:479), so high texel P = (X, Y) lies at the low position
+ *   fx = f32(X) * rx, fy = f32(Y) * ry.
+ *   Snap, per axis, rt_temporal_accumulate's (S = 1/64): x0 = floor(fx), tx = fx - f32(x0); if tx <= S then tx = 0,
+ *   otherwise if tx >= 1 - S then x0 += 1 and tx = 0.  Likewise (y0, ty).
+ *   P is GUIDED when some component of normal(P) is non-zero; normal(P) and point(P) are finite; depth(P) is finite and
+ *   > 0; object(P) != 0xffffffff; and `emission` is NULL or the first three components of emission(P) are all zero.
+ *   Every other texel (a miss, a lamp, a NaN) is PLAIN.
+ *   A low tap q with weight b is VALID when b > 0; q is inside the low frame; all four components of lo_color(q) are
+ *   finite; and lo_object(q) == object(P) (a miss matches a miss, a lamp its own lamp).  For a GUIDED P also: some
+ *   component of lo_normal(q) is non-zero; lo_normal(q) and lo_point(q) are finite; with a = lo_point(q) - point(P) and
+ *   n = normal(P), |(a0 n0 + a1 n1) + a2 n2| <= point_tolerance * depth(P); and with m = lo_normal(q),
+ *   ((n0 m0 + n1 m1) + n2 m2) >= normal_cos.
+ *   c(q) = lo_color(q) -- but when P is GUIDED and both albedo planes are given, components k = 0 .. 2 are
+ *   lo_color(q)_k / a'(lo_albedo(q)_k) with a' rt_denoise's floor at 2^-10; alpha as it is.
+ *   A valid tap adds b * c(q) (four components) to sum and b to wsum, both from +0, in tap order.
+ *   RING 1: rt_temporal_accumulate's four taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with its weights
+ *   (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty.  If wsum > 0: v = sum / wsum and coverage(P) = 2.
+ *   RING 2, only when ring 1 left wsum not > 0: sum and wsum from +0 again over the sixteen taps (x0 + i, y0 + j),
+ *   j = -1 .. 2 (outer), i = -1 .. 2 (inner), b = kx * ky with kx = 1 - |f32(i) - tx| * 0.5 and ky = 1 - |f32(j) - ty| * 0.5
+ *   (a tent of half-width two low texels).  If wsum > 0: v = sum / wsum and coverage(P) = 1.
+ *   HOLE, when both rings fail: v = c(q) of the nearest low texel q = (x0 + (tx > 0.5), y0 + (ty > 0.5)), each coordinate
+ *   clamped into the low frame, whatever that texel holds; coverage(P) = 0.
+ *   Result: out(P) = (v0 * albedo(P)_0, v1 * albedo(P)_1, v2 * albedo(P)_2, v3) when P is GUIDED and both albedo planes are
+ *   given (albedo(P) as it is, not floored), and out(P) = v otherwise.
+ * Consequences.  (1) With w == W, h == H, the low planes being the high planes themselves, no albedo planes and
+ * normal_cos <= 0.99, every texel whose colour is finite takes one tap of weight 1 and `out` is `color` bit for bit (a
+ * component that is -0 comes out +0).  (2) With W == 2w - 1 and H == 2h - 1, rx and ry are exactly 0.5 and the texels with
+ * X and Y even are looked through by the very rays of the low texels (X/2, Y/2): with both G-buffers from
+ * rt_render_gbuffer and no albedo planes, out(X, Y) == lo_color(X/2, Y/2) bit for bit there, wherever that colour is
+ * finite.  (3) rt_upsample and rt_upsample_host give the same bits for every input.
+ * `coverage` (optional, one byte per high texel) says which rule produced the texel.  A caller can re-trace its zeros with
+ * rt_radiance_rays from the high G-buffer's `dir` plane and the pixel's seeds; the library has no helper that does.
+ * point_tolerance and normal_cos are rt_temporal_accumulate's, with depth(P) in the place of the view depth.
+ * Without RT_UPSAMPLE_HOST_MEMORY the planes are device pointers on the handle's device (4-byte aligned; 16 for lo_color,
+ * lo_albedo, albedo, emission and out; 1 for coverage), `lo_color` may be NULL for the handle's current image (w * h texels
+ * of it), and the call is asynchronous on the handle's stream, after every earlier call on the handle and before every
+ * later one.  With the flag they are host pointers, staged WHOLE through one temporary device buffer (44 to 60 bytes per
+ * low texel, 48 to 81 per high texel, `out` in a place of its own) that is counted against option "max_device_mb" while
+ * held (RT_ERR_OUT_OF_MEMORY past the cap), and the call returns when the outputs are on the host.
+ * out and coverage must not overlap any input, nor each other: undefined.  The call keeps no scratch between calls.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle or desc; a null plane other than lo_albedo, albedo,
+ * emission, coverage, and lo_color on the device path; one albedo plane without the other; struct_bytes !=
+ * sizeof(rt_upsample_desc); _p0 != 0; unknown flags; a zero width or height on either side; point_tolerance NaN, <= 0 or
+ * infinite; normal_cos NaN or outside [-1, 1]; misaligned device planes), RT_ERR_CAPACITY (w * h or W * H > 2^31 - 1, or
+ * more low texels than the image has with a NULL lo_color), RT_ERR_OUT_OF_MEMORY.  No scene is needed.
+ * Like the ray queries the call leaves the image (unless `out` is the image), the primary tables, a frame_ahead batch in
+ * flight, the pipeline slots, rt_get_stats and the launch words of rt_last_launch as they are. */
+typedef struct rt_upsample_desc {
+    uint32_t        struct_bytes;     /* = sizeof(rt_upsample_desc) */
+    uint32_t        _p0;              /* must be 0 */
+    uint32_t        lo_width, lo_height;
+    uint32_t        width, height;
+    float           point_tolerance;  /* > 0, finite: plane distance allowed per unit of depth(P) */
+    float           normal_cos;       /* finite, in [-1, 1]: least dot product of the two normals */
+    const float*    lo_color;         /* [h][w][4]; device path: NULL = the handle's image */
+    const float*    lo_point;         /* [h][w][3] */
+    const float*    lo_normal;        /* [h][w][3] */
+    const uint32_t* lo_object;        /* [h][w] */
+    const float*    lo_albedo;        /* [h][w][4] or NULL (with albedo, or not at all) */
+    const float*    depth;            /* [H][W] */
+    const float*    point;            /* [H][W][3] */
+    const float*    normal;           /* [H][W][3] */
+    const uint32_t* object;           /* [H][W] */
+    const float*    albedo;           /* [H][W][4] or NULL */
+    const float*    emission;         /* [H][W][4] or NULL */
+    float*          out;              /* [H][W][4] */
+    uint8_t*        coverage;         /* [H][W] or NULL: 2 = ring 1, 1 = ring 2, 0 = hole */
+} rt_upsample_desc;
+enum { RT_UPSAMPLE_HOST_MEMORY = 1 };
+int rt_upsample(rt_handle* h, const rt_upsample_desc* desc, int flags);
+/* The definition above in executable form: plain C++ over host pointers, no device, no working memory.  `lo_color` is
+ * required.  The same argument errors as rt_upsample (no handle, no flags, no alignment rule), nothing written on an
+ * error, the reason in rt_last_error(NULL). */
+int rt_upsample_host(const rt_upsample_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,24 @@ class TemporalDeformDesc(C.Structure):  # rt_temporal_deform_desc: rt_temporal_m
                                               ("prev_triangles", C.c_void_p), ("tri_first", u32), ("n_prev_triangles", u32)]
 
 
+class UpsampleDesc(C.Structure):  # rt_upsample_desc: a low frame and the G-buffers of both sizes for rt_upsample / rt_upsample_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("lo_width", u32), ("lo_height", u32), ("width", u32), ("height", u32),
+                ("point_tolerance", f32), ("normal_cos", f32), ("lo_color", C.c_void_p), ("lo_point", C.c_void_p),
+                ("lo_normal", C.c_void_p), ("lo_object", C.c_void_p), ("lo_albedo", C.c_void_p), ("depth", C.c_void_p),
+                ("point", C.c_void_p), ("normal", C.c_void_p), ("object", C.c_void_p), ("albedo", C.c_void_p),
+                ("emission", C.c_void_p), ("out", C.c_void_p), ("coverage", C.c_void_p)]
+
+
+# rt_upsample's planes: those of the high frame are frame-shaped; the low frame's (lo_*) are not -- the calls put their
+# shapes in, (h, w, n) or (h, w), as they do for the motion table
+UPSAMPLE_PLANES = {"lo_color": ("<f4", None), "lo_point": ("<f4", None), "lo_normal": ("<f4", None), "lo_object": ("<u4", None),
+                   "lo_albedo": ("<f4", None), "depth": ("<f4", 0), "point": ("<f4", 3), "normal": ("<f4", 3), "object": ("<u4", 0),
+                   "albedo": ("<f4", 4), "emission": ("<f4", 4), "out": ("<f4", 4), "coverage": ("u1", 0)}
+UPSAMPLE_LO_COMPONENTS = {"lo_color": 4, "lo_point": 3, "lo_normal": 3, "lo_object": 0, "lo_albedo": 4}
+UPSAMPLE_HOST_MEMORY = 1
+UPSAMPLE_RING1, UPSAMPLE_RING2, UPSAMPLE_HOLE = 2, 1, 0   # the bytes of `coverage`
+
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():

@@ -23,6 +23,7 @@
 #include "rt_device.h"
 #include "rt_refit.h"
 #include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
+#include "rt_upsample_api.h"  // (guided upsampling: its argument rules and host restatement, host/upsample.cpp; its launch, rt_upsample.hip)
 #include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
 #include "rt_vdenoise_api.h"  // (the variance-guided denoiser: its argument rules and host restatement, host/vdenoise.cpp; its launches, rt_vdenoise.hip)
 #include "rt_adaptive_api.h"  // (adaptive sampling: its argument rules and host restatement, host/adaptive.cpp; its launches, rt_adaptive.hip)
@@ -73,6 +74,7 @@ hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_merge(const AdaptiveMergeArgs& a, hipStream_t stream);
+hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -2308,8 +2310,8 @@ int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* r
 }
 
 // ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
-// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming (DESIGN.md
-// section 2.17) ----
+// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming, rt_upsample
+//  ----
 // Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
 // and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
 // arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
@@ -2430,6 +2432,7 @@ int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) { return host_cal
 int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call(rt2::temporal_host, desc); }
 int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc) { return host_call(rt2::temporal_motion_host, desc); }
 int rt_temporal_accumulate_deforming_host(const rt_temporal_deform_desc* desc) { return host_call(rt2::temporal_deform_host, desc); }
+int rt_upsample_host(const rt_upsample_desc* desc) { return host_call(rt2::upsample_host, desc); }
 
 // ---- denoising a rendered frame (include/rt_abi.h: rt_denoise; rt_denoise.hip; host/denoise.cpp) ----
 static const char* const DENOISE_SCRATCH = "the denoiser's scratch images";
@@ -2614,6 +2617,37 @@ static int temporal_accumulate(rt_handle* h, const void* desc, rt2::TemporalKind
 int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::PLAIN, flags); }
 int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::MOVING, flags); }
 int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::DEFORMING, flags); }
+
+// ---- guided upsampling (include/rt_abi.h: rt_upsample; rt_upsample.hip; host/upsample.cpp) ----
+// No scratch is kept.  The low frame's planes are inputs that are not frame-shaped with respect to the high frame: rows of
+// the table with their own sizes, like the motion table of rt_temporal_accumulate_moving.
+int rt_upsample(rt_handle* h, const rt_upsample_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_UPSAMPLE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_UPSAMPLE_HOST_MEMORY) != 0;
+    std::string err;
+    if (const int rc = rt2::upsample_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t lo = (size_t)desc->lo_width * desc->lo_height, texels = (size_t)desc->width * desc->height;
+    const float* lo_color = desc->lo_color;
+    if (int rc = frame_color(h, lo_color, lo); rc != RT_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, lo_color, desc->out); rc != RT_OK) return rc;
+    const FramePlane planes[13] = {{lo_color, nullptr, lo * 16u}, {desc->lo_point, nullptr, lo * 12u}, {desc->lo_normal, nullptr, lo * 12u},
+                                   {desc->lo_object, nullptr, lo * 4u}, {desc->lo_albedo, nullptr, lo * 16u},
+                                   {desc->depth, nullptr, texels * 4u}, {desc->point, nullptr, texels * 12u},
+                                   {desc->normal, nullptr, texels * 12u}, {desc->object, nullptr, texels * 4u},
+                                   {desc->albedo, nullptr, texels * 16u}, {desc->emission, nullptr, texels * 16u},
+                                   {nullptr, desc->out, texels * 16u}, {nullptr, desc->coverage, texels}};
+    UpsampleArgs a{};
+    a.call = rt2::upsample_call(*desc);
+    return frame_call(h, host, planes, "the staging planes of guided upsampling", "launch_upsample", [&](const void* const* in, void* const* out) {
+        a.lo_color = (const float*)in[0]; a.lo_point = (const float*)in[1]; a.lo_normal = (const float*)in[2];
+        a.lo_object = (const uint32_t*)in[3]; a.lo_albedo = (const float*)in[4]; a.depth = (const float*)in[5];
+        a.point = (const float*)in[6]; a.normal = (const float*)in[7]; a.object = (const uint32_t*)in[8];
+        a.albedo = (const float*)in[9]; a.emission = (const float*)in[10]; a.out = (float*)out[11]; a.coverage = (uint8_t*)out[12];
+        return launch_upsample(a, h->stream);
+    });
+}
 
 int rt_synchronize(rt_handle* h) {
     if (!h) return RT_ERR_INVALID_ARGUMENT;

@@ -82,7 +82,8 @@ def _tensor_planes(d, device, table, W, H, planes, outs):
     res = {}
     for k, v in outs.items():
         if v is True:
-            v = given[k] = torch.empty(_plane_shape(table, k, W, H), dtype=torch.float32 if table[k][0] == "<f4" else torch.int32, device=dev)
+            kind = torch.float32 if table[k][0] == "<f4" else torch.uint8 if table[k][0] == "u1" else torch.int32
+            v = given[k] = torch.empty(_plane_shape(table, k, W, H), dtype=kind, device=dev)
         res[k] = None if v is None or v is False else v
     for k, v in given.items():
         setattr(d, k, v.data_ptr())
@@ -286,6 +287,49 @@ def object_motions(prev_arrays, arrays, deformed=None):
     if rc < 0:
         raise RtError(rc, "rt_object_motions refused its arguments")
     return out
+
+
+# Guided upsampling's default thresholds (RayTracer.upsample, upsample_host): temporal accumulation's, with twice its plane
+# distance -- a low texel's hit point lies up to a low texel's footprint away from the high texel's, not a fraction of
+# one, and on a surface seen at a grazing angle that is further off the tangent plane.  DESIGN.md section 2.18 has what
+# the quality test measured with them, and that (0.01, 0.95) .. (0.05, 0.8) measure the same.
+UPSAMPLE_POINT_TOLERANCE, UPSAMPLE_NORMAL_COS = 0.02, 0.9
+
+
+def _upsample_call(lo_guides, guides, color, point_tolerance, normal_cos):
+    """rt_upsample's desc, its plane table with the low frame's shapes put in, the inputs by name and the high frame's size."""
+    for g, what, need in ((lo_guides, "lo_guides", ("point", "normal", "object")), (guides, "guides", ("depth", "point", "normal", "object"))):
+        for k in need:
+            if k not in g:
+                raise ValueError(f"{what} must hold the {k} plane of render_gbuffer")
+    if ("albedo" in lo_guides) != ("albedo" in guides):
+        raise ValueError("the albedo planes come together or not at all: lo_guides and guides must both hold `albedo`, or neither")
+    planes = {"lo_point": lo_guides["point"], "lo_normal": lo_guides["normal"], "lo_object": lo_guides["object"]}
+    planes.update({k: guides[k] for k in ("depth", "point", "normal", "object", "albedo", "emission") if k in guides})
+    if "albedo" in lo_guides:
+        planes["lo_albedo"] = lo_guides["albedo"]
+    if color is not None:
+        planes["lo_color"] = color
+    w, h = _frame_size(planes["lo_normal"])
+    W, H = _frame_size(planes["normal"])
+    table = dict(A.UPSAMPLE_PLANES, **{k: (A.UPSAMPLE_PLANES[k][0], (h, w, n) if n else (h, w)) for k, n in A.UPSAMPLE_LO_COMPONENTS.items()})
+    d = A.UpsampleDesc(struct_bytes=C.sizeof(A.UpsampleDesc), lo_width=w, lo_height=h, width=W, height=H,
+                       point_tolerance=float(point_tolerance), normal_cos=float(normal_cos))
+    return d, table, planes, W, H
+
+
+def _upsample_result(res):
+    return res["out"] if res["coverage"] is None else (res["out"], res["coverage"])
+
+
+def upsample_host(lo_guides, guides, color, point_tolerance=UPSAMPLE_POINT_TOLERANCE, normal_cos=UPSAMPLE_NORMAL_COS, out=None,
+                  coverage=False):
+    """rt_upsample_host: guided upsampling's definition on the CPU (no device), with RayTracer.upsample's arguments for numpy
+    planes.  RayTracer.upsample computes the same bits on the GPU."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    d, table, planes, W, H = _upsample_call(lo_guides, guides, color, point_tolerance, normal_cos)
+    return _upsample_result(_host_frame_call("rt_upsample_host", d, table, W, H, planes, {"out": _new_or(out), "coverage": coverage}))
 
 
 # The variance-guided denoiser's defaults (RayTracer.denoise_variance, denoise_variance_host): a luminance difference of
@@ -935,6 +979,30 @@ class RayTracer:
                                                     point_tolerance, normal_cos, motions, prev_triangles, tri_first)
         outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
         return _temporal_result(self._frame_call(fn, A.TEMPORAL_HOST_MEMORY, d, table, W, H, planes, outs))
+
+    def upsample(self, lo_guides, guides, color=None, point_tolerance=UPSAMPLE_POINT_TOLERANCE, normal_cos=UPSAMPLE_NORMAL_COS,
+                 out=None, coverage=False):
+        """Guided upsampling (rt_upsample; include/rt_abi.h has the definition): the (h, w, 4) float32 frame `color`, traced at
+        a low resolution, carried onto the G-buffer of a higher one by a joint bilateral filter -- every high texel takes the
+        bilinear taps of the low frame that lie on its own surface (same object, near its tangent plane, a similar normal),
+        a wider ring of sixteen where none of the four does, and the nearest low texel where that fails too.
+        `lo_guides`, `guides`: the dicts render_gbuffer returns at the two sizes under the same camera; lo_guides must hold
+        `point`, `normal` and `object`, guides also `depth`; `albedo` (in both or in neither: the radiance is carried
+        demodulated and takes the high texel's albedo) and guides' `emission` (lamps are not guided) are used when
+        present.  `point_tolerance` is the distance off the high texel's tangent plane a tap may lie, per unit of depth;
+        `normal_cos` the least cosine between the two normals.  Any pair of sizes is allowed.
+        Returns the (H, W, 4) frame, or with coverage=True (or an (H, W) uint8 array / tensor to fill) (out, coverage): 2
+        where the four taps served, 1 where the wider ring did, 0 for a hole -- texels a caller may want to trace itself
+        (radiance, with guides["dir"] and pixel_seeds).
+        numpy planes: a synchronous call that returns numpy.  Torch tensors on this handle's device: an asynchronous call
+        ordered after the current torch stream's work, as render_gbuffer(device=True) orders itself; returns tensors; there
+        color=None takes the handle's image -- what render left at the low size -- as the low frame."""
+        d, table, planes, W, H = _upsample_call(lo_guides, guides, color, point_tolerance, normal_cos)
+        tensors = any(hasattr(v, "data_ptr") for v in (*planes.values(), out, coverage))
+        if not tensors and color is None:
+            raise ValueError("color is required with numpy planes (color=None names the device image)")
+        return _upsample_result(self._frame_call("rt_upsample", A.UPSAMPLE_HOST_MEMORY, d, table, W, H, planes,
+                                                 {"out": _new_or(out), "coverage": coverage}))
 
     def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):
         """Radiance along rays of the caller's (rt_radiance_rays): for ray i `frag`'s sample loop with the ray held fixed --

@@ -338,7 +338,8 @@ int rt_get_stats(rt_handle* h, rt_stats* out);
 /* Shape of the last render launch (what a profile summary needs next to the code object's static resources):
  * out[0] = dynamic LDS bytes per workgroup, out[1] = workgroups of the render kernel, out[2] = 1 when the scene blob
  * was staged into LDS, out[3] = bit 0: many-mesh kernels, bit 1: specialised instantiation, bit 2: one-wave-per-tile
- * variant, bit 3: a deferred-walk sequence ran, bit 4: a wavefront sequence ran (then out[0] / out[1] are the walk kernel's);
+ * variant, bit 3: a deferred-walk sequence ran, bit 4: a wavefront sequence ran (then out[0] / out[1] are the walk kernel's), bit 5: the
+ * instantiation with the default launch's fixed switches compiled in ran (csrc/host/launch_options.h: FixedSwitches);
  * out[4] = MiB of device memory the handle holds on its own initiative right now (batch and pipeline scratch images, primary
  * tables, global-memory memos, park queues, snapshot: what option "max_device_mb" bounds), out[5] = that cap (0 = none). */
 int rt_last_launch(rt_handle* h, uint32_t out[6]);

@@ -173,6 +173,19 @@ int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]);
  * terminal_c. */
 int rt_test_terminal_skip(rt_handle* h, int on, uint32_t last_out[4]);
 
+/* The fixed switches (csrc/host/launch_options.h: FixedSwitches, fixed_switches_ok; the FIXED instantiations of the
+ * persistent SIMPLE render kernels, grouped and ungrouped).  rt_test_fixed_switches: on >= 0 switches them for the handle's later launches -- 1, the default,
+ * lets the rule decide, 0 makes every launch run the general kernels; on < 0 changes nothing.  last_out (may be NULL): 1 if the
+ * handle's last render launch ran the FIXED instantiation (rt_last_launch out[3] bit 5).
+ * rt_test_fixed_switches_rule (no device, no handle): the rule on a launch's values, in the order of FixedSwitchValues --
+ * {stack_wide, forest_cull, roulette_skip, fast_miss, terminal_dark, pixel_cache, has a primary table, primary_complete,
+ * skybox, rays_per_pixel, spp_reciprocal != 0, strip_world, batch_frames, batch_tile_major, frame_group} -> out[0] = the
+ * rule's answer, bit 0 for a launch that takes the grouped kernel, bit 1 for one that takes the ungrouped kernel, out[1] = RT_FIXED_SWITCHES, out[2 ..]: the constants the kernel compiles in, in the same order (a switch that
+ * is only tested against zero: 1 for "not zero"; frame_group: 1 for "more than one"). */
+#define RT_TEST_FIXED_SWITCHES 15
+int rt_test_fixed_switches(rt_handle* h, int on, uint32_t* last_out);
+int rt_test_fixed_switches_rule(const int64_t in[RT_TEST_FIXED_SWITCHES], int64_t out[2 + RT_TEST_FIXED_SWITCHES]);
+
 /* The frame groups of a handle's batches (RenderArgs::frame_group: the frames of a pixel that one lane renders back to
  * back).  force >= 0 sets the group size of the handle's later batches, with or without a taper table, 0 = the rules
  * decide (frame_group_for, and frame_group_tapered_for for a launch that carries a table); a

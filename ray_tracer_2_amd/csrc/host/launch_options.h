@@ -354,6 +354,50 @@ inline uint32_t terminal_skip_for(const TerminalScene& t, bool scene_in_lds, boo
     return RT_TERMINAL_SKIP != 0 && !RT_EXPERIMENTS && enabled && t.ok != 0u && scene_in_lds && !many_mesh && takes_simple && !counters && !parks ? t.dark : 0u;
 }
 
+// The fixed switches (csrc/rt_kernel.hip: the FIXED instantiations of the persistent SIMPLE render kernels on a scene staged
+// in LDS, grouped and ungrouped; fix_switches).  The render kernels carry wave-uniform switches that have one value in every
+// default launch -- each a scalar register or two across the render loop, a branch and a dead path.  A FIXED instantiation
+// compiles the values below in: the same operations, a branch whose condition is known.  FixedSwitches states each value
+// once, for the kernels and for the rule; FixedSwitchValues is what a launch has in those places (the RenderArgs fields of
+// the same names; `primary`: the launch has a primary table; `spp_reciprocal`: 1 / rays_per_pixel is exact, a power of
+// two), and fixed_switches_ok is true exactly when every compiled-in constant equals the launch's value -- a switch that
+// the kernels only test against zero is compared as such.  `grouped_kernel`: the launch takes the grouped kernel, which
+// has the batch's three switches compiled in too (a batch, in tile-major order, in frame groups); the ungrouped one runs
+// single frames, pipelined frames and ungrouped batches and keeps those three as the launch has them.  A frame without a
+// complete table (the first one behind a camera change), an option switched off, 3 samples per pixel, no skybox and a
+// strip share run the general kernel; a counter launch and a scene with a sphere never get here (rt_kernel.hip:
+// render_takes_fixed asks for the SIMPLE kernel first).  -DRT_FIXED_SWITCHES=0 compiles the instantiations out.
+#ifndef RT_FIXED_SWITCHES
+#define RT_FIXED_SWITCHES 1
+#endif
+struct FixedSwitches {
+    static constexpr uint32_t stack_wide = 0;        // one dword per stack entry
+    static constexpr uint32_t forest_cull = 1;       // forest members behind their root boxes
+    static constexpr uint32_t roulette_skip = 1, fast_miss = 1;
+    static constexpr uint32_t pixel_cache = 1;       // the memo in LDS
+    static constexpr uint32_t primary_complete = 1;  // ... and equal to the pixel's table entry (so: a table)
+    static constexpr uint32_t skybox = 1;
+    static constexpr uint32_t strip_world = 1;       // the whole frame
+    static constexpr uint32_t batch_tile_major = 1;
+    // (tested against zero only: the launch's own value stays in its place)
+    static constexpr bool terminal_dark = true, primary = true, spp_reciprocal = true, samples = true, batch = true, grouped = true;
+};
+struct FixedSwitchValues {
+    uint32_t stack_wide, forest_cull, roulette_skip, fast_miss, terminal_dark, pixel_cache, primary, primary_complete;
+    int32_t skybox, rays_per_pixel;
+    uint32_t spp_reciprocal, strip_world, batch_frames, batch_tile_major, frame_group;
+};
+inline bool fixed_switches_ok(const FixedSwitchValues& v, bool grouped_kernel) {
+    using F = FixedSwitches;
+    return RT_FIXED_SWITCHES != 0 && v.stack_wide == F::stack_wide && (v.forest_cull != 0u) == (F::forest_cull != 0u) &&
+           (v.roulette_skip != 0u) == (F::roulette_skip != 0u) && (v.fast_miss != 0u) == (F::fast_miss != 0u) &&
+           (v.terminal_dark != 0u) == F::terminal_dark && v.pixel_cache == F::pixel_cache && (v.primary != 0u) == F::primary &&
+           (v.primary_complete != 0u) == (F::primary_complete != 0u) && (v.skybox != 0) == (F::skybox != 0u) &&
+           (v.rays_per_pixel > 0) == F::samples && (v.spp_reciprocal != 0u) == F::spp_reciprocal && v.strip_world == F::strip_world &&
+           (!grouped_kernel || ((v.batch_frames != 0u) == F::batch && (v.batch_tile_major != 0u) == (F::batch_tile_major != 0u) &&
+                                (v.frame_group > 1u) == F::grouped));
+}
+
 // workgroups that fit a CU's 160 KiB of LDS (BLOCKS_PER_CU when the register budget is the limit)
 inline uint32_t blocks_per_cu_for(size_t lds_bytes) {
     const uint32_t per_cu = lds_bytes ? (uint32_t)(CU_LDS_BYTES / lds_bytes) : BLOCKS_PER_CU;

@@ -37,8 +37,9 @@
 #include "rt_srgb_lut.h"
 
 namespace rtd {
-hipError_t launch_render(const RenderArgs& a, hipStream_t stream);
+hipError_t launch_render(const RenderArgs& a, hipStream_t stream, bool fixed_allowed);
 bool render_takes_simple(const RenderArgs& a);
+bool render_takes_fixed(const RenderArgs& a);
 size_t render_lds_bytes(const RenderArgs& a);
 hipError_t launch_tile_order(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t* order,
                              hipStream_t stream);
@@ -288,6 +289,7 @@ struct rt_handle {
     rt2::TerminalScene terminal;
     bool terminal_skip_on = true;
     uint32_t last_terminal_dark = 0;
+    bool fixed_switches_on = true;           // rt_test_fixed_switches (the test library's): false keeps every launch on the general kernels
     bool queues_noted = false;               // the note about GPU_MAX_HW_QUEUES has been left in `err` once
     std::string err;
 };
@@ -1547,7 +1549,8 @@ static void note_launch(rt_handle* h, const rt_params* params, const RenderArgs&
     h->last_launch[1] = a.kernel_variant == 1 || params->debug_flag != 0 ? tile_blocks : std::min(a.persistent_blocks, tile_blocks);
     h->last_launch[2] = a.lds_scene;
     h->last_launch[3] = (a.many_mesh ? 1u : 0u) | (render_takes_simple(a) ? 2u : 0u) |
-                        (a.kernel_variant == 1 ? 4u : 0u) | (pl.rounds ? 8u : 0u);
+                        (a.kernel_variant == 1 ? 4u : 0u) | (pl.rounds ? 8u : 0u) |
+                        (h->fixed_switches_on && render_takes_fixed(a) ? 32u : 0u);
     h->last_terminal_dark = params->debug_flag != 0 ? 0u : a.terminal_dark;
 }
 
@@ -1573,7 +1576,7 @@ static int launch_pipelined(rt_handle* h, const rt_params* params, RenderArgs& a
     a.batch_frames = 1;
     a.batch_stride = pl.need_texels;
     a.batch_tile_major = 0;
-    HIP_TRY(h, launch_render(a, pl.S));
+    HIP_TRY(h, launch_render(a, pl.S, h->fixed_switches_on));
     HIP_TRY(h, hipEventRecord(slot.sampled, pl.S));
     slot.sampled_set = true;
     HIP_TRY(h, hipEventRecord(pl.ev->second, pl.S));
@@ -1641,7 +1644,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
         ah.work_counter = a.work_counter; ah.defer_mesh = a.defer_mesh; ah.defer_xform = a.defer_xform;
     };
     sync_queues();
-    HIP_TRY(h, launch_render(ah, h->stream));
+    HIP_TRY(h, launch_render(ah, h->stream, h->fixed_switches_on));
     for (uint32_t r = 0; r < R; ++r) {
         const bool last = r + 1 == R;
         a.q_in = h->park_queue[r & 1u];
@@ -1657,7 +1660,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
         a.q_out = last ? nullptr : h->park_queue[(r + 1) & 1u];
         a.q_out_count = last ? nullptr : h->park_counts + r + 1;
         sync_queues();
-        HIP_TRY(h, launch_render(last ? a : ah, h->stream));
+        HIP_TRY(h, launch_render(last ? a : ah, h->stream, h->fixed_switches_on));
     }
     return RT_OK;
 }
@@ -1727,7 +1730,7 @@ static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uin
     if (pl.wf.on) rc = wavefront_run(h, a, pl.wf);
     else if (pl.pipe) rc = launch_pipelined(h, params, a, pl);
     else if (pl.rounds) rc = launch_rounds(h, a, pl);
-    else HIP_TRY(h, launch_render(a, h->stream));
+    else HIP_TRY(h, launch_render(a, h->stream, h->fixed_switches_on));
     if (rc != RT_OK) return rc;
     if (n_batch && !blend_later && (rc = blend_frames(h, h->batch_scratch, pl.need_texels, n_batch, params->frames)) != RT_OK) return rc;
     if (!pl.pipe) {
@@ -3197,6 +3200,32 @@ int rt_test_terminal_skip(rt_handle* h, int on, uint32_t last_out[4]) {
             memcpy(&last_out[1 + k], &c, 4);
         }
     }
+    return RT_OK;
+}
+
+// Test-only: the fixed switches of handle `h` (rt2::FixedSwitches).  on >= 0 switches them for the handle's later launches
+// (1: rt2::fixed_switches_ok decides, the default; 0: every launch runs the general kernel); last_out: 1 if the handle's
+// last render launch ran the FIXED instantiation (rt_last_launch out[3] & 32).
+int rt_test_fixed_switches(rt_handle* h, int on, uint32_t* last_out) {
+    if (!h) return RT_ERR_INVALID_ARGUMENT;
+    if (on >= 0) h->fixed_switches_on = on != 0;
+    if (last_out) *last_out = (h->last_launch[3] & 32u) != 0u ? 1u : 0u;
+    return RT_OK;
+}
+
+// Test-only: rt2::fixed_switches_ok on host-given values, and the constants of rt2::FixedSwitches beside the answer.
+int rt_test_fixed_switches_rule(const int64_t in[RT_TEST_FIXED_SWITCHES], int64_t out[2 + RT_TEST_FIXED_SWITCHES]) {
+    if (!in || !out) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null argument");
+    using F = rt2::FixedSwitches;
+    const rt2::FixedSwitchValues v{(uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], (uint32_t)in[4], (uint32_t)in[5],
+                                   (uint32_t)in[6], (uint32_t)in[7], (int32_t)in[8], (int32_t)in[9], (uint32_t)in[10], (uint32_t)in[11],
+                                   (uint32_t)in[12], (uint32_t)in[13], (uint32_t)in[14]};
+    const int64_t constants[RT_TEST_FIXED_SWITCHES] = {F::stack_wide, F::forest_cull, F::roulette_skip, F::fast_miss, F::terminal_dark, F::pixel_cache,
+                                                        F::primary, F::primary_complete, F::skybox, F::samples, F::spp_reciprocal, F::strip_world,
+                                                        F::batch, F::batch_tile_major, F::grouped};
+    out[0] = (rt2::fixed_switches_ok(v, true) ? 1 : 0) | (rt2::fixed_switches_ok(v, false) ? 2 : 0);
+    out[1] = RT_FIXED_SWITCHES;
+    for (int k = 0; k < RT_TEST_FIXED_SWITCHES; ++k) out[2 + k] = constants[k];
     return RT_OK;
 }
 

@@ -2436,8 +2436,39 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_tiles_k
 // does not depend on which lane rendered which pixel.
 // GROUPS: the instantiations that render a batch in frame groups (RenderArgs::frame_group; launch_render) -- a kernel of
 // their own, so that every other launch runs the code it ran before there were groups.
-template <bool LDS, bool STATS, bool TLAS, bool PARK, bool SIMPLE, bool HYB = false, bool GROUPS = false>
-__global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persistent_kernel(const RenderArgs a) {
+// FIXED: the SIMPLE instantiations, grouped and ungrouped, of a launch on a scene in LDS whose switches have the values of
+// rt2::FixedSwitches (host/launch_options.h: fixed_switches_ok; render_takes_fixed).  fix_switches puts the constants into
+// those fields of the kernel's own copy of the arguments before anything reads them, so the kernel and everything it
+// inlines see a constant wherever they read a switch; the other instantiations never call it and are what they were.
+// GROUPS: the batch's own switches too -- the ungrouped kernel runs single frames, pipelined frames and ungrouped batches,
+// and keeps those three as the launch has them.
+template <bool GROUPS>
+DEV void fix_switches(RenderArgs& a) {
+    using F = rt2::FixedSwitches;
+    a.stack_wide = F::stack_wide;
+    a.forest_cull = F::forest_cull;
+    a.roulette_skip = F::roulette_skip;
+    a.fast_miss = F::fast_miss;
+    a.pixel_cache = F::pixel_cache;
+    a.primary_complete = F::primary_complete;
+    a.params.skybox = (int32_t)F::skybox;
+    a.strip_world = F::strip_world;
+    if constexpr (GROUPS) a.batch_tile_major = F::batch_tile_major;
+    // (tested against zero only: the value is the launch's)
+    __builtin_assume((a.terminal_dark != 0u) == F::terminal_dark);
+    __builtin_assume((a.primary != nullptr) == F::primary);
+    __builtin_assume((a.spp_reciprocal != 0.0f) == F::spp_reciprocal);
+    __builtin_assume((a.params.rays_per_pixel > 0) == F::samples);
+    if constexpr (GROUPS) {
+        __builtin_assume((a.batch_frames != 0u) == F::batch);
+        __builtin_assume((a.frame_group > 1u) == F::grouped);
+    }
+}
+
+template <bool LDS, bool STATS, bool TLAS, bool PARK, bool SIMPLE, bool HYB = false, bool GROUPS = false, bool FIXED = false>
+__global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persistent_kernel(RenderArgs a) {
+    static_assert(!FIXED || (RT_FIXED_SWITCHES != 0 && LDS && SIMPLE && !STATS && !TLAS && !PARK && !HYB), "fixed switches: the <LDS, SIMPLE> kernels");
+    if constexpr (FIXED) fix_switches<GROUPS>(a);
 #if defined(RT_DIAG) || defined(RT_WAVE_TIMES)
     const unsigned long long t_wave_start = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -3158,6 +3189,19 @@ static void launch_k(K kernel, uint32_t blocks, size_t lds, hipStream_t stream, 
 // these arguments takes one.
 bool render_takes_simple(const RenderArgs& a) { return a.many_mesh == 0u && a.simple != 0u && a.count_tests == 0u; }
 
+// The FIXED instantiations exist for the persistent SIMPLE kernels on a scene staged in LDS, grouped and ungrouped: whether
+// a render of these arguments takes one -- it takes one of those kernels (launch_render's own conditions) and
+// rt2::fixed_switches_ok says yes for it.
+rt2::FixedSwitchValues fixed_switch_values(const RenderArgs& a) {
+    return rt2::FixedSwitchValues{a.stack_wide, a.forest_cull, a.roulette_skip, a.fast_miss, a.terminal_dark, a.pixel_cache,
+                                  a.primary != nullptr ? 1u : 0u, a.primary_complete, a.params.skybox, a.params.rays_per_pixel,
+                                  a.spp_reciprocal != 0.0f ? 1u : 0u, a.strip_world, a.batch_frames, a.batch_tile_major, a.frame_group};
+}
+bool render_takes_fixed(const RenderArgs& a) {
+    const bool simple_lds = render_takes_simple(a) && a.lds_scene != 0u && a.params.debug_flag == 0 && a.kernel_variant != 1u;
+    return simple_lds && rt2::fixed_switches_ok(fixed_switch_values(a), FRAME_GROUPS && a.frame_group > 1u);
+}
+
 // THE choice of the instantiation <LDS, TLAS, SIMPLE> of a launch on the scene of `a`: f(lds, tlas, simple) is called
 // with three std::true_type / std::false_type tags.  LDS: the scene is staged into the LDS.  TLAS: the many-mesh code
 // (top-level trees, root-box culling), only compiled into the kernels that need it (register budget).  SIMPLE: only
@@ -3177,10 +3221,12 @@ static void with_instantiation(const RenderArgs& a, bool simple, F&& f) {
 //   persistent <LDS | global> x <few-mesh: general, SIMPLE, counters | many-mesh: general, counters>   = 10
 //   + the deferred-walk launches, global-memory few-mesh scenes only: general, SIMPLE, counters            =  3
 //   + batches in frame groups, LDS few-mesh scenes only: general, SIMPLE, counters                           =  3
+//   + the persistent <LDS, SIMPLE> ones, grouped and ungrouped, with the default launch's fixed switches compiled in =  2
 //   one wave per tile (small launches) <LDS | global> x <few-mesh: general, SIMPLE | many-mesh: general> =  6
 // Counter launches always take the persistent kernel; a scene that fits the LDS has no mesh worth deferring (the host
 // never asks: rt_api.hip render_impl).  -DRT_EXPERIMENTS=1 adds the hybrid launches and the wavefront kernels.
-hipError_t launch_render(const RenderArgs& a, hipStream_t stream) {
+// (`fixed_allowed`: false keeps the FIXED instantiation out of this launch -- the test library's rt_test_fixed_switches)
+hipError_t launch_render(const RenderArgs& a, hipStream_t stream, bool fixed_allowed) {
     const uint32_t ntiles = a.tiles_x * a.tiles_y;
     if (ntiles == 0) return hipSuccess;
     const size_t lds = render_lds_bytes(a);
@@ -3203,11 +3249,23 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t stream) {
                     }
                     if (a.count_tests) return launch_k(rt_render_persistent_kernel<LDS, true, TLAS, PARK, false>, blocks, lds, stream, a);
                 }
+                // the launch's kernel as it is or, <LDS, SIMPLE> only, with the launch's fixed switches compiled in where they have
+                // those values (render_takes_fixed)
+                auto general_or_fixed = [&](auto groups_tag) {
+                    constexpr bool GROUPS = decltype(groups_tag)::value;
+#if RT_FIXED_SWITCHES
+                    if constexpr (LDS && !TLAS && !PARK && !HYB && SIMPLE) {
+                        if (fixed_allowed && render_takes_fixed(a))
+                            return launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB, GROUPS, true>, blocks, lds, stream, a);
+                    }
+#endif
+                    launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB, GROUPS>, blocks, lds, stream, a);
+                };
                 // frame groups (host/launch_options.h: frame_group_for asks for them on these kernels only)
                 if constexpr (FRAME_GROUPS && LDS && !TLAS && !PARK && !HYB) {
-                    if (a.frame_group > 1u) return launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB, true>, blocks, lds, stream, a);
+                    if (a.frame_group > 1u) return general_or_fixed(std::true_type{});
                 }
-                launch_k(rt_render_persistent_kernel<LDS, false, TLAS, PARK, SIMPLE, HYB>, blocks, lds, stream, a);
+                general_or_fixed(std::false_type{});
             };
             // a launch of a deferred-walk sequence (PARK): few-mesh scenes read from global memory
             const bool park = a.park != 0u || a.q_in != nullptr;

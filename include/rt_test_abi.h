@@ -208,6 +208,70 @@ int rt_test_frame_taper_rule(rt_handle* h, const uint32_t* cost, uint32_t n_tile
  * a batch, or a single frame): n_tiles counts in tile order, read after everything queued on the handle is done. */
 int rt_test_tile_costs(rt_handle* h, uint32_t* out, uint32_t n_tiles);
 
+/* The rules of a handle that keep state from call to call (csrc/host/launch_state.h), no device and no handle.  Each entry
+ * point runs a whole sequence: it starts from a fresh state, takes n call records and fills n decision records.
+ *
+ * rt_test_tile_schedule: rt2::TileSchedule, the schedule of render launches' tile order, taper table and cost recording.
+ * A call is a launch -- its shape, frames of the batch (0: a single frame), the head it would take with a taper table,
+ * option tile_feedback_period, and flags: the handle has a taper buffer, the taper is compiled in, the step applies to the
+ * launch (option tile_feedback on, no debug view, tiles within the tables, the persistent kernel), and RESET: the effect of
+ * an option with RT_TEST_OPT_RESETS_TILES comes before the launch.  The decision, and the state behind it. */
+#define RT_TEST_TILE_TAPER_BUFFER 1
+#define RT_TEST_TILE_TAPER_COMPILED 2
+#define RT_TEST_TILE_APPLIES 4
+#define RT_TEST_TILE_RESET 8
+typedef struct rt_test_tile_call {
+    uint32_t width, height, rank, world;
+    uint32_t n_batch, tapered_head;
+    int32_t period;
+    uint32_t flags;
+} rt_test_tile_call;
+typedef struct rt_test_tile_decision {
+    uint32_t rewrite_order, order_from, write_taper, use_order, take_head, record_costs, record_into;
+    uint32_t have_order, costs_ready, order_age, cost_slot, taper_head, taper_batch; /* the state after the launch */
+} rt_test_tile_decision;
+int rt_test_tile_schedule(const rt_test_tile_call* calls, uint32_t n, rt_test_tile_decision* out);
+
+/* rt_test_ahead_sequence: rt2::AheadSequence driven the way render_single, render_impl and rt_set_option drive it, with the
+ * device's part of each call replaced by the record's word.  kind FRAME: a one-frame call (params, rank, world) on a handle
+ * whose option frame_ahead is `frame_ahead` (-1: automatic, the depth is rt2::ahead_depth's for a scene staged in LDS or
+ * not, `texels` of the call's share and a host that waits or not); batch_fails: the batched launch the call would start
+ * cannot be set up.  kind BATCHED: a launch of n_frames frames through the batched path (rt_render_frames).  kind BUMP:
+ * something bumps the handle's generation (rt_set_camera with another camera, an upload ...).  kind SET_OPTION: option
+ * frame_ahead is set (again): a bump, and the automatic depth may try again.
+ * The decision: slot >= 0, the call blended that slot of the batch in flight; began, the frames of the batch it started
+ * (0: none); plain, it rendered its own frame in a launch of its own; and behind the call: a batch is in flight, the ramp,
+ * the automatic depth has failed once, and the frames asked for / speculative as rt_get_stats reports them. */
+#define RT_TEST_AHEAD_FRAME 0
+#define RT_TEST_AHEAD_BATCHED 1
+#define RT_TEST_AHEAD_BUMP 2
+#define RT_TEST_AHEAD_SET_OPTION 3
+typedef struct rt_test_ahead_call {
+    uint32_t kind;
+    rt_params params;
+    uint32_t rank, world;
+    int32_t frame_ahead;
+    uint32_t scene_in_lds, host_waits, batch_fails, n_frames;
+    uint64_t texels;
+} rt_test_ahead_call;
+typedef struct rt_test_ahead_decision {
+    int32_t slot;
+    uint32_t continues, began, plain;
+    uint32_t in_flight, ramp, failed_once;
+    uint32_t frames, frames_speculative;
+} rt_test_ahead_decision;
+int rt_test_ahead_sequence(const rt_test_ahead_call* calls, uint32_t n, rt_test_ahead_decision* out);
+
+/* rt_test_primary_choice: rt2::choose_primary, the primary table of a launch, on n rows of RT_TEST_PRIMARY_FACTS words
+ * {primary_table, primary_hits, primary_per_slot (the options), the camera differs from the last sampled frame's, frames of
+ * the batch, the launch is pipelined, pixel_cache, debug_flag, rays_per_pixel, counters on, then for the shared table and
+ * for the slot's own: serves as it stands, large enough, may grow under the cap} -> RT_TEST_PRIMARY_CHOICE words {table: 0
+ * none, 1 shared, 2 the slot's own; want_hits; rebuild; owed before a rebuild: 0 nothing, 1 the slot's stream is
+ * synchronised, 2 every stream is drained; barrier_other is owed}. */
+#define RT_TEST_PRIMARY_FACTS 16
+#define RT_TEST_PRIMARY_CHOICE 5
+int rt_test_primary_choice(const int32_t* facts, uint32_t n, uint32_t* out);
+
 /* Test-only: the BVH builder's SAH plane search (find_best_split, bvh.rs:299-351) for host-given nodes, without a build
  * around it: device -1 runs the host search (csrc/host/bvh.cpp: make_host_level_search, no GPU needed), device >= 0 the
  * kernels of csrc/rt_bvh_search.hip (make_device_level_search).  tri9: nine floats per triangle (centroid, min, max; any

@@ -1,7 +1,8 @@
 // launch_options.h -- the options of rt_set_option in one table, and the rules that turn them into a launch.  Plain C++
 // without HIP, like the host packer: set, refused and evaluated on a machine without a GPU (tests/test_options_host.py,
-// tests/test_launch_rules_host.py).  include/rt_abi.h documents every option; rt_api.hip keeps what needs the handle's
-// buffers, the device's memory or a stream.
+// tests/test_launch_rules_host.py).  include/rt_abi.h documents every option; the rules that keep state on the handle
+// from one call to the next are launch_state.h's; rt_api.hip keeps the HIP calls: what touches the handle's buffers, the
+// device's memory or a stream.
 #ifndef RT_LAUNCH_OPTIONS_H
 #define RT_LAUNCH_OPTIONS_H
 
@@ -187,7 +188,7 @@ inline uint32_t equal_batch(uint32_t n_frames, uint32_t cap) {
 // per resident wave --, and a strip share of eight ranks from groups of 8 at 64 frames per launch and of 3 at its 28.
 // A launch without a table -- the first launch of a shape, another batch size, no tile order yet, option tile_feedback
 // off -- keeps the cap and the floor above (8 / 5 / 2 / 1 for the same four launches): untapered, groups of 16 are slower
-// than groups of 8, so a long head never runs without its table (rt_api.hip: tile_feedback decides).
+// than groups of 8, so a long head never runs without its table (launch_state.h: TileSchedule decides).
 #ifndef RT_FRAME_GROUP
 #define RT_FRAME_GROUP 8
 #endif

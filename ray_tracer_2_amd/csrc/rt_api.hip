@@ -19,6 +19,7 @@
 
 #include "host/bvh.h"  // (rt2::refit_select / refit_bvh: the selection rule shared with the host refit)
 #include "host/launch_options.h"  // (the option table and the launch rules: plain C++, tested on the CPU)
+#include "host/launch_state.h"  // (the rules that keep state from call to call: tile schedule, frames rendered ahead, primary table)
 #include "host/scene_pack.h"  // (the host packer: scene arrays -> blob)
 #include "rt_device.h"
 #include "rt_refit.h"
@@ -91,15 +92,8 @@ using namespace rtd;
 // The host packer (host/scene_pack.h): the facts of an uploaded scene that the handle keeps.
 using rt2::InstanceFacts, rt2::MeshGeom, rt2::SceneGeom;
 
-// The frame layout a buffer, a table or a history was made for: the image size and the strip split.  The default (zero)
-// shape is "nothing made yet": it equals no shape a launch can have (render_impl refuses world == 0).
-struct FrameShape {
-    uint32_t width = 0, height = 0, rank = 0, world = 0;
-    bool operator==(const FrameShape& o) const { return width == o.width && height == o.height && rank == o.rank && world == o.world; }
-    bool operator!=(const FrameShape& o) const { return !(*this == o); }
-    // texels of this rank's share (world == 1: the frame itself, without the padding of a ragged last strip)
-    uint64_t texels() const { return world == 1 ? (uint64_t)width * height : rt_strip_texels(width, height, rank, world); }
-};
+// The frame layout a buffer, a table or a history was made for (host/launch_state.h).
+using rt2::FrameShape;
 
 // primary table (rt_primary_kernel): every pixel's memo -- its constant primary ray and (option "primary_hits") that
 // ray's hit -- valid for (camera, width, height, strip layout, scene, with / without hits); 64 B per pixel
@@ -154,8 +148,7 @@ struct rt_handle {
     size_t ev_used = 0;
     // launches whose event pairs were harvested when the pool wrapped (rt_get_stats adds the live ones)
     double ev_ms_harvested = 0.0;
-    unsigned long long launches_total = 0, frames_total = 0;  // since rt_reset_timing (frames_total: frames the host asked for)
-    unsigned long long frames_speculative = 0;         // frames rendered ahead (option "frame_ahead") that no call has asked for (yet)
+    unsigned long long launches_total = 0;             // since rt_reset_timing (the frames: ahead.frames_asked, .frames_speculative)
     // frame batches (rt_render_frames): scratch images of the frames in flight
     float4* batch_scratch = nullptr;
     size_t batch_scratch_texels = 0;
@@ -170,27 +163,11 @@ struct rt_handle {
     uint32_t* wf_counts = nullptr;
     size_t wf_capacity = 0, wf_counts_capacity = 0;
     rt2::Options opt;                                  // what rt_set_option sets (host/launch_options.h)
-    // Frames rendered ahead (option "frame_ahead", include/rt_abi.h; the depth: rt2::ahead_depth): the call for frame f
-    // renders frames f .. f + d - 1 in one batched launch into the batch scratch images; the next d - 1 calls only blend theirs.
-    bool frame_ahead_failed = false;                   // the batch could not be set up once (memory): automatic stays off
-    uint32_t ahead_ramp = 2;                           // automatic: batches of 2, 4, 8, ... frames up to the depth while the
-                                                       // sequence goes on, so that a host that stops after n frames has had
-                                                       // at most n rendered in vain; back to 2 when the sequence breaks
+    // Frames rendered ahead (option "frame_ahead", include/rt_abi.h; the depth: rt2::ahead_depth): which one-frame call
+    // starts a batch in the batch scratch images and which calls only blend their slot of it (render_single asks, acts and
+    // reports back), and the frames asked for / rendered ahead that rt_get_stats reports.
+    rt2::AheadSequence ahead;
     uint64_t generation = 0;                           // bumped by everything that changes what a frame looks like
-    struct {
-        bool valid = false;
-        rt_params base{};                              // the parameters of slot 0
-        uint32_t n = 0, next = 0;                      // slots rendered / the next one to hand out
-        uint32_t rank = 0, world = 1;
-        uint64_t generation = 0;
-        uint64_t texels = 0;                           // slot stride
-    } ahead;
-    struct {
-        bool valid = false;
-        rt_params params{};
-        uint32_t rank = 0, world = 1;
-        uint64_t generation = 0;
-    } last_single;                                     // the last one-frame call (render_single)
     // rt_snapshot_image / rt_read_snapshot: a copy of the image taken in stream order (device to device), read back on a
     // stream of its own while the handle's stream renders the next frames
     float4* snapshot = nullptr;
@@ -248,23 +225,17 @@ struct rt_handle {
     uint32_t* tile_cost[2] = {nullptr, nullptr};
     uint32_t* tile_order = nullptr;
     // The taper of the grouped launches (RenderArgs::frame_taper): two tables of rt2::TAPER_WORDS words -- the one that
-    // rt_frame_taper_kernel wrote behind the last tile order, good for batches of taper_batch frames in groups of
-    // taper_head (0: none), and the one a test forces (rt_test_frame_taper: its segments' first ranks and group sizes).
+    // rt_frame_taper_kernel wrote behind the last tile order (tiles.taper_batch, .taper_head say what for), and the one a
+    // test forces (rt_test_frame_taper: its segments' first ranks and group sizes).
     uint32_t* frame_taper = nullptr;
-    uint32_t taper_batch = 0, taper_head = 0;
     const uint32_t* last_taper = nullptr;  // the table of the last launch (null: it ran untapered)
     std::vector<uint32_t> taper_forced;
     uint32_t tile_capacity = 0;
-    int cost_slot = 0;
-    FrameShape history;  // the frame layout the tile costs and the tile order were recorded for
+    rt2::TileSchedule tiles;  // when the order is rewritten and the costs are recorded, and into which table (tile_feedback)
     PrimaryTable primary;  // the shared table (every stream's frames read it); the slots' own: PipeSlot::primary
-    // A frame whose camera is not the previous frame's (the camera is MOVING) renders without a table: every pixel computes its
-    // own memo (its primary ray is traversed once, by its first sample) -- building a table that the next frame throws away
-    // costs more than it saves (config 2: 1.32 ms per frame of a moving camera with a table per frame, 1.24 without).
-    rt_camera_uniform last_frame_camera{};
-    bool last_frame_camera_valid = false;
-    bool have_order = false, costs_ready = false;
-    uint32_t order_age = 0;
+    // The camera of the last sampled frame: a frame whose camera is another one (the camera is MOVING) renders without a
+    // table (rt2::choose_primary) -- every pixel computes its own memo, its primary ray is traversed once, by its first sample.
+    rt2::SampledCamera last_sampled;
     uint32_t compute_units = 1;  // of the device (rt_create); sizes the walk kernel's grid whatever "persistent_blocks" says
     float* srgb_lut = nullptr;
     // scene
@@ -586,7 +557,7 @@ void commit_scene(rt_handle* h, const rt_camera_uniform& camera) {
     h->lds_scene = s.lay.bytes + wave_lds_bytes(h->stack_entries, h->stack_wide, s.tlas_entries, true, false) <= LDS_BUDGET_BYTES;
     h->camera = camera;
     h->have_scene = true;
-    h->history = FrameShape{};
+    h->tiles.reset();
     invalidate_primary_tables(h);  // (the tables hold hits: a function of the scene)
 }
 
@@ -966,8 +937,8 @@ int rt_set_option(rt_handle* h, const char* name, int value) {
     const rt2::SetResult r = rt2::set_option(h->opt, name, value);
     if (r.code() != RT_OK) return fail(h, r.code(), r.error);
     if (r.effects & rt2::OPT_DROPS_PRIMARY) invalidate_primary_tables(h);
-    if (r.effects & rt2::OPT_RESETS_TILES) h->history = FrameShape{};
-    if (r.effects & rt2::OPT_CLEARS_AHEAD_FAILED) h->frame_ahead_failed = false;
+    if (r.effects & rt2::OPT_RESETS_TILES) h->tiles.reset();
+    if (r.effects & rt2::OPT_CLEARS_AHEAD_FAILED) h->ahead.try_again();
     return RT_OK;
 }
 
@@ -1363,37 +1334,35 @@ static int primary_table_make(rt_handle* h, RenderArgs& a, PrimaryTable& t, size
     return RT_OK;
 }
 
-// Primary-ray table for the memo: recomputed when the camera or the frame size changed
+// Primary-ray table for the memo: which one, and whether it is recomputed first, is rt2::choose_primary's decision
+// (host/launch_state.h) over the facts gathered here
 static int bind_primary_table(rt_handle* h, const rt_params* params, RenderArgs& a, LaunchPlan& pl) {
     a.primary = nullptr;
     a.primary_complete = 0u;
-    const bool camera_moved = h->last_frame_camera_valid && memcmp(&h->last_frame_camera, &h->camera, sizeof(rt_camera_uniform)) != 0;
-    if (params->debug_flag == 0 && params->rays_per_pixel > 0) {
-        h->last_frame_camera = h->camera;
-        h->last_frame_camera_valid = true;
-    }
-    // (a batch keeps the table whatever the camera did: its frames share it)
+    rt2::PrimaryFacts f;
+    f.primary_table = h->opt.primary_table, f.primary_hits = h->opt.primary_hits, f.primary_per_slot = h->opt.primary_per_slot;
+    f.camera_moved = h->last_sampled.valid && memcmp(&h->last_sampled.camera, &h->camera, sizeof(rt_camera_uniform)) != 0;
+    if (params->debug_flag == 0 && params->rays_per_pixel > 0) h->last_sampled.sampled(h->camera);
+    f.n_batch = pl.n_batch, f.pipelined = pl.pipe, f.pixel_cache = a.pixel_cache, f.count_tests = a.count_tests;
+    f.debug_flag = params->debug_flag, f.rays_per_pixel = params->rays_per_pixel;
     const size_t texels = (size_t)((params->width + 7) / 8) * ((params->height + 7) / 8) * 64;  // whole 8x8 tiles
-    // (option max_device_mb: a table that would have to be allocated beyond the cap is done without -- every pixel then
-    // computes its own memo; a slot table likewise falls back to the shared one)
-    const bool table_fits = h->primary.texels >= texels || fits_cap(h, texels * 64u, h->primary.texels * 64u);
-    if (!(h->opt.primary_table && table_fits && a.pixel_cache != 0 && params->debug_flag == 0 && params->rays_per_pixel > 0 && !(camera_moved && pl.n_batch == 0)))
-        return RT_OK;
-    // (the counter kernels re-intersect every segment, so a launch with counters neither needs nor fills the hits)
-    const bool want_hits = h->opt.primary_hits != 0 && a.count_tests == 0u;
+    const bool want_hits = rt2::primary_wants_hits(h->opt.primary_hits, a.count_tests);
+    auto facts = [&](const PrimaryTable& t) {  // (option max_device_mb: may a table that is too small be replaced by one that is not?)
+        const bool large_enough = t.texels >= texels;
+        return rt2::TableFacts{primary_table_serves(t, texels, h->camera, pl.shape, want_hits), large_enough,
+                               large_enough || fits_cap(h, texels * 64u, t.texels * 64u)};
+    };
     PrimaryTable& own = h->pipe[pl.pslot].primary;
-    const bool use_own = pl.pipe && !primary_table_serves(h->primary, texels, h->camera, pl.shape, want_hits) && h->opt.primary_per_slot != 0 &&
-                         (own.texels >= texels || fits_cap(h, texels * 64u, own.texels * 64u));
-    PrimaryTable& t = use_own ? own : h->primary;
-    if (!primary_table_serves(t, texels, h->camera, pl.shape, want_hits)) {
-        if (use_own) {
-            if (t.texels < texels) HIP_TRY(h, hipStreamSynchronize(pl.S));   // (the slot's previous frame read the old one)
-        } else {
-            if (t.texels < texels)   // (pipelined frames read the table on their own streams)
-                if (int rc = drain_streams(h); rc != RT_OK) return rc;
-            HIP_TRY(h, barrier_other(h, pl));
-        }
-        if (int rc = primary_table_make(h, a, t, texels, pl.shape, want_hits, pl.S); rc != RT_OK) return rc;
+    f.shared = facts(h->primary), f.own = facts(own);
+    const rt2::PrimaryChoice c = rt2::choose_primary(f);
+    if (c.table == rt2::PrimaryChoice::NONE) return RT_OK;
+    PrimaryTable& t = c.table == rt2::PrimaryChoice::OWN ? own : h->primary;
+    if (c.rebuild) {
+        if (c.sync == rt2::PrimaryChoice::SLOT_STREAM) HIP_TRY(h, hipStreamSynchronize(pl.S));
+        if (c.sync == rt2::PrimaryChoice::DRAIN_STREAMS)
+            if (int rc = drain_streams(h); rc != RT_OK) return rc;
+        if (c.barrier) HIP_TRY(h, barrier_other(h, pl));
+        if (int rc = primary_table_make(h, a, t, texels, pl.shape, c.want_hits, pl.S); rc != RT_OK) return rc;
     }
     a.primary = t.table;
     a.primary_complete = t.with_hits ? 1u : 0u;
@@ -1441,58 +1410,46 @@ static int prepare_park_queues(rt_handle* h, LaunchPlan& pl) {
     return RT_OK;
 }
 
-// Tile-cost feedback (persistent kernel, path-trace frames only): the tiles are handed out in the
-// order of the rays each took in an earlier frame of the same shape, heaviest first.  Progressive
-// accumulation re-renders the same view, so an order stays good: it is refreshed every
-// `tile_feedback_period` frames (costs are recorded in the frame before a refresh), not every frame.
+// Tile-cost feedback (persistent kernel, path-trace frames only): the tiles are handed out in the order of the rays each
+// took in an earlier frame of the same shape, heaviest first.  rt2::TileSchedule (host/launch_state.h) says when the order
+// and its taper table are rewritten, whether this launch uses them, and when it records costs; this step does that.
 static int tile_feedback(rt_handle* h, const rt_params* params, RenderArgs& a, LaunchPlan& pl) {
     const uint32_t n_tiles = pl.n_tiles;
-    if (!(h->opt.tile_feedback && params->debug_flag == 0 && n_tiles <= h->tile_capacity && n_tiles > 0 && a.kernel_variant == 0)) return RT_OK;
-    if (h->history != pl.shape) {
-        h->have_order = false;
-        h->costs_ready = false;
-    }
-    if (!h->have_order) h->taper_head = 0;  // (a table cuts the order it was written behind)
-    if (h->costs_ready && (!h->have_order || h->order_age >= (uint32_t)h->opt.tile_feedback_period)) {
-        const long long per_tile = 64ll * (params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) *
-                                   (params->number_of_bounces >= 0 ? params->number_of_bounces + 1 : 0);
-        const uint32_t max_cost = per_tile > 0xffffffffll ? 0xffffffffu : (uint32_t)per_tile;
-        HIP_TRY(h, barrier_other(h, pl));
-        HIP_TRY(h, launch_tile_order(h->tile_cost[h->cost_slot], n_tiles, max_cost, h->tile_order, pl.S));
-        // ... and, for a grouped launch, the taper of that order from the same costs (rt2::frame_taper_table).  Segments
-        // that a complete primary table serves are counted as rays and cost next to nothing: the floor takes them out.
-        h->taper_head = 0;
-        if (RT_FRAME_TAPER != 0 && pl.tapered_head > 1u && h->frame_taper) {
-            const long long served = a.primary_complete != 0u ? 64ll * params->rays_per_pixel : 0ll;
-            HIP_TRY(h, launch_frame_taper(h->tile_cost[h->cost_slot], n_tiles, max_cost, served > 0xffffffffll ? 0xffffffffu : (uint32_t)served,
-                                          pl.n_batch, pl.tapered_head, a.persistent_blocks * WAVES_PER_BLOCK, rt2::FRAME_TAPER_ALPHA,
-                                          h->frame_taper, pl.S));
-            h->taper_batch = pl.n_batch;
-            h->taper_head = pl.tapered_head;
+    rt2::TileLaunch l;
+    l.shape = pl.shape, l.n_batch = pl.n_batch, l.tapered_head = pl.tapered_head;
+    l.period = h->opt.tile_feedback_period, l.taper_buffer = h->frame_taper != nullptr;
+    l.applies = h->opt.tile_feedback && params->debug_flag == 0 && n_tiles <= h->tile_capacity && n_tiles > 0 && a.kernel_variant == 0;
+    const rt2::TileDecision d = h->tiles.step(l);
+    const auto act = [&]() -> int {
+        if (d.rewrite_order) {
+            const long long per_tile = 64ll * (params->rays_per_pixel > 0 ? params->rays_per_pixel : 0) *
+                                       (params->number_of_bounces >= 0 ? params->number_of_bounces + 1 : 0);
+            const uint32_t max_cost = per_tile > 0xffffffffll ? 0xffffffffu : (uint32_t)per_tile;
+            HIP_TRY(h, barrier_other(h, pl));
+            HIP_TRY(h, launch_tile_order(h->tile_cost[d.order_from], n_tiles, max_cost, h->tile_order, pl.S));
+            // (the taper's floor: segments that a complete primary table serves are counted as rays and cost next to nothing)
+            if (d.write_taper) {
+                const long long served = a.primary_complete != 0u ? 64ll * params->rays_per_pixel : 0ll;
+                HIP_TRY(h, launch_frame_taper(h->tile_cost[d.order_from], n_tiles, max_cost, served > 0xffffffffll ? 0xffffffffu : (uint32_t)served,
+                                              pl.n_batch, pl.tapered_head, a.persistent_blocks * WAVES_PER_BLOCK, rt2::FRAME_TAPER_ALPHA,
+                                              h->frame_taper, pl.S));
+            }
         }
-        h->have_order = true;
-        h->order_age = 0;
-        h->costs_ready = false;
-    }
-    const uint32_t frames_now = pl.n_batch ? pl.n_batch : 1u;
-    if (h->have_order) a.tile_order = h->tile_order;
-    // The launch takes the tapered head exactly when it carries the table written for this batch size and that head --
-    // held from an earlier refresh, or written just above.  (The table of another batch size or head, or no order yet:
-    // the launch runs untapered, in the groups frame_groups gave it.)
-    if (h->have_order && pl.tapered_head > 1u && h->taper_head == pl.tapered_head && h->taper_batch == pl.n_batch) {
-        a.frame_group = h->last_frame_group = pl.tapered_head;
-        a.frame_taper = h->frame_taper;
-    }
-    if (!h->have_order || h->order_age + frames_now >= (uint32_t)h->opt.tile_feedback_period) {
-        h->cost_slot ^= 1;
-        a.tile_cost = h->tile_cost[h->cost_slot];
-        pl.wrote_tables = true;
-        HIP_TRY(h, hipMemsetAsync(a.tile_cost, 0, (size_t)n_tiles * sizeof(uint32_t), pl.S));
-        h->costs_ready = true;
-    }
-    h->order_age += frames_now;
-    h->history = pl.shape;
-    return RT_OK;
+        if (d.use_order) a.tile_order = h->tile_order;
+        if (d.take_head) {
+            a.frame_group = h->last_frame_group = pl.tapered_head;
+            a.frame_taper = h->frame_taper;
+        }
+        if (d.record_costs) {
+            a.tile_cost = h->tile_cost[d.record_into];
+            pl.wrote_tables = true;
+            HIP_TRY(h, hipMemsetAsync(a.tile_cost, 0, (size_t)n_tiles * sizeof(uint32_t), pl.S));
+        }
+        return RT_OK;
+    };
+    const int rc = act();
+    if (rc != RT_OK) h->tiles.reset();  // (the schedule counts on what was not done: it starts over)
+    return rc;
 }
 
 // Test-only (rt_test_frame_taper): the forced segments as this launch's table, in place of the rule's -- for a launch that
@@ -1669,12 +1626,7 @@ static int launch_rounds(rt_handle* h, RenderArgs& a, const LaunchPlan& pl) {
 static void account_launch(rt_handle* h, const rt_params* params, const LaunchPlan& pl) {
     const uint32_t n_batch = pl.n_batch;
     h->launches_total += 1;
-    if (pl.blend_later) {   // (frames rendered ahead: the call's own frame; the others count as asked for when their calls come)
-        h->frames_total += 1u;
-        h->frames_speculative += n_batch - 1u;
-    } else {
-        h->frames_total += n_batch ? n_batch : 1u;
-    }
+    if (!pl.blend_later) h->ahead.launched(n_batch ? n_batch : 1u);  // (frames rendered ahead: render_single reports them)
     if (params->debug_flag == 0 && params->rays_per_pixel > 0) {
         // pixels this call renders (strips are clipped to the image height)
         unsigned long long rows = 0;
@@ -1693,7 +1645,7 @@ static void account_launch(rt_handle* h, const rt_params* params, const LaunchPl
 static int render_impl(rt_handle* h, const rt_params* params, uint32_t rank, uint32_t world, uint32_t n_batch = 0,
                        bool blend_later = false) {
     if (!h || !params) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    h->ahead.valid = false;  // (whatever launches here breaks a sequence of frames rendered ahead: render_single)
+    h->ahead.broken();  // (whatever launches here breaks a sequence of frames rendered ahead: render_single)
     LaunchPlan pl;
     pl.shape = FrameShape{params->width, params->height, rank, world};
     pl.n_batch = n_batch;
@@ -1774,13 +1726,7 @@ static int render_frames_impl(rt_handle* h, const rt_params* params, uint32_t n_
     return RT_OK;
 }
 
-// ---- one frame per call, frames rendered ahead (option "frame_ahead") ---------------------------------------------
-static bool same_frame_params(const rt_params& a, const rt_params& b, int32_t b_frames) {  // (the padding is not compared)
-    return a.width == b.width && a.height == b.height && a.number_of_bounces == b.number_of_bounces &&
-           a.rays_per_pixel == b.rays_per_pixel && a.skybox == b.skybox && a.frames == b_frames && a.accumulate == b.accumulate &&
-           a.debug_flag == b.debug_flag && a.debug_scale == b.debug_scale;
-}
-
+// ---- one frame per call, frames rendered ahead (option "frame_ahead"; the sequence: rt2::AheadSequence) ---------------
 // blend slot `slot` of the frames rendered ahead into the image: wgsl:157-158 with the frame's own weight
 static int blend_ahead_slot(rt_handle* h, uint32_t slot, int32_t frames) {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1796,85 +1742,54 @@ static int blend_ahead_slot(rt_handle* h, uint32_t slot, int32_t frames) {
 
 static int render_single(rt_handle* h, const rt_params* params, uint32_t rank, uint32_t world) {
     if (!h || !params) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    auto remember = [&]() {
-        h->last_single.valid = true;
-        h->last_single.params = *params;
-        h->last_single.rank = rank;
-        h->last_single.world = world;
-        h->last_single.generation = h->generation;
-    };
-    if (h->ahead.valid) {
-        const int32_t want = (int32_t)((uint32_t)h->ahead.base.frames + h->ahead.next);
-        if (h->ahead.generation == h->generation && h->ahead.rank == rank && h->ahead.world == world &&
-            same_frame_params(*params, h->ahead.base, want)) {
-            const int rc = blend_ahead_slot(h, h->ahead.next, params->frames);
-            if (rc != RT_OK) {
-                h->ahead.valid = false;
-                return rc;
-            }
-            h->ahead.next += 1;
-            h->frames_total += 1;   // (a frame rendered ahead has now been asked for)
-            if (h->frames_speculative > 0) h->frames_speculative -= 1;
-            if (h->ahead.next == h->ahead.n) h->ahead.valid = false;
-            remember();
-            return RT_OK;
-        }
-        h->ahead.valid = false;  // the host went another way: what is left of the batch is dropped (it was never blended)
-        h->ahead_ramp = 2;
+    const rt2::FrameCall call{*params, rank, world, h->generation};
+    const rt2::AheadStep step = h->ahead.one_frame_call(call);
+    if (step.slot >= 0) {
+        const int rc = blend_ahead_slot(h, (uint32_t)step.slot, params->frames);
+        if (rc == RT_OK) h->ahead.served(call);
+        else h->ahead.broken();
+        return rc;
     }
-    const bool continues = h->last_single.valid && h->last_single.generation == h->generation &&
-                           h->last_single.rank == rank && h->last_single.world == world &&
-                           same_frame_params(*params, h->last_single.params, (int32_t)((uint32_t)h->last_single.params.frames + 1u));
-    if (continues && h->have_scene && world != 0 && rank < world && params->width != 0 && params->height != 0) {
+    if (step.continues && h->have_scene && world != 0 && rank < world && params->width != 0 && params->height != 0) {
         const uint64_t need_texels = FrameShape{params->width, params->height, rank, world}.texels();
+        const bool automatic = h->opt.frame_ahead < 0;
         // (a host that WAITS for its frames finds the stream idle; one that runs ahead of the device finds it busy)
-        const bool host_waits = h->opt.frame_ahead < 0 && !(hipSetDevice(h->device) == hipSuccess && hipStreamQuery(h->stream) == hipErrorNotReady);
+        const bool host_waits = automatic && !(hipSetDevice(h->device) == hipSuccess && hipStreamQuery(h->stream) == hipErrorNotReady);
         (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure: not for the launchers' hipGetLastError)
-        uint32_t d = rt2::ahead_depth(h->opt, *params, h->count_tests != 0, h->frame_ahead_failed, h->lds_scene, need_texels, host_waits);
-        if (h->opt.frame_ahead < 0 && d >= 2) {
+        const uint32_t full = rt2::ahead_depth(h->opt, *params, h->count_tests != 0, h->ahead.failed_once, h->lds_scene, need_texels, host_waits);
+        if (automatic && full >= 2) {
             // (room for the full depth at once: the batches on the way up would each re-allocate the scratch images -- a
             // stream synchronisation apiece)
-            if (h->batch_scratch_texels < need_texels * d && fits_cap(h, need_texels * d * sizeof(float4), h->batch_scratch_texels * sizeof(float4)) &&
+            if (h->batch_scratch_texels < need_texels * full && fits_cap(h, need_texels * full * sizeof(float4), h->batch_scratch_texels * sizeof(float4)) &&
                 hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess) {
                 float4* bigger = nullptr;
-                if (hipMalloc((void**)&bigger, need_texels * d * sizeof(float4)) == hipSuccess) {
+                if (hipMalloc((void**)&bigger, need_texels * full * sizeof(float4)) == hipSuccess) {
                     free_dev(h->batch_scratch);
                     h->batch_scratch = bigger;
-                    h->batch_scratch_texels = need_texels * d;
+                    h->batch_scratch_texels = need_texels * full;
                     h->batch_zeroed = FrameShape{};  // (new memory: render_impl zeroes it)
                 } else {
                     (void)hipGetLastError();
                 }
             }
-            if (d > h->ahead_ramp) d = h->ahead_ramp;
-            h->ahead_ramp = h->ahead_ramp >= RT_MAX_BATCH_FRAMES / 2 ? RT_MAX_BATCH_FRAMES : h->ahead_ramp * 2;
         }
+        const uint32_t d = h->ahead.start_depth(full, automatic);
         if (d >= 2 && need_texels <= h->image_texels) {
             int rc = render_impl(h, params, rank, world, d, true);
             if (rc == RT_OK) {
-                h->ahead.valid = true;
-                h->ahead.base = *params;
-                h->ahead.n = d;
-                h->ahead.next = 0;
-                h->ahead.rank = rank;
-                h->ahead.world = world;
-                h->ahead.generation = h->generation;
-                h->ahead.texels = need_texels;
+                h->ahead.began(call, d, need_texels);
                 rc = blend_ahead_slot(h, 0, params->frames);
-                h->ahead.next = 1;
-                if (rc != RT_OK) h->ahead.valid = false;
-                else remember();
+                if (rc == RT_OK) h->ahead.remember(call);
+                else h->ahead.broken();
                 return rc;
             }
-            // (no room for the batch: this handle renders its frames one by one from now on)
-            if (h->opt.frame_ahead < 0) h->frame_ahead_failed = true;
+            h->ahead.failed(automatic);  // (no room for the batch: this handle renders its frames one by one from now on)
             (void)hipGetLastError();
         }
     }
-    if (!continues) h->ahead_ramp = 2;
     const int rc = render_impl(h, params, rank, world);
-    if (rc == RT_OK) remember();
-    else h->last_single.valid = false;
+    if (rc == RT_OK) h->ahead.remember(call);
+    else h->ahead.forget();
     return rc;
 }
 
@@ -2748,8 +2663,8 @@ int rt_get_stats(rt_handle* h, rt_stats* out) {
     HIP_TRY(h, harvest_event_times(h, total));
     out->kernel_ms = (float)total;
     out->launches = (uint32_t)h->launches_total;
-    out->frames = (uint32_t)h->frames_total;
-    out->frames_speculative = (uint32_t)h->frames_speculative;
+    out->frames = (uint32_t)h->ahead.frames_asked;
+    out->frames_speculative = (uint32_t)h->ahead.frames_speculative;
     return RT_OK;
 }
 
@@ -2771,7 +2686,8 @@ int rt_reset_timing(rt_handle* h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->ev_used = 0;
     h->ev_ms_harvested = 0.0;
-    h->launches_total = h->frames_total = h->frames_speculative = 0;
+    h->launches_total = 0;
+    h->ahead.reset_counts();
     h->paths_total = 0;
     return RT_OK;
 }
@@ -3288,10 +3204,10 @@ int rt_test_frame_taper_rule(rt_handle* h, const uint32_t* cost, uint32_t n_tile
 // batch, or the single frame), n_tiles of them, once everything queued on the handle is done.
 int rt_test_tile_costs(rt_handle* h, uint32_t* out, uint32_t n_tiles) {
     if (!h || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!h->tile_cost[h->cost_slot]) return fail(h, RT_ERR_INVALID_ARGUMENT, "the handle has no tile-cost tables");
+    if (!h->tile_cost[h->tiles.cost_slot]) return fail(h, RT_ERR_INVALID_ARGUMENT, "the handle has no tile-cost tables");
     if (n_tiles > h->tile_capacity) return fail(h, RT_ERR_INVALID_ARGUMENT, "more tiles than the handle's frame size has");
     if (int rc = rt_synchronize(h); rc != RT_OK) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->tile_cost[h->cost_slot], (size_t)n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out, h->tile_cost[h->tiles.cost_slot], (size_t)n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -44,7 +44,7 @@ TEST_EXPORTS = ["rt_test_device_units", "rt_test_sweep", "rt_test_device_sample_
                 "rt_test_rccl_gather", "rt_test_frame_ahead_depth", "rt_test_intersect", "rt_test_shade", "rt_test_scene_blob", "rt_test_pack_scene", "rt_test_sah_search",
                 "rt_test_option_table", "rt_test_set_option", "rt_test_launch_rule", "rt_test_frame_group", "rt_test_tile_costs",
                 "rt_test_frame_taper", "rt_test_frame_taper_rule", "rt_test_terminal_skip", "rt_test_fixed_switches",
-                "rt_test_fixed_switches_rule"]
+                "rt_test_fixed_switches_rule", "rt_test_tile_schedule", "rt_test_ahead_sequence", "rt_test_primary_choice"]
 
 _lib = None
 _test_lib = None
@@ -206,6 +206,9 @@ def _bind(L, with_test_entries):
             "rt_test_terminal_skip": (i32, [vp, i32, vp]),
             "rt_test_fixed_switches": (i32, [vp, i32, P(u32)]),
             "rt_test_fixed_switches_rule": (i32, [P(C.c_int64 * 15), P(C.c_int64 * 17)]),
+            "rt_test_tile_schedule": (i32, [vp, u32, vp]),
+            "rt_test_ahead_sequence": (i32, [vp, u32, vp]),
+            "rt_test_primary_choice": (i32, [vp, u32, vp]),
         })
         assert set(sig) == set(EXPORTS) | set(TEST_EXPORTS)
     for name, (res, args) in sig.items():

@@ -1313,6 +1313,118 @@ int rt_upsample(rt_handle* h, const rt_upsample_desc* desc, int flags);
  * error, the reason in rt_last_error(NULL). */
 int rt_upsample_host(const rt_upsample_desc* desc);
 
+/* ---- display frames: 8-bit output, tone mapping, auto exposure ----
+ * rt_display turns the RGBA32F frame `color` (width x height, row 0 at the bottom, tightly packed) into four bytes per
+ * texel: what the reference's window shows (shaders/renderer.wgsl onto a Bgra8UnormSrgb surface), with an exposure and a
+ * tone curve in front for frames that leave [0, 1].  Everything is binary32, every operation rounded once, nothing fused,
+ * and no transcendental function is evaluated.
+ *   Exposure, once per call: e = exposure, or exposure * *exposure_scale (one product) when the pointer is given; a scale
+ *   that is not finite and > 0 counts as 1 (e = exposure).
+ *   Input, k = 0 .. 2: v = color_k * e; m = v >= 0 ? min(v, 2^64) : 0 (NaN and negatives become 0, +inf 2^64).
+ *   Tone CLAMP: t = m.  Tone REINHARD: t = (m * (1 + m / (white * white))) / (1 + m), white * white rounded once per call;
+ *   white = +inf gives m / (1 + m).  (A white so small that its square underflows makes t +inf, or NaN at m = 0, which the
+ *   transfers below take as 1 and 0.)
+ *   Transfer SRGB: byte = the number of k in 1 .. 255 with t >= T[k], where T[k] is the smallest binary32 whose exact sRGB
+ *   encoding is >= (k - 1/2) / 255 -- the IEC 61966-2-1 decode (c <= 0.04045 ? c / 12.92 : ((c + 0.055) / 1.055)^2.4) of
+ *   (k - 1/2) / 255 in exact arithmetic, rounded up to binary32 (csrc/rt_srgb_encode_lut.h, generated by
+ *   tools/micro/gen_srgb_encode_lut.py).  This is round(255 srgb(clamp(t))) as a step function of 255 steps; NaN gives 0.
+ *   Transfer LINEAR (for a surface that encodes): l = t > 0 ? min(t, 1) : 0 (NaN: 0); byte = (uint32)(l * 255 + 0.5).
+ *   Alpha: the LINEAR rule on color_3 as it is -- no exposure, no tone.
+ *   Layout: bytes (r, g, b, a), with bit 0 (RT_DISPLAY_LAYOUT_BGRA) (b, g, r, a); input row y goes to output row y, with bit
+ *   1 (RT_DISPLAY_LAYOUT_TOP_FIRST) to row height - 1 - y: the top of the view first.
+ * Consequences.  (1) CLAMP, SRGB, layout = RT_DISPLAY_LAYOUT_BGRA, exposure 1 and no scale pointer give the reference's
+ * window byte for byte.  (2) Every value of rt_srgb_lut.h -- the decode table of the textures -- returns to its byte.
+ * (3) rt_display and rt_display_host give the same bytes for every input.
+ * Without RT_DISPLAY_HOST_MEMORY the planes are device pointers on the handle's device (color 16-byte aligned, out and
+ * exposure_scale 4), `color` may be NULL for the handle's current image (width * height texels of it), and the call is
+ * asynchronous on the handle's stream, after every earlier call on the handle and before every later one: an
+ * exposure_scale that rt_auto_exposure wrote there is read in stream order, with no host round trip.  With the flag they
+ * are host pointers, staged WHOLE through one temporary device buffer (20 bytes per texel) that is counted against option
+ * "max_device_mb" while held (RT_ERR_OUT_OF_MEMORY past the cap), and the call returns when `out` is on the host.
+ * out must not overlap color or exposure_scale: undefined.  The call keeps no scratch between calls.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle or desc; null out; null color except on the device path;
+ * struct_bytes != sizeof(rt_display_desc); _p0 or _p1 != 0; unknown tone, transfer, layout bits or flags; a zero width or
+ * height; exposure NaN, <= 0 or infinite; with REINHARD a white that is NaN or <= 0; misaligned device planes),
+ * RT_ERR_CAPACITY (width * height > 2^31 - 1, or more texels than the image has with a NULL color), RT_ERR_OUT_OF_MEMORY.
+ * No scene is needed.  Like rt_upsample the call leaves the image, the primary tables, a frame_ahead batch in flight, the
+ * pipeline slots, rt_get_stats and the launch words of rt_last_launch as they are. */
+enum { RT_DISPLAY_TONE_CLAMP = 0, RT_DISPLAY_TONE_REINHARD = 1 };
+enum { RT_DISPLAY_SRGB = 0, RT_DISPLAY_LINEAR = 1 };
+enum { RT_DISPLAY_LAYOUT_BGRA = 1, RT_DISPLAY_LAYOUT_TOP_FIRST = 2 };
+typedef struct rt_display_desc {
+    uint32_t     struct_bytes;     /* = sizeof(rt_display_desc) */
+    uint32_t     _p0;              /* must be 0 */
+    uint32_t     width, height;
+    uint32_t     tone;             /* RT_DISPLAY_TONE_CLAMP | RT_DISPLAY_TONE_REINHARD */
+    uint32_t     transfer;         /* RT_DISPLAY_SRGB | RT_DISPLAY_LINEAR */
+    uint32_t     layout;           /* bit 0: B,G,R,A instead of R,G,B,A; bit 1: top row first */
+    uint32_t     _p1;              /* must be 0 */
+    float        exposure;         /* finite, > 0 */
+    float        white;            /* REINHARD: > 0, +inf allowed; ignored by CLAMP */
+    const float* color;            /* [h][w][4]; device path: NULL = the handle's image */
+    const float* exposure_scale;   /* one float or NULL: what rt_auto_exposure wrote */
+    uint8_t*     out;              /* [h][w][4] */
+} rt_display_desc;
+enum { RT_DISPLAY_HOST_MEMORY = 1 };
+int rt_display(rt_handle* h, const rt_display_desc* desc, int flags);
+/* The definition above in executable form: plain C++ over host pointers, no device, no working memory.  `color` is
+ * required.  The same argument errors as rt_display (no handle, no flags, no alignment rule), nothing written on an error,
+ * the reason in rt_last_error(NULL). */
+int rt_display_host(const rt_display_desc* desc);
+
+/* rt_auto_exposure meters the frame `color` and writes one float, *scale, that rt_display takes as exposure_scale: the
+ * factor that brings the frame's trimmed mean log-luminance to `key`.  It is all integers until the last operations, so no
+ * order of summation exists.
+ *   Luminance of a texel: Y = (0.2126 c0 + 0.7152 c1) + 0.0722 c2 (rt_denoise_variance's).
+ *   Counting: a texel whose Y is NaN, <= 0 or +inf is not counted; any other falls into bin
+ *   clamp((bits(Y) >> 20) - 888, 0, 255) -- the exponent and the top three mantissa bits: eight bins per octave over
+ *   2^-16 .. 2^16, a piecewise-linear logarithm.  n_b is the number of texels in bin b.
+ *   Trimming: N = sum n_b, lo = floor(N * low_permille / 1000), hi = floor(N * high_permille / 1000) in 64 bits.  Of the
+ *   texels ranked in ascending bin order the ranks [lo, hi) are kept: k_b is the overlap of bin b's rank interval with it,
+ *   N' = sum k_b, S = sum k_b * b.
+ *   Mean: mbar = f32(S) / f32(N') (each conversion rounded to nearest); Ybar = as_float((uint32)((mbar + 888.5f) *
+ *   1048576.0f)), the same map run backwards through a bin's midpoint; target = min(max(key / Ybar, min_scale), max_scale).
+ *   With N' = 0, target = 1.
+ *   Result: *scale = target; with a prev_scale that is finite and > 0, *scale = prev + (target - prev) * rate (every
+ *   operation rounded).  `histogram`, where given, receives n_b untrimmed.
+ * Device memory (no RT_AUTO_EXPOSURE_HOST_MEMORY): color 16-byte aligned (NULL: the handle's image), the others 4; the
+ * call is asynchronous on the handle's stream, and `scale` may be prev_scale.  The handle keeps 1 KiB of scratch for the
+ * global bins, counted against option "max_device_mb" like rt_adaptive_plan's.  Host memory: staged whole (16 bytes per
+ * texel and three small planes) within the cap; returns when the outputs are on the host.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle, desc or scale; null color except on the device path;
+ * struct_bytes; _p0 != 0; unknown flags; a zero width or height; not 0 <= low_permille < high_permille <= 1000; key,
+ * min_scale or max_scale NaN, <= 0 or infinite, or min_scale > max_scale; rate NaN or outside (0, 1]; misaligned device
+ * planes), RT_ERR_CAPACITY (as rt_display), RT_ERR_OUT_OF_MEMORY.  No scene is needed; side effects as rt_display.
+ * rt_auto_exposure and rt_auto_exposure_host give the same bits for every input. */
+typedef struct rt_auto_exposure_desc {
+    uint32_t     struct_bytes;                  /* = sizeof(rt_auto_exposure_desc) */
+    uint32_t     _p0;                           /* must be 0 */
+    uint32_t     width, height;
+    uint32_t     low_permille, high_permille;   /* 0 <= low < high <= 1000: the ranks kept */
+    float        key;                           /* finite, > 0: the luminance the mean is brought to (0.18) */
+    float        min_scale, max_scale;          /* finite, 0 < min <= max */
+    float        rate;                          /* in (0, 1]; used with prev_scale */
+    const float* color;                         /* [h][w][4]; device path: NULL = the handle's image */
+    const float* prev_scale;                    /* one float or NULL */
+    uint32_t*    histogram;                     /* [256] or NULL */
+    float*       scale;                         /* one float, required */
+} rt_auto_exposure_desc;
+enum { RT_AUTO_EXPOSURE_HOST_MEMORY = 1 };
+int rt_auto_exposure(rt_handle* h, const rt_auto_exposure_desc* desc, int flags);
+int rt_auto_exposure_host(const rt_auto_exposure_desc* desc);
+
+/* The picture to the host: rt_snapshot_image / rt_read_snapshot's protocol with the display pass in the place of the
+ * device-to-device copy.  rt_snapshot_display encodes the first width * height texels of the image, as they are after the
+ * calls made so far, into a buffer of the handle's own (width * height * 4 bytes; desc->color and desc->out must be NULL;
+ * desc->exposure_scale, if given, is a device pointer read in stream order) and does not block; rt_read_display_snapshot
+ * brings the first `bytes` of that picture to the host on the copy stream and returns when they are there, without waiting
+ * for frames rendered since.  The float pair keeps its buffer and its bits, and the two pairs may be interleaved.  The
+ * buffer is allocated on first use (or growth), counted in rt_last_launch's out[4] and against option "max_device_mb":
+ * RT_ERR_OUT_OF_MEMORY when it does not fit.  Errors otherwise as rt_display; RT_ERR_CAPACITY for more texels than the image
+ * has; rt_read_display_snapshot: RT_ERR_INVALID_ARGUMENT before any snapshot or for more bytes than the last one has. */
+int rt_snapshot_display(rt_handle* h, const rt_display_desc* desc);
+int rt_read_display_snapshot(rt_handle* h, uint8_t* out, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

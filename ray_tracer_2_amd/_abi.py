@@ -210,6 +210,26 @@ UPSAMPLE_HOST_MEMORY = 1
 UPSAMPLE_RING1, UPSAMPLE_RING2, UPSAMPLE_HOLE = 2, 1, 0   # the bytes of `coverage`
 
 
+class DisplayDesc(C.Structure):  # rt_display_desc: a frame and how it becomes four bytes per texel, for rt_display / rt_display_host / rt_snapshot_display
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("tone", u32), ("transfer", u32), ("layout", u32),
+                ("_p1", u32), ("exposure", f32), ("white", f32), ("color", C.c_void_p), ("exposure_scale", C.c_void_p), ("out", C.c_void_p)]
+
+
+class AutoExposureDesc(C.Structure):  # rt_auto_exposure_desc: a frame and the meter's settings for rt_auto_exposure / rt_auto_exposure_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("low_permille", u32), ("high_permille", u32),
+                ("key", f32), ("min_scale", f32), ("max_scale", f32), ("rate", f32), ("color", C.c_void_p), ("prev_scale", C.c_void_p),
+                ("histogram", C.c_void_p), ("scale", C.c_void_p)]
+
+
+# the planes of the two calls: `out` is four bytes per texel; the one-float planes and the histogram are not frame-shaped
+DISPLAY_PLANES = {"color": ("<f4", 4), "exposure_scale": ("<f4", (1,)), "out": ("u1", 4)}
+AUTO_EXPOSURE_PLANES = {"color": ("<f4", 4), "prev_scale": ("<f4", (1,)), "histogram": ("<u4", (256,)), "scale": ("<f4", (1,))}
+DISPLAY_HOST_MEMORY = AUTO_EXPOSURE_HOST_MEMORY = 1
+DISPLAY_TONE_CLAMP, DISPLAY_TONE_REINHARD = 0, 1
+DISPLAY_SRGB, DISPLAY_LINEAR = 0, 1
+DISPLAY_LAYOUT_BGRA, DISPLAY_LAYOUT_TOP_FIRST = 1, 2
+
+
 EXPECTED_SIZES = {Params: 48, Material: 96, Sphere: 112, MeshUniform: 240, Node: 48,
                   PackedTriangle: 96, CameraUniform: 84, SceneUniform: 128}
 for _t, _s in EXPECTED_SIZES.items():

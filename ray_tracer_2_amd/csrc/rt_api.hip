@@ -25,6 +25,7 @@
 #include "rt_refit.h"
 #include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
 #include "rt_upsample_api.h"  // (guided upsampling: its argument rules and host restatement, host/upsample.cpp; its launch, rt_upsample.hip)
+#include "rt_display_api.h"  // (the display pass and the exposure meter: their argument rules and host restatements, host/display.cpp; their launches, rt_display.hip)
 #include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
 #include "rt_vdenoise_api.h"  // (the variance-guided denoiser: its argument rules and host restatement, host/vdenoise.cpp; its launches, rt_vdenoise.hip)
 #include "rt_adaptive_api.h"  // (adaptive sampling: its argument rules and host restatement, host/adaptive.cpp; its launches, rt_adaptive.hip)
@@ -77,6 +78,8 @@ hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_merge(const AdaptiveMergeArgs& a, hipStream_t stream);
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t stream);
+hipError_t launch_display(const DisplayArgs& a, hipStream_t stream);
+hipError_t launch_auto_exposure(const AutoExposureArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
                            uint32_t world, unsigned long long pad_texels, hipStream_t stream);
 #if defined(RT_DIAG) || defined(RT_DIAGT)
@@ -178,6 +181,15 @@ struct rt_handle {
     // rt_adaptive_plan: the block sums of its two scans and a few words (rt_adaptive_api.h), kept between calls
     void* adaptive_scratch = nullptr;
     size_t adaptive_scratch_bytes = 0;
+    // rt_auto_exposure: the 256 global bins of its histogram (1 KiB), kept between calls
+    uint32_t* exposure_scratch = nullptr;
+    size_t exposure_scratch_bytes = 0;
+    // rt_snapshot_display / rt_read_display_snapshot: the float pair's protocol on a buffer of four bytes per texel that the
+    // display kernel fills (0 bytes until first used)
+    uint8_t* display_snapshot = nullptr;
+    size_t display_snapshot_capacity = 0, display_snapshot_bytes = 0;
+    hipEvent_t display_taken = nullptr, display_read = nullptr;
+    bool display_read_pending = false;
     hipStream_t copy_stream = nullptr;
     hipEvent_t snapshot_taken = nullptr, snapshot_read = nullptr;
     bool snapshot_read_pending = false;                // a read of the staging buffer was queued since the last snapshot
@@ -290,7 +302,7 @@ int fail(rt_handle* h, int code, const std::string& msg) {
 size_t optional_bytes(const rt_handle* h) {
     size_t b = h->batch_scratch_texels * sizeof(float4) + h->pixel_cache_words * sizeof(uint32_t) + h->primary.texels * 64u +
                2u * (((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4)) + h->snapshot_capacity +
-               h->denoise_scratch_bytes + h->adaptive_scratch_bytes;
+               h->denoise_scratch_bytes + h->adaptive_scratch_bytes + h->exposure_scratch_bytes + h->display_snapshot_capacity;
     for (const PipeSlot& ps : h->pipe) {
         if (ps.scratch) b += h->pipe_scratch_texels * sizeof(float4);
         b += ps.memo_words * sizeof(uint32_t) + ps.primary.texels * 64u;
@@ -505,6 +517,10 @@ void rt_destroy(rt_handle* h) {
     if (h->snapshot_taken) (void)hipEventDestroy(h->snapshot_taken);
     if (h->snapshot_read) (void)hipEventDestroy(h->snapshot_read);
     free_dev(h->snapshot);
+    if (h->display_taken) (void)hipEventDestroy(h->display_taken);
+    if (h->display_read) (void)hipEventDestroy(h->display_read);
+    free_dev(h->display_snapshot);
+    free_dev(h->exposure_scratch);
     free_dev(h->denoise_scratch);
     free_dev(h->adaptive_scratch);
     free_dev(h->wf_state);
@@ -2228,8 +2244,8 @@ int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* r
 }
 
 // ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
-// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming, rt_upsample
-//  ----
+// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming, rt_upsample,
+// rt_display, rt_auto_exposure ----
 // Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
 // and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
 // arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
@@ -2351,6 +2367,8 @@ int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call
 int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc) { return host_call(rt2::temporal_motion_host, desc); }
 int rt_temporal_accumulate_deforming_host(const rt_temporal_deform_desc* desc) { return host_call(rt2::temporal_deform_host, desc); }
 int rt_upsample_host(const rt_upsample_desc* desc) { return host_call(rt2::upsample_host, desc); }
+int rt_display_host(const rt_display_desc* desc) { return host_call(rt2::display_host, desc); }
+int rt_auto_exposure_host(const rt_auto_exposure_desc* desc) { return host_call(rt2::auto_exposure_host, desc); }
 
 // ---- denoising a rendered frame (include/rt_abi.h: rt_denoise; rt_denoise.hip; host/denoise.cpp) ----
 static const char* const DENOISE_SCRATCH = "the denoiser's scratch images";
@@ -2567,6 +2585,54 @@ int rt_upsample(rt_handle* h, const rt_upsample_desc* desc, int flags) {
     });
 }
 
+// ---- display frames (include/rt_abi.h: rt_display, rt_auto_exposure; rt_display.hip; host/display.cpp) ----
+// rt_display keeps no scratch; its one-float exposure_scale is a row of the table like any plane.
+int rt_display(rt_handle* h, const rt_display_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_DISPLAY_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_DISPLAY_HOST_MEMORY) != 0;
+    std::string err;
+    if (const int rc = rt2::display_check(desc, host ? rt2::DisplayPath::STAGED : rt2::DisplayPath::DEVICE, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)desc->width * desc->height;
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, color, reinterpret_cast<const float*>(desc->out)); rc != RT_OK) return rc;
+    const FramePlane planes[3] = {{color, nullptr, texels * 16u}, {desc->exposure_scale, nullptr, 4u}, {nullptr, desc->out, texels * 4u}};
+    DisplayArgs a{};
+    a.call = rt2::display_call(*desc);
+    return frame_call(h, host, planes, "the staging planes of the display pass", "launch_display", [&](const void* const* in, void* const* out) {
+        a.color = (const float*)in[0]; a.exposure_scale = (const float*)in[1]; a.out = (uint32_t*)out[2];
+        return launch_display(a, h->stream);
+    });
+}
+
+// The 1 KiB of global bins is the scratch the handle keeps; prev_scale, histogram and scale are rows of 4, 1024 and 4 bytes.
+int rt_auto_exposure(rt_handle* h, const rt_auto_exposure_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_AUTO_EXPOSURE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_AUTO_EXPOSURE_HOST_MEMORY) != 0;
+    std::string err;
+    if (const int rc = rt2::auto_exposure_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)desc->width * desc->height;
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    static const char* const what_for = "the exposure meter's staging planes";
+    const FramePlane planes[4] = {{color, nullptr, texels * 16u}, {desc->prev_scale, nullptr, 4u},
+                                  {nullptr, desc->histogram, rtdp::BINS * sizeof(uint32_t)}, {nullptr, desc->scale, 4u}};
+    if (int rc = grow_scratch(h, h->exposure_scratch, h->exposure_scratch_bytes, rtdp::BINS * sizeof(uint32_t),
+                              host ? staged_bytes(planes) : 0u, "the exposure meter's bins", what_for); rc != RT_OK) return rc;
+    if (int rc = host ? RT_OK : image_access(h, color, desc->scale); rc != RT_OK) return rc;
+    AutoExposureArgs a{};
+    a.call = rt2::auto_exposure_call(*desc);
+    a.bins = h->exposure_scratch;
+    return frame_call(h, host, planes, what_for, "launch_auto_exposure", [&](const void* const* in, void* const* out) {
+        a.color = (const float*)in[0]; a.prev_scale = (const float*)in[1]; a.histogram = (uint32_t*)out[2]; a.scale = (float*)out[3];
+        return launch_auto_exposure(a, h->stream);
+    });
+}
+
 int rt_synchronize(rt_handle* h) {
     if (!h) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2626,6 +2692,59 @@ int rt_read_snapshot(rt_handle* h, float* out, size_t bytes) {
     HIP_TRY(h, hipMemcpyAsync(out, h->snapshot, bytes, hipMemcpyDeviceToHost, h->copy_stream));
     HIP_TRY(h, hipEventRecord(h->snapshot_read, h->copy_stream));
     h->snapshot_read_pending = true;
+    HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
+    return RT_OK;
+}
+
+// The pair above with the display pass in the place of the copy, on a buffer and events of its own (the copy stream is
+// shared: reads of the two pairs queue behind each other there, nothing else).
+int rt_snapshot_display(rt_handle* h, const rt_display_desc* desc) {
+    if (!h) return RT_ERR_INVALID_ARGUMENT;
+    std::string err;
+    if (const int rc = rt2::display_check(desc, rt2::DisplayPath::SNAPSHOT, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)desc->width * desc->height, bytes = texels * 4u;
+    if (texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
+    if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    if (!h->display_taken) HIP_TRY(h, hipEventCreateWithFlags(&h->display_taken, hipEventDisableTiming));
+    if (!h->display_read) HIP_TRY(h, hipEventCreateWithFlags(&h->display_read, hipEventDisableTiming));
+    if (h->display_snapshot_capacity < bytes) {
+        if (!fits_cap(h, bytes, h->display_snapshot_capacity))
+            return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for the display snapshot");
+        HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        free_dev(h->display_snapshot);
+        h->display_snapshot_capacity = h->display_snapshot_bytes = 0;
+        const hipError_t e = hipMalloc((void**)&h->display_snapshot, bytes);
+        if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, "no device memory for the display snapshot");
+        HIP_TRY(h, e);
+        h->display_snapshot_capacity = bytes;
+        h->display_read_pending = false;
+    }
+    // (a read of the previous picture that is still under way keeps its bytes: the encode waits for it)
+    if (h->display_read_pending) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->display_read, 0));
+    h->display_read_pending = false;
+    DisplayArgs a{};
+    a.call = rt2::display_call(*desc);
+    a.color = reinterpret_cast<const float*>(h->image);
+    a.exposure_scale = desc->exposure_scale;
+    a.out = reinterpret_cast<uint32_t*>(h->display_snapshot);
+    HIP_TRY(h, launch_display(a, h->stream));
+    HIP_TRY(h, hipEventRecord(h->display_taken, h->stream));
+    h->display_snapshot_bytes = bytes;
+    return RT_OK;
+}
+
+int rt_read_display_snapshot(rt_handle* h, uint8_t* out, size_t bytes) {
+    if (!h || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (h->display_snapshot_bytes == 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_snapshot_display has not been called");
+    if (bytes > h->display_snapshot_bytes) return fail(h, RT_ERR_INVALID_ARGUMENT, "read larger than the display snapshot");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->display_taken, 0));
+    HIP_TRY(h, hipMemcpyAsync(out, h->display_snapshot, bytes, hipMemcpyDeviceToHost, h->copy_stream));
+    HIP_TRY(h, hipEventRecord(h->display_read, h->copy_stream));
+    h->display_read_pending = true;
     HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
     return RT_OK;
 }

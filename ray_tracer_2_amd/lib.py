@@ -35,6 +35,7 @@ EXPORTS = [
     "rt_denoise_variance", "rt_luminance_moments", "rt_denoise_variance_host", "rt_luminance_moments_host",
     "rt_adaptive_plan", "rt_adaptive_merge", "rt_adaptive_plan_host", "rt_adaptive_merge_host",
     "rt_upsample", "rt_upsample_host",
+    "rt_display", "rt_display_host", "rt_auto_exposure", "rt_auto_exposure_host", "rt_snapshot_display", "rt_read_display_snapshot",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
     "rt_scene_set_sphere",
     "rt_refit_bvh", "rt_refit_triangles", "rt_refit_built_scene", "rt_scene_set_mesh_vertices", "rt_scene_triangle_order",
@@ -171,6 +172,12 @@ def _bind(L, with_test_entries):
         "rt_adaptive_merge_host": (i32, [P(A.AdaptiveMergeDesc)]),
         "rt_upsample": (i32, [vp, P(A.UpsampleDesc), i32]),
         "rt_upsample_host": (i32, [P(A.UpsampleDesc)]),
+        "rt_display": (i32, [vp, P(A.DisplayDesc), i32]),
+        "rt_display_host": (i32, [P(A.DisplayDesc)]),
+        "rt_auto_exposure": (i32, [vp, P(A.AutoExposureDesc), i32]),
+        "rt_auto_exposure_host": (i32, [P(A.AutoExposureDesc)]),
+        "rt_snapshot_display": (i32, [vp, P(A.DisplayDesc)]),
+        "rt_read_display_snapshot": (i32, [vp, vp, C.c_size_t]),
         "rt_update_instances": (i32, [vp, P(A.SceneUniform), vp, u32, vp, u32]),
         "rt_update_built_scene": (i32, [vp, vp]),
         "rt_scene_set_mesh_transform": (i32, [vp, u32, P(A.Transform)]),

@@ -332,6 +332,81 @@ def upsample_host(lo_guides, guides, color, point_tolerance=UPSAMPLE_POINT_TOLER
     return _upsample_result(_host_frame_call("rt_upsample_host", d, table, W, H, planes, {"out": _new_or(out), "coverage": coverage}))
 
 
+# ---- display frames (RayTracer.display, .auto_exposure, .snapshot_display; display_host, auto_exposure_host) ----
+_DISPLAY_TONES = {"clamp": A.DISPLAY_TONE_CLAMP, "reinhard": A.DISPLAY_TONE_REINHARD}
+_DISPLAY_TRANSFERS = {"srgb": A.DISPLAY_SRGB, "linear": A.DISPLAY_LINEAR}
+# The meter's defaults: the darkest tenth and the brightest twentieth of the counted texels are left out (shadows that no
+# exposure lifts, lamps that any exposure clips), the rest is brought to middle grey, within ten stops either way.
+AUTO_EXPOSURE_LOW, AUTO_EXPOSURE_HIGH, AUTO_EXPOSURE_KEY, AUTO_EXPOSURE_MIN, AUTO_EXPOSURE_MAX = 100, 950, 0.18, 2.0 ** -10, 2.0 ** 10
+
+
+def _one_float(v):
+    """A one-float plane as the calls take it: a (1,) tensor as it is, anything else as a (1,) float32 array."""
+    return v if hasattr(v, "data_ptr") else np.asarray(v, np.float32).reshape(-1)
+
+
+def _display_desc(W, H, tone, transfer, bgra, top_first, exposure, white):
+    tone, transfer = _DISPLAY_TONES.get(tone, tone), _DISPLAY_TRANSFERS.get(transfer, transfer)
+    if tone not in _DISPLAY_TONES.values() or transfer not in _DISPLAY_TRANSFERS.values():
+        raise ValueError("tone must be 'clamp' or 'reinhard' and transfer 'srgb' or 'linear' (or the ABI's numbers)")
+    layout = (A.DISPLAY_LAYOUT_BGRA if bgra else 0) | (A.DISPLAY_LAYOUT_TOP_FIRST if top_first else 0)
+    return A.DisplayDesc(struct_bytes=C.sizeof(A.DisplayDesc), width=W, height=H, tone=tone, transfer=transfer, layout=layout,
+                         exposure=float(exposure), white=float(white))
+
+
+def _display_call(color, width, height, out, exposure_scale, settings):
+    """rt_display's desc, its inputs by name and the frame's size: that of `color`, of a given `out`, or width x height."""
+    sized = color if color is not None else out if out is not None and out is not True else None
+    W, H = _frame_size(sized) if sized is not None else (int(width or 0), int(height or 0))
+    if W <= 0 or H <= 0:
+        raise ValueError("without color (and out) the frame's width and height must be given")
+    planes = {} if color is None else {"color": color}
+    if exposure_scale is not None:
+        planes["exposure_scale"] = _one_float(exposure_scale)
+    return _display_desc(W, H, **settings), planes, W, H
+
+
+def display_host(color, *, tone="clamp", transfer="srgb", bgra=False, top_first=False, exposure=1.0, white=float("inf"),
+                 exposure_scale=None, out=None):
+    """rt_display_host: the display pass's definition on the CPU (no device), with RayTracer.display's arguments for numpy
+    planes.  RayTracer.display computes the same bytes on the GPU."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    d, planes, W, H = _display_call(color, None, None, out, exposure_scale, dict(tone=tone, transfer=transfer, bgra=bgra, top_first=top_first,
+                                                                                 exposure=exposure, white=white))
+    return _host_frame_call("rt_display_host", d, A.DISPLAY_PLANES, W, H, planes, {"out": _new_or(out)})["out"]
+
+
+def _auto_exposure_call(color, width, height, low_permille, high_permille, key, min_scale, max_scale, rate, prev_scale):
+    W, H = _frame_size(color) if color is not None else (int(width or 0), int(height or 0))
+    if W <= 0 or H <= 0:
+        raise ValueError("without color the frame's width and height must be given")
+    low_permille, high_permille = int(low_permille), int(high_permille)
+    if not 0 <= low_permille < high_permille <= 1000:
+        raise ValueError("0 <= low_permille < high_permille <= 1000")
+    d = A.AutoExposureDesc(struct_bytes=C.sizeof(A.AutoExposureDesc), width=W, height=H, low_permille=low_permille,
+                           high_permille=high_permille, key=float(key), min_scale=float(min_scale), max_scale=float(max_scale), rate=float(rate))
+    planes = {} if color is None else {"color": color}
+    if prev_scale is not None:
+        planes["prev_scale"] = _one_float(prev_scale)
+    return d, planes, W, H
+
+
+def _auto_exposure_result(res):
+    return res["scale"] if res["histogram"] is None else (res["scale"], res["histogram"])
+
+
+def auto_exposure_host(color, *, low_permille=AUTO_EXPOSURE_LOW, high_permille=AUTO_EXPOSURE_HIGH, key=AUTO_EXPOSURE_KEY,
+                       min_scale=AUTO_EXPOSURE_MIN, max_scale=AUTO_EXPOSURE_MAX, rate=1.0, prev_scale=None, histogram=False, scale=None):
+    """rt_auto_exposure_host: the exposure meter's definition on the CPU (no device), with RayTracer.auto_exposure's arguments
+    for numpy planes.  RayTracer.auto_exposure computes the same bits on the GPU."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    d, planes, W, H = _auto_exposure_call(color, None, None, low_permille, high_permille, key, min_scale, max_scale, rate, prev_scale)
+    return _auto_exposure_result(_host_frame_call("rt_auto_exposure_host", d, A.AUTO_EXPOSURE_PLANES, W, H, planes,
+                                                  {"scale": _new_or(scale), "histogram": histogram}))
+
+
 # The variance-guided denoiser's defaults (RayTracer.denoise_variance, denoise_variance_host): a luminance difference of
 # sigma_luminance standard deviations of the local noise costs a factor e; a texel's accumulated moments give its variance
 # once min_history frames stand behind them, and the 7 x 7 window does before that.
@@ -596,6 +671,25 @@ class RayTracer:
         """The last snapshot, read on a stream of its own: later frames are not waited for."""
         out = np.empty((height, width, 4), dtype=np.float32)
         self._check(self._L.rt_read_snapshot(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def snapshot_display(self, width, height, *, tone="clamp", transfer="srgb", bgra=False, top_first=False, exposure=1.0,
+                         white=float("inf"), exposure_scale=None):
+        """Keep the picture of the image as it is now aside: snapshot_image with the display pass (display's arguments) in the
+        place of the copy -- four bytes per texel in a buffer of the handle's own; does not block.  `exposure_scale`: a (1,)
+        float32 tensor on this handle's device (auto_exposure's), read in stream order."""
+        d = _display_desc(int(width), int(height), tone, transfer, bgra, top_first, exposure, white)
+        if exposure_scale is None:
+            return self._check(self._L.rt_snapshot_display(self._h, C.byref(d)))
+        if not hasattr(exposure_scale, "data_ptr"):
+            raise ValueError("exposure_scale must be a (1,) float32 tensor on the device (a number goes into `exposure`)")
+        _tensor_planes(d, self.device, A.DISPLAY_PLANES, d.width, d.height, {"exposure_scale": exposure_scale}, {})
+        self._on_handle_stream(lambda: self._check(self._L.rt_snapshot_display(self._h, C.byref(d))))
+
+    def read_display_snapshot(self, width, height):
+        """The last display snapshot as (height, width, 4) uint8, read on a stream of its own: later frames are not waited for."""
+        out = np.empty((height, width, 4), dtype=np.uint8)
+        self._check(self._L.rt_read_display_snapshot(self._h, out.ctypes.data, out.nbytes))
         return out
 
     def write_image(self, img):
@@ -1003,6 +1097,52 @@ class RayTracer:
             raise ValueError("color is required with numpy planes (color=None names the device image)")
         return _upsample_result(self._frame_call("rt_upsample", A.UPSAMPLE_HOST_MEMORY, d, table, W, H, planes,
                                                  {"out": _new_or(out), "coverage": coverage}))
+
+    def _image_call_tensor(self, shape, dtype):
+        """An output tensor of a call that takes the handle's image and was given no tensor: it makes the call a device call."""
+        import torch
+        return torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.device))
+
+    def display(self, color=None, *, tone="clamp", transfer="srgb", bgra=False, top_first=False, exposure=1.0, white=float("inf"),
+                exposure_scale=None, out=None, width=None, height=None):
+        """The display pass (rt_display; include/rt_abi.h has the definition): the (H, W, 4) float32 frame `color` as
+        (H, W, 4) uint8 -- each colour channel times `exposure` (times `exposure_scale`, the one float auto_exposure
+        returns), through the tone curve (`tone`: "clamp", or "reinhard" with the luminance `white` that maps to 1) and
+        the transfer (`transfer`: "srgb" for the exact 8-bit sRGB encoding, "linear" for a surface that encodes itself);
+        alpha is quantised as it is.  `bgra` stores B, G, R, A; `top_first` stores the top row of the view first (the
+        image's row 0 is the bottom).  The defaults with bgra=True are what the reference's window shows.
+        numpy planes: a synchronous call that returns numpy.  Torch tensors on this handle's device: an asynchronous call
+        ordered after the current torch stream's work; returns a tensor; there color=None takes the handle's image
+        (width x height texels of it, or the size of a given `out`), and an exposure_scale tensor is read on the device."""
+        d, planes, W, H = _display_call(color, width, height, out, exposure_scale,
+                                        dict(tone=tone, transfer=transfer, bgra=bgra, top_first=top_first, exposure=exposure, white=white))
+        if color is None and out is None:
+            import torch
+            out = self._image_call_tensor((H, W, 4), torch.uint8)
+        if color is None and "exposure_scale" in planes and not hasattr(planes["exposure_scale"], "data_ptr"):
+            raise ValueError("with color=None (the device image) exposure_scale must be a tensor; a number goes into `exposure`")
+        return self._frame_call("rt_display", A.DISPLAY_HOST_MEMORY, d, A.DISPLAY_PLANES, W, H, planes, {"out": _new_or(out)})["out"]
+
+    def auto_exposure(self, color=None, *, low_permille=AUTO_EXPOSURE_LOW, high_permille=AUTO_EXPOSURE_HIGH, key=AUTO_EXPOSURE_KEY,
+                      min_scale=AUTO_EXPOSURE_MIN, max_scale=AUTO_EXPOSURE_MAX, rate=1.0, prev_scale=None, histogram=False, scale=None,
+                      width=None, height=None):
+        """The exposure meter (rt_auto_exposure; include/rt_abi.h has the definition): a histogram of the frame's luminance
+        over 256 logarithmic bins (eight per octave, 2^-16 .. 2^16), trimmed to the ranks [low_permille, high_permille) per
+        thousand, and from its mean the one float that, as display's exposure_scale, brings that mean to `key` -- clamped to
+        [min_scale, max_scale], and with `prev_scale` (the last frame's) moved only `rate` of the way from it.  Returns the
+        scale as a (1,) float32 array or tensor, or with histogram=True (or a (256,) uint32 array / int32 tensor to fill)
+        (scale, histogram) with the untrimmed counts.
+        numpy planes: a synchronous call.  Torch tensors on this handle's device: asynchronous, nothing comes to the host --
+        display(exposure_scale=...) reads the float in stream order; there color=None meters the handle's image (width x
+        height texels of it).  `scale` may be the prev_scale tensor."""
+        d, planes, W, H = _auto_exposure_call(color, width, height, low_permille, high_permille, key, min_scale, max_scale, rate, prev_scale)
+        if color is None and scale is None:
+            import torch
+            scale = self._image_call_tensor((1,), torch.float32)
+        if color is None and "prev_scale" in planes and not hasattr(planes["prev_scale"], "data_ptr"):
+            raise ValueError("with color=None (the device image) prev_scale must be a tensor")
+        return _auto_exposure_result(self._frame_call("rt_auto_exposure", A.AUTO_EXPOSURE_HOST_MEMORY, d, A.AUTO_EXPOSURE_PLANES, W, H, planes,
+                                                      {"scale": _new_or(scale), "histogram": histogram}))
 
     def radiance(self, origins, dirs, seeds, bounces, samples, skybox=True):
         """Radiance along rays of the caller's (rt_radiance_rays): for ray i `frag`'s sample loop with the ray held fixed --

@@ -1,6 +1,6 @@
 // rt_adaptive_api.h -- what adaptive sampling's units declare to each other (include/rt_abi.h: rt_adaptive_plan,
 // rt_adaptive_merge and their _host forms): the argument rules and the host restatement (host/adaptive.cpp), and the
-// arguments of the device launches (rt_adaptive.hip), both called by the entry points in rt_api.hip.  The rules they share
+// arguments of the device launches (rt_adaptive.hip), both called by the entry points in rt_api_frames.hip.  The rules they share
 // are csrc/rt_adaptive.h.
 #ifndef RT_ADAPTIVE_API_H
 #define RT_ADAPTIVE_API_H

@@ -23,259 +23,10 @@
 #include "host/scene_pack.h"  // (the host packer: scene arrays -> blob)
 #include "rt_device.h"
 #include "rt_refit.h"
-#include "rt_denoise_api.h"  // (the denoiser: its argument rules and host restatement, host/denoise.cpp; its launch, rt_denoise.hip)
-#include "rt_upsample_api.h"  // (guided upsampling: its argument rules and host restatement, host/upsample.cpp; its launch, rt_upsample.hip)
 #include "rt_display_api.h"  // (the display pass and the exposure meter: their argument rules and host restatements, host/display.cpp; their launches, rt_display.hip)
-#include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
-#include "rt_vdenoise_api.h"  // (the variance-guided denoiser: its argument rules and host restatement, host/vdenoise.cpp; its launches, rt_vdenoise.hip)
-#include "rt_adaptive_api.h"  // (adaptive sampling: its argument rules and host restatement, host/adaptive.cpp; its launches, rt_adaptive.hip)
 #include "rt_rccl.h"  // (types of <rccl/rccl.h>; the library itself is loaded on first multi-device use)
-#ifndef RT_TEST_ENTRIES
-#define RT_TEST_ENTRIES 0
-#endif
-#if RT_TEST_ENTRIES
-#include "../../include/rt_test_abi.h"
-#endif
 #include "rt_srgb_lut.h"
-
-namespace rtd {
-hipError_t launch_render(const RenderArgs& a, hipStream_t stream, bool fixed_allowed);
-bool render_takes_simple(const RenderArgs& a);
-bool render_takes_fixed(const RenderArgs& a);
-size_t render_lds_bytes(const RenderArgs& a);
-hipError_t launch_tile_order(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t* order,
-                             hipStream_t stream);
-hipError_t launch_frame_taper(const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor, uint32_t n_batch,
-                              uint32_t head, uint32_t waves, uint32_t alpha, uint32_t* table, hipStream_t stream);
-hipError_t launch_primary(const RenderArgs& a, void* table, bool with_hits, hipStream_t stream);
-hipError_t launch_blend_frames(const BlendArgs& b, hipStream_t stream);
-hipError_t launch_walk(const RenderArgs& a, uint32_t compute_units, hipStream_t stream);
-hipError_t launch_query(const RenderArgs& a, const void* rays, unsigned long long n, void* out, bool any, bool prune_tmax,
-                        uint32_t blocks, uint32_t compute_units, hipStream_t stream);
-hipError_t launch_pick_ray(const RenderArgs& a, uint32_t x, uint32_t y, float4* ray, hipStream_t stream);
-hipError_t launch_gbuffer(const RenderArgs& a, const GBufferArgs& g, hipStream_t stream);
-hipError_t launch_radiance(const RenderArgs& a, const void* rays, uint32_t n, void* out, uint32_t* next_ray, uint32_t compute_units,
-                           hipStream_t stream);
-hipError_t launch_wf_shade(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
-hipError_t launch_wf_walk(const RenderArgs& a, uint32_t blocks, hipStream_t stream);
-size_t wf_walk_lds_bytes(const RenderArgs& a);
-#if RT_TEST_ENTRIES
-hipError_t launch_units(int fn, const float* x, const float* y, float* out, unsigned long long n, hipStream_t stream);
-hipError_t launch_sweep(int which, unsigned long long* out, hipStream_t stream);
-hipError_t launch_test_intersect(const RenderArgs& a, const float* ro, const float* rd, const uint8_t* active,
-                                 unsigned long long n, bool simple, bool stats, uint32_t* out, hipStream_t stream);
-hipError_t launch_units_texture(const uint8_t* rgba8, uint32_t width, uint32_t height, const float* srgb_lut, const float* uv,
-                                float* out, unsigned long long n, hipStream_t stream);
-hipError_t launch_test_shade(const RenderArgs& a, int which, const uint32_t* cases, const uint8_t* active, unsigned long long n,
-                             bool simple, bool fast_miss, bool total_lds, uint32_t* out, hipStream_t stream);
-#endif
-hipError_t launch_refit_fit(const RefitArgs& a, hipStream_t stream);
-hipError_t launch_refit_write(const RefitArgs& a, hipStream_t stream);
-hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream);
-hipError_t launch_temporal(const TemporalArgs& a, rt2::TemporalKind kind, hipStream_t stream);
-hipError_t launch_vdenoise(const VDenoiseArgs& a, hipStream_t stream);
-hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
-hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
-hipError_t launch_adaptive_merge(const AdaptiveMergeArgs& a, hipStream_t stream);
-hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t stream);
-hipError_t launch_display(const DisplayArgs& a, hipStream_t stream);
-hipError_t launch_auto_exposure(const AutoExposureArgs& a, hipStream_t stream);
-hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,
-                           uint32_t world, unsigned long long pad_texels, hipStream_t stream);
-#if defined(RT_DIAG) || defined(RT_DIAGT)
-hipError_t diag_read(unsigned long long* out, bool reset);
-#endif
-#if defined(RT_DIAG) || defined(RT_WAVE_TIMES)
-hipError_t diag_wave_times(unsigned long long* out);
-#endif
-}  // namespace rtd
-
-using namespace rtd;
-
-// The host packer (host/scene_pack.h): the facts of an uploaded scene that the handle keeps.
-using rt2::InstanceFacts, rt2::MeshGeom, rt2::SceneGeom;
-
-// The frame layout a buffer, a table or a history was made for (host/launch_state.h).
-using rt2::FrameShape;
-
-// primary table (rt_primary_kernel): every pixel's memo -- its constant primary ray and (option "primary_hits") that
-// ray's hit -- valid for (camera, width, height, strip layout, scene, with / without hits); 64 B per pixel
-struct PrimaryTable {
-    void* table = nullptr;
-    size_t texels = 0;
-    bool valid = false, with_hits = false;  // (valid: cleared by whatever changes the scene or the walk that found the hits)
-    rt_camera_uniform camera{};
-    FrameShape shape;
-};
-
-// a fresh tile counter per launch: a ring of 64, zeroed in one go each time it wraps (launches on
-// one stream are ordered, so every earlier user of the ring is done by then)
-struct CounterRing {
-    uint32_t* mem = nullptr;
-    uint32_t slot = 0;
-    hipError_t create(hipStream_t stream) {
-        const hipError_t e = hipMalloc((void**)&mem, 64 * sizeof(uint32_t));
-        slot = 0;
-        return e != hipSuccess ? e : hipMemsetAsync(mem, 0, 64 * sizeof(uint32_t), stream);
-    }
-    hipError_t next(hipStream_t stream, uint32_t*& counter) {
-        slot = (slot + 1) & 63u;
-        counter = mem + slot;
-        return slot == 0u ? hipMemsetAsync(mem, 0, 64 * sizeof(uint32_t), stream) : hipSuccess;
-    }
-};
-
-// One frame in flight of the pipelined single frames (option "pipeline"): what is per slot.
-struct PipeSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t sampled = nullptr;     // frame sampled into `scratch` (recorded on `stream`)
-    hipEvent_t blended = nullptr;     // ... and blended out of it (recorded on the handle's stream)
-    bool sampled_set = false, blended_set = false;
-    float4* scratch = nullptr;        // (rt_handle::pipe_scratch_texels texels)
-    FrameShape zeroed;                // the frame layout the scratch image's padding rows were zeroed for
-    CounterRing work;                 // a ring of launch counters per pipe stream
-    uint32_t* memo = nullptr;         // further global-memory primary-ray memos (pixel_cache == 2)
-    size_t memo_words = 0;
-    // A pipelined frame whose camera (or shape) is not the shared table's builds a table of its OWN pipeline slot on its own
-    // stream -- ordered behind that slot's previous frame and read by nobody else, so no frame in flight has to finish
-    // first: the frames of a moving camera overlap like those of a standing one (option "primary_per_slot", default 1).
-    PrimaryTable primary;
-};
-
-struct rt_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;  // created by rt_create; `stream` may be rebound (rt_set_stream)
-    // one (start, stop) event pair per launch since the last rt_reset_timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used = 0;
-    // launches whose event pairs were harvested when the pool wrapped (rt_get_stats adds the live ones)
-    double ev_ms_harvested = 0.0;
-    unsigned long long launches_total = 0;             // since rt_reset_timing (the frames: ahead.frames_asked, .frames_speculative)
-    // frame batches (rt_render_frames): scratch images of the frames in flight
-    float4* batch_scratch = nullptr;
-    size_t batch_scratch_texels = 0;
-    // deferred walks (RenderArgs::park; the deferred mesh found at upload: inst.have_defer): the two park queues, their counters
-#if RT_WALK2
-    float4* walk2 = nullptr;           // experiment: two-level records of the deferred mesh (rt_device.h)
-    uint32_t walk2_base = 0;
-#endif
-    float4* wf_state = nullptr;
-    float4* wf_hit = nullptr;
-    uint32_t* wf_lists = nullptr;     // two lists of wf_capacity slots
-    uint32_t* wf_counts = nullptr;
-    size_t wf_capacity = 0, wf_counts_capacity = 0;
-    rt2::Options opt;                                  // what rt_set_option sets (host/launch_options.h)
-    // Frames rendered ahead (option "frame_ahead", include/rt_abi.h; the depth: rt2::ahead_depth): which one-frame call
-    // starts a batch in the batch scratch images and which calls only blend their slot of it (render_single asks, acts and
-    // reports back), and the frames asked for / rendered ahead that rt_get_stats reports.
-    rt2::AheadSequence ahead;
-    uint64_t generation = 0;                           // bumped by everything that changes what a frame looks like
-    // rt_snapshot_image / rt_read_snapshot: a copy of the image taken in stream order (device to device), read back on a
-    // stream of its own while the handle's stream renders the next frames
-    float4* snapshot = nullptr;
-    size_t snapshot_capacity = 0, snapshot_bytes = 0;  // bytes allocated / bytes of the last snapshot
-    // rt_denoise: per texel a guide record of two float4 and two colour images of one float4 each (64 B), kept between calls
-    float4* denoise_scratch = nullptr;
-    size_t denoise_scratch_bytes = 0;
-    // rt_adaptive_plan: the block sums of its two scans and a few words (rt_adaptive_api.h), kept between calls
-    void* adaptive_scratch = nullptr;
-    size_t adaptive_scratch_bytes = 0;
-    // rt_auto_exposure: the 256 global bins of its histogram (1 KiB), kept between calls
-    uint32_t* exposure_scratch = nullptr;
-    size_t exposure_scratch_bytes = 0;
-    // rt_snapshot_display / rt_read_display_snapshot: the float pair's protocol on a buffer of four bytes per texel that the
-    // display kernel fills (0 bytes until first used)
-    uint8_t* display_snapshot = nullptr;
-    size_t display_snapshot_capacity = 0, display_snapshot_bytes = 0;
-    hipEvent_t display_taken = nullptr, display_read = nullptr;
-    bool display_read_pending = false;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t snapshot_taken = nullptr, snapshot_read = nullptr;
-    bool snapshot_read_pending = false;                // a read of the staging buffer was queued since the last snapshot
-    PipeSlot pipe[rt2::PIPE_MAX];
-    hipEvent_t pipe_book = nullptr;                    // the last tile-order / primary-table rebuild (recorded on a pipe stream)
-    hipEvent_t pipe_main = nullptr;                    // the last launch that was not pipelined (recorded on the handle's stream)
-    bool pipe_book_set = false, pipe_main_set = false;
-    bool pipe_main_need = true;                        // pipelined frames have to wait for pipe_main before they sample (render_impl)
-    size_t pipe_scratch_texels = 0;                    // texels of every slot's scratch image
-    uint32_t pipe_seq = 0;
-    float4* small_blob = nullptr;
-    SceneLayout small_lay{};
-    uint32_t small_stack_entries = 1;
-    bool small_ok = false;
-    float4* park_queue[2] = {nullptr, nullptr};
-    size_t park_capacity = 0;  // records per queue
-    uint32_t* park_counts = nullptr;
-    // rt_render_multi: what the root's stream has to finish before this handle's image may be overwritten
-    // (owned by THIS handle, created on the root's device -- an event is recorded on a stream of its own device --,
-    // so that destroying the root first leaves nothing dangling)
-    hipEvent_t multi_copied = nullptr;
-    int multi_copied_device = -1;
-    bool multi_copy_pending = false;
-    // batch scratch: the frame layout its padding rows were zeroed for
-    FrameShape batch_zeroed;
-    // root side of rt_render_multi
-    std::vector<void*> multi_comms;       // ncclComm_t per rank
-    std::vector<int> multi_comm_devices;  // the device list the communicators were made for
-    std::set<int> multi_peers_enabled;
-    uint32_t top_available = 0;  // breadth-first numbered top records of the biggest mesh's BVH (from geom.top_mesh_base on)
-    float4* own_image = nullptr;  // allocated by rt_create; `image` may be rebound
-    float4* multi_gathered = nullptr;  // rt_render_multi root: [world][pad_texels]
-    float4* multi_frame = nullptr;     // rt_render_multi root: assembled full frame
-    size_t multi_gathered_texels = 0, multi_frame_texels = 0;
-    hipEvent_t multi_event = nullptr;
-    size_t image_texels = 0;
-    unsigned long long paths_total = 0;  // camera paths started since rt_reset_timing
-    uint32_t max_width = 0, max_height = 0;
-    float4* image = nullptr;
-    Counters* counters = nullptr;
-    CounterRing work;  // ring of per-launch tile counters (launches on the handle's stream)
-    uint32_t* pixel_cache_mem = nullptr;  // primary-ray cache when LDS has no room (persistent kernel)
-    size_t pixel_cache_words = 0;
-    // tile-cost feedback: rays per tile of the previous frame order the next frame's tiles
-    uint32_t* tile_cost[2] = {nullptr, nullptr};
-    uint32_t* tile_order = nullptr;
-    // The taper of the grouped launches (RenderArgs::frame_taper): two tables of rt2::TAPER_WORDS words -- the one that
-    // rt_frame_taper_kernel wrote behind the last tile order (tiles.taper_batch, .taper_head say what for), and the one a
-    // test forces (rt_test_frame_taper: its segments' first ranks and group sizes).
-    uint32_t* frame_taper = nullptr;
-    const uint32_t* last_taper = nullptr;  // the table of the last launch (null: it ran untapered)
-    std::vector<uint32_t> taper_forced;
-    uint32_t tile_capacity = 0;
-    rt2::TileSchedule tiles;  // when the order is rewritten and the costs are recorded, and into which table (tile_feedback)
-    PrimaryTable primary;  // the shared table (every stream's frames read it); the slots' own: PipeSlot::primary
-    // The camera of the last sampled frame: a frame whose camera is another one (the camera is MOVING) renders without a
-    // table (rt2::choose_primary) -- every pixel computes its own memo, its primary ray is traversed once, by its first sample.
-    rt2::SampledCamera last_sampled;
-    uint32_t compute_units = 1;  // of the device (rt_create); sizes the walk kernel's grid whatever "persistent_blocks" says
-    float* srgb_lut = nullptr;
-    // scene
-    bool have_scene = false;
-    float4* blob = nullptr;  // the scene, see rt_scene_format.h
-    SceneGeom geom;          // the geometry phase's facts of the uploaded scene (rt_update_instances)
-    InstanceFacts inst;      // the instance phase's decisions of the last upload / update: layout, items, trees, deferred mesh
-    std::vector<rt_mesh_uniform> inst_meshes;  // the instance phase's inputs of the last upload / update (rt_refit_triangles
-    std::vector<rt_sphere> inst_spheres;       // reruns it)
-    bool lds_scene = false;  // the scene fits the LDS beside the stacks (commit_scene; option "lds_scene" = 0 overrides)
-    DTexture* textures = nullptr;
-    std::vector<uint8_t*> texture_data;
-    uint32_t n_textures = 0;
-    uint32_t stack_entries = 1;
-    bool stack_wide = false, stack_must_wide = false;
-    rt_camera_uniform camera{};
-    int count_tests = 0;
-    uint32_t last_launch[4] = {0, 0, 0, 0};  // rt_last_launch (entries 4 and 5 are computed when asked)
-    uint32_t frame_group_forced = 0, last_frame_group = 1;  // rt_test_frame_group (0: rt2::frame_group_for decides)
-    // The terminal skip (RenderArgs::terminal_dark): what rt2::terminal_skip_scene said of the head of the last upload /
-    // update / refit, the switch (rt_test_terminal_skip: the test library's) and the mask of the last render launch.
-    rt2::TerminalScene terminal;
-    bool terminal_skip_on = true;
-    uint32_t last_terminal_dark = 0;
-    bool fixed_switches_on = true;           // rt_test_fixed_switches (the test library's): false keeps every launch on the general kernels
-    bool queues_noted = false;               // the note about GPU_MAX_HW_QUEUES has been left in `err` once
-    std::string err;
-};
+#include "rt_handle.h"  // (the handle, the launch declarations and what the four units of the ABI share)
 
 namespace {
 
@@ -292,11 +43,15 @@ int hw_queues_requested() {
 }
 thread_local std::string g_err;
 
+}  // namespace
+namespace rth {
 int fail(rt_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
     g_err = msg;
     return code;
 }
+}  // namespace rth
+namespace {
 
 // bytes of device memory the handle holds on its own initiative (what option "max_device_mb" bounds)
 size_t optional_bytes(const rt_handle* h) {
@@ -309,26 +64,13 @@ size_t optional_bytes(const rt_handle* h) {
     }
     return b;
 }
+}  // namespace
+namespace rth {
 // may the handle take `extra` more bytes (after giving back `freed` of what it holds)?
-bool fits_cap(const rt_handle* h, size_t extra, size_t freed = 0) {
+bool fits_cap(const rt_handle* h, size_t extra, size_t freed) {
     if (h->opt.max_device_mb == 0) return true;
     const size_t held = optional_bytes(h);
     return (held > freed ? held - freed : 0) + extra <= h->opt.max_device_bytes();
-}
-
-#define HIP_TRY(h, expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(h, RT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-void free_dev(T*& p) {
-    if (p) {
-        (void)hipFree(p);
-        p = nullptr;
-    }
 }
 
 // A device buffer of `have` elements of `each` bytes is replaced by one of `need`: free, hipMalloc, record the size (0
@@ -341,13 +83,8 @@ int replace_dev(rt_handle* h, void** p, size_t& have, size_t need, size_t each) 
     have = need;
     return RT_OK;
 }
-// Grow a device buffer that only the launches on `reader` read: synchronise them, then replace it.
-template <typename T>
-int regrow(rt_handle* h, T*& p, size_t& have, size_t need, hipStream_t reader) {
-    if (have >= need) return RT_OK;
-    HIP_TRY(h, hipStreamSynchronize(reader));
-    return replace_dev(h, (void**)&p, have, need, sizeof(T));
-}
+}  // namespace rth
+namespace {
 
 // (host/launch_options.h repeats these figures of rt_device.h)
 static_assert(rt2::BLOCKS_PER_CU == BLOCKS_PER_CU && rt2::WAVES_PER_BLOCK == WAVES_PER_BLOCK && rt2::MAX_BATCH_FRAMES == RT_MAX_BATCH_FRAMES, "");
@@ -400,14 +137,6 @@ void free_textures(rt_handle* h) {
     h->texture_data.clear();
     free_dev(h->textures);
     h->n_textures = 0;
-}
-
-template <typename T>
-int upload(rt_handle* h, T*& dst, const T* src, size_t n) {
-    size_t bytes = (n ? n : 1) * sizeof(T);
-    HIP_TRY(h, hipMalloc((void**)&dst, bytes));
-    if (n) HIP_TRY(h, hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    return RT_OK;
 }
 
 }  // namespace
@@ -577,6 +306,8 @@ void commit_scene(rt_handle* h, const rt_camera_uniform& camera) {
     invalidate_primary_tables(h);  // (the tables hold hits: a function of the scene)
 }
 
+}  // namespace
+namespace rth {
 // Every launch enqueued so far on any of the handle's streams is complete (they all may read the blob).
 int drain_streams(rt_handle* h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -584,6 +315,8 @@ int drain_streams(rt_handle* h) {
         if (ps.stream) HIP_TRY(h, hipStreamSynchronize(ps.stream));
     return RT_OK;
 }
+}  // namespace rth
+namespace {
 
 // Where rt_update_instances / rt_refit_triangles (`who`) write the head of `lay`, once every launch that may read the blob
 // is complete (the streams are drained): the blob itself while the head keeps its size; else a new blob, allocated before
@@ -905,7 +638,7 @@ int rt_refit_triangles(rt_handle* h, const rt_packed_triangle* triangles, uint32
 
 // rt_render_multi (device-to-device transport): the root may still be copying this handle's previous frame out of
 // h->image.  Everything that writes, rebinds or reads the image on the handle's stream waits for that copy first.
-static int wait_pending_copy(rt_handle* h) {
+extern "C++" int rth::wait_pending_copy(rt_handle* h) {
     if (h->multi_copy_pending) {
         HIP_TRY(h, hipStreamWaitEvent(h->stream, h->multi_copied, 0));
         h->multi_copy_pending = false;
@@ -1002,7 +735,7 @@ static int wavefront_run(rt_handle*, const RenderArgs&, const WavefrontPlan&) { 
 // The scene- and option-dependent part of a launch's arguments: the scene, its item list and stack sizing, and which
 // instantiation the kernels take (scene in LDS, many-mesh, SIMPLE).  render_impl launches with these, and so does the
 // test library's per-ray probe (rt_test_intersect), which therefore walks exactly what a render walks.
-static void scene_args(const rt_handle* h, RenderArgs& a) {
+extern "C++" void rth::scene_args(const rt_handle* h, RenderArgs& a) {
     a.blob = h->blob;
     a.lay = h->inst.lay;
     // (an explicitly requested deferred-walk sequence -- option "sort_rounds" > 0, tests -- reads the scene in place: the
@@ -2004,633 +1737,14 @@ int rt_read_multi_frame(rt_handle* root, float* rgba32f_out, size_t bytes) {
     return RT_OK;
 }
 
-// ---- ray queries (include/rt_abi.h: rt_intersect_rays, rt_occluded_rays, rt_pick; rt_queries.inl: rt_query_kernel) ----
-// A query launch takes the arguments a render of the scene takes (scene_args), no pixel memo, and the render's
-// persistent grid (workgroups that fit the CUs' LDS).  It reads nothing but the scene and writes nothing but its output:
-// the image, the tables, the pipeline slots and the counters are not touched.
-static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 64, "rt_ray / rt_hit layout");
-
-// The arguments of a launch on the scene outside a render (queries, rt_pick, rt_render_gbuffer, the test probe): what a
-// render of the scene takes (scene_args), the handle's camera, and the caller's frame parameters or none.
-static RenderArgs query_args(const rt_handle* h, const rt_params* params) {
-    RenderArgs a{};
-    scene_args(h, a);
-    a.params = params ? *params : rt_params{};
-    a.camera = h->camera;
-    return a;
-}
-
 // Device memory a host-memory call may stage through: at most 64 MB, within what option max_device_mb leaves.
-static size_t staging_room(const rt_handle* h) {
+extern "C++" size_t rth::staging_room(const rt_handle* h) {
     size_t room = (size_t)64 << 20;
     if (h->opt.max_device_mb != 0) {
         const size_t held = optional_bytes(h);
         room = std::min(room, h->opt.max_device_bytes() > held ? h->opt.max_device_bytes() - held : 0);
     }
     return room;
-}
-
-// The loop of a host-memory call (the ray queries, rt_render_gbuffer, rt_radiance_rays): one temporary device buffer of
-// `bytes` (what_for: its name in the out-of-memory message), then step(buf, i0, m, what) for the chunks [i0, i0 + m) of the
-// call's n items.  A step queues its chunk's copies and launch on the handle's stream; when one of them fails it names it in
-// `what` and returns its error.  The stream is drained after every chunk -- the buffer is used again, and the results are on
-// the host when the call returns -- and before the buffer is freed, whatever happened.
-extern "C++" {
-template <class Step>
-static int staged_chunks(rt_handle* h, size_t bytes, uint64_t n, uint64_t chunk, const char* what_for, Step&& step) {
-    auto hip_fail = [&](const char* what, hipError_t e) { return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
-    uint8_t* buf = nullptr;
-    hipError_t e = hipMalloc((void**)&buf, bytes);
-    if (e != hipSuccess)
-        return e == hipErrorOutOfMemory ? fail(h, RT_ERR_OUT_OF_MEMORY, std::string("no device memory for ") + what_for) : hip_fail("hipMalloc", e);
-    int rc = RT_OK;
-    for (uint64_t i0 = 0; rc == RT_OK && i0 < n; i0 += chunk) {
-        const char* what = "hipStreamSynchronize";
-        e = step(buf, i0, std::min<uint64_t>(chunk, n - i0), what);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(what, e);
-    }
-    if (rc != RT_OK) (void)hipStreamSynchronize(h->stream);  // (nothing may still use the buffer when it is freed)
-    free_dev(buf);
-    return rc;
-}
-}  // extern "C++" (a template among the C entry points)
-
-// out_bytes: bytes of output per ray (sizeof(rt_hit) or 4)
-static int query_impl(rt_handle* h, const rt_ray* rays, uint64_t n, void* out, size_t out_bytes, int flags, bool any) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    const int known = RT_QUERY_HOST_MEMORY | (any ? RT_QUERY_PRUNE_TMAX : 0);
-    if (flags & ~known) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    if (n == 0) return RT_OK;
-    if (!rays || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (n > 0x7fffffffull) return fail(h, RT_ERR_CAPACITY, "more than 2^31 - 1 rays");
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    const bool host = (flags & RT_QUERY_HOST_MEMORY) != 0, prune = (flags & RT_QUERY_PRUNE_TMAX) != 0;
-    if (!host && (((uintptr_t)rays & 15u) != 0u || ((uintptr_t)out & (out_bytes == 4 ? 3u : 15u)) != 0u))
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "device rays / results not aligned (16 bytes; 4 for occlusion flags)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const RenderArgs a = query_args(h, nullptr);
-    const uint32_t blocks = rt2::persistent_blocks_for(h->opt, render_lds_bytes(a));
-    if (!host) {
-        HIP_TRY(h, launch_query(a, rays, n, out, any, prune, blocks, h->compute_units, h->stream));
-        return RT_OK;
-    }
-    // host memory: chunks of at most 64 MB of device memory (rays, then results), within option max_device_mb
-    const size_t per_ray = sizeof(rt_ray) + out_bytes;
-    const uint64_t chunk = std::min<uint64_t>(n, staging_room(h) / per_ray);
-    if (chunk == 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for a query's staging buffers");
-    return staged_chunks(h, chunk * per_ray, n, chunk, "a query's staging buffers", [&](uint8_t* buf, uint64_t i0, uint64_t m, const char*& what) {
-        uint8_t* d_out = buf + chunk * sizeof(rt_ray);
-        hipError_t e = hipSuccess;
-        if (what = "hipMemcpyAsync", (e = hipMemcpyAsync(buf, rays + i0, m * sizeof(rt_ray), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
-        if (what = "launch_query", (e = launch_query(a, buf, m, d_out, any, prune, blocks, h->compute_units, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        return hipMemcpyAsync(static_cast<uint8_t*>(out) + i0 * out_bytes, d_out, m * out_bytes, hipMemcpyDeviceToHost, h->stream);
-    });
-}
-
-int rt_intersect_rays(rt_handle* h, const rt_ray* rays, uint64_t n, rt_hit* hits, int flags) {
-    return query_impl(h, rays, n, hits, sizeof(rt_hit), flags, false);
-}
-
-int rt_occluded_rays(rt_handle* h, const rt_ray* rays, uint64_t n, uint32_t* occluded, int flags) {
-    return query_impl(h, rays, n, occluded, sizeof(uint32_t), flags, true);
-}
-
-int rt_pick(rt_handle* h, const rt_params* params, uint32_t x, uint32_t y, rt_hit* hit) {
-    if (!h || !params || !hit) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (x >= params->width || y >= params->height) return fail(h, RT_ERR_INVALID_ARGUMENT, "texel outside the frame");
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const RenderArgs a = query_args(h, params);
-    float4* d = nullptr;  // one rt_ray, then one rt_hit
-    HIP_TRY(h, hipMalloc((void**)&d, sizeof(rt_ray) + sizeof(rt_hit)));
-    hipError_t e = launch_pick_ray(a, x, y, d, h->stream);
-    if (e == hipSuccess) e = launch_query(a, d, 1, d + 2, false, false, 1, 1, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hit, d + 2, sizeof(rt_hit), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e2 = hipStreamSynchronize(h->stream);
-    free_dev(d);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(h, RT_ERR_DEVICE, std::string("rt_pick: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
-// ---- first-hit buffers of a frame (include/rt_abi.h: rt_render_gbuffer; rt_queries.inl: rt_gbuffer_kernel) ----
-// Launched like a query: the arguments a render of the scene takes, nothing read but the scene and nothing written but
-// the caller's planes.
-int rt_render_gbuffer(rt_handle* h, const rt_params* params, const rt_gbuffer* out, int flags) {
-    if (!h || !params || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (out->struct_bytes != sizeof(rt_gbuffer)) return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_gbuffer.struct_bytes is not sizeof(rt_gbuffer)");
-    if (out->_p0 != 0u) return fail(h, RT_ERR_INVALID_ARGUMENT, "rt_gbuffer._p0 must be 0");
-    if (flags & ~RT_GBUFFER_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const uint32_t W = params->width, H = params->height;
-    if (W == 0u || H == 0u) return fail(h, RT_ERR_INVALID_ARGUMENT, "zero width or height");
-    if ((uint64_t)W * H > 0x7fffffffull) return fail(h, RT_ERR_CAPACITY, "more than 2^31 - 1 texels");
-    // the planes in struct order: pointer, bytes per texel, alignment of a device pointer
-    void* const ptr[11] = {out->depth, out->dir, out->point, out->normal, out->bary, out->texcoord, out->albedo, out->emission,
-                           out->object, out->primitive, out->flags};
-    static const uint32_t bytes[11] = {4, 12, 12, 12, 8, 8, 16, 16, 4, 4, 1}, align[11] = {4, 4, 4, 4, 4, 4, 16, 16, 4, 4, 1};
-    static const char* const names[11] = {"depth", "dir", "point", "normal", "bary", "texcoord", "albedo", "emission", "object",
-                                          "primitive", "flags"};
-    size_t per_texel = 0;
-    for (int c = 0; c < 11; ++c) per_texel += ptr[c] ? bytes[c] : 0u;
-    if (per_texel == 0) return RT_OK;   // no plane asked for
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    const bool host = (flags & RT_GBUFFER_HOST_MEMORY) != 0;
-    if (!host)
-        for (int c = 0; c < 11; ++c)
-            if (ptr[c] && ((uintptr_t)ptr[c] & (align[c] - 1u)) != 0u)
-                return fail(h, RT_ERR_INVALID_ARGUMENT, std::string("device plane ") + names[c] + " is not aligned to " + std::to_string(align[c]) + " bytes");
-    HIP_TRY(h, hipSetDevice(h->device));
-    RenderArgs a = query_args(h, nullptr);
-    a.params.width = W;
-    a.params.height = H;
-    GBufferArgs g{};
-    g.width = W;
-    g.height = H;
-    auto bind = [&](void* const p[11]) {
-        g.depth = (float*)p[0]; g.dir = (float*)p[1]; g.point = (float*)p[2]; g.normal = (float*)p[3]; g.bary = (float*)p[4];
-        g.texcoord = (float*)p[5]; g.albedo = (float4*)p[6]; g.emission = (float4*)p[7]; g.object = (uint32_t*)p[8];
-        g.primitive = (uint32_t*)p[9]; g.flags = (uint8_t*)p[10];
-    };
-    if (!host) {
-        g.row0 = 0;
-        g.rows = H;
-        bind(ptr);
-        HIP_TRY(h, launch_gbuffer(a, g, h->stream));
-        return RT_OK;
-    }
-    // host memory: bands of whole rows through one temporary device buffer of at most 64 MB, within option max_device_mb;
-    // each plane's part of it starts at a multiple of 256 bytes (11 x 256 bytes of slack at most)
-    const size_t slack = 11u * 256u, room = staging_room(h);
-    const size_t row_bytes = (size_t)W * per_texel;
-    const uint32_t band = room > slack ? (uint32_t)std::min<uint64_t>(H, (room - slack) / row_bytes) : 0u;
-    if (band == 0u) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for one row of the G-buffer's staging planes");
-    size_t plane_off[11] = {};
-    size_t off = 0;
-    for (int c = 0; c < 11; ++c) {
-        if (!ptr[c]) continue;
-        plane_off[c] = off;
-        off = (off + (size_t)band * W * bytes[c] + 255u) & ~(size_t)255u;
-    }
-    return staged_chunks(h, off, H, band, "the G-buffer's staging planes", [&](uint8_t* buf, uint64_t r0, uint64_t rows, const char*& what) {
-        void* d_ptr[11] = {};
-        for (int c = 0; c < 11; ++c)
-            if (ptr[c]) d_ptr[c] = buf + plane_off[c];
-        bind(d_ptr);
-        g.row0 = (uint32_t)r0;
-        g.rows = (uint32_t)rows;
-        hipError_t e = hipSuccess;
-        if (what = "launch_gbuffer", (e = launch_gbuffer(a, g, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        for (int c = 0; c < 11 && e == hipSuccess; ++c) {
-            if (!ptr[c]) continue;
-            const size_t row = (size_t)W * bytes[c];
-            e = hipMemcpyAsync(static_cast<uint8_t*>(ptr[c]) + r0 * row, d_ptr[c], rows * row, hipMemcpyDeviceToHost, h->stream);
-        }
-        return e;
-    });
-}
-
-// ---- radiance along rays the host gives (include/rt_abi.h: rt_radiance_rays; rt_queries.inl: rt_radiance_kernel) ----
-// Launched like a query: the arguments a render of the scene takes, the caller's bounces, samples and skybox, nothing read
-// but the scene and the rays and nothing written but the caller's output (and a launch counter of the handle's ring).
-static_assert(sizeof(rt_path_ray) == 32, "rt_path_ray layout");
-
-int rt_radiance_rays(rt_handle* h, const rt_params* params, const rt_path_ray* rays, uint64_t n, float* rgba32f_out, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_RADIANCE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    if (n == 0) return RT_OK;
-    if (!params || !rays || !rgba32f_out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (params->number_of_bounces < 0) return fail(h, RT_ERR_INVALID_ARGUMENT, "number_of_bounces must be >= 0");
-    if (params->rays_per_pixel < 1) return fail(h, RT_ERR_INVALID_ARGUMENT, "rays_per_pixel must be >= 1");
-    if (n > 0x7fffffffull) return fail(h, RT_ERR_CAPACITY, "more than 2^31 - 1 rays");
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    const bool host = (flags & RT_RADIANCE_HOST_MEMORY) != 0;
-    if (!host && ((((uintptr_t)rays) | ((uintptr_t)rgba32f_out)) & 15u) != 0u)
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "device rays / results not aligned (16 bytes)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    RenderArgs a = query_args(h, nullptr);
-    a.params.number_of_bounces = params->number_of_bounces;
-    a.params.rays_per_pixel = params->rays_per_pixel;
-    a.params.skybox = params->skybox;
-    a.spp_reciprocal = (params->rays_per_pixel & (params->rays_per_pixel - 1)) == 0 ? 1.0f / (float)params->rays_per_pixel : 0.0f;  // (frame_constants)
-    // SIMPLE from the scene alone: the rays are the caller's, the handle's camera has no part in them
-    a.simple = (h->opt.specialise && h->inst.plain_materials) ? 1u : 0u;
-    // The first hit of a ray serves all its samples from the lane's LDS memo, wherever a workgroup's LDS can hold one (a
-    // ray of one sample has nothing to reuse); with it path_end's and the pre-step's shortcuts on that memo.
-    a.pixel_cache = params->rays_per_pixel > 1 ? 1u : 0u;
-    if (a.pixel_cache && render_lds_bytes(a) > rt2::CU_LDS_BYTES) a.pixel_cache = 0u;
-    a.fast_miss = a.roulette_skip = a.pixel_cache;
-    uint32_t* next_ray = nullptr;
-    if (!host) {
-        HIP_TRY(h, h->work.next(h->stream, next_ray));
-        HIP_TRY(h, launch_radiance(a, rays, (uint32_t)n, rgba32f_out, next_ray, h->compute_units, h->stream));
-        return RT_OK;
-    }
-    // host memory: chunks of at most 64 MB of device memory (rays, then results: 48 bytes per ray), within option max_device_mb
-    const size_t per_ray = sizeof(rt_path_ray) + sizeof(float4);
-    const uint64_t chunk = std::min<uint64_t>(n, staging_room(h) / per_ray);
-    if (chunk == 0) return fail(h, RT_ERR_OUT_OF_MEMORY, "option max_device_mb leaves no room for a radiance call's staging buffers");
-    return staged_chunks(h, chunk * per_ray, n, chunk, "a radiance call's staging buffers", [&](uint8_t* buf, uint64_t i0, uint64_t m, const char*& what) {
-        uint8_t* d_out = buf + chunk * sizeof(rt_path_ray);
-        hipError_t e = hipSuccess;
-        if (what = "hipMemcpyAsync", (e = hipMemcpyAsync(buf, rays + i0, m * sizeof(rt_path_ray), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
-        if (what = "CounterRing::next", (e = h->work.next(h->stream, next_ray)) != hipSuccess) return e;
-        if (what = "launch_radiance", (e = launch_radiance(a, buf, (uint32_t)m, d_out, next_ray, h->compute_units, h->stream)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        return hipMemcpyAsync(rgba32f_out + 4 * i0, d_out, m * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
-    });
-}
-
-// ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
-// rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming, rt_upsample,
-// rt_display, rt_auto_exposure ----
-// Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
-// and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
-// arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
-// temporary device buffer on host memory.
-
-// One plane of a frame pass: read from `in`, written to `out`, or both -- an output that takes its input's place in the
-// staging buffer, as `out` takes `color`'s.  An entry with neither pointer is absent and takes no room.
-struct FramePlane {
-    const void* in;
-    void* out;
-    size_t bytes;
-};
-
-extern "C++" {
-// The staging buffer of the host-memory path: the planes that are there in table order, each at a multiple of 256 bytes.
-template <int N>
-static size_t staged_bytes(const FramePlane (&planes)[N], size_t* offsets = nullptr) {
-    size_t total = 0;
-    for (int c = 0; c < N; ++c) {
-        if (!planes[c].in && !planes[c].out) continue;
-        if (offsets) offsets[c] = total;
-        total = (total + planes[c].bytes + 255u) & ~(size_t)255u;
-    }
-    return total;
-}
-
-// launch(in, out) on the planes of the table, in[c] / out[c] null for an absent plane.  Device memory: the table's own
-// pointers, and the launch is queued.  Host memory: every plane whole through one temporary device buffer within option
-// max_device_mb (a pass may read any row: no bands) -- the inputs copied in, in[c] == out[c] the staged plane, the outputs
-// copied out, all in table order, and the stream drained (staged_chunks).
-template <int N, class Launch>
-static int frame_call(rt_handle* h, bool host, const FramePlane (&planes)[N], const char* what_for, const char* launch_name, Launch&& launch) {
-    const void* in[N] = {};
-    void* out[N] = {};
-    if (!host) {
-        for (int c = 0; c < N; ++c) in[c] = planes[c].in, out[c] = planes[c].out;
-        const hipError_t e = launch(in, out);
-        return e == hipSuccess ? RT_OK : fail(h, RT_ERR_DEVICE, std::string(launch_name) + "(a, h->stream): " + hipGetErrorString(e));
-    }
-    size_t offsets[N] = {};
-    const size_t total = staged_bytes(planes, offsets);
-    if (!fits_cap(h, total)) return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("option max_device_mb leaves no room for ") + what_for);
-    return staged_chunks(h, total, 1, 1, what_for, [&](uint8_t* buf, uint64_t, uint64_t, const char*& what) {
-        hipError_t e = hipSuccess;
-        what = "hipMemcpyAsync";
-        for (int c = 0; c < N && e == hipSuccess; ++c) {
-            if (!planes[c].in && !planes[c].out) continue;
-            in[c] = out[c] = buf + offsets[c];
-            if (planes[c].in) e = hipMemcpyAsync(out[c], planes[c].in, planes[c].bytes, hipMemcpyHostToDevice, h->stream);
-        }
-        if (e != hipSuccess) return e;
-        if (what = launch_name, (e = launch(in, out)) != hipSuccess) return e;
-        what = "hipMemcpyAsync";
-        for (int c = 0; c < N && e == hipSuccess; ++c)
-            if (planes[c].out) e = hipMemcpyAsync(planes[c].out, out[c], planes[c].bytes, hipMemcpyDeviceToHost, h->stream);
-        return e;
-    });
-}
-
-// A scratch the handle keeps between calls (`what`: its name in the messages), grown to `need` bytes on demand within option
-// max_device_mb, together with the `staging` bytes the call is about to take (what_for: their name).  A call whose scratch
-// is large enough checks its staging alone -- on device memory too, where that is 0 bytes: such a call is refused once the
-// handle holds more than the cap, while the passes without a scratch (rt_temporal_accumulate, rt_adaptive_merge) go on.
-template <class T>
-static int grow_scratch(rt_handle* h, T*& scratch, size_t& held, size_t need, size_t staging, const char* what, const char* what_for) {
-    auto no_room = [&](const char* for_what) { return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("option max_device_mb leaves no room for ") + for_what); };
-    if (held >= need) return fits_cap(h, staging) ? RT_OK : no_room(what_for);
-    if (!fits_cap(h, need + staging, held)) return no_room(what);
-    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (an earlier call may still use the old scratch)
-    free_dev(scratch);
-    held = 0;
-    const hipError_t e = hipMalloc((void**)&scratch, need);
-    if (e == hipErrorOutOfMemory) return fail(h, RT_ERR_OUT_OF_MEMORY, std::string("no device memory for ") + what);
-    HIP_TRY(h, e);
-    held = need;
-    return RT_OK;
-}
-
-// A _host entry point: the host unit's restatement, its error kept for rt_last_error(NULL).
-template <class Desc>
-static int host_call(int (*restatement)(const Desc*, std::string&), const Desc* desc) {
-    try {
-        std::string err;
-        const int rc = restatement(desc, err);
-        return rc == RT_OK ? RT_OK : fail(nullptr, rc, err);
-    } catch (const std::bad_alloc&) {
-        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-    }
-}
-}  // extern "C++" (templates among the C entry points)
-
-// The colour plane of a pass: the caller's, or for NULL (device memory only: the checks refuse it elsewhere) the handle's
-// image, which must hold the frame.
-static int frame_color(rt_handle* h, const float*& color, size_t texels) {
-    if (color) return RT_OK;
-    if (texels > h->image_texels) return fail(h, RT_ERR_CAPACITY, "the frame has more texels than the image (color is NULL)");
-    color = reinterpret_cast<const float*>(h->image);
-    return RT_OK;
-}
-
-// Before a pass on device memory that reads `color` and writes `out`: a copy of the image that is still under way is
-// waited for when either is the image, and the image counts as changed when `out` lies in it, as by rt_write_image.
-static int image_access(rt_handle* h, const float* color, const float* out) {
-    const float* image = reinterpret_cast<const float*>(h->image);
-    const bool out_is_image = out >= image && out < image + 4 * h->image_texels;
-    if (color == image || out_is_image) {
-        if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-    }
-    if (out_is_image) h->generation += 1;
-    return RT_OK;
-}
-
-int rt_denoise_host(const rt_denoise_desc* desc) { return host_call(rt2::denoise_host, desc); }
-int rt_denoise_variance_host(const rt_vdenoise_desc* desc) { return host_call(rt2::vdenoise_host, desc); }
-int rt_luminance_moments_host(const rt_vdenoise_desc* desc) { return host_call(rt2::luminance_moments_host, desc); }
-int rt_adaptive_plan_host(const rt_adaptive_plan_desc* desc) { return host_call(rt2::adaptive_plan_host, desc); }
-int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) { return host_call(rt2::adaptive_merge_host, desc); }
-int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call(rt2::temporal_host, desc); }
-int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc) { return host_call(rt2::temporal_motion_host, desc); }
-int rt_temporal_accumulate_deforming_host(const rt_temporal_deform_desc* desc) { return host_call(rt2::temporal_deform_host, desc); }
-int rt_upsample_host(const rt_upsample_desc* desc) { return host_call(rt2::upsample_host, desc); }
-int rt_display_host(const rt_display_desc* desc) { return host_call(rt2::display_host, desc); }
-int rt_auto_exposure_host(const rt_auto_exposure_desc* desc) { return host_call(rt2::auto_exposure_host, desc); }
-
-// ---- denoising a rendered frame (include/rt_abi.h: rt_denoise; rt_denoise.hip; host/denoise.cpp) ----
-static const char* const DENOISE_SCRATCH = "the denoiser's scratch images";
-static const char* const DENOISE_STAGING = "the denoiser's staging planes";
-
-int rt_denoise(rt_handle* h, const rt_denoise_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_DENOISE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_DENOISE_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::denoise_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const FramePlane planes[5] = {{color, desc->out, texels * 16u}, {desc->normal, nullptr, texels * 12u}, {desc->point, nullptr, texels * 12u},
-                                  {desc->albedo, nullptr, texels * 16u}, {desc->emission, nullptr, texels * 16u}};
-    if (int rc = grow_scratch(h, h->denoise_scratch, h->denoise_scratch_bytes, texels * 64u, host ? staged_bytes(planes) : 0u,
-                              DENOISE_SCRATCH, DENOISE_STAGING); rc != RT_OK) return rc;
-    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
-    DenoiseArgs a{};
-    a.width = desc->width;
-    a.height = desc->height;
-    a.iterations = (int)desc->iterations;
-    a.sigma_color = desc->sigma_color;
-    a.sigma_normal = desc->sigma_normal;
-    a.sigma_point = desc->sigma_point;
-    a.guide = h->denoise_scratch;
-    a.ping[0] = h->denoise_scratch + 2 * texels;
-    a.ping[1] = h->denoise_scratch + 3 * texels;
-    return frame_call(h, host, planes, DENOISE_STAGING, "launch_denoise", [&](const void* const* in, void* const* out) {
-        a.color = (const float*)in[0]; a.out = (float*)out[0];
-        a.normal = (const float*)in[1]; a.point = (const float*)in[2]; a.albedo = (const float*)in[3]; a.emission = (const float*)in[4];
-        return launch_denoise(a, h->stream);
-    });
-}
-
-// ---- variance-guided denoising (include/rt_abi.h: rt_denoise_variance, rt_luminance_moments; rt_vdenoise.hip;
-// host/vdenoise.cpp) ----
-// Launched in rt_denoise's scratch: each call of either rewrites every word of it that it later reads.
-// The two entry points: moments_only is rt_luminance_moments, which needs no scratch and takes fewer planes.
-static int vdenoise_call(rt_handle* h, const rt_vdenoise_desc* desc, int flags, bool moments_only) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_VDENOISE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_VDENOISE_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::vdenoise_check(desc, moments_only, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    // the first five are rt_denoise's
-    const bool with_moments = !moments_only && desc->moments, with_variance = !moments_only && desc->out_variance;
-    const FramePlane planes[8] = {{color, desc->out, texels * 16u}, {desc->normal, nullptr, texels * 12u}, {desc->point, nullptr, texels * 12u},
-                                  {desc->albedo, nullptr, texels * 16u}, {desc->emission, nullptr, texels * 16u},
-                                  {with_moments ? desc->moments : nullptr, nullptr, texels * 16u},
-                                  {with_moments ? desc->history : nullptr, nullptr, texels * 4u},
-                                  {nullptr, with_variance ? desc->out_variance : nullptr, texels * 4u}};
-    if (int rc = grow_scratch(h, h->denoise_scratch, h->denoise_scratch_bytes, moments_only ? 0u : texels * 64u,
-                              host ? staged_bytes(planes) : 0u, DENOISE_SCRATCH, DENOISE_STAGING); rc != RT_OK) return rc;
-    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
-    VDenoiseArgs a{};
-    a.width = desc->width;
-    a.height = desc->height;
-    if (!moments_only) {
-        a.iterations = (int)desc->iterations;
-        a.sigma_luminance = desc->sigma_luminance;
-        a.sigma_normal = desc->sigma_normal;
-        a.sigma_point = desc->sigma_point;
-        a.min_history = desc->min_history;
-        a.guide = h->denoise_scratch;
-        a.ping[0] = h->denoise_scratch + 2 * texels;
-        a.ping[1] = h->denoise_scratch + 3 * texels;
-    }
-    return frame_call(h, host, planes, DENOISE_STAGING, moments_only ? "launch_luminance_moments" : "launch_vdenoise",
-                      [&](const void* const* in, void* const* out) {
-        a.color = (const float*)in[0]; a.out = (float*)out[0];
-        a.normal = (const float*)in[1]; a.point = (const float*)in[2]; a.albedo = (const float*)in[3]; a.emission = (const float*)in[4];
-        a.moments = (const float*)in[5]; a.history = (const float*)in[6]; a.out_variance = (float*)out[7];
-        return moments_only ? launch_luminance_moments(a, h->stream) : launch_vdenoise(a, h->stream);
-    });
-}
-
-int rt_denoise_variance(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, false); }
-int rt_luminance_moments(rt_handle* h, const rt_vdenoise_desc* desc, int flags) { return vdenoise_call(h, desc, flags, true); }
-
-// ---- adaptive sampling (include/rt_abi.h: rt_adaptive_plan, rt_adaptive_merge; rt_adaptive.hip; host/adaptive.cpp) ----
-int rt_adaptive_plan(rt_handle* h, const rt_adaptive_plan_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_ADAPTIVE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_ADAPTIVE_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::adaptive_plan_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height, budget = desc->budget;
-    HIP_TRY(h, hipSetDevice(h->device));
-    static const char* const what_for = "the adaptive plan's staging planes";
-    const FramePlane planes[6] = {{desc->variance, nullptr, texels * 4u}, {desc->dir, nullptr, texels * 12u}, {nullptr, desc->counts, texels * 4u},
-                                  {nullptr, desc->offsets, texels * 4u}, {nullptr, desc->rays, budget * sizeof(rt_path_ray)},
-                                  {nullptr, desc->totals, 16u}};
-    if (int rc = grow_scratch(h, h->adaptive_scratch, h->adaptive_scratch_bytes, adaptive_scratch_bytes(texels),
-                              host ? staged_bytes(planes) : 0u, "the adaptive plan's scratch", what_for); rc != RT_OK) return rc;
-    AdaptivePlanArgs a{};
-    a.width = desc->width; a.height = desc->height; a.budget = desc->budget;
-    a.min_samples = desc->min_samples; a.max_samples = desc->max_samples; a.first_frame = desc->first_frame;
-    for (int k = 0; k < 3; ++k) a.origin[k] = desc->origin[k];
-    a.scratch = h->adaptive_scratch;
-    return frame_call(h, host, planes, what_for, "launch_adaptive_plan", [&](const void* const* in, void* const* out) {
-        a.variance = (const float*)in[0]; a.dir = (const float*)in[1];
-        a.counts = (uint32_t*)out[2]; a.offsets = (uint32_t*)out[3]; a.rays = out[4]; a.totals = (uint32_t*)out[5];
-        return launch_adaptive_plan(a, h->stream);
-    });
-}
-
-int rt_adaptive_merge(rt_handle* h, const rt_adaptive_merge_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_ADAPTIVE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_ADAPTIVE_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::adaptive_merge_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height, budget = desc->budget;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
-    // the outputs take the places of color, history and moments
-    const FramePlane planes[7] = {{desc->radiance, nullptr, budget * 16u}, {desc->counts, nullptr, texels * 4u}, {desc->offsets, nullptr, texels * 4u},
-                                  {color, desc->out, texels * 16u}, {desc->history, desc->out_history, texels * 4u},
-                                  {desc->albedo, nullptr, texels * 16u}, {desc->moments, desc->out_moments, texels * 16u}};
-    AdaptiveMergeArgs a{};
-    a.width = desc->width; a.height = desc->height; a.budget = desc->budget; a.max_history = desc->max_history;
-    return frame_call(h, host, planes, "the adaptive merge's staging planes", "launch_adaptive_merge", [&](const void* const* in, void* const* out) {
-        a.radiance = (const float*)in[0]; a.counts = (const uint32_t*)in[1]; a.offsets = (const uint32_t*)in[2];
-        a.color = (const float*)in[3]; a.out = (float*)out[3]; a.history = (const float*)in[4]; a.out_history = (float*)out[4];
-        a.albedo = (const float*)in[5]; a.moments = (const float*)in[6]; a.out_moments = (float*)out[6];
-        return launch_adaptive_merge(a, h->stream);
-    });
-}
-
-// ---- temporal accumulation (include/rt_abi.h: rt_temporal_accumulate; rt_temporal.hip; host/temporal.cpp) ----
-// No scratch is kept.  The three calls are one: `desc` is the kind's desc, which the check widens (rt_temporal_api.h), and
-// the rows of a part the kind does not have -- the motion table (rt_temporal_accumulate_moving: one more input that is not
-// frame-shaped), the current G-buffer's primitive, bary and flags planes and the previous triangles
-// (rt_temporal_accumulate_deforming: a second one) -- are absent from the table and take no room.
-static int temporal_accumulate(rt_handle* h, const void* desc, rt2::TemporalKind kind, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_TEMPORAL_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_TEMPORAL_HOST_MEMORY) != 0;
-    std::string err;
-    rt_temporal_deform_desc d;
-    if (const int rc = rt2::temporal_check(desc, kind, true, host, d, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)d.width * d.height;
-    const float* color = d.color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, color, d.out); rc != RT_OK) return rc;
-    // `out` takes the colour plane's place
-    const FramePlane planes[16] = {{color, d.out, texels * 16u}, {d.point, nullptr, texels * 12u}, {d.normal, nullptr, texels * 12u},
-                                   {d.object, nullptr, texels * 4u}, {d.prev_color, nullptr, texels * 16u},
-                                   {d.prev_history, nullptr, texels * 4u}, {d.prev_point, nullptr, texels * 12u},
-                                   {d.prev_normal, nullptr, texels * 12u}, {d.prev_object, nullptr, texels * 4u},
-                                   {nullptr, d.out_history, texels * 4u}, {nullptr, d.motion, texels * 8u},
-                                   {d.motions, nullptr, (size_t)d.n_objects * sizeof(rt_object_motion)},
-                                   {d.primitive, nullptr, texels * 4u}, {d.bary, nullptr, texels * 8u}, {d.flags, nullptr, texels},
-                                   {d.prev_triangles, nullptr, (size_t)d.n_prev_triangles * sizeof(rt_packed_triangle)}};
-    static const char* const LAUNCH[3] = {"launch_temporal", "launch_temporal_motion", "launch_temporal_deform"};   // (the device error names the kind)
-    TemporalArgs a{};
-    a.call = rt2::temporal_call(d);
-    a.n_objects = d.n_objects;
-    a.tri_first = d.tri_first;
-    a.n_prev_triangles = d.n_prev_triangles;
-    return frame_call(h, host, planes, "the staging planes of temporal accumulation", LAUNCH[(int)kind], [&](const void* const* in, void* const* out) {
-        a.color = (const float*)in[0]; a.out = (float*)out[0]; a.point = (const float*)in[1]; a.normal = (const float*)in[2];
-        a.object = (const uint32_t*)in[3]; a.prev_color = (const float*)in[4]; a.prev_history = (const float*)in[5];
-        a.prev_point = (const float*)in[6]; a.prev_normal = (const float*)in[7]; a.prev_object = (const uint32_t*)in[8];
-        a.out_history = (float*)out[9]; a.motion = (float*)out[10]; a.motions = (const rttp::Motion*)in[11];
-        a.primitive = (const uint32_t*)in[12]; a.bary = (const float*)in[13]; a.flags = (const uint8_t*)in[14];
-        a.prev_triangles = (const rttp::Tri*)in[15];
-        return launch_temporal(a, kind, h->stream);
-    });
-}
-
-int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::PLAIN, flags); }
-int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::MOVING, flags); }
-int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::DEFORMING, flags); }
-
-// ---- guided upsampling (include/rt_abi.h: rt_upsample; rt_upsample.hip; host/upsample.cpp) ----
-// No scratch is kept.  The low frame's planes are inputs that are not frame-shaped with respect to the high frame: rows of
-// the table with their own sizes, like the motion table of rt_temporal_accumulate_moving.
-int rt_upsample(rt_handle* h, const rt_upsample_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_UPSAMPLE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_UPSAMPLE_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::upsample_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t lo = (size_t)desc->lo_width * desc->lo_height, texels = (size_t)desc->width * desc->height;
-    const float* lo_color = desc->lo_color;
-    if (int rc = frame_color(h, lo_color, lo); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, lo_color, desc->out); rc != RT_OK) return rc;
-    const FramePlane planes[13] = {{lo_color, nullptr, lo * 16u}, {desc->lo_point, nullptr, lo * 12u}, {desc->lo_normal, nullptr, lo * 12u},
-                                   {desc->lo_object, nullptr, lo * 4u}, {desc->lo_albedo, nullptr, lo * 16u},
-                                   {desc->depth, nullptr, texels * 4u}, {desc->point, nullptr, texels * 12u},
-                                   {desc->normal, nullptr, texels * 12u}, {desc->object, nullptr, texels * 4u},
-                                   {desc->albedo, nullptr, texels * 16u}, {desc->emission, nullptr, texels * 16u},
-                                   {nullptr, desc->out, texels * 16u}, {nullptr, desc->coverage, texels}};
-    UpsampleArgs a{};
-    a.call = rt2::upsample_call(*desc);
-    return frame_call(h, host, planes, "the staging planes of guided upsampling", "launch_upsample", [&](const void* const* in, void* const* out) {
-        a.lo_color = (const float*)in[0]; a.lo_point = (const float*)in[1]; a.lo_normal = (const float*)in[2];
-        a.lo_object = (const uint32_t*)in[3]; a.lo_albedo = (const float*)in[4]; a.depth = (const float*)in[5];
-        a.point = (const float*)in[6]; a.normal = (const float*)in[7]; a.object = (const uint32_t*)in[8];
-        a.albedo = (const float*)in[9]; a.emission = (const float*)in[10]; a.out = (float*)out[11]; a.coverage = (uint8_t*)out[12];
-        return launch_upsample(a, h->stream);
-    });
-}
-
-// ---- display frames (include/rt_abi.h: rt_display, rt_auto_exposure; rt_display.hip; host/display.cpp) ----
-// rt_display keeps no scratch; its one-float exposure_scale is a row of the table like any plane.
-int rt_display(rt_handle* h, const rt_display_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_DISPLAY_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_DISPLAY_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::display_check(desc, host ? rt2::DisplayPath::STAGED : rt2::DisplayPath::DEVICE, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = host ? RT_OK : image_access(h, color, reinterpret_cast<const float*>(desc->out)); rc != RT_OK) return rc;
-    const FramePlane planes[3] = {{color, nullptr, texels * 16u}, {desc->exposure_scale, nullptr, 4u}, {nullptr, desc->out, texels * 4u}};
-    DisplayArgs a{};
-    a.call = rt2::display_call(*desc);
-    return frame_call(h, host, planes, "the staging planes of the display pass", "launch_display", [&](const void* const* in, void* const* out) {
-        a.color = (const float*)in[0]; a.exposure_scale = (const float*)in[1]; a.out = (uint32_t*)out[2];
-        return launch_display(a, h->stream);
-    });
-}
-
-// The 1 KiB of global bins is the scratch the handle keeps; prev_scale, histogram and scale are rows of 4, 1024 and 4 bytes.
-int rt_auto_exposure(rt_handle* h, const rt_auto_exposure_desc* desc, int flags) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (flags & ~RT_AUTO_EXPOSURE_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    const bool host = (flags & RT_AUTO_EXPOSURE_HOST_MEMORY) != 0;
-    std::string err;
-    if (const int rc = rt2::auto_exposure_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
-    const size_t texels = (size_t)desc->width * desc->height;
-    const float* color = desc->color;
-    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    static const char* const what_for = "the exposure meter's staging planes";
-    const FramePlane planes[4] = {{color, nullptr, texels * 16u}, {desc->prev_scale, nullptr, 4u},
-                                  {nullptr, desc->histogram, rtdp::BINS * sizeof(uint32_t)}, {nullptr, desc->scale, 4u}};
-    if (int rc = grow_scratch(h, h->exposure_scratch, h->exposure_scratch_bytes, rtdp::BINS * sizeof(uint32_t),
-                              host ? staged_bytes(planes) : 0u, "the exposure meter's bins", what_for); rc != RT_OK) return rc;
-    if (int rc = host ? RT_OK : image_access(h, color, desc->scale); rc != RT_OK) return rc;
-    AutoExposureArgs a{};
-    a.call = rt2::auto_exposure_call(*desc);
-    a.bins = h->exposure_scratch;
-    return frame_call(h, host, planes, what_for, "launch_auto_exposure", [&](const void* const* in, void* const* out) {
-        a.color = (const float*)in[0]; a.prev_scale = (const float*)in[1]; a.histogram = (uint32_t*)out[2]; a.scale = (float*)out[3];
-        return launch_auto_exposure(a, h->stream);
-    });
 }
 
 int rt_synchronize(rt_handle* h) {
@@ -2857,554 +1971,6 @@ int rt_diag_read(rt_handle* h, unsigned long long* out64, int reset) {
     return RT_OK;
 }
 #endif
-
-#if RT_TEST_ENTRIES
-// The test entry points (include/rt_test_abi.h) are NOT part of the product library: they are compiled only with
-// -DRT_TEST_ENTRIES=1, into ray_tracer_2_amd/librt2_mi355x_test.so (ray_tracer_2_amd/build.py: build_test_library) --
-// the same sources and flags otherwise.
-// tests/test_gpu_device_units.py: evaluate the kernels' arithmetic building blocks on the device, element-wise over host arrays.
-int rt_test_device_units(rt_handle* h, int fn, const float* x, const float* y, float* out, uint64_t n) {
-    if (!h || !x || !y || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    const size_t bytes = (size_t)(n ? n : 1) * sizeof(float);
-    HIP_TRY(h, hipMalloc((void**)&dx, bytes));
-    HIP_TRY(h, hipMalloc((void**)&dy, bytes));
-    HIP_TRY(h, hipMalloc((void**)&dout, bytes));
-    HIP_TRY(h, hipMemcpyAsync(dx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dy, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, launch_units(fn, dx, dy, dout, n, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_dev(dx);
-    free_dev(dy);
-    free_dev(dout);
-    return RT_OK;
-}
-
-// tests/test_gpu_scene_edits.py: the scene blob as the kernels read it, its SceneLayout and its device address -- to
-// compare an updated handle with a fresh upload, and to see that an in-place update kept its allocation.
-int rt_test_scene_blob(rt_handle* h, void* out, uint64_t bytes, uint32_t layout_out[12], uint64_t* device_ptr) {
-    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    if (out && bytes < h->inst.lay.bytes) return fail(h, RT_ERR_INVALID_ARGUMENT, "output smaller than the blob");
-    static_assert(sizeof(SceneLayout) == 12 * sizeof(uint32_t), "SceneLayout is 12 words");
-    if (layout_out) memcpy(layout_out, &h->inst.lay, sizeof(SceneLayout));
-    if (device_ptr) *device_ptr = (uint64_t)(uintptr_t)h->blob;
-    if (out) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = drain_streams(h); rc != RT_OK) return rc;
-        HIP_TRY(h, hipMemcpy(out, h->blob, h->inst.lay.bytes, hipMemcpyDeviceToHost));
-    }
-    return RT_OK;
-}
-
-// tests/test_scene_pack_host.py, tests/test_gpu_scene_pack.py: the host packer on scene arrays, without a device -- both
-// phases as rt_upload_scene runs them, the blob assembled as the device would hold it (head, tail, zero padding), and the
-// instance phase run again on the same geometry facts, as rt_update_instances would.
-int rt_test_pack_scene(const rt_sphere* spheres, uint32_t n_spheres, const rt_mesh_uniform* meshes, uint32_t n_meshes,
-                       const rt_packed_triangle* triangles, uint32_t n_triangles, const rt_node* nodes, uint32_t n_nodes,
-                       const int32_t options[5], void* out, uint64_t bytes, uint32_t layout_out[12], uint32_t facts_out[RT_TEST_PACK_FACTS]) {
-    if (!options || (n_spheres && !spheres) || (n_meshes && !meshes) || (n_triangles && !triangles) || (n_nodes && !nodes))
-        return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null array with non-zero count");
-    try {
-        const rt2::PackOptions opt{options[0], options[1], options[2], options[3], options[4]};
-        SceneGeom g;
-        InstanceFacts s, again;
-        std::vector<rt2::Quad> head, head_again, tail;
-        std::string why;
-        int rc = rt2::pack_geometry(meshes, n_meshes, triangles, n_triangles, nodes, n_nodes, g, tail, why);
-        if (rc == RT_OK) rc = rt2::pack_instances(opt, g, spheres, n_spheres, meshes, n_meshes, s, head, why);
-        if (rc == RT_OK) rc = rt2::pack_instances(opt, g, spheres, n_spheres, meshes, n_meshes, again, head_again, why);
-        if (rc != RT_OK) return fail(nullptr, rc, why);
-        const size_t head_bytes = head.size() * sizeof(rt2::Quad);
-        const bool same = head.size() == head_again.size() && (head.empty() || memcmp(head.data(), head_again.data(), head_bytes) == 0) &&
-                          memcmp(&s.lay, &again.lay, sizeof(SceneLayout)) == 0;
-        if (out && bytes < s.lay.bytes) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "output smaller than the blob");
-        if (layout_out) memcpy(layout_out, &s.lay, sizeof(SceneLayout));
-        if (facts_out) {
-            const uint32_t f[RT_TEST_PACK_FACTS] = {s.n_items, s.n_tlas_records, s.n_forest_entries, s.tlas_entries, s.has_tlas, s.has_forest, s.plain_materials,
-                                                    s.have_defer, s.defer_mesh, s.defer_xform, s.defer_internal, g.max_height, g.max_leaf_ref, g.top_mesh_records,
-                                                    g.top_mesh_base, g.roots_are_unions, g.any_deep, same};
-            memcpy(facts_out, f, sizeof(f));
-        }
-        if (out) {
-            memset(out, 0, s.lay.bytes);
-            if (!head.empty()) memcpy(out, head.data(), head_bytes);
-            if (!tail.empty()) memcpy((char*)out + s.lay.wide_off, tail.data(), tail.size() * sizeof(rt2::Quad));
-        }
-    } catch (const std::bad_alloc&) {
-        return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-    }
-    return RT_OK;
-}
-
-// tests/test_gpu_intersect.py: intersect_scene for host-given rays, on the uploaded scene, with the arguments and the
-// instantiation a render launches (query_args, render_takes_simple) unless `flags` force one.
-int rt_test_intersect(rt_handle* h, const float* ro, const float* rd, const uint8_t* active, uint64_t n, int flags,
-                      uint32_t* out) {
-    if (!h || (n && (!ro || !rd || !out))) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (flags & ~(RT_TEST_ISECT_GENERAL | RT_TEST_ISECT_STATS | RT_TEST_ISECT_SIMPLE))
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    if ((flags & RT_TEST_ISECT_GENERAL) && (flags & RT_TEST_ISECT_SIMPLE))
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "flags ask for both the general and the SIMPLE instantiation");
-    if (n > RT_TEST_ISECT_MAX_RAYS) return fail(h, RT_ERR_CAPACITY, "too many rays");
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    // only rays a render can trace: finite origins, finite non-zero directions (the kernels' normalize gives these)
-    for (uint64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(ro[i]) || !std::isfinite(rd[i])) return fail(h, RT_ERR_INVALID_ARGUMENT, "non-finite ray");
-    for (uint64_t i = 0; i < n; ++i)
-        if (rd[3 * i] == 0.0f && rd[3 * i + 1] == 0.0f && rd[3 * i + 2] == 0.0f)
-            return fail(h, RT_ERR_INVALID_ARGUMENT, "zero direction");
-    const RenderArgs a = query_args(h, nullptr);
-    const bool stats = (flags & RT_TEST_ISECT_STATS) != 0;
-    bool simple = render_takes_simple(a) && !stats;  // (the counter instantiations are the general code)
-    if (flags & RT_TEST_ISECT_GENERAL) simple = false;
-    if (flags & RT_TEST_ISECT_SIMPLE) {
-        if (a.many_mesh || !h->inst.plain_materials)
-            return fail(h, RT_ERR_INVALID_ARGUMENT, "the SIMPLE instantiation needs a few-mesh scene without spheres, glass or textures");
-        simple = true;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-    float *dro = nullptr, *drd = nullptr;
-    uint8_t* dact = nullptr;
-    uint32_t* dout = nullptr;
-    const size_t m = (size_t)(n ? n : 1);
-    HIP_TRY(h, hipMalloc((void**)&dro, m * 3 * sizeof(float)));
-    HIP_TRY(h, hipMalloc((void**)&drd, m * 3 * sizeof(float)));
-    HIP_TRY(h, hipMalloc((void**)&dout, m * RT_TEST_ISECT_WORDS * sizeof(uint32_t)));
-    if (active) HIP_TRY(h, hipMalloc((void**)&dact, m));
-    HIP_TRY(h, hipMemcpyAsync(dro, ro, n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(drd, rd, n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (active) HIP_TRY(h, hipMemcpyAsync(dact, active, n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(dout, 0, m * RT_TEST_ISECT_WORDS * sizeof(uint32_t), h->stream));
-    HIP_TRY(h, launch_test_intersect(a, dro, drd, dact, n, simple, stats, dout, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out, dout, n * RT_TEST_ISECT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_dev(dro);
-    free_dev(drd);
-    free_dev(dact);
-    free_dev(dout);
-    return RT_OK;
-}
-
-// tests/test_gpu_shade.py: path_end / roulette_skip for host-given lane states and hits, on the uploaded scene's materials
-// and textures, with the arguments of a render (query_args) minus the pixel memo and the instantiation it launches
-// (render_takes_simple) unless `flags` force one.  Everything is checked here: nothing the kernel indexes with comes from
-// the cases unchecked.
-int rt_test_shade(rt_handle* h, int which, const uint32_t* cases, const uint8_t* active, uint64_t n, int number_of_bounces,
-                  int rays_per_pixel, int skybox, int flags, uint32_t* out) {
-    if (!h || (n && (!cases || !out))) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (which != RT_TEST_SHADE_PATH_END && which != RT_TEST_SHADE_ROULETTE_SKIP) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown function");
-    if (flags & ~(RT_TEST_SHADE_GENERAL | RT_TEST_SHADE_NO_FAST_MISS | RT_TEST_SHADE_SIMPLE | RT_TEST_SHADE_TOTAL_REGS))
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
-    if ((flags & RT_TEST_SHADE_GENERAL) && (flags & RT_TEST_SHADE_SIMPLE))
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "flags ask for both the general and the SIMPLE instantiation");
-    if (n > RT_TEST_SHADE_MAX_CASES) return fail(h, RT_ERR_INVALID_ARGUMENT, "too many cases");
-    if (!h->have_scene) return fail(h, RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    RenderArgs a = query_args(h, nullptr);
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint32_t* c = cases + i * RT_TEST_SHADE_WORDS;
-        if (c[30] >= a.n_meshes + a.n_spheres) return fail(h, RT_ERR_INVALID_ARGUMENT, "object index outside the scene");
-        if (c[18] != RT_TEST_SHADE_STEP_END && c[18] != RT_TEST_SHADE_STEP_TRAVERSE) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown step mode");
-    }
-    a.params.number_of_bounces = number_of_bounces;
-    a.params.rays_per_pixel = rays_per_pixel;
-    a.params.skybox = skybox;
-    a.pixel_cache = 0u;  // (no memo: path_end's FAST_MISS reads none, and the LDS map holds none)
-    a.fast_miss = a.roulette_skip = 0u;
-    bool simple = render_takes_simple(a);
-    if (flags & RT_TEST_SHADE_GENERAL) simple = false;
-    if (flags & RT_TEST_SHADE_SIMPLE) {
-        if (a.many_mesh || !h->inst.plain_materials)
-            return fail(h, RT_ERR_INVALID_ARGUMENT, "the SIMPLE instantiation needs a few-mesh scene without spheres, glass or textures");
-        simple = true;
-    }
-    const bool total_lds = total_in_lds(a.lds_scene != 0u) && !(flags & RT_TEST_SHADE_TOTAL_REGS);
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = wait_pending_copy(h); rc != RT_OK) return rc;
-    uint32_t *dcases = nullptr, *dout = nullptr;
-    uint8_t* dact = nullptr;
-    const size_t m = (size_t)(n ? n : 1), bytes = m * RT_TEST_SHADE_WORDS * sizeof(uint32_t), used = (size_t)n * RT_TEST_SHADE_WORDS * sizeof(uint32_t);
-    // One exit: whatever fails, the stream is drained before the buffers are freed (nothing queued may still point at them),
-    // and they are freed (staged_chunks' form).
-    const char* what = "hipMalloc";
-    hipError_t e = hipMalloc((void**)&dcases, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, bytes);
-    if (e == hipSuccess && active) e = hipMalloc((void**)&dact, m);
-    if (e == hipSuccess) {
-        what = "hipMemcpyAsync";
-        e = hipMemcpyAsync(dcases, cases, used, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && active) e = hipMemcpyAsync(dact, active, n, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) what = "hipMemsetAsync", e = hipMemsetAsync(dout, 0, bytes, h->stream);
-        if (e == hipSuccess)
-            what = "launch_test_shade", e = launch_test_shade(a, which, dcases, dact, n, simple, !(flags & RT_TEST_SHADE_NO_FAST_MISS), total_lds, dout, h->stream);
-        if (e == hipSuccess) what = "hipMemcpyAsync", e = hipMemcpyAsync(out, dout, used, hipMemcpyDeviceToHost, h->stream);
-        const hipError_t drained = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) what = "hipStreamSynchronize", e = drained;
-    }
-    free_dev(dcases);
-    free_dev(dact);
-    free_dev(dout);
-    if (e != hipSuccess) return fail(h, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-    return RT_OK;
-}
-
-int rt_test_sweep(rt_handle* h, int which, uint64_t* out3) {
-    if (!h || !out3 || which < 0 || which > 4) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    unsigned long long* d = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d, 3 * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, launch_sweep(which, d, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out3, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_dev(d);
-    return RT_OK;
-}
-
-int rt_test_device_sample_texture(rt_handle* h, const rt_texture_desc* tex, const float* uv, float* rgba_out, uint64_t n) {
-    if (!h || !tex || !tex->rgba8 || !uv || !rgba_out || tex->width == 0 || tex->height == 0)
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    uint8_t* dt = nullptr;
-    float *duv = nullptr, *dout = nullptr;
-    const size_t tb = (size_t)tex->width * tex->height * 4;
-    HIP_TRY(h, hipMalloc((void**)&dt, tb));
-    HIP_TRY(h, hipMalloc((void**)&duv, (size_t)(n ? n : 1) * 2 * sizeof(float)));
-    HIP_TRY(h, hipMalloc((void**)&dout, (size_t)(n ? n : 1) * 4 * sizeof(float)));
-    HIP_TRY(h, hipMemcpyAsync(dt, tex->rgba8, tb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(duv, uv, n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, launch_units_texture(dt, tex->width, tex->height, h->srgb_lut, duv, dout, n, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(rgba_out, dout, n * 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_dev(dt);
-    free_dev(duv);
-    free_dev(dout);
-    return RT_OK;
-}
-
-// Test-only: raw copies of the wavefront sequence's buffers after the last launch (0 path state, 1 hit records,
-// 2 the two slot lists, 3 the per-round list counts), for tests/tools that check the sequence slot by slot.
-int rt_test_read_wavefront(rt_handle* h, int which, void* out, uint64_t bytes) {
-    if (!h || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t blocks = h->wf_capacity / 64;
-    const void* src = nullptr;
-    size_t have = 0;
-    switch (which) {
-        case 0: src = h->wf_state; have = blocks * WF_STATE_PLANES * 64 * sizeof(float4); break;
-        case 1: src = h->wf_hit; have = blocks * WF_HIT_PLANES * 64 * sizeof(float4); break;
-        case 2: src = h->wf_lists; have = 2 * h->wf_capacity * sizeof(uint32_t); break;
-        case 3: src = h->wf_counts; have = h->wf_counts_capacity * sizeof(uint32_t); break;
-        case 4: src = h->park_counts; have = h->park_counts ? 72 * sizeof(uint32_t) : 0; break;
-        case 5: case 6:   // the park records of the last sequence's even / odd rounds (rt_device.h: PARK_PLANES)
-            src = h->park_queue[which - 5];
-            have = src ? ((h->park_capacity + 63) / 64) * (size_t)PARK_PLANES * 64u * sizeof(float4) : 0;
-            break;
-        default: return fail(h, RT_ERR_INVALID_ARGUMENT, "which must be 0..6");
-    }
-    if (!src || bytes > have) return fail(h, RT_ERR_INVALID_ARGUMENT, "no wavefront buffer of that size");
-    HIP_TRY(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RT_OK;
-}
-
-// Test-only, no GPU needed: the automatic depth of option "frame_ahead" (rt2::ahead_depth) for a one-frame call that continues
-// an accumulation -- scene staged in LDS or read from global memory, texels of the call's share, samples per pixel, bounces,
-// and whether the host counts as one that waits for its frames.  tests/test_frame_ahead_policy.py pins the documented
-// figures with it.
-int rt_test_frame_ahead_depth(int lds_scene, uint64_t texels, int rays_per_pixel, int number_of_bounces, int host_waits) {
-    rt_params p{};
-    p.rays_per_pixel = rays_per_pixel;
-    p.number_of_bounces = number_of_bounces;
-    p.frames = 1;
-    return (int)rt2::ahead_depth(rt2::Options{}, p, false, false, lds_scene != 0, texels, host_waits != 0);
-}
-
-// Test-only, no device and no handle (tests/test_options_host.py): row `index` of the option table, and the setter on a
-// fresh set of options.
-int rt_test_option_table(uint32_t index, char name_out[RT_TEST_OPTION_NAME_BYTES], int32_t info_out[4]) {
-    static_assert(RT_TEST_OPT_BOOLEAN == rt2::OPT_BOOLEAN && RT_TEST_OPT_UPLOAD == rt2::OPT_UPLOAD && RT_TEST_OPT_EXPERIMENT == rt2::OPT_EXPERIMENT &&
-                      RT_TEST_OPT_DROPS_PRIMARY == rt2::OPT_DROPS_PRIMARY && RT_TEST_OPT_RESETS_TILES == rt2::OPT_RESETS_TILES &&
-                      RT_TEST_OPT_CLEARS_AHEAD_FAILED == rt2::OPT_CLEARS_AHEAD_FAILED && RT_TEST_OPT_ONE_IS_AUTO == rt2::OPT_ONE_IS_AUTO &&
-                      RT_TEST_OPT_NOT_ONE == rt2::OPT_NOT_ONE,
-                  "include/rt_test_abi.h repeats the flags of host/launch_options.h");
-    const rt2::OptionRow* row = rt2::option_row(index);
-    if (!row || !name_out || !info_out || strlen(row->name) >= RT_TEST_OPTION_NAME_BYTES) return RT_ERR_INVALID_ARGUMENT;
-    rt2::Options fresh;
-    strcpy(name_out, row->name);
-    const int32_t info[4] = {row->lo, row->hi, row->at(fresh), (int32_t)row->flags};
-    memcpy(info_out, info, sizeof(info));
-    return RT_OK;
-}
-int rt_test_set_option(const char* name, int value, int32_t stored_out[2]) {
-    if (!name || !stored_out) return RT_ERR_INVALID_ARGUMENT;
-    rt2::Options opt;
-    const rt2::SetResult r = rt2::set_option(opt, name, value);
-    stored_out[0] = r.row ? r.row->at(opt) : 0;
-    stored_out[1] = (int32_t)r.effects;
-    return r.code() == RT_OK ? RT_OK : fail(nullptr, r.code(), r.error);
-}
-
-// Test-only, no device and no handle (tests/test_launch_rules_host.py): one launch rule of host/launch_options.h on the
-// option values given (what rt_test_set_option stored for them).
-int rt_test_launch_rule(int which, const int64_t in[8], int64_t out[2]) {
-    if (!in || !out) return RT_ERR_INVALID_ARGUMENT;
-    rt2::Options opt;
-    uint32_t a = 0, b = 0;
-    switch (which) {
-        case RT_TEST_RULE_VOTES:
-            opt.vote_eighths = (int)in[0];
-            opt.vote_patience = (int)in[1];
-            rt2::vote_thresholds(opt, in[2] != 0, in[3] != 0, a, b);
-            break;
-        case RT_TEST_RULE_ROUNDS: a = rt2::automatic_rounds((size_t)in[0], (int)in[1], (uint32_t)in[2]); break;
-        case RT_TEST_RULE_VARIANT:
-            opt.kernel_variant = (int)in[0];
-            opt.persistent_blocks = (int)in[1];
-            a = rt2::kernel_variant_for(opt, (uint64_t)in[2], (uint32_t)in[3], in[4] != 0);
-            break;
-        case RT_TEST_RULE_DEPTH:
-            opt.pipeline = (int)in[0];
-            a = (uint32_t)rt2::pipeline_depth(opt, (int)in[1], (uint32_t)in[2]);
-            break;
-        case RT_TEST_RULE_BATCH: a = in[1] >= 1 ? rt2::equal_batch((uint32_t)in[0], (uint32_t)in[1]) : 0u; break;
-        case RT_TEST_RULE_GRID:
-            opt.persistent_blocks = (int)in[1];
-            a = rt2::blocks_per_cu_for((size_t)in[0]);
-            b = rt2::persistent_blocks_for(opt, (size_t)in[0]);
-            break;
-        case RT_TEST_RULE_FRAME_GROUP:
-            a = rt2::frame_group_for((uint32_t)in[0], (uint64_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0, in[5] != 0);
-            b = rt2::FRAME_GROUP_CAP;
-            break;
-        case RT_TEST_RULE_FRAME_GROUP_TAPERED:
-            a = rt2::frame_group_tapered_for((uint32_t)in[0], (uint64_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0, in[5] != 0);
-            b = rt2::FRAME_GROUP_CAP_TAPERED | rt2::FRAME_GROUP_MIN_ITEMS_PER_WAVE_TAPERED << 16;
-            break;
-        case RT_TEST_RULE_FRAME_TAPER: {
-            static_assert(RT_TEST_TAPER_WORDS == rt2::TAPER_WORDS, "include/rt_test_abi.h: the taper table");
-            // (in[6]: the address of n_tiles costs followed by room for the table)
-            uint32_t* words = (uint32_t*)(uintptr_t)in[6];
-            const uint32_t n_tiles = (uint32_t)in[5];
-            if (!words || in[5] < 0 || in[5] > (1ll << 24)) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "frame taper rule: costs and at most 2^24 tiles");
-            uint32_t count[rt2::TAPER_BINS];
-            unsigned long long weight[rt2::TAPER_BINS];
-            rt2::frame_taper_histogram(words, n_tiles, (uint32_t)in[3], (uint32_t)in[4], count, weight);
-            b = in[7] > 0 ? (uint32_t)in[7] : rt2::FRAME_TAPER_ALPHA;
-            rt2::frame_taper_table(count, weight, rt2::TAPER_BINS, (uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], b, words + n_tiles);
-            a = words[n_tiles];
-            break;
-        }
-        case RT_TEST_RULE_TERMINAL_SKIP: {
-            // (in[0]: the address of a packed blob -- rt_test_pack_scene's --, in[1]: of its 12 layout words, in[7]: of three floats)
-            const rt2::Quad* head = (const rt2::Quad*)(uintptr_t)in[0];
-            const uint32_t* words = (const uint32_t*)(uintptr_t)in[1];
-            float* c_out = (float*)(uintptr_t)in[7];
-            if (!head || !words || !c_out || in[2] < 0 || in[3] < 0) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "terminal skip rule: a blob, its layout, room for terminal_c");
-            SceneLayout lay;
-            static_assert(sizeof(lay) == 12 * sizeof(uint32_t), "SceneLayout: 12 words");
-            memcpy(&lay, words, sizeof(lay));
-            const rt2::TerminalScene t = rt2::terminal_skip_scene(head, lay, (uint32_t)in[2], (uint32_t)in[3]);
-            a = rt2::terminal_skip_for(t, in[4] != 0, false, in[5] != 0, in[6] != 0, false);
-            b = t.dark;
-            for (int k = 0; k < 3; ++k) c_out[k] = a != 0u ? t.c[k] : 0.0f;
-            a = a != 0u ? 1u : 0u;
-            break;
-        }
-        default: return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "unknown rule");
-    }
-    out[0] = a;
-    out[1] = b;
-    return RT_OK;
-}
-
-// Test-only: the terminal skip of handle `h` (RenderArgs::terminal_dark).  on >= 0 switches it for the handle's later
-// launches (1: rt2::terminal_skip_for decides, the default; 0: no launch skips); last_out: the mask the handle's last
-// render launch ran with (0: it skipped nothing) and the bits of its terminal_c.
-int rt_test_terminal_skip(rt_handle* h, int on, uint32_t last_out[4]) {
-    if (!h) return RT_ERR_INVALID_ARGUMENT;
-    if (on >= 0) h->terminal_skip_on = on != 0;
-    if (last_out) {
-        last_out[0] = h->last_terminal_dark;
-        for (int k = 0; k < 3; ++k) {
-            const float c = h->last_terminal_dark != 0u ? h->terminal.c[k] : 0.0f;
-            memcpy(&last_out[1 + k], &c, 4);
-        }
-    }
-    return RT_OK;
-}
-
-// Test-only: the fixed switches of handle `h` (rt2::FixedSwitches).  on >= 0 switches them for the handle's later launches
-// (1: rt2::fixed_switches_ok decides, the default; 0: every launch runs the general kernel); last_out: 1 if the handle's
-// last render launch ran the FIXED instantiation (rt_last_launch out[3] & 32).
-int rt_test_fixed_switches(rt_handle* h, int on, uint32_t* last_out) {
-    if (!h) return RT_ERR_INVALID_ARGUMENT;
-    if (on >= 0) h->fixed_switches_on = on != 0;
-    if (last_out) *last_out = (h->last_launch[3] & 32u) != 0u ? 1u : 0u;
-    return RT_OK;
-}
-
-// Test-only: rt2::fixed_switches_ok on host-given values, and the constants of rt2::FixedSwitches beside the answer.
-int rt_test_fixed_switches_rule(const int64_t in[RT_TEST_FIXED_SWITCHES], int64_t out[2 + RT_TEST_FIXED_SWITCHES]) {
-    if (!in || !out) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null argument");
-    using F = rt2::FixedSwitches;
-    const rt2::FixedSwitchValues v{(uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], (uint32_t)in[4], (uint32_t)in[5],
-                                   (uint32_t)in[6], (uint32_t)in[7], (int32_t)in[8], (int32_t)in[9], (uint32_t)in[10], (uint32_t)in[11],
-                                   (uint32_t)in[12], (uint32_t)in[13], (uint32_t)in[14]};
-    const int64_t constants[RT_TEST_FIXED_SWITCHES] = {F::stack_wide, F::forest_cull, F::roulette_skip, F::fast_miss, F::terminal_dark, F::pixel_cache,
-                                                        F::primary, F::primary_complete, F::skybox, F::samples, F::spp_reciprocal, F::strip_world,
-                                                        F::batch, F::batch_tile_major, F::grouped};
-    out[0] = (rt2::fixed_switches_ok(v, true) ? 1 : 0) | (rt2::fixed_switches_ok(v, false) ? 2 : 0);
-    out[1] = RT_FIXED_SWITCHES;
-    for (int k = 0; k < RT_TEST_FIXED_SWITCHES; ++k) out[2 + k] = constants[k];
-    return RT_OK;
-}
-
-// Test-only: the frame groups of handle `h` (RenderArgs::frame_group).  force >= 0 sets the group size of its later batches
-// (0: rt2::frame_group_for decides, and rt2::frame_group_tapered_for for a launch that carries a taper table; an order or a
-// launch sequence that takes no groups still gets 1, as does a library
-// built with -DRT_FRAME_GROUP=1); last_out: the group size of the handle's last launch.
-int rt_test_frame_group(rt_handle* h, int force, uint32_t* last_out) {
-    if (!h || force > (int)RT_MAX_BATCH_FRAMES) return fail(h, RT_ERR_INVALID_ARGUMENT, "frame group: -1 (leave), 0 (the rule), 1..64");
-    if (force >= 0) h->frame_group_forced = (uint32_t)force;
-    if (last_out) *last_out = h->last_frame_group;
-    return RT_OK;
-}
-
-// Test-only: the taper of handle `h` (RenderArgs::frame_taper).  n_segments >= 1 forces the segments {first_rank[k],
-// size[k]} on its later grouped batches, bypassing the rule; 0 gives the rule its say again; < 0 changes nothing.
-// table_out: the table the handle's last launch ran with, zeros if it ran untapered.
-int rt_test_frame_taper(rt_handle* h, int n_segments, const uint32_t* first_rank, const uint32_t* size, uint32_t* table_out) {
-    if (!h) return RT_ERR_INVALID_ARGUMENT;
-    if (n_segments > (int)rt2::TAPER_MAX_SEGMENTS || (n_segments > 0 && (!first_rank || !size)))
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "frame taper: at most 8 segments, each with a first rank and a group size");
-    if (n_segments >= 0) {
-        std::vector<uint32_t> forced;
-        for (int k = 0; k < n_segments; ++k) {
-            if (first_rank[k] < (k ? first_rank[k - 1] : 0u) || (k == 0 && first_rank[0] != 0u) || size[k] < 1u || size[k] > RT_MAX_BATCH_FRAMES)
-                return fail(h, RT_ERR_INVALID_ARGUMENT, "frame taper: first ranks ascending from 0, group sizes 1..64");
-            forced.push_back(first_rank[k]);
-            forced.push_back(size[k]);
-        }
-        h->taper_forced = forced;
-    }
-    if (table_out) {
-        memset(table_out, 0, rt2::TAPER_WORDS * sizeof(uint32_t));
-        if (int rc = rt_synchronize(h); rc != RT_OK) return rc;
-        if (h->last_taper) HIP_TRY(h, hipMemcpy(table_out, h->last_taper, rt2::TAPER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    return RT_OK;
-}
-
-// Test-only: the device's evaluation of the taper rule (rt_frame_taper_kernel) on n_tiles host-given tile costs -- what
-// tile_feedback launches behind a new tile order, with every input the caller's.
-int rt_test_frame_taper_rule(rt_handle* h, const uint32_t* cost, uint32_t n_tiles, uint32_t max_cost, uint32_t cost_floor, uint32_t n_batch,
-                             uint32_t head, uint32_t waves, uint32_t alpha, uint32_t* table_out) {
-    if (!h || !table_out || (n_tiles && !cost)) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_tiles > (1u << 24) || head > RT_MAX_BATCH_FRAMES || n_batch > RT_MAX_BATCH_FRAMES)
-        return fail(h, RT_ERR_INVALID_ARGUMENT, "frame taper rule: at most 2^24 tiles, 64 frames");
-    HIP_TRY(h, hipSetDevice(h->device));
-    uint32_t* dev = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&dev, ((size_t)n_tiles + rt2::TAPER_WORDS) * sizeof(uint32_t)));
-    hipError_t e = n_tiles ? hipMemcpy(dev + rt2::TAPER_WORDS, cost, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess) e = launch_frame_taper(dev + rt2::TAPER_WORDS, n_tiles, max_cost, cost_floor, n_batch, head, waves, alpha, dev, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(table_out, dev, rt2::TAPER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    free_dev(dev);
-    HIP_TRY(h, e);
-    return RT_OK;
-}
-
-// Test-only: the rays per tile that the handle's last cost-recording launch counted (tile_feedback: the first frame of a
-// batch, or the single frame), n_tiles of them, once everything queued on the handle is done.
-int rt_test_tile_costs(rt_handle* h, uint32_t* out, uint32_t n_tiles) {
-    if (!h || !out) return fail(h, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!h->tile_cost[h->tiles.cost_slot]) return fail(h, RT_ERR_INVALID_ARGUMENT, "the handle has no tile-cost tables");
-    if (n_tiles > h->tile_capacity) return fail(h, RT_ERR_INVALID_ARGUMENT, "more tiles than the handle's frame size has");
-    if (int rc = rt_synchronize(h); rc != RT_OK) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->tile_cost[h->tiles.cost_slot], (size_t)n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// Test-only: the grouped gather of rt_render_multi against the RCCL-shaped library at `lib_path`, on fake buffers and
-// with no HIP call (so that it runs on a machine without a GPU): n_ranks communicators from ncclCommInitAll, one
-// rccl_grouped_gather over them; on failure the communicators are aborted, as render_multi_impl does.  The error text
-// goes to rt_last_error(NULL).  tests/test_rccl_group.py drives it against tests/cpp/fake_rccl.c.
-int rt_test_rccl_gather(const char* lib_path, int n_ranks) {
-    if (!lib_path || n_ranks < 1 || n_ranks > 64) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "bad arguments");
-    RcclApi api;
-    if (!api.load(lib_path)) return fail(nullptr, RT_ERR_IO, api.why);
-    std::vector<ncclComm_t> comms((size_t)n_ranks);
-    std::vector<int> devs((size_t)n_ranks);
-    for (int r = 0; r < n_ranks; ++r) devs[(size_t)r] = r;
-    ncclResult_t r0 = api.CommInitAll(comms.data(), n_ranks, devs.data());
-    if (r0 != ncclSuccess) {
-        const std::string why = std::string("ncclCommInitAll: ") + api.GetErrorString(r0);
-        api.unload();
-        return fail(nullptr, RT_ERR_DEVICE, why);
-    }
-    static float fake_send[64][4], fake_recv[64][4];
-    std::vector<GatherLeg> legs;
-    for (int r = 0; r < n_ranks; ++r)
-        legs.push_back(GatherLeg{fake_send[r], fake_recv[r], 4, r, r, comms[(size_t)r], nullptr});
-    std::string gerr;
-    const bool ok = rccl_grouped_gather(api, legs, 0, comms[0], nullptr, [](int, std::string&) { return 0; }, gerr);
-    for (ncclComm_t c : comms) {
-        if (ok) (void)api.CommDestroy(c);
-        else api.drop(c);
-    }
-    api.unload();
-    return ok ? RT_OK : fail(nullptr, RT_ERR_DEVICE, "rt_render_multi gather: " + gerr);
-}
-
-// Test-only: find_best_split for host-given nodes through a LevelSearch -- the host one (device -1, no GPU needed) or
-// the kernels of rt_bvh_search.hip --, the levels in turn through one search object, as bvh_build_levels drives it.
-// tests/test_bvh_search_host.py, tests/test_gpu_bvh_search.py.
-int rt_test_sah_search(int device, const float* tri9, uint64_t n, const uint32_t* order, const rt_test_sah_query* queries,
-                       const uint32_t* level_counts, uint32_t n_levels, rt_test_sah_result* out) {
-    if (device < -1) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "device must be -1 (host search) or a device ordinal");
-    if (n == 0 || n > RT_MAX_TRIANGLES || !tri9 || !order) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "no triangles, or too many");
-    if (n_levels && !level_counts) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null level_counts");
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < n_levels; ++l) total += level_counts[l];
-    if (total && (!queries || !out)) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "null queries or results");
-    for (uint64_t p = 0; p < n; ++p)
-        if (order[p] >= n) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "order[" + std::to_string(p) + "] is not a triangle id");
-    for (uint64_t k = 0; k < total; ++k) {
-        if (queries[k].count < 2)
-            return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "query " + std::to_string(k) + ": count < 2 (the builder never searches such a node)");
-        if ((uint64_t)queries[k].start + queries[k].count > n)
-            return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "query " + std::to_string(k) + ": start + count exceeds the " + std::to_string(n) + " triangles");
-    }
-    try {
-        const rt2::LevelSearch search = device >= 0 ? rt2::make_device_level_search(device, tri9, (size_t)n)
-                                                    : rt2::make_host_level_search(tri9, (size_t)n);
-        std::vector<rt2::SplitQuery> qs;
-        std::vector<rt2::SplitResult> rs;
-        uint64_t base = 0;
-        for (uint32_t l = 0; l < n_levels; ++l) {
-            qs.resize(level_counts[l]);
-            for (uint32_t k = 0; k < level_counts[l]; ++k) {
-                const rt_test_sah_query& q = queries[base + k];
-                qs[k].start = q.start;
-                qs[k].count = q.count;
-                memcpy(qs[k].aabb_min, q.aabb_min, 12);
-                memcpy(qs[k].aabb_max, q.aabb_max, 12);
-            }
-            search(order, (size_t)n, qs, rs);
-            for (uint32_t k = 0; k < level_counts[l]; ++k) out[base + k] = rt_test_sah_result{rs[k].axis, rs[k].pos, rs[k].cost};
-            base += level_counts[l];
-        }
-    } catch (const std::exception& e) {   // (as rt_scene_build_device sorts them)
-        return fail(nullptr, strncmp(e.what(), "HIP", 3) == 0 ? RT_ERR_DEVICE : RT_ERR_OUT_OF_MEMORY, e.what());
-    }
-    return RT_OK;
-}
-#endif  // RT_TEST_ENTRIES
 
 void* rt_device_image(rt_handle* h) { return h ? (void*)h->image : nullptr; }
 void* rt_stream(rt_handle* h) { return h ? (void*)h->stream : nullptr; }

@@ -1,6 +1,6 @@
 // rt_denoise_api.h -- what the denoiser's units declare to each other (include/rt_abi.h: rt_denoise, rt_denoise_host): the
 // argument rules and the host restatement (host/denoise.cpp), and the arguments of the device launch (rt_denoise.hip), both
-// called by the entry points in rt_api.hip.  The arithmetic they share is csrc/rt_denoise.h.
+// called by the entry points in rt_api_frames.hip.  The arithmetic they share is csrc/rt_denoise.h.
 #ifndef RT_DENOISE_API_H
 #define RT_DENOISE_API_H
 

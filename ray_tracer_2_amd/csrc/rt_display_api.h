@@ -1,7 +1,7 @@
 // rt_display_api.h -- what the units of the display pass and the exposure meter declare to each other (include/rt_abi.h:
 // rt_display, rt_auto_exposure, rt_snapshot_display and the _host forms): the argument rules, the once-per-call numbers and
 // the host restatements (host/display.cpp), and the argument structs of the device launches (rt_display.hip), all called by
-// the entry points in rt_api.hip.  The arithmetic they share is csrc/rt_display.h.
+// the entry points in rt_api_frames.hip (rt_snapshot_display: rt_api.hip).  The arithmetic they share is csrc/rt_display.h.
 #ifndef RT_DISPLAY_API_H
 #define RT_DISPLAY_API_H
 

@@ -1,7 +1,7 @@
 // rt_temporal_api.h -- what the units of temporal accumulation declare to each other (include/rt_abi.h:
 // rt_temporal_accumulate, rt_temporal_accumulate_host and their _moving and _deforming forms): the kind of a call, the argument
 // rules, the once-per-call numbers and the host restatement (host/temporal.cpp), and the one argument struct of the device
-// launch (rt_temporal.hip), all called by the entry points in rt_api.hip.  The arithmetic they share is csrc/rt_temporal.h.
+// launch (rt_temporal.hip), all called by the entry points in rt_api_frames.hip.  The arithmetic they share is csrc/rt_temporal.h.
 #ifndef RT_TEMPORAL_API_H
 #define RT_TEMPORAL_API_H
 

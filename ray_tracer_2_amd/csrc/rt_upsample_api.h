@@ -1,6 +1,6 @@
 // rt_upsample_api.h -- what the units of guided upsampling declare to each other (include/rt_abi.h: rt_upsample,
 // rt_upsample_host): the argument rules, the once-per-call numbers and the host restatement (host/upsample.cpp), and the
-// argument struct of the device launch (rt_upsample.hip), all called by the entry points in rt_api.hip.  The arithmetic
+// argument struct of the device launch (rt_upsample.hip), all called by the entry points in rt_api_frames.hip.  The arithmetic
 // they share is csrc/rt_upsample.h.
 #ifndef RT_UPSAMPLE_API_H
 #define RT_UPSAMPLE_API_H

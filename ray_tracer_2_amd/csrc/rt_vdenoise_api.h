@@ -1,7 +1,7 @@
 // rt_vdenoise_api.h -- what the variance-guided denoiser's units declare to each other (include/rt_abi.h:
 // rt_denoise_variance, rt_luminance_moments and their _host forms): the argument rules and the host restatement
 // (host/vdenoise.cpp), and the arguments of the device launches (rt_vdenoise.hip), both called by the entry points in
-// rt_api.hip.  The arithmetic they share is csrc/rt_vdenoise.h.
+// rt_api_frames.hip.  The arithmetic they share is csrc/rt_vdenoise.h.
 #ifndef RT_VDENOISE_API_H
 #define RT_VDENOISE_API_H
 

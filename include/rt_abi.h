@@ -762,7 +762,9 @@ int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags
  * Consequence: with a table whose records all have moved == 0 (and every object word below n_objects) every output plane
  * is rt_temporal_accumulate's bit for bit, for any camera move.
  * What this keeps is an object's OWN history, not the lighting: a turning object's faces change their illumination, shadows
- * and reflections move over surfaces that stand still, and the history lags behind them; max_history bounds the lag.
+ * and reflections move over surfaces that stand still, and the history lags behind them; max_history bounds the lag
+ * everywhere at the price of noise everywhere, and rt_temporal_rectify (below) cuts it where the new frame contradicts the
+ * history.
  * A second call with the luminance moments as color / prev_color and the same table accumulates the moments that
  * rt_denoise_variance takes for a moving object.
  * Memory, asynchrony, aliasing and side effects are rt_temporal_accumulate's.  `motions` is on the side of the planes: a
@@ -839,7 +841,7 @@ int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* d
  * inside the 1/64-texel snap; it takes its own texel as its one tap, motion(p) = (0, 0), and every output plane is
  * rt_temporal_accumulate's bit for bit -- and so rt_render's own accumulation.
  * What still lags or restarts: the lighting around a deforming object lags as it does around a moving one (max_history
- * bounds it); a change of topology restarts (the primitive word then names another triangle or none); the sky restarts;
+ * bounds it, rt_temporal_rectify cuts it where the new frame contradicts the history); a change of topology restarts (the primitive word then names another triangle or none); the sky restarts;
  * a sphere given moved == 2 by a hand-made table restarts or fetches a wrong triangle's history -- its primitive word is
  * read as a triangle index -- which rt_object_motions_deforming never produces.
  * A second call with the luminance moments as color / prev_color and the same arguments accumulates the moments that
@@ -1424,6 +1426,91 @@ int rt_auto_exposure_host(const rt_auto_exposure_desc* desc);
  * has; rt_read_display_snapshot: RT_ERR_INVALID_ARGUMENT before any snapshot or for more bytes than the last one has. */
 int rt_snapshot_display(rt_handle* h, const rt_display_desc* desc);
 int rt_read_display_snapshot(rt_handle* h, uint8_t* out, size_t bytes);
+
+/* ---- history rectification: clip the reprojected history to the new frame ----
+ * rt_temporal_accumulate and its _moving and _deforming forms keep a texel's history across camera moves, moving objects
+ * and deforming meshes, but not across a change of the lighting: a history of n frames takes the new frame in at 1 / (n + 1)
+ * and stays wrong for about n frames.  rt_temporal_rectify is the blend of those calls with variance clipping in front:
+ * the REPROJECTED history is clamped, per colour channel, into mean +- clip_sigma standard deviations of the new frame's
+ * colours around the texel, and a texel that had to be clamped has its history length cut to clip_history, so that new
+ * samples take over quickly.
+ * The reprojected history is what any of the three calls returns for a `color` plane of quiet NaNs: they drop a non-finite
+ * sample (out = the reprojected prev_color, out_history = the reprojected, capped history length; a texel without
+ * history gets out = NaN, out_history = 1).  `history` and `history_length` are those two planes, `color` is the frame the
+ * NaNs stood in for; the moments of rt_denoise_variance go through a reprojection of their own and are `history_moments`.
+ * Frames are width x height, row 0 at the bottom, every plane tightly packed.  Everything is binary32 and unfused, in this
+ * order, r = radius, g = clip_sigma.
+ *   NO HISTORY.  Texel p has no history when some component of history(p) is not finite, or history_length(p) is not finite
+ *   or below 1.  Then out(p) = color(p) bit for bit, out_history(p) = 1, out_moments(p) = moments(p), out_clipped(p) = 0.
+ *   WINDOW, for every other texel.  Taps q = p + (dx, dy) over dy = -r .. r (outer), dx = -r .. r (inner).  A tap COUNTS
+ *   when q is inside the frame, the first three components of color(q) are finite, and `object` is NULL or
+ *   object(q) == object(p).  A counted tap adds color(q)_k to s1_k and color(q)_k * color(q)_k to s2_k, k = 0 .. 2, all from
+ *   +0, and 1 to the integer count c.
+ *   BOX, with c >= 2 and g < +INF, per k = 0 .. 2: mu = s1_k / f32(c); m2 = s2_k / f32(c); v = m2 - mu * mu; v = v > 0 ? v : 0;
+ *   sd = the correctly rounded square root of v; lo = mu - g * sd; hi = mu + g * sd; with h = history(p)_k,
+ *   h' = h < lo ? lo : (h > hi ? hi : h).  The texel is CLIPPED when some h'_k differs in bits from h_k.  With c < 2 or
+ *   g = +INF no box is formed, h' = h and the texel is not clipped.  Alpha is never clipped: h'_3 = h_3.
+ *   LENGTH AND BLEND.  n = history_length(p); n' = (CLIPPED and clip_history < n) ? clip_history : n; w = 1 / (n' + 1);
+ *   rest = 1 - w; out(p)_k = h'_k * rest + color(p)_k * w, k = 0 .. 3 (two products and a sum, rt_temporal_accumulate's
+ *   blend); out_history(p) = n' + 1.  A color(p) with a component that is not finite is dropped: out(p) = h',
+ *   out_history(p) = n'.  out_clipped(p) = 2 when CLIPPED, 1 otherwise.
+ *   MOMENTS (the three planes come together or not at all) are blended with the same w and never clipped:
+ *   out_moments(p)_k = history_moments(p)_k * rest + moments(p)_k * w; a history_moments(p) with a component that is not
+ *   finite gives out_moments(p) = moments(p), and otherwise a moments(p) that is not finite gives history_moments(p).
+ * Consequences.  (1) With clip_sigma = +INF, rt_temporal_rectify on the reprojected history (a call of
+ * rt_temporal_accumulate, _moving or _deforming with NaNs for color) gives `out` and `out_history` of that call on `color`
+ * itself, bit for bit -- for all three forms, any camera move, finite and non-finite samples.  (2) Under an unmoved
+ * camera that is rt_render's own accumulation, bit for bit (rt_temporal_accumulate's consequence).  (3) Where the counted
+ * colours of a window are all equal, to a value whose first c multiples and those of its square are exact in binary32 (a
+ * colour of few mantissa bits: 0.5, 0.75, 3), mu is that colour, sd is 0 and a clipped history becomes that colour exactly;
+ * for any other equal colours it comes within the sums' rounding of it.  (4) At a texel that is not clipped, any clip_sigma gives consequence 1's bits.  (5) rt_temporal_rectify and
+ * rt_temporal_rectify_host give the same bits for every input.
+ * What it does not do: a lamp that gets BRIGHTER widens the new frame's box with its own noise, the old, darker history
+ * lies inside it and is not clipped -- the method reacts to a change that leaves the noise box, not to every change; the
+ * window's statistics are taken on the raw colour, not the demodulated one, so texture detail widens the box; and a channel
+ * is clamped on its own, which can shift a hue.
+ * Unlike rt_temporal_accumulate's, this pass's lanes read their neighbours' `color`: out must not overlap color (an error,
+ * below), object or moments (undefined).  out may be history, out_history may be history_length and out_moments may be
+ * history_moments: each is touched at the texel's own place only, after it was read.
+ * Without RT_RECTIFY_HOST_MEMORY the planes are device pointers on the handle's device (16-byte aligned for the [4] planes,
+ * 4 for the others, 1 for out_clipped), `color` may be NULL for the handle's current image (width * height texels of it,
+ * read only: an `out` that overlaps them is then an error), and the call is asynchronous on the handle's stream, after
+ * every earlier call on the handle and before every later one.  With the flag they are host pointers, staged WHOLE through
+ * one temporary device buffer (36 to 73 bytes per texel: out takes history's place, out_history history_length's,
+ * out_moments history_moments') that is counted against option "max_device_mb" while held (RT_ERR_OUT_OF_MEMORY past the
+ * cap), and the call returns when the outputs are on the host.  The call keeps no scratch between calls.
+ * Errors, nothing written: RT_ERR_INVALID_ARGUMENT (null handle or desc; null history, history_length, out or out_history;
+ * null color except on the device path; one or two of moments, history_moments and out_moments without the rest;
+ * struct_bytes != sizeof(rt_rectify_desc); _p0 or _p1 != 0; unknown flags; a zero width or height; radius outside 1 .. 3;
+ * clip_sigma NaN or < 0; clip_history NaN or < 1; out overlapping color; misaligned device planes), RT_ERR_CAPACITY
+ * (width * height > 2^31 - 1, or more texels than the image has with a NULL color), RT_ERR_OUT_OF_MEMORY.  No scene is
+ * needed.  Like rt_upsample the call leaves the image (unless `out` is in it), the primary tables, a frame_ahead batch in
+ * flight, the pipeline slots, rt_get_stats and the launch words of rt_last_launch as they are. */
+typedef struct rt_rectify_desc {
+    uint32_t        struct_bytes;      /* = sizeof(rt_rectify_desc) */
+    uint32_t        _p0;               /* must be 0 */
+    uint32_t        width, height;
+    uint32_t        radius;            /* 1, 2 or 3: the window is (2 r + 1)^2 texels */
+    float           clip_sigma;        /* >= 0, +INF allowed (no clipping): the box's half-width in standard deviations */
+    float           clip_history;      /* >= 1, +INF allowed (no cut): the history length a clipped texel keeps at most */
+    uint32_t        _p1;               /* must be 0 */
+    const float*    color;             /* [h][w][4] this frame's sample; device path: NULL = the handle's image */
+    const float*    history;           /* [h][w][4] the reprojected history */
+    const float*    history_length;    /* [h][w] its length */
+    const uint32_t* object;            /* [h][w] or NULL: the G-buffer's object word */
+    const float*    moments;           /* [h][w][4] or NULL: this frame's luminance moments */
+    const float*    history_moments;   /* [h][w][4] or NULL: the reprojected moments */
+    float*          out;               /* [h][w][4] */
+    float*          out_history;       /* [h][w] */
+    float*          out_moments;       /* [h][w][4] or NULL */
+    uint8_t*        out_clipped;       /* [h][w] or NULL: 0 = no history, 1 = kept, 2 = clipped */
+} rt_rectify_desc;
+enum { RT_RECTIFY_HOST_MEMORY = 1 };
+int rt_temporal_rectify(rt_handle* h, const rt_rectify_desc* desc, int flags);
+/* The definition above in executable form: plain C++ over host pointers, no device, no working memory.  `color` is
+ * required.  The same argument errors as rt_temporal_rectify (no handle, no flags, no alignment rule), nothing written on
+ * an error, the reason in rt_last_error(NULL). */
+int rt_temporal_rectify_host(const rt_rectify_desc* desc);
 
 #ifdef __cplusplus
 }

@@ -18,5 +18,6 @@ from ._abi import (CameraUniform, Material, MeshUniform, Node, PackedTriangle, P
                    SceneUniform, Sphere, make_params)
 from .lib import LIB_PATH, RtError, load, load_test  # noqa: F401
 from .ray_tracer import (RayTracer, adaptive_merge_host, adaptive_plan_host, auto_exposure_host, denoise_host, display_host, denoise_variance_host, luminance_moments_host, pixel_seeds,  # noqa: F401
-                         object_motions, read_multi_frame, render_multi, temporal_accumulate_host, upsample_host)
+                         object_motions, read_multi_frame, render_multi, temporal_accumulate_host, temporal_rectify_host,
+                         temporal_reproject_host, upsample_host)
 from .scene import Scene, SceneArrays, material, transform  # noqa: F401

@@ -210,6 +210,20 @@ UPSAMPLE_HOST_MEMORY = 1
 UPSAMPLE_RING1, UPSAMPLE_RING2, UPSAMPLE_HOLE = 2, 1, 0   # the bytes of `coverage`
 
 
+class RectifyDesc(C.Structure):  # rt_rectify_desc: a frame, its reprojected history and the clipping rule for rt_temporal_rectify / rt_temporal_rectify_host
+    _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("radius", u32), ("clip_sigma", f32),
+                ("clip_history", f32), ("_p1", u32), ("color", C.c_void_p), ("history", C.c_void_p), ("history_length", C.c_void_p),
+                ("object", C.c_void_p), ("moments", C.c_void_p), ("history_moments", C.c_void_p), ("out", C.c_void_p),
+                ("out_history", C.c_void_p), ("out_moments", C.c_void_p), ("out_clipped", C.c_void_p)]
+
+
+RECTIFY_PLANES = {"color": ("<f4", 4), "history": ("<f4", 4), "history_length": ("<f4", 0), "object": ("<u4", 0),
+                  "moments": ("<f4", 4), "history_moments": ("<f4", 4), "out": ("<f4", 4), "out_history": ("<f4", 0),
+                  "out_moments": ("<f4", 4), "out_clipped": ("u1", 0)}
+RECTIFY_HOST_MEMORY = 1
+RECTIFY_NO_HISTORY, RECTIFY_KEPT, RECTIFY_CLIPPED = 0, 1, 2   # the bytes of `out_clipped`
+
+
 class DisplayDesc(C.Structure):  # rt_display_desc: a frame and how it becomes four bytes per texel, for rt_display / rt_display_host / rt_snapshot_display
     _fields_ = [("struct_bytes", u32), ("_p0", u32), ("width", u32), ("height", u32), ("tone", u32), ("transfer", u32), ("layout", u32),
                 ("_p1", u32), ("exposure", f32), ("white", f32), ("color", C.c_void_p), ("exposure_scale", C.c_void_p), ("out", C.c_void_p)]

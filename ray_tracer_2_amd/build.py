@@ -14,11 +14,11 @@ PRODUCT_SO = os.path.join(ROOT, "ray_tracer_2_amd", "librt2_mi355x.so")
 ORACLE_SO = os.path.join(ROOT, "oracle", "_build", "librt_oracle.so")
 
 PRODUCT_SOURCES = [
-    "rt_kernel.hip", "rt_api.hip", "rt_api_queries.hip", "rt_api_frames.hip", "rt_api_test.hip", "rt_bvh_search.hip", "rt_refit.hip", "rt_denoise.hip", "rt_temporal.hip", "rt_vdenoise.hip", "rt_adaptive.hip", "rt_upsample.hip", "rt_display.hip", "host/obj_loader.cpp", "host/bvh.cpp", "host/scene.cpp", "host/scene_pack.cpp",
-    "host/launch_options.cpp", "host/launch_state_entries.cpp", "host/png_decode.cpp", "host/scene_capi.cpp", "host/denoise.cpp", "host/temporal.cpp", "host/object_motions.cpp", "host/vdenoise.cpp", "host/adaptive.cpp", "host/upsample.cpp", "host/display.cpp", "host/ray_tracer.cpp",
+    "rt_kernel.hip", "rt_api.hip", "rt_api_queries.hip", "rt_api_frames.hip", "rt_api_test.hip", "rt_bvh_search.hip", "rt_refit.hip", "rt_denoise.hip", "rt_temporal.hip", "rt_vdenoise.hip", "rt_adaptive.hip", "rt_upsample.hip", "rt_rectify.hip", "rt_display.hip", "host/obj_loader.cpp", "host/bvh.cpp", "host/scene.cpp", "host/scene_pack.cpp",
+    "host/launch_options.cpp", "host/launch_state_entries.cpp", "host/png_decode.cpp", "host/scene_capi.cpp", "host/denoise.cpp", "host/temporal.cpp", "host/object_motions.cpp", "host/vdenoise.cpp", "host/adaptive.cpp", "host/upsample.cpp", "host/rectify.cpp", "host/display.cpp", "host/ray_tracer.cpp",
 ]
 PRODUCT_HEADERS = [
-    "rt_queries.inl", "rt_test_kernels.inl", "rt_transc.h", "rt_texture.h", "rt_srgb_lut.h", "rt_device.h", "rt_handle.h", "rt_scene_format.h", "rt_rccl.h", "rt_refit.h", "rt_denoise.h", "rt_denoise_api.h", "rt_temporal.h", "rt_temporal_api.h", "rt_vdenoise.h", "rt_vdenoise_api.h", "rt_adaptive.h", "rt_adaptive_api.h", "rt_upsample.h", "rt_upsample_api.h", "rt_display.h", "rt_display_api.h", "rt_srgb_encode_lut.h", "host/glam_math.h",
+    "rt_queries.inl", "rt_test_kernels.inl", "rt_transc.h", "rt_texture.h", "rt_srgb_lut.h", "rt_device.h", "rt_handle.h", "rt_scene_format.h", "rt_rccl.h", "rt_refit.h", "rt_denoise.h", "rt_denoise_api.h", "rt_temporal.h", "rt_temporal_api.h", "rt_vdenoise.h", "rt_vdenoise_api.h", "rt_adaptive.h", "rt_adaptive_api.h", "rt_upsample.h", "rt_upsample_api.h", "rt_rectify.h", "rt_rectify_api.h", "rt_display.h", "rt_display_api.h", "rt_srgb_encode_lut.h", "host/glam_math.h",
     "host/obj_loader.h", "host/bvh.h", "host/scene.h", "host/scene_pack.h", "host/launch_options.h", "host/launch_state.h", "host/plane_check.h", "host/ray_tracer.hpp",
     "../../include/rt_abi.h", "../../include/rt_test_abi.h", "experiments/rt_wavefront.inl", "experiments/rt_wavefront_launch.inl", "experiments/rt_api_wavefront.inl", "experiments/rt_api_hybrid_blob.inl",
 ]

@@ -1,6 +1,6 @@
 // rt_api_frames.hip -- the calls of include/rt_abi.h that work on a rendered frame and launch no render kernel: the
-// denoisers, adaptive sampling, temporal accumulation, guided upsampling, the display pass and the exposure meter, each with
-// its _host restatement.  A unit of the device-side C ABI over rt_handle.h; rt_api.hip has the handle's lifecycle and the
+// denoisers, adaptive sampling, temporal accumulation, history rectification, guided upsampling, the display pass and the
+// exposure meter, each with its _host restatement.  A unit of the device-side C ABI over rt_handle.h; rt_api.hip has the handle's lifecycle and the
 // render path.
 #include <new>
 #include <string>
@@ -10,6 +10,7 @@
 #include "rt_upsample_api.h"  // (guided upsampling: its argument rules and host restatement, host/upsample.cpp; its launch, rt_upsample.hip)
 #include "rt_display_api.h"  // (the display pass and the exposure meter: their argument rules and host restatements, host/display.cpp; their launches, rt_display.hip)
 #include "rt_temporal_api.h"  // (temporal accumulation: its argument rules and host restatement, host/temporal.cpp; its launch, rt_temporal.hip)
+#include "rt_rectify_api.h"  // (history rectification: its argument rules and host restatement, host/rectify.cpp; its launch, rt_rectify.hip)
 #include "rt_vdenoise_api.h"  // (the variance-guided denoiser: its argument rules and host restatement, host/vdenoise.cpp; its launches, rt_vdenoise.hip)
 #include "rt_adaptive_api.h"  // (adaptive sampling: its argument rules and host restatement, host/adaptive.cpp; its launches, rt_adaptive.hip)
 
@@ -17,7 +18,7 @@ extern "C" {
 
 // ---- the passes over a rendered frame: rt_denoise, rt_denoise_variance / rt_luminance_moments, rt_adaptive_plan /
 // rt_adaptive_merge, rt_temporal_accumulate / rt_temporal_accumulate_moving / rt_temporal_accumulate_deforming, rt_upsample,
-// rt_display, rt_auto_exposure ----
+// rt_display, rt_auto_exposure, rt_temporal_rectify ----
 // Launched like a query: nothing read but the caller's planes (or the image) and nothing written but the caller's outputs
 // and a scratch the handle keeps.  Each entry point lists its planes once, in a table of FramePlane, and fills its launch
 // arguments from the two pointer arrays frame_call gives it: the caller's own pointers on device memory, addresses in one
@@ -138,6 +139,7 @@ int rt_adaptive_merge_host(const rt_adaptive_merge_desc* desc) { return host_cal
 int rt_temporal_accumulate_host(const rt_temporal_desc* desc) { return host_call(rt2::temporal_host, desc); }
 int rt_temporal_accumulate_moving_host(const rt_temporal_motion_desc* desc) { return host_call(rt2::temporal_motion_host, desc); }
 int rt_temporal_accumulate_deforming_host(const rt_temporal_deform_desc* desc) { return host_call(rt2::temporal_deform_host, desc); }
+int rt_temporal_rectify_host(const rt_rectify_desc* desc) { return host_call(rt2::rectify_host, desc); }
 int rt_upsample_host(const rt_upsample_desc* desc) { return host_call(rt2::upsample_host, desc); }
 int rt_display_host(const rt_display_desc* desc) { return host_call(rt2::display_host, desc); }
 int rt_auto_exposure_host(const rt_auto_exposure_desc* desc) { return host_call(rt2::auto_exposure_host, desc); }
@@ -325,6 +327,38 @@ static int temporal_accumulate(rt_handle* h, const void* desc, rt2::TemporalKind
 int rt_temporal_accumulate(rt_handle* h, const rt_temporal_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::PLAIN, flags); }
 int rt_temporal_accumulate_moving(rt_handle* h, const rt_temporal_motion_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::MOVING, flags); }
 int rt_temporal_accumulate_deforming(rt_handle* h, const rt_temporal_deform_desc* desc, int flags) { return temporal_accumulate(h, desc, rt2::TemporalKind::DEFORMING, flags); }
+
+// ---- history rectification (include/rt_abi.h: rt_temporal_rectify; rt_rectify.hip; host/rectify.cpp) ----
+// No scratch is kept.  out, out_history and out_moments take the places of history, history_length and history_moments in
+// the staging buffer.  A NULL color names the image read-only: `out` inside the texels the pass reads is refused like an
+// `out` that overlaps the caller's own color.
+int rt_temporal_rectify(rt_handle* h, const rt_rectify_desc* desc, int flags) {
+    if (!h) return fail(h, RT_ERR_INVALID_ARGUMENT, "null handle");
+    if (flags & ~RT_RECTIFY_HOST_MEMORY) return fail(h, RT_ERR_INVALID_ARGUMENT, "unknown flags");
+    const bool host = (flags & RT_RECTIFY_HOST_MEMORY) != 0;
+    std::string err;
+    if (const int rc = rt2::rectify_check(desc, true, host, err); rc != RT_OK) return fail(h, rc, err);
+    const size_t texels = (size_t)desc->width * desc->height;
+    const float* color = desc->color;
+    if (int rc = frame_color(h, color, texels); rc != RT_OK) return rc;
+    if (!desc->color && rt2::rectify_overlap(desc->out, color, texels))
+        return fail(h, RT_ERR_INVALID_ARGUMENT, "out overlaps the image, which color = NULL names and the neighbouring texels read");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = host ? RT_OK : image_access(h, color, desc->out); rc != RT_OK) return rc;
+    const FramePlane planes[7] = {{color, nullptr, texels * 16u}, {desc->history, desc->out, texels * 16u},
+                                  {desc->history_length, desc->out_history, texels * 4u}, {desc->object, nullptr, texels * 4u},
+                                  {desc->moments, nullptr, texels * 16u}, {desc->history_moments, desc->out_moments, texels * 16u},
+                                  {nullptr, desc->out_clipped, texels}};
+    RectifyArgs a{};
+    a.call = rt2::rectify_call(*desc);
+    return frame_call(h, host, planes, "the staging planes of history rectification", "launch_rectify", [&](const void* const* in, void* const* out) {
+        a.color = (const float*)in[0]; a.history = (const float*)in[1]; a.out = (float*)out[1];
+        a.history_length = (const float*)in[2]; a.out_history = (float*)out[2]; a.object = (const uint32_t*)in[3];
+        a.moments = (const float*)in[4]; a.history_moments = (const float*)in[5]; a.out_moments = (float*)out[5];
+        a.out_clipped = (uint8_t*)out[6];
+        return launch_rectify(a, h->stream);
+    });
+}
 
 // ---- guided upsampling (include/rt_abi.h: rt_upsample; rt_upsample.hip; host/upsample.cpp) ----
 // No scratch is kept.  The low frame's planes are inputs that are not frame-shaped with respect to the high frame: rows of

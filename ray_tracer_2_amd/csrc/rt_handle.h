@@ -31,6 +31,7 @@ struct VDenoiseArgs;
 struct AdaptivePlanArgs;
 struct AdaptiveMergeArgs;
 struct UpsampleArgs;
+struct RectifyArgs;
 struct DisplayArgs;
 struct AutoExposureArgs;
 }  // namespace rtd
@@ -65,6 +66,7 @@ hipError_t launch_luminance_moments(const VDenoiseArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs& a, hipStream_t stream);
 hipError_t launch_adaptive_merge(const AdaptiveMergeArgs& a, hipStream_t stream);
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t stream);
+hipError_t launch_rectify(const RectifyArgs& a, hipStream_t stream);
 hipError_t launch_display(const DisplayArgs& a, hipStream_t stream);
 hipError_t launch_auto_exposure(const AutoExposureArgs& a, hipStream_t stream);
 hipError_t launch_assemble(const float4* gathered, float4* image, uint32_t width, uint32_t height,

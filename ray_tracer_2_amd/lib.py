@@ -34,7 +34,7 @@ EXPORTS = [
     "rt_temporal_accumulate_deforming", "rt_temporal_accumulate_deforming_host", "rt_object_motions_deforming",
     "rt_denoise_variance", "rt_luminance_moments", "rt_denoise_variance_host", "rt_luminance_moments_host",
     "rt_adaptive_plan", "rt_adaptive_merge", "rt_adaptive_plan_host", "rt_adaptive_merge_host",
-    "rt_upsample", "rt_upsample_host",
+    "rt_upsample", "rt_upsample_host", "rt_temporal_rectify", "rt_temporal_rectify_host",
     "rt_display", "rt_display_host", "rt_auto_exposure", "rt_auto_exposure_host", "rt_snapshot_display", "rt_read_display_snapshot",
     "rt_update_instances", "rt_update_built_scene", "rt_scene_set_mesh_transform", "rt_scene_set_mesh_material",
     "rt_scene_set_sphere",
@@ -172,6 +172,8 @@ def _bind(L, with_test_entries):
         "rt_adaptive_merge_host": (i32, [P(A.AdaptiveMergeDesc)]),
         "rt_upsample": (i32, [vp, P(A.UpsampleDesc), i32]),
         "rt_upsample_host": (i32, [P(A.UpsampleDesc)]),
+        "rt_temporal_rectify": (i32, [vp, P(A.RectifyDesc), i32]),
+        "rt_temporal_rectify_host": (i32, [P(A.RectifyDesc)]),
         "rt_display": (i32, [vp, P(A.DisplayDesc), i32]),
         "rt_display_host": (i32, [P(A.DisplayDesc)]),
         "rt_auto_exposure": (i32, [vp, P(A.AutoExposureDesc), i32]),

@@ -332,6 +332,67 @@ def upsample_host(lo_guides, guides, color, point_tolerance=UPSAMPLE_POINT_TOLER
     return _upsample_result(_host_frame_call("rt_upsample_host", d, table, W, H, planes, {"out": _new_or(out), "coverage": coverage}))
 
 
+# ---- history rectification (RayTracer.temporal_reproject, .temporal_rectify; temporal_reproject_host, temporal_rectify_host) ----
+# The defaults: a 7 x 7 window -- at 8 samples per pixel a 3 x 3 one is too few samples for a standard deviation, and the
+# box then clips a converged history into noise --, a box of one standard deviation of a single frame's noise either way,
+# which a converged history (noise / sqrt(n) off the mean) stays inside, and four frames kept of a clipped history.
+# DESIGN.md section 2.20 has what the quality test measured with them.
+RECTIFY_RADIUS, RECTIFY_CLIP_SIGMA, RECTIFY_CLIP_HISTORY = 3, 1.0, 4.0
+
+
+def _nan_plane(guides):
+    """The (H, W, 4) float32 plane of quiet NaNs that stands for `color` in a reprojection."""
+    if "normal" not in guides:
+        raise ValueError("guides must hold the normal and point planes of render_gbuffer")
+    W, H = _frame_size(guides["normal"])
+    return np.full((H, W, 4), np.nan, np.float32)
+
+
+def temporal_reproject_host(guides, prev_guides, prev_camera, prev_color, prev_history, max_history=float("inf"),
+                            point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
+                            motion=False, motions=None, prev_triangles=None, tri_first=0):
+    """The reprojected history alone, on the CPU: temporal_accumulate_host with a plane of quiet NaNs for `color`, which it
+    drops -- `out` is prev_color fetched from where each texel lay (NaN where there is no history), out_history the
+    fetched, capped history length (1 there).  What temporal_rectify_host takes as history / history_length."""
+    return temporal_accumulate_host(guides, prev_guides, prev_camera, prev_color, prev_history, _nan_plane(guides), max_history,
+                                    point_tolerance, normal_cos, out, out_history, motion, motions, prev_triangles, tri_first)
+
+
+def _rectify_call(color, history, history_length, object, radius, clip_sigma, clip_history, moments, history_moments, out, out_history,
+                  out_moments, clipped):
+    """rt_temporal_rectify's desc, the inputs and the outputs by name and the frame's size."""
+    if (moments is None) != (history_moments is None):
+        raise ValueError("moments and history_moments come together or not at all")
+    if moments is None and out_moments is not None:
+        raise ValueError("out_moments needs moments and history_moments")
+    planes = {"history": history, "history_length": history_length}
+    for k, v in (("color", color), ("object", object), ("moments", moments), ("history_moments", history_moments)):
+        if v is not None:
+            planes[k] = v
+    W, H = _frame_size(history)
+    d = A.RectifyDesc(struct_bytes=C.sizeof(A.RectifyDesc), width=W, height=H, radius=int(radius), clip_sigma=float(clip_sigma),
+                      clip_history=float(clip_history))
+    outs = {"out": _new_or(out), "out_history": _new_or(out_history),
+            "out_moments": None if moments is None else _new_or(out_moments), "out_clipped": clipped}
+    return d, planes, outs, W, H
+
+
+def _rectify_result(res):
+    return tuple(res[k] for k in ("out", "out_history", "out_moments", "out_clipped") if res[k] is not None)
+
+
+def temporal_rectify_host(color, history, history_length, object=None, radius=RECTIFY_RADIUS, clip_sigma=RECTIFY_CLIP_SIGMA,
+                          clip_history=RECTIFY_CLIP_HISTORY, moments=None, history_moments=None, out=None, out_history=None,
+                          out_moments=None, clipped=False):
+    """rt_temporal_rectify_host: history rectification's definition on the CPU (no device), with RayTracer.temporal_rectify's
+    arguments for numpy planes.  RayTracer.temporal_rectify computes the same bits on the GPU."""
+    if color is None:
+        raise ValueError("color is required on the host")
+    d, planes, outs, W, H = _rectify_call(color, history, history_length, object, radius, clip_sigma, clip_history, moments,
+                                          history_moments, out, out_history, out_moments, clipped)
+    return _rectify_result(_host_frame_call("rt_temporal_rectify_host", d, A.RECTIFY_PLANES, W, H, planes, outs))
+
+
 # ---- display frames (RayTracer.display, .auto_exposure, .snapshot_display; display_host, auto_exposure_host) ----
 _DISPLAY_TONES = {"clamp": A.DISPLAY_TONE_CLAMP, "reinhard": A.DISPLAY_TONE_REINHARD}
 _DISPLAY_TRANSFERS = {"srgb": A.DISPLAY_SRGB, "linear": A.DISPLAY_LINEAR}
@@ -1056,7 +1117,8 @@ class RayTracer:
         meshes or spheres moved between the two frames -- `guides` must then hold `object`.  A moved object's texels fetch
         the history of their own surface point, and `motion` is what the camera and the object produce together; an object
         the table marks as still is worked as without a table.  What is kept is the object's own history, not the lighting
-        that changed around it: `max_history` bounds how long that lags.  A second call with the luminance moments as
+        that changed around it: `max_history` bounds how long that lags, and temporal_reproject + temporal_rectify cut the
+        history where the new frame contradicts it.  A second call with the luminance moments as
         color / prev_color and the same `motions` accumulates the moments denoise_variance takes for a moving object, as it
         does for a moving camera.
         `prev_triangles`, `tri_first` (rt_temporal_accumulate_deforming): for a mesh whose vertices moved between the two
@@ -1073,6 +1135,52 @@ class RayTracer:
                                                     point_tolerance, normal_cos, motions, prev_triangles, tri_first)
         outs = {"out": _new_or(out), "out_history": _new_or(out_history), "motion": motion}
         return _temporal_result(self._frame_call(fn, A.TEMPORAL_HOST_MEMORY, d, table, W, H, planes, outs))
+
+    def temporal_reproject(self, guides, prev_guides, prev_camera, prev_color, prev_history, max_history=float("inf"),
+                           point_tolerance=TEMPORAL_POINT_TOLERANCE, normal_cos=TEMPORAL_NORMAL_COS, out=None, out_history=None,
+                           motion=False, motions=None, prev_triangles=None, tri_first=0):
+        """The reprojected history alone: temporal_accumulate (any of its three forms) with a plane of quiet NaNs for `color`,
+        which the call drops -- `out` is prev_color fetched from where each texel lay under prev_camera (NaN where there is
+        no history), out_history the fetched, capped history length (1 there).  What temporal_rectify takes as history /
+        history_length; the luminance moments go through a call of their own, as with temporal_accumulate.
+        numpy planes or torch tensors on this handle's device, as temporal_accumulate; for tensors the NaN plane is one
+        tensor per frame size that the handle keeps."""
+        given = (prev_color, prev_history, out, out_history, motion, *guides.values(), *prev_guides.values())
+        if any(hasattr(v, "data_ptr") for v in given):
+            import torch
+            W, H = _frame_size(guides["normal"])
+            cache = self.__dict__.setdefault("_nan_planes", {})
+            if (H, W) not in cache:
+                cache[(H, W)] = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device=torch.device("cuda", self.device))
+            color = cache[(H, W)]
+        else:
+            color = _nan_plane(guides)
+        return self.temporal_accumulate(guides, prev_guides, prev_camera, prev_color, prev_history, color, max_history, point_tolerance,
+                                        normal_cos, out, out_history, motion, motions, prev_triangles, tri_first)
+
+    def temporal_rectify(self, color, history, history_length, object=None, radius=RECTIFY_RADIUS, clip_sigma=RECTIFY_CLIP_SIGMA,
+                         clip_history=RECTIFY_CLIP_HISTORY, moments=None, history_moments=None, out=None, out_history=None,
+                         out_moments=None, clipped=False):
+        """History rectification (rt_temporal_rectify; include/rt_abi.h has the definition): temporal_accumulate's blend with
+        variance clipping in front, for lighting that changes.  `history` (H, W, 4) / `history_length` (H, W) are what
+        temporal_reproject returned for this frame, `color` (H, W, 4) the frame itself.  Each texel's history is clamped,
+        per colour channel, into mean +- `clip_sigma` standard deviations of the colours of `color` in the (2 radius + 1)^2
+        window around it (`radius` 1 .. 3; with `object`, the G-buffer's (H, W) object words, only the window's texels of
+        the texel's own object), and a texel that was clamped keeps at most `clip_history` frames of its history; then the
+        frame is blended in at 1 / (length + 1).  clip_sigma=inf is temporal_accumulate itself, bit for bit.
+        `moments` / `history_moments` (H, W, 4; both or neither): this frame's luminance_moments and their reprojection,
+        blended with the texel's weight, never clipped.
+        Returns (out, out_history), then out_moments with the moments, then with clipped=True (or an (H, W) uint8 array /
+        tensor to fill) the plane that says 0 = no history, 1 = kept, 2 = clipped.  out may be history, out_history
+        history_length and out_moments history_moments; out must not be color.
+        What it cannot see: a change that stays inside the new frame's noise -- a lamp that gets brighter widens the box
+        with its own noise.
+        numpy planes: a synchronous call that returns numpy.  Torch tensors on this handle's device: an asynchronous call
+        ordered after the current torch stream's work, as render_gbuffer(device=True) orders itself; returns tensors; there
+        color=None takes the handle's image as the frame (read only: out must not be the image)."""
+        d, planes, outs, W, H = _rectify_call(color, history, history_length, object, radius, clip_sigma, clip_history, moments,
+                                              history_moments, out, out_history, out_moments, clipped)
+        return _rectify_result(self._frame_call("rt_temporal_rectify", A.RECTIFY_HOST_MEMORY, d, A.RECTIFY_PLANES, W, H, planes, outs))
 
     def upsample(self, lo_guides, guides, color=None, point_tolerance=UPSAMPLE_POINT_TOLERANCE, normal_cos=UPSAMPLE_NORMAL_COS,
                  out=None, coverage=False):

@@ -305,6 +305,11 @@ DEV uint32_t fbits(float f) { return __float_as_uint(f); }
 #ifndef RT_TERMINAL_SKIP
 #define RT_TERMINAL_SKIP 1
 #endif
+// The single scatter pass of the FIXED persistent kernels (single_start, single_settle, single_scatter below; DESIGN.md
+// section 4.2); -DRT_SINGLE_SCATTER=0 gives them path_step's loop body back.
+#ifndef RT_SINGLE_SCATTER
+#define RT_SINGLE_SCATTER 1
+#endif
 #ifndef RT_TOP_BRANCH
 #define RT_TOP_BRANCH 1
 #endif
@@ -2132,6 +2137,171 @@ DEV bool roulette_skip(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_
     return s.j >= rpp;
 }
 
+// ---------------------------------------------------------------------------
+// The single scatter pass (RT_SINGLE_SCATTER; the FIXED persistent kernels only: the memo in LDS, a complete table,
+// roulette skip, fast miss, skybox and samples are constants there, and there are no counters and no parking).
+// path_step scatters twice per iteration -- the pre-step's path_end for the lanes that start a sample at their memoised
+// primary hit, and path_end again behind the traversal -- and most lanes of the second pass end their path there: all
+// such a lane needs is light += emitted * T, the RNG 8 steps on and total += light.  Moved half an iteration, every
+// lane scatters once: the FIXED kernels' loop body is
+//   traverse      every lane that holds a ray (no vote: nothing is left to wait for);
+//   single_settle the lanes that traversed: the segment is counted, a miss takes the sky's light, a hit its emitted light,
+//                 and whether the path ends at the hit is decided the way roulette_skip and path_terminal decide it --
+//                 path_end's float operations on path_end's operands, the two draws read ahead of the generator.  A lane
+//                 whose path ends is fresh again; one whose path goes on keeps its Hit, and its RNG untouched;
+//   finish / take a pixel whose last sample has ended (pixel_finish, the tile cost, the group's next frame), new pixels;
+//   single_start  the fresh lanes: the roulette_skip loop, then the survivor takes the memo's hit as its Hit (a memoised
+//                 miss ends the pixel: path_end's FAST_MISS);
+//   single_scatter every lane that holds a Hit, from either side: path_end's hit branch behind the emitted light.
+// Per lane the float operations and the RNG draws are path_step's, in path_step's order; which iteration of its wave a
+// lane performs them in is scheduling.  The Hit lives from the traversal's end to the scatter, never across the traversal
+// or the loop's back edge.
+// ---------------------------------------------------------------------------
+[[maybe_unused]] DEV void count_rays(PixelState& s, uint32_t n) {  // (PixelState::meta's ray count saturates)
+    const uint32_t rays = (s.meta & 0xffffu) + n;
+    s.meta = (s.meta & 0xffff0000u) | (rays < 0xffffu ? rays : 0xffffu);
+}
+[[maybe_unused]] DEV f4 lane_total(const uint32_t* ls) {
+    return f4{__uint_as_float(ls[0]), __uint_as_float(ls[64]), __uint_as_float(ls[128]), __uint_as_float(ls[192])};
+}
+[[maybe_unused]] DEV void lane_total_store(uint32_t* ls, f4 t) {
+    ls[0] = __float_as_uint(t.x); ls[64] = __float_as_uint(t.y); ls[128] = __float_as_uint(t.z); ls[192] = __float_as_uint(t.w);
+}
+
+// The lane has traversed its segment.  s.fresh afterwards: the path ended here (the sample is added to the pixel's sum).
+[[maybe_unused]] DEV void single_settle(const RenderArgs& a, PixelState& s, uint32_t* ls, const Hit& hit, uint32_t& n_segments) {
+    n_segments += 1;
+    count_rays(s, 1u);
+    bool end_path = true;
+    if (!hit.hit) {
+        s.light = s.light + s.T * environment_light(s.rd);
+    } else {
+        const uint32_t mo = hit.mat_off;
+        const float4 msc = ld4<true>(a, mo + M_ABSORB_S);  // (absorb_s, emission_s, smoothness, specular)
+        const float4 ec = ld4<true>(a, mo + M_EMISSION);
+        const float4 cc = ld4<true>(a, mo + M_COLOR);
+        const float4 sc = ld4<true>(a, mo + M_SPECCOL);
+        const float es = msc.y;
+        const f4 emitted{ec.x * es, ec.y * es, ec.z * es, ec.w * es};
+        s.light = s.light + emitted * s.T;
+        uint32_t rng = s.rng;
+        const bool is_spec = msc.w >= rand_(rng);
+        const f4 T = s.T * (is_spec ? f4{sc.x, sc.y, sc.z, sc.w} : f4{cc.x, cc.y, cc.z, cc.w});
+        const float p = max_(T.x, max_(T.y, T.z));
+        // (is_spec, 6 of rand_unit_sphere, the roulette's own: path_terminal's count)
+        const uint32_t rng8 = rng_jump<8>(s.rng);
+        const bool die = (float)rng_output(rng8) * 0x1p-32f >= p;  // (rand_'s conversion)
+        end_path = die || s.seg + 1 > a.params.number_of_bounces;
+        if (end_path) s.rng = rng8;
+    }
+    if (end_path) {  // wgsl:496
+        lane_total_store(ls, lane_total(ls) + s.light);
+        s.j += 1;
+        s.fresh = true;
+    }
+}
+
+// A fresh lane with samples to go.  START_HIT: the sample goes on from its memoised primary hit (`hit`); START_RAY: the
+// pixel has no memoised hit (a -0 in its ray) and the lane holds the sample's primary ray; START_ENDED: the pixel's last
+// sample ended here.
+enum : uint32_t { START_HIT = 0, START_RAY = 1, START_ENDED = 2 };
+[[maybe_unused]] DEV uint32_t single_start(const RenderArgs& a, PixelState& s, uint32_t* ls, Hit& hit, uint32_t& n_segments, uint32_t& more_reused) {
+    const int32_t nb = a.params.number_of_bounces, rpp = a.params.rays_per_pixel;
+    typedef __attribute__((address_space(3))) uint32_t* LdsPtr;
+    const LdsPtr pc = (LdsPtr)(ls - PIXEL_MEMO_DWORDS * 64u);  // (with_memo: the memo in LDS)
+    const uint32_t st = pc[12 * 64];
+    if (nb < 0) {  // no segments at all: a sample is its four draws (path_begin's STEP_END)
+        f4 t = lane_total(ls);
+        for (; s.j < rpp; ++s.j) {
+            s.rng = rng_jump<4>(s.rng);
+            t = t + f4{0, 0, 0, 0};
+        }
+        lane_total_store(ls, t);
+        return START_ENDED;
+    }
+    if ((st & (MEMO_RAY | MEMO_HIT_VALID)) != (MEMO_RAY | MEMO_HIT_VALID)) {
+        uint32_t starve = 0u;
+        (void)path_begin<false, true>(a, s, ls, starve);  // (its fresh branch: the sample's ray)
+        return START_RAY;
+    }
+    s.rd = f3{__uint_as_float(pc[0]), __uint_as_float(pc[64]), __uint_as_float(pc[128])};
+    if ((st & MEMO_HIT) == 0u) {
+        // path_end's FAST_MISS: this sample and every one behind it are the same segment
+        const f4 light = f4{0, 0, 0, 0} + f4{1, 1, 1, 1} * environment_light(s.rd);
+        const uint32_t n = (uint32_t)(rpp - s.j);
+        f4 t = lane_total(ls);
+        for (uint32_t k = 0; k < n; ++k) t = t + light;
+        lane_total_store(ls, t);
+        s.j = rpp;
+        n_segments += n;
+        more_reused += n;
+        count_rays(s, n);
+        return START_ENDED;
+    }
+    // roulette_skip, and with no bounce to go every sample ends at this hit whatever its roulette says
+    const uint32_t mo = st & ~15u;  // (memo_hit_load)
+    const float4 msc = ld4<true>(a, mo + M_ABSORB_S);  // (absorb_s, emission_s, smoothness, specular)
+    const float4 ec = ld4<true>(a, mo + M_EMISSION);
+    const float4 cc = ld4<true>(a, mo + M_COLOR);
+    const float4 sc = ld4<true>(a, mo + M_SPECCOL);
+    const float es = msc.y;
+    const f4 one{1, 1, 1, 1};
+    const f4 emitted{ec.x * es, ec.y * es, ec.z * es, ec.w * es};
+    const f4 L0 = f4{0, 0, 0, 0} + emitted * one;  // s.light + emitted * T
+    const f4 Tc = one * f4{cc.x, cc.y, cc.z, cc.w}, Ts = one * f4{sc.x, sc.y, sc.z, sc.w};
+    const float p_diffuse = max_(Tc.x, max_(Tc.y, Tc.z)), p_spec = max_(Ts.x, max_(Ts.y, Ts.z));
+    uint32_t rng = s.rng, dead = 0u;
+    f4 t = lane_total(ls);
+    while (s.j + (int32_t)dead < rpp) {
+        const bool is_spec = msc.w >= (float)rng_output(rng_jump<5>(rng)) * 0x1p-32f;  // (rand_'s conversion)
+        const float p = is_spec ? p_spec : p_diffuse;
+        const uint32_t rng12 = rng_jump<12>(rng);
+        if (nb >= 1 && !((float)rng_output(rng12) * 0x1p-32f >= p)) break;  // it survives
+        t = t + L0;  // total += incoming_light
+        rng = rng12;
+        dead += 1u;
+    }
+    if (dead != 0u) {
+        lane_total_store(ls, t);
+        s.rng = rng;
+        s.j += (int32_t)dead;
+    }
+    const uint32_t n = dead + (s.j < rpp ? 1u : 0u);  // the survivor's primary segment too: served from the memo
+    n_segments += n;
+    more_reused += n;
+    count_rays(s, n);
+    if (s.j >= rpp) return START_ENDED;
+    s.rng = rng_jump<4>(s.rng);  // (the two disks' four draws: path_begin)
+    s.T = one;
+    s.light = L0;
+    s.seg = 0;
+    s.fresh = false;
+    hit.hit = true;
+    hit.point = f3{__uint_as_float(pc[4 * 64]), __uint_as_float(pc[5 * 64]), __uint_as_float(pc[6 * 64])};
+    hit.normal = f3{__uint_as_float(pc[7 * 64]), __uint_as_float(pc[8 * 64]), __uint_as_float(pc[9 * 64])};
+    hit.mat_off = mo;
+    return START_HIT;
+}
+
+// path_end's hit branch behind `light += emitted * T`, for a lane whose path is known to go on
+[[maybe_unused]] DEV void single_scatter(const RenderArgs& a, PixelState& s, const Hit& hit) {
+    const uint32_t mo = hit.mat_off;
+    const float4 msc = ld4<true>(a, mo + M_ABSORB_S);  // (absorb_s, emission_s, smoothness, specular)
+    const bool is_spec = msc.w >= rand_(s.rng);
+    const f3 sph = rand_unit_sphere<false>(s.rng);
+    const f3 diffuse_dir = sph * sign_(dot3(hit.normal, sph));
+    const f3 specular_dir = reflect3(s.rd, hit.normal);
+    s.rd = normalize3<false>(mix3(diffuse_dir, specular_dir, msc.z * (is_spec ? 1.0f : 0.0f)));
+    s.ro = hit.point;
+    const float4 cc = ld4<true>(a, mo + M_COLOR);
+    const float4 sc = ld4<true>(a, mo + M_SPECCOL);
+    const f4 T = s.T * (is_spec ? f4{sc.x, sc.y, sc.z, sc.w} : f4{cc.x, cc.y, cc.z, cc.w});
+    const float p = max_(T.x, max_(T.y, T.z));  // wgsl:462-466
+    (void)next_random_number(s.rng);  // (the roulette's draw: the path goes on)
+    s.T = T * rcp_(p);
+    s.seg += 1;
+}
+
 // returns PATH_CONTINUE, PATH_PIXEL_DONE (the pixel's last sample ended) or PATH_PARK (the pixel was parked in front
 // of the deferred mesh, RenderArgs::park)
 enum : uint32_t { PATH_CONTINUE = 0, PATH_PIXEL_DONE = 1, PATH_PARK = 2 };
@@ -2174,6 +2344,7 @@ DEV uint32_t path_step(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_
                 mh.suspended = false;
                 memo_hit_load<false, !LDS>(a, s, ls, mh);
                 reused_pre = true;
+                DIAG(35);
                 if (path_end<LDS, total_in_lds(LDS), SIMPLE, true>(a, s, ls, STEP_REUSE, mh, n_segments, &more_reused)) return PATH_PIXEL_DONE;
             }
         }
@@ -2246,6 +2417,14 @@ DEV uint32_t path_step(const RenderArgs& a, PixelState& s, uint32_t* ls, uint32_
         memo_hit_store<STATS, false, !LDS>(a, s, ls, hit);
         TOC(t22, 22);
     }
+#if defined(RT_DIAG)
+    if (mode != STEP_END) {  // the census of the second scatter pass: its lanes, and those whose path ends in it
+        DIAG(36);
+        const bool done = path_end<LDS, total_in_lds(LDS), SIMPLE, !STATS>(a, s, ls, mode, hit, n_segments, &more_reused);
+        if (s.fresh) DIAG(37);
+        return done ? PATH_PIXEL_DONE : PATH_CONTINUE;
+    }
+#endif
     return path_end<LDS, total_in_lds(LDS), SIMPLE, !STATS>(a, s, ls, mode, hit, n_segments, &more_reused) ? PATH_PIXEL_DONE : PATH_CONTINUE;
 }
 
@@ -2442,6 +2621,8 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_tiles_k
 // inlines see a constant wherever they read a switch; the other instantiations never call it and are what they were.
 // GROUPS: the batch's own switches too -- the ungrouped kernel runs single frames, pipelined frames and ungrouped batches,
 // and keeps those three as the launch has them.
+// SINGLE (FIXED with RT_SINGLE_SCATTER): the FIXED kernels' own loop body -- traverse and settle in front of the refill, start
+// and scatter behind it (single_settle, single_start, single_scatter above) -- in place of path_step's.
 template <bool GROUPS>
 DEV void fix_switches(RenderArgs& a) {
     using F = rt2::FixedSwitches;
@@ -2511,7 +2692,45 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
     uint32_t pull_seq = 0;
     uint32_t resume_slot = 0xffffffffu;  // (PARK) the park record this lane's pixel was just resumed from
 
+    // (the single scatter pass: the FIXED kernels' own loop body around the refill)
+    constexpr bool SINGLE = FIXED && RT_SINGLE_SCATTER != 0;
+
     for (;;) {
+        [[maybe_unused]] Hit hit;       // (SINGLE) the hit a lane scatters at in this iteration
+        [[maybe_unused]] bool scatter = false;
+        if constexpr (SINGLE) {
+            if (active && !s.fresh) {  // the lane holds a ray
+                DIAG(0);
+                Isect I;
+                if constexpr (RT_TERMINAL_SKIP != 0 && !RT_EXPERIMENTS) {
+                    if (path_terminal(a, s.seg, s.rng, s.T)) s.seg |= (int32_t)PATH_TERMINAL;  // (seg >= 0: the bit is free)
+                    hit = intersect_scene<LDS, STATS, TLAS, PARK, SIMPLE, HYB, false, false, true>(
+                        a, s.ro, s.rd, stack_of<total_in_lds(LDS)>(ls), node_tests, tri_tests, I, INF, false, (uint32_t)s.seg);
+                    s.seg &= (int32_t)~PATH_TERMINAL;
+                } else
+                    hit = intersect_scene<LDS, STATS, TLAS, PARK, SIMPLE, HYB>(a, s.ro, s.rd, stack_of<total_in_lds(LDS)>(ls), node_tests, tri_tests, I);
+                memo_hit_store<STATS, false, !LDS>(a, s, ls, hit);
+                single_settle(a, s, ls, hit, n_segments);
+                scatter = !s.fresh;
+            }
+            if (active && s.fresh && s.j >= a.params.rays_per_pixel) {
+                // the pixel's last sample has ended, here or in the last iteration's start step: what PATH_PIXEL_DONE does below
+                DIAG(16);
+                pixel_finish<total_in_lds(LDS), GROUPS>(cold_args(), s, ls);
+                if (a.tile_cost && meta_batch_frame<GROUPS>(s.meta) == 0u) tile_cost_add(a, cost_tbl, s);
+                active = false;
+                if constexpr (GROUPS) {
+                    if ((s.meta >> META_FRAMES_LEFT_SHIFT) != 0u) {  // (frame group: the same pixel's next frame, on this lane)
+                        const uint32_t carried = (s.meta & 0xffff0000u) + META_NEXT_FRAME;
+                        pixel_begin<total_in_lds(LDS)>(a, camera_consts(a), s, ls, s.x, frame_row_of(a, s.out_row), s.out_row,
+                                                       meta_batch_frame<true>(carried));
+                        memo_next_frame(a, ls);
+                        s.meta = carried;
+                        active = true;
+                    }
+                }
+            }
+        }
         const unsigned long long idle = __ballot(!active);
         TIC(t14);
         if (idle != 0ull && !exhausted) {
@@ -2627,6 +2846,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS, RT_MIN_WAVES) rt_render_persist
         TOC(t14, 14);
         if (__ballot(active) == 0ull) {
             if (exhausted) break;
+            continue;
+        }
+        if constexpr (SINGLE) {
+            // (a pixel whose last sample ends in the start step is finished in front of the next iteration's refill)
+            if (active && s.fresh) scatter = single_start(a, s, ls, hit, n_segments, more_reused) == START_HIT;
+            if (scatter) single_scatter(a, s, hit);
             continue;
         }
         TIC(t15);

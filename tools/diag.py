@@ -19,7 +19,8 @@ SECTIONS = {0: "iteration (path_step)", 1: "sample start (ray gen)", 3: "mesh tr
             8: "bvh-leaf tri: det", 9: "bvh-leaf tri: body", 10: "mesh hit -> world", 11: "winner finalize",
             12: "miss: sky", 13: "shade: diffuse", 14: "shade: glass", 15: "refill: pixel_begin",
             16: "pixel_finish", 28: "vote: nobody wants", 29: "vote: run, all want", 30: "vote: run, some reuse", 31: "vote: wait", 32: "roulette skip: dead sample", 17: "top tree: node (2 aabb)", 18: "top tree: mesh entry", 19: "shared walk: loop trip",
-            33: "forest: lanes entering", 34: "forest: taken out (terminal)"}
+            33: "forest: lanes entering", 34: "forest: taken out (terminal)",
+            35: "scatter: pre-step", 36: "scatter: after traversal", 37: "  of those: path ends there"}
 # DIAG_NOTERM=1: the census of a build without the terminal skip (-DRT_TERMINAL_SKIP=0), for the node passes before / after
 NOTERM = os.environ.get("DIAG_NOTERM") == "1"
 if NOTERM:
